@@ -12,7 +12,9 @@ BASELINE config the chosen flags are (or says "custom").
 `python bench.py --gpus N` with N > 1 and no torch.distributed environment starts its own
 `python -m torch.distributed.run --nproc-per-node N` child (before anything touches a GPU) and relays its JSON line.
 
-Prints ONE JSON line (rank 0). Objects besides the contract's fields:
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times exactly --steps steps and reports the headline (`value`,
+`ms_per_step`, the workload in `config`); --dump-outputs DIR also writes what the last timed step computed (dump_outputs). Everything
+below is measured only with --full (the --no-* options trim that run). Objects besides the contract's fields:
   roofline      k_read_stats, the kernel that streams the signal (dispatch time stamps on the library's stream)
   whole_step    SURVEY 8(d)'s algorithmic bytes of the COMPLETE step over the step time
   useful        which of the streamed samples the reference would have read at all: it stops at the read that completes
@@ -111,6 +113,9 @@ def main():
     ap.add_argument("--overlap", action="store_true", help="statistics of a batch on a second stream (PG_FLAG_OVERLAP; the library's default since round 3 wherever it applies)")
     ap.add_argument("--one-stream", action="store_true", help="every kernel of a batch on one stream (PG_FLAG_ONE_STREAM): round 2's default")
     ap.add_argument("--homopolymer-frac", type=float, default=None, help="share of reads with a 40-base homopolymer run (default: 0.1 for dna_r10 = SURVEY 8d cfg 3, else 0)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: two more timed blocks, per-kernel times and the roofline, useful samples, "
+                    "the lazy / one-stream / configs[2] / configs[3] / ragged / end-to-end modes, the job layer and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the last step's result arrays as DIR/<name>.npy (float64, under 64 MB in all)")
     ap.add_argument("--job-layer-child", type=int, default=0, help=argparse.SUPPRESS)  # internal: run the pg_job_* step over this many devices and print its JSON object
     args = ap.parse_args()
     if args.job_layer_child:
@@ -276,8 +281,39 @@ def main():
         tot, use = sum(x["samples"] for x in per_rank), sum(x["useful_samples"] for x in per_rank)
         return {"all_kmers_complete": full, "samples": tot, "useful_samples": use, "useful_fraction": use / tot if tot else None, "per_rank": per_rank}
 
-    eng, ms_per_step, enqueue_ms, state = timed(p, args.steps, args.warmup, extra_blocks=2)
+    eng, ms_per_step, enqueue_ms, state = timed(p, args.steps, args.warmup, extra_blocks=2 if args.full else 0)
     value = world * n_samples / (ms_per_step * 1e-3)
+    out = {
+        "metric": "signal samples/sec aggregated into k-mer buckets", "value": value, "unit": "samples/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup + args.pre_warm, "pre_warm_steps": args.pre_warm, "ms_per_step": ms_per_step,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int16 in / f64 arithmetic",
+        "data": "synthetic",
+        "config": {
+            "workload": workload_label(args.kind, args.reads, args.read_len, args.k, args.sample_limit, world),
+            "reads_per_gpu": args.reads, "samples_per_gpu": n_samples, "ss_ops_per_gpu": n_ops, "n_slots": len(kmers),
+            "stats_mode": "lazy" if args.lazy else "every read (as the reference)", "parallelism": f"read-shard x{world}",
+            "collective": ("all_gather of u64[n_slots] accepted counts per step over " + ("RCCL/xGMI" if backend == "nccl" else backend)) if dist_step else None,
+            "statistics_placement": ("behind the issue of the all_gather, on the chain's stream (pg_stats, --defer)" if defer else "queued by pg_count on the second stream, as at N=1") if dist_step else None,
+            "homopolymer_frac": hp_frac,
+        },
+        "host_enqueue_ms_per_step": enqueue_ms,
+        "gen_seconds": gen_s,
+    }
+
+    def emit():
+        if rank == 0:
+            sys.stdout.flush()
+            os.dup2(real_stdout, 1)  # the ONE line of the contract on the real stdout
+            print(json.dumps(out), flush=True)
+        if dist_step:
+            dist.destroy_process_group()
+
+    if not args.full:
+        if args.dump_outputs:
+            dump_outputs(eng.finish(), args.dump_outputs, rank, world)
+        eng.close()
+        return emit()
+
     all_blocks = sorted([ms_per_step] + state["extra_blocks_ms"])
     useful = useful_of(eng, state, args.sample_limit)
 
@@ -400,19 +436,8 @@ def main():
                       "results_equal_two_streams": bool(same)}
         ts.close()
 
-    out = {
-        "metric": "signal samples/sec aggregated into k-mer buckets", "value": value, "unit": "samples/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup + args.pre_warm, "pre_warm_steps": args.pre_warm, "ms_per_step": ms_per_step,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int16 in / f64 arithmetic",
-        "data": "synthetic",
-        "config": {
-            "workload": workload_label(args.kind, args.reads, args.read_len, args.k, args.sample_limit, world),
-            "reads_per_gpu": args.reads, "samples_per_gpu": n_samples, "ss_ops_per_gpu": n_ops, "n_slots": len(kmers),
-            "stats_mode": "lazy" if args.lazy else "every read (as the reference)", "parallelism": f"read-shard x{world}",
-            "collective": ("all_gather of u64[n_slots] accepted counts per step over " + ("RCCL/xGMI" if backend == "nccl" else backend)) if dist_step else None,
-            "statistics_placement": ("behind the issue of the all_gather, on the chain's stream (pg_stats, --defer)" if defer else "queued by pg_count on the second stream, as at N=1") if dist_step else None,
-            "kept_events_rank0": kept_events, "kept_samples_rank0": kept_samples, "homopolymer_frac": hp_frac,
-        },
+    out["config"].update(kept_events_rank0=kept_events, kept_samples_rank0=kept_samples)
+    out.update({
         "ms_per_step_blocks": {"contract_block": ms_per_step, "min": all_blocks[0], "median": all_blocks[len(all_blocks) // 2], "max": all_blocks[-1], "steps_per_block": args.steps,
                                "note": "value / ms_per_step are the first block (exactly --steps timed steps behind exactly `warmup` untimed ones); two more blocks of the same length follow it: the settled figure"},
         "roofline": roofline,
@@ -420,13 +445,13 @@ def main():
         "whole_step_frac": whole_step["frac"],
         "useful": useful,
         "kernels_ms_per_step": kernels_ms,
-        "host_enqueue_ms_per_step": enqueue_ms,
         "lazy_statistics_mode": lazy_info,
         "streams": ("two: statistics of the next batch on a stream of their own (3/4 of every XCD's CUs)" if two_streams_on else "one"),
         "one_stream_mode": one_stream,
         "kmer_model_once_per_job": model_info,
-        "gen_seconds": gen_s,
-    }
+    })
+    if args.dump_outputs:
+        dump_outputs(eng.finish(), args.dump_outputs, rank, world)
     eng.close()
 
     extras = not args.no_extras and not args.force_dist
@@ -453,12 +478,27 @@ def main():
         out["extras_seconds"] = time.time() - t0
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(host, kmers, p, args.cpu_seconds)
-    if rank == 0:
-        sys.stdout.flush()
-        os.dup2(real_stdout, 1)  # the ONE line of the contract on the real stdout
-        print(json.dumps(out), flush=True)
-    if dist_step:
-        dist.destroy_process_group()
+    emit()
+
+
+DUMP_BYTES = 60 * 10**6  # array data of --dump-outputs: below 64 MB with the .npy headers
+
+
+def dump_outputs(res, d, rank, world):
+    """What a caller of the timed path receives from its last step (GmoveEngine.finish(): engine.Result's arrays) as DIR/<name>.npy in
+    float64 (the integers are exact there), prefixed rank<r>_ at N > 1. Past DUMP_BYTES in all, an array is cut to a sample of
+    positions drawn with a fixed seed, sorted: the same positions for the same length, so two builds still compare element for element."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    arrays = sorted(((f, getattr(res, f)) for f in ("counts", "ev_off", "ev_len", "ev_read", "samp_off", "samples", "read_skipped")), key=lambda x: x[1].size)
+    left = DUMP_BYTES // world // 8  # float64 elements this rank may write
+    for i, (name, a) in enumerate(arrays):
+        m = min(a.size, left // (len(arrays) - i))  # smallest first: what a small array leaves goes to the larger ones
+        if m < a.size:
+            a = a[np.sort(np.random.default_rng(20251003).choice(a.size, m, replace=False))]
+        np.save(os.path.join(d, prefix + name + ".npy"), a.astype(np.float64))
+        left -= m
 
 
 def mode_run(shard, host, kmers, q, what, steps=10):
@@ -797,7 +837,7 @@ def live_traffic(args, timeout_s=90):
     try:
         kb = {}
         for name in ("FETCH_SIZE", "WRITE_SIZE"):
-            cmd = [exe, "--pmc", name, "--output-format", "csv", "-d", os.path.join(d, name), "--", sys.executable, os.path.abspath(__file__), "--steps", "2", "--warmup", "1",
+            cmd = [exe, "--pmc", name, "--output-format", "csv", "-d", os.path.join(d, name), "--", sys.executable, os.path.abspath(__file__), "--full", "--steps", "2", "--warmup", "1",
                    "--one-stream", "--no-cpu-baseline", "--no-lazy-extra", "--no-extras", "--reads", str(args.reads), "--read-len", str(args.read_len), "--kind", args.kind,
                    "--k", str(args.k), "--sample-limit", str(args.sample_limit)] + (["--lib", args.lib] if args.lib else [])
             env = dict(os.environ, TMPDIR="/tmp")

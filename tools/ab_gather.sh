@@ -3,7 +3,7 @@
 set -o pipefail
 tag=$1; shift
 out=gpurun_out/$tag; mkdir -p $out
-common="--no-cpu-baseline --no-lazy-extra --no-extras --steps 10 --warmup 3 --one-stream"
+common="--full --no-cpu-baseline --no-lazy-extra --no-extras --steps 10 --warmup 3 --one-stream"
 run() { # name, env, lib
   for wl in "k9:--kind dna_r10 --k 9 --sample-limit 1000" "l5000:--sample-limit 5000"; do
     n=${wl%%:*}; a=${wl#*:}

@@ -3,7 +3,7 @@
 set -o pipefail
 tag=$1; reps=$2; shift 2
 out=gpurun_out/$tag; mkdir -p $out
-common="--no-cpu-baseline --no-lazy-extra --no-extras --steps 20 --warmup 3 --one-stream --kind dna_r10 --k 9 --sample-limit 1000"
+common="--full --no-cpu-baseline --no-lazy-extra --no-extras --steps 20 --warmup 3 --one-stream --kind dna_r10 --k 9 --sample-limit 1000"
 for rep in $(seq 1 $reps); do for v in "$@"; do
   lib=""; [ $v != default ] && lib="--lib build/$v/libpgmove.so"
   timeout -k 10 300 python3 bench.py $common $lib > $out/k9_${v}_$rep.json 2> $out/k9_${v}_$rep.err || { tail -5 $out/k9_${v}_$rep.err; exit 1; }

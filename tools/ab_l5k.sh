@@ -2,7 +2,7 @@
 # sample_limit 5000, one stream, wall per step only (no profile differences): several builds / environments interleaved, 3 reps
 set -o pipefail
 out=gpurun_out/$1; shift; mkdir -p $out
-common="--no-cpu-baseline --no-lazy-extra --no-extras --steps 40 --warmup 3 --one-stream --sample-limit 5000"
+common="--full --no-cpu-baseline --no-lazy-extra --no-extras --steps 40 --warmup 3 --one-stream --sample-limit 5000"
 for rep in 1 2 3 4; do for v in "$@"; do
   lib=""; envs="PG_X=1"
   case $v in

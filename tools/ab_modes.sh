@@ -3,7 +3,7 @@
 set -o pipefail
 tag=$1; shift
 out=gpurun_out/$tag; mkdir -p $out
-common="--no-cpu-baseline --no-lazy-extra --no-extras --steps 20 --warmup 3"
+common="--full --no-cpu-baseline --no-lazy-extra --no-extras --steps 20 --warmup 3"
 for v in "$@"; do
   lib=""; [ $v != default ] && lib="--lib build/$v/libpgmove.so"
   timeout -k 10 300 python3 bench.py $common --kind dna_r10 --k 9 --sample-limit 1000 $lib > $out/${v}_k9.json 2> $out/${v}_k9.err || { tail -5 $out/${v}_k9.err; exit 1; }

@@ -3,7 +3,7 @@
 set -o pipefail
 tag=$1; shift
 out=gpurun_out/$tag; mkdir -p $out
-common="--no-cpu-baseline --no-lazy-extra --no-extras --steps 20 --warmup 3 --one-stream"
+common="--full --no-cpu-baseline --no-lazy-extra --no-extras --steps 20 --warmup 3 --one-stream"
 for rep in 1 2; do for v in "$@"; do
   lib=""; [ $v != default ] && lib="--lib build/$v/libpgmove.so"
   timeout -k 10 300 python3 bench.py $common --sample-limit 5000 $lib > $out/l5000_${v}_$rep.json 2> $out/l5000_${v}_$rep.err || { tail -5 $out/l5000_${v}_$rep.err; exit 1; }

@@ -7,7 +7,7 @@ tag=$1; reps=$2; shift 2
 out=gpurun_out/$tag; mkdir -p $out
 for rep in $(seq 1 $reps); do for c in "$@"; do
   IFS=: read -r name lib envs extra <<< "$c"
-  flags="--no-cpu-baseline --no-lazy-extra --no-extras --steps 40 --warmup 10"
+  flags="--full --no-cpu-baseline --no-lazy-extra --no-extras --steps 40 --warmup 10"
   case $name in
     l5k*) flags="$flags --sample-limit 5000";;
     k9*)  flags="$flags --steps 20 --kind dna_r10 --k 9 --sample-limit 1000";;

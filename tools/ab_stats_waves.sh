@@ -1,5 +1,5 @@
 # k_read_stats compiled for 7 waves per SIMD against the library (bash tools/variants.sh sw7 "-DPG_STATS_WAVES_PER_EU=7" first), C1 both stream modes, three passes
-C="--no-cpu-baseline --no-lazy-extra --no-extras --steps 20 --warmup 3"
+C="--full --no-cpu-baseline --no-lazy-extra --no-extras --steps 20 --warmup 3"
 for r in 1 2 3; do for v in base sw7; do
   L=""; [ $v != base ] && L="--lib build/$v/libpgmove.so"
   for m in "" "--one-stream"; do

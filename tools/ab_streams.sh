@@ -2,7 +2,7 @@
 # one stream against the default two streams, per workload, alternating on one box. usage: bash tools/ab_streams.sh <tag>
 set -o pipefail
 tag=$1; out=gpurun_out/$tag; mkdir -p $out
-common="--no-cpu-baseline --no-lazy-extra --no-extras --steps 20 --warmup 3"
+common="--full --no-cpu-baseline --no-lazy-extra --no-extras --steps 20 --warmup 3"
 for rep in 1 2; do
   for m in "c1:" "k9:--kind dna_r10 --k 9 --sample-limit 1000" "l5000:--sample-limit 5000"; do
     name=${m%%:*}; flags=${m#*:}

@@ -1,6 +1,6 @@
 #!/bin/bash
 # the statistics stream's CU mask (PGMOVE_STATS_CU_WITHHELD: CUs it may NOT use; default a quarter = 64) on the three workloads, one box
-C="--no-cpu-baseline --no-lazy-extra --no-extras --steps 20 --warmup 3"
+C="--full --no-cpu-baseline --no-lazy-extra --no-extras --steps 20 --warmup 3"
 for w in 64 32 96 128 160 0; do
   for wl in "c1:" "k9:--kind dna_r10 --k 9 --sample-limit 1000" "l5000:--sample-limit 5000"; do
     n=${wl%%:*}; a=${wl#*:}

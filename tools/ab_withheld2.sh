@@ -1,6 +1,6 @@
 #!/bin/bash
 # repeated A/B of the statistics stream's CU mask (process-to-process spread is a few per cent): bash tools/ab_withheld2.sh "64 128 160" 3
-C="--no-cpu-baseline --no-lazy-extra --no-extras --steps 20 --warmup 3"
+C="--full --no-cpu-baseline --no-lazy-extra --no-extras --steps 20 --warmup 3"
 vals=${1:-"64 128 160"}; reps=${2:-3}
 for r in $(seq 1 $reps); do
   for w in $vals; do

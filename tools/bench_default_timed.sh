@@ -2,7 +2,7 @@
 # the driver's command, timed on the wall clock: bash tools/bench_default_timed.sh <tag>
 tag=${1:-bd}; out=gpurun_out/$tag; mkdir -p $out
 t0=$(date +%s.%N)
-python bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
+python bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
 t1=$(date +%s.%N)
 python3 - $out $t0 $t1 <<'PY'
 import json, sys

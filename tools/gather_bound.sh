@@ -7,7 +7,7 @@ set -o pipefail
 tag=$1; shift
 out=gpurun_out/$tag; mkdir -p $out
 R=$PWD; cd /tmp && export TMPDIR=/tmp && cd $R
-common="--no-cpu-baseline --no-lazy-extra --no-extras --steps 10 --warmup 3 --one-stream --kind dna_r10 --k 9 --sample-limit 1000"
+common="--full --no-cpu-baseline --no-lazy-extra --no-extras --steps 10 --warmup 3 --one-stream --kind dna_r10 --k 9 --sample-limit 1000"
 for v in default gc_nr gc_ns gc_nrnd gc_nsnd "$@"; do
   lib=""; [ $v != default ] && lib="--lib build/$v/libpgmove.so"
   [ $v != default ] && [ ! -f build/$v/libpgmove.so ] && continue
@@ -24,7 +24,7 @@ PY
 cat $out/summary.txt
 for pass in "TCC_HIT_sum TCC_MISS_sum TCC_EA0_WRREQ_sum TCC_EA0_RDREQ_sum" "TCP_PENDING_STALL_CYCLES_sum TA_BUSY_avr TA_TA_BUSY_sum GRBM_GUI_ACTIVE" "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INST_CYCLES_VMEM_WR SQ_INST_CYCLES_VMEM_RD SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY"; do
   t=$(echo $pass | cut -d' ' -f1)
-  timeout -k 10 300 rocprofv3 --pmc $pass --output-format csv -d $out/pmc_$t -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-lazy-extra --no-extras --one-stream --kind dna_r10 --k 9 --sample-limit 1000 > /dev/null 2> $out/pmc_$t.err || { echo "PMC pass $t FAILED" >> $out/summary.txt; tail -3 $out/pmc_$t.err >> $out/summary.txt; }
+  timeout -k 10 300 rocprofv3 --pmc $pass --output-format csv -d $out/pmc_$t -- python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-lazy-extra --no-extras --one-stream --kind dna_r10 --k 9 --sample-limit 1000 > /dev/null 2> $out/pmc_$t.err || { echo "PMC pass $t FAILED" >> $out/summary.txt; tail -3 $out/pmc_$t.err >> $out/summary.txt; }
 done
 python3 - $out >> $out/summary.txt <<'PY'
 import csv, glob, collections, sys

@@ -9,7 +9,7 @@ set -o pipefail
 tag=$1; shift
 out=gpurun_out/$tag; mkdir -p $out
 R=$PWD; cd /tmp && export TMPDIR=/tmp && cd $R
-common="--no-cpu-baseline --no-lazy-extra --no-extras"
+common="--full --no-cpu-baseline --no-lazy-extra --no-extras"
 python3 bench.py --steps 20 --warmup 3 $common "$@" > $out/bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
 rocprofv3 --kernel-trace --stats -d $out/trace -o trace -- python3 bench.py --steps 10 --warmup 2 --one-stream $common "$@" > $out/trace_bench.json 2> $out/trace.err || { tail -5 $out/trace.err; exit 1; }
 for pass in FETCH_SIZE WRITE_SIZE; do

@@ -1,7 +1,7 @@
 #!/bin/bash
 # how many CUs to withhold from the statistics stream in the default two-stream mode (PGMOVE_STATS_CU_WITHHELD), per workload, one box
 out=gpurun_out/${1:-cusweep}; mkdir -p $out
-common="--no-cpu-baseline --no-lazy-extra --no-extras --steps 30 --warmup 3"
+common="--full --no-cpu-baseline --no-lazy-extra --no-extras --steps 30 --warmup 3"
 for w in 64 32 48 80 96 128 64; do
   for m in "c1:" "l5000:--sample-limit 5000"; do
     name=${m%%:*}; flags=${m#*:}

@@ -2,7 +2,7 @@
 # kernel trace of bench.py in two-stream mode (PG_FLAG_OVERLAP): per-dispatch start / end and queue, for a timeline of the two streams
 out=${1:-gpurun_out/tl}; mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --output-format csv -d $out/trace -o tl -- python3 bench.py --overlap --steps 12 --warmup 3 --no-cpu-baseline --no-lazy-extra --no-extras > $out/bench.json 2> $out/trace.err || { tail -5 $out/trace.err; exit 1; }
+rocprofv3 --kernel-trace --output-format csv -d $out/trace -o tl -- python3 bench.py --overlap --steps 12 --warmup 3 --full --no-cpu-baseline --no-lazy-extra --no-extras > $out/bench.json 2> $out/trace.err || { tail -5 $out/trace.err; exit 1; }
 f=$(find $out/trace -name "*kernel_trace.csv" | head -1)
 python3 - "$f" > $out/timeline.txt <<'PY'
 import csv, sys

@@ -4,7 +4,7 @@
 set -o pipefail
 tag=$1; shift
 out=gpurun_out/$tag; mkdir -p $out
-common="--no-cpu-baseline --no-lazy-extra --no-extras --steps 20 --warmup 3"
+common="--full --no-cpu-baseline --no-lazy-extra --no-extras --steps 20 --warmup 3"
 timeout -k 10 300 python3 bench.py $common "$@" > $out/c1.json 2> $out/c1.err || { tail -5 $out/c1.err; exit 1; }
 timeout -k 10 300 python3 bench.py $common --kind dna_r10 --k 9 --sample-limit 1000 "$@" > $out/k9.json 2> $out/k9.err || { tail -5 $out/k9.err; exit 1; }
 timeout -k 10 300 python3 bench.py $common --sample-limit 5000 "$@" > $out/l5000.json 2> $out/l5000.err || { tail -5 $out/l5000.err; exit 1; }

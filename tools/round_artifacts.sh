@@ -13,12 +13,12 @@ if [ "$2" != "nopytest" ]; then
   timeout -k 10 900 python -m pytest tests -x -q -m gpu > $out/pytest_gpu.txt 2>&1 || { tail -20 $out/pytest_gpu.txt; exit 1; }
   tail -2 $out/pytest_gpu.txt
 fi
-python3 bench.py > $out/bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
-rocprofv3 --kernel-trace --stats -d $out/trace -o trace -- python3 bench.py --steps 10 --warmup 2 --one-stream --no-cpu-baseline --no-lazy-extra --no-extras > $out/trace_bench.json 2> $out/trace.err || { tail -5 $out/trace.err; exit 1; }
+python3 bench.py --full > $out/bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
+rocprofv3 --kernel-trace --stats -d $out/trace -o trace -- python3 bench.py --steps 10 --warmup 2 --one-stream --full --no-cpu-baseline --no-lazy-extra --no-extras > $out/trace_bench.json 2> $out/trace.err || { tail -5 $out/trace.err; exit 1; }
 # the same trace of the DEFAULT command (two streams): what a driver-side trace of `python bench.py` sees; kernels that share the chip take longer there
-rocprofv3 --kernel-trace --stats -d $out/trace2 -o trace -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-lazy-extra --no-extras > $out/trace2_bench.json 2> $out/trace2.err || { tail -5 $out/trace2.err; exit 1; }
+rocprofv3 --kernel-trace --stats -d $out/trace2 -o trace -- python3 bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-lazy-extra --no-extras > $out/trace2_bench.json 2> $out/trace2.err || { tail -5 $out/trace2.err; exit 1; }
 for pass in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $pass --output-format csv -d $out/pmc_$pass -- python3 bench.py --steps 2 --warmup 1 --one-stream --no-cpu-baseline --no-lazy-extra --no-extras > /dev/null 2> $out/pmc_$pass.err || { tail -5 $out/pmc_$pass.err; exit 1; }
+  rocprofv3 --pmc $pass --output-format csv -d $out/pmc_$pass -- python3 bench.py --steps 2 --warmup 1 --one-stream --full --no-cpu-baseline --no-lazy-extra --no-extras > /dev/null 2> $out/pmc_$pass.err || { tail -5 $out/pmc_$pass.err; exit 1; }
 done
 python3 - "$out" <<'PY'
 import csv, glob, collections, json, sqlite3, sys
