@@ -440,6 +440,37 @@ class GmoveEngine:
         self._check(self._lib.pg_text(self._h, C.byref(t)))
         return _text_slots(self, t, self._lib.pg_fetch_text)
 
+    def text_device_offsets(self, counts, ev_len, samples) -> np.ndarray:
+        """pg_text_device over torch CUDA tensors in model_device's layout (counts int64[n_slots], ev_len int32/uint32[n_events],
+        samples float64[]): produces the text on the device and returns slot_off (uint64[n_slots + 1]; slot s is bytes
+        [slot_off[s], slot_off[s+1]) of fetch_text, slot_off[-1] the total). The text stays valid until the context's next text call."""
+        import torch
+        ev_off = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=counts.device)
+        ev_off[1:] = torch.cumsum(counts.to(torch.int64), 0)
+        samp_off = torch.zeros(ev_len.numel() + 1, dtype=torch.int64, device=counts.device)
+        samp_off[1:] = torch.cumsum(ev_len.to(torch.int64), 0)
+        samples = samples.contiguous()
+        assert samples.dtype == torch.float64 and int(samp_off[-1]) == samples.numel() and int(ev_off[-1]) == ev_len.numel()
+        torch.cuda.current_stream(counts.device).synchronize()   # the library launches on its own stream
+        t = _abi.PgTextResult()
+        self._check(self._lib.pg_text_device(self._h, counts.numel(), ev_len.numel(), ev_off.data_ptr(), samp_off.data_ptr(),
+                                             samples.data_ptr() or None, C.byref(t)))
+        off = np.ctypeslib.as_array(t.slot_off, shape=(t.n_slots + 1,)).copy()
+        assert int(off[-1]) == int(t.n_bytes)
+        return off
+
+    def fetch_text(self, first: int, n: int) -> bytes:
+        """bytes [first, first + n) of the context's last text (pg_fetch_text)"""
+        buf = C.create_string_buffer(n + 1)
+        self._check(self._lib.pg_fetch_text(self._h, first, n, buf))
+        return buf.raw[:n]
+
+    def text_device(self, counts, ev_len, samples) -> List[bytes]:
+        """The dump files' text of device arrays (text_device_offsets): one bytes object per slot."""
+        off = self.text_device_offsets(counts, ev_len, samples)
+        raw = self.fetch_text(0, int(off[-1]))
+        return [raw[int(off[s]):int(off[s + 1])] for s in range(off.size - 1)]
+
     def finish_deferred(self, piece: int = 1 << 20) -> Result:
         """pg_finish_deferred + pg_fetch_samples: the same Result as finish(), the samples fetched from the device `piece` at a time."""
         r = _abi.PgResult()

@@ -2,6 +2,7 @@
 import numpy as np
 
 import orc
+from poregen_amd import synth
 from poregen_amd.engine import GmoveParams, generate_kmers
 
 
@@ -36,3 +37,14 @@ def assert_result_equals_oracle(res, o, check_text_slots=8, delimit=False, sampl
     if delimit:  # empty slots still receive ':' per processed read
         for s in range(min(o.n_slots, 4)):
             assert res.slot_text(s, delimit=True, sample_limit=sample_limit) == o.text(s)
+
+
+def dyadic_batch(n_reads, kind, seed):
+    """A synthetic batch re-calibrated to range 1023 / digitisation 4096 (a dyadic scale, 1023 * 2^-12): raw re-derived so that the pA
+    values stay where they were. One pA value in 16 then sits exactly on a tie at the 8th decimal."""
+    b = synth.make_batch(n_reads, kind=kind, seed=seed, indel_rate=0.01)
+    L = np.diff(b.sig_off.astype(np.int64))
+    pa = (b.sig.astype(np.float64) + np.repeat(b.offset, L)) * np.repeat(b.range / b.digitisation, L)
+    b.range = np.full(n_reads, 1023.0); b.digitisation = np.full(n_reads, 4096.0)
+    b.sig = np.clip(np.rint(pa / (1023.0 / 4096.0) - np.repeat(b.offset, L)), -32768, 32767).astype(np.int16)
+    return b

@@ -102,6 +102,41 @@ def test_synthetic_files_equal_oracle(tmp_path, kind, extra):
     assert_same_dirs(tmp_path / "gpu", tmp_path / "cpu")
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("scaling", ["0", "1"])
+def test_dyadic_calibration_text_equals_printf(tmp_path, scaling):
+    """range 1023 / digitisation 4096: exact ties at the 8th decimal reach the dump files. The device text (and the host formatter,
+    POREGEN_HOST_TEXT=1) against the oracle CLI's glibc printf, byte for byte."""
+    from helpers import dyadic_batch
+    b = dyadic_batch(200, "rna004", 909)
+    pre = str(tmp_path / "syn")
+    synth.write_files(b, pre)
+    common = [pre + ".slow5", pre + ".paf", "--fastq", pre + ".fastq", "-k", "5", "--rna", "--scaling", scaling, "--min_dur", "10",
+              "--max_dur", "60", "--file_limit", "1024", "--sample_limit", "30"]
+    o = oracle_cli(common + [tmp_path / "cpu"]); assert o.returncode == 0, o.stderr
+    r = cli(common + [tmp_path / "gpu"]); assert r.returncode == 0, r.stderr
+    assert_same_dirs(tmp_path / "gpu", tmp_path / "cpu")
+    r = cli(common + [tmp_path / "host"], env=dict(os.environ, POREGEN_HOST_TEXT="1")); assert r.returncode == 0, r.stderr
+    assert_same_dirs(tmp_path / "host", tmp_path / "cpu")
+
+
+@pytest.mark.gpu
+def test_pa_beyond_the_device_text_falls_back_to_the_host(tmp_path):
+    """pA values around 1e8 (range x 1e6, the pA window opened wide): the device text refuses them (|x| >= 4e7), the CLI formats on the
+    host instead, exits 0 and writes what the oracle writes."""
+    b = synth.make_batch(40, kind="dna_r10", seed=9)
+    b.range = b.range * 1e6
+    pre = str(tmp_path / "big")
+    synth.write_files(b, pre)
+    common = [pre + ".slow5", pre + ".paf", "--fastq", pre + ".fastq", "-k", "5", "--file_limit", "1024", "--sample_limit", "5",
+              "--pa_min", "-1e300", "--pa_max", "1e300"]
+    o = oracle_cli(common + [tmp_path / "cpu"]); assert o.returncode == 0, o.stderr
+    r = cli(common + [tmp_path / "gpu"]); assert r.returncode == 0, r.stderr
+    assert_same_dirs(tmp_path / "gpu", tmp_path / "cpu")
+    dump = tmp_path / "cpu" / "dump"
+    assert any(abs(float(x)) >= 4e7 for f in dump.iterdir() for x in f.read_text().replace(";", ",").split(",") if x)
+
+
 TABLE_CASES = {
     "t02_defaults": ["{G}/reads.slow5", "{G}/guppy_move", "--file_limit", "50", "{OUT}"],                                         # test_gmove.sh 0.2
     "t04_kmer_file": ["-k", "6", "-m", "0", "{G}/reads.slow5", "{G}/guppy_move", "--kmer_file", "{G}/kmer_file.txt", "{OUT}"],   # 0.4 / 2.1

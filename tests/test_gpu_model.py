@@ -305,3 +305,153 @@ def test_model_one_wave_kernel_on_constructed_files():
             dw = sorted([int(x) - 1 for x in l] + [0])
             assert int(got.dwell_n[s]) == len(dw) and float(got.dwell_median[s]) == (dw[(len(dw) - 1) // 2] + dw[len(dw) // 2]) / 2.0, s
     eng.close()
+
+
+def _model_dev(eng, files, keep_first=True):
+    """model_device over files given as (values, event lengths)"""
+    import torch
+    dev = torch.device("cuda:0")
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).to(dev)
+    counts = np.array([len(l) for _, l in files], np.int64)
+    lens = np.concatenate([np.asarray(l, np.int64) for _, l in files])
+    vals = np.concatenate([np.asarray(v, np.float64) for v, _ in files])
+    return eng.model_device(t(counts, np.int64), t(lens, np.int32), t(vals, np.float64), keep_first=keep_first)
+
+
+def _assert_exact(got, s, units):
+    """one slot's middle order statistics, origin and moments against Python integers (units: the values that count, in order)"""
+    units = np.asarray(units, np.int64)
+    n = units.size
+    assert int(got.n_values[s]) == n, s
+    vals, cnt = np.unique(units, return_counts=True)
+    rank = np.cumsum(cnt)
+    mid = lambda r: int(vals[np.searchsorted(rank, r, side="right")])   # the value of order statistic r (0-based)
+    assert (int(got.mid_lo[s]), int(got.mid_hi[s])) == (mid((n - 1) // 2), mid(n // 2)), s
+    o = int(units[0])
+    assert int(got.origin[s]) == o, s
+    d = [(int(v) - o, int(c)) for v, c in zip(vals, cnt)]
+    assert int(got.sum1[s]) == sum(x * c for x, c in d), s
+    assert (int(got.sum2_hi[s]) << 64) + int(got.sum2_lo[s]) == sum(x * x * c for x, c in d), s
+
+
+def _lens_of(n, ev):
+    lens = [ev] * (n // ev) + ([n % ev] if n % ev else [])
+    return np.asarray(lens, np.int64)
+
+
+def test_model_value_set_in_every_kernel_class():
+    """The adversarial value set of the formatters (tests/f8_values.py) in files of every kernel class: <= 1024 values (one wave),
+    <= 2048 (32 rows), <= 4096 (256 threads, registers) and beyond (1024 threads). The values are cut into groups whose spread stays
+    inside the moment sums' 2^40 units; every group fills one file of each size. fixed8_dev and the one-wave conversion against the
+    exact units of every value."""
+    from f8_values import VALUES, ref_units
+    vals = sorted(VALUES)
+    groups, cur = [], []
+    for x in vals:
+        if cur and (len(cur) == 900 or ref_units(x) - ref_units(cur[0]) >= (1 << 40) // 2):
+            groups.append(cur); cur = []
+        cur.append(x)
+    groups.append(cur)
+    rng = np.random.default_rng(77)
+    units = {x: ref_units(x) for x in vals}
+    files = []
+    for i, g in enumerate(groups):   # the dense groups in files of every size, the sparse ones (the big values) each in one
+        sizes = (1000, 2000, 4000, 6000) if len(g) >= 100 else ((1000, 2000, 4000, 6000)[i % 4],)
+        for size in sizes:
+            v = np.resize(rng.permutation(np.asarray(g)), size)
+            files.append((v, _lens_of(size, 7), np.array([units[x] for x in v.tolist()], np.int64)))
+    eng = GmoveEngine(GmoveParams(kmers=generate_kmers(5), kmer_size=5, scaling=0, sample_limit=10))
+    for keep_first in (True, False):
+        got = _model_dev(eng, [f[:2] for f in files], keep_first)
+        for s, (_, _, u) in enumerate(files):
+            _assert_exact(got, s, u if keep_first else u[1:])
+    eng.close()
+
+
+def test_model_value_set_through_the_merged_workgroup_launch():
+    """pg_model of a job whose files are both SHORT (<= 4096 values) and LONG, fewer than 512 together: the SHORT files ride in the
+    1024-thread launch. Dyadic calibration: exact ties at the 8th decimal among the values. Exact against Python integers."""
+    from f8_values import ref_units
+    from helpers import dyadic_batch
+    kmers = generate_kmers(3, rna=True)
+    p = dict(kmer_size=3, rna=True, scaling=0, min_dur=10, max_dur=60, sample_limit=150)
+    b = dyadic_batch(500, "rna004", 31337)
+    eng = GmoveEngine(GmoveParams(kmers=kmers, **p))
+    eng.submit(b)
+    m = eng.model(keep_first=True)
+    res = eng.finish()
+    sizes = [res.slot_values(s).size for s in range(len(kmers))]
+    assert any(2048 < n <= 4096 for n in sizes) and any(n > 4096 for n in sizes), sizes
+    for s in range(len(kmers)):
+        if sizes[s]:
+            _assert_exact(m, s, [ref_units(x) for x in res.slot_values(s).tolist()])
+    eng.close()
+
+
+def _from_units(u):
+    from decimal import Decimal
+    from f8_values import ref_units
+    x = float(Decimal(u).scaleb(-8))
+    assert ref_units(x) == u, u
+    return x
+
+
+@pytest.mark.parametrize("n", [40, 5000], ids=["one_wave", "workgroup"])
+def test_model_value_and_spread_limits(n):
+    """The fixed-point view's limits at the boundaries themselves, in a one-wave file and in a workgroup file: nextafter(4e7, 0)
+    is accepted and +-4e7 refused; a deviation of 2^40 - 1 units from the origin (either side) is accepted with exact sums, 2^40 refused."""
+    from poregen_amd.engine import PgError
+    from f8_values import ref_units
+    eng = GmoveEngine(GmoveParams(kmers=generate_kmers(3), kmer_size=3, scaling=0, sample_limit=10))
+    rng = np.random.default_rng(n)
+    top = float(np.nextafter(4.0e7, 0.0))
+    ok_files = []
+    for sign in (1.0, -1.0):
+        ok_files.append(np.concatenate([[sign * top], sign * (top - rng.integers(0, 10 ** 6, n - 1) * 1e-8)]))
+    O = 10 ** 10                                        # the origin: 100 pA
+    D = (1 << 40) - 1
+    for sign in (1, -1):
+        u = [O] + [O + int(k) for k in rng.integers(-10 ** 6, 10 ** 6, n - 2)] + [O + sign * D]
+        ok_files.append(np.array([_from_units(x) for x in u]))
+    u = [O] + [O + int(k) for k in rng.integers(-10 ** 6, 10 ** 6, n - 3)] + [O + D, O - D]
+    ok_files.append(np.array([_from_units(x) for x in u]))
+    files = [(v, _lens_of(n, 5)) for v in ok_files]
+    got = _model_dev(eng, files)
+    for s, (v, _) in enumerate(files):
+        _assert_exact(got, s, [ref_units(x) for x in v.tolist()])
+    for bad in (4.0e7, -4.0e7):
+        v = ok_files[0 if bad > 0 else 1].copy(); v[n // 2] = bad
+        with pytest.raises(PgError) as ei:
+            _model_dev(eng, [files[2], (v, _lens_of(n, 5))])
+        assert "4e7" in str(ei.value)
+    for sign in (1, -1):
+        u = [O] + [O + int(k) for k in rng.integers(-10 ** 6, 10 ** 6, n - 2)] + [O + sign * (D + 1)]
+        with pytest.raises(PgError) as ei:
+            _model_dev(eng, [files[2], (np.array([_from_units(x) for x in u]), _lens_of(n, 5))])
+        assert "2^40" in str(ei.value)
+    eng.close()
+
+
+def test_model_count_limit_with_the_largest_sums():
+    """2^23 values that count (the origin, then 2^23 - 1 at +(2^40 - 1) units): sum1 and the limb sums just below 2^63, exact; the
+    sstdev text is the exact value's 14 digits. 2^23 + 1 values are refused."""
+    from decimal import ROUND_HALF_EVEN, Decimal, getcontext
+    from poregen_amd.engine import PgError
+    getcontext().prec = 60
+    O, D, N = 10 ** 10, (1 << 40) - 1, 1 << 23
+    lo, hi = _from_units(O), _from_units(O + D)
+    eng = GmoveEngine(GmoveParams(kmers=generate_kmers(3), kmer_size=3, scaling=0, sample_limit=10))
+    v = np.full(N, hi); v[0] = lo
+    got = _model_dev(eng, [(v, _lens_of(N, 4096))])
+    assert int(got.n_values[0]) == N and int(got.origin[0]) == O
+    assert int(got.sum1[0]) == (N - 1) * D and (N - 1) * D < 2 ** 63
+    assert (int(got.sum2_hi[0]) << 64) + int(got.sum2_lo[0]) == (N - 1) * D * D
+    assert int(got.mid_lo[0]) == O + D and int(got.mid_hi[0]) == O + D
+    sd = (Decimal(D) / Decimal(N).sqrt()).scaleb(-8)      # n * sum d^2 - (sum d)^2 = (n - 1) D^2: sd = D / sqrt(n)
+    want = "%.14g" % float(sd.quantize(Decimal(1).scaleb(sd.adjusted() - 13), rounding=ROUND_HALF_EVEN))
+    assert got.sstdev_text[0] == want, (got.sstdev_text[0], sd)
+    v = np.append(v, hi)
+    with pytest.raises(PgError) as ei:
+        _model_dev(eng, [(v, _lens_of(N + 1, 4096))])
+    assert "2^23" in str(ei.value)
+    eng.close()

@@ -42,6 +42,28 @@ def test_format_f8_equals_printf(h):
         assert buf.raw[:n].decode() == "%.8f" % float(v), v
 
 
+def test_f8_value_set_reference_printf_host_and_fixed8(h):
+    """The shared adversarial set (tests/f8_values.py): exact reference == printf == the host formatter == pg_fixed8 (the units the device
+    text and the model use); pg_fixed8 refuses what lies outside |x| < 4e7 and NaN."""
+    from f8_values import REFUSED, VALUES, ref_f8, ref_units
+    h.pgt_fixed8.argtypes = [C.c_double, C.POINTER(C.c_int)]; h.pgt_fixed8.restype = C.c_longlong
+    buf = C.create_string_buffer(400)
+    bad = C.c_int(0)
+    assert len(VALUES) > 10000
+    for x in VALUES:
+        want = ref_f8(x)
+        assert want == "%.8f" % x, x
+        n = h.pgt_format_f8(x, buf)
+        assert buf.raw[:n].decode() == want, x
+        u = h.pgt_fixed8(x, C.byref(bad))
+        assert bad.value == 0 and u == ref_units(x), x
+        assert want == ("-" if want[0] == "-" else "") + "%d.%08d" % divmod(abs(u), 10 ** 8), x
+    for x in REFUSED:
+        bad.value = 0
+        h.pgt_fixed8(x, C.byref(bad))
+        assert bad.value == 1, x
+
+
 def test_tokenize_ss(h):
     n = np.zeros(64, np.uint32); t = np.zeros(64, np.uint8)
     assert h.pgt_tokenize_ss(b"10,5,3D12,40I7,", n.ctypes.data, t.ctypes.data, 64) == 6
