@@ -44,6 +44,15 @@
  * _fetch_text                                                                                     src/gmove.cpp:938-950
  * pg_set_stream / pg_sync /        (no counterpart: the reference is synchronous and single-threaded)
  * pg_runtime_init / pg_poll / pg_all_slots_full_settled / pg_last_batch_device / pg_kernel_stats*
+ *
+ * The `kmer_freq` subtool (src/kmer_freq.cpp) has a handle of its own:
+ * pg_kfreq_create / pg_kfreq_destroy  the generated 4^k keys at zero and the map   src/kmer_freq.cpp:148-157
+ * pg_kfreq_submit                  the getline loop over the FASTQ: lines, the     src/kmer_freq.cpp:160-181
+ *                                  sequence-line test, one map increment per window
+ * pg_kfreq_finish                  the map's contents (dense ACGT counts + the     src/kmer_freq.cpp:189-192
+ *                                  other keys in byte order); sorting and printing,
+ *                                  :194-220, stay with the caller
+ * pg_kfreq_sync / pg_kfreq_last_error  (no counterpart)
  */
 #ifndef PGMOVE_H
 #define PGMOVE_H
@@ -421,6 +430,34 @@ pg_status   pg_job_kernel_stats(pg_job *job, uint32_t shard, pg_kernel_stat *out
 /* profiling (PG_FLAG_PROFILE): per-kernel launch counts and HIP-event times since the last reset */
 pg_status pg_kernel_stats(pg_ctx *ctx, pg_kernel_stat *out, uint32_t cap, uint32_t *n_out);
 pg_status pg_kernel_stats_reset(pg_ctx *ctx);
+
+/* ---- kmer_freq: every k-byte window of every FASTQ sequence line, counted on the device ----------------------------------------
+ * The input is the raw FASTQ bytes in pieces cut at ANY byte offset; the line structure is found on the device and the state that
+ * crosses a piece boundary stays there. Rules (src/kmer_freq.cpp:160-181): lines as getline returns them, line i is a sequence line
+ * iff i % 4 == 1, the last byte of every line (its '\n', or the last byte of an unterminated final line) is dropped, every window of
+ * kmer_size bytes of the rest is a key. ACGT windows are counted densely (index = 2-bit codes, A=0 C=1 G=2 T=3, first base most
+ * significant: the lexicographic order of the generated keys); any other window is a key of its own bytes ("odd key").
+ * A NUL byte in a sequence line is refused: pg_kfreq_finish returns PG_ERR_INPUT. No CPU fallback: PG_ERR_NO_DEVICE without a GPU. */
+typedef struct pg_kfreq pg_kfreq;
+typedef struct {
+    uint32_t kmer_size;
+    uint32_t reserved;
+    uint64_t n_odd;              /* keys that are not all ACGT */
+    const uint8_t *odd_keys;     /* n_odd * kmer_size bytes, ascending in unsigned byte order (memcmp) */
+    const uint64_t *odd_counts;  /* n_odd counts; both arrays owned by the handle until the next finish / destroy */
+} pg_kfreq_result;
+/* kmer_size in [1,12] (4^12 u64 counters = 128 MiB). The odd-key list takes PGKFREQ_ODD_CAP (default 48 M) 16-byte entries. */
+pg_status pg_kfreq_create(uint32_t kmer_size, int32_t device, pg_kfreq **out);
+void      pg_kfreq_destroy(pg_kfreq *h);
+const char *pg_kfreq_last_error(const pg_kfreq *h); /* h may be NULL: error of the last failed pg_kfreq_create */
+/* The next n_bytes of the stream. PG_LOC_HOST: any host memory, free for reuse when the call returns (page-locked memory is copied
+ * from directly, other memory through two pinned staging buffers). PG_LOC_DEVICE: memory of the handle's device, complete before the
+ * call; it is read in place and must stay unchanged until pg_kfreq_sync or pg_kfreq_finish. */
+pg_status pg_kfreq_submit(pg_kfreq *h, const void *data, uint64_t n_bytes, int32_t location);
+pg_status pg_kfreq_sync(pg_kfreq *h);
+/* End of stream (the window ending on its last byte is dropped: the unterminated-final-line rule). counts_out: host u64[4^kmer_size].
+ * The handle is reset afterwards, also after an error: the next submit starts a new stream. */
+pg_status pg_kfreq_finish(pg_kfreq *h, uint64_t *counts_out, pg_kfreq_result *out);
 
 #ifdef __cplusplus
 }

@@ -37,6 +37,7 @@ EXPORTS = [
     "pg_job_create", "pg_job_destroy", "pg_job_last_error", "pg_job_submit", "pg_job_submit_shards", "pg_job_reset", "pg_job_sync", "pg_job_all_slots_full", "pg_job_finish",
     "pg_job_finish_deferred", "pg_job_fetch_samples", "pg_job_text", "pg_job_fetch_text",
     "pg_job_uses_rccl", "pg_job_model", "pg_job_kernel_stats", "pg_runtime_init", "pg_all_slots_full_settled", "pg_job_all_slots_full_settled", "pg_poll", "pg_job_poll",
+    "pg_kfreq_create", "pg_kfreq_destroy", "pg_kfreq_last_error", "pg_kfreq_submit", "pg_kfreq_sync", "pg_kfreq_finish",
 ]
 PG_JOB_EXCHANGE_AUTO, PG_JOB_EXCHANGE_HOST, PG_JOB_EXCHANGE_RCCL = 0, 1, 2
 
@@ -92,6 +93,11 @@ class PgModelResult(C.Structure):
         ("mid_lo", C.c_void_p), ("mid_hi", C.c_void_p), ("origin", C.c_void_p), ("sum1", C.c_void_p), ("sum2_lo", C.c_void_p),
         ("sum2_hi", C.c_void_p), ("dwell_n", C.c_void_p), ("dwell_median", C.c_void_p),
     ]
+
+
+class PgKfreqResult(C.Structure):
+    _fields_ = [("kmer_size", C.c_uint32), ("reserved", C.c_uint32), ("n_odd", C.c_uint64),
+                ("odd_keys", C.c_void_p), ("odd_counts", C.c_void_p)]
 
 
 class PgKernelStat(C.Structure):
@@ -186,5 +192,11 @@ def load():
     lib.pg_job_uses_rccl.argtypes = [vp]; lib.pg_job_uses_rccl.restype = i32
     lib.pg_job_model.argtypes = [vp, u32, C.POINTER(PgModelResult)]; lib.pg_job_model.restype = i32
     lib.pg_job_kernel_stats.argtypes = [vp, u32, C.POINTER(PgKernelStat), u32, C.POINTER(u32)]; lib.pg_job_kernel_stats.restype = i32
+    lib.pg_kfreq_create.argtypes = [u32, i32, C.POINTER(vp)]; lib.pg_kfreq_create.restype = i32
+    lib.pg_kfreq_destroy.argtypes = [vp]; lib.pg_kfreq_destroy.restype = None
+    lib.pg_kfreq_last_error.argtypes = [vp]; lib.pg_kfreq_last_error.restype = C.c_char_p
+    lib.pg_kfreq_submit.argtypes = [vp, vp, C.c_uint64, i32]; lib.pg_kfreq_submit.restype = i32
+    lib.pg_kfreq_sync.argtypes = [vp]; lib.pg_kfreq_sync.restype = i32
+    lib.pg_kfreq_finish.argtypes = [vp, vp, C.POINTER(PgKfreqResult)]; lib.pg_kfreq_finish.restype = i32
     _lib = lib
     return lib

@@ -1,0 +1,582 @@
+// pg_kfreq.hip -- `poregen kmer_freq` on the device: a histogram of every k-byte window of every FASTQ sequence line
+// (src/kmer_freq.cpp:160-187 of the reference), with the raw FASTQ bytes as input, delivered in pieces cut at any byte.
+//
+// The reference's rules, restated on the byte stream (the CLI, host/kmer_freq_cli.cpp, cites the lines):
+//   * lines are getline()'s: they end after each '\n'; the last one may be unterminated. Line i is a sequence line iff i % 4 == 1.
+//   * the last byte of every line is dropped (the '\n', or a real byte for an unterminated final line), every window of k
+//     consecutive bytes of what remains is counted. So a window ending at stream offset e is counted iff its k bytes hold no '\n',
+//     its line is a sequence line and e is not the LAST byte of the stream. That last condition is all the unterminated-final-line
+//     rule needs: the window ending on a piece's last byte is settled by the next piece, and dropped by finish.
+//   * ACGT windows go to a dense u64[4^k] histogram (2-bit codes, first base most significant: the lexicographic order of the
+//     reference's generated k-mers); any other window ("odd window") is a key of its own bytes, appended to a device list.
+//   * a NUL byte in a sequence line is refused (the reference's std::string(line) truncates there): device flag -> PG_ERR_INPUT.
+//
+// Work is cut into units of at most kUnit bytes (a host piece is staged unit by unit; a device piece is read in place). Per unit:
+//   k_kf_lines : newlines per tile of kTile bytes                                     (reads the unit once)
+//   k_kf_count : tile prefix -> line index mod 4 at every thread's first byte, rolling 2-bit code per thread over its kSpan
+//                bytes (+ k-1 bytes of warm-up), LDS histogram for k <= 6, global u64 adds above; block 0 also settles the windows
+//                that straddle the previous unit (the "seam") and writes the next unit's carried state (line index mod 4, the
+//                open line's last <= k bytes) into the other slot of a two-slot state: no host round trip between units.
+// Equal codes a thread meets back to back (homopolymers) are added once, as a run.
+#include "../../include/pgmove.h"
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <deque>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kSpan = 128;                       // bytes per thread
+constexpr uint64_t kTile = (uint64_t)kThreads * kSpan;  // 32 KiB per workgroup
+constexpr uint64_t kUnit = 16ull << 20;          // bytes per unit (512 tiles)
+constexpr uint32_t kMaxK = 12;
+constexpr uint32_t kLdsMaxK = 6;                 // 4^6 u32 = 16 KiB of LDS
+constexpr int kSnapRing = 64;                    // outstanding odd-count snapshots
+
+struct KfState {       // carried across units; two slots, unit u reads slot u&1 and writes slot (u+1)&1
+    uint32_t mod4;     // index mod 4 of the line open at the unit's first byte
+    uint32_t tail_len; // bytes of that line already seen, capped at k (all of them, if fewer)
+    uint8_t tail[16];  // its last tail_len bytes, oldest first
+};
+
+struct KfDev {
+    unsigned long long *hist;  // u64[4^k]
+    uint4 *odd;                // odd windows, k bytes each, zero padded
+    unsigned long long *odd_n; // windows appended since the last drain (may exceed cap: those past it are lost -- never allowed)
+    uint32_t *err;             // NUL in a sequence line
+    KfState *state;            // [2]
+    uint32_t *tile_nl;         // newlines per tile of the current unit
+    uint64_t odd_cap;
+};
+
+__device__ __forceinline__ int base_code(uint32_t c) {
+    return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1;
+}
+
+// this thread's kSpan bytes of the unit (or fewer at its end), as four-byte words in registers
+template <bool kAligned>
+__device__ __forceinline__ void load_span(const uint8_t *__restrict__ p, uint64_t base, uint64_t n, uint32_t (&w)[kSpan / 4]) {
+    if (kAligned && base + kSpan <= n) {
+        const uint4 *q = reinterpret_cast<const uint4 *>(p + base);
+#pragma unroll
+        for (int i = 0; i < kSpan / 16; i++) { const uint4 v = q[i]; w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w; }
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < kSpan / 4; i++) {
+        uint32_t x = 0;
+        for (int b = 0; b < 4; b++) { const uint64_t o = base + 4 * i + b; if (o < n) x |= (uint32_t)p[o] << (8 * b); }
+        w[i] = x;
+    }
+}
+
+template <bool kAligned>
+__device__ __forceinline__ uint4 load16(const uint8_t *__restrict__ p, uint64_t o, uint64_t n) {
+    if (kAligned && o + 16 <= n) return *reinterpret_cast<const uint4 *>(p + o);
+    uint32_t x[4] = {0, 0, 0, 0};
+    for (int b = 0; b < 16; b++) if (o + b < n) x[b >> 2] |= (uint32_t)p[o + b] << (8 * (b & 3));
+    return make_uint4(x[0], x[1], x[2], x[3]);
+}
+
+__device__ __forceinline__ uint32_t nl_in_word(uint32_t x) { // bytes equal to '\n'
+    const uint32_t y = x ^ 0x0a0a0a0au;
+    return __popc(~(((y & 0x7f7f7f7fu) + 0x7f7f7f7fu) | y | 0x7f7f7f7fu));
+}
+
+template <bool kAligned>
+__global__ __launch_bounds__(kThreads) void k_kf_lines(const uint8_t *__restrict__ p, uint64_t n, uint32_t *__restrict__ tile_nl) {
+    const uint64_t base = blockIdx.x * kTile + threadIdx.x * (uint64_t)kSpan;
+    uint32_t w[kSpan / 4];
+    uint32_t c = 0;
+    if (base < n) {
+        load_span<kAligned>(p, base, n, w);
+#pragma unroll
+        for (int i = 0; i < kSpan / 4; i++) c += nl_in_word(w[i]); // zero padding past n is no newline
+    }
+    __shared__ uint32_t red[kThreads / 64];
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) { uint32_t s = 0; for (int i = 0; i < kThreads / 64; i++) s += red[i]; tile_nl[blockIdx.x] = s; }
+}
+
+__device__ __forceinline__ uint4 odd_key(uint64_t lo, uint32_t hi, uint32_t k) {
+    // lo/hi: the window's bytes, newest in the lowest byte of lo
+    uint32_t key[4] = {0, 0, 0, 0};
+    for (uint32_t i = 0; i < k; i++) {
+        const uint32_t sh = k - 1 - i; // byte i of the key is sh bytes older than the newest
+        const uint32_t b = sh < 8 ? (uint32_t)(lo >> (8 * sh)) & 0xff : (hi >> (8 * (sh - 8))) & 0xff;
+        key[i >> 2] |= b << (8 * (i & 3));
+    }
+    return make_uint4(key[0], key[1], key[2], key[3]);
+}
+
+__device__ __forceinline__ void emit_odd(const KfDev &d, uint4 key) {
+    const unsigned long long i = atomicAdd(d.odd_n, 1ull);
+    if (i < d.odd_cap) d.odd[i] = key;
+}
+
+// odd windows of a workgroup are gathered in LDS and appended with one global add per workgroup; past kOddLds they go out one by one
+constexpr uint32_t kOddLds = 512;
+__device__ __forceinline__ void stage_odd(const KfDev &d, uint4 *s_odd, uint32_t *s_odd_n, uint4 key) {
+    const uint32_t i = atomicAdd(s_odd_n, 1u);
+    if (i < kOddLds) s_odd[i] = key;
+    else emit_odd(d, key);
+}
+
+template <bool kLds>
+__device__ __forceinline__ void add_run(const KfDev &d, uint32_t *lds, uint32_t code, uint32_t cnt) {
+    if (!cnt) return;
+    if (kLds) atomicAdd(&lds[code], cnt);
+    else atomicAdd(&d.hist[code], (unsigned long long)cnt);
+}
+
+// block 0, thread 0: windows that start in the carried tail and end in this unit, then the state the next unit starts from
+__device__ void kf_seam(const KfDev &d, const uint8_t *__restrict__ p, uint64_t n, uint32_t k, uint32_t par, uint32_t total_nl) {
+    const KfState s = d.state[par];
+    uint8_t v[2 * kMaxK];
+    const uint32_t t = s.tail_len;
+    const uint32_t head = (uint32_t)min<uint64_t>(n, k - 1);
+    for (uint32_t i = 0; i < t; i++) v[i] = s.tail[i];
+    for (uint32_t i = 0; i < head; i++) v[t + i] = p[i];
+    // window ending at v[e]: e >= k-1 (whole), e <= t+k-2 (starts in the tail), e <= t+n-2 (not the stream's last byte so far)
+    if (s.mod4 == 1 && t >= 1) { // (k = 1: only the window of the tail's byte, left open by the last unit)
+        const uint64_t e_hi = min<uint64_t>(t + k - 2, t + n - 2);
+        for (uint64_t e = k - 1; e <= e_hi; e++) {
+            bool nl = false, acgt = true;
+            uint32_t code = 0;
+            uint64_t lo = 0; uint32_t hi = 0;
+            for (uint32_t j = 0; j < k; j++) {
+                const uint32_t c = v[e + 1 - k + j];
+                nl |= c == '\n';
+                const int b = base_code(c);
+                acgt &= b >= 0;
+                code = (code << 2) | (uint32_t)(b & 3);
+                hi = (hi << 8) | (uint32_t)(lo >> 56); lo = (lo << 8) | c;
+            }
+            if (nl) break; // every later window holds the same newline
+            if (acgt) atomicAdd(&d.hist[code], 1ull);
+            else emit_odd(d, odd_key(lo, hi, k));
+        }
+    }
+    // the next state: the open line's last <= k bytes
+    KfState o;
+    o.mod4 = (s.mod4 + total_nl) & 3;
+    int64_t nl = -1; // last newline among the unit's last min(n, k) bytes
+    for (uint64_t i = n; i > 0 && n - i < k; i--)
+        if (p[i - 1] == '\n') { nl = (int64_t)i - 1; break; }
+    uint8_t cat[2 * kMaxK];
+    uint32_t m = 0;
+    if (nl < 0 && n < k) for (uint32_t i = 0; i < t; i++) cat[m++] = s.tail[i]; // the whole unit continues the open line
+    for (uint64_t i = nl >= 0 ? (uint64_t)nl + 1 : (n > k ? n - k : 0); i < n; i++) cat[m++] = p[i];
+    const uint32_t keep = min(m, k);
+    o.tail_len = keep;
+    for (uint32_t i = 0; i < 16; i++) o.tail[i] = i < keep ? cat[m - keep + i] : 0;
+    d.state[par ^ 1] = o;
+}
+
+template <bool kAligned, bool kLds>
+__global__ __launch_bounds__(kThreads) void k_kf_count(KfDev d, const uint8_t *__restrict__ p, uint64_t n, uint32_t n_tiles, uint32_t k, uint32_t par) {
+    extern __shared__ uint32_t lds_hist[];
+    __shared__ uint32_t s_scan[kThreads];
+    __shared__ uint32_t s_red[kThreads / 64];
+    __shared__ uint4 s_odd[kOddLds];
+    __shared__ uint32_t s_odd_n;
+    __shared__ unsigned long long s_odd_at;
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) s_odd_n = 0;
+    const uint32_t n_codes = 1u << (2 * k);
+    if (kLds) for (uint32_t i = tid; i < n_codes; i += kThreads) lds_hist[i] = 0;
+
+    // newlines in front of this tile (block 0: in front of the whole unit's end, for the next state)
+    const uint32_t upto = blockIdx.x == 0 ? n_tiles : blockIdx.x;
+    uint32_t pre = 0;
+    for (uint32_t i = tid; i < upto; i += kThreads) pre += d.tile_nl[i];
+    for (int o = 32; o > 0; o >>= 1) pre += __shfl_xor(pre, o);
+    if ((tid & 63) == 0) s_red[tid >> 6] = pre;
+
+    const uint64_t base = blockIdx.x * kTile + tid * (uint64_t)kSpan;
+    uint32_t w[kSpan / 4];
+    uint32_t my_nl = 0;
+    if (base < n) {
+        load_span<kAligned>(p, base, n, w);
+#pragma unroll
+        for (int i = 0; i < kSpan / 4; i++) my_nl += nl_in_word(w[i]);
+    }
+    s_scan[tid] = my_nl;
+    __syncthreads();
+    uint32_t tile_pre = 0;
+    for (int i = 0; i < kThreads / 64; i++) tile_pre += s_red[i];
+    if (blockIdx.x == 0) {
+        if (tid == 0) kf_seam(d, p, n, k, par, tile_pre);
+        tile_pre = 0;
+    }
+    // exclusive scan of the per-thread newline counts (mod 4 is all that is needed; plain sums do not overflow)
+    for (uint32_t off = 1; off < kThreads; off <<= 1) {
+        const uint32_t x = tid >= off ? s_scan[tid - off] : 0;
+        __syncthreads();
+        s_scan[tid] += x;
+        __syncthreads();
+    }
+    const uint32_t excl = s_scan[tid] - my_nl;
+    const KfState st = d.state[par];
+    uint32_t mod4 = (st.mod4 + tile_pre + excl) & 3;
+
+    uint32_t run_code = 0, run_cnt = 0;
+    if (base < n) {
+        const uint64_t mask = n_codes - 1;
+        // warm-up: the k-1 bytes in front of this thread's span (inside the unit; earlier ones are the seam's)
+        uint32_t len = 0, run = 0, code = 0;
+        uint64_t lo = 0; uint32_t hi = 0;
+        const uint64_t w0 = base >= k - 1 ? base - (k - 1) : 0;
+        for (uint64_t q = w0; q < base; q++) {
+            const uint32_t c = p[q];
+            if (c == '\n') { len = 0; run = 0; continue; }
+            len++;
+            const int b = base_code(c);
+            run = b >= 0 ? run + 1 : 0;
+            code = (code << 2) | (uint32_t)(b & 3);
+            hi = (hi << 8) | (uint32_t)(lo >> 56); lo = (lo << 8) | c;
+        }
+        bool bad = false;
+        const uint32_t lim = (uint32_t)min<uint64_t>(kSpan, n - base);
+        // the last byte of the unit is not an end of a counted window here: the seam of the next unit (or finish) settles it
+        const uint32_t last_ok = base + lim == n ? lim - 1 : lim;
+        for (uint32_t ch = 0; ch < kSpan / 16; ch++) {
+            if (ch * 16 >= lim) break;
+            const uint4 v = load16<kAligned>(p, base + 16 * ch, n); // second read of the span: served by the cache
+            const uint32_t ws[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (uint32_t j = 0; j < 16; j++) {
+                const uint32_t i = ch * 16 + j;
+                if (i >= lim) break;
+                const uint32_t c = (ws[j >> 2] >> (8 * (j & 3))) & 0xff;
+                if (c == '\n') { mod4 = (mod4 + 1) & 3; len = 0; run = 0; continue; }
+                const bool seq = mod4 == 1;
+                bad |= seq && c == 0;
+                len++;
+                const int b = base_code(c);
+                run = b >= 0 ? run + 1 : 0;
+                code = ((code << 2) | (uint32_t)(b & 3)) & (uint32_t)mask;
+                hi = (hi << 8) | (uint32_t)(lo >> 56); lo = (lo << 8) | c;
+                if (seq && len >= k && i < last_ok) {
+                    if (run >= k) {
+                        if (code == run_code) run_cnt++;
+                        else { add_run<kLds>(d, lds_hist, run_code, run_cnt); run_code = code; run_cnt = 1; }
+                    } else {
+                        stage_odd(d, s_odd, &s_odd_n, odd_key(lo, hi, k));
+                    }
+                }
+            }
+        }
+        if (bad) atomicOr(d.err, 1u);
+    }
+    // the open run of every thread (the wave is converged here): where all of a wave's runs share one code -- a homopolymer -- one
+    // lane adds their sum, instead of 64 adds to one address
+    const uint32_t c0 = __builtin_amdgcn_readfirstlane(run_code);
+    const bool lone = __ballot(run_cnt != 0 && run_code != c0) != 0;
+    if (lone) {
+        add_run<kLds>(d, lds_hist, run_code, run_cnt);
+    } else {
+        uint32_t sum = run_cnt;
+        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+        if ((tid & 63) == 0) add_run<kLds>(d, lds_hist, c0, sum);
+    }
+    __syncthreads();
+    const uint32_t n_staged = min(s_odd_n, kOddLds);
+    if (n_staged) {
+        if (tid == 0) s_odd_at = atomicAdd(d.odd_n, (unsigned long long)n_staged);
+        __syncthreads();
+        for (uint32_t i = tid; i < n_staged; i += kThreads)
+            if (s_odd_at + i < d.odd_cap) d.odd[s_odd_at + i] = s_odd[i];
+    }
+    if (kLds) {
+        for (uint32_t i = tid; i < n_codes; i += kThreads)
+            if (const uint32_t v = lds_hist[i]) atomicAdd(&d.hist[i], (unsigned long long)v);
+    }
+}
+
+struct OddKey {
+    uint32_t w[4];
+    bool operator==(const OddKey &o) const { return memcmp(w, o.w, sizeof w) == 0; }
+};
+struct OddHash {
+    size_t operator()(const OddKey &k) const {
+        uint64_t a = ((uint64_t)k.w[1] << 32 | k.w[0]) * 0x9E3779B97F4A7C15ull, b = ((uint64_t)k.w[3] << 32 | k.w[2]) * 0xC2B2AE3D27D4EB4Full;
+        return (size_t)(a ^ (b >> 29) ^ (a >> 31));
+    }
+};
+
+thread_local std::string g_kf_create_error;
+
+} // namespace
+
+struct pg_kfreq {
+    uint32_t k = 0, n_codes = 0;
+    int device = 0;
+    uint64_t unit = kUnit; // <= odd_cap: a unit never has more windows than the list holds
+    hipStream_t ks = nullptr, cs = nullptr; // count stream, copy stream (host input)
+    KfDev d{};
+    uint32_t par = 0;
+    // host input: two pinned staging buffers and their device copies
+    uint8_t *stage[2] = {nullptr, nullptr};
+    uint8_t *dbuf[2] = {nullptr, nullptr};
+    hipEvent_t copied[2] = {nullptr, nullptr}, counted[2] = {nullptr, nullptr};
+    int next_buf = 0;
+    // odd-list fill: exact counts read back asynchronously, one snapshot per unit
+    unsigned long long *snap = nullptr; // pinned [kSnapRing]
+    hipEvent_t snap_ev[kSnapRing] = {};
+    struct Pending { int slot; uint64_t bound; };
+    std::deque<Pending> pending;
+    int snap_next = 0;
+    uint64_t odd_known = 0;              // exact list fill as of the newest completed snapshot (or drain)
+    std::unordered_map<OddKey, uint64_t, OddHash> odd_map;
+    std::vector<uint4> drain_buf;
+    // finish output
+    std::vector<uint8_t> out_keys;
+    std::vector<uint64_t> out_counts;
+    bool aligned_stage = true;
+    std::string err;
+};
+
+static pg_status kf_fail(pg_kfreq *h, pg_status code, const char *fmt, ...) {
+    char buf[1024];
+    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
+    if (h) h->err = buf; else g_kf_create_error = buf;
+    return code;
+}
+#define KF_TRY(h, expr) \
+    do { hipError_t e_ = (expr); if (e_ != hipSuccess) return kf_fail((h), PG_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
+
+static uint64_t odd_cap_from_env() {
+    if (const char *s = getenv("PGKFREQ_ODD_CAP")) { const long long v = atoll(s); if (v >= 1) return (uint64_t)v; }
+    return 3 * kUnit; // three units' worth of windows: a unit may be launched while two are still unread (kf_reserve)
+}
+
+// Fold the device odd list into the host map and empty it. The count stream must be idle.
+static pg_status kf_drain(pg_kfreq *h) {
+    unsigned long long n = 0;
+    KF_TRY(h, hipMemcpy(&n, h->d.odd_n, sizeof n, hipMemcpyDeviceToHost));
+    if (n > h->d.odd_cap) return kf_fail(h, PG_ERR_STATE, "internal: odd-window list overflowed (%llu > %llu)", n, (unsigned long long)h->d.odd_cap);
+    if (n) {
+        h->drain_buf.resize(n);
+        KF_TRY(h, hipMemcpy(h->drain_buf.data(), h->d.odd, n * sizeof(uint4), hipMemcpyDeviceToHost));
+        for (const uint4 &v : h->drain_buf) { OddKey key{{v.x, v.y, v.z, v.w}}; h->odd_map[key]++; }
+        KF_TRY(h, hipMemsetAsync(h->d.odd_n, 0, sizeof(unsigned long long), h->ks));
+        KF_TRY(h, hipStreamSynchronize(h->ks));
+    }
+    h->odd_known = 0;
+    h->pending.clear();
+    return PG_OK;
+}
+
+// Before a unit of n bytes is launched: make sure the odd list has room for all its windows. The exact fill is known from the
+// snapshots of earlier units that have completed (never waited for while the bound is low); only when the bound says the list
+// could overflow does the host wait, and only when the exact fill says so does it drain.
+static pg_status kf_reserve(pg_kfreq *h, uint64_t n) {
+    while (!h->pending.empty() && hipEventQuery(h->snap_ev[h->pending.front().slot]) == hipSuccess) {
+        h->odd_known = h->snap[h->pending.front().slot];
+        h->pending.pop_front();
+    }
+    uint64_t bound = h->odd_known + n;
+    for (const auto &q : h->pending) bound += q.bound;
+    if (bound <= h->d.odd_cap && (int)h->pending.size() < kSnapRing - 1) return PG_OK;
+    if (!h->pending.empty()) {
+        KF_TRY(h, hipEventSynchronize(h->snap_ev[h->pending.back().slot]));
+        h->odd_known = h->snap[h->pending.back().slot];
+        h->pending.clear();
+    }
+    if (h->odd_known + n > h->d.odd_cap) {
+        KF_TRY(h, hipStreamSynchronize(h->ks));
+        return kf_drain(h);
+    }
+    return PG_OK;
+}
+
+// one unit of at most kUnit bytes, resident on the device, complete on the count stream's side
+static pg_status kf_unit(pg_kfreq *h, const uint8_t *p, uint64_t n) {
+    if (!n) return PG_OK;
+    if (pg_status s = kf_reserve(h, n)) return s;
+    const uint32_t n_tiles = (uint32_t)((n + kTile - 1) / kTile);
+    const bool al = ((uintptr_t)p & 15) == 0;
+    const bool lds = h->k <= kLdsMaxK;
+    const size_t lds_bytes = lds ? (size_t)h->n_codes * sizeof(uint32_t) : 0;
+    if (al) hipLaunchKernelGGL(k_kf_lines<true>, dim3(n_tiles), dim3(kThreads), 0, h->ks, p, n, h->d.tile_nl);
+    else hipLaunchKernelGGL(k_kf_lines<false>, dim3(n_tiles), dim3(kThreads), 0, h->ks, p, n, h->d.tile_nl);
+    if (al && lds) hipLaunchKernelGGL((k_kf_count<true, true>), dim3(n_tiles), dim3(kThreads), lds_bytes, h->ks, h->d, p, n, n_tiles, h->k, h->par);
+    else if (al) hipLaunchKernelGGL((k_kf_count<true, false>), dim3(n_tiles), dim3(kThreads), 0, h->ks, h->d, p, n, n_tiles, h->k, h->par);
+    else if (lds) hipLaunchKernelGGL((k_kf_count<false, true>), dim3(n_tiles), dim3(kThreads), lds_bytes, h->ks, h->d, p, n, n_tiles, h->k, h->par);
+    else hipLaunchKernelGGL((k_kf_count<false, false>), dim3(n_tiles), dim3(kThreads), 0, h->ks, h->d, p, n, n_tiles, h->k, h->par);
+    KF_TRY(h, hipGetLastError());
+    h->par ^= 1;
+    const int slot = h->snap_next; h->snap_next = (h->snap_next + 1) % kSnapRing;
+    KF_TRY(h, hipMemcpyAsync(&h->snap[slot], h->d.odd_n, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->ks));
+    KF_TRY(h, hipEventRecord(h->snap_ev[slot], h->ks));
+    h->pending.push_back({slot, n});
+    return PG_OK;
+}
+
+static pg_status kf_reset_device(pg_kfreq *h) {
+    KF_TRY(h, hipMemsetAsync(h->d.hist, 0, (size_t)h->n_codes * sizeof(unsigned long long), h->ks));
+    KF_TRY(h, hipMemsetAsync(h->d.odd_n, 0, sizeof(unsigned long long), h->ks));
+    KF_TRY(h, hipMemsetAsync(h->d.err, 0, sizeof(uint32_t), h->ks));
+    KF_TRY(h, hipMemsetAsync(h->d.state, 0, 2 * sizeof(KfState), h->ks));
+    KF_TRY(h, hipStreamSynchronize(h->ks));
+    h->par = 0;
+    h->pending.clear();
+    h->odd_known = 0;
+    h->odd_map.clear();
+    return PG_OK;
+}
+
+extern "C" {
+
+const char *pg_kfreq_last_error(const pg_kfreq *h) { return h ? h->err.c_str() : g_kf_create_error.c_str(); }
+
+pg_status pg_kfreq_create(uint32_t kmer_size, int32_t device, pg_kfreq **out) {
+    if (!out) return kf_fail(nullptr, PG_ERR_INVALID_ARG, "pg_kfreq_create: null argument");
+    *out = nullptr;
+    if (kmer_size < 1 || kmer_size > kMaxK) return kf_fail(nullptr, PG_ERR_INVALID_ARG, "kmer_size must be in [1,%u]", kMaxK);
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0) return kf_fail(nullptr, PG_ERR_NO_DEVICE, "no HIP device available (%s); libpgmove has no CPU fallback", e != hipSuccess ? hipGetErrorString(e) : "device count 0");
+    if (device < 0 || device >= ndev) return kf_fail(nullptr, PG_ERR_NO_DEVICE, "device %d out of range (have %d)", device, ndev);
+    e = hipSetDevice(device);
+    if (e != hipSuccess) return kf_fail(nullptr, PG_ERR_NO_DEVICE, "hipSetDevice(%d): %s", device, hipGetErrorString(e));
+    pg_kfreq *h = new pg_kfreq();
+    h->k = kmer_size; h->n_codes = 1u << (2 * kmer_size); h->device = device;
+    h->d.odd_cap = odd_cap_from_env();
+    h->unit = std::min<uint64_t>(kUnit, h->d.odd_cap);
+    auto bail = [&](pg_status s) { g_kf_create_error = h->err; pg_kfreq_destroy(h); return s; };
+#define KTRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { kf_fail(h, PG_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); return bail(PG_ERR_HIP); } } while (0)
+    KTRY(hipStreamCreateWithFlags(&h->ks, hipStreamNonBlocking));
+    KTRY(hipStreamCreateWithFlags(&h->cs, hipStreamNonBlocking));
+    KTRY(hipMalloc((void **)&h->d.hist, (size_t)h->n_codes * sizeof(unsigned long long)));
+    KTRY(hipMalloc((void **)&h->d.odd, h->d.odd_cap * sizeof(uint4)));
+    KTRY(hipMalloc((void **)&h->d.odd_n, sizeof(unsigned long long)));
+    KTRY(hipMalloc((void **)&h->d.err, sizeof(uint32_t)));
+    KTRY(hipMalloc((void **)&h->d.state, 2 * sizeof(KfState)));
+    KTRY(hipMalloc((void **)&h->d.tile_nl, (kUnit / kTile) * sizeof(uint32_t)));
+    KTRY(hipHostMalloc((void **)&h->snap, kSnapRing * sizeof(unsigned long long), hipHostMallocDefault));
+    for (auto &ev : h->snap_ev) KTRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    for (int i = 0; i < 2; i++) {
+        KTRY(hipEventCreateWithFlags(&h->copied[i], hipEventDisableTiming));
+        KTRY(hipEventCreateWithFlags(&h->counted[i], hipEventDisableTiming));
+    }
+    if (pg_status s = kf_reset_device(h)) return bail(s);
+#undef KTRY
+    *out = h;
+    return PG_OK;
+}
+
+void pg_kfreq_destroy(pg_kfreq *h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    if (h->ks) (void)hipStreamSynchronize(h->ks);
+    if (h->cs) (void)hipStreamSynchronize(h->cs);
+    (void)hipFree(h->d.hist); (void)hipFree(h->d.odd); (void)hipFree(h->d.odd_n); (void)hipFree(h->d.err);
+    (void)hipFree(h->d.state); (void)hipFree(h->d.tile_nl);
+    for (int i = 0; i < 2; i++) {
+        if (h->stage[i]) (void)hipHostFree(h->stage[i]);
+        if (h->dbuf[i]) (void)hipFree(h->dbuf[i]);
+        if (h->copied[i]) (void)hipEventDestroy(h->copied[i]);
+        if (h->counted[i]) (void)hipEventDestroy(h->counted[i]);
+    }
+    for (auto &ev : h->snap_ev) if (ev) (void)hipEventDestroy(ev);
+    if (h->snap) (void)hipHostFree(h->snap);
+    if (h->ks) (void)hipStreamDestroy(h->ks);
+    if (h->cs) (void)hipStreamDestroy(h->cs);
+    delete h;
+}
+
+pg_status pg_kfreq_submit(pg_kfreq *h, const void *data, uint64_t n_bytes, int32_t location) {
+    if (!h) return kf_fail(nullptr, PG_ERR_INVALID_ARG, "pg_kfreq_submit: null handle");
+    if (!n_bytes) return PG_OK;
+    if (!data) return kf_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit: null data");
+    KF_TRY(h, hipSetDevice(h->device));
+    const uint8_t *src = static_cast<const uint8_t *>(data);
+    if (location == PG_LOC_DEVICE) {
+        hipPointerAttribute_t a{};
+        if (hipPointerGetAttributes(&a, data) != hipSuccess || a.type != hipMemoryTypeDevice || a.device != h->device) {
+            (void)hipGetLastError();
+            return kf_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit: PG_LOC_DEVICE data is not device memory of device %d", h->device);
+        }
+        for (uint64_t o = 0; o < n_bytes; o += h->unit)
+            if (pg_status s = kf_unit(h, src + o, std::min<uint64_t>(h->unit, n_bytes - o))) return s;
+        return PG_OK;
+    }
+    if (location != PG_LOC_HOST) return kf_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit: location must be PG_LOC_HOST or PG_LOC_DEVICE");
+    // page-locked caller memory goes to the device as it is; anything else through the pinned staging buffers
+    hipPointerAttribute_t a{};
+    const bool pinned = hipPointerGetAttributes(&a, data) == hipSuccess && a.type == hipMemoryTypeHost;
+    (void)hipGetLastError();
+    for (uint64_t o = 0; o < n_bytes; o += h->unit) {
+        const uint64_t m = std::min<uint64_t>(h->unit, n_bytes - o);
+        const int b = h->next_buf; h->next_buf ^= 1;
+        if (!h->dbuf[b]) {
+            KF_TRY(h, hipMalloc((void **)&h->dbuf[b], kUnit));
+            KF_TRY(h, hipEventRecord(h->copied[b], h->cs));
+            KF_TRY(h, hipEventRecord(h->counted[b], h->ks));
+        }
+        const uint8_t *from = src + o;
+        if (!pinned) {
+            if (!h->stage[b]) KF_TRY(h, hipHostMalloc((void **)&h->stage[b], kUnit, hipHostMallocDefault));
+            KF_TRY(h, hipEventSynchronize(h->copied[b])); // the staging buffer's previous copy is done
+            memcpy(h->stage[b], from, m);
+            from = h->stage[b];
+        }
+        KF_TRY(h, hipStreamWaitEvent(h->cs, h->counted[b], 0)); // the device buffer's previous unit is counted
+        KF_TRY(h, hipMemcpyAsync(h->dbuf[b], from, m, hipMemcpyHostToDevice, h->cs));
+        KF_TRY(h, hipEventRecord(h->copied[b], h->cs));
+        KF_TRY(h, hipStreamWaitEvent(h->ks, h->copied[b], 0));
+        if (pg_status s = kf_unit(h, h->dbuf[b], m)) return s;
+        KF_TRY(h, hipEventRecord(h->counted[b], h->ks));
+    }
+    // the caller may reuse its (page-locked) buffer once submit returns
+    if (pinned) KF_TRY(h, hipStreamSynchronize(h->cs));
+    return PG_OK;
+}
+
+pg_status pg_kfreq_sync(pg_kfreq *h) {
+    if (!h) return kf_fail(nullptr, PG_ERR_INVALID_ARG, "pg_kfreq_sync: null handle");
+    KF_TRY(h, hipSetDevice(h->device));
+    KF_TRY(h, hipStreamSynchronize(h->cs));
+    KF_TRY(h, hipStreamSynchronize(h->ks));
+    return PG_OK;
+}
+
+pg_status pg_kfreq_finish(pg_kfreq *h, uint64_t *counts_out, pg_kfreq_result *out) {
+    if (!h) return kf_fail(nullptr, PG_ERR_INVALID_ARG, "pg_kfreq_finish: null handle");
+    if (!counts_out || !out) return kf_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_finish: null argument");
+    memset(out, 0, sizeof *out);
+    if (pg_status s = pg_kfreq_sync(h)) return s;
+    uint32_t bad = 0;
+    KF_TRY(h, hipMemcpy(&bad, h->d.err, sizeof bad, hipMemcpyDeviceToHost));
+    pg_status st = PG_OK;
+    if (bad) st = kf_fail(h, PG_ERR_INPUT, "a sequence line holds a NUL byte (the reference truncates the line there: undefined counts)");
+    else if ((st = kf_drain(h)) == PG_OK) {
+        KF_TRY(h, hipMemcpy(counts_out, h->d.hist, (size_t)h->n_codes * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        std::vector<std::pair<OddKey, uint64_t>> v(h->odd_map.begin(), h->odd_map.end());
+        const uint32_t k = h->k;
+        std::sort(v.begin(), v.end(), [k](const auto &a, const auto &b) { return memcmp(a.first.w, b.first.w, k) < 0; });
+        h->out_keys.resize(v.size() * k);
+        h->out_counts.resize(v.size());
+        for (size_t i = 0; i < v.size(); i++) { memcpy(&h->out_keys[i * k], v[i].first.w, k); h->out_counts[i] = v[i].second; }
+        out->kmer_size = k;
+        out->n_odd = v.size();
+        out->odd_keys = h->out_keys.data();
+        out->odd_counts = h->out_counts.data();
+    }
+    if (pg_status s = kf_reset_device(h)) return s;
+    return st;
+}
+
+} // extern "C"

@@ -603,3 +603,99 @@ class GmoveJob:
             self.close()
         except Exception:
             pass
+
+
+# ---- kmer_freq ------------------------------------------------------------------------------------------------------------------
+
+@dataclass
+class KmerFreqResult:
+    """Every key of `poregen kmer_freq`: counts[code] for the 4^k ACGT k-mers (code = 2-bit bases, first base most significant, so
+    code order is byte order), plus the keys holding any other byte, ascending in byte order, with their counts."""
+    k: int
+    counts: np.ndarray                      # uint64[4^k]
+    odd_keys: List[bytes]
+    odd_counts: np.ndarray                  # uint64[len(odd_keys)]
+
+    def entries(self):
+        """(key, count) for every key in byte order: the std::map the reference prints (src/kmer_freq.cpp:185-192)."""
+        dense = [bytes(t) for t in itertools.product(b"ACGT", repeat=self.k)]
+        out, j = [], 0
+        for code, key in enumerate(dense):
+            while j < len(self.odd_keys) and self.odd_keys[j] < key:
+                out.append((self.odd_keys[j], int(self.odd_counts[j]))); j += 1
+            out.append((key, int(self.counts[code])))
+        out += [(self.odd_keys[i], int(self.odd_counts[i])) for i in range(j, len(self.odd_keys))]
+        return out
+
+    def lines(self, sort: int = 0, print_absent: int = 1) -> bytes:
+        """The bytes `poregen kmer_freq --sort S --print_absent_kmers P` writes (src/kmer_freq.cpp:194-220)."""
+        e = self.entries()
+        if sort == 1:
+            e.sort(key=lambda t: (t[1], t[0]))
+        elif sort == 2:
+            e.sort(key=lambda t: (t[1], t[0]), reverse=True)
+        return b"".join(b"%s\t%d\n" % (key, c) for key, c in e if print_absent or c)
+
+
+class KmerCounter:
+    """Counts the k-mers of FASTQ bytes on the GPU (pg_kfreq_*). submit() takes the file's bytes in pieces cut anywhere: `bytes`,
+    a numpy uint8 array, or a CUDA torch.uint8 tensor (read in place, no host copy; kept alive until finish)."""
+
+    def __init__(self, k: int, device: int = 0):
+        self._lib = _abi.load()
+        self.k = k
+        h = C.c_void_p()
+        st = self._lib.pg_kfreq_create(k, device, C.byref(h))
+        if st != 0:
+            raise PgError(st, self._lib.pg_kfreq_last_error(None).decode())
+        self._h = h
+        self._keep = []
+
+    def _check(self, st):
+        if st != 0:
+            raise PgError(st, self._lib.pg_kfreq_last_error(self._h).decode())
+
+    def submit(self, piece):
+        if hasattr(piece, "is_cuda") and piece.is_cuda:
+            if piece.dtype.itemsize != 1 or not piece.is_contiguous():
+                raise ValueError("device pieces must be contiguous uint8 tensors")
+            self._keep.append(piece)
+            self._check(self._lib.pg_kfreq_submit(self._h, C.c_void_p(piece.data_ptr()), piece.numel(), _abi.PG_LOC_DEVICE))
+            return
+        a = np.ascontiguousarray(np.frombuffer(piece, np.uint8) if isinstance(piece, (bytes, bytearray, memoryview)) else piece, dtype=np.uint8)
+        if a.size:
+            self._check(self._lib.pg_kfreq_submit(self._h, C.c_void_p(a.ctypes.data), a.size, _abi.PG_LOC_HOST))
+
+    def finish(self) -> KmerFreqResult:
+        counts = np.zeros(4 ** self.k, np.uint64)
+        r = _abi.PgKfreqResult()
+        try:
+            self._check(self._lib.pg_kfreq_finish(self._h, C.c_void_p(counts.ctypes.data), C.byref(r)))
+        finally:
+            self._keep = []
+        n = int(r.n_odd)
+        raw = C.string_at(r.odd_keys, n * self.k) if n else b""
+        keys = [raw[i * self.k:(i + 1) * self.k] for i in range(n)]
+        oc = np.ctypeslib.as_array(C.cast(r.odd_counts, C.POINTER(C.c_uint64)), (n,)).copy() if n else np.zeros(0, np.uint64)
+        return KmerFreqResult(self.k, counts, keys, oc)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.pg_kfreq_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def kmer_freq(data, k: int, device: int = 0) -> KmerFreqResult:
+    """One-shot: the k-mer counts of a whole FASTQ given as bytes / numpy uint8 / CUDA uint8 tensor."""
+    kc = KmerCounter(k, device)
+    try:
+        kc.submit(data)
+        return kc.finish()
+    finally:
+        kc.close()

@@ -1,0 +1,164 @@
+#!/usr/bin/env python3
+"""kfreq_bench.py -- throughput of `poregen kmer_freq` on one MI355X, in GB/s of FASTQ bytes.
+
+A seeded synthetic FASTQ (lognormal read lengths, 0.1 % N, headers and qualities like the fixtures) of --gb gigabytes is made in
+memory. Measured, each as the best of --reps runs after one warm-up:
+  device      the bytes already in HBM (a torch.uint8 tensor, PG_LOC_DEVICE), k = 5, 9, 12, and a homopolymer file (one read of A)
+              at k = 5 and 9; finish() (the D2H of the 4^k counts and the odd keys) is inside the time. Share of the 8 TB/s HBM peak
+              next to the byte rate.
+  host        the bytes in page-locked host memory (PG_LOC_HOST), k = 9, next to a plain copy of the same bytes to the device
+              (torch copy_ from pinned memory = hipMemcpyAsync) measured in the same run: the H2D ceiling.
+  cli         bin/poregen kmer_freq 9 FILE with --sort 0 and --sort 1, output to /dev/null, the file written to --tmp and read once
+              before timing (page cache).
+  cpu         one core: numpy rolling 2-bit codes + bincount over the sequence lines of the first --cpu-mb megabytes.
+Prints one JSON object and writes it to --out.
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def synth(n_bytes, seed=1, n_rate=0.001):
+    rng = np.random.default_rng(seed)
+    parts, total, i = [], 0, 0
+    lut = np.frombuffer(b"ACGT", np.uint8)
+    while total < n_bytes:
+        m = 4096
+        lens = np.clip(rng.lognormal(8.5, 0.8, m), 50, 200_000).astype(np.int64)
+        seq = lut[rng.integers(0, 4, int(lens.sum()))]
+        seq[rng.random(seq.size) < n_rate] = ord("N")
+        qual = rng.integers(35, 75, seq.size).astype(np.uint8)
+        o = 0
+        for L in lens:
+            hdr = b"@%08x-1f2e-4d3c-9b8a-%012d runid=0f1e2d3c read=%d ch=%d start_time=2023-01-01T00:00:00Z\n" % (i, i, i, i % 512)
+            rec = hdr + seq[o:o + L].tobytes() + b"\n+\n" + qual[o:o + L].tobytes() + b"\n"
+            parts.append(rec)
+            total += len(rec); o += L; i += 1
+            if total >= n_bytes:
+                break
+    return b"".join(parts)
+
+
+def timed(fn, reps):
+    import torch
+    fn(); torch.cuda.synchronize()
+    best = 1e30
+    for _ in range(reps):
+        torch.cuda.synchronize(); t = time.perf_counter(); fn(); torch.cuda.synchronize()
+        best = min(best, time.perf_counter() - t)
+    return best
+
+
+def cpu_counter(data, k, limit):
+    """Single-core neighbour: the same windows, counted with numpy (ACGT windows only, the odd ones are skipped)."""
+    buf = np.frombuffer(data[:limit], np.uint8)
+    t = time.perf_counter()
+    nl = np.flatnonzero(buf == 10)
+    starts = np.concatenate(([0], nl[:-1] + 1))
+    lut = np.full(256, 255, np.uint8)
+    for c, v in zip(b"ACGT", range(4)):
+        lut[c] = v
+    hist = np.zeros(4 ** k, np.int64)
+    for li in range(1, len(nl), 4):
+        line = buf[starts[li]:nl[li]]
+        if line.size < k:
+            continue
+        b = lut[line].astype(np.int64)
+        ok = b != 255
+        code = np.zeros(line.size - k + 1, np.int64)
+        good = np.ones(line.size - k + 1, bool)
+        for j in range(k):
+            code = code * 4 + (b[j:j + line.size - k + 1] & 3)
+            good &= ok[j:j + line.size - k + 1]
+        hist += np.bincount(code[good], minlength=4 ** k)
+    dt = time.perf_counter() - t
+    return int(nl[-1]) + 1 if len(nl) else len(buf), dt, int(hist.sum())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gb", type=float, default=2.0)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--cpu-mb", type=int, default=256)
+    ap.add_argument("--tmp", default="/tmp")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "kfreq_bench.json"))
+    a = ap.parse_args()
+    import torch
+    from poregen_amd.engine import KmerCounter
+    if not torch.cuda.is_available():
+        raise SystemExit("kfreq_bench: no GPU (this tool measures the device path; there is no CPU fallback)")
+
+    t0 = time.perf_counter()
+    data = synth(int(a.gb * 1e9))
+    n = len(data)
+    res = {"bytes": n, "gen_s": round(time.perf_counter() - t0, 1), "device_name": torch.cuda.get_device_name(0), "peak_hbm_GBps": 8000}
+    gbps = lambda nb, s: round(nb / s / 1e9, 2)
+
+    dev = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
+    res["device"] = {}
+    for k in (5, 9, 12):
+        kc = KmerCounter(k)
+        s = timed(lambda: (kc.submit(dev), kc.finish()), a.reps)
+        kc.close()
+        res["device"][f"k{k}"] = {"s": round(s, 4), "GBps": gbps(n, s), "of_hbm_peak": round(n / s / 8e12, 4)}
+    homo = torch.full((n,), ord("A"), dtype=torch.uint8, device="cuda")
+    homo[0] = ord("@"); homo[1] = 10; homo[n - 1] = 10
+    for k in (5, 9):
+        kc = KmerCounter(k)
+        s = timed(lambda: (kc.submit(homo), kc.finish()), a.reps)
+        kc.close()
+        res["device"][f"homopolymer_k{k}"] = {"s": round(s, 4), "GBps": gbps(n, s), "of_hbm_peak": round(n / s / 8e12, 4)}
+    del homo
+
+    pinned = torch.frombuffer(bytearray(data), dtype=torch.uint8).pin_memory()
+    pin_np = pinned.numpy()
+    kc = KmerCounter(9)
+    s_host = timed(lambda: (kc.submit(pin_np), kc.finish()), a.reps)
+    kc.close()
+    s_h2d = timed(lambda: dev.copy_(pinned, non_blocking=True), a.reps)
+    res["host_pinned"] = {"k9_s": round(s_host, 4), "k9_GBps": gbps(n, s_host), "h2d_GBps": gbps(n, s_h2d),
+                          "fraction_of_h2d": round(s_h2d / s_host, 3)}
+    del pinned, pin_np, dev
+    torch.cuda.empty_cache()
+
+    path = os.path.join(a.tmp, "kfreq_bench.fastq")
+    with open(path, "wb") as f:
+        f.write(data)
+    with open(path, "rb") as f:
+        while f.read(1 << 26):
+            pass
+    res["cli"] = {}
+    exe = os.path.join(ROOT, "bin", "poregen")
+    for sort in (0, 1):
+        best = 1e30
+        for _ in range(max(1, a.reps - 1)):
+            t = time.perf_counter()
+            r = subprocess.run([exe, "kmer_freq", "--sort", str(sort), "9", path], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=600)
+            best = min(best, time.perf_counter() - t)
+            if r.returncode:
+                raise SystemExit(r.stderr.decode()[-2000:])
+        res["cli"][f"k9_sort{sort}"] = {"s": round(best, 3), "GBps": gbps(n, best)}
+    t = time.perf_counter()
+    r = subprocess.run([exe, "kmer_freq", "--sort", "1", "12", path], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=900)
+    res["cli"]["k12_sort1"] = {"s": round(time.perf_counter() - t, 3), "GBps": gbps(n, time.perf_counter() - t), "lines": 4 ** 12}
+    os.unlink(path)
+
+    nb, s, windows = cpu_counter(data, 9, a.cpu_mb << 20)
+    res["cpu_numpy_1core_k9"] = {"bytes": nb, "s": round(s, 3), "GBps": gbps(nb, s), "windows": windows}
+    line = json.dumps(res)
+    print(line)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
