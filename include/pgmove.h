@@ -53,6 +53,14 @@
  *                                  other keys in byte order); sorting and printing,
  *                                  :194-220, stay with the caller
  * pg_kfreq_sync / pg_kfreq_last_error  (no counterpart)
+ *
+ * The F1-score metric (src/f1_score/f1score.py) has one too:
+ * pg_fscore_create / _destroy     args.rna / args.threshold / args.region         src/f1_score/f1score.py:59-66, 234-246
+ * pg_fscore_submit                 parse_ss_string + compare_mappings of every     src/f1_score/f1score.py:7-119, 135-153
+ *                                  compared pair (the dict rules, si parsing and
+ *                                  printing, :157-231, stay with the caller)
+ * pg_fscore_finish                 the TOT_* sums (per pair on request)            src/f1_score/f1score.py:224-229
+ * pg_fscore_sync / _last_error     (no counterpart)
  */
 #ifndef PGMOVE_H
 #define PGMOVE_H
@@ -458,6 +466,50 @@ pg_status pg_kfreq_sync(pg_kfreq *h);
 /* End of stream (the window ending on its last byte is dropped: the unterminated-final-line rule). counts_out: host u64[4^kmer_size].
  * The handle is reset afterwards, also after an error: the next submit starts a new stream. */
 pg_status pg_kfreq_finish(pg_kfreq *h, uint64_t *counts_out, pg_kfreq_result *out);
+
+/* ---- f1_score: per-signal-point agreement of two ss signal alignments, counted on the device ------------------------------------
+ * A batch holds n_pairs pairs of ss strings, concatenated: string 2p is side 1 (file 1) of pair p, string 2p+1 side 2; string s is
+ * bytes [ss_off[s], ss_off[s + 1]) of ss. Per string: the first signal index (si[0]) and the first reference position (si[2]; side 2
+ * with --base_shift added). Per pair (TP, FP, TN, FN) as f1score.py's evaluate_alignments counts them: op "<n>," maps n points to the
+ * current ref and steps it by dir (+1, or -1 with rna), "<n>I" maps n points to -1, "<n>D" steps the ref by dir * n, other letters do
+ * nothing; over the overlap of the two signal ranges a point counts TN / FP / FN by which ref is -1, then TP if |r1 - r2| <= threshold
+ * and FP otherwise; with use_region a point is skipped when region_start > r1 + 1 or region_end < r1 + 1.
+ * Refused, PG_ERR_INPUT from pg_fscore_finish with the first failing pair in pg_fscore_result: an empty ss, an ss ending in a digit, a byte
+ * >= 0x80, an op count >= 2^32, a side that maps no point. No CPU fallback: PG_ERR_NO_DEVICE without a GPU. */
+typedef struct pg_fscore pg_fscore;
+typedef struct {
+    int32_t rna;              /* dir = -1 */
+    int32_t use_region;
+    int64_t threshold;
+    int64_t region_start, region_end;
+} pg_fscore_params;
+typedef struct {
+    uint64_t n_pairs;
+    int32_t location;         /* PG_LOC_HOST or PG_LOC_DEVICE: where ss lies (ss_off / sig_start / first_ref are host arrays) */
+    int32_t reserved;
+    const uint8_t *ss;
+    const uint64_t *ss_off;   /* 2 * n_pairs + 1 non-decreasing offsets */
+    const int64_t *sig_start; /* 2 * n_pairs */
+    const int64_t *first_ref; /* 2 * n_pairs */
+} pg_fscore_batch;
+typedef struct {
+    uint64_t totals[4];       /* TP, FP, TN, FN over every pair submitted since the last finish */
+    uint64_t n_pairs;
+    int64_t err_pair;         /* PG_ERR_INPUT: the first failing pair (in submission order), else -1 */
+    uint32_t err_code;        /* 1 empty ss, 2 ss ends in a digit, 3 byte >= 0x80, 4 op count >= 2^32, 5 no signal point */
+    uint32_t err_side;        /* 0: side 1 (file 1), 1: side 2 */
+} pg_fscore_result;
+pg_status pg_fscore_create(const pg_fscore_params *params, int32_t device, pg_fscore **out);
+void      pg_fscore_destroy(pg_fscore *h);
+const char *pg_fscore_last_error(const pg_fscore *h); /* h may be NULL: error of the last failed pg_fscore_create */
+/* PG_LOC_HOST ss: any host memory, free for reuse when the call returns. PG_LOC_DEVICE ss: memory of the handle's device, complete
+ * before the call, read in place and unchanged until pg_fscore_sync or pg_fscore_finish. Pairs are cut into pieces of at most 32 MiB of ss
+ * (a larger pair makes a piece of its own), so device memory stays bounded. */
+pg_status pg_fscore_submit(pg_fscore *h, const pg_fscore_batch *batch);
+pg_status pg_fscore_sync(pg_fscore *h);
+/* totals (and, when pair_counts is set, host u64[4 * min(cap_pairs, n_pairs)] per pair) of every pair since the last finish. The
+ * handle is reset afterwards, also after an error. */
+pg_status pg_fscore_finish(pg_fscore *h, pg_fscore_result *out, uint64_t *pair_counts, uint64_t cap_pairs);
 
 #ifdef __cplusplus
 }

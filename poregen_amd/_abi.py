@@ -38,6 +38,7 @@ EXPORTS = [
     "pg_job_finish_deferred", "pg_job_fetch_samples", "pg_job_text", "pg_job_fetch_text",
     "pg_job_uses_rccl", "pg_job_model", "pg_job_kernel_stats", "pg_runtime_init", "pg_all_slots_full_settled", "pg_job_all_slots_full_settled", "pg_poll", "pg_job_poll",
     "pg_kfreq_create", "pg_kfreq_destroy", "pg_kfreq_last_error", "pg_kfreq_submit", "pg_kfreq_sync", "pg_kfreq_finish",
+    "pg_fscore_create", "pg_fscore_destroy", "pg_fscore_last_error", "pg_fscore_submit", "pg_fscore_sync", "pg_fscore_finish",
 ]
 PG_JOB_EXCHANGE_AUTO, PG_JOB_EXCHANGE_HOST, PG_JOB_EXCHANGE_RCCL = 0, 1, 2
 
@@ -98,6 +99,21 @@ class PgModelResult(C.Structure):
 class PgKfreqResult(C.Structure):
     _fields_ = [("kmer_size", C.c_uint32), ("reserved", C.c_uint32), ("n_odd", C.c_uint64),
                 ("odd_keys", C.c_void_p), ("odd_counts", C.c_void_p)]
+
+
+class PgF1Params(C.Structure):
+    _fields_ = [("rna", C.c_int32), ("use_region", C.c_int32), ("threshold", C.c_int64), ("region_start", C.c_int64),
+                ("region_end", C.c_int64)]
+
+
+class PgF1Batch(C.Structure):
+    _fields_ = [("n_pairs", C.c_uint64), ("location", C.c_int32), ("reserved", C.c_int32), ("ss", C.c_void_p),
+                ("ss_off", C.c_void_p), ("sig_start", C.c_void_p), ("first_ref", C.c_void_p)]
+
+
+class PgF1Result(C.Structure):
+    _fields_ = [("totals", C.c_uint64 * 4), ("n_pairs", C.c_uint64), ("err_pair", C.c_int64), ("err_code", C.c_uint32),
+                ("err_side", C.c_uint32)]
 
 
 class PgKernelStat(C.Structure):
@@ -198,5 +214,11 @@ def load():
     lib.pg_kfreq_submit.argtypes = [vp, vp, C.c_uint64, i32]; lib.pg_kfreq_submit.restype = i32
     lib.pg_kfreq_sync.argtypes = [vp]; lib.pg_kfreq_sync.restype = i32
     lib.pg_kfreq_finish.argtypes = [vp, vp, C.POINTER(PgKfreqResult)]; lib.pg_kfreq_finish.restype = i32
+    lib.pg_fscore_create.argtypes = [C.POINTER(PgF1Params), i32, C.POINTER(vp)]; lib.pg_fscore_create.restype = i32
+    lib.pg_fscore_destroy.argtypes = [vp]; lib.pg_fscore_destroy.restype = None
+    lib.pg_fscore_last_error.argtypes = [vp]; lib.pg_fscore_last_error.restype = C.c_char_p
+    lib.pg_fscore_submit.argtypes = [vp, C.POINTER(PgF1Batch)]; lib.pg_fscore_submit.restype = i32
+    lib.pg_fscore_sync.argtypes = [vp]; lib.pg_fscore_sync.restype = i32
+    lib.pg_fscore_finish.argtypes = [vp, C.POINTER(PgF1Result), vp, C.c_uint64]; lib.pg_fscore_finish.restype = i32
     _lib = lib
     return lib

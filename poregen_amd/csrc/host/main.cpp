@@ -1,4 +1,4 @@
-// main.cpp -- `poregen` dispatcher (src/main.c:64-103): the gmove and kmer_freq subtools (device path) and reform (host-only).
+// main.cpp -- `poregen` dispatcher (src/main.c:64-103): the gmove, kmer_freq and f1_score subtools (device path) and reform (host-only).
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -10,9 +10,11 @@
 #ifdef PG_REFORM_ONLY // the sanitizer build of the host-only subtool (Makefile: asan): no device code linked
 static int gmove_main(int, char **) { fprintf(stderr, "[poregen] this build holds reform only\n"); return 1; }
 static int kmer_freq_main(int, char **) { fprintf(stderr, "[poregen] this build holds reform only\n"); return 1; }
+static int f1_score_main(int, char **) { fprintf(stderr, "[poregen] this build holds reform only\n"); return 1; }
 #else
 int gmove_main(int argc, char **argv);
 int kmer_freq_main(int argc, char **argv);
+int f1_score_main(int argc, char **argv);
 #endif
 int reform_main(int argc, char **argv);
 
@@ -21,7 +23,7 @@ static double cputime() { struct rusage r; getrusage(RUSAGE_SELF, &r); return r.
 static long peakrss() { struct rusage r; getrusage(RUSAGE_SELF, &r); return r.ru_maxrss * 1024; }
 
 static int usage(FILE *fp, int code) {
-    fprintf(fp, "Usage: poregen <command> [options]\n\ncommand:\n         gmove      move k-mer signal samples into k-mer buckets (MI355X implementation)\n         reform     rewrite a SAM/BAM move table as TSV or as PAF with ss:Z:\n         kmer_freq  count the k-mers of the reads in a FASTQ file\n");
+    fprintf(fp, "Usage: poregen <command> [options]\n\ncommand:\n         gmove      move k-mer signal samples into k-mer buckets (MI355X implementation)\n         reform     rewrite a SAM/BAM move table as TSV or as PAF with ss:Z:\n         kmer_freq  count the k-mers of the reads in a FASTQ file\n         f1_score   compare two ss signal alignments (SAM/BAM) point by point: TP/FP/TN/FN, F1 score\n");
     return code;
 }
 
@@ -32,6 +34,7 @@ int main(int argc, char **argv) {
     if (strcmp(argv[1], "gmove") == 0) ret = gmove_main(argc - 1, argv + 1);
     else if (strcmp(argv[1], "reform") == 0) ret = reform_main(argc - 1, argv + 1);
     else if (strcmp(argv[1], "kmer_freq") == 0) ret = kmer_freq_main(argc - 1, argv + 1);
+    else if (strcmp(argv[1], "f1_score") == 0) ret = f1_score_main(argc - 1, argv + 1);
     else if (strcmp(argv[1], "--version") == 0 || strcmp(argv[1], "-V") == 0) { fprintf(stdout, "poregen 0.1.0 (pgmove, gfx950)\n"); return 0; }
     else if (strcmp(argv[1], "--help") == 0 || strcmp(argv[1], "-h") == 0) return usage(stdout, 0);
     else { fprintf(stderr, "[poregen] Unrecognised command %s\n", argv[1]); return usage(stderr, 1); }

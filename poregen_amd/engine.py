@@ -699,3 +699,92 @@ def kmer_freq(data, k: int, device: int = 0) -> KmerFreqResult:
         return kc.finish()
     finally:
         kc.close()
+
+
+@dataclass
+class F1Counts:
+    """(TP, FP, TN, FN) over all pairs (`totals`) and per pair (`pairs`, n x 4), as f1score.py's compare_files sums them."""
+    totals: np.ndarray
+    pairs: np.ndarray
+
+
+class AlignmentScorer:
+    """Compares pairs of ss signal alignments on the GPU (pg_fscore_*), the per-point rules of the reference's f1score.py. submit() takes
+    the ss strings of n pairs concatenated (string 2p = side 1, 2p + 1 = side 2 of pair p; `bytes`, numpy uint8, or a CUDA torch.uint8
+    tensor read in place and kept alive until finish), 2n + 1 offsets, and per string the first signal index and first reference
+    position (side 2 with base_shift already added). region = (start, end) applies f1score.py's --region point filter."""
+
+    def __init__(self, rna: bool = False, threshold: int = 0, region=None, device: int = 0):
+        self._lib = _abi.load()
+        p = _abi.PgF1Params(int(bool(rna)), int(region is not None), int(threshold),
+                            int(region[0]) if region is not None else 0, int(region[1]) if region is not None else 0)
+        h = C.c_void_p()
+        st = self._lib.pg_fscore_create(C.byref(p), device, C.byref(h))
+        if st != 0:
+            raise PgError(st, self._lib.pg_fscore_last_error(None).decode())
+        self._h = h
+        self._keep = []
+        self._n = 0
+        self.last_result = None
+
+    def _check(self, st):
+        if st != 0:
+            raise PgError(st, self._lib.pg_fscore_last_error(self._h).decode())
+
+    def submit(self, ss, offsets, sig_start, first_ref):
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        sig = np.ascontiguousarray(sig_start, dtype=np.int64)
+        ref = np.ascontiguousarray(first_ref, dtype=np.int64)
+        ns = off.size - 1
+        if ns < 0 or ns % 2 or sig.size != ns or ref.size != ns:
+            raise ValueError("need 2n + 1 offsets and 2n start signals / first refs")
+        if hasattr(ss, "is_cuda") and ss.is_cuda:
+            if ss.dtype.itemsize != 1 or not ss.is_contiguous():
+                raise ValueError("device ss must be a contiguous uint8 tensor")
+            self._keep.append(ss)
+            ptr, loc = ss.data_ptr(), _abi.PG_LOC_DEVICE
+        else:
+            a = np.ascontiguousarray(np.frombuffer(ss, np.uint8) if isinstance(ss, (bytes, bytearray, memoryview)) else ss, dtype=np.uint8)
+            if ns and int(off[-1]) > a.size:
+                raise ValueError("offsets run past the ss bytes")
+            ptr, loc = (a.ctypes.data if a.size else None), _abi.PG_LOC_HOST
+        b = _abi.PgF1Batch(ns // 2, loc, 0, ptr, off.ctypes.data, sig.ctypes.data, ref.ctypes.data)
+        self._check(self._lib.pg_fscore_submit(self._h, C.byref(b)))
+        self._n += ns // 2
+
+    def finish(self) -> F1Counts:
+        r = _abi.PgF1Result()
+        n_cap = self._n
+        pairs = np.zeros((max(n_cap, 1), 4), np.uint64)
+        self._n = 0
+        try:
+            st = self._lib.pg_fscore_sync(self._h)
+            self._check(st)
+            st = self._lib.pg_fscore_finish(self._h, C.byref(r), C.c_void_p(pairs.ctypes.data), n_cap)
+            self.last_result = r
+            self._check(st)
+        finally:
+            self._keep = []
+        n = int(r.n_pairs)
+        return F1Counts(np.array(list(r.totals), np.uint64), pairs[:n].copy())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.pg_fscore_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def f1_counts(ss, offsets, sig_start, first_ref, rna: bool = False, threshold: int = 0, region=None, device: int = 0) -> F1Counts:
+    """One-shot AlignmentScorer: totals and per-pair (TP, FP, TN, FN)."""
+    sc = AlignmentScorer(rna, threshold, region, device)
+    try:
+        sc.submit(ss, offsets, sig_start, first_ref)
+        return sc.finish()
+    finally:
+        sc.close()

@@ -508,3 +508,150 @@ def write_paf_fastq(b: Batch, prefix: str):
         for r in range(b.n_reads):
             L = int(b.sig_off[r + 1] - b.sig_off[r]); ns = int(b.seq_off[r + 1] - b.seq_off[r])
             f.write(f"r{r}\t{L}\t{int(b.query_start[r])}\t{L}\t+\tr{r}\t{ns}\t{int(b.target_start[r])}\t{int(b.target_end[r])}\t{ns}\t{ns}\t255\tss:Z:{ss_string(b, r)}\n")
+
+
+def _ops_to_ss(counts: np.ndarray, kinds: np.ndarray) -> bytes:
+    """ss text of ops given as counts (0..999) and kind bytes (b',', b'I', b'D', ...), built without a Python loop per op."""
+    c = np.asarray(counts, np.int64)
+    nd = 1 + (c >= 10) + (c >= 100)
+    width = nd + 1
+    end = np.cumsum(width)
+    start = end - width
+    out = np.zeros(int(end[-1]) if c.size else 0, np.uint8)
+    for k in range(3):  # digit k counted from the right
+        m = nd > k
+        out[(start + nd - 1 - k)[m]] = (48 + (c[m] // 10 ** k) % 10).astype(np.uint8)
+    out[end - 1] = np.asarray(kinds, np.uint8)
+    return out.tobytes()
+
+
+def alignment_pairs(lengths, seed=20261016, rna=False, dwell_mean=9.0, indel_rate=0.03, max_shift=0.1, ref_jitter=2):
+    """Seeded pairs of ss signal alignments for the F1-score metric: pair p is (a truth-like alignment of lengths[p] signal points,
+    a perturbed copy). Side 1: "<n>," ops with geometric dwell, "<n>I" and "<k>D" ops at `indel_rate`. Side 2: every ',' boundary
+    moved by -1..1 points, extra I / D ops, its signal start moved by up to max_shift of the read (partial overlap) and its first
+    reference position by up to ref_jitter. Returns a list of (name, ss1, si1, ss2, si2) with ss as bytes and si as text
+    ("sig_start,sig_end,ref_a,ref_b"; the metric reads si[0] and si[2])."""
+    rng = np.random.default_rng(seed)
+    out = []
+    kc, ki, kd = ord(","), ord("I"), ord("D")
+    for p, L in enumerate(np.asarray(lengths, np.int64)):
+        L = int(L)
+        n_ops = max(1, int(L / dwell_mean * 1.1) + 8)
+        cnt = np.minimum(rng.geometric(1.0 / dwell_mean, n_ops), 999)
+        kind = np.full(n_ops, kc, np.uint8)
+        r = rng.random(n_ops)
+        kind[r < indel_rate] = ki
+        dm = (r >= indel_rate) & (r < 2 * indel_rate)
+        kind[dm] = kd
+        cnt[dm] = rng.integers(1, 4, int(dm.sum()))
+        cs = np.cumsum(np.where(kind == kd, 0, cnt))
+        keep = int(np.searchsorted(cs, L, side="left")) + 1
+        cnt, kind = cnt[:keep].copy(), kind[:keep].copy()
+        pts = np.where(kind == kd, 0, cnt)
+        over = int(pts.sum()) - L
+        if over > 0 and kind[-1] != kd:
+            cnt[-1] -= over
+        if kind[-1] == kd or cnt[-1] <= 0:
+            cnt[-1], kind[-1] = max(1, int(cnt[-1])), kc
+        sig0 = int(rng.integers(0, 5000))
+        ref0 = int(rng.integers(1000, 10 ** 7))
+        if rna:
+            ref0 += 10 ** 6
+        n_steps = int(np.where(kind == kc, 1, np.where(kind == kd, cnt, 0)).sum())
+        ref_end = ref0 - n_steps if rna else ref0 + n_steps
+        ss1 = _ops_to_ss(cnt, kind)
+        P1 = int(np.where(kind == kd, 0, cnt).sum())
+        si1 = f"{sig0},{sig0 + P1},{ref0},{ref_end}"
+        # side 2: moved boundaries, extra indels, shifted window and first ref
+        c2 = cnt.copy()
+        m = kind == kc
+        c2[m] = np.clip(c2[m] + rng.integers(-1, 2, int(m.sum())), 1, 999)
+        k2 = kind.copy()
+        extra = rng.random(c2.size) < indel_rate
+        c2 = np.insert(c2, np.nonzero(extra)[0], rng.integers(1, 4, int(extra.sum())))
+        k2 = np.insert(k2, np.nonzero(extra)[0], np.where(rng.random(int(extra.sum())) < 0.5, ki, kd).astype(np.uint8))
+        if k2[-1] == kd:
+            k2[-1] = kc
+        P2 = int(np.where(k2 == kd, 0, c2).sum())
+        shift = int(rng.integers(-int(max_shift * L), int(max_shift * L) + 1))
+        sig2 = max(0, sig0 + shift)
+        ref2 = ref0 + int(rng.integers(-ref_jitter, ref_jitter + 1))
+        si2 = f"{sig2},{sig2 + P2},{ref2},{ref_end}"
+        out.append((f"read_{p}", ss1, si1, _ops_to_ss(c2, k2), si2))
+    return out
+
+
+def _cigar_rlen(cigar: str) -> int:
+    n, t = 0, 0
+    for ch in cigar:
+        if ch.isdigit():
+            n = n * 10 + int(ch)
+        else:
+            t += n if ch in "MDN=X" else 0
+            n = 0
+    return t
+
+
+def write_alignment_sam(path, records, contigs=(("chr1", 1 << 30),)):
+    """records: dicts with name, ss (bytes), si (str) and optional flag (0), rname ('chr1'), pos (1-based, 1), cigar ('10M'),
+    extra (list of additional tag strings). Written as SAM text with @SQ lines for `contigs`."""
+    with open(path, "wb") as f:
+        f.write(b"@HD\tVN:1.6\tSO:coordinate\n")
+        for name, ln in contigs:
+            f.write(f"@SQ\tSN:{name}\tLN:{ln}\n".encode())
+        for r in records:
+            tags = []
+            if r.get("ss") is not None:
+                tags.append(b"ss:Z:" + r["ss"])
+            if r.get("si") is not None:
+                tags.append(b"si:Z:" + r["si"].encode())
+            tags += [t.encode() for t in r.get("extra", [])]
+            cols = [r["name"].encode(), str(r.get("flag", 0)).encode(), r.get("rname", "chr1").encode(), str(r.get("pos", 1)).encode(),
+                    b"60", r.get("cigar", "10M").encode(), b"*", b"0", b"0", b"*", b"*"] + tags
+            f.write(b"\t".join(cols) + b"\n")
+
+
+def write_alignment_bam(path, records, contigs=(("chr1", 1 << 30),), block_bytes=60000):
+    """The records of write_alignment_sam as BAM (BGZF blocks as write_bam writes them)."""
+    import struct
+    import zlib
+    ops = "MIDNSHP=X"
+    text = b"@HD\tVN:1.6\tSO:coordinate\n" + b"".join(f"@SQ\tSN:{n}\tLN:{ln}\n".encode() for n, ln in contigs)
+    raw = bytearray(b"BAM\x01" + struct.pack("<i", len(text)) + text + struct.pack("<i", len(contigs)))
+    tid = {}
+    for i, (n, ln) in enumerate(contigs):
+        raw += struct.pack("<i", len(n) + 1) + n.encode() + b"\x00" + struct.pack("<i", ln)
+        tid[n] = i
+    for r in records:
+        cig = r.get("cigar", "10M")
+        cigar = []
+        if cig != "*":
+            num = 0
+            for ch in cig:
+                if ch.isdigit():
+                    num = num * 10 + int(ch)
+                else:
+                    cigar.append(num << 4 | ops.index(ch)); num = 0
+        name = r["name"].encode() + b"\x00"
+        tags = b""
+        if r.get("ss") is not None:
+            tags += b"ssZ" + r["ss"] + b"\x00"
+        if r.get("si") is not None:
+            tags += b"siZ" + r["si"].encode() + b"\x00"
+        for t in r.get("extra", []):
+            k, ty, v = t.split(":", 2)
+            tags += k.encode() + (b"Z" + v.encode() + b"\x00" if ty == "Z" else b"i" + struct.pack("<i", int(v)))
+        rn = r.get("rname", "chr1")
+        body = (struct.pack("<iiBBHHHiiii", tid.get(rn, -1), int(r.get("pos", 1)) - 1, len(name), 60, 4680, len(cigar), int(r.get("flag", 0)),
+                            0, -1, -1, 0) + name + b"".join(struct.pack("<I", c) for c in cigar) + tags)
+        raw += struct.pack("<i", len(body)) + body
+    with open(path, "wb") as f:
+        def block(data: bytes):
+            c = zlib.compressobj(6, zlib.DEFLATED, -15)
+            comp = c.compress(data) + c.flush()
+            bsize = 18 + len(comp) + 8 - 1
+            f.write(b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + struct.pack("<H", bsize) + comp
+                    + struct.pack("<II", zlib.crc32(data) & 0xffffffff, len(data)))
+        for o in range(0, len(raw), block_bytes):
+            block(bytes(raw[o:o + block_bytes]))
+        block(b"")
