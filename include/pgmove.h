@@ -103,8 +103,8 @@ enum {
                                      chain's workgroups find room. Pays when batches follow each other (configs[1]: 0.162 -> 0.141 ms per
                                      batch). Every kernel then shares the chip: per-kernel timings (PG_FLAG_PROFILE, bench.py's roofline
                                      object) are taken on one stream. Setting the flag explicitly asks for the mode where it is not the
-                                     default; PGMOVE_GATHER_SIDE=1 additionally puts the gather of batch i beside the chain of batch i+1
-                                     (measured: 0-5 %, profiles/r04_side_gather.txt). */
+                                     default. The gather stays on the chain's stream (beside the chain of batch i+1 it was worth 0-5 %,
+                                     profiles/r04_side_gather.txt). */
     PG_FLAG_SHORT_READS_OK = 1u << 4, /* a read with fewer than k matched bases simply has no events (move-table front-end,
                                         where that is well defined); default: PG_ERR_INPUT, because the PAF path of the
                                         reference has undefined behaviour there (src/gmove.cpp:891) */

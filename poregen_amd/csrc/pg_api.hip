@@ -60,13 +60,10 @@ struct ProfEntry { const char *name; hipEvent_t a, b; bool bracket; };
 struct pg_ctx {
     pg_params prm{};
     int device = 0;
-    hipStream_t st = nullptr, st2 = nullptr, st3 = nullptr, own_st = nullptr; // st3: the gather of a two-stream context (created at its first use)
+    hipStream_t st = nullptr, st2 = nullptr, own_st = nullptr;
     hipEvent_t ev_fork = nullptr;
     hipEvent_t ev_join[2] = {nullptr, nullptr}, ev_gathered[2] = {nullptr, nullptr}; // per statistics slot
     bool slot_used[2] = {false, false};
-    // the kept records, their offsets, totals and chunk sums exist twice only for the side gather (PGMOVE_GATHER_SIDE: batch i's gather beside batch
-    // i + 1's chain); without it one set serves every batch (the chain of batch i + 1 follows the gather of batch i on its stream): rslot = 0
-    int rslot = 0; bool side_enabled = false;
     PgSettlePack *settle_host = nullptr; // host-mapped: what settle_batch learns of a finished batch, packed by one launch (k_settle_pack)
     int slot = 0; // statistics buffers are double-buffered so that batch i+1's statistics overlap batch i's tail
     bool user_stream = false, batch_is_host = false;
@@ -80,21 +77,23 @@ struct pg_ctx {
     // per-batch work buffers
     DevBuf m_start, m_len, m_base, m_tix, ev_slot, status, errflag;
     DevBuf sk[2], sv[2], hist, wcnt, totals, dbase, scount;
-    DevBuf slot_start, slot_end, acc_cnt, running, keep, keep32, ev_off, plan_totals[2], base_stage, tile_last; // plan_totals, chunk_part: per statistics slot (the gather of batch i may run beside the chain of batch i + 1)
-    DevBuf ev_rec[2], ev_len, ev_read, read_needed, samp_off[2], scan_scratch, samples; // ev_rec, samp_off: per statistics slot, like plan_totals // ev_len / ev_read: unpacked from the records on demand (ensure_unpacked)
+    // plan_totals, ev_rec, samp_off and chunk_part exist once: the chain of batch i + 1 follows the gather of batch i on the main stream
+    DevBuf slot_start, slot_end, acc_cnt, running, keep, keep32, ev_off, plan_totals, base_stage, tile_last;
+    DevBuf ev_rec, ev_len, ev_read, read_needed, samp_off, scan_scratch, samples; // ev_len / ev_read: unpacked from the records on demand (ensure_unpacked)
     bool unpacked = false;
     uint32_t win_hint = 0; // mean kept window of the last settled batch (samples): picks the gather's lanes per event
     // partitioned ranking (1024 < slots <= 2^20; pg_place.hip)
     bool part_mode = false; uint32_t part_hi = 0, part_lo = 0;
-    DevBuf part_elem, part_lodig, part_rbase, part_tile_region, part_ntiles, part_histB, part_Bp, chunk_part[2], region_state; uint32_t region_epoch = 0; // region_state / region_epoch: k_region_scan_cut
-    bool gather_side = false; int gather_side_slot = 0; bool side_used[2] = {false, false}; // the last chunked gather was queued on the second stream (two-stream mode) and nothing on `st` has waited for it yet
+    DevBuf part_elem, part_lodig, part_rbase, part_tile_region, part_ntiles, part_histB, part_Bp, chunk_part, region_state; uint32_t region_epoch = 0; // region_state / region_epoch: k_region_scan_cut
     DevBuf med[2], mad[2], gcal[2], read_plan[2], stat_status[2], stat_err[2], wide_list[2];
     bool stat_flags_reset = false; // stat_err[slot] was reset by k_batch_init of the current batch
     // long-read counters (PgLongState::cnt), a ring of four entries of four words: batch number b uses entry b & 3 and its k_batch_init zeroes
     // entry (b + 2) & 3. Round 5 kept them beside the statistics flags of the two slots, zeroed by the batch in front -- but the reservations
     // of batch b + 1 (k_read_plan on the statistics stream, released by the gather of batch b - 1) are not ordered behind k_batch_init of
     // batch b on the chain's stream: both start when that gather ends, and a zero could wipe reservations. Two batches of distance put the
-    // zeroing in front of the gather the reserving launch waits for.
+    // zeroing in front of the gather the reserving launch waits for. They also put it behind the entry's last reader: k_read_stats of batch b
+    // (statistics stream) precedes ev_join of batch b, the gather of batch b (chain's stream) waits for that event, and k_batch_init of batch
+    // b + 2, which zeroes entry b & 3, follows that gather on the chain's stream.
     DevBuf long_ring; uint32_t long_seq = 0;
     DevBuf meta, huge_scratch, oor;
     DevBuf blk_read, gen_flag, gen_list, cum, btot, tile_read; // PgWalkOut: owner index, generic-read list, block sums of op_n
@@ -259,16 +258,15 @@ void pg_destroy(pg_ctx *c) {
     (void)hipSetDevice(c->device);
     if (c->st) (void)hipStreamSynchronize(c->st);
     if (c->st2) (void)hipStreamSynchronize(c->st2);
-    if (c->st3) (void)hipStreamSynchronize(c->st3);
     if (c->settle_host) (void)hipHostFree(c->settle_host);
     DevBuf *bufs[] = {&c->table_t, &c->table_u, &c->s_sig, &c->s_sig_off, &c->s_dig, &c->s_off, &c->s_range, &c->s_qs, &c->s_ts,
                       &c->s_te, &c->s_seq, &c->s_seq_off, &c->s_op_n, &c->s_op_t, &c->s_op_off, &c->m_start, &c->m_len, &c->m_base,
                       &c->m_tix, &c->ev_slot, &c->status, &c->errflag, &c->sk[0], &c->sk[1], &c->sv[0], &c->sv[1],
                       &c->hist, &c->wcnt, &c->totals, &c->dbase, &c->scount, &c->slot_start, &c->slot_end, &c->acc_cnt, &c->running,
-                      &c->keep, &c->keep32, &c->tile_last, &c->ev_off, &c->plan_totals[0], &c->plan_totals[1], &c->base_stage, &c->dmerged, &c->dseg, &c->ev_rec[0], &c->ev_rec[1], &c->ev_len, &c->ev_read, &c->read_needed,
+                      &c->keep, &c->keep32, &c->tile_last, &c->ev_off, &c->plan_totals, &c->base_stage, &c->dmerged, &c->dseg, &c->ev_rec, &c->ev_len, &c->ev_read, &c->read_needed,
                       &c->tx_samp_off, &c->tx_ev_off, &c->tx_len, &c->tx_off, &c->tx_text, &c->tx_slot_off, &c->tx_flag,
-                      &c->part_elem, &c->part_lodig, &c->part_rbase, &c->part_tile_region, &c->part_ntiles, &c->part_histB, &c->part_Bp, &c->chunk_part[0], &c->chunk_part[1], &c->region_state,
-                      &c->samp_off[0], &c->samp_off[1], &c->cancel_flag, &c->long_tab, &c->long_hist, &c->long_ring, &c->scan_scratch, &c->samples, &c->med[0], &c->mad[0], &c->gcal[0], &c->gcal[1], &c->read_plan[0], &c->stat_status[0], &c->stat_err[0], &c->wide_list[0],
+                      &c->part_elem, &c->part_lodig, &c->part_rbase, &c->part_tile_region, &c->part_ntiles, &c->part_histB, &c->part_Bp, &c->chunk_part, &c->region_state,
+                      &c->samp_off, &c->cancel_flag, &c->long_tab, &c->long_hist, &c->long_ring, &c->scan_scratch, &c->samples, &c->med[0], &c->mad[0], &c->gcal[0], &c->gcal[1], &c->read_plan[0], &c->stat_status[0], &c->stat_err[0], &c->wide_list[0],
                       &c->med[1], &c->mad[1], &c->read_plan[1], &c->stat_status[1], &c->stat_err[1], &c->wide_list[1], &c->meta, &c->huge_scratch, &c->oor,
                       &c->blk_read, &c->gen_flag, &c->gen_list, &c->cum, &c->btot, &c->tile_read,
                       &c->job_total, &c->job_freq, &c->md_ev_off, &c->md_samp_off, &c->md_ev_len, &c->md_samples, &c->md_out, &c->md_dwell, &c->md_class};
@@ -280,7 +278,6 @@ void pg_destroy(pg_ctx *c) {
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->own_st) (void)hipStreamDestroy(c->own_st);
     if (c->st2) (void)hipStreamDestroy(c->st2);
-    if (c->st3) (void)hipStreamDestroy(c->st3);
     delete c;
 }
 
@@ -323,8 +320,7 @@ pg_status pg_create(const pg_params *p, pg_ctx **out) {
     pg_ctx *c = new pg_ctx();
     c->prm = *p;
     // two-stream mode is the default wherever it applies (include/pgmove.h: PG_FLAG_ONE_STREAM)
-    if (!(p->flags & (PG_FLAG_ONE_STREAM | PG_FLAG_PROFILE | PG_FLAG_LAZY_STATS | PG_FLAG_SKIP_OUT_OF_RANGE | PG_FLAG_DEFER_STATS | PG_FLAG_OVERLAP_TAIL)) && p->scaling == 1 &&
-        !getenv("PGMOVE_ONE_STREAM"))
+    if (!(p->flags & (PG_FLAG_ONE_STREAM | PG_FLAG_PROFILE | PG_FLAG_LAZY_STATS | PG_FLAG_SKIP_OUT_OF_RANGE | PG_FLAG_DEFER_STATS | PG_FLAG_OVERLAP_TAIL)) && p->scaling == 1)
         c->prm.flags |= PG_FLAG_OVERLAP;
     c->device = p->device;
     c->n_codes = 1u << (2 * p->kmer_size);
@@ -382,7 +378,6 @@ pg_status pg_create(const pg_params *p, pg_ctx **out) {
     };
     for (int i = 0; i < 2; i++) { CTRY(make_event(&c->ev_join[i])); CTRY(make_event(&c->ev_gathered[i])); }
     CTRY(make_event(&c->ev_fork));
-    c->side_enabled = getenv("PGMOVE_GATHER_SIDE") != nullptr;
     CTRY(hipHostMalloc((void **)&c->settle_host, sizeof(PgSettlePack), hipHostMallocDefault));
     const size_t tb = (size_t)c->n_codes * sizeof(int32_t);
     // one allocation, the U-spelled table right behind the T-spelled one: a kernel reaches both from ONE uniform base with a 32-bit
@@ -409,11 +404,11 @@ pg_status pg_create(const pg_params *p, pg_ctx **out) {
     const uint32_t ns = p->n_slots;
     CTRY(c->slot_start.ensure(ns * 4ull)); CTRY(c->slot_end.ensure(ns * 4ull));
     CTRY(c->acc_cnt.ensure(ns * 8ull)); CTRY(c->running.ensure(ns * 8ull)); CTRY(c->keep.ensure(ns * 8ull)); CTRY(c->tile_last.ensure(ns * 4ull));
-    CTRY(c->ev_off.ensure((ns + 1) * 8ull)); CTRY(c->plan_totals[0].ensure(64)); CTRY(c->plan_totals[1].ensure(64)); CTRY(c->base_stage.ensure(ns * 8ull));
+    CTRY(c->ev_off.ensure((ns + 1) * 8ull)); CTRY(c->plan_totals.ensure(64)); CTRY(c->base_stage.ensure(ns * 8ull));
     CTRY(c->job_total.ensure(ns * 8ull)); CTRY(c->job_freq.ensure(ns * 8ull)); // allocated once: callers may cache the pointers
     CTRY(c->totals.ensure(256 * 4)); CTRY(c->dbase.ensure(256 * 4)); CTRY(c->scount.ensure(16)); CTRY(c->errflag.ensure(32));
     CTRY(hipMemset(c->errflag.p, 0, 32)); // [0] u64 error word, [8] i32 layout flag, [16] u32 gen_count[2] (PgWalkOut), [24] u32 ticket (k_rank_scan)
-    CTRY(c->stat_err[0].ensure(32)); CTRY(c->stat_err[1].ensure(32)); // [0..2] statistics flags, [3] pg_div_domain_ok failed, [4..5] long-read counters (PgLongState::cnt)
+    CTRY(c->stat_err[0].ensure(32)); CTRY(c->stat_err[1].ensure(32)); // [0..2] statistics flags, [3] pg_div_domain_ok failed (the long-read counters live in long_ring)
     CTRY(hipMemset(c->stat_err[0].p, 0, 32)); CTRY(hipMemset(c->stat_err[1].p, 0, 32));
     CTRY(c->long_ring.ensure(64)); CTRY(hipMemset(c->long_ring.p, 0, 64));
     CTRY(hipMemset(c->running.p, 0, ns * 8ull));
@@ -429,7 +424,6 @@ pg_status pg_reset(pg_ctx *c) {
     if (c->prm.flags & PG_FLAG_PROFILE) {
         HIP_TRY(c, hipStreamSynchronize(c->st));
         if (c->st2) HIP_TRY(c, hipStreamSynchronize(c->st2));
-    if (c->st3) HIP_TRY(c, hipStreamSynchronize(c->st3));
         prof_drain(c);
     }
     // the running per-slot counts are zeroed by the next batch's init kernel (stream order is enough)
@@ -461,7 +455,7 @@ static pg_status download_last(pg_ctx *c, bool more_coming) {
     HIP_TRY(c, hipMemcpy(h.ev_off.data(), c->ev_off.p, (ns + 1) * 8ull, hipMemcpyDeviceToHost));
     if (h.n_events) {
         { pg_status su = ensure_unpacked(c); if (su != PG_OK) return su; }
-        HIP_TRY(c, hipMemcpy(h.samp_off.data(), c->samp_off[c->rslot].p, (h.n_events + 1) * 8ull, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(h.samp_off.data(), c->samp_off.p, (h.n_events + 1) * 8ull, hipMemcpyDeviceToHost));
         HIP_TRY(c, hipMemcpy(h.ev_len.data(), c->ev_len.p, h.n_events * 4ull, hipMemcpyDeviceToHost));
         HIP_TRY(c, hipMemcpy(h.ev_read.data(), c->ev_read.p, h.n_events * 4ull, hipMemcpyDeviceToHost));
     } else h.samp_off[0] = 0;
@@ -718,7 +712,7 @@ static int gather_lanes(const pg_ctx *c) {
 // (PGMOVE_DENSE_MIN=n lowers the bound: tests and the fuzzers run small jobs through the kernels built for many kept events)
 static uint64_t dense_min() { const char *e = getenv("PGMOVE_DENSE_MIN"); return e ? strtoull(e, nullptr, 10) : 64ull * 4096; }
 static bool dense_direct(const pg_ctx *c, uint64_t n_ops) {
-    return c->prm.n_slots <= PG_DIRECT_MAX_SLOTS && std::min<uint64_t>(n_ops, (uint64_t)c->prm.n_slots * c->prm.sample_limit) > dense_min() && !getenv("PGMOVE_EMIT1");
+    return c->prm.n_slots <= PG_DIRECT_MAX_SLOTS && std::min<uint64_t>(n_ops, (uint64_t)c->prm.n_slots * c->prm.sample_limit) > dense_min();
 }
 
 static void fill_part(pg_ctx *c, PgPartBufs &P, uint64_t n_ops) {
@@ -731,7 +725,7 @@ static void fill_part(pg_ctx *c, PgPartBufs &P, uint64_t n_ops) {
 static pg_status ensure_unpacked(pg_ctx *c) {
     if (c->unpacked) return PG_OK;
     HIP_TRY(c, c->ev_len.ensure((c->cur_n_kept + 1) * 4)); HIP_TRY(c, c->ev_read.ensure((c->cur_n_kept + 1) * 4));
-    HIP_TRY(c, pg_launch_unpack_recs(c->st, c->ev_rec[c->rslot].as<PgKeptRec>(), c->cur_n_kept, c->ev_len.as<uint32_t>(), c->ev_read.as<uint32_t>()));
+    HIP_TRY(c, pg_launch_unpack_recs(c->st, c->ev_rec.as<PgKeptRec>(), c->cur_n_kept, c->ev_len.as<uint32_t>(), c->ev_read.as<uint32_t>()));
     HIP_TRY(c, hipStreamSynchronize(c->st));
     c->unpacked = true;
     return PG_OK;
@@ -757,10 +751,6 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
     c->batch_is_host = b->location == PG_LOC_HOST;
     c->batch_all_matches = (b->flags & PG_BATCH_ALL_MATCHES) != 0 && !(c->prm.flags & PG_FLAG_DEBUG_SPLIT_WALK);
     if (b->location == PG_LOC_HOST) {
-        if (c->gather_side) { // the staging buffers still hold the batch whose gather runs on the second stream
-            HIP_TRY(c, hipStreamWaitEvent(c->st, c->ev_gathered[c->gather_side_slot], 0));
-            c->gather_side = false;
-        }
         s = stage_host_batch(c, b);
         if (s != PG_OK) return s;
         PG_TMARK("count: staging copies queued");
@@ -808,7 +798,7 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
     uint32_t ndig;
     if (direct) {
         ndig = 2; while (ndig < c->prm.n_slots) ndig <<= 1;
-        if (dense_direct(c, N)) { HIP_TRY(c, c->part_Bp.ensure((Nn / 256 + 4) * 4)); HIP_TRY(c, c->chunk_part[0].ensure(PG_CHUNK_PART_N * 8)); if (c->side_enabled) HIP_TRY(c, c->chunk_part[1].ensure(PG_CHUNK_PART_N * 8)); }
+        if (dense_direct(c, N)) { HIP_TRY(c, c->part_Bp.ensure((Nn / 256 + 4) * 4)); HIP_TRY(c, c->chunk_part.ensure(PG_CHUNK_PART_N * 8)); }
     }
     else if (c->part_mode) {
         ndig = 1u << c->part_hi;
@@ -816,7 +806,7 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
         HIP_TRY(c, c->part_elem.ensure((size_t)tcap * PG_SORT_TILE * 16)); HIP_TRY(c, c->part_lodig.ensure((size_t)tcap * PG_SORT_TILE * 2)); HIP_TRY(c, c->part_rbase.ensure((ndig + 2) * 4ull));
         HIP_TRY(c, c->part_tile_region.ensure((tcap + 1) * 4ull)); HIP_TRY(c, c->part_ntiles.ensure(16));
         HIP_TRY(c, c->part_histB.ensure(((size_t)tcap << c->part_lo) * 4)); HIP_TRY(c, c->part_Bp.ensure((Nn / 256 + 4) * 4));
-        HIP_TRY(c, c->chunk_part[0].ensure(PG_CHUNK_PART_N * 8)); if (c->side_enabled) HIP_TRY(c, c->chunk_part[1].ensure(PG_CHUNK_PART_N * 8));
+        HIP_TRY(c, c->chunk_part.ensure(PG_CHUNK_PART_N * 8));
     } else {
         const uint32_t passes = (c->key_bits + PG_RANK_MAX_BITS - 1) / PG_RANK_MAX_BITS;
         ndig = 1u << ((c->key_bits + passes - 1) / passes);
@@ -830,7 +820,6 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
     PG_TMARK("count: work buffers");
     c->full_before_batch = c->full_slots == c->prm.n_slots && c->prm.n_slots > 0;
     c->slot ^= 1; // this batch's statistics buffers
-    c->rslot = c->side_enabled ? c->slot : 0;
     const bool skip_oor = (c->prm.flags & PG_FLAG_SKIP_OUT_OF_RANGE) != 0; // statistics first: the walk needs their verdict
     const bool eager_stats = skip_oor || (c->prm.scaling == 1 && !(c->prm.flags & PG_FLAG_LAZY_STATS));
     const bool overlap = !skip_oor && (c->prm.flags & PG_FLAG_OVERLAP) != 0;
@@ -889,8 +878,8 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
         const bool fuse_plan = c->in_submit;
         HIP_TRY(c, pg_launch_rank_direct_count(c->st, O.ev_slot, N, c->prm.n_slots, S, c->acc_cnt.as<uint64_t>(), c->running.as<uint64_t>(), c->prm.sample_limit,
                                     c->tile_last.as<int32_t>(), acc_copy, fuse_plan ? c->keep.as<uint64_t>() : nullptr, c->ev_off.as<uint64_t>(),
-                                    c->plan_totals[c->rslot].as<uint64_t>(), c->errflag.as<uint32_t>() + 6, &c->plan_done,
-                                    O.btot, dense_direct(c, N) ? c->part_Bp.as<uint32_t>() : nullptr, dense_direct(c, N) ? c->chunk_part[c->rslot].as<uint64_t>() : nullptr));
+                                    c->plan_totals.as<uint64_t>(), c->errflag.as<uint32_t>() + 6, &c->plan_done,
+                                    O.btot, dense_direct(c, N) ? c->part_Bp.as<uint32_t>() : nullptr, dense_direct(c, N) ? c->chunk_part.as<uint64_t>() : nullptr));
         prof_end(c, c->st);
     } else if (c->part_mode) {
         // partitioned ranking, pass A and the counts of pass B (pg_place.hip): everything pg_count's result needs
@@ -898,7 +887,7 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
         fill_part(c, P, Nn);
         if (N) {
             prof_begin(c, "part_tile_scan", c->st);
-            HIP_TRY(c, pg_launch_part_tile_scan(c->st, P, N, O.btot, c->chunk_part[c->rslot].as<uint64_t>()));
+            HIP_TRY(c, pg_launch_part_tile_scan(c->st, P, N, O.btot, c->chunk_part.as<uint64_t>()));
             prof_end(c, c->st);
             prof_begin(c, "k_part_bases", c->st);
             HIP_TRY(c, pg_launch_part_bases(c->st, P, c->B, O));
@@ -915,7 +904,7 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
                 if (c->region_state.cap != before) HIP_TRY(c, hipMemsetAsync(c->region_state.p, 0, c->region_state.cap, c->st));
                 if (++c->region_epoch > pg_region_cut_epochs()) { c->region_epoch = 1; HIP_TRY(c, hipMemsetAsync(c->region_state.p, 0, c->region_state.cap, c->st)); }
                 HIP_TRY(c, c->keep32.ensure(c->prm.n_slots * 4ull));
-                cut.running = c->running.as<uint64_t>(); cut.keep = c->keep.as<uint64_t>(); cut.ev_off = c->ev_off.as<uint64_t>(); cut.totals = c->plan_totals[c->rslot].as<uint64_t>();
+                cut.running = c->running.as<uint64_t>(); cut.keep = c->keep.as<uint64_t>(); cut.ev_off = c->ev_off.as<uint64_t>(); cut.totals = c->plan_totals.as<uint64_t>();
                 cut.keep32 = c->keep32.as<uint32_t>(); cut.state = c->region_state.as<uint64_t>(); cut.limit = c->prm.sample_limit; cut.epoch = c->region_epoch;
             }
             prof_begin(c, "region_counts", c->st, true);
@@ -1030,7 +1019,7 @@ static pg_status collect_impl(pg_ctx *c, const uint64_t *base, int32_t base_loca
                                   base_location == PG_LOC_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->st));
         d_base = c->base_stage.as<uint64_t>();
     }
-    uint64_t *totals = c->plan_totals[c->rslot].as<uint64_t>();
+    uint64_t *totals = c->plan_totals.as<uint64_t>();
     // capacity for the kept events of this batch: everything downstream is sized by this bound and reads the
     // actual counts from device memory, so the batch needs no host round trip
     const uint64_t ke_cap = std::min<uint64_t>(N, (uint64_t)ns * c->prm.sample_limit);
@@ -1053,57 +1042,21 @@ static pg_status collect_impl(pg_ctx *c, const uint64_t *base, int32_t base_loca
 
     const uint64_t win_cap = (uint64_t)c->prm.max_dur + 2ull * c->prm.signal_print_margin;
     const uint64_t samp_cap = ke_cap * win_cap;
-    HIP_TRY(c, c->ev_rec[c->rslot].ensure((ke_cap + 1) * sizeof(PgKeptRec)));
-    HIP_TRY(c, c->samp_off[c->rslot].ensure((ke_cap + 2) * 8));
+    HIP_TRY(c, c->ev_rec.ensure((ke_cap + 1) * sizeof(PgKeptRec)));
+    HIP_TRY(c, c->samp_off.ensure((ke_cap + 2) * 8));
     c->unpacked = false;
 
     PgWalkParams W{}; PgWalkOut O{};
     fill_walk(c, W, O);
     PgKeptOut K{};
-    K.rec = c->ev_rec[c->rslot].as<PgKeptRec>();
+    K.rec = c->ev_rec.as<PgKeptRec>();
     // the per-read "owns a kept event" flags are only consumed by the lazy statistics: no scattered byte stores otherwise
     K.read_needed = (c->prm.scaling == 1 && (c->prm.flags & PG_FLAG_LAZY_STATS) && !(c->prm.flags & PG_FLAG_SKIP_OUT_OF_RANGE)) ? c->read_needed.as<uint8_t>() : nullptr;
     // Many kept events (nearly every accepted event kept: large sample_limit, k = 9): the offset scan happens inside the gather's
     // workgroups (pg_place.hip). Few (the default limit: 10^5 events): the one-launch chained scan + the strided gather of round 2.
     const bool chunked = ke_cap > dense_min() && (win_cap + 1) * 4096 < (1ull << 32);
     bool sums_ready = false;
-    // Two-stream mode, many kept events: the gather of this batch goes to a THIRD stream, behind the batch's statistics (second stream)
-    // and its placing kernel, and the main stream goes on with the next batch's init / events / ranking / placing -- chains of dependent
-    // round trips that leave the memory system idle (VALU 0.2-0.3 busy, 0.15-0.4 of the HBM rate) -- beside it. What the next batch's
-    // chain writes and this gather reads exists per statistics slot (records, sample offsets, kept-event total, chunk sums); the sample
-    // buffer exists once: gathers follow each other on their stream.
-    // Measured (profiles/r04_side_gather.txt): 0-5 % at sample_limit 5000, nothing at k = 9, whatever share of the CUs the gather's stream
-    // is given -- the chain's kernels wait inside occupied wave slots, they do not leave CUs free, and the gather needs its CUs (half of them:
-    // +14 %). So it is opt-in (PGMOVE_GATHER_SIDE=1), and tests/test_gpu_parity.py runs the suite's cases through it once.
-    const bool gather_side_on = c->side_enabled; // (PGMOVE_GATHER_SIDE, read when the context is created)
-    const bool side = chunked && c->stats_in_flight && c->st2 && !c->user_stream && gather_side_on && (c->prm.flags & PG_FLAG_OVERLAP);
-    if (side && !c->st3) { // like the statistics stream: a quarter of every XCD's CUs stays free of it, or the chain's 16-wave workgroups never find room
-        const char *wh = getenv("PGMOVE_GATHER_CU_WITHHELD");
-        hipDeviceProp_t prop;
-        HIP_TRY(c, hipGetDeviceProperties(&prop, c->device));
-        const int cus = prop.multiProcessorCount, withheld = wh ? atoi(wh) : cus / 4;
-        bool masked = false;
-        if (withheld > 0 && withheld < cus) {
-            std::vector<uint32_t> mask((size_t)(cus + 31) / 32, 0u);
-            for (int i = 0; i < cus - withheld; i++) mask[(size_t)i / 32] |= 1u << (i % 32);
-            masked = hipExtStreamCreateWithCUMask(&c->st3, (uint32_t)mask.size(), mask.data()) == hipSuccess;
-            if (!masked) (void)hipGetLastError();
-        }
-        if (!masked) {
-            int prio_low = 0, prio_high = 0;
-            HIP_TRY(c, hipDeviceGetStreamPriorityRange(&prio_low, &prio_high));
-            HIP_TRY(c, hipStreamCreateWithPriority(&c->st3, hipStreamNonBlocking, prio_low));
-        }
-    }
-    if (c->side_used[c->slot]) { // the gather that read this slot's records two batches ago
-        HIP_TRY(c, hipStreamWaitEvent(c->st, c->ev_gathered[c->slot], 0));
-        c->side_used[c->slot] = false;
-    }
-    if (!side && c->gather_side) { // this batch's gather runs on the main stream and writes the sample buffer the previous one is still filling
-        HIP_TRY(c, hipStreamWaitEvent(c->st, c->ev_gathered[c->gather_side_slot], 0));
-        c->gather_side = false;
-    }
-    if (chunked) HIP_TRY(c, c->chunk_part[c->rslot].ensure(PG_CHUNK_PART_N * 8)); // (partitioned ranking has it already, zeroed by its scan launch in pg_count)
+    if (chunked) HIP_TRY(c, c->chunk_part.ensure(PG_CHUNK_PART_N * 8)); // (partitioned ranking has it already, zeroed by its scan launch in pg_count)
     if (direct) {
         PgSortBufs S{};
         fill_sort(c, S, 0);
@@ -1116,7 +1069,7 @@ static pg_status collect_impl(pg_ctx *c, const uint64_t *base, int32_t base_loca
         fill_part(c, P, N ? N : 1);
         if (N) {
             prof_begin(c, "k_region_place", c->st);
-            HIP_TRY(c, pg_launch_region_place(c->st, P, ns, c->keep32.as<uint32_t>(), c->ev_off.as<uint64_t>(), O, K, chunked ? c->chunk_part[c->rslot].as<uint64_t>() : nullptr, chunked ? ke_cap : 0));
+            HIP_TRY(c, pg_launch_region_place(c->st, P, ns, c->keep32.as<uint32_t>(), c->ev_off.as<uint64_t>(), O, K, chunked ? c->chunk_part.as<uint64_t>() : nullptr, chunked ? ke_cap : 0));
             prof_end(c, c->st);
             sums_ready = chunked;
         }
@@ -1138,10 +1091,10 @@ static pg_status collect_impl(pg_ctx *c, const uint64_t *base, int32_t base_loca
         // the rare statistics ride in that pass's launch, or get their own
         if (!sums_ready) {
             // the coarse sums are ADDED to: zeroed by the tile scan's extra workgroup where there is one (dense direct ranking; partitioned
-            // ranking, whose placing kernel has filled them by now), else here (the radix-sort ranking, PGMOVE_EMIT1)
-            if (!(direct && dense_direct(c, N)) && !c->part_mode) HIP_TRY(c, hipMemsetAsync(c->chunk_part[c->rslot].p, 0, PG_CHUNK_PART_N * 8, c->st));
+            // ranking, whose placing kernel has filled them by now), else here (the radix-sort ranking)
+            if (!(direct && dense_direct(c, N)) && !c->part_mode) HIP_TRY(c, hipMemsetAsync(c->chunk_part.p, 0, PG_CHUNK_PART_N * 8, c->st));
             prof_begin(c, "len_partials", c->st);
-            HIP_TRY(c, pg_launch_len_partials(c->st, ke_cap, totals, c->ev_rec[c->rslot].as<PgKeptRec>(), c->chunk_part[c->rslot].as<uint64_t>(), c->rare_pending ? &c->rare : nullptr));
+            HIP_TRY(c, pg_launch_len_partials(c->st, ke_cap, totals, c->ev_rec.as<PgKeptRec>(), c->chunk_part.as<uint64_t>(), c->rare_pending ? &c->rare : nullptr));
             prof_end(c, c->st);
         } else if (c->rare_pending) {
             prof_begin(c, "k_read_stats_rare", c->st);
@@ -1151,7 +1104,7 @@ static pg_status collect_impl(pg_ctx *c, const uint64_t *base, int32_t base_loca
         c->rare_pending = false;
     } else {
         prof_begin(c, "scan_ev_len", c->st, /*bracket=*/(ke_cap + 4095) / 4096 > 64); // long inputs: three launches (pg_launch_scan_u32_u64)
-        HIP_TRY(c, pg_launch_scan_u32_u64(c->st, reinterpret_cast<const uint32_t *>(c->ev_rec[c->rslot].p) + 2, 4, ke_cap, totals, c->samp_off[c->rslot].as<uint64_t>(), c->scan_scratch.as<uint64_t>(),
+        HIP_TRY(c, pg_launch_scan_u32_u64(c->st, reinterpret_cast<const uint32_t *>(c->ev_rec.p) + 2, 4, ke_cap, totals, c->samp_off.as<uint64_t>(), c->scan_scratch.as<uint64_t>(),
                                           c->rare_pending ? &c->rare : nullptr, totals + 2));
         c->rare_pending = false;
         prof_end(c, c->st);
@@ -1176,7 +1129,7 @@ static pg_status collect_impl(pg_ctx *c, const uint64_t *base, int32_t base_loca
             HIP_TRY(c, hipMemcpyAsync(tot, totals, 24, hipMemcpyDeviceToHost, c->st));
             if (chunked) { // the kept samples' total is left by the GATHER there (its last chunk); in front of it: the sum of the coarse chunk sums
                 uint64_t coarse[PG_CHUNK_COARSE];
-                HIP_TRY(c, hipMemcpyAsync(coarse, c->chunk_part[c->rslot].as<uint64_t>() + PG_CHUNK_FINE, sizeof coarse, hipMemcpyDeviceToHost, c->st));
+                HIP_TRY(c, hipMemcpyAsync(coarse, c->chunk_part.as<uint64_t>() + PG_CHUNK_FINE, sizeof coarse, hipMemcpyDeviceToHost, c->st));
                 HIP_TRY(c, hipStreamSynchronize(c->st));
                 tot[2] = 0;
                 for (uint64_t v : coarse) tot[2] += v;
@@ -1185,29 +1138,23 @@ static pg_status collect_impl(pg_ctx *c, const uint64_t *base, int32_t base_loca
             gather_cap = tot[0];
         }
     }
-    hipStream_t gst = c->st;
-    if (side) { // behind this batch's statistics (second stream) and behind the placing kernel + chunk sums of the main one
-        HIP_TRY(c, hipEventRecord(c->ev_fork, c->st));
-        HIP_TRY(c, hipStreamWaitEvent(c->st3, c->ev_fork, 0));
-        HIP_TRY(c, hipStreamWaitEvent(c->st3, c->ev_join[c->slot], 0));
-        gst = c->st3; c->stats_in_flight = false;
-    }
+    // The gather stays on the main stream, behind the batch's statistics: on a stream of its own beside the next batch's chain it was worth
+    // 0-5 % at sample_limit 5000 and nothing at k = 9, whatever share of the CUs it was given (profiles/r04_side_gather.txt).
     if (c->stats_in_flight) { HIP_TRY(c, hipStreamWaitEvent(c->st, c->ev_join[c->slot], 0)); c->stats_in_flight = false; }
-    prof_begin(c, "k_gather", gst);
+    prof_begin(c, "k_gather", c->st);
     if (chunked)
-        HIP_TRY(c, pg_launch_gather_chunks(gst, c->B, ke_cap, totals, c->ev_rec[c->rslot].as<PgKeptRec>(), c->chunk_part[c->rslot].as<uint64_t>(), c->samp_off[c->rslot].as<uint64_t>(), totals + 2, c->prm.scaling,
+        HIP_TRY(c, pg_launch_gather_chunks(c->st, c->B, ke_cap, totals, c->ev_rec.as<PgKeptRec>(), c->chunk_part.as<uint64_t>(), c->samp_off.as<uint64_t>(), totals + 2, c->prm.scaling,
                                            c->prm.pa_min, c->prm.pa_max, c->samples.as<double>(), c->prm.scaling == 1 ? c->gcal[c->slot].as<double>() : nullptr, gather_lanes(c),
                                            c->prm.scaling == 1 ? c->stat_err[c->slot].as<int32_t>() : nullptr));
     else
-        HIP_TRY(c, pg_launch_gather(c->st, c->B, gather_cap, totals, c->ev_rec[c->rslot].as<PgKeptRec>(),
-                     c->samp_off[c->rslot].as<uint64_t>(), c->prm.scaling, c->prm.pa_min, c->prm.pa_max, c->med[c->slot].as<double>(), c->mad[c->slot].as<double>(),
+        HIP_TRY(c, pg_launch_gather(c->st, c->B, gather_cap, totals, c->ev_rec.as<PgKeptRec>(),
+                     c->samp_off.as<uint64_t>(), c->prm.scaling, c->prm.pa_min, c->prm.pa_max, c->med[c->slot].as<double>(), c->mad[c->slot].as<double>(),
                      c->samples.as<double>(), c->prm.scaling == 1 ? c->gcal[c->slot].as<double>() : nullptr));
-    prof_end(c, gst);
-    // "this slot's statistics buffers have been read": for the statistics stream two batches on (and the side gather). With one stream nobody
-    // waits for it, and a record ends the gather with 4.6 us in which the stream starts nothing (rocprofv3 kernel trace, tools/trace_gaps.py:
-    // every other kernel-to-kernel gap of the chain is 0.0 us).
-    if (c->st2 || c->st3) HIP_TRY(c, hipEventRecord(c->ev_gathered[c->slot], gst));
-    if (side) { c->gather_side = true; c->gather_side_slot = c->slot; c->side_used[c->slot] = true; }
+    prof_end(c, c->st);
+    // "this slot's statistics buffers have been read": for the statistics stream two batches on. With one stream nobody waits for it, and a
+    // record ends the gather with 4.6 us in which the stream starts nothing (rocprofv3 kernel trace, tools/trace_gaps.py: every other
+    // kernel-to-kernel gap of the chain is 0.0 us).
+    if (c->st2) HIP_TRY(c, hipEventRecord(c->ev_gathered[c->slot], c->st));
     PG_TMARK("collect: buffers + kernels queued");
     if (timing_on()) { HIP_TRY(c, hipStreamSynchronize(c->st)); PG_TMARK("collect: kernels done (sync)"); }
     c->slot_used[c->slot] = true;
@@ -1218,12 +1165,11 @@ static pg_status collect_impl(pg_ctx *c, const uint64_t *base, int32_t base_loca
 // after a collect: wait for the batch, surface per-read errors, learn how many events/samples were kept
 static pg_status settle_batch(pg_ctx *c) {
     if (!c->have_batch_result || c->totals_known) return PG_OK;
-    // the other streams first: the record is packed on the main one, behind everything that writes what it reads (k_settle_pack: one launch
+    // the statistics stream first: the record is packed on the main one, behind everything that writes what it reads (k_settle_pack: one launch
     // into host-mapped memory instead of four blocking copies of 8-24 bytes, ~80 -> ~10 us per call)
     if (c->st2) HIP_TRY(c, hipStreamSynchronize(c->st2));
-    if (c->st3) HIP_TRY(c, hipStreamSynchronize(c->st3));
-    HIP_TRY(c, pg_launch_settle_pack(c->st, c->errflag.as<uint32_t>(), c->stat_err[c->slot].as<int32_t>(), c->long_ring.as<int32_t>() + 4u * (c->long_seq & 3u), c->plan_totals[c->rslot].as<uint64_t>(),
-                                     c->samp_off[c->rslot].as<uint64_t>(), c->samp_off[c->rslot].cap / 8, c->cancel_pending ? c->cancel_flag.as<uint32_t>() : nullptr, c->settle_host));
+    HIP_TRY(c, pg_launch_settle_pack(c->st, c->errflag.as<uint32_t>(), c->stat_err[c->slot].as<int32_t>(), c->long_ring.as<int32_t>() + 4u * (c->long_seq & 3u), c->plan_totals.as<uint64_t>(),
+                                     c->samp_off.as<uint64_t>(), c->samp_off.cap / 8, c->cancel_pending ? c->cancel_flag.as<uint32_t>() : nullptr, c->settle_host));
     HIP_TRY(c, hipStreamSynchronize(c->st));
     const PgSettlePack pk = *c->settle_host;
     pg_status s = check_read_errors(c, pk);
@@ -1263,7 +1209,6 @@ pg_status pg_sync(pg_ctx *c) {
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->st));
     if (c->st2) HIP_TRY(c, hipStreamSynchronize(c->st2));
-    if (c->st3) HIP_TRY(c, hipStreamSynchronize(c->st3));
     return settle_batch(c);
 }
 
@@ -1272,7 +1217,6 @@ pg_status pg_set_stream(pg_ctx *c, void *hip_stream) {
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->st));
     if (c->st2) HIP_TRY(c, hipStreamSynchronize(c->st2));
-    if (c->st3) HIP_TRY(c, hipStreamSynchronize(c->st3));
     c->st = hip_stream ? (hipStream_t)hip_stream : c->own_st;
     c->user_stream = hip_stream != nullptr;
     return PG_OK;
@@ -1301,7 +1245,7 @@ int32_t pg_poll(pg_ctx *c) {
     if (!c) return PG_ERR_INVALID_ARG;
     if (!c->have_batch_result || c->totals_known) return 1;
     if (hipSetDevice(c->device) != hipSuccess) return PG_ERR_HIP;
-    if (hipStreamQuery(c->st) != hipSuccess || (c->st2 && hipStreamQuery(c->st2) != hipSuccess) || (c->st3 && hipStreamQuery(c->st3) != hipSuccess)) { (void)hipGetLastError(); return 0; } // hipErrorNotReady
+    if (hipStreamQuery(c->st) != hipSuccess || (c->st2 && hipStreamQuery(c->st2) != hipSuccess)) { (void)hipGetLastError(); return 0; } // hipErrorNotReady
     const pg_status s = settle_batch(c);
     return s == PG_OK ? 1 : s;
 }
@@ -1316,7 +1260,7 @@ pg_status pg_last_batch_device(pg_ctx *c, pg_device_view *v) {
     { pg_status su = ensure_unpacked(c); if (su != PG_OK) return su; }
     v->n_events = c->cur_n_kept; v->n_samples = c->cur_n_samples;
     v->d_keep = c->keep.as<uint64_t>(); v->d_ev_off = c->ev_off.as<uint64_t>(); v->d_ev_len = c->ev_len.as<uint32_t>();
-    v->d_ev_read = c->ev_read.as<uint32_t>(); v->d_samp_off = c->samp_off[c->rslot].as<uint64_t>(); v->d_samples = c->samples.as<double>();
+    v->d_ev_read = c->ev_read.as<uint32_t>(); v->d_samp_off = c->samp_off.as<uint64_t>(); v->d_samples = c->samples.as<double>();
     v->d_med = c->prm.scaling == 1 ? c->med[c->slot].as<double>() : nullptr; v->d_mad = c->prm.scaling == 1 ? c->mad[c->slot].as<double>() : nullptr;
     return PG_OK;
 }
@@ -1536,7 +1480,7 @@ pg_status pg_text(pg_ctx *c, pg_text_result *out) {
     const uint32_t ns = c->prm.n_slots;
     const uint64_t ne = R.n_events;
     const uint64_t *d_samp_off, *d_ev_off;
-    if (c->batches.size() == 1 && c->have_batch_result && c->cur_n_kept == ne) { d_samp_off = c->samp_off[c->rslot].as<uint64_t>(); d_ev_off = c->ev_off.as<uint64_t>(); } // still there
+    if (c->batches.size() == 1 && c->have_batch_result && c->cur_n_kept == ne) { d_samp_off = c->samp_off.as<uint64_t>(); d_ev_off = c->ev_off.as<uint64_t>(); } // still there
     else {
         HIP_TRY(c, c->tx_samp_off.ensure((ne + 1) * 8ull)); HIP_TRY(c, c->tx_ev_off.ensure((ns + 1) * 8ull));
         HIP_TRY(c, hipMemcpyAsync(c->tx_samp_off.p, R.samp_off, (ne + 1) * 8ull, hipMemcpyHostToDevice, c->st));
@@ -1601,7 +1545,7 @@ pg_status pg_model(pg_ctx *c, uint32_t flags, pg_model_result *out) {
     if (c->batches.size() == 1 && c->have_batch_result && c->cur_n_kept == R.n_events && c->cur_n_samples == R.n_samples) {
         // one batch: its kept events are still on the device, in the same order
         { pg_status su = ensure_unpacked(c); if (su != PG_OK) return su; }
-        d_ev_off = c->ev_off.as<uint64_t>(); d_samp_off = c->samp_off[c->rslot].as<uint64_t>(); d_ev_len = c->ev_len.as<uint32_t>(); d_samples = c->samples.as<double>();
+        d_ev_off = c->ev_off.as<uint64_t>(); d_samp_off = c->samp_off.as<uint64_t>(); d_ev_len = c->ev_len.as<uint32_t>(); d_samples = c->samples.as<double>();
     } else { // several batches were merged on the host (slot-major): hand the merged arrays back
         HIP_TRY(c, c->md_ev_off.ensure((ns + 1) * 8ull)); HIP_TRY(c, c->md_samp_off.ensure((R.n_events + 1) * 8ull));
         HIP_TRY(c, c->md_ev_len.ensure(R.n_events * 4ull + 4));
@@ -1662,7 +1606,6 @@ pg_status pg_kernel_stats(pg_ctx *c, pg_kernel_stat *out, uint32_t cap, uint32_t
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->st));
     if (c->st2) HIP_TRY(c, hipStreamSynchronize(c->st2));
-    if (c->st3) HIP_TRY(c, hipStreamSynchronize(c->st3));
     prof_drain(c);
     uint32_t n = 0;
     for (auto &name : c->prof_names) {
@@ -1689,7 +1632,6 @@ pg_status pg_kernel_stats_reset(pg_ctx *c) {
     if (!c) return PG_ERR_INVALID_ARG;
     HIP_TRY(c, hipStreamSynchronize(c->st));
     if (c->st2) HIP_TRY(c, hipStreamSynchronize(c->st2));
-    if (c->st3) HIP_TRY(c, hipStreamSynchronize(c->st3));
     prof_drain(c);
     c->prof_acc.clear(); c->prof_names.clear(); c->stats_cancelled = 0; c->long_reads_split = 0; c->long_helpers_short = 0;
     return PG_OK;

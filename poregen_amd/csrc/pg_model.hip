@@ -623,7 +623,7 @@ hipError_t pg_launch_slot_model(hipStream_t st, uint32_t n_slots, const int any_
     // any_kind[] = how many files of each kind the host knows of (1 << 20 = "some" when it does not hold the offsets). A workgroup kernel's launch is
     // the lifetime of one workgroup (~55 us at k = 9 for 34 SHORT and 28 LONG files): when both kinds together fit one round of the
     // 1024-thread kernel, the SHORT files go on its list too.
-    const bool merge = any_kind[PG_MODEL_SHORT] > 0 && any_kind[PG_MODEL_LONG] > 0 && any_kind[PG_MODEL_SHORT] + any_kind[PG_MODEL_LONG] <= 512 && !getenv("PGMOVE_MODEL_NO_MERGE");
+    const bool merge = any_kind[PG_MODEL_SHORT] > 0 && any_kind[PG_MODEL_LONG] > 0 && any_kind[PG_MODEL_SHORT] + any_kind[PG_MODEL_LONG] <= 512;
     const int short_kind = merge ? PG_MODEL_LONG : PG_MODEL_SHORT;
     const hipError_t e = hipMemsetAsync(counts, 0, 64, st);
     if (e != hipSuccess) return e;

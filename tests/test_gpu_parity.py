@@ -262,12 +262,11 @@ def test_overlap_mode_same_bits(mode, fence, monkeypatch):
 
 
 @pytest.mark.parametrize("k", [5, 9])
-def test_gather_beside_the_next_batch_same_bits(k, monkeypatch):
-    """PGMOVE_GATHER_SIDE=1: the chunked gather of a batch on a third stream while the main stream already runs the next batch's chain
-    (records, sample offsets, totals and chunk sums per statistics slot). Different device-resident batches back to back without a
-    synchronisation in between, as bench.py's steps are: each job's result equals its own oracle run, whatever was in flight beside it."""
+def test_chunked_gather_job_train_same_bits(k, monkeypatch):
+    """The chunked gather (PGMOVE_DENSE_MIN=0) in the default two-stream mode, the next batch's chain queued behind it on the main stream
+    while the statistics stream runs ahead. Different device-resident batches back to back without a synchronisation in between, as
+    bench.py's steps are: each job's result equals its own oracle run, whatever was in flight beside it."""
     import torch
-    monkeypatch.setenv("PGMOVE_GATHER_SIDE", "1")
     monkeypatch.setenv("PGMOVE_DENSE_MIN", "0")
     kind = "rna004" if k == 5 else "dna_r10"
     p = dict(kmer_size=k, rna=k == 5, scaling=1, sample_limit=40 if k == 5 else 3)
