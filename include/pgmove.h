@@ -511,6 +511,49 @@ pg_status pg_fscore_sync(pg_fscore *h);
  * handle is reset afterwards, also after an error. */
 pg_status pg_fscore_finish(pg_fscore *h, pg_fscore_result *out, uint64_t *pair_counts, uint64_t cap_pairs);
 
+/* ---- subtool0 / pa_stats: the mean pA of every read, and of every sample of the dataset ------------------------------------------
+ * Per read (src/poregen.cpp:133-151, printed by output_db, src/poregen.cpp:166-175, as printf("%s\t%f\n", read_id, mean)): the mean of
+ * x_i = ((double)raw_i + offset) * (range / digitisation), which the reference sums SEQUENTIALLY in one double from 0.0. The library
+ * returns, for every read with n > 0, a double whose printf("%f") text is the reference's text: the device counts exact integer moments
+ * of the samples and settles the text from them where a proven bound allows (csrc/pg_pamean.h); every other read (a mean too near a
+ * rounding boundary of %f, a non-finite digitisation / offset / range, a read longer than 2^30 samples) is finished on the host by
+ * the reference's own loop. Zero-length reads get NaN (the reference prints nothing for them).
+ * Per dataset (scripts/poregen.sh STEP 7, `sigtk pa | datamash mean 1 sstdev 1`): N = sum n, the mean and the sample standard
+ * deviation sqrt(sum (x - mean)^2 / (N - 1)) of all pA values, folded in file order from exact per-read integer moments; the result does
+ * not depend on how the reads are cut into batches or where they lie. The moments are those of a_i = (raw_i + offset) * scale taken
+ * exactly, not of the rounded x_i: |x_i - a_i| <= 2.0001 u |a_i| (u = 2^-53), so the relative gap to the exact statistics of the x_i is
+ * at most about 2u mean|x| / |mean| for the mean and 2u sqrt(1 + mean^2 / var) for the sstdev -- below 1e-13 while |mean| / sstdev < 400
+ * (nanopore pA data: about 5), larger for a dataset with almost no spread far from zero. Not byte-pinned to
+ * sigtk | datamash (section 11.3). No CPU fallback: PG_ERR_NO_DEVICE without a GPU. */
+typedef struct pg_pamean pg_pamean;
+typedef struct {
+    uint64_t n_reads;
+    int32_t location;              /* PG_LOC_HOST or PG_LOC_DEVICE: all five arrays */
+    int32_t reserved;
+    const int16_t *sig;
+    const uint64_t *sig_off;       /* n_reads + 1 non-decreasing offsets into sig, which holds at least sig_off[n_reads] samples (the
+                                      library cannot see the size of sig: offsets past it are read); a read has fewer than 2^33 samples */
+    const double *digitisation, *offset, *range; /* n_reads each */
+} pg_pamean_batch;
+typedef struct {
+    uint64_t n_reads;              /* reads submitted since the last finish (zero-length ones included) */
+    uint64_t n_fallback;           /* reads whose mean the host finished with the sequential loop */
+    uint64_t n_samples;            /* N */
+    double mean;                   /* NaN when N == 0 */
+    double sstdev;                 /* NaN when N < 2 */
+} pg_pamean_result;
+pg_status pg_pamean_create(int32_t device, pg_pamean **out);
+void      pg_pamean_destroy(pg_pamean *h);
+const char *pg_pamean_last_error(const pg_pamean *h); /* h may be NULL: error of the last failed pg_pamean_create */
+/* Queues one batch and returns; means_out (host double[n_reads], may be NULL) is filled by the next pg_pamean_sync / submit / finish.
+ * PG_LOC_HOST arrays: any host memory (page-locked signal is copied from directly, other memory through a pinned buffer); they must stay
+ * valid until that call returns (the host reads the samples of the reads it finishes). PG_LOC_DEVICE arrays: memory of the handle's
+ * device, complete before the call, read in place and unchanged until that call returns. */
+pg_status pg_pamean_submit(pg_pamean *h, const pg_pamean_batch *batch, double *means_out);
+pg_status pg_pamean_sync(pg_pamean *h);
+/* The dataset summary of every read since the last finish; the handle is reset afterwards, also after an error. */
+pg_status pg_pamean_finish(pg_pamean *h, pg_pamean_result *out);
+
 #ifdef __cplusplus
 }
 #endif

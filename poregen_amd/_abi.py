@@ -39,6 +39,7 @@ EXPORTS = [
     "pg_job_uses_rccl", "pg_job_model", "pg_job_kernel_stats", "pg_runtime_init", "pg_all_slots_full_settled", "pg_job_all_slots_full_settled", "pg_poll", "pg_job_poll",
     "pg_kfreq_create", "pg_kfreq_destroy", "pg_kfreq_last_error", "pg_kfreq_submit", "pg_kfreq_sync", "pg_kfreq_finish",
     "pg_fscore_create", "pg_fscore_destroy", "pg_fscore_last_error", "pg_fscore_submit", "pg_fscore_sync", "pg_fscore_finish",
+    "pg_pamean_create", "pg_pamean_destroy", "pg_pamean_last_error", "pg_pamean_submit", "pg_pamean_sync", "pg_pamean_finish",
 ]
 PG_JOB_EXCHANGE_AUTO, PG_JOB_EXCHANGE_HOST, PG_JOB_EXCHANGE_RCCL = 0, 1, 2
 
@@ -114,6 +115,15 @@ class PgF1Batch(C.Structure):
 class PgF1Result(C.Structure):
     _fields_ = [("totals", C.c_uint64 * 4), ("n_pairs", C.c_uint64), ("err_pair", C.c_int64), ("err_code", C.c_uint32),
                 ("err_side", C.c_uint32)]
+
+
+class PgPameanBatch(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("location", C.c_int32), ("reserved", C.c_int32), ("sig", C.c_void_p), ("sig_off", C.c_void_p),
+                ("digitisation", C.c_void_p), ("offset", C.c_void_p), ("range", C.c_void_p)]
+
+
+class PgPameanResult(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("n_fallback", C.c_uint64), ("n_samples", C.c_uint64), ("mean", C.c_double), ("sstdev", C.c_double)]
 
 
 class PgKernelStat(C.Structure):
@@ -220,5 +230,11 @@ def load():
     lib.pg_fscore_submit.argtypes = [vp, C.POINTER(PgF1Batch)]; lib.pg_fscore_submit.restype = i32
     lib.pg_fscore_sync.argtypes = [vp]; lib.pg_fscore_sync.restype = i32
     lib.pg_fscore_finish.argtypes = [vp, C.POINTER(PgF1Result), vp, C.c_uint64]; lib.pg_fscore_finish.restype = i32
+    lib.pg_pamean_create.argtypes = [i32, C.POINTER(vp)]; lib.pg_pamean_create.restype = i32
+    lib.pg_pamean_destroy.argtypes = [vp]; lib.pg_pamean_destroy.restype = None
+    lib.pg_pamean_last_error.argtypes = [vp]; lib.pg_pamean_last_error.restype = C.c_char_p
+    lib.pg_pamean_submit.argtypes = [vp, C.POINTER(PgPameanBatch), vp]; lib.pg_pamean_submit.restype = i32
+    lib.pg_pamean_sync.argtypes = [vp]; lib.pg_pamean_sync.restype = i32
+    lib.pg_pamean_finish.argtypes = [vp, C.POINTER(PgPameanResult)]; lib.pg_pamean_finish.restype = i32
     _lib = lib
     return lib

@@ -109,6 +109,11 @@ bool Slow5File::open(const std::string &path, std::string &err) {
     return binary_ ? index_blow5(err) : index_ascii(err);
 }
 
+bool Slow5File::open_walk(const std::string &path, std::string &err) {
+    walk_ = true;
+    return open(path, err);
+}
+
 bool Slow5File::index_ascii(std::string &err) {
     const char *p = f_.data, *e = f_.data + f_.size;
     while (p < e) {
@@ -128,6 +133,7 @@ bool Slow5File::index_ascii(std::string &err) {
                     }
                 }
             } else if (*p != '@') {
+                if (walk_) { recs_.push_back(Loc{(uint64_t)(p - f_.data), (uint64_t)(le - p)}); p = nl ? nl + 1 : e; continue; }
                 const char *t = next_tab(p, le);
                 std::string id(p, t);
                 if (!index_.emplace(id, Loc{(uint64_t)(p - f_.data), (uint64_t)(le - p)}).second) { err = "duplicate read id " + id; return false; }
@@ -164,6 +170,7 @@ bool Slow5File::index_blow5(std::string &err) {
         if (sz > f_.size - pos) { err = "truncated BLOW5 record"; return false; } // (not pos + sz: a size field of 2^64 - 1 must not wrap)
         if (sz < 2) { err = "corrupt BLOW5 record"; return false; }
         Loc l{pos, sz};
+        if (walk_) { recs_.push_back(l); pos += sz; continue; } // (the read id is read when the record is decoded)
         // the read id sits at the start of the (possibly zlib-compressed) body
         std::string id;
         if (rec_press_ == 0) {
@@ -239,7 +246,7 @@ static bool svb_decode(const unsigned char *in, size_t in_len, uint32_t n, std::
     return true;
 }
 
-bool Slow5File::decode_blow5(const Loc &l, Slow5Rec &out, std::string &err) const {
+bool Slow5File::decode_blow5(const Loc &l, Slow5Rec &out, std::string &err, std::string *read_id) const {
     const unsigned char *body = (const unsigned char *)f_.data + l.off;
     size_t blen = l.len;
     std::vector<unsigned char> inflated;
@@ -268,6 +275,7 @@ bool Slow5File::decode_blow5(const Loc &l, Slow5Rec &out, std::string &err) cons
     if (!need(2)) { err = "corrupt BLOW5 record"; return false; }
     memcpy(&il, body, 2); p = 2 + il;
     if (!need(4 + 32 + 8)) { err = "corrupt BLOW5 record"; return false; }
+    if (read_id) { read_id->assign((const char *)body + 2, il); if (!read_id->empty() && read_id->back() == '\0') read_id->pop_back(); }
     p += 4; // read_group
     double sampling;
     memcpy(&out.digitisation, body + p, 8); memcpy(&out.offset, body + p + 8, 8); memcpy(&out.range, body + p + 16, 8);
@@ -299,14 +307,19 @@ bool Slow5File::decode_blow5(const Loc &l, Slow5Rec &out, std::string &err) cons
 bool Slow5File::raw_view(const std::string &read_id, RawView &v, std::string &err) const {
     auto it = index_.find(read_id);
     if (it == index_.end()) { err = "read " + read_id + " not found"; return false; }
+    return view_blow5(it->second, v, err);
+}
+
+bool Slow5File::view_blow5(const Loc &l, RawView &v, std::string &err, std::string *read_id) const {
     if (!has_raw_views()) { err = "BLOW5 records are compressed"; return false; }
-    const unsigned char *body = (const unsigned char *)f_.data + it->second.off;
-    const size_t blen = it->second.len;
+    const unsigned char *body = (const unsigned char *)f_.data + l.off;
+    const size_t blen = l.len;
     uint16_t il;
     if (blen < 2) { err = "corrupt BLOW5 record"; return false; }
     memcpy(&il, body, 2);
     size_t p = 2 + (size_t)il;
     if (p + 4 + 32 + 8 > blen) { err = "corrupt BLOW5 record"; return false; }
+    if (read_id) { read_id->assign((const char *)body + 2, il); if (!read_id->empty() && read_id->back() == '\0') read_id->pop_back(); }
     p += 4; // read_group
     memcpy(&v.digitisation, body + p, 8); memcpy(&v.offset, body + p + 8, 8); memcpy(&v.range, body + p + 16, 8); p += 32;
     memcpy(&v.n, body + p, 8); p += 8;
@@ -315,11 +328,27 @@ bool Slow5File::raw_view(const std::string &read_id, RawView &v, std::string &er
     return true;
 }
 
+bool Slow5File::record(size_t i, std::string &read_id, Slow5Rec &out, std::string &err) const {
+    const Loc &l = recs_[i];
+    if (binary_) return decode_blow5(l, out, err, &read_id);
+    const char *p = f_.data + l.off, *e = p + l.len;
+    read_id.assign(p, next_tab(p, e));
+    return parse_ascii(l, out, read_id, err);
+}
+
+bool Slow5File::record_view(size_t i, std::string &read_id, RawView &v, std::string &err) const {
+    return view_blow5(recs_[i], v, err, &read_id);
+}
+
 bool Slow5File::get(const std::string &read_id, Slow5Rec &out, std::string &err) const {
     auto it = index_.find(read_id);
     if (it == index_.end()) { err = "read " + read_id + " not found"; return false; }
     if (binary_) return decode_blow5(it->second, out, err);
-    const char *p = f_.data + it->second.off, *e = p + it->second.len;
+    return parse_ascii(it->second, out, read_id, err);
+}
+
+bool Slow5File::parse_ascii(const Loc &l, Slow5Rec &out, const std::string &read_id, std::string &err) const {
+    const char *p = f_.data + l.off, *e = p + l.len;
     int col = 0;
     uint64_t len = 0; bool have_len = false;
     const char *sig_b = nullptr, *sig_e = nullptr;

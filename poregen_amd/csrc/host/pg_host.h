@@ -35,6 +35,14 @@ public:
     bool has_raw_views() const { return binary_ && rec_press_ == 0 && sig_press_ == 0; }
     bool raw_view(const std::string &read_id, RawView &v, std::string &err) const;
     size_t n_reads() const { return index_.size(); }
+    // File-order walk (subtool0: slow5_get_next_bytes, src/poregen.cpp:84-116): every record in the order of the file, records with the
+    // same read id included; no read-id index is built (get / raw_view / n_reads are not for a walk). record / record_view may be called
+    // from several threads at once.
+    bool open_walk(const std::string &path, std::string &err);
+    size_t n_records() const { return recs_.size(); }
+    uint64_t record_bytes(size_t i) const { return recs_[i].len; }
+    bool record(size_t i, std::string &read_id, Slow5Rec &out, std::string &err) const;
+    bool record_view(size_t i, std::string &read_id, RawView &v, std::string &err) const; // has_raw_views() only
     bool is_binary() const { return binary_; }
     const std::vector<std::string> &ids_in_file_order() const { return order_; }
 private:
@@ -45,9 +53,13 @@ private:
     int col_dig_ = 2, col_off_ = 3, col_range_ = 4, col_len_ = 6, col_sig_ = 7;
     std::unordered_map<std::string, Loc> index_;
     std::vector<std::string> order_;
+    bool walk_ = false;
+    std::vector<Loc> recs_; // open_walk: every record, in file order
     bool index_ascii(std::string &err);
     bool index_blow5(std::string &err);
-    bool decode_blow5(const Loc &l, Slow5Rec &out, std::string &err) const;
+    bool decode_blow5(const Loc &l, Slow5Rec &out, std::string &err, std::string *read_id = nullptr) const;
+    bool parse_ascii(const Loc &l, Slow5Rec &out, const std::string &label, std::string &err) const;
+    bool view_blow5(const Loc &l, RawView &v, std::string &err, std::string *read_id = nullptr) const;
 };
 
 // ---- FASTA/FASTQ with faidx semantics (replaces fai_load / faidx_fetch_seq, src/gmove.cpp:724,805) -----

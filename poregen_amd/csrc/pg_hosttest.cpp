@@ -214,3 +214,27 @@ extern "C" int pgt_job_stats_rule(uint32_t rank, const uint64_t *shard_ops, cons
                                   int have_batch, uint64_t full_slots_prev, const char *mode) {
     return (int)pg_job_stats_place(rank, shard_ops, shard_reads, n_slots, sample_limit, have_batch != 0, full_slots_prev, mode && *mode ? mode : nullptr);
 }
+
+// ---- subtool0 / pa_stats (pg_pamean.h, host/io.cpp) ----------------------------------------------------------------------------
+#include "pg_pamean.h"
+extern "C" int pgt_pa_shift(double offset) { return pg_pa_shift(offset); }
+// the device's decision for one read, from the integer moments it counts: 1 = settled (*mean set)
+extern "C" int pgt_pa_certify(uint64_t n, int64_t s1, uint64_t sa, double offset, double scale, double *mean) {
+    return pg_pa_certify(n, s1, sa, pg_pa_shift(offset), offset, scale, mean);
+}
+extern "C" double pgt_pa_sequential_mean(const int16_t *raw, uint64_t n, double dig, double off, double range) {
+    return pg_pa_sequential_mean(raw, n, dig, off, range);
+}
+// the file-order walk: record count, or -1 (errbuf); ids joined by '\n' into ids (cap bytes), sample counts into lens (up to max)
+extern "C" long pgt_slow5_walk(const char *path, char *ids, size_t cap, uint64_t *lens, size_t max, char *errbuf, size_t ecap) {
+    pgh::Slow5File f; std::string err, all;
+    if (!f.open_walk(path, err)) { put_err(err, errbuf, ecap); return -1; }
+    for (size_t i = 0; i < f.n_records(); i++) {
+        std::string id; pgh::Slow5Rec r;
+        if (!f.record(i, id, r, err)) { put_err(err, errbuf, ecap); return -1; }
+        all += id; all += '\n';
+        if (i < max) lens[i] = r.raw.size();
+    }
+    if (all.size() < cap) { memcpy(ids, all.data(), all.size()); ids[all.size()] = 0; }
+    return (long)f.n_records();
+}

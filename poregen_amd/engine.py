@@ -788,3 +788,98 @@ def f1_counts(ss, offsets, sig_start, first_ref, rna: bool = False, threshold: i
         return sc.finish()
     finally:
         sc.close()
+
+
+# ---- subtool0 / pa_stats ----------------------------------------------------------------------------------------------------------
+
+@dataclass
+class PaMeans:
+    """`poregen subtool0` per read and `poregen pa_stats` per dataset: `means` (float64, NaN for a read without samples) print with "%f"
+    exactly as the reference prints them; n_fallback reads were finished on the host by the reference's sequential loop; n_samples, mean
+    and sstdev (sample standard deviation) are over every pA value."""
+    means: np.ndarray
+    n_fallback: int
+    n_samples: int
+    mean: float
+    sstdev: float
+
+
+class SignalMeans:
+    """Mean pA of every read and of the dataset on the GPU (pg_pamean_*). submit() takes one batch in the pg_batch signal layout: int16
+    samples, n + 1 offsets, and per read digitisation / offset / range -- numpy arrays, or CUDA torch tensors read in place (int64 offsets,
+    float64 parameters; kept alive until finish). finish() returns every read since the last finish, in submission order."""
+
+    def __init__(self, device: int = 0):
+        self._lib = _abi.load()
+        h = C.c_void_p()
+        st = self._lib.pg_pamean_create(device, C.byref(h))
+        if st != 0:
+            raise PgError(st, self._lib.pg_pamean_last_error(None).decode())
+        self._h = h
+        self._keep = []
+        self._means = []
+
+    def _check(self, st):
+        if st != 0:
+            raise PgError(st, self._lib.pg_pamean_last_error(self._h).decode())
+
+    def submit(self, sig, sig_off, digitisation, offset, range):
+        arrs = (sig, sig_off, digitisation, offset, range)
+        dev = [hasattr(a, "is_cuda") and a.is_cuda for a in arrs]
+        if any(dev):
+            if not all(dev):
+                raise ValueError("device input: all five arrays must be CUDA tensors")
+            for a, itemsize in zip(arrs, (2, 8, 8, 8, 8)):
+                if a.dtype.itemsize != itemsize or not a.is_contiguous():
+                    raise ValueError("device input: contiguous int16 samples, 64-bit offsets, float64 parameters")
+            n = sig_off.numel() - 1
+            if n > 0 and int(sig_off[-1].item()) > sig.numel():  # (the kernels trust the offsets: never let them point past the samples)
+                raise ValueError("sig_off runs past the samples")
+            loc = _abi.PG_LOC_DEVICE
+            kept = list(arrs)
+        else:
+            kept = [np.ascontiguousarray(sig, np.int16), np.ascontiguousarray(sig_off, np.uint64),
+                    np.ascontiguousarray(digitisation, np.float64), np.ascontiguousarray(offset, np.float64),
+                    np.ascontiguousarray(range, np.float64)]
+            n = kept[1].size - 1
+            if n > 0 and int(kept[1][-1]) > kept[0].size:
+                raise ValueError("sig_off runs past the samples")
+            loc = _abi.PG_LOC_HOST
+        if n < 0 or any((a.numel() if hasattr(a, "numel") else a.size) != n for a in kept[2:]):
+            raise ValueError("need n + 1 offsets and n digitisation / offset / range values")
+        means = np.empty(max(n, 0), np.float64)
+        b = _abi.PgPameanBatch(n, loc, 0, *[_ptr(a) if (hasattr(a, "numel") and a.numel()) or (isinstance(a, np.ndarray) and a.size) else None
+                                             for a in kept])
+        self._keep.append(kept)
+        self._check(self._lib.pg_pamean_submit(self._h, C.byref(b), C.c_void_p(means.ctypes.data) if n else None))
+        self._means.append(means)
+
+    def finish(self) -> PaMeans:
+        r = _abi.PgPameanResult()
+        try:
+            self._check(self._lib.pg_pamean_finish(self._h, C.byref(r)))
+            means = np.concatenate(self._means) if self._means else np.zeros(0, np.float64)
+        finally:
+            self._keep, self._means = [], []
+        return PaMeans(means, int(r.n_fallback), int(r.n_samples), float(r.mean), float(r.sstdev))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.pg_pamean_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def read_means(sig, sig_off, digitisation, offset, range, device: int = 0) -> PaMeans:
+    """One-shot SignalMeans: per-read means, the fallback count and the dataset summary of one batch (host or device arrays)."""
+    sm = SignalMeans(device)
+    try:
+        sm.submit(sig, sig_off, digitisation, offset, range)
+        return sm.finish()
+    finally:
+        sm.close()
