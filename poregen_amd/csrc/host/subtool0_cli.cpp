@@ -18,6 +18,7 @@
 #include "pg_host.h"
 
 #include <hip/hip_runtime_api.h>
+#include "../pg_hip_host.h"
 
 #include <algorithm>
 #include <atomic>
@@ -83,29 +84,13 @@ uint64_t batch_bytes_from_env() { // record bytes per device batch
     return 64ull << 20;
 }
 
-// page-locked host memory that only grows: the decoded samples are written here once and go to the device by DMA from here
-struct PinnedBuf {
-    void *p = nullptr; size_t bytes = 0;
-    PinnedBuf() = default;
-    PinnedBuf(const PinnedBuf &) = delete; PinnedBuf &operator=(const PinnedBuf &) = delete;
-    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
-    bool grow(size_t want) {
-        if (want <= bytes) return true;
-        if (p) { (void)hipHostFree(p); p = nullptr; bytes = 0; }
-        const size_t b = want + want / 4; // (batches differ in size: a little room saves re-pinning)
-        if (hipHostMalloc(&p, b, hipHostMallocDefault) != hipSuccess) { p = nullptr; return false; }
-        bytes = b;
-        return true;
-    }
-};
-
 // one batch of records, decoded: the layout pg_pamean_batch takes
 struct HostBatch {
     size_t n = 0;
     std::vector<std::string> ids;
     std::vector<uint64_t> off;            // n + 1
     std::vector<double> dig, offs, rng, means;
-    PinnedBuf sig;
+    PgPinned<int16_t> sig; // the decoded samples are written here once and go to the device by DMA from here
 };
 
 class Walker {
@@ -136,8 +121,12 @@ class Walker {
             for (size_t i = 0; i < n; i++) if (!errs[i].empty()) { err = "record " + std::to_string(first + i) + ": " + errs[i]; return false; }
         }
         for (size_t i = 0; i < n; i++) b.off[i + 1] += b.off[i];
-        if (!b.sig.grow(std::max<uint64_t>(b.off[n], 1) * sizeof(int16_t))) { err = "cannot allocate page-locked memory for the samples"; return false; }
-        int16_t *dst = static_cast<int16_t *>(b.sig.p);
+        const size_t want = std::max<uint64_t>(b.off[n], 1) * sizeof(int16_t);
+        if (b.sig.ensure(want, want + want / 4) != hipSuccess) { // (batches differ in size: a little room saves re-pinning)
+            err = "cannot allocate page-locked memory for the samples";
+            return false;
+        }
+        int16_t *dst = b.sig.p;
         on_threads(n, [&](size_t i) { // the samples copied once, from the mapping (or the decoder) to page-locked memory
             const uint64_t len = b.off[i + 1] - b.off[i];
             if (!len) return;
@@ -221,7 +210,7 @@ int run(const char *tool, int argc, char **argv, bool stats) {
         HostBatch &b = hb[k & 1];
         pg_pamean_batch pb{};
         pb.n_reads = b.n; pb.location = PG_LOC_HOST;
-        pb.sig = static_cast<const int16_t *>(b.sig.p); pb.sig_off = b.off.data();
+        pb.sig = b.sig.p; pb.sig_off = b.off.data();
         pb.digitisation = b.dig.data(); pb.offset = b.offs.data(); pb.range = b.rng.data();
         if (pg_pamean_submit(h, &pb, b.means.data()) != PG_OK) { S0_ERROR(tool, "%s", pg_pamean_last_error(h)); exit(EXIT_FAILURE); }
         if (k + 1 < n_batches) fill(k + 1); // the next batch is decoded while the device works on this one

@@ -28,10 +28,9 @@
 // that maps no point. Reference positions are carried in 128-bit integers, so no input value can overflow them.
 #include "../../include/pgmove.h"
 #include <hip/hip_runtime.h>
+#include "pg_hip_host.h"
 
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -338,15 +337,14 @@ __global__ __launch_bounds__(kThreads) void k_f1_merge(const unsigned long long 
     }
 }
 
-thread_local std::string g_f1_create_error;
-
 struct Slot { // one piece in flight: its device inputs (host batches), its results and the event that says they are back
-    uint8_t *dbytes = nullptr; uint64_t dbytes_cap = 0;
-    uint8_t *stage = nullptr; uint64_t stage_cap = 0;             // pinned copy of the bytes (pageable host input)
-    uint64_t *doff = nullptr; long long *dsig = nullptr, *dref = nullptr; uint64_t str_cap = 0;
-    uint64_t *hoff = nullptr; long long *hsig = nullptr, *href = nullptr; // pinned
-    unsigned long long *dcounts = nullptr, *hcounts = nullptr, *derr = nullptr, *herr = nullptr; uint64_t pair_cap = 0;
-    hipEvent_t done = nullptr;
+    PgEvent done;
+    PgDev<uint8_t> dbytes;
+    PgPinned<uint8_t> stage; // copy of the bytes (pageable host input)
+    PgDev<uint64_t> doff; PgDev<long long> dsig, dref;
+    PgPinned<uint64_t> hoff; PgPinned<long long> hsig, href;
+    PgDev<unsigned long long> dcounts, derr;
+    PgPinned<unsigned long long> hcounts, herr;
     bool busy = false;
     uint64_t first_pair = 0, n_pairs = 0;
 };
@@ -356,14 +354,14 @@ struct Slot { // one piece in flight: its device inputs (host batches), its resu
 struct pg_fscore {
     int device = 0;
     F1Params prm{};
-    hipStream_t st = nullptr;
+    PgStream st;
     Slot slot[2];
     int next = 0;
     // per-piece work space
-    unsigned long long *t_ops = nullptr, *t_pts = nullptr, *t_steps = nullptr; uint64_t tile_cap = 0;
-    unsigned long long *op_pts = nullptr, *op_steps = nullptr; uint8_t *op_kind = nullptr; uint64_t op_cap = 0;
-    StrBase *sb = nullptr; uint64_t sb_cap = 0;
-    unsigned long long *chunk_off = nullptr; uint64_t chunk_cap = 0;
+    PgDev<unsigned long long> t_ops, t_pts, t_steps;
+    PgDev<unsigned long long> op_pts, op_steps; PgDev<uint8_t> op_kind;
+    PgDev<StrBase> sb;
+    PgDev<unsigned long long> chunk_off;
     // results since the last finish
     uint64_t n_pairs = 0;
     std::vector<unsigned long long> counts; // 4 per pair
@@ -371,37 +369,13 @@ struct pg_fscore {
     std::string err;
 };
 
-static pg_status f1_fail(pg_fscore *h, pg_status code, const char *fmt, ...) {
-    char buf[1024];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    if (h) h->err = buf; else g_f1_create_error = buf;
-    return code;
-}
-#define F1_TRY(h, expr) \
-    do { hipError_t e_ = (expr); if (e_ != hipSuccess) return f1_fail((h), PG_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
-
-template <class T>
-static hipError_t grow_dev(T *&p, uint64_t &cap, uint64_t want) {
-    if (want <= cap) return hipSuccess;
-    if (p) { hipError_t e = hipFree(p); if (e != hipSuccess) return e; p = nullptr; cap = 0; }
-    hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
-    if (e == hipSuccess) cap = want;
-    return e;
-}
-template <class T>
-static hipError_t grow_host(T *&p, uint64_t want, uint64_t cap) {
-    if (want <= cap) return hipSuccess;
-    if (p) { hipError_t e = hipHostFree(p); if (e != hipSuccess) return e; p = nullptr; }
-    return hipHostMalloc((void **)&p, want * sizeof(T), hipHostMallocDefault);
-}
-
 // wait for a slot's piece and fold its results in
 static pg_status f1_drain(pg_fscore *h, Slot &sl) {
     if (!sl.busy) return PG_OK;
-    F1_TRY(h, hipEventSynchronize(sl.done));
+    PG_HIP_TRY(h, hipEventSynchronize(sl.done));
     sl.busy = false;
-    memcpy(h->counts.data() + 4 * sl.first_pair, sl.hcounts, 4 * sl.n_pairs * sizeof(unsigned long long));
-    if (*sl.herr != kNoErr && h->err_word == kNoErr) { h->err_word = *sl.herr; h->err_first_pair = sl.first_pair; }
+    memcpy(h->counts.data() + 4 * sl.first_pair, sl.hcounts.p, 4 * sl.n_pairs * sizeof(unsigned long long));
+    if (*sl.herr.p != kNoErr && h->err_word == kNoErr) { h->err_word = *sl.herr.p; h->err_first_pair = sl.first_pair; }
     return PG_OK;
 }
 
@@ -414,81 +388,68 @@ static pg_status f1_piece(pg_fscore *h, const uint8_t *bytes, bool dev, bool pin
     const uint32_t np = ns / 2;
     // inputs: offsets rebased to the piece, scalars (pinned, then one copy each)
     const uint64_t strs = (uint64_t)ns + 1;
-    if (strs > sl.str_cap) {
-        F1_TRY(h, grow_host(sl.hoff, strs, sl.str_cap)); F1_TRY(h, grow_host(sl.hsig, strs, sl.str_cap)); F1_TRY(h, grow_host(sl.href, strs, sl.str_cap));
-        uint64_t c1 = sl.str_cap, c2 = sl.str_cap, c3 = sl.str_cap;
-        F1_TRY(h, grow_dev(sl.doff, c1, strs)); F1_TRY(h, grow_dev(sl.dsig, c2, strs)); F1_TRY(h, grow_dev(sl.dref, c3, strs));
-        sl.str_cap = strs;
-    }
-    if (np > sl.pair_cap) {
-        F1_TRY(h, grow_host(sl.hcounts, 4ull * np, 4ull * sl.pair_cap));
-        uint64_t c = 4ull * sl.pair_cap;
-        F1_TRY(h, grow_dev(sl.dcounts, c, 4ull * np));
-        sl.pair_cap = np;
-    }
-    for (uint32_t i = 0; i <= ns; i++) sl.hoff[i] = off[s0 + i] - b0;
-    memcpy(sl.hsig, sig + s0, ns * sizeof(int64_t));
-    memcpy(sl.href, ref + s0, ns * sizeof(int64_t));
-    *sl.herr = kNoErr;
-    F1_TRY(h, hipMemcpyAsync(sl.doff, sl.hoff, strs * sizeof(uint64_t), hipMemcpyHostToDevice, h->st));
-    F1_TRY(h, hipMemcpyAsync(sl.dsig, sl.hsig, ns * sizeof(int64_t), hipMemcpyHostToDevice, h->st));
-    F1_TRY(h, hipMemcpyAsync(sl.dref, sl.href, ns * sizeof(int64_t), hipMemcpyHostToDevice, h->st));
-    F1_TRY(h, hipMemcpyAsync(sl.derr, sl.herr, sizeof(unsigned long long), hipMemcpyHostToDevice, h->st));
+    PG_HIP_TRY(h, sl.hoff.ensure(strs * 8)); PG_HIP_TRY(h, sl.hsig.ensure(strs * 8)); PG_HIP_TRY(h, sl.href.ensure(strs * 8));
+    PG_HIP_TRY(h, sl.doff.ensure(strs * 8)); PG_HIP_TRY(h, sl.dsig.ensure(strs * 8)); PG_HIP_TRY(h, sl.dref.ensure(strs * 8));
+    PG_HIP_TRY(h, sl.hcounts.ensure(4ull * np * 8)); PG_HIP_TRY(h, sl.dcounts.ensure(4ull * np * 8));
+    for (uint32_t i = 0; i <= ns; i++) sl.hoff.p[i] = off[s0 + i] - b0;
+    memcpy(sl.hsig.p, sig + s0, ns * sizeof(int64_t));
+    memcpy(sl.href.p, ref + s0, ns * sizeof(int64_t));
+    *sl.herr.p = kNoErr;
+    PG_HIP_TRY(h, hipMemcpyAsync(sl.doff.p, sl.hoff.p, strs * sizeof(uint64_t), hipMemcpyHostToDevice, h->st));
+    PG_HIP_TRY(h, hipMemcpyAsync(sl.dsig.p, sl.hsig.p, ns * sizeof(int64_t), hipMemcpyHostToDevice, h->st));
+    PG_HIP_TRY(h, hipMemcpyAsync(sl.dref.p, sl.href.p, ns * sizeof(int64_t), hipMemcpyHostToDevice, h->st));
+    PG_HIP_TRY(h, hipMemcpyAsync(sl.derr.p, sl.herr.p, sizeof(unsigned long long), hipMemcpyHostToDevice, h->st));
     const uint8_t *p = bytes + b0;
     if (!dev && n) {
-        F1_TRY(h, grow_dev(sl.dbytes, sl.dbytes_cap, n));
+        PG_HIP_TRY(h, sl.dbytes.ensure(n));
         const uint8_t *from = p;
         if (!pinned) {
-            if (n > sl.stage_cap) { F1_TRY(h, grow_host(sl.stage, n, sl.stage_cap)); sl.stage_cap = n; }
-            memcpy(sl.stage, p, n);
-            from = sl.stage;
+            PG_HIP_TRY(h, sl.stage.ensure(n));
+            memcpy(sl.stage.p, p, n);
+            from = sl.stage.p;
         }
-        F1_TRY(h, hipMemcpyAsync(sl.dbytes, from, n, hipMemcpyHostToDevice, h->st));
-        p = sl.dbytes;
+        PG_HIP_TRY(h, hipMemcpyAsync(sl.dbytes.p, from, n, hipMemcpyHostToDevice, h->st));
+        p = sl.dbytes.p;
     }
     // work space
     const uint64_t n_tiles = (n + kTile - 1) / kTile;
-    if (n_tiles > h->tile_cap) {
-        uint64_t c1 = h->tile_cap, c2 = h->tile_cap, c3 = h->tile_cap;
-        F1_TRY(h, hipStreamSynchronize(h->st)); // the other slot's piece may still use the old buffers
-        F1_TRY(h, grow_dev(h->t_ops, c1, n_tiles)); F1_TRY(h, grow_dev(h->t_pts, c2, n_tiles)); F1_TRY(h, grow_dev(h->t_steps, c3, n_tiles));
-        h->tile_cap = n_tiles;
+    if (n_tiles * 8 > h->t_ops.cap) {
+        PG_HIP_TRY(h, hipStreamSynchronize(h->st)); // the other slot's piece may still use the old buffers
+        PG_HIP_TRY(h, h->t_ops.ensure(n_tiles * 8)); PG_HIP_TRY(h, h->t_pts.ensure(n_tiles * 8)); PG_HIP_TRY(h, h->t_steps.ensure(n_tiles * 8));
     }
     const uint64_t max_ops = n / 2 + 1; // an op takes a digit and its terminator
-    if (max_ops > h->op_cap) {
-        uint64_t c1 = h->op_cap, c2 = h->op_cap, c3 = h->op_cap;
-        F1_TRY(h, hipStreamSynchronize(h->st));
-        F1_TRY(h, grow_dev(h->op_pts, c1, max_ops)); F1_TRY(h, grow_dev(h->op_steps, c2, max_ops)); F1_TRY(h, grow_dev(h->op_kind, c3, max_ops));
-        h->op_cap = max_ops;
+    if (max_ops * 8 > h->op_pts.cap) {
+        PG_HIP_TRY(h, hipStreamSynchronize(h->st));
+        PG_HIP_TRY(h, h->op_pts.ensure(max_ops * 8)); PG_HIP_TRY(h, h->op_steps.ensure(max_ops * 8)); PG_HIP_TRY(h, h->op_kind.ensure(max_ops));
     }
-    if (strs > h->sb_cap) { F1_TRY(h, hipStreamSynchronize(h->st)); F1_TRY(h, grow_dev(h->sb, h->sb_cap, strs)); }
-    if (np + 1ull > h->chunk_cap) { F1_TRY(h, hipStreamSynchronize(h->st)); F1_TRY(h, grow_dev(h->chunk_off, h->chunk_cap, np + 1ull)); }
+    if (strs * sizeof(StrBase) > h->sb.cap) { PG_HIP_TRY(h, hipStreamSynchronize(h->st)); PG_HIP_TRY(h, h->sb.ensure(strs * sizeof(StrBase))); }
+    if ((np + 1ull) * 8 > h->chunk_off.cap) { PG_HIP_TRY(h, hipStreamSynchronize(h->st)); PG_HIP_TRY(h, h->chunk_off.ensure((np + 1ull) * 8)); }
     if (n_tiles) {
-        hipLaunchKernelGGL(k_f1_tiles, dim3((uint32_t)n_tiles), dim3(kThreads), 0, h->st, p, n, sl.doff, ns, h->t_ops, h->t_pts, h->t_steps, sl.derr);
-        F1_TRY(h, hipGetLastError());
+        hipLaunchKernelGGL(k_f1_tiles, dim3((uint32_t)n_tiles), dim3(kThreads), 0, h->st, p, n, sl.doff.p, ns, h->t_ops.p, h->t_pts.p, h->t_steps.p, sl.derr.p);
+        PG_HIP_TRY(h, hipGetLastError());
     }
-    hipLaunchKernelGGL(k_f1_scan, dim3(1), dim3(1024), 0, h->st, (uint32_t)n_tiles, h->t_ops, h->t_pts, h->t_steps, sl.doff, ns, h->sb);
-    F1_TRY(h, hipGetLastError());
+    hipLaunchKernelGGL(k_f1_scan, dim3(1), dim3(1024), 0, h->st, (uint32_t)n_tiles, h->t_ops.p, h->t_pts.p, h->t_steps.p, sl.doff.p, ns, h->sb.p);
+    PG_HIP_TRY(h, hipGetLastError());
     if (n_tiles) {
-        hipLaunchKernelGGL(k_f1_emit, dim3((uint32_t)n_tiles), dim3(kThreads), 0, h->st, p, n, sl.doff, ns, h->t_ops, h->t_pts, h->t_steps,
-                           h->op_pts, h->op_steps, h->op_kind, h->sb, sl.derr);
-        F1_TRY(h, hipGetLastError());
+        hipLaunchKernelGGL(k_f1_emit, dim3((uint32_t)n_tiles), dim3(kThreads), 0, h->st, p, n, sl.doff.p, ns, h->t_ops.p, h->t_pts.p, h->t_steps.p,
+                           h->op_pts.p, h->op_steps.p, h->op_kind.p, h->sb.p, sl.derr.p);
+        PG_HIP_TRY(h, hipGetLastError());
     }
-    hipLaunchKernelGGL(k_f1_strings, dim3((ns + 255) / 256), dim3(256), 0, h->st, p, sl.doff, ns, sl.derr);
-    F1_TRY(h, hipGetLastError());
-    hipLaunchKernelGGL(k_f1_chunks, dim3((np + 255) / 256), dim3(256), 0, h->st, h->sb, np, h->chunk_off);
-    F1_TRY(h, hipGetLastError());
-    hipLaunchKernelGGL(k_f1_scan_u64, dim3(1), dim3(1024), 0, h->st, np, h->chunk_off);
-    F1_TRY(h, hipGetLastError());
-    F1_TRY(h, hipMemsetAsync(sl.dcounts, 0, 4ull * np * sizeof(unsigned long long), h->st));
+    hipLaunchKernelGGL(k_f1_strings, dim3((ns + 255) / 256), dim3(256), 0, h->st, p, sl.doff.p, ns, sl.derr.p);
+    PG_HIP_TRY(h, hipGetLastError());
+    hipLaunchKernelGGL(k_f1_chunks, dim3((np + 255) / 256), dim3(256), 0, h->st, h->sb.p, np, h->chunk_off.p);
+    PG_HIP_TRY(h, hipGetLastError());
+    hipLaunchKernelGGL(k_f1_scan_u64, dim3(1), dim3(1024), 0, h->st, np, h->chunk_off.p);
+    PG_HIP_TRY(h, hipGetLastError());
+    PG_HIP_TRY(h, hipMemsetAsync(sl.dcounts.p, 0, 4ull * np * sizeof(unsigned long long), h->st));
     // chunks <= sum over pairs of (ops / kChunk + 1) <= max_ops / kChunk + np
     const uint64_t grid = max_ops / kChunk + np + 1;
-    hipLaunchKernelGGL(k_f1_merge, dim3((uint32_t)grid), dim3(kThreads), 0, h->st, h->op_pts, h->op_steps, h->op_kind, h->sb, sl.dsig, sl.dref,
-                       h->chunk_off, np, h->prm, sl.dcounts, sl.derr);
-    F1_TRY(h, hipGetLastError());
-    F1_TRY(h, hipMemcpyAsync(sl.hcounts, sl.dcounts, 4ull * np * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->st));
-    F1_TRY(h, hipMemcpyAsync(sl.herr, sl.derr, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->st));
-    F1_TRY(h, hipEventRecord(sl.done, h->st));
+    hipLaunchKernelGGL(k_f1_merge, dim3((uint32_t)grid), dim3(kThreads), 0, h->st, h->op_pts.p, h->op_steps.p, h->op_kind.p, h->sb.p, sl.dsig.p, sl.dref.p,
+                       h->chunk_off.p, np, h->prm, sl.dcounts.p, sl.derr.p);
+    PG_HIP_TRY(h, hipGetLastError());
+    PG_HIP_TRY(h, hipMemcpyAsync(sl.hcounts.p, sl.dcounts.p, 4ull * np * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->st));
+    PG_HIP_TRY(h, hipMemcpyAsync(sl.herr.p, sl.derr.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->st));
+    PG_HIP_TRY(h, hipEventRecord(sl.done, h->st));
     sl.busy = true; sl.first_pair = h->n_pairs; sl.n_pairs = np;
     h->n_pairs += np;
     return PG_OK;
@@ -496,30 +457,26 @@ static pg_status f1_piece(pg_fscore *h, const uint8_t *bytes, bool dev, bool pin
 
 extern "C" {
 
-const char *pg_fscore_last_error(const pg_fscore *h) { return h ? h->err.c_str() : g_f1_create_error.c_str(); }
+const char *pg_fscore_last_error(const pg_fscore *h) { return h ? h->err.c_str() : pg_create_error<pg_fscore>().c_str(); }
 
 pg_status pg_fscore_create(const pg_fscore_params *params, int32_t device, pg_fscore **out) {
-    if (!out || !params) return f1_fail(nullptr, PG_ERR_INVALID_ARG, "pg_fscore_create: null argument");
+    if (!out || !params) return pg_fail<pg_fscore>(nullptr, PG_ERR_INVALID_ARG, "pg_fscore_create: null argument");
     *out = nullptr;
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) return f1_fail(nullptr, PG_ERR_NO_DEVICE, "no HIP device available (%s); libpgmove has no CPU fallback", e != hipSuccess ? hipGetErrorString(e) : "device count 0");
-    if (device < 0 || device >= ndev) return f1_fail(nullptr, PG_ERR_NO_DEVICE, "device %d out of range (have %d)", device, ndev);
-    e = hipSetDevice(device);
-    if (e != hipSuccess) return f1_fail(nullptr, PG_ERR_NO_DEVICE, "hipSetDevice(%d): %s", device, hipGetErrorString(e));
+    if (pg_status st = pg_select_device<pg_fscore>(device)) return st;
     pg_fscore *h = new pg_fscore();
     h->device = device;
     h->prm = F1Params{params->rna ? -1 : 1, params->use_region ? 1 : 0, (long long)params->threshold, (long long)params->region_start,
                       (long long)params->region_end};
-    auto bail = [&](pg_status s) { g_f1_create_error = h->err; pg_fscore_destroy(h); return s; };
-#define KTRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { f1_fail(h, PG_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); return bail(PG_ERR_HIP); } } while (0)
-    KTRY(hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking));
-    for (Slot &sl : h->slot) {
-        KTRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-        KTRY(hipMalloc((void **)&sl.derr, sizeof(unsigned long long)));
-        KTRY(hipHostMalloc((void **)&sl.herr, sizeof(unsigned long long), hipHostMallocDefault));
-    }
-#undef KTRY
+    auto init = [&]() -> pg_status {
+        PG_HIP_TRY(h, hipStreamCreateWithFlags(&h->st.h, hipStreamNonBlocking));
+        for (Slot &sl : h->slot) {
+            PG_HIP_TRY(h, hipEventCreateWithFlags(&sl.done.h, hipEventDisableTiming));
+            PG_HIP_TRY(h, sl.derr.ensure(sizeof(unsigned long long)));
+            PG_HIP_TRY(h, sl.herr.ensure(sizeof(unsigned long long)));
+        }
+        return PG_OK;
+    };
+    if (pg_status st = init()) return pg_create_failed(h, st, pg_fscore_destroy);
     *out = h;
     return PG_OK;
 }
@@ -528,44 +485,29 @@ void pg_fscore_destroy(pg_fscore *h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->st) (void)hipStreamSynchronize(h->st);
-    for (Slot &sl : h->slot) {
-        (void)hipFree(sl.dbytes); (void)hipFree(sl.doff); (void)hipFree(sl.dsig); (void)hipFree(sl.dref); (void)hipFree(sl.dcounts); (void)hipFree(sl.derr);
-        if (sl.stage) (void)hipHostFree(sl.stage);
-        if (sl.hoff) (void)hipHostFree(sl.hoff);
-        if (sl.hsig) (void)hipHostFree(sl.hsig);
-        if (sl.href) (void)hipHostFree(sl.href);
-        if (sl.hcounts) (void)hipHostFree(sl.hcounts);
-        if (sl.herr) (void)hipHostFree(sl.herr);
-        if (sl.done) (void)hipEventDestroy(sl.done);
-    }
-    (void)hipFree(h->t_ops); (void)hipFree(h->t_pts); (void)hipFree(h->t_steps);
-    (void)hipFree(h->op_pts); (void)hipFree(h->op_steps); (void)hipFree(h->op_kind); (void)hipFree(h->sb); (void)hipFree(h->chunk_off);
-    if (h->st) (void)hipStreamDestroy(h->st);
     delete h;
 }
 
 pg_status pg_fscore_submit(pg_fscore *h, const pg_fscore_batch *b) {
-    if (!h) return f1_fail(nullptr, PG_ERR_INVALID_ARG, "pg_fscore_submit: null handle");
-    if (!b) return f1_fail(h, PG_ERR_INVALID_ARG, "pg_fscore_submit: null batch");
+    if (!h) return pg_fail<pg_fscore>(nullptr, PG_ERR_INVALID_ARG, "pg_fscore_submit: null handle");
+    if (!b) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fscore_submit: null batch");
     if (!b->n_pairs) return PG_OK;
-    if (!b->ss_off || !b->sig_start || !b->first_ref) return f1_fail(h, PG_ERR_INVALID_ARG, "pg_fscore_submit: null array");
-    if (b->location != PG_LOC_HOST && b->location != PG_LOC_DEVICE) return f1_fail(h, PG_ERR_INVALID_ARG, "pg_fscore_submit: location must be PG_LOC_HOST or PG_LOC_DEVICE");
-    F1_TRY(h, hipSetDevice(h->device));
+    if (!b->ss_off || !b->sig_start || !b->first_ref) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fscore_submit: null array");
+    if (b->location != PG_LOC_HOST && b->location != PG_LOC_DEVICE) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fscore_submit: location must be PG_LOC_HOST or PG_LOC_DEVICE");
+    PG_HIP_TRY(h, hipSetDevice(h->device));
     const uint64_t ns = 2 * b->n_pairs;
     const uint64_t *off = b->ss_off;
     for (uint64_t s = 0; s < ns; s++)
-        if (off[s + 1] < off[s]) return f1_fail(h, PG_ERR_INVALID_ARG, "pg_fscore_submit: ss_off decreases at string %llu", (unsigned long long)s);
+        if (off[s + 1] < off[s]) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fscore_submit: ss_off decreases at string %llu", (unsigned long long)s);
     const uint64_t total = off[ns] - off[0];
-    if (total && !b->ss) return f1_fail(h, PG_ERR_INVALID_ARG, "pg_fscore_submit: null ss");
+    if (total && !b->ss) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fscore_submit: null ss");
     const bool dev = b->location == PG_LOC_DEVICE;
     bool pinned = false;
     if (total) {
-        hipPointerAttribute_t a{};
-        const bool known = hipPointerGetAttributes(&a, b->ss + off[0]) == hipSuccess;
-        (void)hipGetLastError();
-        if (dev && (!known || a.type != hipMemoryTypeDevice || a.device != h->device))
-            return f1_fail(h, PG_ERR_INVALID_ARG, "pg_fscore_submit: PG_LOC_DEVICE ss is not device memory of device %d", h->device);
-        pinned = !dev && known && a.type == hipMemoryTypeHost;
+        const PgPtrKind kind = pg_ptr_kind(b->ss + off[0], h->device);
+        if (dev && kind != PG_PTR_DEVICE)
+            return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fscore_submit: PG_LOC_DEVICE ss is not device memory of device %d", h->device);
+        pinned = !dev && kind == PG_PTR_PINNED;
     }
     h->counts.resize(4 * (h->n_pairs + b->n_pairs));
     // pieces of whole pairs: at most kUnit bytes and kUnitPairs pairs, a larger pair alone
@@ -577,20 +519,20 @@ pg_status pg_fscore_submit(pg_fscore *h, const pg_fscore_batch *b) {
         p0 = p1;
     }
     // the caller may reuse its host memory once submit returns: pageable input was staged above, page-locked input is read by the copies
-    if (pinned) F1_TRY(h, hipStreamSynchronize(h->st));
+    if (pinned) PG_HIP_TRY(h, hipStreamSynchronize(h->st));
     return PG_OK;
 }
 
 pg_status pg_fscore_sync(pg_fscore *h) {
-    if (!h) return f1_fail(nullptr, PG_ERR_INVALID_ARG, "pg_fscore_sync: null handle");
-    F1_TRY(h, hipSetDevice(h->device));
+    if (!h) return pg_fail<pg_fscore>(nullptr, PG_ERR_INVALID_ARG, "pg_fscore_sync: null handle");
+    PG_HIP_TRY(h, hipSetDevice(h->device));
     for (int k = 0; k < 2; k++) if (pg_status s = f1_drain(h, h->slot[h->next ^ k])) return s; // the older piece first
     return PG_OK;
 }
 
 pg_status pg_fscore_finish(pg_fscore *h, pg_fscore_result *out, uint64_t *pair_counts, uint64_t cap_pairs) {
-    if (!h) return f1_fail(nullptr, PG_ERR_INVALID_ARG, "pg_fscore_finish: null handle");
-    if (!out) return f1_fail(h, PG_ERR_INVALID_ARG, "pg_fscore_finish: null result");
+    if (!h) return pg_fail<pg_fscore>(nullptr, PG_ERR_INVALID_ARG, "pg_fscore_finish: null handle");
+    if (!out) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fscore_finish: null result");
     memset(out, 0, sizeof *out);
     pg_status st = pg_fscore_sync(h);
     if (st == PG_OK) {
@@ -604,7 +546,7 @@ pg_status pg_fscore_finish(pg_fscore *h, pg_fscore_result *out, uint64_t *pair_c
             out->err_pair = (int64_t)pair;
             out->err_code = code;
             out->err_side = side;
-            st = f1_fail(h, PG_ERR_INPUT, "pair %llu, file %u: %s", (unsigned long long)pair, side + 1, code < 6 ? what[code] : "?");
+            st = pg_fail(h, PG_ERR_INPUT, "pair %llu, file %u: %s", (unsigned long long)pair, side + 1, code < 6 ? what[code] : "?");
         } else {
             for (uint64_t i = 0; i < h->n_pairs; i++)
                 for (int c = 0; c < 4; c++) out->totals[c] += h->counts[4 * i + c];

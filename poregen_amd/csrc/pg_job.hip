@@ -16,12 +16,11 @@
 #include "../../include/pgmove.h"
 #include "pg_internal.h"
 #include "pg_hostmem.h"
+#include "pg_hip_host.h"
 #include <rccl/rccl.h>
 
 #include <algorithm>
 #include <condition_variable>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <dlfcn.h>
 #include <functional>
@@ -35,8 +34,6 @@ extern "C" const double *pgi_fin_dev(pg_ctx *c); // pg_api.hip: where pg_finish_
 extern "C" uint64_t pgi_full_slots_settled(const pg_ctx *c); // pg_api.hip: k-mers complete after the last settled batch
 extern "C" pg_status pgi_skip_stats(pg_ctx *c); // pg_api.hip: a deferred-statistics batch that will keep nothing needs none
 extern "C" pg_status pgi_stats_gathered(pg_ctx *c, const uint64_t *all_counts, uint32_t world, uint32_t rank); // pg_api.hip: pg_stats, cancelled on the device when the rows below `rank` complete every k-mer
-
-static thread_local std::string g_job_create_error;
 
 namespace {
 
@@ -129,15 +126,8 @@ struct pg_job {
     bool merged = false; pg_result merged_view{};
     bool samples_on_host = false, samples_on_dev = false, small_on_dev = false; // where the merged view's arrays are (device = md[] on the first device)
     // pg_job_model
-    void *md[4] = {nullptr, nullptr, nullptr, nullptr}; size_t md_cap[4] = {0, 0, 0, 0};
+    PgDev<> md[4];
 };
-
-static pg_status jfail(pg_job *j, pg_status code, const char *fmt, ...) {
-    char buf[1200];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    if (j) j->err = buf; else g_job_create_error = buf;
-    return code;
-}
 
 // fn(g) on rank g's own thread, all ranks at once; the first failing rank (lowest shard = first in PAF order) decides
 static pg_status on_ranks(pg_job *j, const std::function<pg_status(uint32_t, std::string &)> &fn) {
@@ -146,16 +136,15 @@ static pg_status on_ranks(pg_job *j, const std::function<pg_status(uint32_t, std
     for (uint32_t g = 0; g < j->n; ++g) j->workers[g].post([&, g] { rc[g] = fn(g, msg[g]); });
     for (uint32_t g = 0; g < j->n; ++g) j->workers[g].wait();
     for (uint32_t g = 0; g < j->n; ++g)
-        if (rc[g] != PG_OK) return jfail(j, rc[g], "shard %u (device %d): %s", g, j->devices[g], msg[g].c_str());
+        if (rc[g] != PG_OK) return pg_fail(j, rc[g], "shard %u (device %d): %s", g, j->devices[g], msg[g].c_str());
     return PG_OK;
 }
 
-#define JHIP(j, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return jfail((j), PG_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
-#define JNCCL(j, expr) do { ncclResult_t r_ = (expr); if (r_ != ncclSuccess) return jfail((j), PG_ERR_HIP, "%s failed: %s", #expr, rccl().GetErrorString ? rccl().GetErrorString(r_) : "?"); } while (0)
+#define JNCCL(j, expr) do { ncclResult_t r_ = (expr); if (r_ != ncclSuccess) return pg_fail((j), PG_ERR_HIP, "%s failed: %s", #expr, rccl().GetErrorString ? rccl().GetErrorString(r_) : "?"); } while (0)
 
 extern "C" {
 
-const char *pg_job_last_error(const pg_job *j) { return j ? j->err.c_str() : g_job_create_error.c_str(); }
+const char *pg_job_last_error(const pg_job *j) { return j ? j->err.c_str() : pg_create_error<pg_job>().c_str(); }
 int32_t pg_job_uses_rccl(const pg_job *j) { return j && j->use_rccl; }
 
 void pg_job_destroy(pg_job *j) {
@@ -177,7 +166,7 @@ void pg_job_destroy(pg_job *j) {
         if (g < j->ev_gathered.size() && j->ev_gathered[g]) (void)hipEventDestroy(j->ev_gathered[g]);
         if (g < j->gbuf.size() && j->gbuf[g]) (void)hipFree(j->gbuf[g]);
     }
-    if (j->n) { (void)hipSetDevice(j->devices[0]); for (void *p : j->md) if (p) (void)hipFree(p); }
+    if (j->n) { (void)hipSetDevice(j->devices[0]); for (auto &b : j->md) b.release(); }
     for (auto c : j->ctx) if (c) pg_destroy(c);
     for (auto &w : j->workers) w.stop();
     delete j;
@@ -185,15 +174,15 @@ void pg_job_destroy(pg_job *j) {
 }
 
 pg_status pg_job_create(const pg_params *p, const int32_t *devices, uint32_t n, uint32_t exchange, pg_job **out) {
-    if (!p || !devices || !out || n == 0 || n > 64) return jfail(nullptr, PG_ERR_INVALID_ARG, "pg_job_create: params / devices / n_devices (1..64)");
+    if (!p || !devices || !out || n == 0 || n > 64) return pg_fail<pg_job>(nullptr, PG_ERR_INVALID_ARG, "pg_job_create: params / devices / n_devices (1..64)");
     *out = nullptr;
-    if (exchange > PG_JOB_EXCHANGE_RCCL) return jfail(nullptr, PG_ERR_INVALID_ARG, "pg_job_create: unknown exchange mode %u", exchange);
+    if (exchange > PG_JOB_EXCHANGE_RCCL) return pg_fail<pg_job>(nullptr, PG_ERR_INVALID_ARG, "pg_job_create: unknown exchange mode %u", exchange);
     bool distinct = true;
     for (uint32_t a = 0; a < n; ++a) for (uint32_t b = a + 1; b < n; ++b) if (devices[a] == devices[b]) distinct = false;
     bool want_rccl = exchange == PG_JOB_EXCHANGE_RCCL || (exchange == PG_JOB_EXCHANGE_AUTO && distinct);
-    if (want_rccl && !distinct) return jfail(nullptr, PG_ERR_INVALID_ARG, "pg_job_create: RCCL needs distinct devices (a device is listed twice)");
+    if (want_rccl && !distinct) return pg_fail<pg_job>(nullptr, PG_ERR_INVALID_ARG, "pg_job_create: RCCL needs distinct devices (a device is listed twice)");
     if (want_rccl && !rccl().ok()) {
-        if (exchange == PG_JOB_EXCHANGE_RCCL) return jfail(nullptr, PG_ERR_NO_DEVICE, "pg_job_create: RCCL is not available: %s", rccl().why.c_str());
+        if (exchange == PG_JOB_EXCHANGE_RCCL) return pg_fail<pg_job>(nullptr, PG_ERR_NO_DEVICE, "pg_job_create: RCCL is not available: %s", rccl().why.c_str());
         want_rccl = false;
     }
     pg_job *j = new pg_job();
@@ -203,7 +192,6 @@ pg_status pg_job_create(const pg_params *p, const int32_t *devices, uint32_t n, 
     j->ev_counted.assign(n, nullptr); j->ev_gathered.assign(n, nullptr);
     j->workers = std::vector<Worker>(n); j->shard = std::vector<Shard>(n);
     for (auto &w : j->workers) w.start();
-    auto bail = [&](pg_status s) { g_job_create_error = j->err; pg_job_destroy(j); return s; };
     // the contexts come up side by side (the HIP runtime takes 0.1-0.2 s per device)
     pg_status s = on_ranks(j, [&](uint32_t g, std::string &msg) -> pg_status {
         pg_params q = *p;
@@ -221,14 +209,14 @@ pg_status pg_job_create(const pg_params *p, const int32_t *devices, uint32_t n, 
         if (e != hipSuccess) { msg = hipGetErrorString(e); return PG_ERR_HIP; }
         return PG_OK;
     });
-    if (s != PG_OK) return bail(s);
+    if (s != PG_OK) return pg_create_failed(j, s, pg_job_destroy);
     if (j->use_rccl) {
         j->comms.assign(n, nullptr);
         const ncclResult_t r = rccl().CommInitAll(j->comms.data(), (int)n, j->devices.data());
         if (r != ncclSuccess) {
-            jfail(j, PG_ERR_HIP, "ncclCommInitAll over %u devices failed: %s", n, rccl().GetErrorString(r));
+            pg_fail(j, PG_ERR_HIP, "ncclCommInitAll over %u devices failed: %s", n, rccl().GetErrorString(r));
             j->comms.clear();
-            if (exchange == PG_JOB_EXCHANGE_RCCL) return bail(PG_ERR_HIP);
+            if (exchange == PG_JOB_EXCHANGE_RCCL) return pg_create_failed(j, PG_ERR_HIP, pg_job_destroy);
             j->use_rccl = false; j->err.clear();
         }
     }
@@ -256,10 +244,10 @@ static pg_status job_exchange_and_collect(pg_job *j, std::vector<uint64_t> &&cut
 
 pg_status pg_job_submit(pg_job *j, const pg_batch *b) {
     if (!j || !b) return PG_ERR_INVALID_ARG;
-    if (b->struct_size != sizeof(pg_batch)) return jfail(j, PG_ERR_INVALID_ARG, "pg_batch.struct_size mismatch");
-    if (b->location != PG_LOC_HOST) return jfail(j, PG_ERR_UNSUPPORTED, "pg_job_submit takes host batches (shards that are resident on their devices: pg_job_submit_shards)");
+    if (b->struct_size != sizeof(pg_batch)) return pg_fail(j, PG_ERR_INVALID_ARG, "pg_batch.struct_size mismatch");
+    if (b->location != PG_LOC_HOST) return pg_fail(j, PG_ERR_UNSUPPORTED, "pg_job_submit takes host batches (shards that are resident on their devices: pg_job_submit_shards)");
     const uint32_t n = j->n, nr = b->n_reads;
-    if (!b->sig_off || !b->seq_off || !b->op_off) return jfail(j, PG_ERR_INVALID_ARG, "batch offsets missing");
+    if (!b->sig_off || !b->seq_off || !b->op_off) return pg_fail(j, PG_ERR_INVALID_ARG, "batch offsets missing");
     j->merged = false;
     // contiguous shards of about equal numbers of samples (reads differ in length; any contiguous cut is correct)
     std::vector<uint64_t> cut(n + 1, 0);
@@ -310,21 +298,21 @@ pg_status pg_job_submit(pg_job *j, const pg_batch *b) {
 pg_status pg_job_submit_shards(pg_job *j, const pg_batch *shards, uint32_t n_shards) {
     if (!j || !shards) return PG_ERR_INVALID_ARG;
     const uint32_t n = j->n;
-    if (n_shards != n) return jfail(j, PG_ERR_INVALID_ARG, "pg_job_submit_shards: %u shards for a job of %u devices", n_shards, n);
+    if (n_shards != n) return pg_fail(j, PG_ERR_INVALID_ARG, "pg_job_submit_shards: %u shards for a job of %u devices", n_shards, n);
     std::vector<uint64_t> cut(n + 1, 0), shard_ops(n, 0);
     for (uint32_t g = 0; g < n; ++g) {
-        if (shards[g].struct_size != sizeof(pg_batch)) return jfail(j, PG_ERR_INVALID_ARG, "pg_batch.struct_size mismatch (shard %u)", g);
-        if (shards[g].location != PG_LOC_DEVICE && shards[g].location != PG_LOC_HOST) return jfail(j, PG_ERR_INVALID_ARG, "shard %u: pg_batch.location", g);
+        if (shards[g].struct_size != sizeof(pg_batch)) return pg_fail(j, PG_ERR_INVALID_ARG, "pg_batch.struct_size mismatch (shard %u)", g);
+        if (shards[g].location != PG_LOC_DEVICE && shards[g].location != PG_LOC_HOST) return pg_fail(j, PG_ERR_INVALID_ARG, "shard %u: pg_batch.location", g);
         if (shards[g].location == PG_LOC_DEVICE && shards[g].n_reads) {
             // a device shard must live on the device that works it (advisor r05): one attribute query per shard and submit. A pointer the
             // runtime does not know (or managed / host memory) is refused here rather than faulting inside the first kernel that reads it.
             const void *probe[] = {shards[g].sig, shards[g].sig_off, shards[g].op_n, shards[g].seq};
             for (const void *ptr : probe) {
-                hipPointerAttribute_t at; memset(&at, 0, sizeof at);
-                const hipError_t e = ptr ? hipPointerGetAttributes(&at, ptr) : hipErrorInvalidValue;
-                if (e != hipSuccess) { (void)hipGetLastError(); return jfail(j, PG_ERR_INVALID_ARG, "shard %u: a PG_LOC_DEVICE array is not device memory known to the runtime", g); }
-                if (at.type != hipMemoryTypeDevice || at.device != j->devices[g])
-                    return jfail(j, PG_ERR_INVALID_ARG, "shard %u: its arrays live on device %d, the job works it on device %d", g, at.device, j->devices[g]);
+                int owner = 0;
+                const PgPtrKind kind = pg_ptr_kind(ptr, j->devices[g], &owner);
+                if (kind == PG_PTR_UNKNOWN) return pg_fail(j, PG_ERR_INVALID_ARG, "shard %u: a PG_LOC_DEVICE array is not device memory known to the runtime", g);
+                if (kind != PG_PTR_DEVICE)
+                    return pg_fail(j, PG_ERR_INVALID_ARG, "shard %u: its arrays live on device %d, the job works it on device %d", g, owner, j->devices[g]);
             }
         }
         cut[g + 1] = cut[g] + shards[g].n_reads;
@@ -353,18 +341,18 @@ static pg_status job_exchange_and_collect(pg_job *j, std::vector<uint64_t> &&cut
     j->full_slots_prev = j->have_batch ? pgi_full_slots_settled(j->ctx[n - 1]) : 0; // k-mers the job had completed before this batch (the last shard's cut saw them all)
     // phase 2: the exchange
     if (j->use_rccl) {
-        for (uint32_t g = 0; g < n; ++g) { JHIP(j, hipSetDevice(j->devices[g])); JHIP(j, hipStreamWaitEvent(j->comm_st[g], j->ev_counted[g], 0)); }
+        for (uint32_t g = 0; g < n; ++g) { PG_HIP_TRY(j, hipSetDevice(j->devices[g])); PG_HIP_TRY(j, hipStreamWaitEvent(j->comm_st[g], j->ev_counted[g], 0)); }
         JNCCL(j, rccl().GroupStart());
         for (uint32_t g = 0; g < n; ++g) {
             uint64_t *rows = j->gbuf[g] + ns; // rows 1..n: sendbuff == recvbuff + rank * count, i.e. in place
             const ncclResult_t r = rccl().AllGather(rows + (size_t)g * ns, rows, ns, ncclUint64, j->comms[g], j->comm_st[g]);
-            if (r != ncclSuccess) { (void)rccl().GroupEnd(); return jfail(j, PG_ERR_HIP, "ncclAllGather (rank %u) failed: %s", g, rccl().GetErrorString(r)); }
+            if (r != ncclSuccess) { (void)rccl().GroupEnd(); return pg_fail(j, PG_ERR_HIP, "ncclAllGather (rank %u) failed: %s", g, rccl().GetErrorString(r)); }
         }
         JNCCL(j, rccl().GroupEnd());
-        for (uint32_t g = 0; g < n; ++g) { JHIP(j, hipSetDevice(j->devices[g])); JHIP(j, hipEventRecord(j->ev_gathered[g], j->comm_st[g])); }
+        for (uint32_t g = 0; g < n; ++g) { PG_HIP_TRY(j, hipSetDevice(j->devices[g])); PG_HIP_TRY(j, hipEventRecord(j->ev_gathered[g], j->comm_st[g])); }
     }
     else // through host memory: every rank's row has been queued for download behind its counting kernels (phase 1)
-        for (uint32_t g = 0; g < n; ++g) { JHIP(j, hipSetDevice(j->devices[g])); JHIP(j, hipStreamSynchronize((hipStream_t)pgi_stream(j->ctx[g]))); }
+        for (uint32_t g = 0; g < n; ++g) { PG_HIP_TRY(j, hipSetDevice(j->devices[g])); PG_HIP_TRY(j, hipStreamSynchronize((hipStream_t)pgi_stream(j->ctx[g]))); }
     // phase 3, every rank on its own thread: the statistics behind the ISSUE of the collective, then the wait for it (on the
     // stream, not on the host), the cut + gather, and the new running total into row 0 for the next batch
     s = on_ranks(j, [&](uint32_t g, std::string &msg) -> pg_status {
@@ -465,7 +453,7 @@ int32_t pg_job_poll(pg_job *j) {
     for (uint32_t g = 0; g < j->n; ++g) {
         const int32_t r = pg_poll(j->ctx[g]);
         if (r == 0) return 0;
-        if (r < 0) return jfail(j, r, "shard %u (device %d): %s", g, j->devices[g], pg_last_error(j->ctx[g]));
+        if (r < 0) return pg_fail(j, r, "shard %u (device %d): %s", g, j->devices[g], pg_last_error(j->ctx[g]));
     }
     return 1;
 }
@@ -477,11 +465,7 @@ int32_t pg_job_all_slots_full_settled(const pg_job *j) {
 
 // md[i] (device 0) grown to hold `bytes`
 static pg_status md_ensure(pg_job *j, int i, size_t bytes) {
-    if (bytes + 16 <= j->md_cap[i]) return PG_OK;
-    if (j->md[i]) JHIP(j, hipFree(j->md[i]));
-    j->md[i] = nullptr; j->md_cap[i] = 0;
-    JHIP(j, hipMalloc(&j->md[i], bytes + bytes / 8 + 64));
-    j->md_cap[i] = bytes + bytes / 8 + 64;
+    PG_HIP_TRY(j, j->md[i].ensure(bytes + 16, bytes + bytes / 8 + 64));
     return PG_OK;
 }
 
@@ -498,7 +482,7 @@ static pg_status job_finish(pg_job *j, pg_result *out, bool want_samples) {
         if (want_samples && !j->samples_on_host && j->merged_view.n_samples) { // deferred before, wanted now: one download
             const uint64_t n_samples = j->merged_view.n_samples;
             j->r_samples.resize(n_samples);
-            JHIP(j, hipSetDevice(j->devices[0]));
+            PG_HIP_TRY(j, hipSetDevice(j->devices[0]));
             const unsigned parts = n_samples * 8ull >= (64ull << 20) ? 8u : 1u;
             const uint64_t step = ((n_samples + parts - 1) / parts + 511) & ~511ull;
             std::vector<hipError_t> rc(parts, hipSuccess);
@@ -508,10 +492,10 @@ static pg_status job_finish(pg_job *j, pg_result *out, bool want_samples) {
                     const uint64_t a = std::min<uint64_t>(n_samples, t * step), b2 = std::min<uint64_t>(n_samples, a + step);
                     if (b2 <= a) return;
                     rc[t] = hipSetDevice(j->devices[0]);
-                    if (rc[t] == hipSuccess) rc[t] = hipMemcpy(j->r_samples.data() + a, (const double *)j->md[3] + a, (b2 - a) * 8ull, hipMemcpyDeviceToHost);
+                    if (rc[t] == hipSuccess) rc[t] = hipMemcpy(j->r_samples.data() + a, (const double *)j->md[3].p + a, (b2 - a) * 8ull, hipMemcpyDeviceToHost);
                 });
             for (auto &th : pool) th.join();
-            for (hipError_t e2 : rc) JHIP(j, e2);
+            for (hipError_t e2 : rc) PG_HIP_TRY(j, e2);
             j->samples_on_host = true;
             j->merged_view.samples = j->r_samples.data();
         }
@@ -619,7 +603,7 @@ static pg_status job_finish(pg_job *j, pg_result *out, bool want_samples) {
     j->samples_on_host = !all_dev; j->samples_on_dev = false;
     if (all_dev && n_samples) { // the concatenation on the first device
         const int dev0 = j->devices[0];
-        JHIP(j, hipSetDevice(dev0));
+        PG_HIP_TRY(j, hipSetDevice(dev0));
         hipStream_t st0 = (hipStream_t)pgi_stream(j->ctx[0]);
         { const pg_status se = md_ensure(j, 3, n_samples * 8ull); if (se != PG_OK) return se; }
         std::vector<void *> staged(n, nullptr);
@@ -631,7 +615,7 @@ static pg_status job_finish(pg_job *j, pg_result *out, bool want_samples) {
             if (j->devices[g] == dev0 && !force_peer) { base[g] = dev_src[g]; continue; }
             hipError_t e = hipMalloc(&staged[g], R[g].n_samples * 8ull); // this rank's stream over xGMI, whole
             if (e == hipSuccess) e = hipMemcpyPeerAsync(staged[g], dev0, dev_src[g], j->devices[g], R[g].n_samples * 8ull, st0);
-            if (e != hipSuccess) { drop_staged(); return jfail(j, PG_ERR_HIP, "peer copy of shard %u's samples (device %d -> %d): %s", g, j->devices[g], dev0, hipGetErrorString(e)); }
+            if (e != hipSuccess) { drop_staged(); return pg_fail(j, PG_ERR_HIP, "peer copy of shard %u's samples (device %d -> %d): %s", g, j->devices[g], dev0, hipGetErrorString(e)); }
             base[g] = static_cast<const double *>(staged[g]);
         }
         size_t nseg = 0;
@@ -644,11 +628,11 @@ static pg_status job_finish(pg_job *j, pg_result *out, bool want_samples) {
         void *dseg = nullptr;
         hipError_t e = hipMalloc(&dseg, segs.size() * sizeof(PgSeg) + 16);
         if (e == hipSuccess) e = hipMemcpyAsync(dseg, segs.data(), segs.size() * sizeof(PgSeg), hipMemcpyHostToDevice, st0);
-        if (e == hipSuccess) e = pg_launch_merge_segments(st0, static_cast<const PgSeg *>(dseg), (uint32_t)segs.size(), static_cast<double *>(j->md[3]), n_samples);
+        if (e == hipSuccess) e = pg_launch_merge_segments(st0, static_cast<const PgSeg *>(dseg), (uint32_t)segs.size(), static_cast<double *>(j->md[3].p), n_samples);
         if (e == hipSuccess) e = hipStreamSynchronize(st0);
         if (dseg) (void)hipFree(dseg);
         drop_staged();
-        if (e != hipSuccess) return jfail(j, PG_ERR_HIP, "device merge of the shards' samples: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return pg_fail(j, PG_ERR_HIP, "device merge of the shards' samples: %s", hipGetErrorString(e));
         j->samples_on_dev = true;
     }
     pg_result &v = j->merged_view;
@@ -671,7 +655,7 @@ pg_status pg_job_fetch_samples(pg_job *j, uint64_t first, uint64_t n, double *ds
     if (first > j->merged_view.n_samples || n > j->merged_view.n_samples - first) return PG_ERR_INVALID_ARG;
     if (!n) return PG_OK;
     if (j->samples_on_host) { memcpy(dst, j->r_samples.data() + first, n * sizeof(double)); return PG_OK; }
-    if (hipSetDevice(j->devices[0]) != hipSuccess || hipMemcpy(dst, (const double *)j->md[3] + first, n * 8ull, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return PG_ERR_HIP; }
+    if (hipSetDevice(j->devices[0]) != hipSuccess || hipMemcpy(dst, (const double *)j->md[3].p + first, n * 8ull, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return PG_ERR_HIP; }
     return PG_OK;
 }
 
@@ -679,7 +663,7 @@ pg_status pg_job_fetch_samples(pg_job *j, uint64_t first, uint64_t n, double *ds
 static pg_status job_device_view(pg_job *j, pg_result *R) {
     pg_status s = job_finish(j, R, false);
     if (s != PG_OK) return s;
-    JHIP(j, hipSetDevice(j->devices[0]));
+    PG_HIP_TRY(j, hipSetDevice(j->devices[0]));
     const void *src[4] = {R->ev_off, R->samp_off, R->ev_len, j->samples_on_dev ? nullptr : j->r_samples.data()};
     const size_t bytes[4] = {(R->n_slots + 1) * 8ull, (R->n_events + 1) * 8ull, R->n_events * 4ull, R->n_samples * 8ull};
     for (int i = 0; i < 4; ++i) {
@@ -687,7 +671,7 @@ static pg_status job_device_view(pg_job *j, pg_result *R) {
         if (i == 3 && (j->samples_on_dev || !bytes[3])) continue;
         s = md_ensure(j, i, bytes[i]);
         if (s != PG_OK) return s;
-        if (bytes[i]) JHIP(j, hipMemcpy(j->md[i], src[i], bytes[i], hipMemcpyHostToDevice));
+        if (bytes[i]) PG_HIP_TRY(j, hipMemcpy(j->md[i].p, src[i], bytes[i], hipMemcpyHostToDevice));
     }
     j->small_on_dev = true;
     if (bytes[3]) j->samples_on_dev = true; // (a host merge's samples are now there as well)
@@ -699,8 +683,8 @@ pg_status pg_job_text(pg_job *j, pg_text_result *out) {
     pg_result R;
     pg_status s = job_device_view(j, &R);
     if (s != PG_OK) return s;
-    s = pg_text_device(j->ctx[0], R.n_slots, R.n_events, (const uint64_t *)j->md[0], (const uint64_t *)j->md[1], (const double *)j->md[3], out);
-    if (s != PG_OK) return jfail(j, s, "%s", pg_last_error(j->ctx[0]));
+    s = pg_text_device(j->ctx[0], R.n_slots, R.n_events, (const uint64_t *)j->md[0].p, (const uint64_t *)j->md[1].p, (const double *)j->md[3].p, out);
+    if (s != PG_OK) return pg_fail(j, s, "%s", pg_last_error(j->ctx[0]));
     return PG_OK;
 }
 pg_status pg_job_fetch_text(pg_job *j, uint64_t first, uint64_t n, char *dst) { return j ? pg_fetch_text(j->ctx[0], first, n, dst) : PG_ERR_INVALID_ARG; }
@@ -708,7 +692,7 @@ pg_status pg_job_fetch_text(pg_job *j, uint64_t first, uint64_t n, char *dst) { 
 pg_status pg_job_kernel_stats(pg_job *j, uint32_t shard, pg_kernel_stat *out, uint32_t cap, uint32_t *n_out) {
     if (!j || shard >= j->n) return PG_ERR_INVALID_ARG;
     const pg_status st = pg_kernel_stats(j->ctx[shard], out, cap, n_out);
-    return st == PG_OK ? PG_OK : jfail(j, st, "shard %u: %s", shard, pg_last_error(j->ctx[shard]));
+    return st == PG_OK ? PG_OK : pg_fail(j, st, "shard %u: %s", shard, pg_last_error(j->ctx[shard]));
 }
 
 pg_status pg_job_model(pg_job *j, uint32_t flags, pg_model_result *out) {
@@ -716,8 +700,8 @@ pg_status pg_job_model(pg_job *j, uint32_t flags, pg_model_result *out) {
     pg_result R;
     pg_status s = job_device_view(j, &R);
     if (s != PG_OK) return s;
-    s = pg_model_device(j->ctx[0], R.n_slots, (const uint64_t *)j->md[0], (const uint64_t *)j->md[1], (const uint32_t *)j->md[2], (const double *)j->md[3], flags, out);
-    if (s != PG_OK) return jfail(j, s, "%s", pg_last_error(j->ctx[0]));
+    s = pg_model_device(j->ctx[0], R.n_slots, (const uint64_t *)j->md[0].p, (const uint64_t *)j->md[1].p, (const uint32_t *)j->md[2].p, (const double *)j->md[3].p, flags, out);
+    if (s != PG_OK) return pg_fail(j, s, "%s", pg_last_error(j->ctx[0]));
     return PG_OK;
 }
 

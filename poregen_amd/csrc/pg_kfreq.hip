@@ -20,10 +20,9 @@
 // Equal codes a thread meets back to back (homopolymers) are added once, as a run.
 #include "../../include/pgmove.h"
 #include <hip/hip_runtime.h>
+#include "pg_hip_host.h"
 
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <deque>
@@ -315,25 +314,23 @@ struct OddHash {
     }
 };
 
-thread_local std::string g_kf_create_error;
-
 } // namespace
 
 struct pg_kfreq {
     uint32_t k = 0, n_codes = 0;
     int device = 0;
     uint64_t unit = kUnit; // <= odd_cap: a unit never has more windows than the list holds
-    hipStream_t ks = nullptr, cs = nullptr; // count stream, copy stream (host input)
+    PgStream ks, cs; // count stream, copy stream (host input)
+    PgEvent copied[2], counted[2], snap_ev[kSnapRing];
+    PgDev<> mem[6];  // what d points to, in the order of KfDev's members
     KfDev d{};
     uint32_t par = 0;
     // host input: two pinned staging buffers and their device copies
-    uint8_t *stage[2] = {nullptr, nullptr};
-    uint8_t *dbuf[2] = {nullptr, nullptr};
-    hipEvent_t copied[2] = {nullptr, nullptr}, counted[2] = {nullptr, nullptr};
+    PgPinned<uint8_t> stage[2];
+    PgDev<uint8_t> dbuf[2];
     int next_buf = 0;
     // odd-list fill: exact counts read back asynchronously, one snapshot per unit
-    unsigned long long *snap = nullptr; // pinned [kSnapRing]
-    hipEvent_t snap_ev[kSnapRing] = {};
+    PgPinned<unsigned long long> snap; // [kSnapRing]
     struct Pending { int slot; uint64_t bound; };
     std::deque<Pending> pending;
     int snap_next = 0;
@@ -347,15 +344,6 @@ struct pg_kfreq {
     std::string err;
 };
 
-static pg_status kf_fail(pg_kfreq *h, pg_status code, const char *fmt, ...) {
-    char buf[1024];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    if (h) h->err = buf; else g_kf_create_error = buf;
-    return code;
-}
-#define KF_TRY(h, expr) \
-    do { hipError_t e_ = (expr); if (e_ != hipSuccess) return kf_fail((h), PG_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
-
 static uint64_t odd_cap_from_env() {
     if (const char *s = getenv("PGKFREQ_ODD_CAP")) { const long long v = atoll(s); if (v >= 1) return (uint64_t)v; }
     return 3 * kUnit; // three units' worth of windows: a unit may be launched while two are still unread (kf_reserve)
@@ -364,14 +352,14 @@ static uint64_t odd_cap_from_env() {
 // Fold the device odd list into the host map and empty it. The count stream must be idle.
 static pg_status kf_drain(pg_kfreq *h) {
     unsigned long long n = 0;
-    KF_TRY(h, hipMemcpy(&n, h->d.odd_n, sizeof n, hipMemcpyDeviceToHost));
-    if (n > h->d.odd_cap) return kf_fail(h, PG_ERR_STATE, "internal: odd-window list overflowed (%llu > %llu)", n, (unsigned long long)h->d.odd_cap);
+    PG_HIP_TRY(h, hipMemcpy(&n, h->d.odd_n, sizeof n, hipMemcpyDeviceToHost));
+    if (n > h->d.odd_cap) return pg_fail(h, PG_ERR_STATE, "internal: odd-window list overflowed (%llu > %llu)", n, (unsigned long long)h->d.odd_cap);
     if (n) {
         h->drain_buf.resize(n);
-        KF_TRY(h, hipMemcpy(h->drain_buf.data(), h->d.odd, n * sizeof(uint4), hipMemcpyDeviceToHost));
+        PG_HIP_TRY(h, hipMemcpy(h->drain_buf.data(), h->d.odd, n * sizeof(uint4), hipMemcpyDeviceToHost));
         for (const uint4 &v : h->drain_buf) { OddKey key{{v.x, v.y, v.z, v.w}}; h->odd_map[key]++; }
-        KF_TRY(h, hipMemsetAsync(h->d.odd_n, 0, sizeof(unsigned long long), h->ks));
-        KF_TRY(h, hipStreamSynchronize(h->ks));
+        PG_HIP_TRY(h, hipMemsetAsync(h->d.odd_n, 0, sizeof(unsigned long long), h->ks));
+        PG_HIP_TRY(h, hipStreamSynchronize(h->ks));
     }
     h->odd_known = 0;
     h->pending.clear();
@@ -383,19 +371,19 @@ static pg_status kf_drain(pg_kfreq *h) {
 // could overflow does the host wait, and only when the exact fill says so does it drain.
 static pg_status kf_reserve(pg_kfreq *h, uint64_t n) {
     while (!h->pending.empty() && hipEventQuery(h->snap_ev[h->pending.front().slot]) == hipSuccess) {
-        h->odd_known = h->snap[h->pending.front().slot];
+        h->odd_known = h->snap.p[h->pending.front().slot];
         h->pending.pop_front();
     }
     uint64_t bound = h->odd_known + n;
     for (const auto &q : h->pending) bound += q.bound;
     if (bound <= h->d.odd_cap && (int)h->pending.size() < kSnapRing - 1) return PG_OK;
     if (!h->pending.empty()) {
-        KF_TRY(h, hipEventSynchronize(h->snap_ev[h->pending.back().slot]));
-        h->odd_known = h->snap[h->pending.back().slot];
+        PG_HIP_TRY(h, hipEventSynchronize(h->snap_ev[h->pending.back().slot]));
+        h->odd_known = h->snap.p[h->pending.back().slot];
         h->pending.clear();
     }
     if (h->odd_known + n > h->d.odd_cap) {
-        KF_TRY(h, hipStreamSynchronize(h->ks));
+        PG_HIP_TRY(h, hipStreamSynchronize(h->ks));
         return kf_drain(h);
     }
     return PG_OK;
@@ -415,21 +403,21 @@ static pg_status kf_unit(pg_kfreq *h, const uint8_t *p, uint64_t n) {
     else if (al) hipLaunchKernelGGL((k_kf_count<true, false>), dim3(n_tiles), dim3(kThreads), 0, h->ks, h->d, p, n, n_tiles, h->k, h->par);
     else if (lds) hipLaunchKernelGGL((k_kf_count<false, true>), dim3(n_tiles), dim3(kThreads), lds_bytes, h->ks, h->d, p, n, n_tiles, h->k, h->par);
     else hipLaunchKernelGGL((k_kf_count<false, false>), dim3(n_tiles), dim3(kThreads), 0, h->ks, h->d, p, n, n_tiles, h->k, h->par);
-    KF_TRY(h, hipGetLastError());
+    PG_HIP_TRY(h, hipGetLastError());
     h->par ^= 1;
     const int slot = h->snap_next; h->snap_next = (h->snap_next + 1) % kSnapRing;
-    KF_TRY(h, hipMemcpyAsync(&h->snap[slot], h->d.odd_n, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->ks));
-    KF_TRY(h, hipEventRecord(h->snap_ev[slot], h->ks));
+    PG_HIP_TRY(h, hipMemcpyAsync(&h->snap.p[slot], h->d.odd_n, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->ks));
+    PG_HIP_TRY(h, hipEventRecord(h->snap_ev[slot], h->ks));
     h->pending.push_back({slot, n});
     return PG_OK;
 }
 
 static pg_status kf_reset_device(pg_kfreq *h) {
-    KF_TRY(h, hipMemsetAsync(h->d.hist, 0, (size_t)h->n_codes * sizeof(unsigned long long), h->ks));
-    KF_TRY(h, hipMemsetAsync(h->d.odd_n, 0, sizeof(unsigned long long), h->ks));
-    KF_TRY(h, hipMemsetAsync(h->d.err, 0, sizeof(uint32_t), h->ks));
-    KF_TRY(h, hipMemsetAsync(h->d.state, 0, 2 * sizeof(KfState), h->ks));
-    KF_TRY(h, hipStreamSynchronize(h->ks));
+    PG_HIP_TRY(h, hipMemsetAsync(h->d.hist, 0, (size_t)h->n_codes * sizeof(unsigned long long), h->ks));
+    PG_HIP_TRY(h, hipMemsetAsync(h->d.odd_n, 0, sizeof(unsigned long long), h->ks));
+    PG_HIP_TRY(h, hipMemsetAsync(h->d.err, 0, sizeof(uint32_t), h->ks));
+    PG_HIP_TRY(h, hipMemsetAsync(h->d.state, 0, 2 * sizeof(KfState), h->ks));
+    PG_HIP_TRY(h, hipStreamSynchronize(h->ks));
     h->par = 0;
     h->pending.clear();
     h->odd_known = 0;
@@ -439,40 +427,34 @@ static pg_status kf_reset_device(pg_kfreq *h) {
 
 extern "C" {
 
-const char *pg_kfreq_last_error(const pg_kfreq *h) { return h ? h->err.c_str() : g_kf_create_error.c_str(); }
+const char *pg_kfreq_last_error(const pg_kfreq *h) { return h ? h->err.c_str() : pg_create_error<pg_kfreq>().c_str(); }
 
 pg_status pg_kfreq_create(uint32_t kmer_size, int32_t device, pg_kfreq **out) {
-    if (!out) return kf_fail(nullptr, PG_ERR_INVALID_ARG, "pg_kfreq_create: null argument");
+    if (!out) return pg_fail<pg_kfreq>(nullptr, PG_ERR_INVALID_ARG, "pg_kfreq_create: null argument");
     *out = nullptr;
-    if (kmer_size < 1 || kmer_size > kMaxK) return kf_fail(nullptr, PG_ERR_INVALID_ARG, "kmer_size must be in [1,%u]", kMaxK);
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) return kf_fail(nullptr, PG_ERR_NO_DEVICE, "no HIP device available (%s); libpgmove has no CPU fallback", e != hipSuccess ? hipGetErrorString(e) : "device count 0");
-    if (device < 0 || device >= ndev) return kf_fail(nullptr, PG_ERR_NO_DEVICE, "device %d out of range (have %d)", device, ndev);
-    e = hipSetDevice(device);
-    if (e != hipSuccess) return kf_fail(nullptr, PG_ERR_NO_DEVICE, "hipSetDevice(%d): %s", device, hipGetErrorString(e));
+    if (kmer_size < 1 || kmer_size > kMaxK) return pg_fail<pg_kfreq>(nullptr, PG_ERR_INVALID_ARG, "kmer_size must be in [1,%u]", kMaxK);
+    if (pg_status st = pg_select_device<pg_kfreq>(device)) return st;
     pg_kfreq *h = new pg_kfreq();
     h->k = kmer_size; h->n_codes = 1u << (2 * kmer_size); h->device = device;
     h->d.odd_cap = odd_cap_from_env();
     h->unit = std::min<uint64_t>(kUnit, h->d.odd_cap);
-    auto bail = [&](pg_status s) { g_kf_create_error = h->err; pg_kfreq_destroy(h); return s; };
-#define KTRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { kf_fail(h, PG_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); return bail(PG_ERR_HIP); } } while (0)
-    KTRY(hipStreamCreateWithFlags(&h->ks, hipStreamNonBlocking));
-    KTRY(hipStreamCreateWithFlags(&h->cs, hipStreamNonBlocking));
-    KTRY(hipMalloc((void **)&h->d.hist, (size_t)h->n_codes * sizeof(unsigned long long)));
-    KTRY(hipMalloc((void **)&h->d.odd, h->d.odd_cap * sizeof(uint4)));
-    KTRY(hipMalloc((void **)&h->d.odd_n, sizeof(unsigned long long)));
-    KTRY(hipMalloc((void **)&h->d.err, sizeof(uint32_t)));
-    KTRY(hipMalloc((void **)&h->d.state, 2 * sizeof(KfState)));
-    KTRY(hipMalloc((void **)&h->d.tile_nl, (kUnit / kTile) * sizeof(uint32_t)));
-    KTRY(hipHostMalloc((void **)&h->snap, kSnapRing * sizeof(unsigned long long), hipHostMallocDefault));
-    for (auto &ev : h->snap_ev) KTRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    for (int i = 0; i < 2; i++) {
-        KTRY(hipEventCreateWithFlags(&h->copied[i], hipEventDisableTiming));
-        KTRY(hipEventCreateWithFlags(&h->counted[i], hipEventDisableTiming));
-    }
-    if (pg_status s = kf_reset_device(h)) return bail(s);
-#undef KTRY
+    auto init = [&]() -> pg_status {
+        PG_HIP_TRY(h, hipStreamCreateWithFlags(&h->ks.h, hipStreamNonBlocking));
+        PG_HIP_TRY(h, hipStreamCreateWithFlags(&h->cs.h, hipStreamNonBlocking));
+        const size_t bytes[6] = {(size_t)h->n_codes * sizeof(unsigned long long), h->d.odd_cap * sizeof(uint4), sizeof(unsigned long long),
+                                 sizeof(uint32_t), 2 * sizeof(KfState), (kUnit / kTile) * sizeof(uint32_t)};
+        for (int i = 0; i < 6; i++) PG_HIP_TRY(h, h->mem[i].ensure(bytes[i]));
+        h->d.hist = h->mem[0].as<unsigned long long>(); h->d.odd = h->mem[1].as<uint4>(); h->d.odd_n = h->mem[2].as<unsigned long long>();
+        h->d.err = h->mem[3].as<uint32_t>(); h->d.state = h->mem[4].as<KfState>(); h->d.tile_nl = h->mem[5].as<uint32_t>();
+        PG_HIP_TRY(h, h->snap.ensure(kSnapRing * sizeof(unsigned long long)));
+        for (auto &ev : h->snap_ev) PG_HIP_TRY(h, hipEventCreateWithFlags(&ev.h, hipEventDisableTiming));
+        for (int i = 0; i < 2; i++) {
+            PG_HIP_TRY(h, hipEventCreateWithFlags(&h->copied[i].h, hipEventDisableTiming));
+            PG_HIP_TRY(h, hipEventCreateWithFlags(&h->counted[i].h, hipEventDisableTiming));
+        }
+        return kf_reset_device(h);
+    };
+    if (pg_status st = init()) return pg_create_failed(h, st, pg_kfreq_destroy);
     *out = h;
     return PG_OK;
 }
@@ -482,88 +464,71 @@ void pg_kfreq_destroy(pg_kfreq *h) {
     (void)hipSetDevice(h->device);
     if (h->ks) (void)hipStreamSynchronize(h->ks);
     if (h->cs) (void)hipStreamSynchronize(h->cs);
-    (void)hipFree(h->d.hist); (void)hipFree(h->d.odd); (void)hipFree(h->d.odd_n); (void)hipFree(h->d.err);
-    (void)hipFree(h->d.state); (void)hipFree(h->d.tile_nl);
-    for (int i = 0; i < 2; i++) {
-        if (h->stage[i]) (void)hipHostFree(h->stage[i]);
-        if (h->dbuf[i]) (void)hipFree(h->dbuf[i]);
-        if (h->copied[i]) (void)hipEventDestroy(h->copied[i]);
-        if (h->counted[i]) (void)hipEventDestroy(h->counted[i]);
-    }
-    for (auto &ev : h->snap_ev) if (ev) (void)hipEventDestroy(ev);
-    if (h->snap) (void)hipHostFree(h->snap);
-    if (h->ks) (void)hipStreamDestroy(h->ks);
-    if (h->cs) (void)hipStreamDestroy(h->cs);
     delete h;
 }
 
 pg_status pg_kfreq_submit(pg_kfreq *h, const void *data, uint64_t n_bytes, int32_t location) {
-    if (!h) return kf_fail(nullptr, PG_ERR_INVALID_ARG, "pg_kfreq_submit: null handle");
+    if (!h) return pg_fail<pg_kfreq>(nullptr, PG_ERR_INVALID_ARG, "pg_kfreq_submit: null handle");
     if (!n_bytes) return PG_OK;
-    if (!data) return kf_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit: null data");
-    KF_TRY(h, hipSetDevice(h->device));
+    if (!data) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit: null data");
+    PG_HIP_TRY(h, hipSetDevice(h->device));
     const uint8_t *src = static_cast<const uint8_t *>(data);
     if (location == PG_LOC_DEVICE) {
-        hipPointerAttribute_t a{};
-        if (hipPointerGetAttributes(&a, data) != hipSuccess || a.type != hipMemoryTypeDevice || a.device != h->device) {
-            (void)hipGetLastError();
-            return kf_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit: PG_LOC_DEVICE data is not device memory of device %d", h->device);
-        }
+        if (pg_ptr_kind(data, h->device) != PG_PTR_DEVICE)
+            return pg_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit: PG_LOC_DEVICE data is not device memory of device %d", h->device);
         for (uint64_t o = 0; o < n_bytes; o += h->unit)
             if (pg_status s = kf_unit(h, src + o, std::min<uint64_t>(h->unit, n_bytes - o))) return s;
         return PG_OK;
     }
-    if (location != PG_LOC_HOST) return kf_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit: location must be PG_LOC_HOST or PG_LOC_DEVICE");
+    if (location != PG_LOC_HOST) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit: location must be PG_LOC_HOST or PG_LOC_DEVICE");
     // page-locked caller memory goes to the device as it is; anything else through the pinned staging buffers
-    hipPointerAttribute_t a{};
-    const bool pinned = hipPointerGetAttributes(&a, data) == hipSuccess && a.type == hipMemoryTypeHost;
-    (void)hipGetLastError();
+    const bool pinned = pg_ptr_kind(data, h->device) == PG_PTR_PINNED;
     for (uint64_t o = 0; o < n_bytes; o += h->unit) {
         const uint64_t m = std::min<uint64_t>(h->unit, n_bytes - o);
         const int b = h->next_buf; h->next_buf ^= 1;
-        if (!h->dbuf[b]) {
-            KF_TRY(h, hipMalloc((void **)&h->dbuf[b], kUnit));
-            KF_TRY(h, hipEventRecord(h->copied[b], h->cs));
-            KF_TRY(h, hipEventRecord(h->counted[b], h->ks));
+        if (!h->dbuf[b].p) {
+            PG_HIP_TRY(h, h->dbuf[b].ensure(kUnit));
+            PG_HIP_TRY(h, hipEventRecord(h->copied[b], h->cs));
+            PG_HIP_TRY(h, hipEventRecord(h->counted[b], h->ks));
         }
         const uint8_t *from = src + o;
         if (!pinned) {
-            if (!h->stage[b]) KF_TRY(h, hipHostMalloc((void **)&h->stage[b], kUnit, hipHostMallocDefault));
-            KF_TRY(h, hipEventSynchronize(h->copied[b])); // the staging buffer's previous copy is done
-            memcpy(h->stage[b], from, m);
-            from = h->stage[b];
+            PG_HIP_TRY(h, h->stage[b].ensure(kUnit));
+            PG_HIP_TRY(h, hipEventSynchronize(h->copied[b])); // the staging buffer's previous copy is done
+            memcpy(h->stage[b].p, from, m);
+            from = h->stage[b].p;
         }
-        KF_TRY(h, hipStreamWaitEvent(h->cs, h->counted[b], 0)); // the device buffer's previous unit is counted
-        KF_TRY(h, hipMemcpyAsync(h->dbuf[b], from, m, hipMemcpyHostToDevice, h->cs));
-        KF_TRY(h, hipEventRecord(h->copied[b], h->cs));
-        KF_TRY(h, hipStreamWaitEvent(h->ks, h->copied[b], 0));
-        if (pg_status s = kf_unit(h, h->dbuf[b], m)) return s;
-        KF_TRY(h, hipEventRecord(h->counted[b], h->ks));
+        PG_HIP_TRY(h, hipStreamWaitEvent(h->cs, h->counted[b], 0)); // the device buffer's previous unit is counted
+        PG_HIP_TRY(h, hipMemcpyAsync(h->dbuf[b].p, from, m, hipMemcpyHostToDevice, h->cs));
+        PG_HIP_TRY(h, hipEventRecord(h->copied[b], h->cs));
+        PG_HIP_TRY(h, hipStreamWaitEvent(h->ks, h->copied[b], 0));
+        if (pg_status s = kf_unit(h, h->dbuf[b].p, m)) return s;
+        PG_HIP_TRY(h, hipEventRecord(h->counted[b], h->ks));
     }
     // the caller may reuse its (page-locked) buffer once submit returns
-    if (pinned) KF_TRY(h, hipStreamSynchronize(h->cs));
+    if (pinned) PG_HIP_TRY(h, hipStreamSynchronize(h->cs));
     return PG_OK;
 }
 
 pg_status pg_kfreq_sync(pg_kfreq *h) {
-    if (!h) return kf_fail(nullptr, PG_ERR_INVALID_ARG, "pg_kfreq_sync: null handle");
-    KF_TRY(h, hipSetDevice(h->device));
-    KF_TRY(h, hipStreamSynchronize(h->cs));
-    KF_TRY(h, hipStreamSynchronize(h->ks));
+    if (!h) return pg_fail<pg_kfreq>(nullptr, PG_ERR_INVALID_ARG, "pg_kfreq_sync: null handle");
+    PG_HIP_TRY(h, hipSetDevice(h->device));
+    PG_HIP_TRY(h, hipStreamSynchronize(h->cs));
+    PG_HIP_TRY(h, hipStreamSynchronize(h->ks));
     return PG_OK;
 }
 
 pg_status pg_kfreq_finish(pg_kfreq *h, uint64_t *counts_out, pg_kfreq_result *out) {
-    if (!h) return kf_fail(nullptr, PG_ERR_INVALID_ARG, "pg_kfreq_finish: null handle");
-    if (!counts_out || !out) return kf_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_finish: null argument");
+    if (!h) return pg_fail<pg_kfreq>(nullptr, PG_ERR_INVALID_ARG, "pg_kfreq_finish: null handle");
+    if (!counts_out || !out) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_finish: null argument");
     memset(out, 0, sizeof *out);
     if (pg_status s = pg_kfreq_sync(h)) return s;
     uint32_t bad = 0;
-    KF_TRY(h, hipMemcpy(&bad, h->d.err, sizeof bad, hipMemcpyDeviceToHost));
+    PG_HIP_TRY(h, hipMemcpy(&bad, h->d.err, sizeof bad, hipMemcpyDeviceToHost));
     pg_status st = PG_OK;
-    if (bad) st = kf_fail(h, PG_ERR_INPUT, "a sequence line holds a NUL byte (the reference truncates the line there: undefined counts)");
+    if (bad) st = pg_fail(h, PG_ERR_INPUT, "a sequence line holds a NUL byte (the reference truncates the line there: undefined counts)");
     else if ((st = kf_drain(h)) == PG_OK) {
-        KF_TRY(h, hipMemcpy(counts_out, h->d.hist, (size_t)h->n_codes * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        PG_HIP_TRY(h, hipMemcpy(counts_out, h->d.hist, (size_t)h->n_codes * sizeof(uint64_t), hipMemcpyDeviceToHost));
         std::vector<std::pair<OddKey, uint64_t>> v(h->odd_map.begin(), h->odd_map.end());
         const uint32_t k = h->k;
         std::sort(v.begin(), v.end(), [k](const auto &a, const auto &b) { return memcmp(a.first.w, b.first.w, k) < 0; });

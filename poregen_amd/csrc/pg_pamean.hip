@@ -12,11 +12,10 @@
 #include "../../include/pgmove.h"
 #include <hip/hip_runtime.h>
 #include "pg_pamean.h"
+#include "pg_hip_host.h"
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -122,25 +121,6 @@ __global__ __launch_bounds__(kThreads) void k_pa_final(const uint64_t *__restric
     out[r] = o;
 }
 
-thread_local std::string g_pa_create_error;
-
-template <typename T>
-hipError_t grow_dev(T *&p, size_t &cap, size_t want) {
-    if (want <= cap) return hipSuccess;
-    if (p) { hipError_t e = hipFree(p); if (e != hipSuccess) return e; p = nullptr; cap = 0; }
-    hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
-    if (e == hipSuccess) cap = want;
-    return e;
-}
-template <typename T>
-hipError_t grow_pinned(T *&p, size_t &cap, size_t want) {
-    if (want <= cap) return hipSuccess;
-    if (p) { hipError_t e = hipHostFree(p); if (e != hipSuccess) return e; p = nullptr; cap = 0; }
-    hipError_t e = hipHostMalloc((void **)&p, want * sizeof(T), hipHostMallocDefault);
-    if (e == hipSuccess) cap = want;
-    return e;
-}
-
 // Neumaier's compensated sum, in the order given
 struct CompSum {
     long double s = 0, c = 0;
@@ -174,17 +154,17 @@ struct Summary {
 
 struct pg_pamean {
     int device = 0;
-    hipStream_t s = nullptr;
-    hipEvent_t done = nullptr;
-    // device copies of a host batch, and the per-read work arrays
-    int16_t *d_sig = nullptr; size_t cap_sig = 0;
-    uint64_t *d_off = nullptr; size_t cap_off = 0;
-    double *d_par = nullptr; size_t cap_par = 0;   // digitisation, offset, range: 3 * n_reads
-    uint2 *d_extra = nullptr; size_t cap_extra = 0;
-    PaAcc *d_acc = nullptr; size_t cap_acc = 0;
-    PaOut *d_out = nullptr; size_t cap_out = 0;
-    int16_t *h_stage = nullptr; size_t cap_stage = 0; // pinned staging of a pageable host signal
-    PaOut *h_out = nullptr; size_t cap_hout = 0;       // pinned
+    PgStream s;
+    PgEvent done;
+    // device copies of a host batch, and the per-read work arrays (grown to the exact size of the largest batch so far)
+    PgDev<int16_t> d_sig;
+    PgDev<uint64_t> d_off;
+    PgDev<double> d_par;   // digitisation, offset, range: 3 * n_reads
+    PgDev<uint2> d_extra;
+    PgDev<PaAcc> d_acc;
+    PgDev<PaOut> d_out;
+    PgPinned<int16_t> h_stage; // staging of a pageable host signal
+    PgPinned<PaOut> h_out;
     std::vector<uint64_t> h_sig_off;                 // the batch's offsets on the host
     std::vector<uint2> h_extra;
     // the batch in flight
@@ -197,38 +177,16 @@ struct pg_pamean {
     std::string err;
 };
 
-static pg_status pa_fail(pg_pamean *h, pg_status code, const char *fmt, ...) {
-    char buf[1024];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    if (h) h->err = buf; else g_pa_create_error = buf;
-    return code;
-}
-#define PA_TRY(h, expr) \
-    do { hipError_t e_ = (expr); if (e_ != hipSuccess) return pa_fail((h), PG_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
-
-static bool is_device_mem(const void *p, int device) {
-    hipPointerAttribute_t a{};
-    const bool ok = p && hipPointerGetAttributes(&a, p) == hipSuccess && a.type == hipMemoryTypeDevice && a.device == device;
-    (void)hipGetLastError();
-    return ok;
-}
-static bool is_pinned(const void *p) {
-    hipPointerAttribute_t a{};
-    const bool ok = p && hipPointerGetAttributes(&a, p) == hipSuccess && a.type == hipMemoryTypeHost;
-    (void)hipGetLastError();
-    return ok;
-}
-
 // wait for the batch in flight, finish the reads the device did not settle, fold every read into the summary
 static pg_status pa_complete(pg_pamean *h) {
     if (!h->pending) return PG_OK;
     h->pending = false;
-    PA_TRY(h, hipEventSynchronize(h->done));
+    PG_HIP_TRY(h, hipEventSynchronize(h->done));
     const pg_pamean_batch &b = h->b;
     const uint64_t n_reads = b.n_reads;
     std::vector<int16_t> tmp;
     for (uint64_t r = 0; r < n_reads; r++) {
-        const PaOut &o = h->h_out[r];
+        const PaOut &o = h->h_out.p[r];
         double mean = o.mean;
         if (o.n == 0) { if (h->means_out) h->means_out[r] = __builtin_nan(""); continue; }
         if (std::isnan(mean)) { // not settled on the device: the reference's loop on the read's samples
@@ -240,10 +198,10 @@ static pg_status pa_complete(pg_pamean *h) {
             } else {
                 tmp.resize(o.n);
                 double par[3];
-                PA_TRY(h, hipMemcpy(tmp.data(), b.sig + first, o.n * sizeof(int16_t), hipMemcpyDeviceToHost));
-                PA_TRY(h, hipMemcpy(&par[0], b.digitisation + r, sizeof(double), hipMemcpyDeviceToHost));
-                PA_TRY(h, hipMemcpy(&par[1], b.offset + r, sizeof(double), hipMemcpyDeviceToHost));
-                PA_TRY(h, hipMemcpy(&par[2], b.range + r, sizeof(double), hipMemcpyDeviceToHost));
+                PG_HIP_TRY(h, hipMemcpy(tmp.data(), b.sig + first, o.n * sizeof(int16_t), hipMemcpyDeviceToHost));
+                PG_HIP_TRY(h, hipMemcpy(&par[0], b.digitisation + r, sizeof(double), hipMemcpyDeviceToHost));
+                PG_HIP_TRY(h, hipMemcpy(&par[1], b.offset + r, sizeof(double), hipMemcpyDeviceToHost));
+                PG_HIP_TRY(h, hipMemcpy(&par[2], b.range + r, sizeof(double), hipMemcpyDeviceToHost));
                 raw = tmp.data(); dig = par[0]; off = par[1]; range = par[2];
             }
             mean = pg_pa_sequential_mean(raw, o.n, dig, off, range);
@@ -262,25 +220,19 @@ static pg_status pa_complete(pg_pamean *h) {
 
 extern "C" {
 
-const char *pg_pamean_last_error(const pg_pamean *h) { return h ? h->err.c_str() : g_pa_create_error.c_str(); }
+const char *pg_pamean_last_error(const pg_pamean *h) { return h ? h->err.c_str() : pg_create_error<pg_pamean>().c_str(); }
 
 pg_status pg_pamean_create(int32_t device, pg_pamean **out) {
-    if (!out) return pa_fail(nullptr, PG_ERR_INVALID_ARG, "pg_pamean_create: null argument");
+    if (!out) return pg_fail<pg_pamean>(nullptr, PG_ERR_INVALID_ARG, "pg_pamean_create: null argument");
     *out = nullptr;
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) return pa_fail(nullptr, PG_ERR_NO_DEVICE, "no HIP device available (%s); libpgmove has no CPU fallback", e != hipSuccess ? hipGetErrorString(e) : "device count 0");
-    if (device < 0 || device >= ndev) return pa_fail(nullptr, PG_ERR_NO_DEVICE, "device %d out of range (have %d)", device, ndev);
-    e = hipSetDevice(device);
-    if (e != hipSuccess) return pa_fail(nullptr, PG_ERR_NO_DEVICE, "hipSetDevice(%d): %s", device, hipGetErrorString(e));
+    if (pg_status st = pg_select_device<pg_pamean>(device)) return st;
     pg_pamean *h = new pg_pamean();
     h->device = device;
-    e = hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->done, hipEventDisableTiming);
+    hipError_t e = hipStreamCreateWithFlags(&h->s.h, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->done.h, hipEventDisableTiming);
     if (e != hipSuccess) {
-        pa_fail(nullptr, PG_ERR_HIP, "pg_pamean_create: %s", hipGetErrorString(e));
-        pg_pamean_destroy(h);
-        return PG_ERR_HIP;
+        pg_fail(h, PG_ERR_HIP, "pg_pamean_create: %s", hipGetErrorString(e));
+        return pg_create_failed(h, PG_ERR_HIP, pg_pamean_destroy);
     }
     *out = h;
     return PG_OK;
@@ -290,91 +242,85 @@ void pg_pamean_destroy(pg_pamean *h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->s) (void)hipStreamSynchronize(h->s);
-    (void)hipFree(h->d_sig); (void)hipFree(h->d_off); (void)hipFree(h->d_par); (void)hipFree(h->d_extra);
-    (void)hipFree(h->d_acc); (void)hipFree(h->d_out);
-    if (h->h_stage) (void)hipHostFree(h->h_stage);
-    if (h->h_out) (void)hipHostFree(h->h_out);
-    if (h->done) (void)hipEventDestroy(h->done);
-    if (h->s) (void)hipStreamDestroy(h->s);
     delete h;
 }
 
 pg_status pg_pamean_submit(pg_pamean *h, const pg_pamean_batch *b, double *means_out) {
-    if (!h) return pa_fail(nullptr, PG_ERR_INVALID_ARG, "pg_pamean_submit: null handle");
-    if (!b) return pa_fail(h, PG_ERR_INVALID_ARG, "pg_pamean_submit: null batch");
-    PA_TRY(h, hipSetDevice(h->device));
+    if (!h) return pg_fail<pg_pamean>(nullptr, PG_ERR_INVALID_ARG, "pg_pamean_submit: null handle");
+    if (!b) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_pamean_submit: null batch");
+    PG_HIP_TRY(h, hipSetDevice(h->device));
     if (pg_status s = pa_complete(h)) return s;
     const uint64_t n_reads = b->n_reads;
     if (!n_reads) return PG_OK;
-    if (n_reads >= (1ull << 31)) return pa_fail(h, PG_ERR_INVALID_ARG, "pg_pamean_submit: %llu reads in one batch (at most 2^31 - 1)", (unsigned long long)n_reads);
-    if (!b->sig_off || !b->digitisation || !b->offset || !b->range) return pa_fail(h, PG_ERR_INVALID_ARG, "pg_pamean_submit: null array");
-    if (b->location != PG_LOC_HOST && b->location != PG_LOC_DEVICE) return pa_fail(h, PG_ERR_INVALID_ARG, "pg_pamean_submit: location must be PG_LOC_HOST or PG_LOC_DEVICE");
+    if (n_reads >= (1ull << 31)) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_pamean_submit: %llu reads in one batch (at most 2^31 - 1)", (unsigned long long)n_reads);
+    if (!b->sig_off || !b->digitisation || !b->offset || !b->range) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_pamean_submit: null array");
+    if (b->location != PG_LOC_HOST && b->location != PG_LOC_DEVICE) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_pamean_submit: location must be PG_LOC_HOST or PG_LOC_DEVICE");
     const bool dev = b->location == PG_LOC_DEVICE;
     if (dev) {
         const void *arrs[5] = {b->sig, b->sig_off, b->digitisation, b->offset, b->range};
         for (int i = 0; i < 5; i++)
-            if ((i > 0 || b->sig) && !is_device_mem(arrs[i], h->device))
-                return pa_fail(h, PG_ERR_INVALID_ARG, "pg_pamean_submit: PG_LOC_DEVICE arrays must be device memory of device %d", h->device);
+            if ((i > 0 || b->sig) && pg_ptr_kind(arrs[i], h->device) != PG_PTR_DEVICE)
+                return pg_fail(h, PG_ERR_INVALID_ARG, "pg_pamean_submit: PG_LOC_DEVICE arrays must be device memory of device %d", h->device);
     }
     // the offsets on the host: they plan the pieces of long reads, and they locate the reads the host finishes
     h->h_sig_off.resize(n_reads + 1);
-    if (dev) PA_TRY(h, hipMemcpy(h->h_sig_off.data(), b->sig_off, (n_reads + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (dev) PG_HIP_TRY(h, hipMemcpy(h->h_sig_off.data(), b->sig_off, (n_reads + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
     else memcpy(h->h_sig_off.data(), b->sig_off, (n_reads + 1) * sizeof(uint64_t));
     const uint64_t *so = h->h_sig_off.data();
     h->h_extra.clear();
     for (uint64_t r = 0; r < n_reads; r++) {
-        if (so[r + 1] < so[r]) return pa_fail(h, PG_ERR_INPUT, "pg_pamean_submit: sig_off decreases at read %llu", (unsigned long long)r);
+        if (so[r + 1] < so[r]) return pg_fail(h, PG_ERR_INPUT, "pg_pamean_submit: sig_off decreases at read %llu", (unsigned long long)r);
         const uint64_t n = so[r + 1] - so[r];
-        if (n >= kMaxReadLen) return pa_fail(h, PG_ERR_INPUT, "pg_pamean_submit: read %llu has %llu samples (at most 2^33 - 1)", (unsigned long long)r, (unsigned long long)n);
+        if (n >= kMaxReadLen) return pg_fail(h, PG_ERR_INPUT, "pg_pamean_submit: read %llu has %llu samples (at most 2^33 - 1)", (unsigned long long)r, (unsigned long long)n);
         for (uint64_t p = 1; p * kPiece < n; p++) h->h_extra.push_back(make_uint2((uint32_t)r, (uint32_t)p));
     }
     const uint64_t total = so[n_reads];
-    if (total && !b->sig) return pa_fail(h, PG_ERR_INVALID_ARG, "pg_pamean_submit: null sig");
-    if (n_reads + h->h_extra.size() > 0x7fffffffull) return pa_fail(h, PG_ERR_INVALID_ARG, "pg_pamean_submit: batch too large");
+    if (total && !b->sig) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_pamean_submit: null sig");
+    if (n_reads + h->h_extra.size() > 0x7fffffffull) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_pamean_submit: batch too large");
     const int16_t *dsig;
     const uint64_t *doff;
     const double *ddig, *doffs, *drange;
     if (dev) {
         dsig = b->sig; doff = b->sig_off; ddig = b->digitisation; doffs = b->offset; drange = b->range;
     } else {
-        PA_TRY(h, grow_dev(h->d_sig, h->cap_sig, std::max<uint64_t>(total, 1)));
-        PA_TRY(h, grow_dev(h->d_off, h->cap_off, n_reads + 1));
-        PA_TRY(h, grow_dev(h->d_par, h->cap_par, 3 * n_reads));
+        PG_HIP_TRY(h, h->d_sig.ensure(std::max<uint64_t>(total, 1) * sizeof(int16_t)));
+        PG_HIP_TRY(h, h->d_off.ensure((n_reads + 1) * sizeof(uint64_t)));
+        PG_HIP_TRY(h, h->d_par.ensure(3 * n_reads * sizeof(double)));
         if (total) {
             const int16_t *from = b->sig;
-            if (!is_pinned(b->sig)) { // through pinned memory: one copy on the host, one DMA
-                PA_TRY(h, grow_pinned(h->h_stage, h->cap_stage, total));
-                memcpy(h->h_stage, b->sig, total * sizeof(int16_t));
-                from = h->h_stage;
+            if (pg_ptr_kind(b->sig, h->device) != PG_PTR_PINNED) { // through pinned memory: one copy on the host, one DMA
+                PG_HIP_TRY(h, h->h_stage.ensure(total * sizeof(int16_t)));
+                memcpy(h->h_stage.p, b->sig, total * sizeof(int16_t));
+                from = h->h_stage.p;
             }
-            PA_TRY(h, hipMemcpyAsync(h->d_sig, from, total * sizeof(int16_t), hipMemcpyHostToDevice, h->s));
+            PG_HIP_TRY(h, hipMemcpyAsync(h->d_sig.p, from, total * sizeof(int16_t), hipMemcpyHostToDevice, h->s));
         }
-        PA_TRY(h, hipMemcpyAsync(h->d_off, so, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, h->s));
-        PA_TRY(h, hipMemcpyAsync(h->d_par, b->digitisation, n_reads * sizeof(double), hipMemcpyHostToDevice, h->s));
-        PA_TRY(h, hipMemcpyAsync(h->d_par + n_reads, b->offset, n_reads * sizeof(double), hipMemcpyHostToDevice, h->s));
-        PA_TRY(h, hipMemcpyAsync(h->d_par + 2 * n_reads, b->range, n_reads * sizeof(double), hipMemcpyHostToDevice, h->s));
-        dsig = h->d_sig; doff = h->d_off; ddig = h->d_par; doffs = h->d_par + n_reads; drange = h->d_par + 2 * n_reads;
+        PG_HIP_TRY(h, hipMemcpyAsync(h->d_off.p, so, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, h->s));
+        PG_HIP_TRY(h, hipMemcpyAsync(h->d_par.p, b->digitisation, n_reads * sizeof(double), hipMemcpyHostToDevice, h->s));
+        PG_HIP_TRY(h, hipMemcpyAsync(h->d_par.p + n_reads, b->offset, n_reads * sizeof(double), hipMemcpyHostToDevice, h->s));
+        PG_HIP_TRY(h, hipMemcpyAsync(h->d_par.p + 2 * n_reads, b->range, n_reads * sizeof(double), hipMemcpyHostToDevice, h->s));
+        dsig = h->d_sig.p; doff = h->d_off.p; ddig = h->d_par.p; doffs = h->d_par.p + n_reads; drange = h->d_par.p + 2 * n_reads;
     }
     const size_t n_extra = h->h_extra.size();
     if (n_extra) {
-        PA_TRY(h, grow_dev(h->d_extra, h->cap_extra, n_extra));
-        PA_TRY(h, hipMemcpyAsync(h->d_extra, h->h_extra.data(), n_extra * sizeof(uint2), hipMemcpyHostToDevice, h->s));
+        PG_HIP_TRY(h, h->d_extra.ensure(n_extra * sizeof(uint2)));
+        PG_HIP_TRY(h, hipMemcpyAsync(h->d_extra.p, h->h_extra.data(), n_extra * sizeof(uint2), hipMemcpyHostToDevice, h->s));
     }
-    PA_TRY(h, grow_dev(h->d_acc, h->cap_acc, n_reads));
-    PA_TRY(h, grow_dev(h->d_out, h->cap_out, n_reads));
-    PA_TRY(h, grow_pinned(h->h_out, h->cap_hout, n_reads));
-    PA_TRY(h, hipMemsetAsync(h->d_acc, 0, n_reads * sizeof(PaAcc), h->s));
+    PG_HIP_TRY(h, h->d_acc.ensure(n_reads * sizeof(PaAcc)));
+    PG_HIP_TRY(h, h->d_out.ensure(n_reads * sizeof(PaOut)));
+    PG_HIP_TRY(h, h->h_out.ensure(n_reads * sizeof(PaOut)));
+    PG_HIP_TRY(h, hipMemsetAsync(h->d_acc.p, 0, n_reads * sizeof(PaAcc), h->s));
     const uint32_t grid = (uint32_t)(n_reads + n_extra);
     if (((uintptr_t)dsig & 15) == 0)
-        hipLaunchKernelGGL(k_pa_sums<true>, dim3(grid), dim3(kWave), 0, h->s, dsig, doff, doffs, h->d_extra, (uint32_t)n_reads, h->d_acc);
+        hipLaunchKernelGGL(k_pa_sums<true>, dim3(grid), dim3(kWave), 0, h->s, dsig, doff, doffs, h->d_extra.p, (uint32_t)n_reads, h->d_acc.p);
     else
-        hipLaunchKernelGGL(k_pa_sums<false>, dim3(grid), dim3(kWave), 0, h->s, dsig, doff, doffs, h->d_extra, (uint32_t)n_reads, h->d_acc);
-    PA_TRY(h, hipGetLastError());
+        hipLaunchKernelGGL(k_pa_sums<false>, dim3(grid), dim3(kWave), 0, h->s, dsig, doff, doffs, h->d_extra.p, (uint32_t)n_reads, h->d_acc.p);
+    PG_HIP_TRY(h, hipGetLastError());
     hipLaunchKernelGGL(k_pa_final, dim3((uint32_t)((n_reads + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->s, doff, ddig, doffs, drange,
-                       h->d_acc, (uint32_t)n_reads, h->d_out);
-    PA_TRY(h, hipGetLastError());
-    PA_TRY(h, hipMemcpyAsync(h->h_out, h->d_out, n_reads * sizeof(PaOut), hipMemcpyDeviceToHost, h->s));
-    PA_TRY(h, hipEventRecord(h->done, h->s));
+                       h->d_acc.p, (uint32_t)n_reads, h->d_out.p);
+    PG_HIP_TRY(h, hipGetLastError());
+    PG_HIP_TRY(h, hipMemcpyAsync(h->h_out.p, h->d_out.p, n_reads * sizeof(PaOut), hipMemcpyDeviceToHost, h->s));
+    PG_HIP_TRY(h, hipEventRecord(h->done, h->s));
     h->b = *b;
     h->means_out = means_out;
     h->pending = true;
@@ -382,14 +328,14 @@ pg_status pg_pamean_submit(pg_pamean *h, const pg_pamean_batch *b, double *means
 }
 
 pg_status pg_pamean_sync(pg_pamean *h) {
-    if (!h) return pa_fail(nullptr, PG_ERR_INVALID_ARG, "pg_pamean_sync: null handle");
-    PA_TRY(h, hipSetDevice(h->device));
+    if (!h) return pg_fail<pg_pamean>(nullptr, PG_ERR_INVALID_ARG, "pg_pamean_sync: null handle");
+    PG_HIP_TRY(h, hipSetDevice(h->device));
     return pa_complete(h);
 }
 
 pg_status pg_pamean_finish(pg_pamean *h, pg_pamean_result *out) {
-    if (!h) return pa_fail(nullptr, PG_ERR_INVALID_ARG, "pg_pamean_finish: null handle");
-    if (!out) return pa_fail(h, PG_ERR_INVALID_ARG, "pg_pamean_finish: null argument");
+    if (!h) return pg_fail<pg_pamean>(nullptr, PG_ERR_INVALID_ARG, "pg_pamean_finish: null handle");
+    if (!out) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_pamean_finish: null argument");
     memset(out, 0, sizeof *out);
     pg_status st = pg_pamean_sync(h);
     if (st == PG_OK) {

@@ -54,10 +54,14 @@ def _has_gpu():
 
 @pytest.mark.skipif(_has_gpu(), reason="only meaningful on a box without a GPU")
 def test_no_device_fails_loudly():
-    from poregen_amd.engine import GmoveEngine, GmoveParams, PgError, generate_kmers
-    with pytest.raises(PgError) as ei:
-        GmoveEngine(GmoveParams(kmers=generate_kmers(3), kmer_size=3))
-    assert ei.value.status == _abi.PG_ERR_NO_DEVICE and "no CPU fallback" in ei.value.text
+    from poregen_amd import engine
+    from poregen_amd.engine import GmoveParams, PgError, generate_kmers
+    creates = {"GmoveEngine": lambda: engine.GmoveEngine(GmoveParams(kmers=generate_kmers(3), kmer_size=3)),
+               "KmerCounter": lambda: engine.KmerCounter(3), "AlignmentScorer": engine.AlignmentScorer, "SignalMeans": engine.SignalMeans}
+    for name, create in creates.items():  # the four creates share one device selection (pg_hip_host.h)
+        with pytest.raises(PgError) as ei:
+            create()
+        assert ei.value.status == _abi.PG_ERR_NO_DEVICE and "no CPU fallback" in ei.value.text, name
 
 
 def test_create_validates_arguments():
