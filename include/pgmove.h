@@ -61,6 +61,13 @@
  *                                  printing, :157-231, stay with the caller)
  * pg_fscore_finish                 the TOT_* sums (per pair on request)            src/f1_score/f1score.py:224-229
  * pg_fscore_sync / _last_error     (no counterpart)
+ *
+ * The k-mer model from dump directories (STEP 6 of scripts/poregen.sh as a tool of its own) has one as well:
+ * pg_dmodel_create / _destroy      (no counterpart)
+ * pg_dmodel_submit                 tr ';,' '\n' < file | tail -n +2 and awk -F';' of a batch of dump files: the text parsed on the
+ *                                  device                                          scripts/poregen.sh:66-67, 43
+ * pg_dmodel_finish / _format       datamash median / sstdev per file               scripts/poregen.sh:66-67, 43
+ * pg_dmodel_sync / _last_error     (no counterpart)
  */
 #ifndef PGMOVE_H
 #define PGMOVE_H
@@ -553,6 +560,45 @@ pg_status pg_pamean_submit(pg_pamean *h, const pg_pamean_batch *batch, double *m
 pg_status pg_pamean_sync(pg_pamean *h);
 /* The dataset summary of every read since the last finish; the handle is reset afterwards, also after an error. */
 pg_status pg_pamean_finish(pg_pamean *h, pg_pamean_result *out);
+
+/* ---- model: the k-mer model from the TEXT of dump files, parsed and reduced on the device ---------------------------------------------
+ * What scripts/poregen.sh:54-85 (tr ';,' '\n' | tail -n +2 | datamash median 1 / sstdev 1) and :33-52 (awk comma counts | datamash
+ * median) compute per dump file, for files that already exist: written by the reference, by an earlier run, with -d, or several
+ * directories' files of one name back to back. A submission holds n_files files: file i is bytes [file_off[i], file_off[i + 1]).
+ * The device parses the files of the strict grammar  (-?D+.DDDDDDDD[,;])*  -- exactly eight decimals, |value| < 4e7, the last byte
+ * a ';': every file gmove writes without -d -- into integers of 1e-8 units and reduces them with pg_model's kernels: the same exact
+ * median and moments, without a double in between. Every other file (':' of -d, a newline, "1e2", "+1.5", blanks, "inf", another
+ * number of decimals, an unclosed last event, ...) and every file the reduction declines (more than 2^23 values, values further than
+ * 2^40 units from the first, a negative zero that may be the median) is finished on the host by the pipeline's rules restated
+ * (strtold into long double, datamash's median and sstdev); pg_dmodel_info counts them. No valid input is refused.
+ * Results: pg_model_result over all files since the last finish, in submission order. For a file the host finished, the exact fields
+ * (mid_lo, mid_hi, origin, sum1, sum2_*) are 0 and median / sstdev are the long doubles rounded; its texts come from pg_dmodel_format,
+ * which is pg_model_format for every other file. The --stdv_limit cap stays with the caller. No CPU fallback for the whole:
+ * PG_ERR_NO_DEVICE without a GPU. */
+typedef struct pg_dmodel pg_dmodel;
+enum { PG_DMODEL_PROFILE = 1u << 8 }; /* pg_dmodel_create flags (beside PG_MODEL_KEEP_FIRST): time the kernels with HIP events */
+typedef struct {
+    uint64_t n_files;
+    uint64_t n_bytes;
+    uint64_t n_values;            /* values the device parsed (before tail -n +2) */
+    uint64_t n_host_files;        /* files finished on the host */
+    const uint32_t *host_files;   /* [n_host_files] their indices, ascending; owned by the handle until the next finish / destroy */
+    uint32_t n_batches, reserved;
+    double parse_ms, model_ms;    /* PG_DMODEL_PROFILE: device time of the parse kernels and of the reduction, else 0 */
+} pg_dmodel_info;
+pg_status pg_dmodel_create(int32_t device, uint32_t flags, pg_dmodel **out);
+void      pg_dmodel_destroy(pg_dmodel *h);
+const char *pg_dmodel_last_error(const pg_dmodel *h); /* h may be NULL: error of the last failed pg_dmodel_create */
+/* file_off: host uint64[n_files + 1], non-decreasing, file_off[0] = 0; bytes: file_off[n_files] bytes, at most 2^31, n_files at most 2^24
+ * per call. PG_LOC_HOST: any host memory, free for reuse when the call returns. PG_LOC_DEVICE: memory of the handle's device, complete
+ * before the call, read in place and unchanged until pg_dmodel_sync or pg_dmodel_finish. The call queues the batch and settles the one
+ * before it (download, host-finished files), so that a caller reads its next files while this batch is on the device. */
+pg_status pg_dmodel_submit(pg_dmodel *h, const void *bytes, const uint64_t *file_off, uint32_t n_files, int32_t location);
+pg_status pg_dmodel_sync(pg_dmodel *h);
+/* Every file since the last finish. out and info (may be NULL) are owned by the handle until the next submit / finish / destroy. */
+pg_status pg_dmodel_finish(pg_dmodel *h, pg_model_result *out, pg_dmodel_info *info);
+/* pg_model_format for the handle's last finish (which = PG_MODEL_TEXT_*), with the host-finished files' texts as datamash prints them */
+size_t    pg_dmodel_format(const pg_dmodel *h, uint32_t file, int32_t which, char *buf, size_t cap);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,7 @@ PG_FLAG_DEBUG_SPLIT_WALK = 256
 PG_FLAG_OVERLAP_TAIL = 512
 PG_FLAG_ONE_STREAM = 1024
 PG_MODEL_KEEP_FIRST = 1
+PG_DMODEL_PROFILE = 256
 PG_MODEL_TEXT_MEDIAN, PG_MODEL_TEXT_SSTDEV, PG_MODEL_TEXT_DWELL = 0, 1, 2
 
 # every symbol include/pgmove.h declares (checked by tests/test_abi.py)
@@ -40,6 +41,7 @@ EXPORTS = [
     "pg_kfreq_create", "pg_kfreq_destroy", "pg_kfreq_last_error", "pg_kfreq_submit", "pg_kfreq_sync", "pg_kfreq_finish",
     "pg_fscore_create", "pg_fscore_destroy", "pg_fscore_last_error", "pg_fscore_submit", "pg_fscore_sync", "pg_fscore_finish",
     "pg_pamean_create", "pg_pamean_destroy", "pg_pamean_last_error", "pg_pamean_submit", "pg_pamean_sync", "pg_pamean_finish",
+    "pg_dmodel_create", "pg_dmodel_destroy", "pg_dmodel_last_error", "pg_dmodel_submit", "pg_dmodel_sync", "pg_dmodel_finish", "pg_dmodel_format",
 ]
 PG_JOB_EXCHANGE_AUTO, PG_JOB_EXCHANGE_HOST, PG_JOB_EXCHANGE_RCCL = 0, 1, 2
 
@@ -124,6 +126,12 @@ class PgPameanBatch(C.Structure):
 
 class PgPameanResult(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_fallback", C.c_uint64), ("n_samples", C.c_uint64), ("mean", C.c_double), ("sstdev", C.c_double)]
+
+
+class PgDmodelInfo(C.Structure):
+    _fields_ = [("n_files", C.c_uint64), ("n_bytes", C.c_uint64), ("n_values", C.c_uint64), ("n_host_files", C.c_uint64),
+                ("host_files", C.POINTER(C.c_uint32)), ("n_batches", C.c_uint32), ("reserved", C.c_uint32),
+                ("parse_ms", C.c_double), ("model_ms", C.c_double)]
 
 
 class PgKernelStat(C.Structure):
@@ -236,5 +244,12 @@ def load():
     lib.pg_pamean_submit.argtypes = [vp, C.POINTER(PgPameanBatch), vp]; lib.pg_pamean_submit.restype = i32
     lib.pg_pamean_sync.argtypes = [vp]; lib.pg_pamean_sync.restype = i32
     lib.pg_pamean_finish.argtypes = [vp, C.POINTER(PgPameanResult)]; lib.pg_pamean_finish.restype = i32
+    lib.pg_dmodel_create.argtypes = [i32, u32, C.POINTER(vp)]; lib.pg_dmodel_create.restype = i32
+    lib.pg_dmodel_destroy.argtypes = [vp]; lib.pg_dmodel_destroy.restype = None
+    lib.pg_dmodel_last_error.argtypes = [vp]; lib.pg_dmodel_last_error.restype = C.c_char_p
+    lib.pg_dmodel_submit.argtypes = [vp, vp, vp, u32, i32]; lib.pg_dmodel_submit.restype = i32
+    lib.pg_dmodel_sync.argtypes = [vp]; lib.pg_dmodel_sync.restype = i32
+    lib.pg_dmodel_finish.argtypes = [vp, C.POINTER(PgModelResult), C.POINTER(PgDmodelInfo)]; lib.pg_dmodel_finish.restype = i32
+    lib.pg_dmodel_format.argtypes = [vp, u32, i32, C.c_char_p, C.c_size_t]; lib.pg_dmodel_format.restype = C.c_size_t
     _lib = lib
     return lib

@@ -1,4 +1,4 @@
-// main.cpp -- `poregen` dispatcher (src/main.c:64-103): the gmove, kmer_freq, f1_score, subtool0 and pa_stats subtools (device path)
+// main.cpp -- `poregen` dispatcher (src/main.c:64-103): the gmove, kmer_freq, f1_score, subtool0, pa_stats and model subtools (device path)
 // and reform (host-only).
 #include <cstdio>
 #include <cstring>
@@ -14,12 +14,14 @@ static int kmer_freq_main(int, char **) { fprintf(stderr, "[poregen] this build 
 static int f1_score_main(int, char **) { fprintf(stderr, "[poregen] this build holds reform only\n"); return 1; }
 static int subtool0_main(int, char **) { fprintf(stderr, "[poregen] this build holds reform only\n"); return 1; }
 static int pa_stats_main(int, char **) { fprintf(stderr, "[poregen] this build holds reform only\n"); return 1; }
+static int model_main(int, char **) { fprintf(stderr, "[poregen] this build holds reform only\n"); return 1; }
 #else
 int gmove_main(int argc, char **argv);
 int kmer_freq_main(int argc, char **argv);
 int f1_score_main(int argc, char **argv);
 int subtool0_main(int argc, char **argv);
 int pa_stats_main(int argc, char **argv);
+int model_main(int argc, char **argv);
 #endif
 int reform_main(int argc, char **argv);
 
@@ -28,7 +30,7 @@ static double cputime() { struct rusage r; getrusage(RUSAGE_SELF, &r); return r.
 static long peakrss() { struct rusage r; getrusage(RUSAGE_SELF, &r); return r.ru_maxrss * 1024; }
 
 static int usage(FILE *fp, int code) {
-    fprintf(fp, "Usage: poregen <command> [options]\n\ncommand:\n         gmove      move k-mer signal samples into k-mer buckets (MI355X implementation)\n         reform     rewrite a SAM/BAM move table as TSV or as PAF with ss:Z:\n         kmer_freq  count the k-mers of the reads in a FASTQ file\n         f1_score   compare two ss signal alignments (SAM/BAM) point by point: TP/FP/TN/FN, F1 score\n         subtool0   mean pA of every read of a SLOW5/BLOW5 file\n         pa_stats   mean and sample standard deviation of every pA value of a SLOW5/BLOW5 file\n");
+    fprintf(fp, "Usage: poregen <command> [options]\n\ncommand:\n         gmove      move k-mer signal samples into k-mer buckets (MI355X implementation)\n         reform     rewrite a SAM/BAM move table as TSV or as PAF with ss:Z:\n         kmer_freq  count the k-mers of the reads in a FASTQ file\n         f1_score   compare two ss signal alignments (SAM/BAM) point by point: TP/FP/TN/FN, F1 score\n         subtool0   mean pA of every read of a SLOW5/BLOW5 file\n         pa_stats   mean and sample standard deviation of every pA value of a SLOW5/BLOW5 file\n         model      k-mer model (median, stddev, dwell) from the files of dump directories\n");
     return code;
 }
 
@@ -42,6 +44,7 @@ int main(int argc, char **argv) {
     else if (strcmp(argv[1], "f1_score") == 0) ret = f1_score_main(argc - 1, argv + 1);
     else if (strcmp(argv[1], "subtool0") == 0) ret = subtool0_main(argc - 1, argv + 1);
     else if (strcmp(argv[1], "pa_stats") == 0) ret = pa_stats_main(argc - 1, argv + 1);
+    else if (strcmp(argv[1], "model") == 0) ret = model_main(argc - 1, argv + 1);
     else if (strcmp(argv[1], "--version") == 0 || strcmp(argv[1], "-V") == 0) { fprintf(stdout, "poregen 0.1.0 (pgmove, gfx950)\n"); return 0; }
     else if (strcmp(argv[1], "--help") == 0 || strcmp(argv[1], "-h") == 0) return usage(stdout, 0);
     else { fprintf(stderr, "[poregen] Unrecognised command %s\n", argv[1]); return usage(stderr, 1); }

@@ -238,3 +238,35 @@ extern "C" long pgt_slow5_walk(const char *path, char *ids, size_t cap, uint64_t
     if (all.size() < cap) { memcpy(ids, all.data(), all.size()); ids[all.size()] = 0; }
     return (long)f.n_records();
 }
+
+// ---- poregen model (pg_dumphost.h, host/pg_dumpdir.h): the host path of a dump file and the directory listing / merging ------------
+#include "pg_dumphost.h"
+#include "host/pg_dumpdir.h"
+// the raw model lines (which = 0, stddev capped at `limit`) or the dwell lines (which = 1) of the directories' logical files, all of them
+// finished by the host path; returns the length (the text is cut at cap - 1), or -1 with the message in errbuf
+extern "C" long pgt_dump_model_host(const char *const *dirs, size_t n_dirs, int which, const char *limit, int keep_first, int n_threads,
+                                    char *out, size_t cap, char *errbuf, size_t ecap) {
+    pgh::DumpSet ds; std::string err, text;
+    if (!pgh::list_dump_dirs(std::vector<std::string>(dirs, dirs + n_dirs), n_threads, ds, err)) { put_err(err, errbuf, ecap); return -1; }
+    std::vector<uint8_t> bytes; std::vector<uint64_t> off;
+    if (!pgh::read_dump_files(ds, 0, ds.names.size(), n_threads, bytes, off, err)) { put_err(err, errbuf, ecap); return -1; }
+    for (size_t i = 0; i < ds.names.size(); i++) {
+        const char *b = reinterpret_cast<const char *>(bytes.data()) + off[i];
+        const size_t len = off[i + 1] - off[i];
+        text += ds.names[i]; text += '\t';
+        if (which == 0) {
+            PgDumpHostStats hs;
+            pg_dump_host_stats(b, len, keep_first != 0, hs);
+            text += hs.median; text += '\t'; text += pg_dump_sd_capped(hs.sstdev.c_str(), limit) ? std::string(limit) : hs.sstdev;
+        } else {
+            PgDumpHostDwell hd;
+            pg_dump_host_dwell(b, len, hd);
+            char t[64]; t[0] = 0;
+            if (hd.n) snprintf(t, sizeof t, "%.14Lg", ((long double)hd.mid_lo + (long double)hd.mid_hi) / 2.0L);
+            text += t;
+        }
+        text += '\n';
+    }
+    if (out && cap) { const size_t n = text.size() < cap - 1 ? text.size() : cap - 1; memcpy(out, text.data(), n); out[n] = 0; }
+    return (long)text.size();
+}

@@ -274,6 +274,9 @@ struct PgSlotModel; struct PgSlotDwell; // pg_model.h
 hipError_t pg_launch_slot_model(hipStream_t st, uint32_t n_slots, const int any_kind[4], const uint64_t *ev_off, const uint64_t *samp_off,
                                 const uint32_t *ev_len, const double *samples, uint32_t drop_first, PgSlotModel *out, PgSlotDwell *dwell,
                                 void *scratch /* >= pg_slot_model_scratch_bytes(n_slots): the lists of the rarer kinds */);
+// the same reduction over samples given as integers of 1e-8 units (|units| < PG_MODEL_MAX_UNITS; pg_dumptext.hip parses them out of dump text)
+hipError_t pg_launch_slot_model_units(hipStream_t st, uint32_t n_slots, const int any_kind[4], const uint64_t *ev_off, const uint64_t *samp_off,
+                                      const uint32_t *ev_len, const int64_t *units, uint32_t drop_first, PgSlotModel *out, PgSlotDwell *dwell, void *scratch);
 size_t pg_slot_model_scratch_bytes(uint32_t n_slots);
 // the generic walk (one wave per listed read: walk + event loop) over O.gen_list
 hipError_t pg_launch_walk(hipStream_t st, const PgDevBatch &B, const PgWalkParams &W, const PgWalkOut &O);

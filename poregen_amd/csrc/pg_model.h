@@ -18,6 +18,7 @@
 #endif
 
 #define PG_MODEL_MAX_ABS 4.0e7            /* |sample| the fixed-point view accepts (|units| < 2^52) */
+#define PG_MODEL_MAX_UNITS 4000000000000000ll /* the same bound in 1e-8 units */
 #define PG_MODEL_LIMB_BITS 20             /* deviations from the slot's first value are split in two 20-bit limbs */
 #define PG_MODEL_MAX_DEV (1ll << 40)      /* |value - first value| in 1e-8 units the moment sums accept (~10995 pA) */
 #define PG_MODEL_TINY_MAX 1024            /* files up to this many values and fewer than PG_MODEL_TINY_EVENTS events: one wave, 16 values per lane */

@@ -14,6 +14,7 @@
 //                           then the upper middle value; the file stays in L2 / MALL between the passes (150 k values = 1.2 MB at sample_limit 5000)
 #include "pg_internal.h"
 #include "pg_model.h"
+#include <type_traits>
 
 #ifndef PG_MODEL_TINY_WAVES
 #define PG_MODEL_TINY_WAVES 6 // waves per SIMD the one-wave kernel is compiled for: 80 registers and 20 bytes of scratch; k = 9 0.586 (5 waves, 85 registers) -> 0.550 ms, 8 waves (64 registers, 96 bytes of scratch) the same
@@ -222,12 +223,16 @@ __device__ __forceinline__ int64_t fixed8_dev(double x, bool &bad) {
     else if (f == -0.5 && e < 0.0) t -= 1.0;
     return (int64_t)((uint64_t)__double_as_longlong(t) & ((1ull << 52) - 1)) - (1ll << 51);
 }
+// A sample as the kernels are handed it (S): the double gmove held, converted as above, or -- pg_dumptext.hip, which reads the dump text
+// back -- the integer of 1e-8 units itself, which never passes through a double.
+__device__ __forceinline__ int64_t sample_units(double x, bool &bad) { return fixed8_dev(x, bad); }
+__device__ __forceinline__ int64_t sample_units(int64_t v, bool &bad) { if (!(v > -PG_MODEL_MAX_UNITS && v < PG_MODEL_MAX_UNITS)) bad = true; return v; }
 
 // The two workgroup kernels, by file size: SHORT (256 threads, <= 4096 values) converts the whole file once into 16 registers per
 // thread; LONG (1024 threads) re-reads the file per pass. Both stride over the list of their slots. Separate kernels because each needs
 // its own register budget; the host launches only the ones with work.
-template <int MT, int KIND> __global__ __launch_bounds__(MT, KIND == PG_MODEL_LONG ? 8 : 4) void k_slot_model(const FileRef *__restrict__ list, const uint32_t *__restrict__ list_n, const uint32_t *ev_len,
-                                                                      const double *samples, PgSlotModel *out, PgSlotDwell *dwell) {
+template <int MT, int KIND, class S> __global__ __launch_bounds__(MT, KIND == PG_MODEL_LONG ? 8 : 4) void k_slot_model(const FileRef *__restrict__ list, const uint32_t *__restrict__ list_n, const uint32_t *ev_len,
+                                                                      const S *samples, PgSlotModel *out, PgSlotDwell *dwell) {
     constexpr bool SHORT = KIND != PG_MODEL_LONG; // register-resident
     __shared__ ModelSmem<MT> sm;
     constexpr int C = SHORT ? ModelCfg<MT>::CACHE : 0;
@@ -242,12 +247,12 @@ template <int MT, int KIND> __global__ __launch_bounds__(MT, KIND == PG_MODEL_LO
     m.n = n;
     if (n > 0) {
         bool bad = false, wide = false;
-        const int64_t origin = fixed8_dev(samples[first], bad);
+        const int64_t origin = sample_units(samples[first], bad);
         // pass A: range and moments about the first value
         uint64_t mn = ~0ull, mx = 0, hh = 0, hl = 0, ll = 0;
         int64_t s1 = 0;
-        auto account = [&](double x) {
-            const int64_t v = fixed8_dev(x, bad);
+        auto account = [&](S x) {
+            const int64_t v = sample_units(x, bad);
             const uint64_t key = (uint64_t)v ^ (1ull << 63); // order-preserving
             mn = op_min(mn, key); mx = op_max(mx, key);
             const int64_t d = v - origin;
@@ -261,13 +266,13 @@ template <int MT, int KIND> __global__ __launch_bounds__(MT, KIND == PG_MODEL_LO
         rk.cnt = 0;
         if constexpr (SHORT) {
             static_assert(MT * ModelCfg<MT>::CACHE == PG_MODEL_SHORT_MAX, "the kernel holds the whole file in registers");
-            double x[C];
+            S x[C];
             rk.cnt = n > threadIdx.x ? (int)((n - threadIdx.x + MT - 1) / MT) : 0;
 #pragma unroll
             for (int u = 0; u < C; ++u) { const uint64_t i = (uint64_t)u * MT + threadIdx.x; x[u] = samples[first + (i < n ? i : n - 1)]; }
 #pragma unroll
             for (int u = 0; u < C; ++u) rk.k[u] = u < rk.cnt ? account(x[u]) : 0ull;
-        } else for_each_mine<MT, ModelCfg<MT>::U, double>(n, [&](uint64_t i) { return samples[first + i]; }, [&](double x) { (void)account(x); });
+        } else for_each_mine<MT, ModelCfg<MT>::U, S>(n, [&](uint64_t i) { return samples[first + i]; }, [&](S x) { (void)account(x); });
         mn = block_reduce<MT>(sm, mn, op_min); mx = block_reduce<MT>(sm, mx, op_max);
         m.s1 = (int64_t)block_reduce<MT>(sm, (uint64_t)s1, op_sum);
         m.s2_hh = block_reduce<MT>(sm, hh, op_sum); m.s2_hl = block_reduce<MT>(sm, hl, op_sum); m.s2_ll = block_reduce<MT>(sm, ll, op_sum);
@@ -282,7 +287,7 @@ template <int MT, int KIND> __global__ __launch_bounds__(MT, KIND == PG_MODEL_LO
             else {
                 auto key_at = [&](uint64_t i) {
                     bool b2 = false;
-                    return ((uint64_t)fixed8_dev(samples[first + i], b2) ^ (1ull << 63)) - mn;
+                    return ((uint64_t)sample_units(samples[first + i], b2) ^ (1ull << 63)) - mn;
                 };
                 const GlobalKeys<MT, decltype(key_at)> gk{n, key_at};
                 block_middle_long<MT>(sm, gk, n, bits, k_lo, k_hi);
@@ -329,6 +334,7 @@ template <int MT, int KIND> __global__ __launch_bounds__(MT, KIND == PG_MODEL_LO
 //    than another window -- for a med-MAD file after one or two -- in 32-bit arithmetic when the spread allows.
 #define WV_MAGIC 6755399441055744.0             /* 1.5 * 2^52 (even): p + WV_MAGIC has ulp 1 */
 #define WV_MAX_ABS 2.2e7                        /* |x| * 1e8 < 2^51 */
+#define WV_MAX_UNITS 2200000000000000ll          /* the same bound for samples that arrive as units */
 struct WaveSmem { uint32_t hist[256]; uint64_t cand[64]; };
 
 __device__ __forceinline__ uint64_t readlane64(uint64_t v, int l) {
@@ -480,8 +486,8 @@ template <class K, int C> __device__ void wave_middle(WaveSmem &sm, const K (&k)
 }
 
 // One file on one wave: C rows of 64 values, D rows of 64 events. Returns false when the file holds a value the conversion cannot take.
-template <int C, int D> __device__ __forceinline__ bool wave_file(WaveSmem &sm, const FileRef &fr, uint32_t s, const uint32_t *__restrict__ ev_len,
-                                                                   const double *__restrict__ samples, PgSlotModel *__restrict__ out, PgSlotDwell *__restrict__ dwell) {
+template <int C, int D, class S> __device__ __forceinline__ bool wave_file(WaveSmem &sm, const FileRef &fr, uint32_t s, const uint32_t *__restrict__ ev_len,
+                                                                   const S *__restrict__ samples, PgSlotModel *__restrict__ out, PgSlotDwell *__restrict__ dwell) {
     constexpr int WV_C = C, WV_D = D;
     const uint32_t lane = threadIdx.x;
     const uint64_t first = uniform64(fr.first), e0 = uniform64(fr.e0); // (scalar registers: the row guards below are scalar branches)
@@ -497,20 +503,26 @@ template <int C, int D> __device__ __forceinline__ bool wave_file(WaveSmem &sm, 
     constexpr int CH = WV_C > 32 ? 32 : WV_C;
 #pragma unroll
     for (int h = 0; h < WV_C; h += CH) {
-        double x[CH];
+        S x[CH];
 #pragma unroll
-        for (int v = 0; v < CH; ++v) { const int u = h + v; if ((uint32_t)u * 64 < n) { const uint32_t i = (uint32_t)u * 64 + lane; x[v] = samples[first + (i < n ? i : 0u)]; } else x[v] = 0.0; }
+        for (int v = 0; v < CH; ++v) { const int u = h + v; if ((uint32_t)u * 64 < n) { const uint32_t i = (uint32_t)u * 64 + lane; x[v] = samples[first + (i < n ? i : 0u)]; } else x[v] = S(0); }
 #pragma unroll
         for (int v = 0; v < CH; ++v) {
             const int u = h + v;
             if ((uint32_t)u * 64 < n) {
-                big |= !(fabs(x[v]) < WV_MAX_ABS); // also NaN
-                const double p = x[v] * 1e8, e = fma(x[v], 1e8, -p);
-                double tt = p + WV_MAGIC; // rint(p), ties to even (WV_MAGIC is even)
-                const double f = p - (tt - WV_MAGIC);
-                if (__ballot(fabs(f) == 0.5)) { // p sits on a tie that the addition broke to even; e says on which side the exact product lies
-                    if (f == 0.5 && e > 0.0) tt += 1.0;
-                    else if (f == -0.5 && e < 0.0) tt -= 1.0;
+                double tt;
+                if constexpr (std::is_same<S, double>::value) {
+                    big |= !(fabs(x[v]) < WV_MAX_ABS); // also NaN
+                    const double p = x[v] * 1e8, e = fma(x[v], 1e8, -p);
+                    tt = p + WV_MAGIC; // rint(p), ties to even (WV_MAGIC is even)
+                    const double f = p - (tt - WV_MAGIC);
+                    if (__ballot(fabs(f) == 0.5)) { // p sits on a tie that the addition broke to even; e says on which side the exact product lies
+                        if (f == 0.5 && e > 0.0) tt += 1.0;
+                        else if (f == -0.5 && e < 0.0) tt -= 1.0;
+                    }
+                } else { // units: the conversion and the sum are exact below 2^51
+                    big |= !(x[v] > -WV_MAX_UNITS && x[v] < WV_MAX_UNITS);
+                    tt = (double)x[v] + WV_MAGIC;
                 }
                 t[u] = tt;
                 tmin = min_f64_raw(tmin, tt); tmax = max_f64_raw(tmax, tt);
@@ -583,21 +595,21 @@ template <int C, int D> __device__ __forceinline__ bool wave_file(WaveSmem &sm, 
 }
 
 // The kernel over ALL slots (a wave each): the TINY files are reduced here, the others go on the list of their kind (lists[kind - 1]).
-__global__ __launch_bounds__(64, PG_MODEL_TINY_WAVES) void k_slot_model_wave(const uint64_t *__restrict__ ev_off, const uint64_t *__restrict__ samp_off, uint32_t n_slots, uint32_t drop_first,
-                                                                              const uint32_t *__restrict__ ev_len, const double *__restrict__ samples, PgSlotModel *__restrict__ out,
+template <class S> __global__ __launch_bounds__(64, PG_MODEL_TINY_WAVES) void k_slot_model_wave(const uint64_t *__restrict__ ev_off, const uint64_t *__restrict__ samp_off, uint32_t n_slots, uint32_t drop_first,
+                                                                              const uint32_t *__restrict__ ev_len, const S *__restrict__ samples, PgSlotModel *__restrict__ out,
                                                                               PgSlotDwell *__restrict__ dwell, FileRef *__restrict__ lists, uint32_t *__restrict__ counts, int short_kind) {
     __shared__ WaveSmem sm;
     const uint32_t s = blockIdx.x;
     if (s >= n_slots) return;
     const FileRef fr = file_ref(ev_off, samp_off, s, drop_first);
     int kind = (int)uniform32((uint32_t)pg_model_kind(fr.n, fr.nev));
-    if (kind == PG_MODEL_TINY && !wave_file<PG_MODEL_TINY_MAX / 64, PG_MODEL_TINY_EVENTS / 64>(sm, fr, s, ev_len, samples, out, dwell)) kind = PG_MODEL_SHORT;
+    if (kind == PG_MODEL_TINY && !wave_file<PG_MODEL_TINY_MAX / 64, PG_MODEL_TINY_EVENTS / 64, S>(sm, fr, s, ev_len, samples, out, dwell)) kind = PG_MODEL_SHORT;
     if (kind == PG_MODEL_SHORT) kind = short_kind; // (the launcher may send the few SHORT files of a job with the LONG ones: one launch less)
     if (kind != PG_MODEL_TINY && threadIdx.x == 0) lists[(size_t)(kind - 1) * n_slots + atomicAdd(counts + (kind - 1), 1u)] = fr; // (any order: every slot writes its own result)
 }
 // The MID files (up to 2048 values and 511 events: at k = 9 the ~3 000 files above the one-wave size): the same code with 32 rows, over their list.
-__global__ __launch_bounds__(64, 2) void k_slot_model_wave_mid(const uint64_t *__restrict__ ev_off, const uint64_t *__restrict__ samp_off, uint32_t n_slots, uint32_t drop_first,
-                                                                const uint32_t *__restrict__ ev_len, const double *__restrict__ samples, PgSlotModel *__restrict__ out,
+template <class S> __global__ __launch_bounds__(64, 2) void k_slot_model_wave_mid(const uint64_t *__restrict__ ev_off, const uint64_t *__restrict__ samp_off, uint32_t n_slots, uint32_t drop_first,
+                                                                const uint32_t *__restrict__ ev_len, const S *__restrict__ samples, PgSlotModel *__restrict__ out,
                                                                 PgSlotDwell *__restrict__ dwell, FileRef *__restrict__ lists, uint32_t *__restrict__ counts, int short_kind) {
     __shared__ WaveSmem sm;
     const uint32_t n_mine = uniform32(counts[PG_MODEL_MID - 1]);
@@ -605,16 +617,13 @@ __global__ __launch_bounds__(64, 2) void k_slot_model_wave_mid(const uint64_t *_
         const FileRef fr = lists[(size_t)(PG_MODEL_MID - 1) * n_slots + it];
         const uint32_t s = uniform32(fr.slot);
         if (it != blockIdx.x) __syncthreads();
-        if (!wave_file<PG_MODEL_MID_MAX / 64, PG_MODEL_MID_EVENTS / 64>(sm, fr, s, ev_len, samples, out, dwell) && threadIdx.x == 0)
+        if (!wave_file<PG_MODEL_MID_MAX / 64, PG_MODEL_MID_EVENTS / 64, S>(sm, fr, s, ev_len, samples, out, dwell) && threadIdx.x == 0)
             lists[(size_t)(short_kind - 1) * n_slots + atomicAdd(counts + (short_kind - 1), 1u)] = fr;
     }
 }
 
-} // namespace
-
-size_t pg_slot_model_scratch_bytes(uint32_t n_slots) { return 3 * (size_t)n_slots * sizeof(FileRef) + 64; }
-hipError_t pg_launch_slot_model(hipStream_t st, uint32_t n_slots, const int any_kind[4], const uint64_t *ev_off, const uint64_t *samp_off,
-                                const uint32_t *ev_len, const double *samples, uint32_t drop_first, PgSlotModel *out, PgSlotDwell *dwell, void *scratch) {
+template <class S> hipError_t launch_slot_model(hipStream_t st, uint32_t n_slots, const int any_kind[4], const uint64_t *ev_off, const uint64_t *samp_off,
+                                                const uint32_t *ev_len, const S *samples, uint32_t drop_first, PgSlotModel *out, PgSlotDwell *dwell, void *scratch) {
     if (n_slots == 0) return hipSuccess;
     (void)hipGetLastError(); // sticky per-thread state of an unrelated earlier failure
     // scratch: [3] list lengths (+ padding to 64 bytes), the lists of the MID, SHORT and LONG files (FileRef entries)
@@ -630,14 +639,26 @@ hipError_t pg_launch_slot_model(hipStream_t st, uint32_t n_slots, const int any_
     // the one-wave kernel over all slots, always: it is also the pass that sorts the slots into the lists (a wave that is not TINY leaves after four
     // scalar loads). (Lists written by the host when it holds the offsets and no file is TINY: measured at k = 5, two small uploads cost what
     // the launch does -- 60.8 against 60.0 us for the model of the headline job.)
-    hipLaunchKernelGGL(k_slot_model_wave, dim3(n_slots), dim3(64), 0, st, ev_off, samp_off, n_slots, drop_first, ev_len, samples, out, dwell, lists, counts, short_kind);
-    if (any_kind[PG_MODEL_MID]) hipLaunchKernelGGL(k_slot_model_wave_mid, dim3(n_slots < 4096u ? n_slots : 4096u), dim3(64), 0, st, ev_off, samp_off, n_slots, drop_first, ev_len, samples, out, dwell, lists, counts, short_kind);
+    hipLaunchKernelGGL(k_slot_model_wave<S>, dim3(n_slots), dim3(64), 0, st, ev_off, samp_off, n_slots, drop_first, ev_len, samples, out, dwell, lists, counts, short_kind);
+    if (any_kind[PG_MODEL_MID]) hipLaunchKernelGGL(k_slot_model_wave_mid<S>, dim3(n_slots < 4096u ? n_slots : 4096u), dim3(64), 0, st, ev_off, samp_off, n_slots, drop_first, ev_len, samples, out, dwell, lists, counts, short_kind);
     // (the one-wave kernels hand files with values of 2.2e7 and beyond to the 256-thread one)
     if (!merge && (any_kind[PG_MODEL_SHORT] || any_kind[PG_MODEL_TINY] || any_kind[PG_MODEL_MID]))
-        hipLaunchKernelGGL((k_slot_model<256, PG_MODEL_SHORT>), dim3(n_slots < 2048u ? n_slots : 2048u), dim3(256), 0, st,
+        hipLaunchKernelGGL((k_slot_model<256, PG_MODEL_SHORT, S>), dim3(n_slots < 2048u ? n_slots : 2048u), dim3(256), 0, st,
                            (const FileRef *)(lists + (size_t)(PG_MODEL_SHORT - 1) * n_slots), (const uint32_t *)(counts + (PG_MODEL_SHORT - 1)), ev_len, samples, out, dwell);
     if (any_kind[PG_MODEL_LONG])
-        hipLaunchKernelGGL((k_slot_model<1024, PG_MODEL_LONG>), dim3(n_slots < 512u ? n_slots : 512u), dim3(1024), 0, st,
+        hipLaunchKernelGGL((k_slot_model<1024, PG_MODEL_LONG, S>), dim3(n_slots < 512u ? n_slots : 512u), dim3(1024), 0, st,
                            (const FileRef *)(lists + (size_t)(PG_MODEL_LONG - 1) * n_slots), (const uint32_t *)(counts + (PG_MODEL_LONG - 1)), ev_len, samples, out, dwell);
     return hipGetLastError();
+}
+
+} // namespace
+
+size_t pg_slot_model_scratch_bytes(uint32_t n_slots) { return 3 * (size_t)n_slots * sizeof(FileRef) + 64; }
+hipError_t pg_launch_slot_model(hipStream_t st, uint32_t n_slots, const int any_kind[4], const uint64_t *ev_off, const uint64_t *samp_off,
+                                const uint32_t *ev_len, const double *samples, uint32_t drop_first, PgSlotModel *out, PgSlotDwell *dwell, void *scratch) {
+    return launch_slot_model<double>(st, n_slots, any_kind, ev_off, samp_off, ev_len, samples, drop_first, out, dwell, scratch);
+}
+hipError_t pg_launch_slot_model_units(hipStream_t st, uint32_t n_slots, const int any_kind[4], const uint64_t *ev_off, const uint64_t *samp_off,
+                                      const uint32_t *ev_len, const int64_t *units, uint32_t drop_first, PgSlotModel *out, PgSlotDwell *dwell, void *scratch) {
+    return launch_slot_model<int64_t>(st, n_slots, any_kind, ev_off, samp_off, ev_len, units, drop_first, out, dwell, scratch);
 }

@@ -883,3 +883,135 @@ def read_means(sig, sig_off, digitisation, offset, range, device: int = 0) -> Pa
         return sm.finish()
     finally:
         sm.close()
+
+
+# ---- model: the k-mer model from the text of dump files (pg_dmodel_*) ------------------------------------------------------------------
+
+@dataclass
+class DumpModelInfo:
+    n_files: int
+    n_bytes: int
+    n_values: int          # values the device parsed
+    n_host_files: int      # files finished on the host (outside the strict grammar, or declined by the reduction)
+    host_files: np.ndarray
+    n_batches: int
+    parse_ms: float        # device time of the parse kernels / of the reduction (profile=True), else 0
+    model_ms: float
+
+
+def _model_arrays(m, text_of) -> "Model":
+    ns = m.n_slots
+
+    def arr(ptr, dt):
+        if ns == 0 or not ptr:
+            return np.zeros(0, dtype=dt)
+        return np.frombuffer((C.c_char * (ns * np.dtype(dt).itemsize)).from_address(ptr), dtype=dt).copy()
+    texts = [[text_of(s, which) for s in range(ns)] for which in (_abi.PG_MODEL_TEXT_MEDIAN, _abi.PG_MODEL_TEXT_SSTDEV, _abi.PG_MODEL_TEXT_DWELL)]
+    return Model(n_values=arr(m.n_values, np.uint64), median=arr(m.median, np.float64), sstdev=arr(m.sstdev, np.float64),
+                 mid_lo=arr(m.mid_lo, np.int64), mid_hi=arr(m.mid_hi, np.int64), origin=arr(m.origin, np.int64),
+                 sum1=arr(m.sum1, np.int64), sum2_lo=arr(m.sum2_lo, np.uint64), sum2_hi=arr(m.sum2_hi, np.uint64),
+                 dwell_n=arr(m.dwell_n, np.uint64), dwell_median=arr(m.dwell_median, np.float64),
+                 median_text=texts[0], sstdev_text=texts[1], dwell_text=texts[2])
+
+
+class DumpModel:
+    """The k-mer model of dump FILES on the GPU (pg_dmodel_*): submit() takes a batch of files as one buffer of their bytes -- `bytes`, a
+    numpy uint8 array, or a CUDA torch.uint8 tensor (read in place, kept alive until finish) -- and file_off[n_files + 1]; finish()
+    returns a Model with one entry per file in submission order, and a DumpModelInfo."""
+
+    def __init__(self, keep_first: bool = False, device: int = 0, profile: bool = False):
+        self._lib = _abi.load()
+        h = C.c_void_p()
+        flags = (_abi.PG_MODEL_KEEP_FIRST if keep_first else 0) | (_abi.PG_DMODEL_PROFILE if profile else 0)
+        st = self._lib.pg_dmodel_create(device, flags, C.byref(h))
+        if st != 0:
+            raise PgError(st, self._lib.pg_dmodel_last_error(None).decode())
+        self._h = h
+        self._keep = []
+
+    def _check(self, st):
+        if st != 0:
+            raise PgError(st, self._lib.pg_dmodel_last_error(self._h).decode())
+
+    def submit(self, data, file_off):
+        off = np.ascontiguousarray(file_off, dtype=np.uint64)
+        if off.size < 1:
+            raise ValueError("file_off needs n_files + 1 entries")
+        if hasattr(data, "is_cuda") and data.is_cuda:
+            if data.dtype.itemsize != 1 or not data.is_contiguous() or data.numel() < int(off[-1]):
+                raise ValueError("device data must be a contiguous uint8 tensor of file_off[-1] bytes")
+            self._keep.append(data)
+            self._check(self._lib.pg_dmodel_submit(self._h, C.c_void_p(data.data_ptr()), C.c_void_p(off.ctypes.data), off.size - 1, _abi.PG_LOC_DEVICE))
+            return
+        a = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else data, dtype=np.uint8)
+        if a.size < int(off[-1]):
+            raise ValueError("data is shorter than file_off[-1]")
+        self._check(self._lib.pg_dmodel_submit(self._h, C.c_void_p(a.ctypes.data) if a.size else None, C.c_void_p(off.ctypes.data), off.size - 1, _abi.PG_LOC_HOST))
+
+    def finish(self):
+        m = _abi.PgModelResult()
+        info = _abi.PgDmodelInfo()
+        try:
+            self._check(self._lib.pg_dmodel_finish(self._h, C.byref(m), C.byref(info)))
+        finally:
+            self._keep = []
+        buf = C.create_string_buffer(64)
+
+        def text_of(s, which):
+            n = self._lib.pg_dmodel_format(self._h, s, which, buf, 64)
+            return buf.raw[:n].decode()
+        nh = int(info.n_host_files)
+        hf = np.ctypeslib.as_array(info.host_files, (nh,)).copy() if nh else np.zeros(0, np.uint32)
+        return _model_arrays(m, text_of), DumpModelInfo(int(info.n_files), int(info.n_bytes), int(info.n_values), nh, hf, int(info.n_batches),
+                                                        float(info.parse_ms), float(info.model_ms))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.pg_dmodel_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def list_dump_dirs(dirs):
+    """(names, paths): the sorted union of the directories' file names (byte order; dot files and everything that is not a regular file
+    skipped) and, per name, its files in argument order -- what `poregen model` reads."""
+    import os
+    found = {}
+    for d in dirs:
+        for name in os.listdir(os.fsencode(d)):
+            path = os.path.join(os.fsencode(d), name)
+            if not name.startswith(b".") and os.path.isfile(path):
+                found.setdefault(name, []).append(path)
+    names = sorted(found)
+    return [os.fsdecode(n) for n in names], [found[n] for n in names]
+
+
+def model_from_dumps(dirs, limit: str = "3.1", keep_first: bool = False, batch_bytes: int = 64 << 20, device: int = 0, profile: bool = False):
+    """One-shot `poregen model`: (raw_lines, dwell_lines, info) of the dump directories -- NAME<TAB>median<TAB>stddev (capped at `limit`) and
+    NAME<TAB>median dwell per file name; files of one name in several directories are read back to back."""
+    if isinstance(dirs, (str, bytes)) or hasattr(dirs, "__fspath__"):
+        dirs = [dirs]
+    names, paths = list_dump_dirs(dirs)
+    dm = DumpModel(keep_first=keep_first, device=device, profile=profile)
+    try:
+        chunks, off = [], [0]
+
+        def flush():
+            if len(off) > 1:
+                dm.submit(b"".join(chunks), off)
+            chunks.clear(); del off[1:]
+        for ps in paths:
+            data = b"".join(open(p, "rb").read() for p in ps)
+            if len(off) > 1 and off[-1] + len(data) > batch_bytes:
+                flush()
+            chunks.append(data); off.append(off[-1] + len(data))
+        flush()
+        m, info = dm.finish()
+    finally:
+        dm.close()
+    return m.raw_model_lines(names, limit), m.dwell_lines(names), info
