@@ -68,6 +68,11 @@
  *                                  device                                          scripts/poregen.sh:66-67, 43
  * pg_dmodel_finish / _format       datamash median / sstdev per file               scripts/poregen.sh:66-67, 43
  * pg_dmodel_sync / _last_error     (no counterpart)
+ *
+ * STEP 7 of the same script, the raw model to the final model file, is one host-only call:
+ * pg_transform_model               apply_transformation and set_stddev: echo | bc -l per row, datamash min max, cut | paste
+ *                                                                                  scripts/poregen.sh:87-148
+ * pg_transform_free                (no counterpart)
  */
 #ifndef PGMOVE_H
 #define PGMOVE_H
@@ -599,6 +604,22 @@ pg_status pg_dmodel_sync(pg_dmodel *h);
 pg_status pg_dmodel_finish(pg_dmodel *h, pg_model_result *out, pg_dmodel_info *info);
 /* pg_model_format for the handle's last finish (which = PG_MODEL_TEXT_*), with the host-finished files' texts as datamash prints them */
 size_t    pg_dmodel_format(const pg_dmodel *h, uint32_t file, int32_t which, char *buf, size_t cap);
+
+/* ---- transform: the raw k-mer model to the final model file (STEP 7), on the host -------------------------------------------------------
+ * scripts/poregen.sh:87-129 (apply_transformation) and, with stdv_from, :131-148 (set_stddev), without bc, datamash, cut and paste. No
+ * handle, no device, no global state: 4^k rows of exact decimal arithmetic by bc's rules (scale 20; csrc/pg_bcdec.h).
+ *   raw        n bytes of KMER<TAB>level_mean<TAB>level_stdv rows (further columns ignored; a last line without '\n' counts)
+ *   A, B       NUL-terminated decimal texts: level_mean' = (level_mean * A) + B  (sstdev and mean of the whole pA dataset)
+ *   C, D       level_stdv' = (level_stdv - min) * (D - C) / (max - min) + C, min and max as `datamash min 1 max 1` prints them
+ *   stdv_from  NULL, or n_from bytes of a model file: column 3 of its lines 8 onward replaces level_stdv', by position, verbatim
+ * PG_OK: *out holds *n_out bytes (and a NUL behind them) -- the seven header lines, "#k" with the first k-mer's length, and one row per
+ * input row -- to be released with pg_transform_free. PG_ERR_INPUT: the model is refused as a whole (a field that is no number to bc
+ * -- "1e-05", "nan", "+1", an empty field --, a row with fewer than 3 fields, k-mers of two lengths, max == min, an empty model, unequal
+ * row counts with stdv_from, a text bc would wrap); *out is NULL and err (err_cap bytes, may be NULL) names the line and the reason.
+ * PG_ERR_INVALID_ARG: a missing pointer, or out of memory. Never a wrong digit. */
+pg_status pg_transform_model(const char *raw, size_t n, const char *A, const char *B, const char *C, const char *D, const char *stdv_from, size_t n_from,
+                             char **out, size_t *n_out, char *err, size_t err_cap);
+void      pg_transform_free(char *text);
 
 #ifdef __cplusplus
 }

@@ -42,6 +42,7 @@ EXPORTS = [
     "pg_fscore_create", "pg_fscore_destroy", "pg_fscore_last_error", "pg_fscore_submit", "pg_fscore_sync", "pg_fscore_finish",
     "pg_pamean_create", "pg_pamean_destroy", "pg_pamean_last_error", "pg_pamean_submit", "pg_pamean_sync", "pg_pamean_finish",
     "pg_dmodel_create", "pg_dmodel_destroy", "pg_dmodel_last_error", "pg_dmodel_submit", "pg_dmodel_sync", "pg_dmodel_finish", "pg_dmodel_format",
+    "pg_transform_model", "pg_transform_free",
 ]
 PG_JOB_EXCHANGE_AUTO, PG_JOB_EXCHANGE_HOST, PG_JOB_EXCHANGE_RCCL = 0, 1, 2
 
@@ -251,5 +252,8 @@ def load():
     lib.pg_dmodel_sync.argtypes = [vp]; lib.pg_dmodel_sync.restype = i32
     lib.pg_dmodel_finish.argtypes = [vp, C.POINTER(PgModelResult), C.POINTER(PgDmodelInfo)]; lib.pg_dmodel_finish.restype = i32
     lib.pg_dmodel_format.argtypes = [vp, u32, i32, C.c_char_p, C.c_size_t]; lib.pg_dmodel_format.restype = C.c_size_t
+    lib.pg_transform_model.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t,
+                                       C.POINTER(vp), C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]; lib.pg_transform_model.restype = i32
+    lib.pg_transform_free.argtypes = [vp]; lib.pg_transform_free.restype = None
     _lib = lib
     return lib

@@ -1,5 +1,5 @@
-// main.cpp -- `poregen` dispatcher (src/main.c:64-103): the gmove, kmer_freq, f1_score, subtool0, pa_stats and model subtools (device path)
-// and reform (host-only).
+// main.cpp -- `poregen` dispatcher (src/main.c:64-103): the gmove, kmer_freq, f1_score, subtool0, pa_stats and model subtools (device path),
+// reform and transform (host-only; transform --signal runs pa_stats' device path).
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -8,7 +8,7 @@
 #include <cstdlib>
 #include <unistd.h>
 
-#ifdef PG_REFORM_ONLY // the sanitizer build of the host-only subtool (Makefile: asan): no device code linked
+#ifdef PG_REFORM_ONLY // the sanitizer build of the host-only subtools, reform and transform (Makefile: asan): no device code linked
 static int gmove_main(int, char **) { fprintf(stderr, "[poregen] this build holds reform only\n"); return 1; }
 static int kmer_freq_main(int, char **) { fprintf(stderr, "[poregen] this build holds reform only\n"); return 1; }
 static int f1_score_main(int, char **) { fprintf(stderr, "[poregen] this build holds reform only\n"); return 1; }
@@ -24,13 +24,14 @@ int pa_stats_main(int argc, char **argv);
 int model_main(int argc, char **argv);
 #endif
 int reform_main(int argc, char **argv);
+int transform_main(int argc, char **argv);
 
 static double realtime() { struct timeval tp; gettimeofday(&tp, nullptr); return tp.tv_sec + tp.tv_usec * 1e-6; }
 static double cputime() { struct rusage r; getrusage(RUSAGE_SELF, &r); return r.ru_utime.tv_sec + r.ru_stime.tv_sec + 1e-6 * (r.ru_utime.tv_usec + r.ru_stime.tv_usec); }
 static long peakrss() { struct rusage r; getrusage(RUSAGE_SELF, &r); return r.ru_maxrss * 1024; }
 
 static int usage(FILE *fp, int code) {
-    fprintf(fp, "Usage: poregen <command> [options]\n\ncommand:\n         gmove      move k-mer signal samples into k-mer buckets (MI355X implementation)\n         reform     rewrite a SAM/BAM move table as TSV or as PAF with ss:Z:\n         kmer_freq  count the k-mers of the reads in a FASTQ file\n         f1_score   compare two ss signal alignments (SAM/BAM) point by point: TP/FP/TN/FN, F1 score\n         subtool0   mean pA of every read of a SLOW5/BLOW5 file\n         pa_stats   mean and sample standard deviation of every pA value of a SLOW5/BLOW5 file\n         model      k-mer model (median, stddev, dwell) from the files of dump directories\n");
+    fprintf(fp, "Usage: poregen <command> [options]\n\ncommand:\n         gmove      move k-mer signal samples into k-mer buckets (MI355X implementation)\n         reform     rewrite a SAM/BAM move table as TSV or as PAF with ss:Z:\n         kmer_freq  count the k-mers of the reads in a FASTQ file\n         f1_score   compare two ss signal alignments (SAM/BAM) point by point: TP/FP/TN/FN, F1 score\n         subtool0   mean pA of every read of a SLOW5/BLOW5 file\n         pa_stats   mean and sample standard deviation of every pA value of a SLOW5/BLOW5 file\n         model      k-mer model (median, stddev, dwell) from the files of dump directories\n         transform  the final model file from a raw k-mer model: (median * stdv) + mean, stddev projected onto [2.5, 4]\n");
     return code;
 }
 
@@ -45,6 +46,7 @@ int main(int argc, char **argv) {
     else if (strcmp(argv[1], "subtool0") == 0) ret = subtool0_main(argc - 1, argv + 1);
     else if (strcmp(argv[1], "pa_stats") == 0) ret = pa_stats_main(argc - 1, argv + 1);
     else if (strcmp(argv[1], "model") == 0) ret = model_main(argc - 1, argv + 1);
+    else if (strcmp(argv[1], "transform") == 0) ret = transform_main(argc - 1, argv + 1);
     else if (strcmp(argv[1], "--version") == 0 || strcmp(argv[1], "-V") == 0) { fprintf(stdout, "poregen 0.1.0 (pgmove, gfx950)\n"); return 0; }
     else if (strcmp(argv[1], "--help") == 0 || strcmp(argv[1], "-h") == 0) return usage(stdout, 0);
     else { fprintf(stderr, "[poregen] Unrecognised command %s\n", argv[1]); return usage(stderr, 1); }

@@ -150,31 +150,12 @@ class Walker {
     unsigned nt_;
 };
 
-int run(const char *tool, int argc, char **argv, bool stats) {
-    int c, longindex = 0;
-    Opts opt;
-    bool help_to_stdout = false;
-    optind = 1;
-    while ((c = getopt_long(argc, argv, "t:B:K:v:o:hV", kLongOptions, &longindex)) >= 0) {
-        if (c == 'B') {
-            opt.batch_bytes = mm_parse_num(optarg);
-            if (opt.batch_bytes <= 0) { S0_ERROR(tool, "%s", "Maximum number of bytes should be larger than 0."); exit(EXIT_FAILURE); }
-        } else if (c == 'K') {
-            opt.batch_size = atoi(optarg);
-            if (opt.batch_size < 1) { S0_ERROR(tool, "Batch size should larger than 0. You entered %d", opt.batch_size); exit(EXIT_FAILURE); }
-        } else if (c == 't') {
-            opt.threads = atoi(optarg);
-            if (opt.threads < 1) { S0_ERROR(tool, "Number of threads should larger than 0. You entered %d", opt.threads); exit(EXIT_FAILURE); }
-        } else if (c == 'v') g_log_level = atoi(optarg);
-        else if (c == 'V') { fprintf(stdout, "%s %s\n", tool, "0.1.0"); exit(EXIT_SUCCESS); }
-        else if (c == 'h') help_to_stdout = true;
-        // 'o' and --debug-break (c == 0, longindex 7): accepted, no effect
-    }
-    if (argc - optind != 1 || help_to_stdout) {
-        print_help(help_to_stdout ? stdout : stderr, tool, opt);
-        exit(help_to_stdout ? EXIT_SUCCESS : EXIT_FAILURE);
-    }
-    const char *path = argv[optind];
+// pa_stats' two numbers as it prints them ("%.14g"): `poregen transform --signal` takes the texts from the same walk
+struct StatsTexts { bool print; std::string mean, sstdev; };
+
+// The walk of one file: every record in file order, batch by batch through pg_pamean_*. stats == nullptr: subtool0's line per record;
+// otherwise the dataset's mean and sstdev. Every error is the tool's ERROR line and exit 1.
+void walk(const char *tool, const char *path, const Opts &opt, StatsTexts *stats) {
     const double t0 = now();
     pgh::Slow5File f;
     std::string err;
@@ -232,11 +213,42 @@ int run(const char *tool, int argc, char **argv, bool stats) {
     pg_pamean_destroy(h);
     if (stats) {
         if (r.n_samples < 2) { S0_ERROR(tool, "%s holds %llu pA values: the sample standard deviation needs at least 2", path, (unsigned long long)r.n_samples); exit(EXIT_FAILURE); }
-        fprintf(stdout, "%.14g\t%.14g\n", r.mean, r.sstdev);
+        char t[64];
+        snprintf(t, sizeof t, "%.14g", r.mean); stats->mean = t;
+        snprintf(t, sizeof t, "%.14g", r.sstdev); stats->sstdev = t;
+        if (stats->print) fprintf(stdout, "%s\t%s\n", stats->mean.c_str(), stats->sstdev.c_str());
     }
     fflush(stdout);
     fprintf(stderr, "[%s] %llu records, %llu samples, %llu finished on the host; host decode %.3f s, waiting for the device %.3f s, total %.3f s\n", tool,
             (unsigned long long)r.n_reads, (unsigned long long)r.n_samples, (unsigned long long)r.n_fallback, t_decode, t_wait, now() - t0);
+}
+
+int run(const char *tool, int argc, char **argv, bool stats) {
+    int c, longindex = 0;
+    Opts opt;
+    bool help_to_stdout = false;
+    optind = 1;
+    while ((c = getopt_long(argc, argv, "t:B:K:v:o:hV", kLongOptions, &longindex)) >= 0) {
+        if (c == 'B') {
+            opt.batch_bytes = mm_parse_num(optarg);
+            if (opt.batch_bytes <= 0) { S0_ERROR(tool, "%s", "Maximum number of bytes should be larger than 0."); exit(EXIT_FAILURE); }
+        } else if (c == 'K') {
+            opt.batch_size = atoi(optarg);
+            if (opt.batch_size < 1) { S0_ERROR(tool, "Batch size should larger than 0. You entered %d", opt.batch_size); exit(EXIT_FAILURE); }
+        } else if (c == 't') {
+            opt.threads = atoi(optarg);
+            if (opt.threads < 1) { S0_ERROR(tool, "Number of threads should larger than 0. You entered %d", opt.threads); exit(EXIT_FAILURE); }
+        } else if (c == 'v') g_log_level = atoi(optarg);
+        else if (c == 'V') { fprintf(stdout, "%s %s\n", tool, "0.1.0"); exit(EXIT_SUCCESS); }
+        else if (c == 'h') help_to_stdout = true;
+        // 'o' and --debug-break (c == 0, longindex 7): accepted, no effect
+    }
+    if (argc - optind != 1 || help_to_stdout) {
+        print_help(help_to_stdout ? stdout : stderr, tool, opt);
+        exit(help_to_stdout ? EXIT_SUCCESS : EXIT_FAILURE);
+    }
+    StatsTexts st{true, "", ""};
+    walk(tool, argv[optind], opt, stats ? &st : nullptr);
     return 0;
 }
 
@@ -244,3 +256,9 @@ int run(const char *tool, int argc, char **argv, bool stats) {
 
 int subtool0_main(int argc, char **argv) { return run("subtool0", argc, argv, false); }
 int pa_stats_main(int argc, char **argv) { return run("pa_stats", argc, argv, true); }
+// `poregen transform --signal FILE` (transform_cli.cpp): the two texts `poregen pa_stats FILE` prints, nothing on stdout; exits like pa_stats
+void pa_stats_texts(const char *tool, const char *path, std::string &mean, std::string &sstdev) {
+    StatsTexts st{false, "", ""};
+    walk(tool, path, Opts(), &st);
+    mean = st.mean; sstdev = st.sstdev;
+}

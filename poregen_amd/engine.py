@@ -1015,3 +1015,25 @@ def model_from_dumps(dirs, limit: str = "3.1", keep_first: bool = False, batch_b
     finally:
         dm.close()
     return m.raw_model_lines(names, limit), m.dwell_lines(names), info
+
+
+def transform_model(raw_text, stdv, mean, stdv_min="2.5", stdv_max="4", stdv_from=None) -> str:
+    """`poregen transform` (STEP 7, scripts/poregen.sh:87-148): the final model file from a raw model's KMER<TAB>median<TAB>stddev rows.
+    level_mean' = (level_mean * stdv) + mean and level_stdv projected onto [stdv_min, stdv_max], digit for digit as `bc -l` prints them; the
+    four constants are decimal TEXTS (a float would lose the digits bc keeps). stdv_from: the text of another model file whose level_stdv
+    column replaces the projected one, row by row. Host only: no GPU is touched. ValueError with the library's message when the model is
+    refused (a field that is no number to bc, a k-mer without samples, max == min, ...)."""
+    def enc(x):
+        return x if isinstance(x, bytes) else str(x).encode()
+    lib = _abi.load()
+    raw = enc(raw_text)
+    frm = None if stdv_from is None else enc(stdv_from)
+    out, n_out, err = C.c_void_p(), C.c_size_t(), C.create_string_buffer(512)
+    st = lib.pg_transform_model(raw, len(raw), enc(stdv), enc(mean), enc(stdv_min), enc(stdv_max), frm, 0 if frm is None else len(frm),
+                                C.byref(out), C.byref(n_out), err, len(err))
+    if st != _abi.PG_OK:
+        raise ValueError(err.value.decode(errors="replace"))
+    try:
+        return C.string_at(out, n_out.value).decode()
+    finally:
+        lib.pg_transform_free(out)
