@@ -78,6 +78,16 @@ def load_dict(path, region=None):
     return d
 
 
+def expand_ops(n, k, sig0: int, ref0: int, direction: int):
+    """expand() on the ops themselves: counts n and kind bytes k as int64 arrays"""
+    match, ins, dele = k == ord(","), k == ord("I"), k == ord("D")
+    step = np.where(match, 1, np.where(dele, n, 0))
+    ref_at = ref0 + direction * (np.cumsum(step) - step)  # ref before each op
+    pts = np.where(match | ins, n, 0)
+    refs = np.repeat(np.where(ins, -1, ref_at), pts)
+    return sig0, refs
+
+
 def expand(ss: bytes, sig0: int, ref0: int, direction: int):
     """signal positions (contiguous from sig0) and their refs"""
     if not ss or ss[-1:].isdigit():
@@ -85,12 +95,7 @@ def expand(ss: bytes, sig0: int, ref0: int, direction: int):
     ops = re.findall(rb"(\d+)(\D)", ss)
     n = np.array([int(a) for a, _ in ops], np.int64)
     k = np.array([b[0] for _, b in ops], np.int64)
-    match, ins, dele = k == ord(","), k == ord("I"), k == ord("D")
-    step = np.where(match, 1, np.where(dele, n, 0))
-    ref_at = ref0 + direction * (np.cumsum(step) - step)  # ref before each op
-    pts = np.where(match | ins, n, 0)
-    refs = np.repeat(np.where(ins, -1, ref_at), pts)
-    return sig0, refs
+    return expand_ops(n, k, sig0, ref0, direction)
 
 
 def compare(a, b, threshold=0, region=None):
@@ -119,6 +124,53 @@ def pair_counts(ss1, si1, ss2, si2, rna=False, threshold=0, base_shift=0, region
         raise F1Error("tuple index out of range")
     d = -1 if rna else 1
     return compare(expand(ss1, a[0], a[2], d), expand(ss2, b[0], b[2] + base_shift, d), threshold, region)
+
+
+def pair_counts_py(ss1, sig1, ref1, ss2, sig2, ref2, rna=False, threshold=0, region=None):
+    """pair_counts on Python ints, one point at a time as f1score.py walks them (parse_ss_string :19-57, compare_mappings :89-116):
+    for values whose sums or differences leave int64. ss as bytes, the scalars as ints (side 2's ref with base_shift added)."""
+    maps = []
+    for ss, sig, ref in ((ss1, sig1, ref1), (ss2, sig2, ref2)):
+        if not ss or ss[-1:].isdigit():
+            raise F1Error("Invalid ss string")
+        m, num = {}, ""
+        for ch in ss.decode("ascii"):
+            if ch.isdigit():
+                num += ch
+                continue
+            if num:
+                n = int(num)
+                if ch == ",":
+                    for _ in range(n):
+                        m[sig] = ref
+                        sig += 1
+                    ref += -1 if rna else 1
+                elif ch == "D":
+                    ref += -n if rna else n
+                elif ch == "I":
+                    for _ in range(n):
+                        m[sig] = -1
+                        sig += 1
+            num = ""
+        if not m:
+            raise F1Error("list index out of range")
+        maps.append(m)
+    tp = fp = tn = fn = 0
+    for sig in sorted(maps[0].keys() & maps[1].keys()):  # both ranges are contiguous: the common keys are the overlap
+        r1, r2 = maps[0][sig], maps[1][sig]
+        if region is not None and (region[0] > r1 + 1 or region[1] < r1 + 1):
+            continue
+        if r1 == -1 and r2 == -1:
+            tn += 1
+        elif r1 == -1:
+            fp += 1
+        elif r2 == -1:
+            fn += 1
+        if abs(r1 - r2) <= threshold:
+            tp += 1
+        else:
+            fp += 1
+    return [tp, fp, tn, fn]
 
 
 def metrics(tp, fp, tn, fn):

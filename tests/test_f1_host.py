@@ -5,6 +5,7 @@ import subprocess
 
 import pytest
 
+import f1_cases
 import f1_ref as R
 from poregen_amd import synth
 
@@ -77,6 +78,44 @@ def test_ss_and_si_errors():
     with pytest.raises(R.F1Error):     # a side that maps no point
         R.pair_counts(b"3D", "0,1,1,1", b"1,", "0,1,1,1")
     assert counts(b"1,", " +0 , 1_0 ,1,1", b"1,", "0,1,1,1") == [1, 0, 0, 0]
+
+
+@pytest.mark.parametrize("case", f1_cases.QUIRKS, ids=[c[0] for c in f1_cases.QUIRKS])
+def test_quirk_table(case):
+    # the table the device suite runs (tests/test_gpu_f1_edges.py): both restatements against the hand-derived counts
+    _, ss1, si1, ss2, si2, kw, want = case
+    assert counts(ss1, si1, ss2, si2, **kw) == want
+    a, b = [R.py_int(v) for v in si1.split(",")], [R.py_int(v) for v in si2.split(",")]
+    assert R.pair_counts_py(ss1, a[0], a[2], ss2, b[0], b[2] + kw.get("base_shift", 0), kw.get("rna", False), kw.get("threshold", 0),
+                            kw.get("region")) == want
+
+
+def test_small_strings_and_the_two_restatements_agree():
+    strings = f1_cases.small_strings()
+    kept = [s for s in strings if f1_cases.maps_a_point(s)]
+    assert (len(strings), len(kept)) == (156, 84)
+    for s in strings:  # the filter is the restatement's own refusal
+        if s in kept:
+            assert R.expand(s, 0, 0, 1)[1].size > 0
+        else:
+            assert R.expand(s, 0, 0, 1)[1].size == 0
+    for i, a in enumerate(kept):
+        b = kept[(7 * i + 3) % len(kept)]
+        for rna, thr, reg, sig2, ref1 in ((False, 0, None, 1, -2), (True, 1, (0, 2), 0, 1)):
+            assert counts(a, f"0,0,{ref1},0", b, f"{sig2},0,0,0", rna=rna, threshold=thr, region=reg) == \
+                R.pair_counts_py(a, 0, ref1, b, sig2, 0, rna, thr, reg)
+
+
+def test_large_magnitude_table():
+    got = [R.pair_counts_py(*p, rna, thr, reg) for p, rna, thr, reg in f1_cases.LARGE]
+    # 0..3: side 1 maps M, M, M + 2^32, then three points at M + 2^33; side 2 M, M, M + 2^32 twice, M + 2^33 twice: only point 3 differs
+    assert got[:4] == [[5, 1, 0, 0]] * 4
+    # 4, 5: point 0: |M - -M| = 2^63 - 2 meets the threshold 2^63 - 1; point 1: M + 1 + 3 (2^32 - 1) against -M is past 2^63. 6: both past 2^62
+    assert got[4:7] == [[1, 1, 0, 0], [1, 1, 0, 0], [0, 2, 0, 0]]
+    # 7: 15 common points, 10 at ref 5 on both sides, 5 against I (FN, then FP); 8: 3 common points; 9, 10: none
+    assert got[7:11] == [[10, 5, 0, 5], [3, 0, 0, 0], [0, 0, 0, 0], [0, 0, 0, 0]]
+    # 11: M - 0 meets the threshold M, M + 1 - 0 misses it; 12: only r1 = M is kept, against M; 13: only r1 = -M - 1, against -M
+    assert got[11:] == [[1, 1, 0, 0], [1, 0, 0, 0], [0, 1, 0, 0]]
 
 
 def rec(name, ss=b"2,", si="0,2,5,7", **kw):
