@@ -49,6 +49,11 @@
  * pg_kfreq_create / pg_kfreq_destroy  the generated 4^k keys at zero and the map   src/kmer_freq.cpp:148-157
  * pg_kfreq_submit                  the getline loop over the FASTQ: lines, the     src/kmer_freq.cpp:160-181
  *                                  sequence-line test, one map increment per window
+ * pg_kfreq_submit_reads            the same loop over the FASTQ that `samtools fastq` README.md STEP 2
+ *                                  (and `sed '2~4s/N/T/g'`) would print from a batch
+ *                                  of BAM records, without the text: the records'
+ *                                  packed sequence fields are the input
+ * pg_kfreq_reads_piece             (no counterpart)
  * pg_kfreq_finish                  the map's contents (dense ACGT counts + the     src/kmer_freq.cpp:189-192
  *                                  other keys in byte order); sorting and printing,
  *                                  :194-220, stay with the caller
@@ -474,6 +479,21 @@ const char *pg_kfreq_last_error(const pg_kfreq *h); /* h may be NULL: error of t
  * from directly, other memory through two pinned staging buffers). PG_LOC_DEVICE: memory of the handle's device, complete before the
  * call; it is read in place and must stay unchanged until pg_kfreq_sync or pg_kfreq_finish. */
 pg_status pg_kfreq_submit(pg_kfreq *h, const void *data, uint64_t n_bytes, int32_t location);
+/* The stream's other input form: n_reads reads as a BAM record stores its sequence, two 4-bit codes per byte ("=ACMGRSVTWYHKDBN",
+ * high nibble first). Read r is l_seq[r] bases from byte byte_off[r] of seq_bytes (any offset; reads may lie anywhere in the
+ * n_seq_bytes bytes, so a run of whole BAM records can be passed as it is); the low nibble of the last byte of an odd-length read is
+ * padding and never read as a base. Each read counts as one FASTQ sequence line: l_seq - kmer_size + 1 windows, none if it is shorter;
+ * ACGT windows densely, any other window as an odd key of its letters. reverse[r] != 0: the read is counted as `samtools fastq` prints
+ * a record with flag 0x10, bases in reverse order and every code complemented (its four bits reversed: A<->T, C<->G, M<->K, R<->Y,
+ * V<->B, H<->D; '=', S, W, N stay). flags: PG_KFREQ_N_TO_T counts code 15 (N) of the printed read as T (sed '2~4s/N/T/g'); other
+ * ambiguity codes stay. The result equals pg_kfreq_submit on the FASTQ text of the reads with every line '\n'-terminated.
+ * One stream (up to the next finish) takes one form: a submit_reads after a submit, or a submit after a submit_reads, returns
+ * PG_ERR_INVALID_ARG and counts nothing. location as for pg_kfreq_submit, for all four arrays; host arrays are free for reuse when the
+ * call returns. Long reads are cut into pieces of pg_kfreq_reads_piece(h) windows, one wave of the device each. */
+enum { PG_KFREQ_N_TO_T = 1 };
+pg_status pg_kfreq_submit_reads(pg_kfreq *h, const uint8_t *seq_bytes, uint64_t n_seq_bytes, const uint64_t *byte_off, const uint32_t *l_seq,
+                                const uint8_t *reverse, uint64_t n_reads, uint32_t flags, int32_t location);
+uint32_t  pg_kfreq_reads_piece(const pg_kfreq *h);
 pg_status pg_kfreq_sync(pg_kfreq *h);
 /* End of stream (the window ending on its last byte is dropped: the unterminated-final-line rule). counts_out: host u64[4^kmer_size].
  * The handle is reset afterwards, also after an error: the next submit starts a new stream. */

@@ -46,8 +46,6 @@ namespace {
 int64_t end_of(int64_t pos, uint32_t flag, int64_t rlen) { return pos + ((flag & 4) || rlen == 0 ? 1 : rlen); }
 bool ref_op(int op) { return op == 0 || op == 2 || op == 3 || op == 7 || op == 8; }
 
-struct Block { size_t off, hdr, clen, out; uint32_t isize; };
-
 } // namespace
 
 bool AlnFile::load(const std::string &path, unsigned threads, std::string &err) {
@@ -128,16 +126,15 @@ bool AlnFile::parse_sam(std::string &err) {
     return true;
 }
 
-bool AlnFile::parse_bam(unsigned threads, std::string &err) {
-    // 1. the blocks: compressed extent and inflated size, from the headers and footers alone
-    std::vector<Block> blocks;
-    size_t total = 0;
-    for (size_t pos = 0; pos < f_.size;) {
-        if (f_.size - pos < 18) { err = "corrupt BGZF block"; return false; }
-        const unsigned char *b = (const unsigned char *)f_.data + pos;
+bool bgzf_scan(const char *data, size_t size, size_t &pos, size_t want, std::vector<BgzfBlock> &blocks, size_t &total, std::string &err) {
+    blocks.clear();
+    total = 0;
+    while (pos < size && total < want) {
+        if (size - pos < 18) { err = "corrupt BGZF block"; return false; }
+        const unsigned char *b = (const unsigned char *)data + pos;
         if (b[0] != 0x1f || b[1] != 0x8b || !(b[3] & 4)) { err = "corrupt BGZF block"; return false; }
         uint16_t xlen; memcpy(&xlen, b + 10, 2);
-        if (12u + (size_t)xlen > f_.size - pos) { err = "corrupt BGZF block"; return false; }
+        if (12u + (size_t)xlen > size - pos) { err = "corrupt BGZF block"; return false; }
         uint32_t bsize = 0; bool found = false;
         for (size_t o = 12; o + 4 <= 12u + xlen;) {
             uint16_t slen; memcpy(&slen, b + o + 2, 2);
@@ -145,15 +142,17 @@ bool AlnFile::parse_bam(unsigned threads, std::string &err) {
             o += 4u + slen;
         }
         const size_t hdr = 12u + xlen;
-        if (!found || bsize > f_.size - pos || bsize < hdr + 8) { err = "corrupt BGZF block"; return false; }
+        if (!found || bsize > size - pos || bsize < hdr + 8) { err = "corrupt BGZF block"; return false; }
         uint32_t isize; memcpy(&isize, b + bsize - 4, 4);
         if (isize > 65536u) { err = "corrupt BGZF block"; return false; }
-        blocks.push_back(Block{pos, hdr, bsize - hdr - 8, total, isize});
+        blocks.push_back(BgzfBlock{pos, hdr, bsize - hdr - 8, total, isize});
         total += isize;
         pos += bsize;
     }
-    // 2. inflate them in parallel, each to its offset
-    text_.resize(total);
+    return true;
+}
+
+bool bgzf_inflate(const char *data, const std::vector<BgzfBlock> &blocks, char *out, unsigned threads, std::string &err) {
     std::atomic<size_t> next{0};
     std::atomic<bool> bad{false};
     auto work = [&]() {
@@ -161,11 +160,11 @@ bool AlnFile::parse_bam(unsigned threads, std::string &err) {
         if (inflateInit2(&zs, -15) != Z_OK) { bad = true; return; }
         for (size_t i; !bad && (i = next.fetch_add(64)) < blocks.size();) {
             for (size_t k = i; k < std::min(blocks.size(), i + 64); k++) {
-                const Block &bl = blocks[k];
+                const BgzfBlock &bl = blocks[k];
                 if (!bl.isize) continue;
                 if (inflateReset(&zs) != Z_OK) { bad = true; break; }
-                zs.next_in = (Bytef *)(f_.data + bl.off + bl.hdr); zs.avail_in = (uInt)bl.clen;
-                zs.next_out = (Bytef *)text_.data() + bl.out; zs.avail_out = bl.isize;
+                zs.next_in = (Bytef *)(data + bl.off + bl.hdr); zs.avail_in = (uInt)bl.clen;
+                zs.next_out = (Bytef *)out + bl.out; zs.avail_out = bl.isize;
                 if (inflate(&zs, Z_FINISH) != Z_STREAM_END || zs.avail_out != 0) { bad = true; break; }
             }
         }
@@ -177,6 +176,17 @@ bool AlnFile::parse_bam(unsigned threads, std::string &err) {
     work();
     for (auto &t : pool) t.join();
     if (bad) { err = "zlib error in BGZF block"; return false; }
+    return true;
+}
+
+bool AlnFile::parse_bam(unsigned threads, std::string &err) {
+    // 1. the blocks: compressed extent and inflated size, from the headers and footers alone
+    std::vector<BgzfBlock> blocks;
+    size_t total = 0, pos = 0;
+    if (!bgzf_scan(f_.data, f_.size, pos, SIZE_MAX, blocks, total, err)) return false;
+    // 2. inflate them in parallel, each to its offset
+    text_.resize(total);
+    if (!bgzf_inflate(f_.data, blocks, text_.data(), threads, err)) return false;
     // 3. header and records
     const char *d = text_.data();
     size_t p = 0;

@@ -14,9 +14,14 @@
 //   * the keys are the 4^k generated ACGT k-mers at 0 plus every other window met, in std::map order = unsigned byte order
 //     (:148-157, :185-192); --sort 1: count ascending then key ascending, --sort 2: count descending then key descending
 //     (:194-212); --print_absent_kmers 0 drops zero counts (:215-219); one line "%s\t%" PRIu64 "\n" per key (:220).
+// Beyond the reference: a file named *.bam or *.sam (the suffix test of gmove_cli.cpp) is read as the basecaller's BAM / SAM, and its
+// reads are counted as the FASTQ that `samtools fastq FILE` would print (flags 0x100 / 0x800 skipped, flag 0x10 reverse-complemented;
+// host/kfreq_reads.cpp, pg_kfreq_submit_reads); --n_to_t adds the workflow's `sed '2~4s/N/T/g'` (README.md STEP 2 of the reference) and
+// is refused for FASTQ input. Any other name is FASTQ, as before.
 // Refused (exit 1, DESIGN.md "kmer_freq"): kmer_size outside 1..12 (the reference recurses without end for negative values,
 // prints one empty key for 0, and needs gigabytes of strings above 12), and a NUL byte in a sequence line (PG_ERR_INPUT).
 #include "../../../include/pgmove.h"
+#include "pg_kfreq_host.h"
 
 #include <algorithm>
 #include <cerrno>
@@ -44,13 +49,15 @@ const struct option kLongOptions[] = {
     {"version", no_argument, nullptr, 'V'},                // 3
     {"output", required_argument, nullptr, 'o'},           // 4
     {"debug-break", required_argument, nullptr, 0},        // 5
+    {"n_to_t", no_argument, nullptr, 0},                   // 6 (not in the reference: appended, the indices above keep their meaning)
     {nullptr, 0, nullptr, 0}};
 
 void print_help(FILE *fp) { // src/kmer_freq.cpp:30-42
-    fprintf(fp, "Usage: poregen kmer_freq kmer_size reads.fastq\n");
+    fprintf(fp, "Usage: poregen kmer_freq kmer_size reads.fastq|reads.bam|reads.sam\n");
     fprintf(fp, "\nbasic options:\n");
     fprintf(fp, "   --sort INT                 sort based on frequency (0-no sorting, 1-ascend, 2-descend) [0] \n");
     fprintf(fp, "   --print_absent_kmers INT   print kmers with 0 frequency (0-do not print, 1-print) [1] \n");
+    fprintf(fp, "   --n_to_t                   count N as T, as sed '2~4s/N/T/g' on the FASTQ would (.bam / .sam input only)\n");
     fprintf(fp, "   -o FILE                    output to file [stdout]\n");
     fprintf(fp, "   --verbose INT              verbosity level [%d]\n", g_log_level);
     fprintf(fp, "   --version                  print version\n");
@@ -112,6 +119,7 @@ uint64_t piece_bytes() {
 int kmer_freq_main(int argc, char **argv) {
     int c, longindex = 0;
     int flag_sort = 0, flag_print_absent = 1;
+    bool n_to_t = false;
     bool help_to_stdout = false;
     const char *out_path = nullptr;
     optind = 1;
@@ -128,12 +136,19 @@ int kmer_freq_main(int argc, char **argv) {
             const int v = atoi(optarg);
             if (v != 0 && v != 1) { KF_ERROR("print_absent_kmers flag must be 0 or 1 You entered %d", v); exit(EXIT_FAILURE); }
             flag_print_absent = v;
-        }
+        } else if (c == 0 && longindex == 6) n_to_t = true;
         // longindex 5 (debug-break): accepted, no effect (the reference reads it at longindex 4)
     }
     if (argc - optind != 2 || help_to_stdout) {
         print_help(help_to_stdout ? stdout : stderr);
         exit(help_to_stdout ? EXIT_SUCCESS : EXIT_FAILURE);
+    }
+    const std::string in_name(argv[optind + 1]);
+    const std::string ext = in_name.size() >= 4 ? in_name.substr(in_name.size() - 4) : "";
+    const bool is_bam = ext == ".bam", is_reads = is_bam || ext == ".sam";
+    if (n_to_t && !is_reads) {
+        KF_ERROR("--n_to_t applies to .bam and .sam input only (for a FASTQ: sed '2~4s/N/T/g') You entered %s", in_name.c_str());
+        exit(EXIT_FAILURE);
     }
     FILE *out = stdout;
     if (out_path) {
@@ -153,6 +168,12 @@ int kmer_freq_main(int argc, char **argv) {
 
     FILE *in = fopen(fastq, "r");
     if (!in) { fprintf(stderr, "Error in opening file %s\n", fastq); exit(EXIT_FAILURE); }
+    pgh::PackedReads reads;
+    if (is_reads) {
+        fclose(in);
+        std::string err;
+        if (!reads.open(fastq, is_bam, err)) { KF_ERROR("%s: %s", fastq, err.c_str()); exit(EXIT_FAILURE); }
+    }
 
     pg_kfreq *h = nullptr;
     if (pg_kfreq_create(k, 0, &h) != PG_OK) {
@@ -160,14 +181,26 @@ int kmer_freq_main(int argc, char **argv) {
         exit(EXIT_FAILURE);
     }
     const uint64_t piece = piece_bytes();
-    std::vector<uint8_t> buf(piece);
-    for (;;) {
-        const size_t got = fread(buf.data(), 1, piece, in);
-        if (got && pg_kfreq_submit(h, buf.data(), got, PG_LOC_HOST) != PG_OK) { KF_ERROR("%s", pg_kfreq_last_error(h)); exit(EXIT_FAILURE); }
-        if (got < piece) break;
+    if (is_reads) {
+        // a batch is on the device's side when submit_reads returns: the next one is inflated and parsed while it is counted
+        pgh::PackedBatch b;
+        std::string err;
+        int rc;
+        while ((rc = reads.next(b, piece, err)) == 1) {
+            if (pg_kfreq_submit_reads(h, b.seq.data(), b.seq.size(), b.off.data(), b.len.data(), b.rev.data(), b.len.size(),
+                                      n_to_t ? PG_KFREQ_N_TO_T : 0, PG_LOC_HOST) != PG_OK) { KF_ERROR("%s", pg_kfreq_last_error(h)); exit(EXIT_FAILURE); }
+        }
+        if (rc < 0) { KF_ERROR("%s: %s", fastq, err.c_str()); exit(EXIT_FAILURE); }
+    } else {
+        std::vector<uint8_t> buf(piece);
+        for (;;) {
+            const size_t got = fread(buf.data(), 1, piece, in);
+            if (got && pg_kfreq_submit(h, buf.data(), got, PG_LOC_HOST) != PG_OK) { KF_ERROR("%s", pg_kfreq_last_error(h)); exit(EXIT_FAILURE); }
+            if (got < piece) break;
+        }
+        if (ferror(in)) { KF_ERROR("reading %s: %s", fastq, strerror(errno)); exit(EXIT_FAILURE); }
+        fclose(in);
     }
-    if (ferror(in)) { KF_ERROR("reading %s: %s", fastq, strerror(errno)); exit(EXIT_FAILURE); }
-    fclose(in);
     std::vector<uint64_t> counts(n_codes);
     pg_kfreq_result r;
     if (pg_kfreq_finish(h, counts.data(), &r) != PG_OK) { KF_ERROR("%s: %s", fastq, pg_kfreq_last_error(h)); exit(EXIT_FAILURE); }

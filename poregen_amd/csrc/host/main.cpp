@@ -31,7 +31,7 @@ static double cputime() { struct rusage r; getrusage(RUSAGE_SELF, &r); return r.
 static long peakrss() { struct rusage r; getrusage(RUSAGE_SELF, &r); return r.ru_maxrss * 1024; }
 
 static int usage(FILE *fp, int code) {
-    fprintf(fp, "Usage: poregen <command> [options]\n\ncommand:\n         gmove      move k-mer signal samples into k-mer buckets (MI355X implementation)\n         reform     rewrite a SAM/BAM move table as TSV or as PAF with ss:Z:\n         kmer_freq  count the k-mers of the reads in a FASTQ file\n         f1_score   compare two ss signal alignments (SAM/BAM) point by point: TP/FP/TN/FN, F1 score\n         subtool0   mean pA of every read of a SLOW5/BLOW5 file\n         pa_stats   mean and sample standard deviation of every pA value of a SLOW5/BLOW5 file\n         model      k-mer model (median, stddev, dwell) from the files of dump directories\n         transform  the final model file from a raw k-mer model: (median * stdv) + mean, stddev projected onto [2.5, 4]\n");
+    fprintf(fp, "Usage: poregen <command> [options]\n\ncommand:\n         gmove      move k-mer signal samples into k-mer buckets (MI355X implementation)\n         reform     rewrite a SAM/BAM move table as TSV or as PAF with ss:Z:\n         kmer_freq  count the k-mers of the reads in a FASTQ, BAM or SAM file\n         f1_score   compare two ss signal alignments (SAM/BAM) point by point: TP/FP/TN/FN, F1 score\n         subtool0   mean pA of every read of a SLOW5/BLOW5 file\n         pa_stats   mean and sample standard deviation of every pA value of a SLOW5/BLOW5 file\n         model      k-mer model (median, stddev, dwell) from the files of dump directories\n         transform  the final model file from a raw k-mer model: (median * stdv) + mean, stddev projected onto [2.5, 4]\n");
     return code;
 }
 

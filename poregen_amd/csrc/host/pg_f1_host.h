@@ -35,6 +35,14 @@ private:
     bool parse_bam(unsigned threads, std::string &err);
 };
 
+// The BGZF layer of that reader, for callers that take a BAM file piece by piece (kmer_freq). bgzf_scan walks the block headers and
+// footers from file offset `pos` until the blocks found inflate to `want` bytes or more, or the file ends (`pos` moves behind the last
+// block taken; `out` of a block is its place among the bytes of this scan); bgzf_inflate inflates them to out + block.out on up to
+// `threads` threads, 16 at most.
+struct BgzfBlock { size_t off, hdr, clen, out; uint32_t isize; };
+bool bgzf_scan(const char *data, size_t size, size_t &pos, size_t want, std::vector<BgzfBlock> &blocks, size_t &total, std::string &err);
+bool bgzf_inflate(const char *data, const std::vector<BgzfBlock> &blocks, char *out, unsigned threads, std::string &err);
+
 // Python's int(str) for base 10 on ASCII text: surrounding whitespace, one sign, digits with single '_' between them.
 // Returns 0 ok, 1 not an integer (Python's ValueError), 2 a magnitude of 2^62 or more (valid, but refused here).
 int parse_py_int(std::string_view s, int64_t &out);

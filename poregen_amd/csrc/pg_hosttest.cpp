@@ -270,3 +270,9 @@ extern "C" long pgt_dump_model_host(const char *const *dirs, size_t n_dirs, int 
     if (out && cap) { const size_t n = text.size() < cap - 1 ? text.size() : cap - 1; memcpy(out, text.data(), n); out[n] = 0; }
     return (long)text.size();
 }
+
+// ---- kmer_freq on SAM/BAM input (pg_kfreq_codes.h): the 4-bit code htslib packs for a byte of SEQ, a code's letter and its complement --
+#include "pg_kfreq_codes.h"
+extern "C" int pgt_kf_code_of_byte(int byte) { return (int)pg_kf_code_of_byte((uint32_t)byte & 0xff); }
+extern "C" int pgt_kf_letter(int code) { return (int)pg_kf_letter((uint32_t)code & 15); }
+extern "C" int pgt_kf_complement(int code) { return (int)pg_kf_complement((uint32_t)code & 15); }

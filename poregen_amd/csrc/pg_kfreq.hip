@@ -18,9 +18,17 @@
 //                that straddle the previous unit (the "seam") and writes the next unit's carried state (line index mod 4, the
 //                open line's last <= k bytes) into the other slot of a two-slot state: no host round trip between units.
 // Equal codes a thread meets back to back (homopolymers) are added once, as a run.
+//
+// Second input form, pg_kfreq_submit_reads: reads as a BAM record stores them, two 4-bit codes per byte (pg_kfreq_codes.h), each read a
+// sequence line of its own. No lines to find, so one launch per submit (or per h->unit windows of it):
+//   k_kf_reads : one wave per piece of at most `piece` window starts of one read (the host lists the pieces; neighbours overlap by the
+//                k - 1 bases a window spans), the piece's windows spread evenly over the 64 lanes, each lane rolling over its share plus
+//                k - 1 bases of warm-up with 8-byte loads. A read with the reverse flag is walked as stored and the window formed as
+//                `samtools fastq` prints it: codes complemented, newest base most significant. Same histograms, same odd list.
 #include "../../include/pgmove.h"
 #include <hip/hip_runtime.h>
 #include "pg_hip_host.h"
+#include "pg_kfreq_codes.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -303,6 +311,104 @@ __global__ __launch_bounds__(kThreads) void k_kf_count(KfDev d, const uint8_t *_
     }
 }
 
+// ---- packed reads ---------------------------------------------------------------------------------------------------------------
+constexpr uint32_t kReadPiece = 4096;            // window starts per wave of work: 64 per lane
+constexpr uint32_t kReadBlocks = 512;            // workgroups of a launch at most (two per CU); waves stride over the pieces
+constexpr uint32_t kMaxReadLen = 0x7fffffffu;    // BAM's l_seq is an int32
+
+struct KfReads {
+    const uint8_t *seq;      // n_bytes bytes; read r starts at byte off[r], high nibble first
+    uint64_t n_bytes;
+    const uint64_t *off;
+    const uint32_t *len;
+    const uint8_t *rev;
+    const uint2 *work;       // (read, piece) of every piece of this launch
+    uint32_t n_work, piece, n_to_t;
+};
+
+template <bool kAligned>
+__device__ __forceinline__ uint64_t load8(const uint8_t *__restrict__ p, uint64_t o, uint64_t n) {
+    if (kAligned && o + 8 <= n) return *reinterpret_cast<const unsigned long long *>(p + o);
+    uint64_t x = 0;
+    for (int b = 0; b < 8; b++) if (o + b < n) x |= (uint64_t)p[o + b] << (8 * b);
+    return x;
+}
+
+__device__ __forceinline__ uint4 odd_key_rev(uint64_t lo, uint32_t hi, uint32_t k) {
+    // the window read backwards: byte i of the key is i bytes older than the newest
+    uint32_t key[4] = {0, 0, 0, 0};
+    for (uint32_t i = 0; i < k; i++) {
+        const uint32_t b = i < 8 ? (uint32_t)(lo >> (8 * i)) & 0xff : (hi >> (8 * (i - 8))) & 0xff;
+        key[i >> 2] |= b << (8 * (i & 3));
+    }
+    return make_uint4(key[0], key[1], key[2], key[3]);
+}
+
+template <bool kAligned, bool kLds>
+__global__ __launch_bounds__(kThreads) void k_kf_reads(KfDev d, KfReads in, uint32_t k) {
+    extern __shared__ uint32_t lds_hist[];
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    const uint32_t n_codes = 1u << (2 * k), mask = n_codes - 1, top = 2 * (k - 1);
+    if (kLds) {
+        for (uint32_t i = tid; i < n_codes; i += kThreads) lds_hist[i] = 0;
+        __syncthreads();
+    }
+    constexpr uint32_t kWaves = kThreads / 64;
+    uint32_t run_code = 0, run_cnt = 0; // the open run lives across pieces
+    for (uint32_t w = blockIdx.x * kWaves + (tid >> 6); w < in.n_work; w += gridDim.x * kWaves) {
+        const uint2 it = in.work[w];
+        const uint32_t len = in.len[it.x];
+        const bool rev = in.rev[it.x] != 0;
+        const uint64_t nib0 = in.off[it.x] * 2; // the read's first base, counted in nibbles from seq
+        if (len < k) continue;
+        const uint32_t n_win = len - k + 1;
+        const uint64_t ws = (uint64_t)it.y * in.piece;
+        if (ws >= n_win) continue;
+        const uint32_t we = (uint32_t)min<uint64_t>(n_win, ws + in.piece);
+        const uint32_t span = (we - (uint32_t)ws + 63) / 64;
+        const uint64_t a = ws + (uint64_t)lane * span;           // this lane's window starts: [a, b)
+        if (a >= we) continue;
+        const uint64_t b = min<uint64_t>(we, a + span);
+        uint64_t cur = 0, lo = 0;
+        uint32_t hi = 0, run = 0, code = 0;
+        for (uint64_t j = a; j < b + k - 1; j++) {               // bases [a, b + k - 1) of the read as stored: below len
+            const uint64_t q = nib0 + j;
+            if (j == a || (q & 15) == 0) cur = load8<kAligned>(in.seq, (q >> 4) << 3, in.n_bytes);
+            uint32_t c = (uint32_t)(cur >> (4 * ((q & 15) ^ 1))) & 15;
+            if (rev) c = pg_kf_complement(c);
+            if (in.n_to_t && c == 15) c = 8;
+            const bool acgt = c != 0 && (c & (c - 1)) == 0;      // exactly one base
+            const uint32_t b2 = acgt ? (uint32_t)__ffs((int)c) - 1 : 0;
+            run = acgt ? run + 1 : 0;
+            code = rev ? (code >> 2) | (b2 << top) : ((code << 2) | b2) & mask;
+            hi = (hi << 8) | (uint32_t)(lo >> 56); lo = (lo << 8) | pg_kf_letter(c);
+            if (j - a + 1 >= k) {
+                if (run >= k) {
+                    if (code == run_code) run_cnt++;
+                    else { add_run<kLds>(d, lds_hist, run_code, run_cnt); run_code = code; run_cnt = 1; }
+                } else {
+                    emit_odd(d, rev ? odd_key_rev(lo, hi, k) : odd_key(lo, hi, k));
+                }
+            }
+        }
+    }
+    // as in k_kf_count: a wave whose open runs all share one code adds their sum from one lane
+    const uint32_t c0 = __builtin_amdgcn_readfirstlane(run_code);
+    const bool lone = __ballot(run_cnt != 0 && run_code != c0) != 0;
+    if (lone) {
+        add_run<kLds>(d, lds_hist, run_code, run_cnt);
+    } else {
+        uint32_t sum = run_cnt;
+        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+        if (lane == 0) add_run<kLds>(d, lds_hist, c0, sum);
+    }
+    if (kLds) {
+        __syncthreads();
+        for (uint32_t i = tid; i < n_codes; i += kThreads)
+            if (const uint32_t v = lds_hist[i]) atomicAdd(&d.hist[i], (unsigned long long)v);
+    }
+}
+
 struct OddKey {
     uint32_t w[4];
     bool operator==(const OddKey &o) const { return memcmp(w, o.w, sizeof w) == 0; }
@@ -341,6 +447,14 @@ struct pg_kfreq {
     std::vector<uint8_t> out_keys;
     std::vector<uint64_t> out_counts;
     bool aligned_stage = true;
+    // packed reads: what one submit uploads (sequence bytes, offsets, lengths, flags, the piece list) as one block, two in rotation
+    int form = 0;              // the stream's input form: 0 none yet, 1 text, 2 reads
+    uint32_t piece = kReadPiece; // <= unit
+    PgPinned<uint8_t> r_stage[2];
+    PgDev<uint8_t> r_dev[2];
+    std::vector<uint64_t> r_off;   // PG_LOC_DEVICE: the caller's offsets and lengths, brought over to plan the pieces
+    std::vector<uint32_t> r_len;
+    std::vector<uint2> r_work;
     std::string err;
 };
 
@@ -389,6 +503,15 @@ static pg_status kf_reserve(pg_kfreq *h, uint64_t n) {
     return PG_OK;
 }
 
+// behind a launch of at most n windows: the odd list's fill as of its end, on its way to the host
+static pg_status kf_snapshot(pg_kfreq *h, uint64_t n) {
+    const int slot = h->snap_next; h->snap_next = (h->snap_next + 1) % kSnapRing;
+    PG_HIP_TRY(h, hipMemcpyAsync(&h->snap.p[slot], h->d.odd_n, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->ks));
+    PG_HIP_TRY(h, hipEventRecord(h->snap_ev[slot], h->ks));
+    h->pending.push_back({slot, n});
+    return PG_OK;
+}
+
 // one unit of at most kUnit bytes, resident on the device, complete on the count stream's side
 static pg_status kf_unit(pg_kfreq *h, const uint8_t *p, uint64_t n) {
     if (!n) return PG_OK;
@@ -405,11 +528,7 @@ static pg_status kf_unit(pg_kfreq *h, const uint8_t *p, uint64_t n) {
     else hipLaunchKernelGGL((k_kf_count<false, false>), dim3(n_tiles), dim3(kThreads), 0, h->ks, h->d, p, n, n_tiles, h->k, h->par);
     PG_HIP_TRY(h, hipGetLastError());
     h->par ^= 1;
-    const int slot = h->snap_next; h->snap_next = (h->snap_next + 1) % kSnapRing;
-    PG_HIP_TRY(h, hipMemcpyAsync(&h->snap.p[slot], h->d.odd_n, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->ks));
-    PG_HIP_TRY(h, hipEventRecord(h->snap_ev[slot], h->ks));
-    h->pending.push_back({slot, n});
-    return PG_OK;
+    return kf_snapshot(h, n);
 }
 
 static pg_status kf_reset_device(pg_kfreq *h) {
@@ -419,6 +538,7 @@ static pg_status kf_reset_device(pg_kfreq *h) {
     PG_HIP_TRY(h, hipMemsetAsync(h->d.state, 0, 2 * sizeof(KfState), h->ks));
     PG_HIP_TRY(h, hipStreamSynchronize(h->ks));
     h->par = 0;
+    h->form = 0;
     h->pending.clear();
     h->odd_known = 0;
     h->odd_map.clear();
@@ -438,6 +558,7 @@ pg_status pg_kfreq_create(uint32_t kmer_size, int32_t device, pg_kfreq **out) {
     h->k = kmer_size; h->n_codes = 1u << (2 * kmer_size); h->device = device;
     h->d.odd_cap = odd_cap_from_env();
     h->unit = std::min<uint64_t>(kUnit, h->d.odd_cap);
+    h->piece = (uint32_t)std::min<uint64_t>(kReadPiece, h->unit);
     auto init = [&]() -> pg_status {
         PG_HIP_TRY(h, hipStreamCreateWithFlags(&h->ks.h, hipStreamNonBlocking));
         PG_HIP_TRY(h, hipStreamCreateWithFlags(&h->cs.h, hipStreamNonBlocking));
@@ -471,6 +592,9 @@ pg_status pg_kfreq_submit(pg_kfreq *h, const void *data, uint64_t n_bytes, int32
     if (!h) return pg_fail<pg_kfreq>(nullptr, PG_ERR_INVALID_ARG, "pg_kfreq_submit: null handle");
     if (!n_bytes) return PG_OK;
     if (!data) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit: null data");
+    if (h->form == 2) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit: this stream holds packed reads (one input form per stream)");
+    if (location != PG_LOC_HOST && location != PG_LOC_DEVICE) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit: location must be PG_LOC_HOST or PG_LOC_DEVICE");
+    h->form = 1;
     PG_HIP_TRY(h, hipSetDevice(h->device));
     const uint8_t *src = static_cast<const uint8_t *>(data);
     if (location == PG_LOC_DEVICE) {
@@ -507,6 +631,103 @@ pg_status pg_kfreq_submit(pg_kfreq *h, const void *data, uint64_t n_bytes, int32
     }
     // the caller may reuse its (page-locked) buffer once submit returns
     if (pinned) PG_HIP_TRY(h, hipStreamSynchronize(h->cs));
+    return PG_OK;
+}
+
+uint32_t pg_kfreq_reads_piece(const pg_kfreq *h) { return h ? h->piece : 0; }
+
+pg_status pg_kfreq_submit_reads(pg_kfreq *h, const uint8_t *seq_bytes, uint64_t n_seq_bytes, const uint64_t *byte_off, const uint32_t *l_seq,
+                                const uint8_t *reverse, uint64_t n_reads, uint32_t flags, int32_t location) {
+    if (!h) return pg_fail<pg_kfreq>(nullptr, PG_ERR_INVALID_ARG, "pg_kfreq_submit_reads: null handle");
+    if (h->form == 1) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit_reads: this stream holds FASTQ text (one input form per stream)");
+    if (flags & ~(uint32_t)PG_KFREQ_N_TO_T) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit_reads: unknown flags 0x%x", flags);
+    if (location != PG_LOC_HOST && location != PG_LOC_DEVICE) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit_reads: location must be PG_LOC_HOST or PG_LOC_DEVICE");
+    if (!n_reads) return PG_OK;
+    if (n_reads > 0xffffffffull) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit_reads: %llu reads in one call (at most 2^32 - 1)", (unsigned long long)n_reads);
+    if (!byte_off || !l_seq || !reverse || (n_seq_bytes && !seq_bytes)) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit_reads: null array");
+    PG_HIP_TRY(h, hipSetDevice(h->device));
+    const bool dev = location == PG_LOC_DEVICE;
+    const uint64_t *off = byte_off;
+    const uint32_t *len = l_seq;
+    if (dev) {
+        const void *arrs[4] = {byte_off, l_seq, reverse, seq_bytes};
+        for (int i = 0; i < 4; i++)
+            if ((i < 3 || n_seq_bytes) && pg_ptr_kind(arrs[i], h->device) != PG_PTR_DEVICE)
+                return pg_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit_reads: PG_LOC_DEVICE arrays must be device memory of device %d", h->device);
+        h->r_off.resize(n_reads); h->r_len.resize(n_reads);
+        PG_HIP_TRY(h, hipMemcpy(h->r_off.data(), byte_off, n_reads * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        PG_HIP_TRY(h, hipMemcpy(h->r_len.data(), l_seq, n_reads * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        off = h->r_off.data(); len = h->r_len.data();
+    }
+    // every read inside seq_bytes; the pieces of the reads that hold a window, and where the launches are cut (h->unit windows at most)
+    const uint32_t k = h->k, piece = h->piece;
+    h->r_work.clear();
+    std::vector<std::pair<size_t, uint64_t>> cuts; // (end in r_work, windows) per launch
+    uint64_t seg = 0;
+    for (uint64_t r = 0; r < n_reads; r++) {
+        const uint64_t n = len[r];
+        if (n > kMaxReadLen) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit_reads: read %llu has %llu bases (at most 2^31 - 1)", (unsigned long long)r, (unsigned long long)n);
+        if (off[r] > n_seq_bytes || (n + 1) / 2 > n_seq_bytes - off[r])
+            return pg_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit_reads: read %llu lies outside seq_bytes", (unsigned long long)r);
+        if (n < k) continue;
+        const uint64_t n_win = n - k + 1;
+        for (uint64_t p = 0; p * piece < n_win; p++) {
+            const uint64_t m = std::min<uint64_t>(piece, n_win - p * piece);
+            if (seg + m > h->unit) { cuts.emplace_back(h->r_work.size(), seg); seg = 0; }
+            h->r_work.push_back(make_uint2((uint32_t)r, (uint32_t)p));
+            seg += m;
+        }
+    }
+    h->form = 2;
+    if (h->r_work.empty()) return PG_OK;
+    cuts.emplace_back(h->r_work.size(), seg);
+    // the block: [sequence bytes | offsets | piece list | lengths | flags], each part 16-byte aligned; device input uploads the list alone
+    auto up16 = [](uint64_t x) { return (x + 15) & ~15ull; };
+    const uint64_t o_off = dev ? 0 : up16(n_seq_bytes), o_work = dev ? 0 : o_off + up16(n_reads * sizeof(uint64_t));
+    const uint64_t o_len = o_work + up16(h->r_work.size() * sizeof(uint2)), o_rev = dev ? o_len : o_len + up16(n_reads * sizeof(uint32_t));
+    const uint64_t total = dev ? o_len : o_rev + up16(n_reads);
+    const int b = h->next_buf; h->next_buf ^= 1;
+    PG_HIP_TRY(h, hipEventSynchronize(h->copied[b]));  // the staging block's previous copy is done
+    PG_HIP_TRY(h, h->r_stage[b].ensure(total, total + total / 4));
+    if (total > h->r_dev[b].cap) PG_HIP_TRY(h, hipEventSynchronize(h->counted[b])); // about to be freed: its last launch is over
+    PG_HIP_TRY(h, h->r_dev[b].ensure(total, total + total / 4));
+    uint8_t *st = h->r_stage[b].p;
+    if (!dev) {
+        if (n_seq_bytes) memcpy(st, seq_bytes, n_seq_bytes);
+        memcpy(st + o_off, byte_off, n_reads * sizeof(uint64_t));
+        memcpy(st + o_len, l_seq, n_reads * sizeof(uint32_t));
+        memcpy(st + o_rev, reverse, n_reads);
+    }
+    memcpy(st + o_work, h->r_work.data(), h->r_work.size() * sizeof(uint2));
+    PG_HIP_TRY(h, hipStreamWaitEvent(h->cs, h->counted[b], 0)); // the device block's previous launches are over
+    PG_HIP_TRY(h, hipMemcpyAsync(h->r_dev[b].p, st, total, hipMemcpyHostToDevice, h->cs));
+    PG_HIP_TRY(h, hipEventRecord(h->copied[b], h->cs));
+    PG_HIP_TRY(h, hipStreamWaitEvent(h->ks, h->copied[b], 0));
+    const uint8_t *base = h->r_dev[b].p;
+    KfReads in{};
+    in.seq = dev ? seq_bytes : base; in.n_bytes = n_seq_bytes;
+    in.off = dev ? byte_off : reinterpret_cast<const uint64_t *>(base + o_off);
+    in.len = dev ? l_seq : reinterpret_cast<const uint32_t *>(base + o_len);
+    in.rev = dev ? reverse : base + o_rev;
+    in.piece = piece; in.n_to_t = flags & PG_KFREQ_N_TO_T ? 1 : 0;
+    const bool al = ((uintptr_t)in.seq & 7) == 0;
+    const bool lds = k <= kLdsMaxK;
+    const size_t lds_bytes = lds ? (size_t)h->n_codes * sizeof(uint32_t) : 0;
+    size_t w0 = 0;
+    for (const auto &cut : cuts) {
+        if (pg_status s = kf_reserve(h, cut.second)) return s;
+        in.work = reinterpret_cast<const uint2 *>(base + o_work) + w0;
+        in.n_work = (uint32_t)(cut.first - w0);
+        const uint32_t grid = std::min<uint32_t>(kReadBlocks, (in.n_work + kThreads / 64 - 1) / (kThreads / 64));
+        if (al && lds) hipLaunchKernelGGL((k_kf_reads<true, true>), dim3(grid), dim3(kThreads), lds_bytes, h->ks, h->d, in, k);
+        else if (al) hipLaunchKernelGGL((k_kf_reads<true, false>), dim3(grid), dim3(kThreads), 0, h->ks, h->d, in, k);
+        else if (lds) hipLaunchKernelGGL((k_kf_reads<false, true>), dim3(grid), dim3(kThreads), lds_bytes, h->ks, h->d, in, k);
+        else hipLaunchKernelGGL((k_kf_reads<false, false>), dim3(grid), dim3(kThreads), 0, h->ks, h->d, in, k);
+        PG_HIP_TRY(h, hipGetLastError());
+        if (pg_status s = kf_snapshot(h, cut.second)) return s;
+        w0 = cut.first;
+    }
+    PG_HIP_TRY(h, hipEventRecord(h->counted[b], h->ks));
     return PG_OK;
 }
 

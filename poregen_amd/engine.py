@@ -666,6 +666,40 @@ class KmerCounter:
         if a.size:
             self._check(self._lib.pg_kfreq_submit(self._h, C.c_void_p(a.ctypes.data), a.size, _abi.PG_LOC_HOST))
 
+    @property
+    def reads_piece(self) -> int:
+        """Window starts per piece of a long read in submit_reads (pg_kfreq_reads_piece)."""
+        return int(self._lib.pg_kfreq_reads_piece(self._h))
+
+    def submit_reads(self, seq_bytes, byte_off, l_seq, reverse, n_to_t: bool = False):
+        """Layout rule: read r is l_seq[r] bases from byte byte_off[r] of seq_bytes, BAM's 4-bit codes "=ACMGRSVTWYHKDBN", high nibble first.
+        seq_bytes uint8, byte_off uint64, l_seq uint32, reverse uint8 (non-zero: counted reverse-complemented): all four numpy arrays
+        (`bytes` for seq_bytes too), or all four contiguous CUDA tensors of those widths (read in place, kept alive until finish).
+        n_to_t counts N as T. A stream takes either submit() or submit_reads() until finish()."""
+        flags = _abi.PG_KFREQ_N_TO_T if n_to_t else 0
+        arrs = (seq_bytes, byte_off, l_seq, reverse)
+        if all(hasattr(a, "is_cuda") and a.is_cuda for a in arrs):
+            for a, size in zip(arrs, (1, 8, 4, 1)):
+                if a.dtype.itemsize != size or not a.is_contiguous():
+                    raise ValueError("device reads: contiguous tensors of 1-, 8-, 4- and 1-byte integers")
+            n = l_seq.numel()
+            if byte_off.numel() != n or reverse.numel() != n:
+                raise ValueError("byte_off, l_seq and reverse must have one entry per read")
+            self._keep.append(arrs)
+            self._check(self._lib.pg_kfreq_submit_reads(self._h, C.c_void_p(seq_bytes.data_ptr()), seq_bytes.numel(), C.c_void_p(byte_off.data_ptr()),
+                                                        C.c_void_p(l_seq.data_ptr()), C.c_void_p(reverse.data_ptr()), n, flags, _abi.PG_LOC_DEVICE))
+            return
+        if any(hasattr(a, "is_cuda") and a.is_cuda for a in arrs):
+            raise ValueError("submit_reads takes four host arrays or four device tensors, not a mixture")
+        s = np.ascontiguousarray(np.frombuffer(seq_bytes, np.uint8) if isinstance(seq_bytes, (bytes, bytearray, memoryview)) else seq_bytes, dtype=np.uint8)
+        o = np.ascontiguousarray(byte_off, dtype=np.uint64)
+        ln = np.ascontiguousarray(l_seq, dtype=np.uint32)
+        rv = np.ascontiguousarray(reverse, dtype=np.uint8)
+        if o.size != ln.size or rv.size != ln.size:
+            raise ValueError("byte_off, l_seq and reverse must have one entry per read")
+        self._check(self._lib.pg_kfreq_submit_reads(self._h, C.c_void_p(s.ctypes.data), s.size, C.c_void_p(o.ctypes.data), C.c_void_p(ln.ctypes.data),
+                                                    C.c_void_p(rv.ctypes.data), ln.size, flags, _abi.PG_LOC_HOST))
+
     def finish(self) -> KmerFreqResult:
         counts = np.zeros(4 ** self.k, np.uint64)
         r = _abi.PgKfreqResult()
