@@ -31,9 +31,10 @@ def pa(raw, dig, off, rng) -> np.ndarray:
 
 
 def seq_mean(raw, dig, off, rng) -> float:
+    """the reference's loop: a sequential double sum started at +0.0 (so samples that are all -0.0 give 0.0, not -0.0), over n"""
     x = pa(raw, dig, off, rng)
     with np.errstate(all="ignore"):
-        return float(np.cumsum(x)[-1] / np.float64(x.size))
+        return float(np.cumsum(np.concatenate([[0.0], x]))[-1] / np.float64(x.size))
 
 
 def exact_mean(raw, dig, off, rng) -> float:

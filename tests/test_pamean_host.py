@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import pamean_cases as K
 import pamean_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -60,6 +61,9 @@ def test_sequential_loop_is_the_reference(h):
     assert R.fmt_f(h.pgt_pa_sequential_mean(raw.ctypes.data, 3, 0.0, 0.0, 281.0)) == b"-nan"
     raw = np.array([5, 6], np.int16)
     assert R.fmt_f(h.pgt_pa_sequential_mean(raw.ctypes.data, 2, 0.0, 0.0, 281.0)) == b"inf"
+    # range 0 under negative samples: every x_i is -0.0, and the sum that starts at +0.0 stays +0.0
+    raw = np.array([-5, -6, -32768], np.int16)
+    assert R.fmt_f(h.pgt_pa_sequential_mean(raw.ctypes.data, 3, 2048.0, 0.0, 0.0)) == R.fmt_f(R.seq_mean(raw, 2048.0, 0.0, 0.0)) == b"0.000000"
 
 
 def test_cells_just_inside_and_just_outside(h):
@@ -130,6 +134,83 @@ def test_boundary_reads_fall_back(h):
     for rid, raw, d, o, r in R.boundary_reads(200_000, 3):
         assert certify(h, raw, d, o, r) is None
         assert R.fmt_f(R.exact_mean(raw, d, o, r)) != R.fmt_f(R.seq_mean(raw, d, o, r))
+
+
+def test_shift_rounds_to_nearest_and_clamps(h):
+    """c is the integer nearest -offset (ties to even), clamped to +-2^20; a NaN gives a valid c as well"""
+    for off, c in ((0.0, 0), (-0.0, 0), (-243.0, 243), (243.4, -243), (2.5, -2), (-3.5, 4), (1048575.5, -1048576), (-1048575.5, 1048576),
+                   (1048576.5, -1048576), (-1048576.5, 1048576), (2e6, -1048576), (-2e6, 1048576), (1e300, -1048576), (-1e300, 1048576),
+                   (float("inf"), -1048576), (float("-inf"), 1048576)):
+        assert h.pgt_pa_shift(off) == c, off
+    assert abs(h.pgt_pa_shift(float("nan"))) <= 1048576
+
+
+def test_grid_holds_every_edge():
+    """the shapes the GPU suite runs: every head / tail length, one trip of the vector loop +- 1 vector +- 1 sample, the piece +- 1"""
+    assert set(range(25)) <= set(K.N_GRID) and {63, 64, 65, 8191, 8192, 8193, 12_293, 16_384, 16_385, 24_577, 70_001} <= set(K.N_GRID)
+    assert {8 * v + e for v in (511, 512, 513) for e in (-1, 0, 1)} <= set(K.N_GRID)
+    assert K.K_PIECE == 8192 and K.A_GRID == tuple(range(9)) and K.N_HUGE == 2 ** 20 + 1
+    for family in K.FAMILIES:
+        recs = K.grid_batch(family)
+        assert len(recs[0][1]) == 0 and len(recs[-1][1]) == 0
+        cur = 0
+        seen = set()
+        for rid, raw, *_ in recs:
+            assert not (raw == 0).any()
+            if rid.startswith("read_"):
+                a, n = (int(v) for v in rid.split("_")[1:])
+                assert cur % 8 == a % 8 and len(raw) == n
+                seen.add((a, n))
+            cur += len(raw)
+        assert seen == {(a, n) for a in K.A_GRID for n in K.N_GRID}
+        for a, n, (pad, read) in K.grid_cycles(family):
+            assert len(pad[1]) == a and len(read[1]) == n
+    low, alt, cap = (K.grid_cycles(f)[-1][2][1][1] for f in ("low", "alternating", "capped"))
+    assert (low == -32768).all() and set(alt[::2]) == {-32768} and set(alt[1::2]) == {32767} and (cap[0], cap[-1]) == (32767, -32768)
+
+
+def test_every_probe_shape_yields_both_probes(h):
+    """the generator of the threshold probes (pamean_cases.py): every shape of the probe set gives a just-settled and a just-refused
+    probe within its 20 draws, with the one-third margins on sa, and a settled probe's text is the reference's"""
+    sh = K.shim()
+    n_probes = 0
+    for a, n in K.probe_shapes():
+        for offset in K.PROBE_OFFSETS:
+            for fi, family in enumerate(K.PROBE_FAMILIES):
+                raw, rr, tries = K.probe_pair(sh, n, offset, family, np.random.default_rng([7, a, n, int(-offset), fi]))
+                assert tries <= K.PROBE_TRIES and raw.size == n
+                c = sh.shift(offset)
+                _, s1, sa = sh.sums(raw, offset)
+                dist = np.abs(raw.astype(np.int64) - c)
+                d = int(dist.min())
+                assert d >= 100 and not (raw == 0).any() and c == int(-offset)
+                m = d // 3
+                cert = lambda s, r: sh.certify(n, s1, s, offset, r) is not None      # noqa: E731
+                # just settled: settled with room for the margin, refused once any one sample is counted twice
+                r = rr["settled"]
+                assert cert(sa + m, r) and cert(sa, r) and not cert(sa + d - m, r) and not cert(sa + d, r)
+                assert check(h, raw, 1.0, offset, r)
+                # just refused: refused with room for the margin, settled once any one sample is dropped
+                r = rr["refused"]
+                assert not cert(sa - m, r) and not cert(sa, r) and cert(sa - d + m, r) and cert(sa - d, r)
+                assert not check(h, raw, 1.0, offset, r)
+                n_probes += 2
+    assert n_probes == 2 * 2 * 2 * (3 * 13 + 1)
+
+
+def test_probe_batches_are_decided_as_built():
+    """each probe sits at its a behind its pad read, and the host's decision is the one the batch is named after, pads included"""
+    sh = K.shim()
+    for kind, by_a in K.probe_batches().items():
+        for a, recs in by_a.items():
+            cur = 0
+            for rid, raw, dig, off, rng in recs:
+                if rid.startswith("probe_"):
+                    assert cur % 8 == a
+                if len(raw):
+                    assert sh.settles(raw, dig, off, rng) == (kind == "settled"), (kind, a, rid)
+                cur += len(raw)
+            assert sh.n_fallback(recs) == (0 if kind == "settled" else sum(1 for r in recs if len(r[1])))
 
 
 def walk(h, path):
