@@ -53,6 +53,9 @@
  *                                  (and `sed '2~4s/N/T/g'`) would print from a batch
  *                                  of BAM records, without the text: the records'
  *                                  packed sequence fields are the input
+ * pg_kfreq_submit_fasta            the same count over a FASTA (README.md STEP 3:   README.md STEP 2-3
+ *                                  count_kmer_freq.py 5 ${FASTA}), records wrapped
+ *                                  over any number of lines
  * pg_kfreq_reads_piece             (no counterpart)
  * pg_kfreq_finish                  the map's contents (dense ACGT counts + the     src/kmer_freq.cpp:189-192
  *                                  other keys in byte order); sorting and printing,
@@ -462,7 +465,9 @@ pg_status pg_kernel_stats_reset(pg_ctx *ctx);
  * iff i % 4 == 1, the last byte of every line (its '\n', or the last byte of an unterminated final line) is dropped, every window of
  * kmer_size bytes of the rest is a key. ACGT windows are counted densely (index = 2-bit codes, A=0 C=1 G=2 T=3, first base most
  * significant: the lexicographic order of the generated keys); any other window is a key of its own bytes ("odd key").
- * A NUL byte in a sequence line is refused: pg_kfreq_finish returns PG_ERR_INPUT. No CPU fallback: PG_ERR_NO_DEVICE without a GPU. */
+ * A NUL byte in a sequence line is refused: pg_kfreq_finish returns PG_ERR_INPUT. No CPU fallback: PG_ERR_NO_DEVICE without a GPU.
+ * A stream (up to the next finish) takes one of three input forms: FASTQ text (pg_kfreq_submit), packed reads (pg_kfreq_submit_reads) or
+ * FASTA text (pg_kfreq_submit_fasta). Any mix of them returns PG_ERR_INVALID_ARG and counts nothing. */
 typedef struct pg_kfreq pg_kfreq;
 typedef struct {
     uint32_t kmer_size;
@@ -487,15 +492,24 @@ pg_status pg_kfreq_submit(pg_kfreq *h, const void *data, uint64_t n_bytes, int32
  * a record with flag 0x10, bases in reverse order and every code complemented (its four bits reversed: A<->T, C<->G, M<->K, R<->Y,
  * V<->B, H<->D; '=', S, W, N stay). flags: PG_KFREQ_N_TO_T counts code 15 (N) of the printed read as T (sed '2~4s/N/T/g'); other
  * ambiguity codes stay. The result equals pg_kfreq_submit on the FASTQ text of the reads with every line '\n'-terminated.
- * One stream (up to the next finish) takes one form: a submit_reads after a submit, or a submit after a submit_reads, returns
- * PG_ERR_INVALID_ARG and counts nothing. location as for pg_kfreq_submit, for all four arrays; host arrays are free for reuse when the
+ * location as for pg_kfreq_submit, for all four arrays; host arrays are free for reuse when the
  * call returns. Long reads are cut into pieces of pg_kfreq_reads_piece(h) windows, one wave of the device each. */
 enum { PG_KFREQ_N_TO_T = 1 };
 pg_status pg_kfreq_submit_reads(pg_kfreq *h, const uint8_t *seq_bytes, uint64_t n_seq_bytes, const uint64_t *byte_off, const uint32_t *l_seq,
                                 const uint8_t *reverse, uint64_t n_reads, uint32_t flags, int32_t location);
 uint32_t  pg_kfreq_reads_piece(const pg_kfreq *h);
+/* The stream's third input form: the next n_bytes of a FASTA, in pieces cut at ANY byte offset; location and lifetime as for
+ * pg_kfreq_submit. Lines end at '\n' and nowhere else (a '\r' is a byte of its line; the last line may be unterminated). A line whose
+ * first byte is '>' is a header line, every other line -- an empty one, one with '>' further in -- a sequence line. A record is a
+ * maximal run of sequence lines with no header line between them (also in front of the first header; a header followed by a header is
+ * an empty record), its sequence those lines' bytes in order without the '\n's, and every window of kmer_size bytes of a record's
+ * sequence is a key: windows run across line ends, never across a header. ACGT windows densely, any other window ('N', lower case,
+ * '\r', ...) as an odd key of its bytes, as in the FASTQ form. No byte is dropped: the window that ends on the stream's last byte
+ * counts (the one difference to the FASTQ form over the same bytes). The result equals pg_kfreq_submit on the FASTQ text
+ * "@\n" + sequence + "\n+\n\n" of every record. A NUL byte in a sequence line: PG_ERR_INPUT at finish; header lines are not looked at. */
+pg_status pg_kfreq_submit_fasta(pg_kfreq *h, const void *data, uint64_t n_bytes, int32_t location);
 pg_status pg_kfreq_sync(pg_kfreq *h);
-/* End of stream (the window ending on its last byte is dropped: the unterminated-final-line rule). counts_out: host u64[4^kmer_size].
+/* End of stream (FASTQ form: the window ending on its last byte is dropped, the unterminated-final-line rule). counts_out: host u64[4^kmer_size].
  * The handle is reset afterwards, also after an error: the next submit starts a new stream. */
 pg_status pg_kfreq_finish(pg_kfreq *h, uint64_t *counts_out, pg_kfreq_result *out);
 

@@ -39,7 +39,7 @@ EXPORTS = [
     "pg_job_create", "pg_job_destroy", "pg_job_last_error", "pg_job_submit", "pg_job_submit_shards", "pg_job_reset", "pg_job_sync", "pg_job_all_slots_full", "pg_job_finish",
     "pg_job_finish_deferred", "pg_job_fetch_samples", "pg_job_text", "pg_job_fetch_text",
     "pg_job_uses_rccl", "pg_job_model", "pg_job_kernel_stats", "pg_runtime_init", "pg_all_slots_full_settled", "pg_job_all_slots_full_settled", "pg_poll", "pg_job_poll",
-    "pg_kfreq_create", "pg_kfreq_destroy", "pg_kfreq_last_error", "pg_kfreq_submit", "pg_kfreq_submit_reads", "pg_kfreq_reads_piece", "pg_kfreq_sync", "pg_kfreq_finish",
+    "pg_kfreq_create", "pg_kfreq_destroy", "pg_kfreq_last_error", "pg_kfreq_submit", "pg_kfreq_submit_reads", "pg_kfreq_submit_fasta", "pg_kfreq_reads_piece", "pg_kfreq_sync", "pg_kfreq_finish",
     "pg_fscore_create", "pg_fscore_destroy", "pg_fscore_last_error", "pg_fscore_submit", "pg_fscore_sync", "pg_fscore_finish",
     "pg_pamean_create", "pg_pamean_destroy", "pg_pamean_last_error", "pg_pamean_submit", "pg_pamean_sync", "pg_pamean_finish",
     "pg_dmodel_create", "pg_dmodel_destroy", "pg_dmodel_last_error", "pg_dmodel_submit", "pg_dmodel_sync", "pg_dmodel_finish", "pg_dmodel_format",
@@ -233,6 +233,7 @@ def load():
     lib.pg_kfreq_last_error.argtypes = [vp]; lib.pg_kfreq_last_error.restype = C.c_char_p
     lib.pg_kfreq_submit.argtypes = [vp, vp, C.c_uint64, i32]; lib.pg_kfreq_submit.restype = i32
     lib.pg_kfreq_submit_reads.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, u32, i32]; lib.pg_kfreq_submit_reads.restype = i32
+    lib.pg_kfreq_submit_fasta.argtypes = [vp, vp, C.c_uint64, i32]; lib.pg_kfreq_submit_fasta.restype = i32
     lib.pg_kfreq_reads_piece.argtypes = [vp]; lib.pg_kfreq_reads_piece.restype = u32
     lib.pg_kfreq_sync.argtypes = [vp]; lib.pg_kfreq_sync.restype = i32
     lib.pg_kfreq_finish.argtypes = [vp, vp, C.POINTER(PgKfreqResult)]; lib.pg_kfreq_finish.restype = i32

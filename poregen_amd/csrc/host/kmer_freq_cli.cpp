@@ -17,7 +17,9 @@
 // Beyond the reference: a file named *.bam or *.sam (the suffix test of gmove_cli.cpp) is read as the basecaller's BAM / SAM, and its
 // reads are counted as the FASTQ that `samtools fastq FILE` would print (flags 0x100 / 0x800 skipped, flag 0x10 reverse-complemented;
 // host/kfreq_reads.cpp, pg_kfreq_submit_reads); --n_to_t adds the workflow's `sed '2~4s/N/T/g'` (README.md STEP 2 of the reference) and
-// is refused for FASTQ input. Any other name is FASTQ, as before.
+// is refused for FASTQ input. A file named *.fa, *.fasta or *.fna, or any file with --fasta, is read as a FASTA (README.md STEP 3 of the
+// reference runs the count on one): header lines start with '>', a record's sequence may be wrapped over any number of lines and its
+// windows run across the line ends (pg_kfreq_submit_fasta). --fasta on a .bam / .sam is refused. Any other name is FASTQ, as before.
 // Refused (exit 1, DESIGN.md "kmer_freq"): kmer_size outside 1..12 (the reference recurses without end for negative values,
 // prints one empty key for 0, and needs gigabytes of strings above 12), and a NUL byte in a sequence line (PG_ERR_INPUT).
 #include "../../../include/pgmove.h"
@@ -50,14 +52,16 @@ const struct option kLongOptions[] = {
     {"output", required_argument, nullptr, 'o'},           // 4
     {"debug-break", required_argument, nullptr, 0},        // 5
     {"n_to_t", no_argument, nullptr, 0},                   // 6 (not in the reference: appended, the indices above keep their meaning)
+    {"fasta", no_argument, nullptr, 0},                    // 7 (likewise)
     {nullptr, 0, nullptr, 0}};
 
 void print_help(FILE *fp) { // src/kmer_freq.cpp:30-42
-    fprintf(fp, "Usage: poregen kmer_freq kmer_size reads.fastq|reads.bam|reads.sam\n");
+    fprintf(fp, "Usage: poregen kmer_freq kmer_size reads.fastq|reads.bam|reads.sam|seqs.fa|seqs.fasta|seqs.fna\n");
     fprintf(fp, "\nbasic options:\n");
     fprintf(fp, "   --sort INT                 sort based on frequency (0-no sorting, 1-ascend, 2-descend) [0] \n");
     fprintf(fp, "   --print_absent_kmers INT   print kmers with 0 frequency (0-do not print, 1-print) [1] \n");
     fprintf(fp, "   --n_to_t                   count N as T, as sed '2~4s/N/T/g' on the FASTQ would (.bam / .sam input only)\n");
+    fprintf(fp, "   --fasta                    read the file as a FASTA, records wrapped or not (implied by .fa / .fasta / .fna)\n");
     fprintf(fp, "   -o FILE                    output to file [stdout]\n");
     fprintf(fp, "   --verbose INT              verbosity level [%d]\n", g_log_level);
     fprintf(fp, "   --version                  print version\n");
@@ -119,7 +123,7 @@ uint64_t piece_bytes() {
 int kmer_freq_main(int argc, char **argv) {
     int c, longindex = 0;
     int flag_sort = 0, flag_print_absent = 1;
-    bool n_to_t = false;
+    bool n_to_t = false, fasta = false;
     bool help_to_stdout = false;
     const char *out_path = nullptr;
     optind = 1;
@@ -137,6 +141,7 @@ int kmer_freq_main(int argc, char **argv) {
             if (v != 0 && v != 1) { KF_ERROR("print_absent_kmers flag must be 0 or 1 You entered %d", v); exit(EXIT_FAILURE); }
             flag_print_absent = v;
         } else if (c == 0 && longindex == 6) n_to_t = true;
+        else if (c == 0 && longindex == 7) fasta = true;
         // longindex 5 (debug-break): accepted, no effect (the reference reads it at longindex 4)
     }
     if (argc - optind != 2 || help_to_stdout) {
@@ -146,6 +151,12 @@ int kmer_freq_main(int argc, char **argv) {
     const std::string in_name(argv[optind + 1]);
     const std::string ext = in_name.size() >= 4 ? in_name.substr(in_name.size() - 4) : "";
     const bool is_bam = ext == ".bam", is_reads = is_bam || ext == ".sam";
+    auto ends_with = [&](const char *suffix) { const size_t m = strlen(suffix); return in_name.size() >= m && in_name.compare(in_name.size() - m, m, suffix) == 0; };
+    if (fasta && is_reads) {
+        KF_ERROR("--fasta does not apply to .bam and .sam input You entered %s", in_name.c_str());
+        exit(EXIT_FAILURE);
+    }
+    if (ends_with(".fa") || ends_with(".fasta") || ends_with(".fna")) fasta = true;
     if (n_to_t && !is_reads) {
         KF_ERROR("--n_to_t applies to .bam and .sam input only (for a FASTQ: sed '2~4s/N/T/g') You entered %s", in_name.c_str());
         exit(EXIT_FAILURE);
@@ -195,7 +206,7 @@ int kmer_freq_main(int argc, char **argv) {
         std::vector<uint8_t> buf(piece);
         for (;;) {
             const size_t got = fread(buf.data(), 1, piece, in);
-            if (got && pg_kfreq_submit(h, buf.data(), got, PG_LOC_HOST) != PG_OK) { KF_ERROR("%s", pg_kfreq_last_error(h)); exit(EXIT_FAILURE); }
+            if (got && (fasta ? pg_kfreq_submit_fasta : pg_kfreq_submit)(h, buf.data(), got, PG_LOC_HOST) != PG_OK) { KF_ERROR("%s", pg_kfreq_last_error(h)); exit(EXIT_FAILURE); }
             if (got < piece) break;
         }
         if (ferror(in)) { KF_ERROR("reading %s: %s", fastq, strerror(errno)); exit(EXIT_FAILURE); }

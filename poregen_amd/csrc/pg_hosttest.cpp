@@ -276,3 +276,117 @@ extern "C" long pgt_dump_model_host(const char *const *dirs, size_t n_dirs, int 
 extern "C" int pgt_kf_code_of_byte(int byte) { return (int)pg_kf_code_of_byte((uint32_t)byte & 0xff); }
 extern "C" int pgt_kf_letter(int code) { return (int)pg_kf_letter((uint32_t)code & 15); }
 extern "C" int pgt_kf_complement(int code) { return (int)pg_kf_complement((uint32_t)code & 15); }
+
+// ---- kmer_freq on FASTA input (pg_kfreq_fasta.h): the kernels' decomposition on the host -- a unit's tiles summarised span by span as
+// k_kf_fa_lines does, then every span walked from the state k_kf_fa_count derives for it (tile summaries across tiles, span summaries
+// inside one), the carried state handed from unit to unit. Only the order differs: one thread after the other instead of a scan.
+#include "pg_kfreq_fasta.h"
+#include <map>
+namespace {
+constexpr uint64_t kFaTile = (uint64_t)kFaSpan * kFaTileSpans;
+struct FaHostSink {
+    uint32_t k; std::map<uint32_t, uint64_t> *hist; std::map<std::string, uint64_t> *odd_map;
+    void dense(uint32_t code) { (*hist)[code]++; }
+    void odd(uint64_t lo, uint32_t hi) {
+        std::string key(k, '\0');
+        for (uint32_t i = 0; i < k; i++) { const uint32_t sh = k - 1 - i; key[i] = (char)(sh < 8 ? lo >> (8 * sh) : hi >> (8 * (sh - 8))); }
+        (*odd_map)[key]++;
+    }
+};
+struct FaHostLoad {
+    const uint8_t *p; uint64_t base, n;
+    void operator()(uint32_t ch, uint32_t (&ws)[4]) const {
+        for (int i = 0; i < 4; i++) ws[i] = 0;
+        for (uint32_t b = 0; b < 16; b++) { const uint64_t o = base + 16 * ch + b; if (o < n) ws[b >> 2] |= (uint32_t)p[o] << (8 * (b & 3)); }
+    }
+};
+struct FaHostState { uint32_t kind; PgFaSum rec; };
+uint32_t fa_host_span(const uint8_t *p, uint64_t base, uint64_t n, PgFaSpan &sp) { // returns the span's first byte
+    uint32_t w[kFaSpan / 4];
+    FaHostLoad load{p, base, n};
+    for (uint32_t ch = 0; ch < kFaSpan / 16; ch++) { uint32_t ws[4]; load(ch, ws); for (int i = 0; i < 4; i++) w[4 * ch + i] = ws[i]; }
+    pg_fa_span_summary(w, (uint32_t)std::min<uint64_t>(kFaSpan, n - base), sp);
+    return w[0] & 0xff;
+}
+bool fa_host_unit(const uint8_t *p, uint64_t n, uint32_t k, FaHostState &st, FaHostSink &sink) {
+    const uint64_t n_tiles = (n + kFaTile - 1) / kFaTile;
+    std::vector<uint64_t> tile_ls(n_tiles, 0);
+    std::vector<PgFaSum> tile_fa(n_tiles), tile_pb(n_tiles);
+    for (uint64_t t = 0; t < n_tiles; t++) { // k_kf_fa_lines
+        const uint64_t tile0 = t * kFaTile, tile_end = std::min<uint64_t>(n, tile0 + kFaTile);
+        uint64_t ls = 0, fa_end = tile_end;
+        PgFaSum rest = pg_fa_empty();
+        for (uint64_t base = tile0; base < tile_end; base += kFaSpan) {
+            PgFaSpan sp;
+            const uint32_t first_byte = fa_host_span(p, base, n, sp);
+            rest = pg_fa_compose(rest, ls ? pg_fa_resolve(pg_fa_kind_at(p, ls, base, PG_FA_SEQ), first_byte, sp.fa, sp.pb) : sp.pb);
+            if (sp.has_nl) {
+                if (!ls) { fa_end = base; while (p[fa_end] != '\n') fa_end++; }
+                ls = base + sp.last_nl + 1;
+            }
+        }
+        PgFaSum f = pg_fa_empty();
+        for (uint64_t q = fa_end - tile0 > kFaTail ? fa_end - kFaTail : tile0; q < fa_end; q++) pg_fa_append(f, p[q]);
+        tile_ls[t] = ls; tile_fa[t] = f; tile_pb[t] = rest;
+    }
+    bool bad = false;
+    uint64_t line_in = 0;
+    PgFaSum rec_in = st.rec;
+    for (uint64_t t = 0; t < n_tiles; t++) { // k_kf_fa_count, block t
+        const uint64_t tile0 = t * kFaTile, tile_end = std::min<uint64_t>(n, tile0 + kFaTile);
+        uint64_t ls = line_in;
+        PgFaSum rec = rec_in;
+        for (uint64_t base = tile0; base < tile_end; base += kFaSpan) {
+            PgFaSpan sp;
+            const uint32_t first_byte = fa_host_span(p, base, n, sp);
+            const uint32_t kind = pg_fa_kind_at(p, ls, base, st.kind);
+            FaHostLoad load{p, base, n};
+            bad |= pg_fa_walk(load, (uint32_t)std::min<uint64_t>(kFaSpan, n - base), k, kind, rec, sink);
+            rec = pg_fa_compose(rec, pg_fa_resolve(kind, first_byte, sp.fa, sp.pb));
+            if (sp.has_nl) ls = base + sp.last_nl + 1;
+        }
+        // what the next block folds from the tile summaries
+        rec_in = pg_fa_compose(rec_in, pg_fa_resolve(pg_fa_kind_at(p, line_in, tile0, st.kind), p[tile0], tile_fa[t], tile_pb[t]));
+        line_in = std::max(line_in, tile_ls[t]);
+    }
+    st.kind = pg_fa_kind_at(p, line_in, n, st.kind);
+    st.rec = rec_in;
+    return bad;
+}
+} // namespace
+// The FASTA form on data[0, n) delivered in pieces that end at cuts[0] <= cuts[1] <= ... (the last one at n), each piece cut into units of
+// at most `unit` bytes. The ACGT keys met, ascending: codes into dense_codes, counts into dense_counts, up to dense_cap, their number into
+// *n_dense. The odd keys in byte order: k bytes each into odd_keys, counts into odd_counts, up to odd_cap. Returns the number of odd keys;
+// *nul = a sequence line holds a NUL byte.
+extern "C" long pgt_kf_fasta(const uint8_t *data, uint64_t n, const uint64_t *cuts, size_t n_cuts, uint32_t k, uint64_t unit,
+                             uint32_t *dense_codes, uint64_t *dense_counts, size_t dense_cap, uint8_t *odd_keys, uint64_t *odd_counts,
+                             size_t *n_dense, size_t odd_cap, int *nul) {
+    std::map<uint32_t, uint64_t> hist;
+    std::map<std::string, uint64_t> odd;
+    FaHostSink sink{k, &hist, &odd};
+    FaHostState st{PG_FA_FRESH, pg_fa_empty()};
+    bool bad = false;
+    uint64_t at = 0;
+    for (size_t c = 0; c < n_cuts; c++) {
+        const uint64_t end = std::min<uint64_t>(cuts[c], n);
+        while (at < end) {
+            const uint64_t m = std::min<uint64_t>(unit, end - at);
+            const std::vector<uint8_t> u(data + at, data + at + m); // a buffer of its own: nothing outside the unit can be read unnoticed
+            bad |= fa_host_unit(u.data(), m, k, st, sink);
+            at += m;
+        }
+    }
+    size_t i = 0;
+    for (const auto &kv : hist) {
+        if (i < dense_cap) { dense_codes[i] = kv.first; dense_counts[i] = kv.second; }
+        i++;
+    }
+    *n_dense = i;
+    i = 0;
+    for (const auto &kv : odd) {
+        if (i < odd_cap) { memcpy(odd_keys + i * k, kv.first.data(), k); odd_counts[i] = kv.second; }
+        i++;
+    }
+    *nul = bad;
+    return (long)i;
+}

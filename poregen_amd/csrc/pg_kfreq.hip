@@ -25,10 +25,22 @@
 //                k - 1 bases a window spans), the piece's windows spread evenly over the 64 lanes, each lane rolling over its share plus
 //                k - 1 bases of warm-up with 8-byte loads. A read with the reverse flag is walked as stored and the window formed as
 //                `samtools fastq` prints it: codes complemented, newest base most significant. Same histograms, same odd list.
+//
+// Third input form, pg_kfreq_submit_fasta: FASTA bytes, in pieces cut anywhere, units as for the FASTQ text. A line's kind is its first byte
+// and a record's windows cross line ends, so the two facts the FASTQ kernels rest on are replaced (pg_kfreq_fasta.h has the rules and the
+// record-tail monoid; DESIGN.md 9.2 the reasoning):
+//   k_kf_fa_lines : per tile, the offset behind its last newline and the tile's summary (the last <= 11 sequence bytes in front of its
+//                   first newline; behind it, whether a header line lies there and the last <= 11 sequence bytes after the last one)
+//   k_kf_fa_count : prefix maximum of the tiles' line starts -> the kind of the line open at every tile's first byte (one byte read) ->
+//                   the tiles' summaries resolved and folded in order -> the same again over the tile's 256 spans: every thread starts
+//                   with the state a sequential walk holds at its first byte, and walks its span alone. Block 0 writes the carried
+//                   state (kind of the open line, the open record's last <= 11 bytes). Nothing is deferred: a window is counted by the
+//                   thread that holds its last byte, the stream's last byte included, so finish has nothing to settle.
 #include "../../include/pgmove.h"
 #include <hip/hip_runtime.h>
 #include "pg_hip_host.h"
 #include "pg_kfreq_codes.h"
+#include "pg_kfreq_fasta.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -54,6 +66,14 @@ struct KfState {       // carried across units; two slots, unit u reads slot u&1
     uint8_t tail[16];  // its last tail_len bytes, oldest first
 };
 
+struct KfFaState {     // the FASTA form's carried state, two slots like KfState; all zero at the start of a stream
+    uint32_t kind;     // PG_FA_*: the line open at the unit's first byte (FRESH: it starts there)
+    uint32_t pad;
+    PgFaSum rec;       // the open record's last <= kFaTail sequence bytes
+};
+static_assert(kSpan == kFaSpan && kThreads == kFaTileSpans && kMaxK - 1 <= kFaTail, "pg_kfreq_fasta.h describes these spans and tiles");
+static_assert(kUnit / kTile <= 2 * kThreads, "k_kf_fa_count folds two tile summaries per thread");
+
 struct KfDev {
     unsigned long long *hist;  // u64[4^k]
     uint4 *odd;                // odd windows, k bytes each, zero padded
@@ -61,12 +81,13 @@ struct KfDev {
     uint32_t *err;             // NUL in a sequence line
     KfState *state;            // [2]
     uint32_t *tile_nl;         // newlines per tile of the current unit
+    uint32_t *tile_ls;         // FASTA: per tile, the offset in the unit behind its last newline ("line start"); 0 = the tile holds none
+    PgFaSum *fa_tile;          // FASTA: per tile, [2 t] the bytes in front of its first newline, [2 t + 1] the rest (PgFaSpan's fa, pb)
+    KfFaState *fa_state;       // [2]
     uint64_t odd_cap;
 };
 
-__device__ __forceinline__ int base_code(uint32_t c) {
-    return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1;
-}
+__device__ __forceinline__ int base_code(uint32_t c) { return pg_kf_base_code(c); }
 
 // this thread's kSpan bytes of the unit (or fewer at its end), as four-byte words in registers
 template <bool kAligned>
@@ -144,6 +165,36 @@ __device__ __forceinline__ void add_run(const KfDev &d, uint32_t *lds, uint32_t 
     if (!cnt) return;
     if (kLds) atomicAdd(&lds[code], cnt);
     else atomicAdd(&d.hist[code], (unsigned long long)cnt);
+}
+
+// The end of a text kernel, all threads of the workgroup: the open run of every thread (the wave is converged here) -- where all of a
+// wave's runs share one code, a homopolymer, one lane adds their sum, instead of 64 adds to one address -- then the staged odd windows
+// and the LDS histogram.
+template <bool kLds>
+__device__ __forceinline__ void kf_flush(const KfDev &d, uint32_t *lds_hist, uint32_t n_codes, uint32_t run_code, uint32_t run_cnt,
+                                         const uint4 *s_odd, const uint32_t *s_odd_n, unsigned long long *s_odd_at) {
+    const uint32_t tid = threadIdx.x;
+    const uint32_t c0 = __builtin_amdgcn_readfirstlane(run_code);
+    const bool lone = __ballot(run_cnt != 0 && run_code != c0) != 0;
+    if (lone) {
+        add_run<kLds>(d, lds_hist, run_code, run_cnt);
+    } else {
+        uint32_t sum = run_cnt;
+        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+        if ((tid & 63) == 0) add_run<kLds>(d, lds_hist, c0, sum);
+    }
+    __syncthreads();
+    const uint32_t n_staged = min(*s_odd_n, kOddLds);
+    if (n_staged) {
+        if (tid == 0) *s_odd_at = atomicAdd(d.odd_n, (unsigned long long)n_staged);
+        __syncthreads();
+        for (uint32_t i = tid; i < n_staged; i += kThreads)
+            if (*s_odd_at + i < d.odd_cap) d.odd[*s_odd_at + i] = s_odd[i];
+    }
+    if (kLds) {
+        for (uint32_t i = tid; i < n_codes; i += kThreads)
+            if (const uint32_t v = lds_hist[i]) atomicAdd(&d.hist[i], (unsigned long long)v);
+    }
 }
 
 // block 0, thread 0: windows that start in the carried tail and end in this unit, then the state the next unit starts from
@@ -286,29 +337,162 @@ __global__ __launch_bounds__(kThreads) void k_kf_count(KfDev d, const uint8_t *_
         }
         if (bad) atomicOr(d.err, 1u);
     }
-    // the open run of every thread (the wave is converged here): where all of a wave's runs share one code -- a homopolymer -- one
-    // lane adds their sum, instead of 64 adds to one address
-    const uint32_t c0 = __builtin_amdgcn_readfirstlane(run_code);
-    const bool lone = __ballot(run_cnt != 0 && run_code != c0) != 0;
-    if (lone) {
-        add_run<kLds>(d, lds_hist, run_code, run_cnt);
-    } else {
-        uint32_t sum = run_cnt;
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-        if ((tid & 63) == 0) add_run<kLds>(d, lds_hist, c0, sum);
-    }
+    kf_flush<kLds>(d, lds_hist, n_codes, run_code, run_cnt, s_odd, &s_odd_n, &s_odd_at);
+}
+
+// ---- FASTA text ------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ PgFaSum fa_shfl_up(const PgFaSum &v, int delta) {
+    PgFaSum r;
+    r.lo = (uint64_t)__shfl_up((uint32_t)(v.lo >> 32), delta) << 32 | __shfl_up((uint32_t)v.lo, delta);
+    r.hi = __shfl_up(v.hi, delta);
+    r.meta = __shfl_up(v.meta, delta);
+    return r;
+}
+
+// Scans over the workgroup's threads in thread order (all threads call; s_w: one LDS entry per wave, free again on return).
+// The maximum of x over the threads in front of this one (0 if none); *total: over all of them.
+__device__ __forceinline__ uint32_t block_max_before(uint32_t x, uint32_t *s_w, uint32_t *total) {
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(x, o); if (lane >= (uint32_t)o) x = max(x, y); }
+    if (lane == 63) s_w[wave] = x;
+    uint32_t before = __shfl_up(x, 1);
+    if (lane == 0) before = 0;
     __syncthreads();
-    const uint32_t n_staged = min(s_odd_n, kOddLds);
-    if (n_staged) {
-        if (tid == 0) s_odd_at = atomicAdd(d.odd_n, (unsigned long long)n_staged);
-        __syncthreads();
-        for (uint32_t i = tid; i < n_staged; i += kThreads)
-            if (s_odd_at + i < d.odd_cap) d.odd[s_odd_at + i] = s_odd[i];
+    uint32_t all = 0;
+    for (uint32_t i = 0; i < kThreads / 64; i++) { if (i == wave) before = max(before, all); all = max(all, s_w[i]); }
+    __syncthreads();
+    *total = all;
+    return before;
+}
+// The composition of v over the threads in front of this one; *total: over all of them.
+__device__ __forceinline__ PgFaSum block_compose_before(PgFaSum v, PgFaSum *s_w, PgFaSum *total) {
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int o = 1; o < 64; o <<= 1) { const PgFaSum u = fa_shfl_up(v, o); if (lane >= (uint32_t)o) v = pg_fa_compose(u, v); }
+    if (lane == 63) s_w[wave] = v;
+    PgFaSum before = fa_shfl_up(v, 1);
+    if (lane == 0) before = pg_fa_empty();
+    __syncthreads();
+    PgFaSum all = pg_fa_empty();
+    for (uint32_t i = 0; i < kThreads / 64; i++) { if (i == wave) before = pg_fa_compose(all, before); all = pg_fa_compose(all, s_w[i]); }
+    __syncthreads();
+    *total = all;
+    return before;
+}
+
+template <bool kAligned>
+__global__ __launch_bounds__(kThreads) void k_kf_fa_lines(const uint8_t *__restrict__ p, uint64_t n, uint32_t *__restrict__ tile_ls, PgFaSum *__restrict__ fa_tile) {
+    __shared__ uint32_t s_m[kThreads / 64];
+    __shared__ PgFaSum s_w[kThreads / 64];
+    const uint64_t tile0 = blockIdx.x * kTile, base = tile0 + threadIdx.x * (uint64_t)kSpan;
+    PgFaSpan sp;
+    sp.fa = sp.pb = pg_fa_empty(); sp.has_nl = 0; sp.last_nl = 0;
+    uint32_t first_byte = 0;
+    if (base < n) {
+        uint32_t w[kSpan / 4];
+        load_span<kAligned>(p, base, n, w);
+        pg_fa_span_summary(w, (uint32_t)min<uint64_t>(kSpan, n - base), sp);
+        first_byte = w[0] & 0xff;
     }
-    if (kLds) {
-        for (uint32_t i = tid; i < n_codes; i += kThreads)
-            if (const uint32_t v = lds_hist[i]) atomicAdd(&d.hist[i], (unsigned long long)v);
+    // where the line open at this span's first byte starts, if that is inside the tile (a unit has < 2^32 bytes). An offset behind a
+    // newline is at least 1, so 0 stands for "no newline" and the maximum needs no flag.
+    uint32_t tile_last;
+    const uint32_t ls = block_max_before(sp.has_nl ? (uint32_t)base + sp.last_nl + 1 : 0, s_m, &tile_last);
+    // the part of the tile behind its first newline: there the kind of every span's first line is known
+    PgFaSum e = sp.pb;
+    if (ls != 0 && base < n) e = pg_fa_resolve(pg_fa_kind_at(p, ls, base, PG_FA_SEQ), first_byte, sp.fa, sp.pb);
+    PgFaSum rest;
+    block_compose_before(e, s_w, &rest);
+    if (threadIdx.x == 0) { tile_ls[blockIdx.x] = tile_last; fa_tile[2 * blockIdx.x + 1] = rest; }
+    // the part in front of it: its last <= kFaTail bytes lie side by side in front of that newline (or of the tile's end)
+    const bool owner = tile_last == 0 ? threadIdx.x == 0 : ls == 0 && sp.has_nl;
+    if (owner) {
+        uint64_t end = min<uint64_t>(n, tile0 + kTile);
+        if (sp.has_nl) { uint32_t first = 0; while (p[base + first] != '\n') first++; end = base + first; }
+        PgFaSum f = pg_fa_empty();
+        for (uint64_t q = end - tile0 > kFaTail ? end - kFaTail : tile0; q < end; q++) pg_fa_append(f, p[q]);
+        fa_tile[2 * blockIdx.x] = f;
     }
+}
+
+template <bool kLds>
+struct KfFaSink {
+    const KfDev &d;
+    uint32_t *lds_hist;
+    uint4 *s_odd;
+    uint32_t *s_odd_n;
+    uint32_t k, run_code, run_cnt;
+    __device__ __forceinline__ void dense(uint32_t code) {
+        if (code == run_code) run_cnt++;
+        else { add_run<kLds>(d, lds_hist, run_code, run_cnt); run_code = code; run_cnt = 1; }
+    }
+    __device__ __forceinline__ void odd(uint64_t lo, uint32_t hi) { stage_odd(d, s_odd, s_odd_n, odd_key(lo, hi, k)); }
+};
+template <bool kAligned>
+struct KfFaLoad {
+    const uint8_t *p;
+    uint64_t base, n;
+    __device__ __forceinline__ void operator()(uint32_t ch, uint32_t (&ws)[4]) const {
+        const uint4 v = load16<kAligned>(p, base + 16 * ch, n); // second read of the span: served by the cache
+        ws[0] = v.x; ws[1] = v.y; ws[2] = v.z; ws[3] = v.w;
+    }
+};
+
+template <bool kAligned, bool kLds>
+__global__ __launch_bounds__(kThreads) void k_kf_fa_count(KfDev d, const uint8_t *__restrict__ p, uint64_t n, uint32_t n_tiles, uint32_t k, uint32_t par) {
+    extern __shared__ uint32_t lds_hist[];
+    __shared__ uint32_t s_m[kThreads / 64];
+    __shared__ PgFaSum s_w[kThreads / 64];
+    __shared__ uint4 s_odd[kOddLds];
+    __shared__ uint32_t s_odd_n;
+    __shared__ unsigned long long s_odd_at;
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) s_odd_n = 0;
+    const uint32_t n_codes = 1u << (2 * k);
+    if (kLds) for (uint32_t i = tid; i < n_codes; i += kThreads) lds_hist[i] = 0;
+    const KfFaState st = d.fa_state[par];
+
+    // the tiles in front of this one (block 0: all of them, for the next unit's state), two per thread: where the line open at each
+    // tile's first byte starts -> its kind -> the tile's effect on the record tail; folded in order
+    const uint32_t upto = blockIdx.x == 0 ? n_tiles : blockIdx.x;
+    const uint32_t t0 = 2 * tid, t1 = t0 + 1;
+    const uint32_t ls0 = t0 < upto ? d.tile_ls[t0] : 0, ls1 = t1 < upto ? d.tile_ls[t1] : 0; // 0: no newline in the tile (a line start is >= 1)
+    uint32_t line_in;
+    const uint32_t ls_t0 = block_max_before(max(ls0, ls1), s_m, &line_in);
+    PgFaSum e = pg_fa_empty();
+    if (t0 < upto) e = pg_fa_resolve(pg_fa_kind_at(p, ls_t0, t0 * kTile, st.kind), p[t0 * kTile], d.fa_tile[2 * t0], d.fa_tile[2 * t0 + 1]);
+    if (t1 < upto) e = pg_fa_compose(e, pg_fa_resolve(pg_fa_kind_at(p, max(ls_t0, ls0), t1 * kTile, st.kind), p[t1 * kTile], d.fa_tile[2 * t1], d.fa_tile[2 * t1 + 1]));
+    PgFaSum rec_in;
+    block_compose_before(e, s_w, &rec_in);
+    rec_in = pg_fa_compose(st.rec, rec_in);
+    if (blockIdx.x == 0) {
+        if (tid == 0) { KfFaState o; o.kind = pg_fa_kind_at(p, line_in, n, st.kind); o.pad = 0; o.rec = rec_in; d.fa_state[par ^ 1] = o; }
+        line_in = 0; rec_in = st.rec;
+    }
+
+    // the same over this tile's spans
+    const uint64_t base = blockIdx.x * kTile + tid * (uint64_t)kSpan;
+    const uint32_t lim = base < n ? (uint32_t)min<uint64_t>(kSpan, n - base) : 0;
+    PgFaSpan sp;
+    sp.fa = sp.pb = pg_fa_empty(); sp.has_nl = 0; sp.last_nl = 0;
+    uint32_t first_byte = 0;
+    if (lim) {
+        uint32_t w[kSpan / 4];
+        load_span<kAligned>(p, base, n, w);
+        pg_fa_span_summary(w, lim, sp);
+        first_byte = w[0] & 0xff;
+    }
+    uint32_t unused;
+    const uint32_t ls = max(line_in, block_max_before(sp.has_nl ? (uint32_t)base + sp.last_nl + 1 : 0, s_m, &unused));
+    const uint32_t kind = lim ? pg_fa_kind_at(p, ls, base, st.kind) : (uint32_t)PG_FA_SEQ;
+    PgFaSum all;
+    const PgFaSum rec = pg_fa_compose(rec_in, block_compose_before(lim ? pg_fa_resolve(kind, first_byte, sp.fa, sp.pb) : pg_fa_empty(), s_w, &all));
+
+    KfFaSink<kLds> sink{d, lds_hist, s_odd, &s_odd_n, k, 0, 0};
+    if (lim) {
+        KfFaLoad<kAligned> load{p, base, n};
+        if (pg_fa_walk(load, lim, k, kind, rec, sink)) atomicOr(d.err, 1u);
+    }
+    kf_flush<kLds>(d, lds_hist, n_codes, sink.run_code, sink.run_cnt, s_odd, &s_odd_n, &s_odd_at);
 }
 
 // ---- packed reads ---------------------------------------------------------------------------------------------------------------
@@ -428,7 +612,7 @@ struct pg_kfreq {
     uint64_t unit = kUnit; // <= odd_cap: a unit never has more windows than the list holds
     PgStream ks, cs; // count stream, copy stream (host input)
     PgEvent copied[2], counted[2], snap_ev[kSnapRing];
-    PgDev<> mem[6];  // what d points to, in the order of KfDev's members
+    PgDev<> mem[9];  // what d points to, in the order of KfDev's members
     KfDev d{};
     uint32_t par = 0;
     // host input: two pinned staging buffers and their device copies
@@ -448,7 +632,7 @@ struct pg_kfreq {
     std::vector<uint64_t> out_counts;
     bool aligned_stage = true;
     // packed reads: what one submit uploads (sequence bytes, offsets, lengths, flags, the piece list) as one block, two in rotation
-    int form = 0;              // the stream's input form: 0 none yet, 1 text, 2 reads
+    int form = 0;              // the stream's input form: 0 none yet, 1 FASTQ text, 2 reads, 3 FASTA text
     uint32_t piece = kReadPiece; // <= unit
     PgPinned<uint8_t> r_stage[2];
     PgDev<uint8_t> r_dev[2];
@@ -457,6 +641,8 @@ struct pg_kfreq {
     std::vector<uint2> r_work;
     std::string err;
 };
+
+static const char *const kFormName[4] = {"nothing", "FASTQ text", "packed reads", "FASTA text"};
 
 static uint64_t odd_cap_from_env() {
     if (const char *s = getenv("PGKFREQ_ODD_CAP")) { const long long v = atoll(s); if (v >= 1) return (uint64_t)v; }
@@ -520,6 +706,17 @@ static pg_status kf_unit(pg_kfreq *h, const uint8_t *p, uint64_t n) {
     const bool al = ((uintptr_t)p & 15) == 0;
     const bool lds = h->k <= kLdsMaxK;
     const size_t lds_bytes = lds ? (size_t)h->n_codes * sizeof(uint32_t) : 0;
+    if (h->form == 3) {
+        if (al) hipLaunchKernelGGL(k_kf_fa_lines<true>, dim3(n_tiles), dim3(kThreads), 0, h->ks, p, n, h->d.tile_ls, h->d.fa_tile);
+        else hipLaunchKernelGGL(k_kf_fa_lines<false>, dim3(n_tiles), dim3(kThreads), 0, h->ks, p, n, h->d.tile_ls, h->d.fa_tile);
+        if (al && lds) hipLaunchKernelGGL((k_kf_fa_count<true, true>), dim3(n_tiles), dim3(kThreads), lds_bytes, h->ks, h->d, p, n, n_tiles, h->k, h->par);
+        else if (al) hipLaunchKernelGGL((k_kf_fa_count<true, false>), dim3(n_tiles), dim3(kThreads), 0, h->ks, h->d, p, n, n_tiles, h->k, h->par);
+        else if (lds) hipLaunchKernelGGL((k_kf_fa_count<false, true>), dim3(n_tiles), dim3(kThreads), lds_bytes, h->ks, h->d, p, n, n_tiles, h->k, h->par);
+        else hipLaunchKernelGGL((k_kf_fa_count<false, false>), dim3(n_tiles), dim3(kThreads), 0, h->ks, h->d, p, n, n_tiles, h->k, h->par);
+        PG_HIP_TRY(h, hipGetLastError());
+        h->par ^= 1;
+        return kf_snapshot(h, n);
+    }
     if (al) hipLaunchKernelGGL(k_kf_lines<true>, dim3(n_tiles), dim3(kThreads), 0, h->ks, p, n, h->d.tile_nl);
     else hipLaunchKernelGGL(k_kf_lines<false>, dim3(n_tiles), dim3(kThreads), 0, h->ks, p, n, h->d.tile_nl);
     if (al && lds) hipLaunchKernelGGL((k_kf_count<true, true>), dim3(n_tiles), dim3(kThreads), lds_bytes, h->ks, h->d, p, n, n_tiles, h->k, h->par);
@@ -536,6 +733,7 @@ static pg_status kf_reset_device(pg_kfreq *h) {
     PG_HIP_TRY(h, hipMemsetAsync(h->d.odd_n, 0, sizeof(unsigned long long), h->ks));
     PG_HIP_TRY(h, hipMemsetAsync(h->d.err, 0, sizeof(uint32_t), h->ks));
     PG_HIP_TRY(h, hipMemsetAsync(h->d.state, 0, 2 * sizeof(KfState), h->ks));
+    PG_HIP_TRY(h, hipMemsetAsync(h->d.fa_state, 0, 2 * sizeof(KfFaState), h->ks));
     PG_HIP_TRY(h, hipStreamSynchronize(h->ks));
     h->par = 0;
     h->form = 0;
@@ -562,11 +760,13 @@ pg_status pg_kfreq_create(uint32_t kmer_size, int32_t device, pg_kfreq **out) {
     auto init = [&]() -> pg_status {
         PG_HIP_TRY(h, hipStreamCreateWithFlags(&h->ks.h, hipStreamNonBlocking));
         PG_HIP_TRY(h, hipStreamCreateWithFlags(&h->cs.h, hipStreamNonBlocking));
-        const size_t bytes[6] = {(size_t)h->n_codes * sizeof(unsigned long long), h->d.odd_cap * sizeof(uint4), sizeof(unsigned long long),
-                                 sizeof(uint32_t), 2 * sizeof(KfState), (kUnit / kTile) * sizeof(uint32_t)};
-        for (int i = 0; i < 6; i++) PG_HIP_TRY(h, h->mem[i].ensure(bytes[i]));
+        const size_t bytes[9] = {(size_t)h->n_codes * sizeof(unsigned long long), h->d.odd_cap * sizeof(uint4), sizeof(unsigned long long),
+                                 sizeof(uint32_t), 2 * sizeof(KfState), (kUnit / kTile) * sizeof(uint32_t), (kUnit / kTile) * sizeof(uint32_t),
+                                 2 * (kUnit / kTile) * sizeof(PgFaSum), 2 * sizeof(KfFaState)};
+        for (int i = 0; i < 9; i++) PG_HIP_TRY(h, h->mem[i].ensure(bytes[i]));
         h->d.hist = h->mem[0].as<unsigned long long>(); h->d.odd = h->mem[1].as<uint4>(); h->d.odd_n = h->mem[2].as<unsigned long long>();
         h->d.err = h->mem[3].as<uint32_t>(); h->d.state = h->mem[4].as<KfState>(); h->d.tile_nl = h->mem[5].as<uint32_t>();
+        h->d.tile_ls = h->mem[6].as<uint32_t>(); h->d.fa_tile = h->mem[7].as<PgFaSum>(); h->d.fa_state = h->mem[8].as<KfFaState>();
         PG_HIP_TRY(h, h->snap.ensure(kSnapRing * sizeof(unsigned long long)));
         for (auto &ev : h->snap_ev) PG_HIP_TRY(h, hipEventCreateWithFlags(&ev.h, hipEventDisableTiming));
         for (int i = 0; i < 2; i++) {
@@ -588,23 +788,23 @@ void pg_kfreq_destroy(pg_kfreq *h) {
     delete h;
 }
 
-pg_status pg_kfreq_submit(pg_kfreq *h, const void *data, uint64_t n_bytes, int32_t location) {
-    if (!h) return pg_fail<pg_kfreq>(nullptr, PG_ERR_INVALID_ARG, "pg_kfreq_submit: null handle");
+static pg_status kf_submit_text(pg_kfreq *h, const void *data, uint64_t n_bytes, int32_t location, int form, const char *fn) {
+    if (!h) return pg_fail<pg_kfreq>(nullptr, PG_ERR_INVALID_ARG, "%s: null handle", fn);
     if (!n_bytes) return PG_OK;
-    if (!data) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit: null data");
-    if (h->form == 2) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit: this stream holds packed reads (one input form per stream)");
-    if (location != PG_LOC_HOST && location != PG_LOC_DEVICE) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit: location must be PG_LOC_HOST or PG_LOC_DEVICE");
-    h->form = 1;
+    if (!data) return pg_fail(h, PG_ERR_INVALID_ARG, "%s: null data", fn);
+    if (h->form && h->form != form) return pg_fail(h, PG_ERR_INVALID_ARG, "%s: this stream holds %s (one input form per stream)", fn, kFormName[h->form]);
+    if (location != PG_LOC_HOST && location != PG_LOC_DEVICE) return pg_fail(h, PG_ERR_INVALID_ARG, "%s: location must be PG_LOC_HOST or PG_LOC_DEVICE", fn);
+    h->form = form;
     PG_HIP_TRY(h, hipSetDevice(h->device));
     const uint8_t *src = static_cast<const uint8_t *>(data);
     if (location == PG_LOC_DEVICE) {
         if (pg_ptr_kind(data, h->device) != PG_PTR_DEVICE)
-            return pg_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit: PG_LOC_DEVICE data is not device memory of device %d", h->device);
+            return pg_fail(h, PG_ERR_INVALID_ARG, "%s: PG_LOC_DEVICE data is not device memory of device %d", fn, h->device);
         for (uint64_t o = 0; o < n_bytes; o += h->unit)
             if (pg_status s = kf_unit(h, src + o, std::min<uint64_t>(h->unit, n_bytes - o))) return s;
         return PG_OK;
     }
-    if (location != PG_LOC_HOST) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit: location must be PG_LOC_HOST or PG_LOC_DEVICE");
+    if (location != PG_LOC_HOST) return pg_fail(h, PG_ERR_INVALID_ARG, "%s: location must be PG_LOC_HOST or PG_LOC_DEVICE", fn);
     // page-locked caller memory goes to the device as it is; anything else through the pinned staging buffers
     const bool pinned = pg_ptr_kind(data, h->device) == PG_PTR_PINNED;
     for (uint64_t o = 0; o < n_bytes; o += h->unit) {
@@ -634,12 +834,20 @@ pg_status pg_kfreq_submit(pg_kfreq *h, const void *data, uint64_t n_bytes, int32
     return PG_OK;
 }
 
+pg_status pg_kfreq_submit(pg_kfreq *h, const void *data, uint64_t n_bytes, int32_t location) {
+    return kf_submit_text(h, data, n_bytes, location, 1, "pg_kfreq_submit");
+}
+
+pg_status pg_kfreq_submit_fasta(pg_kfreq *h, const void *data, uint64_t n_bytes, int32_t location) {
+    return kf_submit_text(h, data, n_bytes, location, 3, "pg_kfreq_submit_fasta");
+}
+
 uint32_t pg_kfreq_reads_piece(const pg_kfreq *h) { return h ? h->piece : 0; }
 
 pg_status pg_kfreq_submit_reads(pg_kfreq *h, const uint8_t *seq_bytes, uint64_t n_seq_bytes, const uint64_t *byte_off, const uint32_t *l_seq,
                                 const uint8_t *reverse, uint64_t n_reads, uint32_t flags, int32_t location) {
     if (!h) return pg_fail<pg_kfreq>(nullptr, PG_ERR_INVALID_ARG, "pg_kfreq_submit_reads: null handle");
-    if (h->form == 1) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit_reads: this stream holds FASTQ text (one input form per stream)");
+    if (h->form && h->form != 2) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit_reads: this stream holds %s (one input form per stream)", kFormName[h->form]);
     if (flags & ~(uint32_t)PG_KFREQ_N_TO_T) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit_reads: unknown flags 0x%x", flags);
     if (location != PG_LOC_HOST && location != PG_LOC_DEVICE) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_kfreq_submit_reads: location must be PG_LOC_HOST or PG_LOC_DEVICE");
     if (!n_reads) return PG_OK;

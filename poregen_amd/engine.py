@@ -639,7 +639,8 @@ class KmerFreqResult:
 
 class KmerCounter:
     """Counts the k-mers of FASTQ bytes on the GPU (pg_kfreq_*). submit() takes the file's bytes in pieces cut anywhere: `bytes`,
-    a numpy uint8 array, or a CUDA torch.uint8 tensor (read in place, no host copy; kept alive until finish)."""
+    a numpy uint8 array, or a CUDA torch.uint8 tensor (read in place, no host copy; kept alive until finish). submit_fasta() takes a
+    FASTA the same way, submit_reads() packed BAM reads; one stream (up to finish) takes one of the three."""
 
     def __init__(self, k: int, device: int = 0):
         self._lib = _abi.load()
@@ -655,16 +656,24 @@ class KmerCounter:
         if st != 0:
             raise PgError(st, self._lib.pg_kfreq_last_error(self._h).decode())
 
-    def submit(self, piece):
+    def _submit_text(self, fn, piece):
         if hasattr(piece, "is_cuda") and piece.is_cuda:
             if piece.dtype.itemsize != 1 or not piece.is_contiguous():
                 raise ValueError("device pieces must be contiguous uint8 tensors")
             self._keep.append(piece)
-            self._check(self._lib.pg_kfreq_submit(self._h, C.c_void_p(piece.data_ptr()), piece.numel(), _abi.PG_LOC_DEVICE))
+            self._check(fn(self._h, C.c_void_p(piece.data_ptr()), piece.numel(), _abi.PG_LOC_DEVICE))
             return
         a = np.ascontiguousarray(np.frombuffer(piece, np.uint8) if isinstance(piece, (bytes, bytearray, memoryview)) else piece, dtype=np.uint8)
         if a.size:
-            self._check(self._lib.pg_kfreq_submit(self._h, C.c_void_p(a.ctypes.data), a.size, _abi.PG_LOC_HOST))
+            self._check(fn(self._h, C.c_void_p(a.ctypes.data), a.size, _abi.PG_LOC_HOST))
+
+    def submit(self, piece):
+        self._submit_text(self._lib.pg_kfreq_submit, piece)
+
+    def submit_fasta(self, piece):
+        """The next bytes of a FASTA (pg_kfreq_submit_fasta): '>' lines are headers, a record's sequence is the lines between two of
+        them joined, and its windows run across the line ends. Pieces as for submit()."""
+        self._submit_text(self._lib.pg_kfreq_submit_fasta, piece)
 
     @property
     def reads_piece(self) -> int:
@@ -725,11 +734,11 @@ class KmerCounter:
             pass
 
 
-def kmer_freq(data, k: int, device: int = 0) -> KmerFreqResult:
-    """One-shot: the k-mer counts of a whole FASTQ given as bytes / numpy uint8 / CUDA uint8 tensor."""
+def kmer_freq(data, k: int, device: int = 0, fasta: bool = False) -> KmerFreqResult:
+    """One-shot: the k-mer counts of a whole FASTQ (fasta=True: a whole FASTA) given as bytes / numpy uint8 / CUDA uint8 tensor."""
     kc = KmerCounter(k, device)
     try:
-        kc.submit(data)
+        (kc.submit_fasta if fasta else kc.submit)(data)
         return kc.finish()
     finally:
         kc.close()

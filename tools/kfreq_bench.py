@@ -15,7 +15,12 @@ memory. Measured, each as the best of --reps runs after one warm-up:
               k = 5, 9, 12 and from page-locked host memory at k = 9, each next to the FASTQ path on the same reads in the same run
               (rates in G bases/s, since the two forms differ in bytes per base), and the CLI on a BAM of the first --bam-mb
               megabytes of the FASTQ (written here with zlib level 1) next to the CLI on that FASTQ.
---cases picks a subset (device,host,cli,cpu,reads).
+  fasta       a seeded synthetic FASTA (60-column lines, ~200-byte headers, lognormal record lengths, 0.1 % N) through
+              KmerCounter.submit_fasta next to the FASTQ above through submit, in the same run: device-resident and from page-locked
+              host memory, k = 5 and 9. Rates in G windows/s (the windows counted, from the result itself): a FASTA is nearly all
+              sequence, a FASTQ about half, so bytes per second do not compare.
+--cases picks a subset of device,host,cli,cpu,reads,fasta; the default is all but fasta, which has a profile of its own:
+    tools/kfreq_bench.py --cases fasta --out profiles/kfreq_fasta_bench.json
 Prints one JSON object and writes it to --out.
 """
 import argparse
@@ -45,6 +50,31 @@ def synth(n_bytes, seed=1, n_rate=0.001):
         for L in lens:
             hdr = b"@%08x-1f2e-4d3c-9b8a-%012d runid=0f1e2d3c read=%d ch=%d start_time=2023-01-01T00:00:00Z\n" % (i, i, i, i % 512)
             rec = hdr + seq[o:o + L].tobytes() + b"\n+\n" + qual[o:o + L].tobytes() + b"\n"
+            parts.append(rec)
+            total += len(rec); o += L; i += 1
+            if total >= n_bytes:
+                break
+    return b"".join(parts)
+
+
+def synth_fasta(n_bytes, seed=2, n_rate=0.001, width=60):
+    """Records like a transcriptome FASTA: a header of about 200 bytes, the sequence wrapped at `width` columns."""
+    rng = np.random.default_rng(seed)
+    parts, total, i = [], 0, 0
+    lut = np.frombuffer(b"ACGT", np.uint8)
+    while total < n_bytes:
+        lens = np.clip(rng.lognormal(8.5, 0.8, 4096), 50, 200_000).astype(np.int64)
+        seq = lut[rng.integers(0, 4, int(lens.sum()))]
+        seq[rng.random(seq.size) < n_rate] = ord("N")
+        o = 0
+        for L in lens:
+            hdr = (b">ENST%011d.%d cdna chromosome:GRCh38:%d:%d:%d:1 gene:ENSG%011d.%d gene_biotype:protein_coding transcript_biotype:protein_coding "
+                   b"gene_symbol:SYN%d description:synthetic record %d of the benchmark [Source:kfreq_bench;Acc:%08d]\n") % (i, i % 9, i % 22 + 1, i * 7, i * 7 + L, i, i % 5, i, i, i)
+            body = seq[o:o + L]
+            full = (L // width) * width
+            lines = np.empty((L // width, width + 1), np.uint8)
+            lines[:, :width] = body[:full].reshape(-1, width); lines[:, width] = 10
+            rec = hdr + lines.tobytes() + (body[full:].tobytes() + b"\n" if L > full else b"")
             parts.append(rec)
             total += len(rec); o += L; i += 1
             if total >= n_bytes:
@@ -177,6 +207,28 @@ def main():
         res["host_pinned"] = {"k9_s": round(s_host, 4), "k9_GBps": gbps(n, s_host), "h2d_GBps": gbps(n, s_h2d),
                               "fraction_of_h2d": round(s_h2d / s_host, 3)}
 
+    if "fasta" in cases:
+        fa = synth_fasta(n)
+        fa_dev = torch.frombuffer(bytearray(fa), dtype=torch.uint8).cuda()
+        fa_pin = torch.frombuffer(bytearray(fa), dtype=torch.uint8).pin_memory().numpy()
+        fr = {"fasta_bytes": len(fa), "fastq_bytes": n}
+        for k in (5, 9):
+            kc = KmerCounter(k)
+            windows = {}
+            for name, submit, d_in, h_in in (("fasta", kc.submit_fasta, fa_dev, fa_pin), ("fastq", kc.submit, dev, pin_np)):
+                submit(d_in)
+                r = kc.finish()
+                windows[name] = int(r.counts.sum()) + int(r.odd_counts.sum())
+                s_d = timed(lambda: (submit(d_in), kc.finish()), a.reps)
+                s_h = timed(lambda: (submit(h_in), kc.finish()), a.reps)
+                fr[f"{name}_k{k}"] = {"windows": windows[name], "device_s": round(s_d, 4), "device_Gwindows": round(windows[name] / s_d / 1e9, 2),
+                                      "device_GBps": gbps(len(fa) if name == "fasta" else n, s_d), "host_pinned_s": round(s_h, 4),
+                                      "host_pinned_Gwindows": round(windows[name] / s_h / 1e9, 2)}
+            kc.close()
+            fr[f"fasta_over_fastq_device_k{k}"] = round(fr[f"fasta_k{k}"]["device_Gwindows"] / fr[f"fastq_k{k}"]["device_Gwindows"], 3)
+        res["fasta"] = fr
+        del fa_dev, fa_pin
+
     exe = os.path.join(ROOT, "bin", "poregen")
 
     def cli(args, timeout=600):
@@ -243,7 +295,7 @@ def main():
         res["cpu_numpy_1core_k9"] = {"bytes": nb, "s": round(s, 3), "GBps": gbps(nb, s), "windows": windows}
     line = json.dumps(res)
     print(line)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         f.write(line + "\n")
 
