@@ -600,6 +600,49 @@ pg_status pg_pamean_sync(pg_pamean *h);
 /* The dataset summary of every read since the last finish; the handle is reset afterwards, also after an error. */
 pg_status pg_pamean_finish(pg_pamean *h, pg_pamean_result *out);
 
+/* ---- svb-zd signal blocks decoded on the device ----------------------------------------------------------------------------------
+ * A BLOW5 record with signal compression svb-zd holds its samples as a block: u32 count, ceil(count / 4) control bytes (2 bits per
+ * value: byte length - 1, value i in bits 2 (i & 3) of byte i >> 2), then the values' 1-4 little-endian data bytes; the samples are the
+ * running sum, modulo 2^32 from 0, of the zig-zag decoded values, cut to 16 bits. Every code of every length is valid input (a small
+ * value in a long code, a non-zero top byte, a wrapping sum), unused bytes behind the data are accepted, and a 4-byte block with count 0
+ * is an empty read. The blocks of n_reads reads lie in one byte array, read r in [block_off[r], block_off[r + 1]), at any byte offset.
+ * A block is corrupt when it is shorter than 4 bytes, when the control bytes of its count or one data byte per value do not fit (found
+ * on the host, before anything is sized by the count), or when its byte lengths sum to more than its data bytes (found on the device).
+ * A corrupt block is flagged, never an error of the call: no load for it leaves the block, nothing is stored outside its read's span.
+ * No CPU fallback: PG_ERR_NO_DEVICE without a GPU. */
+typedef struct pg_sigdec pg_sigdec;
+pg_status pg_sigdec_create(int32_t device, pg_sigdec **out);
+void      pg_sigdec_destroy(pg_sigdec *h);
+const char *pg_sigdec_last_error(const pg_sigdec *h); /* h may be NULL: error of the last failed pg_sigdec_create */
+/* counts_out (host u32[n_reads]): the samples each read decodes to -- the block's count, 0 for a block the host's checks refuse. */
+pg_status pg_sigdec_counts(pg_sigdec *h, const void *blocks, uint64_t n_block_bytes, const uint64_t *block_off, uint64_t n_reads, int32_t location,
+                           uint32_t *counts_out);
+/* Decodes read r to sig_out_device[sig_off[r] ... sig_off[r] + count(r)) and returns when the samples are there. location says where
+ * blocks lies: PG_LOC_HOST, any host memory (page-locked memory is copied from directly, other memory through a pinned buffer), or
+ * PG_LOC_DEVICE, memory of the handle's device, complete before the call. block_off, sig_off (n_reads + 1 non-decreasing offsets each;
+ * a span shorter than its read's count is PG_ERR_INVALID_ARG) and bad_out (n_reads bytes: 1 for a corrupt block, whose span then holds
+ * unspecified samples) are host memory. Samples outside [sig_off[r], sig_off[r] + count(r)) are not written. */
+pg_status pg_sigdec_decode(pg_sigdec *h, const void *blocks, uint64_t n_block_bytes, const uint64_t *block_off, uint64_t n_reads, int32_t location,
+                           int16_t *sig_out_device, const uint64_t *sig_off, uint8_t *bad_out);
+
+typedef struct {
+    uint64_t n_reads;
+    int32_t location;              /* PG_LOC_HOST or PG_LOC_DEVICE: where blocks lies */
+    int32_t reserved;
+    const void *blocks;
+    uint64_t n_block_bytes;
+    const uint64_t *block_off;     /* host, n_reads + 1 */
+} pg_svb_batch;
+/* pg_pamean_submit for a batch whose samples are still svb-zd blocks: they are decoded on the device into a buffer of the handle, the
+ * reads back to back, and that buffer takes the PG_LOC_DEVICE path of pg_pamean_submit. digitisation, offset and range are host arrays
+ * of n_reads values; nothing of the batch is needed after the call returns. A corrupt block fails the call with PG_ERR_INPUT -- the
+ * text names the first such read's index in the batch and says "corrupt streamvbyte block" --, nothing of the batch is counted and the
+ * handle stays usable. */
+pg_status pg_pamean_submit_svb(pg_pamean *h, const pg_svb_batch *svb, const double *digitisation, const double *offset, const double *range,
+                               double *means_out);
+/* the samples pg_pamean_submit_svb has decoded on the device since create */
+uint64_t  pg_pamean_svb_samples(const pg_pamean *h);
+
 /* ---- model: the k-mer model from the TEXT of dump files, parsed and reduced on the device ---------------------------------------------
  * What scripts/poregen.sh:54-85 (tr ';,' '\n' | tail -n +2 | datamash median 1 / sstdev 1) and :33-52 (awk comma counts | datamash
  * median) compute per dump file, for files that already exist: written by the reference, by an earlier run, with -d, or several

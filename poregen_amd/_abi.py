@@ -42,6 +42,8 @@ EXPORTS = [
     "pg_kfreq_create", "pg_kfreq_destroy", "pg_kfreq_last_error", "pg_kfreq_submit", "pg_kfreq_submit_reads", "pg_kfreq_submit_fasta", "pg_kfreq_reads_piece", "pg_kfreq_sync", "pg_kfreq_finish",
     "pg_fscore_create", "pg_fscore_destroy", "pg_fscore_last_error", "pg_fscore_submit", "pg_fscore_sync", "pg_fscore_finish",
     "pg_pamean_create", "pg_pamean_destroy", "pg_pamean_last_error", "pg_pamean_submit", "pg_pamean_sync", "pg_pamean_finish",
+    "pg_pamean_submit_svb", "pg_pamean_svb_samples",
+    "pg_sigdec_create", "pg_sigdec_destroy", "pg_sigdec_last_error", "pg_sigdec_counts", "pg_sigdec_decode",
     "pg_dmodel_create", "pg_dmodel_destroy", "pg_dmodel_last_error", "pg_dmodel_submit", "pg_dmodel_sync", "pg_dmodel_finish", "pg_dmodel_format",
     "pg_transform_model", "pg_transform_free",
 ]
@@ -128,6 +130,11 @@ class PgPameanBatch(C.Structure):
 
 class PgPameanResult(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_fallback", C.c_uint64), ("n_samples", C.c_uint64), ("mean", C.c_double), ("sstdev", C.c_double)]
+
+
+class PgSvbBatch(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("location", C.c_int32), ("reserved", C.c_int32), ("blocks", C.c_void_p),
+                ("n_block_bytes", C.c_uint64), ("block_off", C.c_void_p)]
 
 
 class PgDmodelInfo(C.Structure):
@@ -249,6 +256,13 @@ def load():
     lib.pg_pamean_submit.argtypes = [vp, C.POINTER(PgPameanBatch), vp]; lib.pg_pamean_submit.restype = i32
     lib.pg_pamean_sync.argtypes = [vp]; lib.pg_pamean_sync.restype = i32
     lib.pg_pamean_finish.argtypes = [vp, C.POINTER(PgPameanResult)]; lib.pg_pamean_finish.restype = i32
+    lib.pg_pamean_submit_svb.argtypes = [vp, C.POINTER(PgSvbBatch), vp, vp, vp, vp]; lib.pg_pamean_submit_svb.restype = i32
+    lib.pg_pamean_svb_samples.argtypes = [vp]; lib.pg_pamean_svb_samples.restype = C.c_uint64
+    lib.pg_sigdec_create.argtypes = [i32, C.POINTER(vp)]; lib.pg_sigdec_create.restype = i32
+    lib.pg_sigdec_destroy.argtypes = [vp]; lib.pg_sigdec_destroy.restype = None
+    lib.pg_sigdec_last_error.argtypes = [vp]; lib.pg_sigdec_last_error.restype = C.c_char_p
+    lib.pg_sigdec_counts.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, i32, vp]; lib.pg_sigdec_counts.restype = i32
+    lib.pg_sigdec_decode.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, i32, vp, vp, vp]; lib.pg_sigdec_decode.restype = i32
     lib.pg_dmodel_create.argtypes = [i32, u32, C.POINTER(vp)]; lib.pg_dmodel_create.restype = i32
     lib.pg_dmodel_destroy.argtypes = [vp]; lib.pg_dmodel_destroy.restype = None
     lib.pg_dmodel_last_error.argtypes = [vp]; lib.pg_dmodel_last_error.restype = C.c_char_p

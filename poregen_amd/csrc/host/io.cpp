@@ -1,5 +1,6 @@
 // io.cpp -- memory-mapped files, ASCII SLOW5 / BLOW5 reader, FASTA/FASTQ index, PAF + ss tokeniser.
 #include "pg_host.h"
+#include "../pg_svb.h"
 
 // zstd record compression (`make zstd=1` in the reference: /root/reference/Makefile:12-13,67 links -lzstd into slow5lib). Here libzstd is
 // looked up at run time, once, so that neither bin/poregen nor the test shim carries a link-time dependency: a BLOW5 file with zstd
@@ -246,10 +247,10 @@ static bool svb_decode(const unsigned char *in, size_t in_len, uint32_t n, std::
     return true;
 }
 
-bool Slow5File::decode_blow5(const Loc &l, Slow5Rec &out, std::string &err, std::string *read_id) const {
-    const unsigned char *body = (const unsigned char *)f_.data + l.off;
-    size_t blen = l.len;
-    std::vector<unsigned char> inflated;
+// the record's body as the fields lie in it: the mapped bytes, or `inflated` for zlib / zstd records
+bool Slow5File::body_of(const Loc &l, std::vector<unsigned char> &inflated, const unsigned char *&body, size_t &blen, std::string &err) const {
+    body = (const unsigned char *)f_.data + l.off;
+    blen = l.len;
     if (rec_press_ == 2) {
         if (!zstd_record(body, blen, inflated, err)) return false;
         body = inflated.data(); blen = inflated.size();
@@ -269,7 +270,13 @@ bool Slow5File::decode_blow5(const Loc &l, Slow5Rec &out, std::string &err, std:
         }
         body = inflated.data(); blen = inflated.size();
     }
-    size_t p = 0;
+    return true;
+}
+
+// read id, calibration and len_raw_signal of a body; p: where the signal starts
+bool Slow5File::head_of(const unsigned char *body, size_t blen, std::string *read_id, double &dig, double &off, double &range, uint64_t &len,
+                        size_t &p, std::string &err) const {
+    p = 0;
     auto need = [&](size_t n) { return p + n <= blen; };
     uint16_t il;
     if (!need(2)) { err = "corrupt BLOW5 record"; return false; }
@@ -277,10 +284,32 @@ bool Slow5File::decode_blow5(const Loc &l, Slow5Rec &out, std::string &err, std:
     if (!need(4 + 32 + 8)) { err = "corrupt BLOW5 record"; return false; }
     if (read_id) { read_id->assign((const char *)body + 2, il); if (!read_id->empty() && read_id->back() == '\0') read_id->pop_back(); }
     p += 4; // read_group
-    double sampling;
-    memcpy(&out.digitisation, body + p, 8); memcpy(&out.offset, body + p + 8, 8); memcpy(&out.range, body + p + 16, 8);
-    memcpy(&sampling, body + p + 24, 8); p += 32;
-    uint64_t len; memcpy(&len, body + p, 8); p += 8;
+    memcpy(&dig, body + p, 8); memcpy(&off, body + p + 8, 8); memcpy(&range, body + p + 16, 8); // (+ 24: sampling_rate)
+    p += 32;
+    memcpy(&len, body + p, 8); p += 8;
+    return true;
+}
+
+// svb-zd: in the record len_raw_signal holds the BYTE length of the compressed signal; the compressed
+// block is u32 count + streamvbyte of zig-zag deltas of the int16 samples widened to int32 (pg_svb.h)
+bool Slow5File::record_svb(size_t i, std::string &read_id, SvbView &v, std::vector<unsigned char> &inflated, std::string &err) const {
+    const unsigned char *body; size_t blen, p;
+    if (!body_of(recs_[i], inflated, body, blen, err)) return false;
+    uint64_t clen;
+    if (!head_of(body, blen, &read_id, v.digitisation, v.offset, v.range, clen, p, err)) return false;
+    if (clen > blen - p || clen < 4) { err = "corrupt BLOW5 record (svb-zd)"; return false; }
+    memcpy(&v.count, body + p, 4);
+    if (pg_svb_check(clen, v.count) != PG_SVB_OK) { err = "corrupt streamvbyte block"; return false; } // (what svb_decode refuses before it looks at the control bytes)
+    v.block = body + p; v.len = clen;
+    return true;
+}
+
+bool Slow5File::decode_blow5(const Loc &l, Slow5Rec &out, std::string &err, std::string *read_id) const {
+    const unsigned char *body; size_t blen, p;
+    std::vector<unsigned char> inflated;
+    if (!body_of(l, inflated, body, blen, err)) return false;
+    uint64_t len;
+    if (!head_of(body, blen, read_id, out.digitisation, out.offset, out.range, len, p, err)) return false;
     if (sig_press_ == 0) {
         if (len > (blen - p) / 2) { err = "corrupt BLOW5 record (signal)"; return false; } // (before the vector is sized by a number the file supplied)
         out.raw.resize(len);

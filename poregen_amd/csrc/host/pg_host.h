@@ -43,6 +43,13 @@ public:
     uint64_t record_bytes(size_t i) const { return recs_[i].len; }
     bool record(size_t i, std::string &read_id, Slow5Rec &out, std::string &err) const;
     bool record_view(size_t i, std::string &read_id, RawView &v, std::string &err) const; // has_raw_views() only
+    // svb-zd BLOW5 (record compression none, zlib or zstd): a record's calibration and its signal block (pg_svb.h) as a byte range, for a
+    // decoder elsewhere. The block has passed pg_svb_check and lies in the mapped file or, for compressed records, in `inflated`, which
+    // the caller keeps for as long as it needs the block.
+    struct SvbView { const unsigned char *block = nullptr; uint64_t len = 0; uint32_t count = 0; double digitisation = 0, offset = 0, range = 0; };
+    bool has_svb_views() const { return binary_ && sig_press_ == 1; }
+    bool records_compressed() const { return rec_press_ != 0; } // the blocks then lie in `inflated`, else in the mapped file
+    bool record_svb(size_t i, std::string &read_id, SvbView &v, std::vector<unsigned char> &inflated, std::string &err) const; // has_svb_views() only
     bool is_binary() const { return binary_; }
     const std::vector<std::string> &ids_in_file_order() const { return order_; }
 private:
@@ -57,6 +64,9 @@ private:
     std::vector<Loc> recs_; // open_walk: every record, in file order
     bool index_ascii(std::string &err);
     bool index_blow5(std::string &err);
+    bool body_of(const Loc &l, std::vector<unsigned char> &inflated, const unsigned char *&body, size_t &blen, std::string &err) const;
+    bool head_of(const unsigned char *body, size_t blen, std::string *read_id, double &dig, double &off, double &range, uint64_t &len, size_t &p,
+                 std::string &err) const;
     bool decode_blow5(const Loc &l, Slow5Rec &out, std::string &err, std::string *read_id = nullptr) const;
     bool parse_ascii(const Loc &l, Slow5Rec &out, const std::string &label, std::string &err) const;
     bool view_blow5(const Loc &l, RawView &v, std::string &err, std::string *read_id = nullptr) const;

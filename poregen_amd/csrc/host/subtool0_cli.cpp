@@ -1,6 +1,7 @@
 // subtool0_cli.cpp -- `poregen subtool0` (src/subtool0.c, src/poregen.cpp:24-180 of the reference) and `poregen pa_stats`, over
 // libpgmove's pg_pamean_* (include/pgmove.h). Host work here: options, the file-order record walk, decoding records on a thread pool
-// while the device works on the batch before, and printing.
+// while the device works on the batch before, and printing. Records with svb-zd signals are only inflated here: their signal blocks go
+// to the device as they lie in the record and are decoded there (pg_pamean_submit_svb).
 //
 // Rules kept from the reference, with its lines (src/subtool0.c):
 //   * optstring "t:B:K:v:o:hV" and the long options threads, batchsize, max-bytes, verbose, help, version, output, debug-break (:16-25,
@@ -91,6 +92,10 @@ struct HostBatch {
     std::vector<uint64_t> off;            // n + 1
     std::vector<double> dig, offs, rng, means;
     PgPinned<int16_t> sig; // the decoded samples are written here once and go to the device by DMA from here
+    // svb-zd files: the signal blocks back to back instead, and where each lies (off: the samples they will decode to)
+    bool svb = false;
+    PgPinned<unsigned char> blocks;
+    std::vector<uint64_t> block_off;      // n + 1
 };
 
 class Walker {
@@ -98,6 +103,7 @@ class Walker {
     Walker(const pgh::Slow5File &f, unsigned n_threads) : f_(f), nt_(n_threads) {}
     // decodes records [first, first + n) into b; false (err) when one of them cannot be decoded
     bool fill(HostBatch &b, size_t first, size_t n, std::string &err) {
+        if (f_.has_svb_views()) return fill_svb(b, first, n, err);
         b.n = n;
         b.ids.assign(n, std::string()); b.off.assign(n + 1, 0);
         b.dig.resize(n); b.offs.resize(n); b.rng.resize(n); b.means.assign(n, 0.0);
@@ -136,16 +142,69 @@ class Walker {
         return true;
     }
 
+    // svb-zd: the headers of records [first, first + n) parsed, their blocks copied to b.blocks. Uncompressed records: the blocks are
+    // located first and copied once, from the mapping. zlib / zstd records: every thread inflates its run of records through one
+    // buffer and keeps the blocks, back to back, in a buffer of its own that lasts from batch to batch; the runs are then copied to
+    // their places. (Keeping every inflated record until the offsets are known cost more in fresh pages than the host decoder took.)
+    bool fill_svb(HostBatch &b, size_t first, size_t n, std::string &err) {
+        b.n = n; b.svb = true;
+        b.ids.assign(n, std::string()); b.off.assign(n + 1, 0); b.block_off.assign(n + 1, 0);
+        b.dig.resize(n); b.offs.resize(n); b.rng.resize(n); b.means.assign(n, 0.0);
+        const bool packed = f_.records_compressed();
+        std::vector<pgh::Slow5File::SvbView> views(packed ? 0 : n);
+        std::vector<std::string> errs(n);
+        std::atomic<bool> bad{false};
+        if (runs_.size() < nt_) runs_.resize(nt_);
+        on_runs(n, [&](unsigned t, size_t lo, size_t hi) {
+            std::vector<unsigned char> body;
+            if (packed) runs_[t].clear();
+            for (size_t i = lo; i < hi; i++) {
+                pgh::Slow5File::SvbView one;
+                pgh::Slow5File::SvbView &v = packed ? one : views[i];
+                if (!f_.record_svb(first + i, b.ids[i], v, body, errs[i])) { bad = true; continue; }
+                b.off[i + 1] = v.count; b.block_off[i + 1] = v.len;
+                b.dig[i] = v.digitisation; b.offs[i] = v.offset; b.rng[i] = v.range;
+                if (packed) runs_[t].insert(runs_[t].end(), v.block, v.block + v.len);
+            }
+        });
+        if (bad) {
+            for (size_t i = 0; i < n; i++) {
+                if (errs[i].empty()) { // a block in front of the first refused record may be one the device would refuse: the first error of the batch is reported
+                    pgh::Slow5Rec rec;
+                    std::string id;
+                    if (f_.record(first + i, id, rec, errs[i])) continue;
+                }
+                err = "record " + std::to_string(first + i) + ": " + errs[i];
+                return false;
+            }
+        }
+        for (size_t i = 0; i < n; i++) { b.off[i + 1] += b.off[i]; b.block_off[i + 1] += b.block_off[i]; }
+        const size_t want = std::max<uint64_t>(b.block_off[n], 1);
+        if (b.blocks.ensure(want, want + want / 4) != hipSuccess) {
+            err = "cannot allocate page-locked memory for the samples";
+            return false;
+        }
+        unsigned char *dst = b.blocks.p;
+        on_runs(n, [&](unsigned t, size_t lo, size_t hi) {
+            if (packed) { if (!runs_[t].empty()) memcpy(dst + b.block_off[lo], runs_[t].data(), runs_[t].size()); return; }
+            for (size_t i = lo; i < hi; i++) memcpy(dst + b.block_off[i], views[i].block, views[i].len);
+        });
+        return true;
+    }
+
   private:
     // every thread takes a contiguous run of the n items
-    void on_threads(size_t n, const std::function<void(size_t)> &fn) {
+    void on_runs(size_t n, const std::function<void(unsigned, size_t, size_t)> &fn) {
         const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(nt_, n / 64 + 1));
-        if (nt == 1) { for (size_t i = 0; i < n; i++) fn(i); return; }
+        if (nt == 1) { fn(0, 0, n); return; }
         std::vector<std::thread> pool;
-        for (unsigned t = 0; t < nt; t++)
-            pool.emplace_back([&, t] { for (size_t i = n * t / nt, e = n * (t + 1) / nt; i < e; i++) fn(i); });
+        for (unsigned t = 0; t < nt; t++) pool.emplace_back([&, t] { fn(t, n * t / nt, n * (t + 1) / nt); });
         for (auto &th : pool) th.join();
     }
+    void on_threads(size_t n, const std::function<void(size_t)> &fn) {
+        on_runs(n, [&](unsigned, size_t lo, size_t hi) { for (size_t i = lo; i < hi; i++) fn(i); });
+    }
+    std::vector<std::vector<unsigned char>> runs_; // fill_svb: the blocks of each thread's run
     const pgh::Slow5File &f_;
     unsigned nt_;
 };
@@ -180,36 +239,62 @@ void walk(const char *tool, const char *path, const Opts &opt, StatsTexts *stats
     const size_t n_batches = cuts.size() - 1;
     HostBatch hb[2];
     double t_decode = 0, t_wait = 0;
+    auto parse_error = [&]() { S0_ERROR(tool, "Error parsing the record: %s", err.c_str()); exit(EXIT_FAILURE); };
     auto fill = [&](size_t k) {
         const double a = now();
-        if (!w.fill(hb[k & 1], cuts[k], cuts[k + 1] - cuts[k], err)) { S0_ERROR(tool, "Error parsing the record: %s", err.c_str()); exit(EXIT_FAILURE); }
+        if (!w.fill(hb[k & 1], cuts[k], cuts[k + 1] - cuts[k], err)) parse_error();
         t_decode += now() - a;
     };
+    auto submit = [&](size_t k) {
+        HostBatch &b = hb[k & 1];
+        pg_status st;
+        if (b.svb) {
+            pg_svb_batch sb{};
+            sb.n_reads = b.n; sb.location = PG_LOC_HOST;
+            sb.blocks = b.blocks.p; sb.n_block_bytes = b.block_off[b.n]; sb.block_off = b.block_off.data();
+            st = pg_pamean_submit_svb(h, &sb, b.dig.data(), b.offs.data(), b.rng.data(), b.means.data());
+            unsigned long long r = 0;
+            if (st == PG_ERR_INPUT && sscanf(pg_pamean_last_error(h), "pg_pamean_submit_svb: read %llu: corrupt streamvbyte block", &r) == 1) {
+                err = "record " + std::to_string(cuts[k] + r) + ": corrupt streamvbyte block"; // a block only the device can refuse: the host decoder's words
+                parse_error();
+            }
+        } else {
+            pg_pamean_batch pb{};
+            pb.n_reads = b.n; pb.location = PG_LOC_HOST;
+            pb.sig = b.sig.p; pb.sig_off = b.off.data();
+            pb.digitisation = b.dig.data(); pb.offset = b.offs.data(); pb.range = b.rng.data();
+            st = pg_pamean_submit(h, &pb, b.means.data());
+        }
+        if (st != PG_OK) { S0_ERROR(tool, "%s", pg_pamean_last_error(h)); exit(EXIT_FAILURE); }
+    };
+    // Batch k + 1 is decoded while the device works on batch k. A batch of svb-zd blocks is submitted before batch k is printed: a record
+    // that cannot be decoded ends the run with the batch before its own unprinted, whether the host refuses it (fill) or the device (submit).
     std::string out;
-    if (n_batches) fill(0);
+    if (n_batches) { fill(0); submit(0); }
     for (size_t k = 0; k < n_batches; k++) {
         HostBatch &b = hb[k & 1];
-        pg_pamean_batch pb{};
-        pb.n_reads = b.n; pb.location = PG_LOC_HOST;
-        pb.sig = b.sig.p; pb.sig_off = b.off.data();
-        pb.digitisation = b.dig.data(); pb.offset = b.offs.data(); pb.range = b.rng.data();
-        if (pg_pamean_submit(h, &pb, b.means.data()) != PG_OK) { S0_ERROR(tool, "%s", pg_pamean_last_error(h)); exit(EXIT_FAILURE); }
-        if (k + 1 < n_batches) fill(k + 1); // the next batch is decoded while the device works on this one
+        const bool more = k + 1 < n_batches;
+        if (more) fill(k + 1);
         const double a = now();
         if (pg_pamean_sync(h) != PG_OK) { S0_ERROR(tool, "%s", pg_pamean_last_error(h)); exit(EXIT_FAILURE); }
         t_wait += now() - a;
-        if (stats) continue;
-        out.clear();
-        char num[512];
-        for (size_t i = 0; i < b.n; i++) {
-            if (b.off[i + 1] == b.off[i]) continue;
-            const int len = snprintf(num, sizeof num, "%f", b.means[i]);
-            out += b.ids[i]; out += '\t'; out.append(num, (size_t)len); out += '\n';
+        const bool early = more && hb[(k + 1) & 1].svb;
+        if (early) submit(k + 1);
+        if (!stats) {
+            out.clear();
+            char num[512];
+            for (size_t i = 0; i < b.n; i++) {
+                if (b.off[i + 1] == b.off[i]) continue;
+                const int len = snprintf(num, sizeof num, "%f", b.means[i]);
+                out += b.ids[i]; out += '\t'; out.append(num, (size_t)len); out += '\n';
+            }
+            fwrite(out.data(), 1, out.size(), stdout);
         }
-        fwrite(out.data(), 1, out.size(), stdout);
+        if (more && !early) submit(k + 1);
     }
     pg_pamean_result r;
     if (pg_pamean_finish(h, &r) != PG_OK) { S0_ERROR(tool, "%s", pg_pamean_last_error(h)); exit(EXIT_FAILURE); }
+    const unsigned long long on_device = pg_pamean_svb_samples(h);
     pg_pamean_destroy(h);
     if (stats) {
         if (r.n_samples < 2) { S0_ERROR(tool, "%s holds %llu pA values: the sample standard deviation needs at least 2", path, (unsigned long long)r.n_samples); exit(EXIT_FAILURE); }
@@ -221,6 +306,7 @@ void walk(const char *tool, const char *path, const Opts &opt, StatsTexts *stats
     fflush(stdout);
     fprintf(stderr, "[%s] %llu records, %llu samples, %llu finished on the host; host decode %.3f s, waiting for the device %.3f s, total %.3f s\n", tool,
             (unsigned long long)r.n_reads, (unsigned long long)r.n_samples, (unsigned long long)r.n_fallback, t_decode, t_wait, now() - t0);
+    if (g_log_level >= 4) fprintf(stderr, "[%s] %llu samples decoded from svb-zd blocks on the device\n", tool, on_device); // (-v 4 and above)
 }
 
 int run(const char *tool, int argc, char **argv, bool stats) {

@@ -239,6 +239,27 @@ extern "C" long pgt_slow5_walk(const char *path, char *ids, size_t cap, uint64_t
     return (long)f.n_records();
 }
 
+// ---- svb-zd blocks (pg_svb.h): the checks the host makes before a block reaches the device, and the walk that hands the blocks over --
+#include "pg_svb.h"
+extern "C" int pgt_svb_check(uint64_t len, uint32_t count) { return pg_svb_check(len, count); }
+extern "C" uint64_t pgt_svb_nctrl(uint32_t count) { return pg_svb_nctrl(count); }
+extern "C" void pgt_svb_levels(uint32_t *out3) { out3[0] = PG_SVB_LANE_VALUES; out3[1] = PG_SVB_WAVE_VALUES; out3[2] = PG_SVB_PIECE_VALUES; }
+// record count, or -1 (errbuf: "record <i>: <message>"); counts and block lengths of up to max records, the blocks back to back in blocks
+extern "C" long pgt_slow5_svb_walk(const char *path, uint32_t *counts, uint64_t *lens, size_t max, uint8_t *blocks, size_t cap, char *errbuf, size_t ecap) {
+    pgh::Slow5File f; std::string err;
+    if (!f.open_walk(path, err)) { put_err(err, errbuf, ecap); return -1; }
+    if (!f.has_svb_views()) { put_err("no svb-zd signals", errbuf, ecap); return -1; }
+    size_t at = 0;
+    for (size_t i = 0; i < f.n_records(); i++) {
+        std::string id; pgh::Slow5File::SvbView v; std::vector<unsigned char> inflated;
+        if (!f.record_svb(i, id, v, inflated, err)) { put_err("record " + std::to_string(i) + ": " + err, errbuf, ecap); return -1; }
+        if (i < max) { counts[i] = v.count; lens[i] = v.len; }
+        if (at + v.len <= cap) memcpy(blocks + at, v.block, v.len);
+        at += v.len;
+    }
+    return (long)f.n_records();
+}
+
 // ---- poregen model (pg_dumphost.h, host/pg_dumpdir.h): the host path of a dump file and the directory listing / merging ------------
 #include "pg_dumphost.h"
 #include "host/pg_dumpdir.h"

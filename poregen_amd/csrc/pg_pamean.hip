@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include "pg_pamean.h"
 #include "pg_hip_host.h"
+#include "pg_sigdec.h"
 
 #include <algorithm>
 #include <cmath>
@@ -167,6 +168,11 @@ struct pg_pamean {
     PgPinned<PaOut> h_out;
     std::vector<uint64_t> h_sig_off;                 // the batch's offsets on the host
     std::vector<uint2> h_extra;
+    // pg_pamean_submit_svb: the decoder, its batch's offsets and flags, the samples it has decoded since create
+    PgSvbCore svb;
+    std::vector<uint64_t> svb_off;
+    std::vector<uint8_t> svb_bad;
+    uint64_t svb_samples = 0;
     // the batch in flight
     bool pending = false;
     pg_pamean_batch b{};
@@ -326,6 +332,55 @@ pg_status pg_pamean_submit(pg_pamean *h, const pg_pamean_batch *b, double *means
     h->pending = true;
     return PG_OK;
 }
+
+// The blocks are decoded into d_sig, the reads back to back, and offsets and parameters go to d_off / d_par: the buffers of a host batch,
+// which the PG_LOC_DEVICE path of pg_pamean_submit leaves alone. The decode is waited for (the flags decide whether the batch counts).
+pg_status pg_pamean_submit_svb(pg_pamean *h, const pg_svb_batch *svb, const double *digitisation, const double *offset, const double *range,
+                               double *means_out) {
+    if (!h) return pg_fail<pg_pamean>(nullptr, PG_ERR_INVALID_ARG, "pg_pamean_submit_svb: null handle");
+    if (!svb) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_pamean_submit_svb: null batch");
+    PG_HIP_TRY(h, hipSetDevice(h->device));
+    if (pg_status s = pa_complete(h)) return s;                      // (the batch in flight may read d_sig)
+    const uint64_t n_reads = svb->n_reads;
+    if (!n_reads) return PG_OK;
+    if (!digitisation || !offset || !range) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_pamean_submit_svb: null array");
+    std::string err;
+    if (pg_status st = h->svb.prepare(h->device, h->s, svb->blocks, svb->n_block_bytes, svb->block_off, n_reads, svb->location, err)) {
+        (void)hipStreamSynchronize(h->s);
+        return pg_fail(h, st, "pg_pamean_submit_svb: %s", err.c_str());
+    }
+    h->svb_off.resize(n_reads + 1);
+    h->svb_off[0] = 0;
+    for (uint64_t r = 0; r < n_reads; r++) h->svb_off[r + 1] = h->svb_off[r] + h->svb.count(r);
+    const uint64_t total = h->svb_off[n_reads];
+    h->svb_bad.assign(n_reads, 0);
+    pg_status st = PG_OK;
+    {
+        const size_t want = std::max<uint64_t>(total, 1) * sizeof(int16_t);
+        const hipError_t e = h->d_sig.ensure(want, want + want / 4);  // (batches differ in size: a little room saves reallocating)
+        if (e != hipSuccess) { st = PG_ERR_HIP; err = std::string("hipMalloc failed: ") + hipGetErrorString(e); }
+    }
+    if (st == PG_OK) st = h->svb.run(h->s, h->d_sig.p, h->svb_off.data(), h->svb_bad.data(), err);
+    if (st) { (void)hipStreamSynchronize(h->s); return pg_fail(h, st, "pg_pamean_submit_svb: %s", err.c_str()); }
+    for (uint64_t r = 0; r < n_reads; r++)
+        if (h->svb_bad[r]) return pg_fail(h, PG_ERR_INPUT, "pg_pamean_submit_svb: read %llu: corrupt streamvbyte block", (unsigned long long)r);
+    PG_HIP_TRY(h, h->d_off.ensure((n_reads + 1) * sizeof(uint64_t)));
+    PG_HIP_TRY(h, h->d_par.ensure(3 * n_reads * sizeof(double)));
+    PG_HIP_TRY(h, hipMemcpyAsync(h->d_off.p, h->svb_off.data(), (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, h->s));
+    PG_HIP_TRY(h, hipMemcpyAsync(h->d_par.p, digitisation, n_reads * sizeof(double), hipMemcpyHostToDevice, h->s));
+    PG_HIP_TRY(h, hipMemcpyAsync(h->d_par.p + n_reads, offset, n_reads * sizeof(double), hipMemcpyHostToDevice, h->s));
+    PG_HIP_TRY(h, hipMemcpyAsync(h->d_par.p + 2 * n_reads, range, n_reads * sizeof(double), hipMemcpyHostToDevice, h->s));
+    PG_HIP_TRY(h, hipStreamSynchronize(h->s));                       // (the caller's arrays are free; pg_pamean_submit reads the offsets back)
+    pg_pamean_batch b{};
+    b.n_reads = n_reads; b.location = PG_LOC_DEVICE;
+    b.sig = h->d_sig.p; b.sig_off = h->d_off.p;
+    b.digitisation = h->d_par.p; b.offset = h->d_par.p + n_reads; b.range = h->d_par.p + 2 * n_reads;
+    st = pg_pamean_submit(h, &b, means_out);
+    if (st == PG_OK) h->svb_samples += total;
+    return st;
+}
+
+uint64_t pg_pamean_svb_samples(const pg_pamean *h) { return h ? h->svb_samples : 0; }
 
 pg_status pg_pamean_sync(pg_pamean *h) {
     if (!h) return pg_fail<pg_pamean>(nullptr, PG_ERR_INVALID_ARG, "pg_pamean_sync: null handle");

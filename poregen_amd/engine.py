@@ -897,6 +897,26 @@ class SignalMeans:
         self._check(self._lib.pg_pamean_submit(self._h, C.byref(b), C.c_void_p(means.ctypes.data) if n else None))
         self._means.append(means)
 
+    def submit_svb(self, blocks, block_off, digitisation, offset, range):
+        """submit() for a batch whose samples are still svb-zd blocks (SignalDecoder): uint8 bytes in a numpy array or a CUDA tensor,
+        n + 1 host offsets into them, host parameters. The blocks are decoded on the device; a corrupt block raises PgError
+        (PG_ERR_INPUT) and nothing of the batch is counted."""
+        blocks, boff, loc = _svb_arrays(blocks, block_off)
+        par = [np.ascontiguousarray(a, np.float64) for a in (digitisation, offset, range)]
+        n = boff.size - 1
+        if any(a.size != n for a in par):
+            raise ValueError("need n + 1 offsets and n digitisation / offset / range values")
+        means = np.empty(n, np.float64)
+        sb = _abi.PgSvbBatch(n, loc, 0, _ptr(blocks) if _size(blocks) else None, _size(blocks), boff.ctypes.data)
+        self._check(self._lib.pg_pamean_submit_svb(self._h, C.byref(sb), *[C.c_void_p(a.ctypes.data) if n else None for a in par],
+                                                    C.c_void_p(means.ctypes.data) if n else None))
+        self._means.append(means)
+
+    @property
+    def svb_samples(self) -> int:
+        """samples submit_svb has decoded on the device since this object was created"""
+        return int(self._lib.pg_pamean_svb_samples(self._h))
+
     def finish(self) -> PaMeans:
         r = _abi.PgPameanResult()
         try:
@@ -926,6 +946,110 @@ def read_means(sig, sig_off, digitisation, offset, range, device: int = 0) -> Pa
         return sm.finish()
     finally:
         sm.close()
+
+
+def read_means_svb(blocks, block_off, digitisation, offset, range, device: int = 0) -> PaMeans:
+    """read_means() for one batch of svb-zd blocks (SignalMeans.submit_svb)."""
+    sm = SignalMeans(device)
+    try:
+        sm.submit_svb(blocks, block_off, digitisation, offset, range)
+        return sm.finish()
+    finally:
+        sm.close()
+
+
+# ---- svb-zd signal blocks (pg_sigdec_*) --------------------------------------------------------------------------------------------
+
+def _size(a):
+    return a.numel() if hasattr(a, "numel") else a.size
+
+
+def _svb_arrays(blocks, block_off):
+    """(blocks, block_off as uint64, location): blocks a contiguous uint8 numpy array or CUDA tensor, the offsets inside it"""
+    if hasattr(blocks, "is_cuda") and blocks.is_cuda:
+        if blocks.dtype.itemsize != 1 or not blocks.is_contiguous():
+            raise ValueError("device blocks: a contiguous uint8 tensor")
+        loc = _abi.PG_LOC_DEVICE
+    else:
+        blocks = np.ascontiguousarray(np.frombuffer(blocks, np.uint8) if isinstance(blocks, (bytes, bytearray, memoryview)) else blocks, np.uint8)
+        loc = _abi.PG_LOC_HOST
+    boff = np.ascontiguousarray(block_off, np.uint64)
+    if boff.ndim != 1 or boff.size < 1:
+        raise ValueError("need n + 1 block offsets")
+    if (boff[1:] < boff[:-1]).any() or int(boff[-1]) > _size(blocks):  # (the kernels trust the offsets: never let them point past the bytes)
+        raise ValueError("block_off decreases or runs past the blocks")
+    return blocks, boff, loc
+
+
+class SignalDecoder:
+    """svb-zd signal blocks of BLOW5 records decoded on the GPU (pg_sigdec_*): read r's block is blocks[block_off[r]:block_off[r + 1]],
+    bytes in a numpy array or a CUDA tensor, at any byte offset."""
+
+    def __init__(self, device: int = 0):
+        self._lib = _abi.load()
+        h = C.c_void_p()
+        st = self._lib.pg_sigdec_create(device, C.byref(h))
+        if st != 0:
+            raise PgError(st, self._lib.pg_sigdec_last_error(None).decode())
+        self._h = h
+        self._device = device
+
+    def _check(self, st):
+        if st != 0:
+            raise PgError(st, self._lib.pg_sigdec_last_error(self._h).decode())
+
+    def counts(self, blocks, block_off) -> np.ndarray:
+        """the samples each read decodes to (uint32): the block's count field, 0 for a block the host's checks refuse"""
+        blocks, boff, loc = _svb_arrays(blocks, block_off)
+        n = boff.size - 1
+        out = np.zeros(n, np.uint32)
+        self._check(self._lib.pg_sigdec_counts(self._h, _ptr(blocks) if _size(blocks) else None, _size(blocks), boff.ctypes.data, n, loc,
+                                               out.ctypes.data if n else None))
+        return out
+
+    def decode(self, blocks, block_off, sig_off=None, out=None):
+        """(samples, sig_off, bad): an int16 CUDA tensor with read r at [sig_off[r], sig_off[r] + count_r), the offsets (uint64) and the
+        mask of corrupt blocks, whose spans hold unspecified samples. sig_off=None puts the reads back to back. out: the tensor to decode
+        into (int16, contiguous, on the decoder's device, at least sig_off[-1] samples); nothing outside the spans is written."""
+        import torch
+        blocks, boff, loc = _svb_arrays(blocks, block_off)
+        n = boff.size - 1
+        if sig_off is None:
+            cnt = self.counts(blocks, boff)
+            soff = np.concatenate([[0], np.cumsum(cnt, dtype=np.uint64)]).astype(np.uint64)
+        else:
+            soff = np.ascontiguousarray(sig_off, np.uint64)
+            if soff.size != n + 1 or (soff[1:] < soff[:-1]).any():
+                raise ValueError("need n + 1 non-decreasing sample offsets")
+        total = int(soff[-1])
+        if out is None:
+            out = torch.empty(total, dtype=torch.int16, device=f"cuda:{self._device}")
+        elif not (out.is_cuda and out.dtype == torch.int16 and out.is_contiguous() and out.numel() >= total):
+            raise ValueError("out: a contiguous int16 CUDA tensor of at least sig_off[-1] samples")
+        bad = np.zeros(n, np.uint8)
+        self._check(self._lib.pg_sigdec_decode(self._h, _ptr(blocks) if _size(blocks) else None, _size(blocks), boff.ctypes.data, n, loc,
+                                               out.data_ptr() if out.numel() else None, soff.ctypes.data, bad.ctypes.data if n else None))
+        return out, soff, bad.astype(bool)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.pg_sigdec_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def decode_svb_zd(blocks, block_off, device: int = 0):
+    """One-shot SignalDecoder: (samples, sig_off, bad) of one batch of svb-zd blocks, the reads back to back."""
+    dec = SignalDecoder(device)
+    try:
+        return dec.decode(blocks, block_off)
+    finally:
+        dec.close()
 
 
 # ---- model: the k-mer model from the text of dump files (pg_dmodel_*) ------------------------------------------------------------------

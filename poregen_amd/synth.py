@@ -462,6 +462,7 @@ def write_blow5(b: Batch, path: str, compress=False):
     """BLOW5 for the batch (layout: SURVEY.md 8f-1); read ids are r<index>. compress=False: record compression none,
     signal compression none -- meant for throughput-sized CLI runs where ASCII SLOW5 parsing would dominate.
     compress=True: zlib records + svb-zd signals, what slow5tools writes by default (as test/example.blow5).
+    compress="svb-zd": record compression none + svb-zd signals (the signal blocks lie in the file as they are).
     compress="zstd": zstd records (record compression 2; the reference's `make zstd=1` build) + svb-zd signals; "zstd-stream": the same with
     frames that do not carry their content size."""
     import struct
@@ -471,14 +472,14 @@ def write_blow5(b: Batch, path: str, compress=False):
                b"#char*\tuint32_t\tdouble\tdouble\tdouble\tdouble\tuint64_t\tint16_t*\n"
                b"#read_id\tread_group\tdigitisation\toffset\trange\tsampling_rate\tlen_raw_signal\traw_signal\n")
         with open(path, "wb") as f:
-            f.write(b"BLOW5\x01" + bytes([0, 2, 0]) + bytes([2 if compress in ("zstd", "zstd-stream") else 1]) + struct.pack("<I", 1) + bytes([1]) + bytes(64 - 15))
+            f.write(b"BLOW5\x01" + bytes([0, 2, 0]) + bytes([2 if compress in ("zstd", "zstd-stream") else (0 if compress == "svb-zd" else 1)]) + struct.pack("<I", 1) + bytes([1]) + bytes(64 - 15))
             f.write(struct.pack("<I", len(hdr)) + hdr)
             for r in range(b.n_reads):
                 rid = f"r{r}".encode()
                 blk = _svb_zd(b.sig[int(b.sig_off[r]):int(b.sig_off[r + 1])])
                 body = (struct.pack("<H", len(rid)) + rid + struct.pack("<I", 0)
                         + struct.pack("<dddd", b.digitisation[r], b.offset[r], b.range[r], 4000.0) + struct.pack("<Q", len(blk)) + blk)
-                z = zstd_compress(body, streamed=(compress == "zstd-stream")) if compress in ("zstd", "zstd-stream") else zlib.compress(body)
+                z = zstd_compress(body, streamed=(compress == "zstd-stream")) if compress in ("zstd", "zstd-stream") else (body if compress == "svb-zd" else zlib.compress(body))
                 f.write(struct.pack("<Q", len(z)) + z)
             f.write(b"5WOLB")
         return

@@ -11,7 +11,10 @@ Measured, each as the best of --reps runs after one warm-up, with a device synch
            HBM peak, the figure the targets are set in. --trace-out writes the table as text.
   host     the configs[1] batch in page-locked host memory (PG_LOC_HOST), next to a plain H2D copy of the same bytes.
   cli      bin/poregen subtool0 on an uncompressed BLOW5 and on a zlib + svb-zd BLOW5 of the same --cli-reads reads (files in the page
-           cache), with the host-decode / device-wait split the CLI reports on stderr; pa_stats on the uncompressed one.
+           cache), with the host-decode / device-wait split the CLI reports on stderr; pa_stats on the uncompressed one. A third file,
+           none + svb-zd, holds the same blocks without the record compression: its host-decode time against the zlib file's splits
+           the host time into inflate and the rest. --exe LABEL=PATH (repeatable) runs other builds of bin/poregen on the same files,
+           the builds taking turns rep by rep (an A/B on one box); every run's time is kept (`runs_s`), so the spread is in the output.
 Prints one JSON object and writes it to --out.
 """
 import argparse
@@ -76,11 +79,40 @@ def kernel_table(db, workloads, out_path):
     return out
 
 
+def device_and_host(a, res, c1, rg, read_means):
+    import torch
+    res["device"] = {}
+    for name, b in (("configs1", c1), ("ragged", rg)):
+        d = to_dev(b)
+        s, r = timed(lambda: read_means(*d), a.reps)
+        nb = b.sig.nbytes
+        res["device"][name] = {"reads": b.n_reads, "samples": int(b.sig.size), "bytes": nb, "s": round(s, 6),
+                               "call_GBps": round(nb / s / 1e9, 1), "call_of_hbm_peak": round(nb / s / PEAK, 3), "fallback_reads": r.n_fallback,
+                               "fallback_share": round(r.n_fallback / b.n_reads, 6), "longest_read": int(np.diff(b.sig_off).max())}
+        del d
+        torch.cuda.empty_cache()
+    if a.only == "device":
+        return
+    if a.trace:
+        res["kernels"] = kernel_table(a.trace, {name: res["device"][name] for name in res["device"]}, a.trace_out)
+
+    pin = [torch.from_numpy(x).pin_memory() for x in (c1.sig, c1.sig_off.view(np.int64), c1.digitisation, c1.offset, c1.range)]
+    pin_np = [t.numpy() for t in pin]
+    pin_np[1] = pin_np[1].view(np.uint64)
+    s_host, _ = timed(lambda: read_means(*pin_np), a.reps)
+    dst = torch.empty_like(pin[0], device="cuda")
+    s_h2d, _ = timed(lambda: dst.copy_(pin[0], non_blocking=True), a.reps)
+    res["host_pinned"] = {"s": round(s_host, 6), "GBps": round(c1.sig.nbytes / s_host / 1e9, 1),
+                          "h2d_GBps": round(c1.sig.nbytes / s_h2d / 1e9, 1), "fraction_of_h2d": round(s_h2d / s_host, 3)}
+    del pin, pin_np, dst
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--cli-reads", type=int, default=50000)
-    ap.add_argument("--only", choices=["all", "device"], default="all")
+    ap.add_argument("--only", choices=["all", "device", "cli"], default="all")
+    ap.add_argument("--exe", action="append", default=[], help="LABEL=PATH of another bin/poregen for the cli section")
     ap.add_argument("--tmp", default="/tmp")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pamean_bench.json"))
     ap.add_argument("--trace", help="rocprofv3 database of an --only device run")
@@ -100,58 +132,43 @@ def main():
     res = {"device_name": torch.cuda.get_device_name(0), "peak_hbm_GBps": PEAK / 1e9}
 
     c1 = synth.make_batch_fast(50000, 4000, seed=20251003)
-    lens = synth.ragged_lengths()
-    rg = synth.make_ragged_fast(lens)
-    res["device"] = {}
-    for name, b in (("configs1", c1), ("ragged", rg)):
-        d = to_dev(b)
-        s, r = timed(lambda: read_means(*d), a.reps)
-        nb = b.sig.nbytes
-        res["device"][name] = {"reads": b.n_reads, "samples": int(b.sig.size), "bytes": nb, "s": round(s, 6),
-                               "call_GBps": round(nb / s / 1e9, 1), "call_of_hbm_peak": round(nb / s / PEAK, 3), "fallback_reads": r.n_fallback,
-                               "fallback_share": round(r.n_fallback / b.n_reads, 6), "longest_read": int(np.diff(b.sig_off).max())}
-        del d
-        torch.cuda.empty_cache()
-    if a.only == "device":
-        print(json.dumps(res))
-        return
-    if a.trace:
-        res["kernels"] = kernel_table(a.trace, {name: res["device"][name] for name in res["device"]}, a.trace_out)
-
-    pin = [torch.from_numpy(x).pin_memory() for x in (c1.sig, c1.sig_off.view(np.int64), c1.digitisation, c1.offset, c1.range)]
-    pin_np = [t.numpy() for t in pin]
-    pin_np[1] = pin_np[1].view(np.uint64)
-    s_host, _ = timed(lambda: read_means(*pin_np), a.reps)
-    dst = torch.empty_like(pin[0], device="cuda")
-    s_h2d, _ = timed(lambda: dst.copy_(pin[0], non_blocking=True), a.reps)
-    res["host_pinned"] = {"s": round(s_host, 6), "GBps": round(c1.sig.nbytes / s_host / 1e9, 1),
-                          "h2d_GBps": round(c1.sig.nbytes / s_h2d / 1e9, 1), "fraction_of_h2d": round(s_h2d / s_host, 3)}
-    del pin, pin_np, dst
-
+    rg = synth.make_ragged_fast(synth.ragged_lengths()) if a.only != "cli" else None
+    if a.only != "cli":
+        device_and_host(a, res, c1, rg, read_means)
+        if a.only == "device":
+            print(json.dumps(res))
+            return
     sub = c1.slice_reads(0, min(a.cli_reads, c1.n_reads))
     exe = os.path.join(ROOT, "bin", "poregen")
     res["cli"] = {"reads": sub.n_reads, "samples_bytes": int(sub.sig.nbytes)}
-    for kind, comp in (("blow5_none", False), ("blow5_zlib_svbzd", True)):
+    exes = [("", exe)] + [tuple(x.split("=", 1)) for x in a.exe]
+    n_runs = max(1, a.reps - 2)
+    for kind, comp in (("blow5_none", False), ("blow5_zlib_svbzd", True), ("blow5_none_svbzd", "svb-zd")):
         path = os.path.join(a.tmp, f"pamean_bench_{kind}.blow5")
         synth.write_blow5(sub, path, compress=comp)
         with open(path, "rb") as f:
             while f.read(1 << 26):
                 pass
         for cmd in (("subtool0", "pa_stats") if kind == "blow5_none" else ("subtool0",)):
-            best, split = 1e30, None
-            for _ in range(max(1, a.reps - 2)):
-                t = time.perf_counter()
-                r = subprocess.run([exe, cmd, path], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=900)
-                dt = time.perf_counter() - t
-                if r.returncode:
-                    raise SystemExit(r.stderr.decode()[-2000:])
-                if dt < best:
-                    best = dt
+            runs = {label: [] for label, _ in exes}
+            for label, e in exes:                                 # one unrecorded run each: the binary and its libraries in the page cache
+                subprocess.run([e, cmd, path], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=900)
+            for _ in range(n_runs):
+                for label, e in exes:
+                    t = time.perf_counter()
+                    r = subprocess.run([e, cmd, path], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=900)
+                    dt = time.perf_counter() - t
+                    if r.returncode:
+                        raise SystemExit(r.stderr.decode()[-2000:])
                     m = re.search(rb"host decode ([0-9.]+) s, waiting for the device ([0-9.]+) s, total ([0-9.]+) s", r.stderr)
-                    split = [float(x) for x in m.groups()] if m else None
-            res["cli"][f"{cmd}_{kind}"] = {"file_bytes": os.path.getsize(path), "s": round(best, 3),
-                                           "GBps_of_samples": round(sub.sig.nbytes / best / 1e9, 2),
-                                           "host_decode_s": split and split[0], "device_wait_s": split and split[1], "in_process_s": split and split[2]}
+                    runs[label].append((dt, [float(x) for x in m.groups()] if m else None))
+            for label, _ in exes:
+                best, split = min(runs[label], key=lambda x: x[0])
+                res["cli"][f"{cmd}_{kind}" + (f"@{label}" if label else "")] = {
+                    "file_bytes": os.path.getsize(path), "s": round(best, 3), "runs_s": [round(x[0], 3) for x in runs[label]],
+                    "GBps_of_samples": round(sub.sig.nbytes / best / 1e9, 2),
+                    "host_decode_s": split and split[0], "device_wait_s": split and split[1], "in_process_s": split and split[2],
+                    "host_decode_runs_s": [x[1] and x[1][0] for x in runs[label]]}
         os.unlink(path)
     line = json.dumps(res)
     print(line)
