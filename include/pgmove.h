@@ -62,6 +62,13 @@
  *                                  :194-220, stay with the caller
  * pg_kfreq_sync / pg_kfreq_last_error  (no counterpart)
  *
+ * The move tables of BAM records to ss ops (scripts/poregen.sh STEP 4, `reform -c -k 1`) have one:
+ * pg_mvops_create / _destroy       (no counterpart)
+ * pg_mvops_expand                  the PAF branch of reform() for a batch of      src/reform.cpp:284-358
+ *                                  records, and `samtools fastq` of their bases
+ * pg_mvops_piece / _set_stream /   (no counterpart)
+ * _stream / _last_error
+ *
  * The F1-score metric (src/f1_score/f1score.py) has one too:
  * pg_fscore_create / _destroy     args.rna / args.threshold / args.region         src/f1_score/f1score.py:59-66, 234-246
  * pg_fscore_submit                 parse_ss_string + compare_mappings of every     src/f1_score/f1score.py:7-119, 135-153
@@ -642,6 +649,61 @@ pg_status pg_pamean_submit_svb(pg_pamean *h, const pg_svb_batch *svb, const doub
                                double *means_out);
 /* the samples pg_pamean_submit_svb has decoded on the device since create */
 uint64_t  pg_pamean_svb_samples(const pg_pamean *h);
+
+/* ---- move tables to ss ops: what `reform -c -k 1 -m 0` prints for a batch of BAM records, produced on the device -------------------------
+ * Read r of a batch: its table is the int8 elements of the record's mv:B:c array behind the stride element, bytes [mv_off[r], mv_off[r + 1])
+ * of mv as they lie in the record (any byte offset; an element is a move iff it is 1), with stride[r] = the array's first element, ns[r] and
+ * ts[r] the tags of those names, l_seq[r] bases packed two 4-bit codes per byte from byte byte_off[r] of seq_bytes (the layout of
+ * pg_kfreq_submit_reads) and flag[r] the record's FLAG. Records with flag 0x100 or 0x800 are the caller's to drop. With pos[] the 1-based
+ * positions of the moves and n the table's length, the read's ops are (host/reform_cli.cpp, reform_record; src/reform.cpp:284-358):
+ *   query_start = ts + (pos[0] - 1) * stride;  one op (pos[j + 1] - pos[j]) * stride per later move while bases remain;  then, if an element
+ *   lies behind pos[0] and a base remains, the tail op (n - pos[last]) * stride + (ns - ((n - 1) * stride + ts))
+ * in reform's arithmetic (uint32 gaps that wrap, int64 ns and ts). target_start / target_end are 0 / l_seq, or l_seq / 0 with PG_MVOPS_RNA
+ * (`reform --rna`); seq is the read as `samtools fastq` prints it (flag 0x10: reversed and complemented; PG_MVOPS_N_TO_T: N printed as T).
+ * A read reform refuses gets no ops and a status: the caller decides what that means. An accepted read has exactly l_seq ops, all matches.
+ * The result lies in device memory of the handle, laid out as the arrays of the same names of a pg_batch, op_t all 0 (the batch may be
+ * submitted with PG_BATCH_ALL_MATCHES), complete when the call returns, valid until the next pg_mvops_expand or pg_mvops_destroy on the
+ * handle. location: where all nine input arrays lie; host arrays are free for reuse when the call returns, device arrays are read in place.
+ * Long tables are cut into pieces of pg_mvops_piece elements, one wave of the device each. No CPU fallback: PG_ERR_NO_DEVICE without a GPU. */
+typedef struct pg_mvops pg_mvops;
+enum { PG_MVOPS_RNA = 1, PG_MVOPS_N_TO_T = 2 };
+enum { PG_MVOPS_ST_ACCEPTED = 0, PG_MVOPS_ST_NO_MOVE_IN_TABLE = 1, PG_MVOPS_ST_NEGATIVE_TAIL = 2, PG_MVOPS_ST_BASES_LEFT_OVER = 3, PG_MVOPS_ST_BAD_STRIDE = 4 };
+typedef struct {
+    uint64_t n_reads;
+    int32_t  location;           /* PG_LOC_HOST or PG_LOC_DEVICE */
+    uint32_t flags;              /* PG_MVOPS_* */
+    const int8_t   *mv;
+    uint64_t n_mv_bytes;         /* bytes of mv; mv_off[n_reads] may not exceed it */
+    const uint64_t *mv_off;      /* [n_reads + 1] */
+    const int32_t  *stride;      /* [n_reads] */
+    const uint64_t *ns, *ts;
+    const uint32_t *l_seq, *flag;
+    const uint8_t  *seq_bytes;
+    uint64_t n_seq_bytes;
+    const uint64_t *byte_off;    /* [n_reads] */
+} pg_mvops_batch;
+typedef struct {
+    uint64_t n_reads, n_ops, n_seq;  /* n_ops = op_off[n_reads], n_seq = seq_off[n_reads] */
+    uint64_t n_refused;
+    int64_t  first_refused;          /* the first read with a status other than 0, or -1 */
+    const uint32_t *op_n;            /* device, dense */
+    const uint8_t  *op_t;            /* device, all 0 */
+    const uint64_t *op_off;          /* device [n_reads + 1] */
+    const int32_t  *query_start, *target_start, *target_end; /* device [n_reads] */
+    const uint8_t  *seq;             /* device, ASCII */
+    const uint64_t *seq_off;         /* device [n_reads + 1] */
+    const uint32_t *status;          /* device [n_reads], PG_MVOPS_ST_* */
+    const uint32_t *status_host;     /* the same in host memory of the handle */
+} pg_mvops_result;
+pg_status pg_mvops_create(int32_t device, pg_mvops **out);
+void      pg_mvops_destroy(pg_mvops *h);
+const char *pg_mvops_last_error(const pg_mvops *h); /* h may be NULL: error of the last failed pg_mvops_create */
+uint32_t  pg_mvops_piece(const pg_mvops *h);        /* h may be NULL */
+/* The kernels and copies of the following calls go to a caller-owned HIP stream (hipStream_t as void*, e.g. the one handed to
+ * pg_set_stream); NULL restores the handle's own. pg_mvops_stream returns the stream in use. */
+pg_status pg_mvops_set_stream(pg_mvops *h, void *hip_stream);
+void     *pg_mvops_stream(const pg_mvops *h);
+pg_status pg_mvops_expand(pg_mvops *h, const pg_mvops_batch *batch, pg_mvops_result *out);
 
 /* ---- model: the k-mer model from the TEXT of dump files, parsed and reduced on the device ---------------------------------------------
  * What scripts/poregen.sh:54-85 (tr ';,' '\n' | tail -n +2 | datamash median 1 / sstdev 1) and :33-52 (awk comma counts | datamash

@@ -29,6 +29,8 @@ PG_FLAG_ONE_STREAM = 1024
 PG_MODEL_KEEP_FIRST = 1
 PG_KFREQ_N_TO_T = 1
 PG_DMODEL_PROFILE = 256
+PG_MVOPS_RNA, PG_MVOPS_N_TO_T = 1, 2
+PG_MVOPS_ST_ACCEPTED, PG_MVOPS_ST_NO_MOVE_IN_TABLE, PG_MVOPS_ST_NEGATIVE_TAIL, PG_MVOPS_ST_BASES_LEFT_OVER, PG_MVOPS_ST_BAD_STRIDE = 0, 1, 2, 3, 4
 PG_MODEL_TEXT_MEDIAN, PG_MODEL_TEXT_SSTDEV, PG_MODEL_TEXT_DWELL = 0, 1, 2
 
 # every symbol include/pgmove.h declares (checked by tests/test_abi.py)
@@ -46,6 +48,7 @@ EXPORTS = [
     "pg_sigdec_create", "pg_sigdec_destroy", "pg_sigdec_last_error", "pg_sigdec_counts", "pg_sigdec_decode",
     "pg_dmodel_create", "pg_dmodel_destroy", "pg_dmodel_last_error", "pg_dmodel_submit", "pg_dmodel_sync", "pg_dmodel_finish", "pg_dmodel_format",
     "pg_transform_model", "pg_transform_free",
+    "pg_mvops_create", "pg_mvops_destroy", "pg_mvops_last_error", "pg_mvops_piece", "pg_mvops_set_stream", "pg_mvops_stream", "pg_mvops_expand",
 ]
 PG_JOB_EXCHANGE_AUTO, PG_JOB_EXCHANGE_HOST, PG_JOB_EXCHANGE_RCCL = 0, 1, 2
 
@@ -145,6 +148,18 @@ class PgDmodelInfo(C.Structure):
 
 class PgKernelStat(C.Structure):
     _fields_ = [("name", C.c_char_p), ("launches", C.c_uint64), ("total_ms", C.c_double)]
+
+
+class PgMvopsBatch(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("location", C.c_int32), ("flags", C.c_uint32), ("mv", C.c_void_p), ("n_mv_bytes", C.c_uint64),
+                ("mv_off", C.c_void_p), ("stride", C.c_void_p), ("ns", C.c_void_p), ("ts", C.c_void_p), ("l_seq", C.c_void_p), ("flag", C.c_void_p),
+                ("seq_bytes", C.c_void_p), ("n_seq_bytes", C.c_uint64), ("byte_off", C.c_void_p)]
+
+
+class PgMvopsResult(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("n_ops", C.c_uint64), ("n_seq", C.c_uint64), ("n_refused", C.c_uint64), ("first_refused", C.c_int64),
+                ("op_n", C.c_void_p), ("op_t", C.c_void_p), ("op_off", C.c_void_p), ("query_start", C.c_void_p), ("target_start", C.c_void_p),
+                ("target_end", C.c_void_p), ("seq", C.c_void_p), ("seq_off", C.c_void_p), ("status", C.c_void_p), ("status_host", C.c_void_p)]
 
 
 _lib = None
@@ -273,5 +288,12 @@ def load():
     lib.pg_transform_model.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t,
                                        C.POINTER(vp), C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]; lib.pg_transform_model.restype = i32
     lib.pg_transform_free.argtypes = [vp]; lib.pg_transform_free.restype = None
+    lib.pg_mvops_create.argtypes = [i32, C.POINTER(vp)]; lib.pg_mvops_create.restype = i32
+    lib.pg_mvops_destroy.argtypes = [vp]; lib.pg_mvops_destroy.restype = None
+    lib.pg_mvops_last_error.argtypes = [vp]; lib.pg_mvops_last_error.restype = C.c_char_p
+    lib.pg_mvops_piece.argtypes = [vp]; lib.pg_mvops_piece.restype = u32
+    lib.pg_mvops_set_stream.argtypes = [vp, vp]; lib.pg_mvops_set_stream.restype = i32
+    lib.pg_mvops_stream.argtypes = [vp]; lib.pg_mvops_stream.restype = vp
+    lib.pg_mvops_expand.argtypes = [vp, C.POINTER(PgMvopsBatch), C.POINTER(PgMvopsResult)]; lib.pg_mvops_expand.restype = i32
     _lib = lib
     return lib

@@ -3,6 +3,7 @@
 // parsing into batches, writing the dump directory. The per-read computation runs on the GPU.
 #include "../../../include/pgmove.h"
 #include "pg_host.h"
+#include "../pg_hip_host.h"
 #include <future>
 #include <algorithm>
 
@@ -45,6 +46,7 @@ struct option long_options[] = {
     {"batch_reads", required_argument, 0, 0}, {"device", required_argument, 0, 0}, {"lazy_stats", no_argument, 0, 0},
     {"raw_model", required_argument, 0, 0}, {"stdv_limit", required_argument, 0, 0}, {"dwell_model", required_argument, 0, 0},
     {"devices", required_argument, 0, 0}, {"exchange", required_argument, 0, 0},
+    {"reform", no_argument, 0, 0}, {"n_to_t", no_argument, 0, 0},
     {0, 0, 0, 0}};
 
 void print_help(FILE *fp, const Opt &o) { // src/gmove.cpp:80-104
@@ -83,6 +85,9 @@ void print_help(FILE *fp, const Opt &o) { // src/gmove.cpp:80-104
     fprintf(fp, "                              (what scripts/poregen.sh calculate_mean_stddev_all derives from the dump files)\n");
     fprintf(fp, "   --stdv_limit NUM           cap of the stddev column of --raw_model [3.1]\n");
     fprintf(fp, "   --dwell_model FILE         also write KMER<TAB>median dwell (scripts/poregen.sh calculate_dwell_times_medians)\n");
+    fprintf(fp, "   --reform                   .bam / .sam only: read the move tables as `poregen reform -c -k 1 --stride 0` would (with --rna: reform --rna)\n");
+    fprintf(fp, "                              and collect by the rules of a .paf -- the tables are expanded on the GPU, no PAF and no --fastq needed\n");
+    fprintf(fp, "   --n_to_t                   with --reform: an N of a read counts as T (sed '2~4s/N/T/g' on the FASTQ)\n");
 }
 
 // The signal of a batch is hundreds of MB: a std::vector would zero every byte on resize (one thread, and the page faults
@@ -149,6 +154,7 @@ int gmove_main(int argc, char **argv) {
     uint32_t batch_reads = 20000; bool batch_reads_set = false; int device = 0; bool lazy = false;
     std::vector<int32_t> devices; uint32_t exchange = PG_JOB_EXCHANGE_AUTO;
     const char *raw_model_path = nullptr, *dwell_model_path = nullptr, *stdv_limit = "3.1";
+    bool reform_mode = false, n_to_t = false;
     optind = 1;
     while ((c = getopt_long(argc, argv, "k:m:s:d", long_options, &longindex)) >= 0) { // src/gmove.cpp:240-327
         if (c == 'k') { if (atoi(optarg) < 1) { fprintf(stderr, "Kmer length should be larger than 0. You entered %d\n", atoi(optarg)); return EXIT_FAILURE; } opt.kmer_size = atoi(optarg); }
@@ -190,12 +196,20 @@ int gmove_main(int argc, char **argv) {
             if (!strcmp(optarg, "auto")) exchange = PG_JOB_EXCHANGE_AUTO; else if (!strcmp(optarg, "host")) exchange = PG_JOB_EXCHANGE_HOST;
             else if (!strcmp(optarg, "rccl")) exchange = PG_JOB_EXCHANGE_RCCL; else return die("--exchange must be auto, host or rccl. You entered %s", optarg);
         }
+        else if (c == 0 && longindex == 30) reform_mode = true;
+        else if (c == 0 && longindex == 31) n_to_t = true;
     }
     if (argc - optind != 3 || fp_help == stdout) { // src/gmove.cpp:330-336
         print_help(fp_help, opt);
         return fp_help == stdout ? EXIT_SUCCESS : EXIT_FAILURE;
     }
     const char *slow5file = argv[optind], *move_table = argv[optind + 1], *output_dir = argv[optind + 2];
+    {
+        const size_t ml = strlen(move_table);
+        const bool sam_or_bam = ml >= 4 && (!strcmp(move_table + ml - 4, ".bam") || !strcmp(move_table + ml - 4, ".sam"));
+        if (reform_mode && !sam_or_bam) { fprintf(stderr, "--reform applies to a .bam or .sam event_alignment_file only\n"); print_help(fp_help, opt); return EXIT_FAILURE; }
+        if (n_to_t && !reform_mode) { fprintf(stderr, "--n_to_t applies with --reform only\n"); print_help(fp_help, opt); return EXIT_FAILURE; }
+    }
     // --devices cuts every batch into one contiguous shard per device: the default batch grows with the device count, so that a shard
     // stays at the 20 000 reads (160 MB of signal) the one-device pipeline is tuned for instead of shrinking to a latency-bound sliver
     const size_t n_shards = devices.empty() ? 1 : devices.size();
@@ -291,7 +305,8 @@ int gmove_main(int argc, char **argv) {
     pg_params prm; pg_default_params(&prm);
     prm.kmer_size = opt.kmer_size; prm.sig_move_offset = opt.sig_move_offset; prm.signal_print_margin = opt.signal_print_margin;
     prm.sample_limit = opt.sample_limit; prm.max_dur = opt.max_dur; prm.min_dur = opt.min_dur; prm.kmer_pick_margin = (int32_t)opt.kmer_pick_margin;
-    if (!is_paf) { // the move-table front-end has no indel logic and resolves -m / -s on the host (gmove.cpp:620-639)
+    const bool paf_rules = is_paf || reform_mode; // --reform: the records become what the PAF front-end reads, on the device
+    if (!paf_rules) { // the move-table front-end has no indel logic and resolves -m / -s on the host (gmove.cpp:620-639)
         prm.kmer_pick_margin = 0; prm.sig_move_offset = 0;
     }
     prm.scaling = scaling; prm.allow_rna = opt.flag_rna; prm.pa_min = opt.pa_min; prm.pa_max = opt.pa_max;
@@ -299,7 +314,7 @@ int gmove_main(int argc, char **argv) {
     if (!whole_list || !ramp_armed) ramp_reads = batch_reads; // the ramp of the batch sizes (above) is for jobs that can end early
     auto next_batch_reads = [&]() -> uint32_t { const uint32_t v = ramp_reads; ramp_reads = (uint32_t)std::min<uint64_t>(2ull * ramp_reads, batch_reads); return v; };
     uint32_t this_batch_reads = next_batch_reads();
-    prm.n_slots = (uint32_t)slot_kmers.size(); prm.flags = PG_FLAG_ONE_STREAM /* a job of a few batches: no second hardware queue (15-20 ms) */ | (whole_list ? PG_FLAG_STOP_WHEN_FULL : 0) | (lazy ? PG_FLAG_LAZY_STATS : 0) | (is_paf ? 0 : PG_FLAG_SHORT_READS_OK) | (is_bam ? PG_FLAG_SKIP_OUT_OF_RANGE : 0);
+    prm.n_slots = (uint32_t)slot_kmers.size(); prm.flags = PG_FLAG_ONE_STREAM /* a job of a few batches: no second hardware queue (15-20 ms) */ | (whole_list ? PG_FLAG_STOP_WHEN_FULL : 0) | (lazy ? PG_FLAG_LAZY_STATS : 0) | (paf_rules ? 0 : PG_FLAG_SHORT_READS_OK) | (is_bam && !reform_mode ? PG_FLAG_SKIP_OUT_OF_RANGE : 0);
     prm.device = device;
     prm.table_t = table_t.data(); prm.table_u = table_u.data();
     Backend dev;
@@ -585,6 +600,158 @@ int gmove_main(int argc, char **argv) {
                 else if (status == EXIT_SUCCESS) { fprintf(stderr, "%s\n", runs[last_run].msg.c_str()); status = EXIT_FAILURE; }
             }
         }
+    } else if (reform_mode) {
+        // ---- --reform: the records of the SAM / BAM file as they are stored -- move arrays, packed bases -- go to the device, which writes
+        // the ss ops `reform -c -k 1 -m 0 --stride 0` would have printed (pg_mvops_expand) into a device batch; the collector runs on that
+        // batch by the PAF front-end's rules. Per batch the host reads the records, fetches the signals (pool threads), uploads, expands
+        // and submits. Two expanders take turns: the ops of batch i are read by the device until batch i + 1 has been submitted.
+        unsigned nt = std::thread::hardware_concurrency(); if (nt > 16) nt = 16; if (nt < 1) nt = 1;
+        struct Slot { pg_mvops *ex = nullptr; PgDev<int16_t> sig; PgDev<uint64_t> sig_off; PgDev<double> cal; };
+        Slot slots[2];
+        struct Recs {
+            std::vector<std::string> names; std::vector<int8_t> mv; std::vector<uint64_t> mv_off{0}, ns, ts, boff; std::vector<int32_t> stride;
+            std::vector<uint32_t> l_seq, flag; std::vector<uint8_t> seqb;
+            void clear() { names.clear(); mv.clear(); mv_off.assign(1, 0); ns.clear(); ts.clear(); boff.clear(); stride.clear(); l_seq.clear(); flag.clear(); seqb.clear(); }
+        } rb;
+        std::vector<pgh::Slow5File::RawView> views; std::vector<pgh::Slow5Rec> recs; std::vector<std::string> fetch_err;
+        std::vector<double> cal;
+        std::vector<uint32_t> h_opn; // --devices: the expansion comes back to the host, which cuts the batch into the job's shards
+        pgh::RawMoveRec raw;
+        auto reform_msg = [](const char *msg, const std::string &id) { char b[600]; snprintf(b, sizeof b, "[reform::ERROR]\033[1;31m %s Read_id: %s\033[0m", msg, id.c_str()); return std::string(b); };
+        static const char *const kRefusal[] = {"", "the move table holds fewer moves than sig_move_offset + 1.", "Error in calcuation. (ns - ((i-1)*EXPECTED_STRIDE + ts)) > 0 is not valid.",
+                                               "Error in the implementation. Please report the command with minimal reproducible data.", "the stride of the move table (mv[0]) is less than 1."};
+        auto release = [&]() { for (Slot &sl : slots) { if (sl.ex) pg_mvops_destroy(sl.ex); sl.ex = nullptr; sl.sig.release(); sl.sig_off.release(); sl.cal.release(); } };
+        bool eof = false;
+        while (!stop && !eof && status == EXIT_SUCCESS) {
+            // ---- the records: the first one that cannot be taken ends the batch in front of it
+            rb.clear();
+            std::string bad; // why the record behind the batch's last read cannot be taken (empty: nothing wrong)
+            while (rb.names.size() < this_batch_reads && rb.mv.size() < ((size_t)1 << 30)) {
+                const int nr = sam.next_raw(raw, err);
+                if (nr == 0) { eof = true; break; }
+                if (nr < 0) { bad = "[gmove] " + err; break; }
+                if (raw.flag & 0x900u) continue; // secondary / supplementary: `samtools fastq` does not print them
+                if (!raw.has_ns) { bad = reform_msg("tag 'ns' is not found. Please check your SAM/BAM file:", raw.qname); break; }
+                if (!raw.has_ts) { bad = reform_msg("tag 'ts' is not found. Please check your SAM/BAM file:", raw.qname); break; }
+                if (!raw.has_mv) { bad = reform_msg("NULL returned for tag mv:", raw.qname); break; }
+                if (!raw.mv_is_Bc) { bad = reform_msg("tag 'mv' specification is incorrect.", raw.qname); break; }
+                if (raw.mv_len == 0) { bad = reform_msg("mv array length is 0:", raw.qname); break; }
+                rb.names.push_back(raw.qname);
+                rb.mv.insert(rb.mv.end(), raw.mv, raw.mv + (raw.mv_len - 1)); rb.mv_off.push_back(rb.mv.size());
+                rb.stride.push_back(raw.stride); rb.ns.push_back(raw.ns); rb.ts.push_back(raw.ts); rb.l_seq.push_back(raw.l_seq); rb.flag.push_back(raw.flag);
+                rb.boff.push_back(rb.seqb.size()); rb.seqb.insert(rb.seqb.end(), raw.packed, raw.packed + ((size_t)raw.l_seq + 1) / 2);
+            }
+            size_t n = rb.names.size();
+            // ---- the signals, on the pool: where each read's samples lie (or the samples, decoded), then one copy to their place
+            const bool can_place = s5.has_raw_views();
+            views.assign(can_place ? n : 0, {}); recs.resize(can_place ? 0 : n); fetch_err.assign(nt, std::string());
+            std::vector<size_t> first_missing(nt, n);
+            auto on_threads = [&](const std::function<void(unsigned)> &fn) {
+                if (nt == 1 || n < 64) { for (unsigned t = 0; t < nt; t++) fn(t); return; }
+                std::vector<std::thread> pool;
+                for (unsigned t = 0; t < nt; t++) pool.emplace_back(fn, t);
+                for (auto &th : pool) th.join();
+            };
+            on_threads([&](unsigned t) {
+                std::string e2;
+                for (size_t i = n * t / nt; i < n * (t + 1) / nt; i++) {
+                    const bool ok = can_place ? s5.raw_view(rb.names[i], views[i], e2) : s5.get(rb.names[i], recs[i], e2);
+                    if (!ok) { first_missing[t] = i; fetch_err[t] = e2; return; }
+                }
+            });
+            for (unsigned t = 0; t < nt; t++)
+                if (first_missing[t] < n) { n = first_missing[t]; bad = "Error in when fetching the read (" + fetch_err[t] + ")"; eof = false; break; } // gmove.cpp:745-749
+            HostBatch &hb = hbs[cur];
+            hb.clear(); hb.sig_off.resize(n + 1); hb.dig.resize(n); hb.off.resize(n); hb.range.resize(n);
+            for (size_t i = 0; i < n; i++) hb.sig_off[i + 1] = hb.sig_off[i] + (can_place ? views[i].n : recs[i].raw.size());
+            hb.sig.resize(hb.sig_off[n]);
+            on_threads([&](unsigned t) {
+                for (size_t i = n * t / nt; i < n * (t + 1) / nt; i++) {
+                    const size_t len = hb.sig_off[i + 1] - hb.sig_off[i];
+                    if (len) memcpy(hb.sig.data() + hb.sig_off[i], can_place ? views[i].samples : (const void *)recs[i].raw.data(), len * sizeof(int16_t));
+                    hb.dig[i] = can_place ? views[i].digitisation : recs[i].digitisation; hb.off[i] = can_place ? views[i].offset : recs[i].offset;
+                    hb.range[i] = can_place ? views[i].range : recs[i].range;
+                }
+            });
+            // ---- upload, expand, submit
+            if (n) {
+                const clk::time_point tf0 = clk::now();
+                if (!need_ctx()) { status = EXIT_FAILURE; break; }
+                Slot &sl = slots[cur];
+                const int ex_device = devices.empty() ? device : devices[0];
+                if (!sl.ex && pg_mvops_create(ex_device, &sl.ex) != PG_OK) { fprintf(stderr, "[gmove] %s\n", pg_mvops_last_error(nullptr)); status = EXIT_FAILURE; break; }
+                pg_mvops_batch mb; memset(&mb, 0, sizeof mb);
+                mb.n_reads = n; mb.location = PG_LOC_HOST; mb.flags = (opt.flag_rna ? PG_MVOPS_RNA : 0) | (n_to_t ? PG_MVOPS_N_TO_T : 0);
+                mb.mv = rb.mv.data(); mb.n_mv_bytes = rb.mv_off[n]; mb.mv_off = rb.mv_off.data(); mb.stride = rb.stride.data(); mb.ns = rb.ns.data(); mb.ts = rb.ts.data();
+                mb.l_seq = rb.l_seq.data(); mb.flag = rb.flag.data(); mb.seq_bytes = rb.seqb.data(); mb.n_seq_bytes = rb.seqb.size(); mb.byte_off = rb.boff.data();
+                pg_mvops_result mr;
+                auto hip_ok = [&](hipError_t e, const char *what) { if (e == hipSuccess) return true; fprintf(stderr, "[gmove] %s: %s\n", what, hipGetErrorString(e)); status = EXIT_FAILURE; return false; };
+                hipStream_t xs = (hipStream_t)pg_mvops_stream(sl.ex);
+                if (!dev.job) { // the signal and its calibration go up in front of the expansion, on its stream: complete when it returns
+                    const size_t sb = hb.sig_off[n] * sizeof(int16_t);
+                    cal.resize(3 * n);
+                    for (size_t i = 0; i < n; i++) { cal[i] = hb.dig[i]; cal[n + i] = hb.off[i]; cal[2 * n + i] = hb.range[i]; }
+                    if (!hip_ok(hipSetDevice(ex_device), "hipSetDevice") || !hip_ok(sl.sig.ensure(sb ? sb : 1, sb + sb / 4 + 256), "hipMalloc") ||
+                        !hip_ok(sl.sig_off.ensure((n + 1) * 8, (n + 1) * 10), "hipMalloc") || !hip_ok(sl.cal.ensure(3 * n * 8, 3 * n * 10), "hipMalloc") ||
+                        (sb && !hip_ok(hipMemcpyAsync(sl.sig.p, hb.sig.data(), sb, hipMemcpyHostToDevice, xs), "hipMemcpyAsync")) ||
+                        !hip_ok(hipMemcpyAsync(sl.sig_off.p, hb.sig_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, xs), "hipMemcpyAsync") ||
+                        !hip_ok(hipMemcpyAsync(sl.cal.p, cal.data(), 3 * n * 8, hipMemcpyHostToDevice, xs), "hipMemcpyAsync")) break;
+                }
+                if (pg_mvops_expand(sl.ex, &mb, &mr) != PG_OK) { fprintf(stderr, "[gmove] %s\n", pg_mvops_last_error(sl.ex)); status = EXIT_FAILURE; break; }
+                if (mr.first_refused >= 0) { // reform returns -1 on this record: the reads in front of it are the batch
+                    const size_t f = (size_t)mr.first_refused;
+                    const uint32_t code = mr.status_host[f];
+                    bad = reform_msg(kRefusal[code < 5 ? code : 3], rb.names[f]);
+                    n = f; eof = false;
+                }
+                uint64_t n_ops = 0, n_seq = 0; // an accepted read has as many ops as bases
+                for (size_t i = 0; i < n; i++) { n_ops += rb.l_seq[i]; n_seq += rb.l_seq[i]; }
+                total_samples += hb.sig_off[n];
+                for (size_t i = 0; i < n; i++) if (++count_reads % 10000 == 0) fprintf(stderr, "*"); // PROGRESS_BATCH_SIZE
+                if (n && dev.job) {
+                    hb.sig.resize(hb.sig_off[n]); hb.sig_off.resize(n + 1); hb.dig.resize(n); hb.off.resize(n); hb.range.resize(n);
+                    h_opn.resize(n_ops); hb.op_t.assign(n_ops, 0); hb.op_off.resize(n + 1); hb.seq.resize(n_seq); hb.seq_off.resize(n + 1); hb.qs.resize(n); hb.ts.resize(n); hb.te.resize(n);
+                    if ((n_ops && !hip_ok(hipMemcpy(h_opn.data(), mr.op_n, n_ops * 4, hipMemcpyDeviceToHost), "hipMemcpy")) ||
+                        (n_seq && !hip_ok(hipMemcpy(hb.seq.data(), mr.seq, n_seq, hipMemcpyDeviceToHost), "hipMemcpy")) ||
+                        !hip_ok(hipMemcpy(hb.op_off.data(), mr.op_off, (n + 1) * 8, hipMemcpyDeviceToHost), "hipMemcpy") ||
+                        !hip_ok(hipMemcpy(hb.seq_off.data(), mr.seq_off, (n + 1) * 8, hipMemcpyDeviceToHost), "hipMemcpy") ||
+                        !hip_ok(hipMemcpy(hb.qs.data(), mr.query_start, n * 4, hipMemcpyDeviceToHost), "hipMemcpy") ||
+                        !hip_ok(hipMemcpy(hb.ts.data(), mr.target_start, n * 4, hipMemcpyDeviceToHost), "hipMemcpy") ||
+                        !hip_ok(hipMemcpy(hb.te.data(), mr.target_end, n * 4, hipMemcpyDeviceToHost), "hipMemcpy")) break;
+                    hb.op_n.swap(h_opn);
+                    t_device += secs(tf0, clk::now());
+                    if (!flush()) { status = EXIT_FAILURE; break; }
+                } else if (n) {
+                    pg_batch b; memset(&b, 0, sizeof b);
+                    b.struct_size = sizeof b; b.location = PG_LOC_DEVICE; b.n_reads = (uint32_t)n; b.n_ops = (uint32_t)n_ops;
+                    if (n_ops > 0xffffffffull) { fprintf(stderr, "[gmove] a batch of %llu ops: use a smaller --batch_reads\n", (unsigned long long)n_ops); status = EXIT_FAILURE; break; }
+                    b.sig = sl.sig.p; b.sig_off = sl.sig_off.p; b.digitisation = sl.cal.p; b.offset = sl.cal.p + mr.n_reads; b.range = sl.cal.p + 2 * mr.n_reads;
+                    b.query_start = mr.query_start; b.target_start = mr.target_start; b.target_end = mr.target_end; b.seq = mr.seq; b.seq_off = mr.seq_off;
+                    b.op_n = mr.op_n; b.op_t = mr.op_t; b.op_off = mr.op_off;
+                    b.flags = PG_BATCH_ALL_MATCHES; // every op is a match and a read has as many ops as bases: what `reform` writes
+                    if (dev.submit(&b) != PG_OK) { fprintf(stderr, "[gmove] %s\n", dev.error()); status = EXIT_FAILURE; break; }
+                    t_device += secs(tf0, clk::now());
+                    cur ^= 1;
+                    this_batch_reads = next_batch_reads();
+                    if (whole_list && dev.all_full_settled()) stop = true;
+                }
+            }
+            if (status == EXIT_SUCCESS && !stop && !bad.empty()) {
+                // a record the two-step route may never have read: gmove stops reading the PAF once every k-mer of the whole list is complete.
+                // Wait for the batches in flight and look before failing.
+                bool complete = false;
+                if (whole_list && need_ctx()) {
+                    if (dev.sync() != PG_OK) { fprintf(stderr, "[gmove] %s\n", dev.error()); status = EXIT_FAILURE; }
+                    else complete = dev.all_full();
+                }
+                if (complete) stop = true;
+                else if (status == EXIT_SUCCESS) { fprintf(stderr, "%s\n", bad.c_str()); status = EXIT_FAILURE; }
+            }
+        }
+        // the device has read the last batch's ops before the expanders go
+        if (dev.ok() && dev.sync() != PG_OK && status == EXIT_SUCCESS) { fprintf(stderr, "[gmove] %s\n", dev.error()); status = EXIT_FAILURE; }
+        release();
+        hbs[0].clear(); hbs[1].clear(); // (nothing is left for the flush behind the loops)
     } else
     for (;;) {
         if (stop) break;
@@ -620,7 +787,7 @@ int gmove_main(int argc, char **argv) {
         if (++count_reads % 10000 == 0) fprintf(stderr, "*"); // PROGRESS_BATCH_SIZE
         if (hbs[cur].n() >= this_batch_reads || hbs[cur].sig.size() >= batch_samples_cap) { if (!flush()) { status = EXIT_FAILURE; flush_failed = true; break; } }
     }
-    if (status == EXIT_FAILURE && !is_paf && !flush_failed && whole_list) {
+    if (status == EXIT_FAILURE && !is_paf && !reform_mode && !flush_failed && whole_list) {
         // A RECORD error (a failed submit / device error is never rescued): the reference may never have read that record -- it stops once
         // every k-mer of the whole list is complete (gmove.cpp:733-735), and the reads in front of the bad record, queued or still in
         // the unflushed batch, may do that. As the PAF loop above: drop what the bad record left half-appended, submit the valid reads in

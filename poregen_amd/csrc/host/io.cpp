@@ -1,5 +1,6 @@
 // io.cpp -- memory-mapped files, ASCII SLOW5 / BLOW5 reader, FASTA/FASTQ index, PAF + ss tokeniser.
 #include "pg_host.h"
+#include "../pg_kfreq_codes.h"
 #include "../pg_svb.h"
 
 // zstd record compression (`make zstd=1` in the reference: /root/reference/Makefile:12-13,67 links -lzstd into slow5lib). Here libzstd is
@@ -576,7 +577,21 @@ bool SamBamReader::fill(size_t need, std::string &err) {
     return true;
 }
 
-int SamBamReader::next(MoveRec &out, std::string &err) {
+int SamBamReader::next(MoveRec &out, std::string &err) { return next_impl(out, nullptr, err); }
+
+int SamBamReader::next_raw(RawMoveRec &raw, std::string &err) {
+    MoveRec head; // the fields the two forms share
+    raw.flag = 0; raw.l_seq = 0; raw.mv = nullptr; raw.packed = nullptr; raw.mv_store.clear(); raw.packed_store.clear();
+    const int rc = next_impl(head, &raw, err);
+    raw.qname.swap(head.qname);
+    raw.stride = head.stride; raw.mv_len = head.mv_len; raw.ns = head.ns; raw.ts = head.ts;
+    raw.has_ns = head.has_ns; raw.has_ts = head.has_ts; raw.has_mv = head.has_mv; raw.mv_is_Bc = head.mv_is_Bc;
+    if (rc == 1 && !bam_) { raw.mv = raw.mv_store.data(); raw.packed = raw.packed_store.data(); }
+    return rc;
+}
+
+// raw: the move array and the bases are not expanded into out.is_one / out.seq but handed on as they are stored (RawMoveRec)
+int SamBamReader::next_impl(MoveRec &out, RawMoveRec *raw, std::string &err) {
     out = MoveRec();
     if (!bam_) {
         const char *e = f_.data + f_.size;
@@ -590,6 +605,13 @@ int SamBamReader::next(MoveRec &out, std::string &err) {
             while (p <= le) {
                 const char *t = (const char *)memchr(p, '\t', (size_t)(le - p)); if (!t) t = le;
                 if (col == 0) out.qname.assign(p, t);
+                else if (col == 1 && raw) raw->flag = (uint32_t)strtoul(std::string(p, t).c_str(), nullptr, 0);
+                else if (col == 9 && raw) { // packed by htslib's rule, as a BAM record would hold it
+                    size_t n = (size_t)(t - p); if (n == 1 && *p == '*') n = 0;
+                    if (n > 0x7fffffffu) { err = "SAM record with more than 2^31 - 1 bases"; return -1; }
+                    raw->l_seq = (uint32_t)n; raw->packed_store.assign((n + 1) / 2, 0);
+                    for (size_t i = 0; i < n; i++) raw->packed_store[i >> 1] |= (uint8_t)(pg_kf_code_of_byte((unsigned char)p[i]) << ((~i & 1) << 2));
+                }
                 else if (col == 9) { out.seq.assign(p, t); if (out.seq == "*") out.seq.clear(); for (auto &ch : out.seq) ch = seq_letter(ch); }
                 else if (col >= 11 && t - p >= 5) {
                     if (memcmp(p, "ns:i:", 5) == 0) { out.ns = strtoull(std::string(p + 5, t).c_str(), nullptr, 10); out.has_ns = true; }
@@ -603,7 +625,7 @@ int SamBamReader::next(MoveRec &out, std::string &err) {
                                 if (*q == ',') q++;
                                 char *endp; const long v = strtol(q, &endp, 10);
                                 if (endp == q) break;
-                                if (first) { out.stride = (int)v; first = false; } else out.is_one.push_back(v == 1);
+                                if (first) { out.stride = (int)v; first = false; } else if (raw) raw->mv_store.push_back((int8_t)v); else out.is_one.push_back(v == 1);
                                 out.mv_len++;
                                 q = endp;
                             }
@@ -639,8 +661,11 @@ int SamBamReader::next(MoveRec &out, std::string &err) {
     p += 4u * (size_t)n_cigar;
     if (l_seq < 0 || ((size_t)l_seq + 1) / 2 + (size_t)l_seq > left()) { err = "corrupt BAM record"; return -1; }
     static const char code[] = "=ACMGRSVTWYHKDBN";
-    out.seq.resize((size_t)l_seq);
-    for (int32_t i = 0; i < l_seq; i++) out.seq[(size_t)i] = seq_letter(code[(p[i >> 1] >> ((~i & 1) << 2)) & 15]);
+    if (raw) { uint16_t flag; memcpy(&flag, r + 14, 2); raw->flag = flag; raw->l_seq = (uint32_t)l_seq; raw->packed = p; }
+    else {
+        out.seq.resize((size_t)l_seq);
+        for (int32_t i = 0; i < l_seq; i++) out.seq[(size_t)i] = seq_letter(code[(p[i >> 1] >> ((~i & 1) << 2)) & 15]);
+    }
     p += ((size_t)l_seq + 1) / 2 + (size_t)l_seq;
     while (left() >= 3) { // tags
         const char t0 = (char)p[0], t1 = (char)p[1], ty = (char)p[2];
@@ -665,7 +690,8 @@ int SamBamReader::next(MoveRec &out, std::string &err) {
                 if (cnt < 0 || (size_t)cnt > (left() - 5) / esz) { err = "corrupt BAM tag"; return -1; }
                 if (t0 == 'm' && t1 == 'v') {
                     out.has_mv = true; out.mv_is_Bc = sub == 'c'; out.mv_len = (uint32_t)cnt;
-                    if (out.mv_is_Bc && cnt > 0) {
+                    if (out.mv_is_Bc && cnt > 0 && raw) { out.stride = (int8_t)p[5]; raw->mv = (const int8_t *)(p + 6); }
+                    else if (out.mv_is_Bc && cnt > 0) {
                         out.stride = (int8_t)p[5];
                         out.is_one.resize((size_t)cnt - 1);
                         for (int32_t i = 1; i < cnt; i++) out.is_one[(size_t)i - 1] = (int8_t)p[5 + i] == 1;

@@ -106,11 +106,28 @@ struct MoveRec {
     uint64_t ns = 0, ts = 0;       // signal length / trim offset tags
     bool has_ns = false, has_ts = false, has_mv = false, mv_is_Bc = false;
 };
+// The same record with nothing expanded (gmove --reform): the move array and the bases as a BAM record stores them -- the int8
+// elements of mv:B:c behind the stride element, two 4-bit base codes per byte (csrc/pg_kfreq_codes.h). A BAM record's two arrays are
+// pointed at where they lie in the reader's buffer, a SAM line's are packed into the record's own storage; either way the pointers hold
+// until the next call on the reader.
+struct RawMoveRec {
+    std::string qname;
+    uint32_t flag = 0, l_seq = 0;
+    int stride = 0;                // mv[0]
+    uint32_t mv_len = 0;           // elements of mv, the stride element included
+    const int8_t *mv = nullptr;    // mv[1..]: mv_len - 1 elements
+    const uint8_t *packed = nullptr; // (l_seq + 1) / 2 bytes
+    uint64_t ns = 0, ts = 0;
+    bool has_ns = false, has_ts = false, has_mv = false, mv_is_Bc = false;
+    std::vector<int8_t> mv_store; std::vector<uint8_t> packed_store; // SAM
+};
 class SamBamReader {
 public:
     bool open(const std::string &path, std::string &err); // SAM text or BGZF-compressed BAM, detected by content
     int next(MoveRec &out, std::string &err);              // 1 = record, 0 = end of file, -1 = error
+    int next_raw(RawMoveRec &out, std::string &err);       // the same
 private:
+    int next_impl(MoveRec &out, RawMoveRec *raw, std::string &err);
     MappedFile f_;
     bool bam_ = false;
     size_t pos_ = 0;                 // SAM: offset into the file; BAM: offset of the next BGZF block

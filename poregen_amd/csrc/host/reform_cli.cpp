@@ -17,7 +17,14 @@
 
 namespace {
 
-constexpr uint32_t kStride = 5; // EXPECTED_STRIDE, src/reform.cpp:22
+constexpr uint32_t kDefaultStride = 5; // EXPECTED_STRIDE, src/reform.cpp:22
+
+// --rna, --stride: what `squigualiser reform --rna` adds to the reference's reform (scripts/poregen.sh STEP 4) and the stride of an
+// RNA004 basecaller's move table (10)
+struct Extra {
+    bool rna = false;
+    uint32_t stride = kDefaultStride; // the stride mv[0] has to hold; 0: whatever it holds, from 1 up (the gmove BAM path takes any)
+};
 
 const struct option kLongOptions[] = {
     {"kmer_length", required_argument, nullptr, 'k'},
@@ -31,6 +38,8 @@ const struct option kLongOptions[] = {
     {"version", no_argument, nullptr, 'V'},
     {"output", required_argument, nullptr, 'o'},
     {"debug-break", required_argument, nullptr, 0},
+    {"rna", no_argument, nullptr, 0},
+    {"stride", required_argument, nullptr, 0},
     {nullptr, 0, nullptr, 0}};
 
 void usage(FILE *fp, uint32_t k, uint32_t m) {
@@ -42,6 +51,8 @@ void usage(FILE *fp, uint32_t k, uint32_t m) {
     fprintf(fp, "   -o FILE                    output to file [stdout]\n");
     fprintf(fp, "   --verbose INT              verbosity level\n");
     fprintf(fp, "   --version                  print version\n");
+    fprintf(fp, "   --rna                      dataset is rna: PAF target columns n_kmers, 0 and a k-mer index that counts down\n");
+    fprintf(fp, "   --stride INT               expected stride of the move table, 0 = any [%u]\n", kDefaultStride);
 }
 
 int fail(const char *msg) {
@@ -51,13 +62,19 @@ int fail(const char *msg) {
 
 // One record. Returns 0, or -1 where the reference returns -1 (src/reform.cpp:212-240,344-357) or would read
 // past the end of the mv array (src/reform.cpp:248-254,287-294: fewer than sig_move_offset+1 moves).
-int reform_record(FILE *out, const pgh::MoveRec &r, uint32_t k, uint32_t m, bool paf) {
+int reform_record(FILE *out, const pgh::MoveRec &r, uint32_t k, uint32_t m, bool paf, const Extra &x) {
     if (!r.has_ns) return fail("tag 'ns' is not found. Please check your SAM/BAM file: ");
     if (!r.has_ts) return fail("tag 'ts' is not found. Please check your SAM/BAM file: ");
     if (!r.has_mv) return fail("NULL returned for tag mv: ");
     if (!r.mv_is_Bc) return fail("tag 'mv' specification is incorrect");
     if (r.mv_len == 0) return fail("mv array length is 0: ");
-    if (r.stride != (int)kStride) return fail("expected stride of 5 is missing.");
+    if (x.stride ? r.stride != (int)x.stride : r.stride < 1) {
+        if (x.stride == kDefaultStride) return fail("expected stride of 5 is missing.");
+        if (!x.stride) return fail("the stride of the move table (mv[0]) is less than 1.");
+        fprintf(stderr, "[reform::ERROR]\033[1;31m expected stride of %u is missing.\033[0m\n", x.stride);
+        return -1;
+    }
+    const uint32_t stride = (uint32_t)r.stride;
 
     const uint32_t len_mv = r.mv_len;
     const int64_t ns = (int64_t)r.ns, ts = (int64_t)r.ts;
@@ -75,11 +92,14 @@ int reform_record(FILE *out, const pgh::MoveRec &r, uint32_t k, uint32_t m, bool
     const char *id = r.qname.c_str();
 
     if (!paf) { // src/reform.cpp:245-282
-        uint64_t start = (uint64_t)(ts + ((int64_t)first - 1) * kStride);
-        uint32_t kmer_idx = 0;
+        uint64_t start = (uint64_t)(ts + ((int64_t)first - 1) * stride);
+        // --rna: the rows keep their signal order, the index counts down from n_kmers - 1 (the 3' end is sequenced first)
+        uint32_t kmer_idx = x.rna ? n_kmers - 1 : 0;
+        const uint32_t step = x.rna ? (uint32_t)-1 : 1u;
         for (size_t j = 0; j < n_after && n_kmers > 0; j++, n_kmers--) {
-            const uint64_t end = (uint64_t)(ts + ((int64_t)pos[m + 1 + j] - 1) * kStride);
-            fprintf(out, "%s\t%" PRIu32 "\t%" PRIu64 "\t%" PRIu64 "\n", id, kmer_idx++, start, end);
+            const uint64_t end = (uint64_t)(ts + ((int64_t)pos[m + 1 + j] - 1) * stride);
+            fprintf(out, "%s\t%" PRIu32 "\t%" PRIu64 "\t%" PRIu64 "\n", id, kmer_idx, start, end);
+            kmer_idx += step;
             start = end;
         }
         if (body && n_kmers > 0) // the last k-mer runs to the end of the signal
@@ -92,20 +112,20 @@ int reform_record(FILE *out, const pgh::MoveRec &r, uint32_t k, uint32_t m, bool
     const uint32_t want = n_kmers + m + 1;
     uint64_t raw_end;
     if (want > pos.size()) raw_end = (uint64_t)ns;
-    else raw_end = (uint64_t)(ts + ((int64_t)(want ? pos[want - 1] : 2u) - 1) * kStride);
-    fprintf(out, "%s\t%" PRIu64 "\t%" PRIu64 "\t%" PRIu64 "\t+\t%s\t%" PRIu32 "\t0\t%" PRIu32 "\t%" PRIu32 "\t%" PRIu32 "\t255\tss:Z:", id, (uint64_t)ns,
-            (uint64_t)(ts + ((int64_t)first - 1) * kStride), raw_end, id, n_kmers, n_kmers, n_kmers, n_kmers);
+    else raw_end = (uint64_t)(ts + ((int64_t)(want ? pos[want - 1] : 2u) - 1) * stride);
+    fprintf(out, "%s\t%" PRIu64 "\t%" PRIu64 "\t%" PRIu64 "\t+\t%s\t%" PRIu32 "\t%" PRIu32 "\t%" PRIu32 "\t%" PRIu32 "\t%" PRIu32 "\t255\tss:Z:", id, (uint64_t)ns,
+            (uint64_t)(ts + ((int64_t)first - 1) * stride), raw_end, id, n_kmers, x.rna ? n_kmers : 0u, x.rna ? 0u : n_kmers, n_kmers, n_kmers);
     uint32_t prev = first;
     for (size_t j = 0; j < n_after && n_kmers > 0; j++, n_kmers--) {
-        fprintf(out, "%" PRIu32 ",", (pos[m + 1 + j] - prev) * kStride);
+        fprintf(out, "%" PRIu32 ",", (pos[m + 1 + j] - prev) * stride);
         prev = pos[m + 1 + j];
     }
     if (body && n_kmers > 0) {
         const uint32_t last = len_mv - 1;
-        const int64_t tail = ns - ((int64_t)((last - 1) * kStride) + ts);
+        const int64_t tail = ns - ((int64_t)((last - 1) * stride) + ts);
         if (tail < 0) return fail("Error in calcuation. (ns - ((i-1)*EXPECTED_STRIDE + ts)) > 0 is not valid");
         n_kmers--;
-        fprintf(out, "%" PRIu32 ",", (uint32_t)((last - prev) * kStride + tail));
+        fprintf(out, "%" PRIu32 ",", (uint32_t)((last - prev) * stride + tail));
     }
     if (n_kmers != 0) {
         fprintf(stderr, "[reform::ERROR]\033[1;31m Error in the implementation. Please report the command with minimal reproducible data. Read_id: %s\033[0m\n", id);
@@ -120,6 +140,7 @@ int reform_record(FILE *out, const pgh::MoveRec &r, uint32_t k, uint32_t m, bool
 int reform_main(int argc, char **argv) {
     uint32_t k = 9, m = 0; // init_opt, src/poregen.cpp:209-237
     bool paf = false, help_to_stdout = false;
+    Extra extra;
     const char *out_path = nullptr;
     int c, longindex = 0;
     optind = 1;
@@ -132,6 +153,11 @@ int reform_main(int argc, char **argv) {
         else if (c == 'o') out_path = optarg;
         else if (c == 'V') { fprintf(stdout, "subtool0 0.1.0\n"); exit(EXIT_SUCCESS); }
         else if (c == 'h') help_to_stdout = true;
+        else if (c == 0 && !strcmp(kLongOptions[longindex].name, "rna")) extra.rna = true;
+        else if (c == 0 && !strcmp(kLongOptions[longindex].name, "stride")) {
+            if (atoi(optarg) < 0) { fail("Stride should not be negative."); exit(EXIT_FAILURE); }
+            extra.stride = (uint32_t)atoi(optarg);
+        }
     }
     if (k < 1) return fail("kmer length must be a positive integer");
     if (k <= m) return fail("signal move offset value must less than the kmer length");
@@ -155,7 +181,7 @@ int reform_main(int argc, char **argv) {
     pgh::MoveRec rec;
     int got, ret = 0;
     while ((got = rd.next(rec, err)) > 0)
-        if ((ret = reform_record(out, rec, k, m, paf)) != 0) break;
+        if ((ret = reform_record(out, rec, k, m, paf, extra)) != 0) break;
     if (got < 0) { fail(err.c_str()); ret = -1; }
     if (out_path) fclose(out);
     else fflush(out);

@@ -411,3 +411,12 @@ extern "C" long pgt_kf_fasta(const uint8_t *data, uint64_t n, const uint64_t *cu
     *nul = bad;
     return (long)i;
 }
+
+// ---- move-table expansion: the per-read rule the kernels of pg_mvops.hip compile (pg_mvops.h), run on the host ----------------------
+#include "pg_mvops.h"
+extern "C" void pgt_mvops_levels(uint32_t *out3) { out3[0] = PG_MVOPS_LANE; out3[1] = PG_MVOPS_STEP; out3[2] = PG_MVOPS_PIECE; }
+extern "C" int pgt_mvops_mask4(uint32_t w) { return (int)pg_mv_mask4(w); }
+extern "C" int pgt_mvops_expand(const uint8_t *mv, uint32_t n, int32_t stride, uint64_t ns, uint64_t ts, uint32_t l_seq, const uint8_t *packed, int reverse,
+                                int n_to_t, uint32_t *ops, uint32_t *n_ops, int32_t *query_start, uint8_t *seq) {
+    return (int)pg_mv_expand_host(mv, n, stride, ns, ts, l_seq, packed, reverse != 0, n_to_t != 0, ops, n_ops, query_start, seq);
+}

@@ -1204,3 +1204,131 @@ def transform_model(raw_text, stdv, mean, stdv_min="2.5", stdv_max="4", stdv_fro
         return C.string_at(out, n_out.value).decode()
     finally:
         lib.pg_transform_free(out)
+
+
+# ---- move tables to ss ops (pg_mvops_*) ------------------------------------------------------------------------------------------------
+
+class MoveOps:
+    """The result of MoveExpander.expand: CUDA tensors that alias the expander's device buffers (valid until its next expand / close), in
+    the layout of a pg_batch -- op_n uint32 (as int32 bits), op_t uint8, op_off int64[n + 1], query_start / target_start / target_end
+    int32[n], seq uint8 (ASCII), seq_off int64[n + 1], status int32[n] -- plus n_ops, n_refused, first_refused and the statuses on the
+    host (numpy uint32[n])."""
+
+    def __init__(self, res, device):
+        import torch
+
+        class _Alias:  # zero-copy hand-over through the CUDA array interface
+            def __init__(self, ptr, n, typestr):
+                self.__cuda_array_interface__ = {"shape": (int(n),), "typestr": typestr, "data": (int(ptr or 0), False), "version": 2}
+
+        dev = torch.device("cuda", device)
+
+        def wrap(ptr, n, typestr, dtype):
+            if n == 0 or not ptr:
+                return torch.empty(0, dtype=dtype, device=dev)
+            return torch.as_tensor(_Alias(ptr, n, typestr), device=dev)
+
+        n = int(res.n_reads)
+        self.n_reads, self.n_ops, self.n_seq = n, int(res.n_ops), int(res.n_seq)
+        self.n_refused, self.first_refused = int(res.n_refused), int(res.first_refused)
+        self.op_n = wrap(res.op_n, self.n_ops, "<i4", torch.int32)
+        self.op_t = wrap(res.op_t, self.n_ops, "|u1", torch.uint8)
+        self.op_off = wrap(res.op_off, n + 1, "<i8", torch.int64)
+        self.query_start = wrap(res.query_start, n, "<i4", torch.int32)
+        self.target_start = wrap(res.target_start, n, "<i4", torch.int32)
+        self.target_end = wrap(res.target_end, n, "<i4", torch.int32)
+        self.seq = wrap(res.seq, self.n_seq, "|u1", torch.uint8)
+        self.seq_off = wrap(res.seq_off, n + 1, "<i8", torch.int64)
+        self.status_device = wrap(res.status, n, "<i4", torch.int32)
+        self.status = np.ctypeslib.as_array(C.cast(res.status_host, C.POINTER(C.c_uint32)), (n,)).copy() if n else np.zeros(0, np.uint32)
+
+    def to_host(self):
+        """Every array as numpy, in the widths of the ABI (op_n uint32, offsets uint64)."""
+        return dict(op_n=self.op_n.cpu().numpy().view(np.uint32), op_t=self.op_t.cpu().numpy(), op_off=self.op_off.cpu().numpy().view(np.uint64),
+                    query_start=self.query_start.cpu().numpy(), target_start=self.target_start.cpu().numpy(), target_end=self.target_end.cpu().numpy(),
+                    seq=self.seq.cpu().numpy(), seq_off=self.seq_off.cpu().numpy().view(np.uint64), status=self.status_device.cpu().numpy().view(np.uint32))
+
+
+class MoveExpander:
+    """Expands the move tables of a batch of BAM records into the ss ops `poregen reform -c -k 1 -m 0` prints (pg_mvops_*). The nine
+    arrays of expand() are numpy arrays, or contiguous CUDA tensors of the same widths (read in place)."""
+
+    _ARGS = (("mv", 1, np.int8), ("mv_off", 8, np.uint64), ("stride", 4, np.int32), ("ns", 8, np.uint64), ("ts", 8, np.uint64), ("l_seq", 4, np.uint32),
+             ("flag", 4, np.uint32), ("seq_bytes", 1, np.uint8), ("byte_off", 8, np.uint64))
+
+    def __init__(self, device: int = 0):
+        self._lib = _abi.load()
+        self.device = device
+        h = C.c_void_p()
+        st = self._lib.pg_mvops_create(device, C.byref(h))
+        if st != 0:
+            raise PgError(st, self._lib.pg_mvops_last_error(None).decode())
+        self._h = h
+
+    @property
+    def piece(self) -> int:
+        """Table elements per piece of a long read (pg_mvops_piece)."""
+        return int(self._lib.pg_mvops_piece(self._h))
+
+    def set_stream(self, stream=None):
+        """Run on a caller-owned stream (a torch.cuda.Stream or a raw hipStream_t value); None: the expander's own."""
+        ptr = None if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
+        st = self._lib.pg_mvops_set_stream(self._h, ptr)
+        if st != 0:
+            raise PgError(st, self._lib.pg_mvops_last_error(self._h).decode())
+
+    def expand(self, mv, mv_off, stride, ns, ts, l_seq, flag, seq_bytes, byte_off, rna: bool = False, n_to_t: bool = False) -> MoveOps:
+        given = (mv, mv_off, stride, ns, ts, l_seq, flag, seq_bytes, byte_off)
+        on_dev = [hasattr(a, "is_cuda") and a.is_cuda for a in given]
+        b = _abi.PgMvopsBatch()
+        b.flags = (_abi.PG_MVOPS_RNA if rna else 0) | (_abi.PG_MVOPS_N_TO_T if n_to_t else 0)
+        if all(on_dev):
+            for a, (name, size, _) in zip(given, self._ARGS):
+                if a.dtype.itemsize != size or not a.is_contiguous():
+                    raise ValueError(f"device batch: {name} must be a contiguous tensor of {size}-byte integers")
+            keep = given
+            ptrs = [C.c_void_p(a.data_ptr()) for a in given]
+            sizes = [a.numel() for a in given]
+            b.location = _abi.PG_LOC_DEVICE
+        elif any(on_dev):
+            raise ValueError("expand takes nine host arrays or nine device tensors, not a mixture")
+        else:
+            keep = [np.ascontiguousarray(np.frombuffer(a, dt) if isinstance(a, (bytes, bytearray, memoryview)) else a, dtype=dt) for a, (_, _, dt) in zip(given, self._ARGS)]
+            ptrs = [C.c_void_p(a.ctypes.data) for a in keep]
+            sizes = [a.size for a in keep]
+            b.location = _abi.PG_LOC_HOST
+        n = sizes[5]
+        if sizes[1] != n + 1 or any(sizes[i] != n for i in (2, 3, 4, 6, 8)):
+            raise ValueError("mv_off needs n + 1 entries; stride, ns, ts, l_seq, flag and byte_off one per read")
+        b.n_reads = n
+        b.mv, b.mv_off, b.stride, b.ns, b.ts, b.l_seq, b.flag, b.seq_bytes, b.byte_off = ptrs
+        b.n_mv_bytes, b.n_seq_bytes = sizes[0], sizes[7]
+        res = _abi.PgMvopsResult()
+        st = self._lib.pg_mvops_expand(self._h, C.byref(b), C.byref(res))
+        del keep
+        if st != 0:
+            raise PgError(st, self._lib.pg_mvops_last_error(self._h).decode())
+        return MoveOps(res, self.device)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.pg_mvops_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def reform_ops(mv, mv_off, stride, ns, ts, l_seq, flag, seq_bytes, byte_off, rna: bool = False, n_to_t: bool = False, device: int = 0):
+    """One-shot MoveExpander.expand: the result's arrays on the host (MoveOps.to_host) plus n_ops, n_refused and first_refused."""
+    ex = MoveExpander(device)
+    try:
+        r = ex.expand(mv, mv_off, stride, ns, ts, l_seq, flag, seq_bytes, byte_off, rna=rna, n_to_t=n_to_t)
+        out = r.to_host()
+        out.update(n_ops=r.n_ops, n_refused=r.n_refused, first_refused=r.first_refused)
+        return out
+    finally:
+        ex.close()
