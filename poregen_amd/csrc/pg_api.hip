@@ -99,6 +99,7 @@ struct pg_ctx {
     // long reads (PgLongState): helper table + per-read histograms in global memory, sized for long_cap helpers; long_want = helpers the
     // next batch is expected to want (host batches: counted from sig_off; device batches: what the last settled batch wanted, at least 256)
     PgDev<> long_tab, long_hist; uint32_t long_cap = 0, long_use = 0, long_want = 256; uint64_t long_reads_split = 0, long_helpers_short = 0;
+    uint64_t gather_forms[PG_GATHER_FORMS] = {0, 0, 0, 0, 0}; // launches of the chunked gather by the kernel taken (pg_gather_form), for pg_kernel_stats
 
     PgDevBatch B{};       // current batch (device view)
     bool have_count = false, have_batch_result = false, downloaded = true;
@@ -1094,9 +1095,11 @@ static pg_status collect_impl(pg_ctx *c, const uint64_t *base, int32_t base_loca
     // 0-5 % at sample_limit 5000 and nothing at k = 9, whatever share of the CUs it was given (profiles/r04_side_gather.txt).
     if (c->stats_in_flight) { PG_HIP_TRY(c, hipStreamWaitEvent(c->st, c->ev_join[c->slot], 0)); c->stats_in_flight = false; }
     prof_begin(c, "k_gather", c->st);
+    const int lanes = chunked ? gather_lanes(c) : 0;
+    if (chunked) c->gather_forms[pg_gather_form(lanes)]++;
     if (chunked)
         PG_HIP_TRY(c, pg_launch_gather_chunks(c->st, c->B, ke_cap, totals, c->ev_rec.as<PgKeptRec>(), c->chunk_part.as<uint64_t>(), c->samp_off.as<uint64_t>(), totals + 2, c->prm.scaling,
-                                           c->prm.pa_min, c->prm.pa_max, c->samples.as<double>(), c->prm.scaling == 1 ? c->gcal[c->slot].as<double>() : nullptr, gather_lanes(c),
+                                           c->prm.pa_min, c->prm.pa_max, c->samples.as<double>(), c->prm.scaling == 1 ? c->gcal[c->slot].as<double>() : nullptr, lanes,
                                            c->prm.scaling == 1 ? c->stat_err[c->slot].as<int32_t>() : nullptr));
     else
         PG_HIP_TRY(c, pg_launch_gather(c->st, c->B, gather_cap, totals, c->ev_rec.as<PgKeptRec>(),
@@ -1576,6 +1579,12 @@ pg_status pg_kernel_stats(pg_ctx *c, pg_kernel_stat *out, uint32_t cap, uint32_t
         if (out && n < cap) { out[n].name = "long_helpers_short_batches"; out[n].launches = c->long_helpers_short; out[n].total_ms = 0.0; }
         n++;
     }
+    static const char *const form_names[PG_GATHER_FORMS] = {"gather_form_wave", "gather_form_evpair", "gather_form_lanes4", "gather_form_lanes8", "gather_form_lanes16"};
+    for (int f = 0; f < PG_GATHER_FORMS; ++f)
+        if (c->gather_forms[f]) { // chunked gathers queued with this kernel (which one: gather_lanes)
+            if (out && n < cap) { out[n].name = form_names[f]; out[n].launches = c->gather_forms[f]; out[n].total_ms = 0.0; }
+            n++;
+        }
     *n_out = n;
     return PG_OK;
 }
@@ -1586,6 +1595,7 @@ pg_status pg_kernel_stats_reset(pg_ctx *c) {
     if (c->st2) PG_HIP_TRY(c, hipStreamSynchronize(c->st2));
     prof_drain(c);
     c->prof_acc.clear(); c->prof_names.clear(); c->stats_cancelled = 0; c->long_reads_split = 0; c->long_helpers_short = 0;
+    for (uint64_t &f : c->gather_forms) f = 0;
     return PG_OK;
 }
 

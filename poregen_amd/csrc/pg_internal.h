@@ -177,6 +177,9 @@ hipError_t pg_launch_rank_emit2(hipStream_t st, const uint32_t *ev_slot, uint64_
 // (part zeroed beforehand: k_rank_scan's extra workgroup). rare (may be null): the rare statistics ride in the same launch
 hipError_t pg_launch_len_partials(hipStream_t st, uint64_t n_kept_cap, const uint64_t *n_kept_ptr, const PgKeptRec *rec, uint64_t *part, const PgRareArgs *rare);
 uint32_t pg_gather_chunks(uint64_t n_kept_cap, uint32_t *sub_per_chunk);
+// the kernel pg_launch_gather_chunks launches for `lanes`: 0 k_gather_wave, 1 k_gather_evpair, 2 / 3 / 4 k_gather_chunks<4,4> / <8,3> / <16,2>
+#define PG_GATHER_FORMS 5
+int pg_gather_form(int lanes);
 // total_out: [0] = all kept samples (= samp_off[n_kept], written too), left by the workgroup of the last chunk
 hipError_t pg_launch_gather_chunks(hipStream_t st, const PgDevBatch &B, uint64_t n_kept_cap, const uint64_t *n_kept_ptr, const PgKeptRec *rec, const uint64_t *part,
                                    uint64_t *samp_off, uint64_t *total_out, int scaling, double pa_min, double pa_max, double *samples, const double *gcal, int lanes,

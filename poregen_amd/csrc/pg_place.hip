@@ -1273,21 +1273,24 @@ uint32_t pg_gather_chunks(uint64_t n_kept_cap, uint32_t *sub_per_chunk) {
     return (uint32_t)((n_kept_cap + (uint64_t)m * PG_G2_SUB - 1) / ((uint64_t)m * PG_G2_SUB));
 }
 
+int pg_gather_form(int lanes) { return lanes == 1 ? 1 : lanes == 0 ? 0 : lanes <= 4 ? 2 : lanes <= 8 ? 3 : 4; }
+
 // lanes: 0 = k_gather_wave (the default); else lanes per kept event (4, 8 or 16) of k_gather_chunks: any value is correct for any window length
 hipError_t pg_launch_gather_chunks(hipStream_t st, const PgDevBatch &B, uint64_t n_kept_cap, const uint64_t *n_kept_ptr, const PgKeptRec *rec, const uint64_t *part,
                                    uint64_t *samp_off, uint64_t *total_out, int scaling, double pa_min, double pa_max, double *samples, const double *gcal, int lanes, const int32_t *stat_flags) {
     if (n_kept_cap == 0) return hipSuccess;
     uint32_t m; const uint32_t n_chunks = pg_gather_chunks(n_kept_cap, &m);
-    if (lanes == 1) { // the event-pair form (a lane per pair of samples of ONE window)
+    const int form = pg_gather_form(lanes);
+    if (form == 1) { // the event-pair form (a lane per pair of samples of ONE window)
         PG_LAUNCH(k_gather_evpair, dim3(n_chunks), dim3(256), 0, st, B, n_kept_ptr, rec, part, m, samp_off, total_out, scaling, pa_min, pa_max, samples, gcal, stat_flags);
         return hipSuccess;
     }
-    if (lanes == 0) { // the wave form: a lane per pair of output samples, a wave per 64 events
+    if (form == 0) { // the wave form: a lane per pair of output samples, a wave per 64 events
         PG_LAUNCH(k_gather_wave, dim3(n_chunks), dim3(256), 0, st, B, n_kept_ptr, rec, part, m, samp_off, total_out, scaling, pa_min, pa_max, samples, gcal, stat_flags);
         return hipSuccess;
     }
-    if (lanes <= 4) PG_LAUNCH((k_gather_chunks<4, 4>), dim3(n_chunks), dim3(256), 0, st, B, n_kept_ptr, rec, part, m, samp_off, total_out, scaling, pa_min, pa_max, samples, gcal);
-    else if (lanes <= 8) PG_LAUNCH((k_gather_chunks<8, 3>), dim3(n_chunks), dim3(256), 0, st, B, n_kept_ptr, rec, part, m, samp_off, total_out, scaling, pa_min, pa_max, samples, gcal);
+    if (form == 2) PG_LAUNCH((k_gather_chunks<4, 4>), dim3(n_chunks), dim3(256), 0, st, B, n_kept_ptr, rec, part, m, samp_off, total_out, scaling, pa_min, pa_max, samples, gcal);
+    else if (form == 3) PG_LAUNCH((k_gather_chunks<8, 3>), dim3(n_chunks), dim3(256), 0, st, B, n_kept_ptr, rec, part, m, samp_off, total_out, scaling, pa_min, pa_max, samples, gcal);
     else PG_LAUNCH((k_gather_chunks<16, 2>), dim3(n_chunks), dim3(256), 0, st, B, n_kept_ptr, rec, part, m, samp_off, total_out, scaling, pa_min, pa_max, samples, gcal);
     return hipSuccess;
 }
