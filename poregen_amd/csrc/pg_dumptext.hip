@@ -17,12 +17,14 @@
 //   k_dt_evlen   ev_len[e] = samp_off[e + 1] - samp_off[e]
 // then pg_launch_slot_model_units: the tiny / mid / short / long kernels of pg_model.hip over (ev_off, samp_off, ev_len, units).
 // Files the device declines are finished on the host (pg_dumphost.h) when their batch is settled; see include/pgmove.h.
+// The rule for one field and the bytes per lane / tile / workgroup are pg_dumptext.h, which the host test build compiles as well.
 #include "../../include/pgmove.h"
 #include <hip/hip_runtime.h>
 #include "pg_hip_host.h"
 #include "pg_internal.h"
 #include "pg_model.h"
 #include "pg_dumphost.h"
+#include "pg_dumptext.h"
 
 #include <algorithm>
 #include <cstring>
@@ -31,15 +33,15 @@
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr uint32_t kLane = 16;                    // bytes per lane
-constexpr uint32_t kTile = 64 * kLane;            // bytes per wave: the granule of the separator prefix
-constexpr uint32_t kBlockBytes = kThreads * kLane;
+constexpr int kThreads = PG_DT_THREADS;
+constexpr uint32_t kLane = PG_DT_LANE;            // bytes per lane
+constexpr uint32_t kTile = PG_DT_TILE;            // bytes per wave: the granule of the separator prefix
+constexpr uint32_t kBlockBytes = PG_DT_BLOCK;
 constexpr int kScanThreads = 1024;
 constexpr uint64_t kMaxBatchBytes = 1ull << 31;
 constexpr uint32_t kMaxBatchFiles = 1u << 24;
-constexpr uint32_t kMinField = 11;                // "0.00000000," : a file of the strict grammar holds at most bytes / 11 values
-enum { DT_BAD = 1, DT_NEGZERO = 2 };              // per-file flags
+constexpr uint32_t kMinField = PG_DT_MIN_FIELD;   // a file of the strict grammar holds at most bytes / 11 values
+static_assert(kLane == 16 && kTile == 64 * kLane && kBlockBytes % kTile == 0, "a lane is one 16-byte load, a tile one wave of them");
 
 struct DtBatch { // one batch on the device
     const uint8_t *p; uint64_t n;
@@ -66,36 +68,6 @@ __device__ __forceinline__ uint32_t file_of(const uint64_t *__restrict__ file_of
     uint32_t lo = 0, hi = n_files;
     while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (file_off[mid] <= pos) lo = mid; else hi = mid; }
     return lo;
-}
-
-// The field in front of the separator at `sep`, read backwards; `lo` is the first byte of its file and no byte in front of lo is read.
-// true: the field is -?D{1,8}.DDDDDDDD with |value| < 4e7 and begins at lo or right behind another separator.
-__device__ __forceinline__ bool parse_field(const uint8_t *__restrict__ p, uint64_t sep, uint64_t lo, int64_t &units, bool &negzero) {
-    units = 0; negzero = false;
-    if (sep < lo + 10) return false; // shorter than D.DDDDDDDD
-    uint32_t frac = 0, mul = 1;
-    bool ok = true;
-#pragma unroll
-    for (int i = 1; i <= 8; i++) { const uint32_t d = (uint32_t)p[sep - i] - '0'; ok &= d < 10u; frac += d * mul; mul *= 10; }
-    ok &= p[sep - 9] == '.';
-    if (!ok) return false;
-    uint64_t q = sep - 9; // first byte of what has been read
-    uint32_t ip = 0, nd = 0;
-    mul = 1;
-    while (q > lo) {
-        const uint32_t d = (uint32_t)p[q - 1] - '0';
-        if (d >= 10u) break;
-        if (nd == 8) return false; // a ninth integer digit: not below 4e7 unless zeros lead, which the host path reads as well
-        ip += d * mul; mul *= 10; nd++; q--;
-    }
-    if (nd == 0 || ip >= 40000000u) return false;
-    bool neg = false;
-    if (q > lo && p[q - 1] == '-') { neg = true; q--; }
-    if (q > lo && p[q - 1] != ',' && p[q - 1] != ';') return false;
-    const int64_t v = (int64_t)ip * 100000000ll + (int64_t)frac;
-    units = neg ? -v : v;
-    negzero = neg && v == 0;
-    return true;
 }
 
 // the separators among a lane's 16 bytes as bit masks (bit j = byte j); bytes at and beyond lim do not count
@@ -140,7 +112,7 @@ template <bool kAligned> __global__ __launch_bounds__(kThreads) void k_dt_count(
                 const uint64_t pos = base + (uint32_t)__builtin_ctz(m);
                 if (pos >= lf.hi) next_file(b, lf, pos);
                 int64_t u; bool nz;
-                if (!parse_field(b.p, pos, lf.lo, u, nz)) atomicOr(&b.fflags[lf.f], (uint32_t)DT_BAD);
+                if (!pg_dt_parse_field(b.p, pos, lf.lo, u, nz)) atomicOr(&b.fflags[lf.f], (uint32_t)DT_BAD);
                 else if (nz) atomicOr(&b.fflags[lf.f], (uint32_t)DT_NEGZERO);
             }
         }
@@ -256,7 +228,7 @@ template <bool kAligned> __global__ __launch_bounds__(kThreads) void k_dt_parse(
         if (pos >= lf.hi) { next_file(b, lf, pos); fs = b.fstart[lf.f]; vb = b.val_base[lf.f]; eb = b.ev_off[lf.f]; bad = b.fflags[lf.f] & DT_BAD; }
         if (bad) continue;
         int64_t u; bool nz;
-        (void)parse_field(b.p, pos, lf.lo, u, nz); // (valid: k_dt_count looked at it)
+        (void)pg_dt_parse_field(b.p, pos, lf.lo, u, nz); // (valid: k_dt_count looked at it)
         const uint64_t at = vb + (tp.x + pre_sep + __popc(m_sep & below) - fs.x);
         if (at >= b.cap_values) continue; // (never: a value takes 11 bytes)
         b.units[at] = u;

@@ -420,3 +420,14 @@ extern "C" int pgt_mvops_expand(const uint8_t *mv, uint32_t n, int32_t stride, u
                                 int n_to_t, uint32_t *ops, uint32_t *n_ops, int32_t *query_start, uint8_t *seq) {
     return (int)pg_mv_expand_host(mv, n, stride, ns, ts, l_seq, packed, reverse != 0, n_to_t != 0, ops, n_ops, query_start, seq);
 }
+
+// ---- the dump-text parser (pg_dumptext.h): the geometry of its kernels and the field rule they compile, run on the host ----------------
+#include "pg_dumptext.h"
+extern "C" void pgt_dumptext_levels(uint32_t *out4) { out4[0] = PG_DT_LANE; out4[1] = PG_DT_TILE; out4[2] = PG_DT_BLOCK; out4[3] = PG_DT_MIN_FIELD; }
+// 1 = the field in front of the separator at p[sep] is one of the strict grammar (*units, *negzero set); lo = the first byte of its file
+extern "C" int pgt_dumptext_field(const uint8_t *p, uint64_t sep, uint64_t lo, int64_t *units, int *negzero) {
+    int64_t u = 0; bool nz = false;
+    const bool ok = pg_dt_parse_field(p, sep, lo, u, nz);
+    *units = u; *negzero = nz;
+    return ok;
+}
