@@ -84,6 +84,13 @@
  * pg_dmodel_finish / _format       datamash median / sstdev per file               scripts/poregen.sh:66-67, 43
  * pg_dmodel_sync / _last_error     (no counterpart)
  *
+ * Pools of dump files -- several files read as one, `cat F1 F2 ... | tr | tail | datamash` -- have one too:
+ * pg_pool_create / _destroy        (no counterpart)
+ * pg_pool_submit                   the same parse; every file carries one group per labeling
+ * pg_pool_finish / _format         datamash median / sstdev of every group's files concatenated        scripts/poregen.sh:73-74
+ * pg_pool_sync / _last_error /     (no counterpart)
+ * _refusal
+ *
  * STEP 7 of the same script, the raw model to the final model file, is one host-only call:
  * pg_transform_model               apply_transformation and set_stddev: echo | bc -l per row, datamash min max, cut | paste
  *                                                                                  scripts/poregen.sh:87-148
@@ -745,6 +752,49 @@ pg_status pg_dmodel_sync(pg_dmodel *h);
 pg_status pg_dmodel_finish(pg_dmodel *h, pg_model_result *out, pg_dmodel_info *info);
 /* pg_model_format for the handle's last finish (which = PG_MODEL_TEXT_*), with the host-finished files' texts as datamash prints them */
 size_t    pg_dmodel_format(const pg_dmodel *h, uint32_t file, int32_t which, char *buf, size_t cap);
+
+/* ---- pools: median and sstdev of dump files read back to back, parsed, kept and selected on the device --------------------------------
+ * A pool is a list of dump files in a fixed order; its numbers are the pipeline's for the files concatenated: `cat F1 F2 ... | tr ';,' '\n'
+ * | tail -n +2 | datamash median 1` and `... sstdev 1` (scripts/poregen.sh:73-74). So the first value of the CONCATENATION is dropped --
+ * the first value of the first member that has one -- unless PG_MODEL_KEEP_FIRST is given. A caller declares n_labelings labelings,
+ * labeling l with n_groups[l] groups; every submitted file carries one group id per labeling (PG_POOL_NO_GROUP: in none), and the files
+ * of a group count in submission order, across submits. Per batch the device parses the text (the kernels of pg_dmodel_*), reduces every
+ * file with its first value kept, and appends the parsed values to an arena of 8 bytes per value that lives until finish. finish adds the
+ * files' exact moments up on the host and selects every group's two middle values on the device: a radix selection over the arena, seven
+ * streaming reads of it for all labelings and groups at once.
+ * A group is REFUSED -- status, the first file that caused it, a message; every other group is still right -- when one of its members
+ * is a file pg_dmodel_* would finish on the host (outside the strict grammar, more than 2^23 values, values further than 2^40 units from
+ * its first), when it holds a negative zero and both middle values are 0, when it has more than 2^32 - 1 values, or when its moments do
+ * not fit the result's fields. There is NO host path for pools: the text of earlier batches is gone at finish. Never a wrong number.
+ * max_values caps the arena (0: half of the device's free memory at create, in values); a submit that would pass it fails with
+ * PG_ERR_UNSUPPORTED, counts nothing of its batch and leaves the handle usable. No CPU fallback: PG_ERR_NO_DEVICE without a GPU. */
+typedef struct pg_pool pg_pool;
+#define PG_POOL_NO_GROUP 0xffffffffu
+#define PG_POOL_MAX_LABELINGS 16u
+enum { PG_POOL_GROUP_OK = 0, PG_POOL_GROUP_EMPTY = 1, PG_POOL_GROUP_REFUSED = 2 };
+typedef struct {
+    pg_model_result model;        /* one slot per group, labeling after labeling; dwell_n 0 and dwell_median NaN; a refused group reads as empty */
+    uint32_t n_groups, n_batches; /* sum of n_groups[] */
+    const uint32_t *status;       /* [n_groups] PG_POOL_GROUP_* */
+    const int64_t  *refused_file; /* [n_groups] the first file (index in submission order since the last finish) that caused the refusal, else -1 */
+    const uint64_t *n_files;      /* [n_groups] members */
+    uint64_t n_files_total, n_bytes;
+    uint64_t n_values;            /* values in the arena */
+    double select_ms;             /* device time of the seven histogram passes and their picks (HIP events) */
+} pg_pool_result;
+pg_status pg_pool_create(int32_t device, uint32_t n_labelings, const uint32_t *n_groups, uint64_t max_values, uint32_t flags, pg_pool **out);
+void      pg_pool_destroy(pg_pool *h);
+const char *pg_pool_last_error(const pg_pool *h); /* h may be NULL: error of the last failed pg_pool_create */
+/* bytes, file_off, n_files, location: as pg_dmodel_submit, with the same limits. group: host uint32[n_labelings][n_files]. The call
+ * returns when the batch is in the arena; PG_LOC_DEVICE bytes are free again then. */
+pg_status pg_pool_submit(pg_pool *h, const void *bytes, const uint64_t *file_off, uint32_t n_files, const uint32_t *group, int32_t location);
+pg_status pg_pool_sync(pg_pool *h);
+/* Every file since the last finish; the arena is emptied by the next submit. out is owned by the handle until the next submit / finish / destroy. */
+pg_status pg_pool_finish(pg_pool *h, pg_pool_result *out);
+/* pg_model_format of a group (which = PG_MODEL_TEXT_MEDIAN or PG_MODEL_TEXT_SSTDEV); an empty or refused group gives the empty string */
+size_t    pg_pool_format(const pg_pool *h, uint32_t group, int32_t which, char *buf, size_t cap);
+/* why the group was refused at the last finish ("" for a group that was not); owned by the handle */
+const char *pg_pool_refusal(const pg_pool *h, uint32_t group);
 
 /* ---- transform: the raw k-mer model to the final model file (STEP 7), on the host -------------------------------------------------------
  * scripts/poregen.sh:87-129 (apply_transformation) and, with stdv_from, :131-148 (set_stddev), without bc, datamash, cut and paste. No

@@ -32,6 +32,9 @@ PG_DMODEL_PROFILE = 256
 PG_MVOPS_RNA, PG_MVOPS_N_TO_T = 1, 2
 PG_MVOPS_ST_ACCEPTED, PG_MVOPS_ST_NO_MOVE_IN_TABLE, PG_MVOPS_ST_NEGATIVE_TAIL, PG_MVOPS_ST_BASES_LEFT_OVER, PG_MVOPS_ST_BAD_STRIDE = 0, 1, 2, 3, 4
 PG_MODEL_TEXT_MEDIAN, PG_MODEL_TEXT_SSTDEV, PG_MODEL_TEXT_DWELL = 0, 1, 2
+PG_POOL_NO_GROUP = 0xffffffff
+PG_POOL_MAX_LABELINGS = 16
+PG_POOL_GROUP_OK, PG_POOL_GROUP_EMPTY, PG_POOL_GROUP_REFUSED = 0, 1, 2
 
 # every symbol include/pgmove.h declares (checked by tests/test_abi.py)
 EXPORTS = [
@@ -47,6 +50,7 @@ EXPORTS = [
     "pg_pamean_submit_svb", "pg_pamean_svb_samples",
     "pg_sigdec_create", "pg_sigdec_destroy", "pg_sigdec_last_error", "pg_sigdec_counts", "pg_sigdec_decode",
     "pg_dmodel_create", "pg_dmodel_destroy", "pg_dmodel_last_error", "pg_dmodel_submit", "pg_dmodel_sync", "pg_dmodel_finish", "pg_dmodel_format",
+    "pg_pool_create", "pg_pool_destroy", "pg_pool_last_error", "pg_pool_submit", "pg_pool_sync", "pg_pool_finish", "pg_pool_format", "pg_pool_refusal",
     "pg_transform_model", "pg_transform_free",
     "pg_mvops_create", "pg_mvops_destroy", "pg_mvops_last_error", "pg_mvops_piece", "pg_mvops_set_stream", "pg_mvops_stream", "pg_mvops_expand",
 ]
@@ -144,6 +148,11 @@ class PgDmodelInfo(C.Structure):
     _fields_ = [("n_files", C.c_uint64), ("n_bytes", C.c_uint64), ("n_values", C.c_uint64), ("n_host_files", C.c_uint64),
                 ("host_files", C.POINTER(C.c_uint32)), ("n_batches", C.c_uint32), ("reserved", C.c_uint32),
                 ("parse_ms", C.c_double), ("model_ms", C.c_double)]
+
+
+class PgPoolResult(C.Structure):
+    _fields_ = [("model", PgModelResult), ("n_groups", C.c_uint32), ("n_batches", C.c_uint32), ("status", C.c_void_p), ("refused_file", C.c_void_p),
+                ("n_files", C.c_void_p), ("n_files_total", C.c_uint64), ("n_bytes", C.c_uint64), ("n_values", C.c_uint64), ("select_ms", C.c_double)]
 
 
 class PgKernelStat(C.Structure):
@@ -285,6 +294,15 @@ def load():
     lib.pg_dmodel_sync.argtypes = [vp]; lib.pg_dmodel_sync.restype = i32
     lib.pg_dmodel_finish.argtypes = [vp, C.POINTER(PgModelResult), C.POINTER(PgDmodelInfo)]; lib.pg_dmodel_finish.restype = i32
     lib.pg_dmodel_format.argtypes = [vp, u32, i32, C.c_char_p, C.c_size_t]; lib.pg_dmodel_format.restype = C.c_size_t
+    if hasattr(lib, "pg_pool_create"):  # (as above: an earlier round's measurement build lacks the newer entry points)
+        lib.pg_pool_create.argtypes = [i32, u32, vp, C.c_uint64, u32, C.POINTER(vp)]; lib.pg_pool_create.restype = i32
+        lib.pg_pool_destroy.argtypes = [vp]; lib.pg_pool_destroy.restype = None
+        lib.pg_pool_last_error.argtypes = [vp]; lib.pg_pool_last_error.restype = C.c_char_p
+        lib.pg_pool_submit.argtypes = [vp, vp, vp, u32, vp, i32]; lib.pg_pool_submit.restype = i32
+        lib.pg_pool_sync.argtypes = [vp]; lib.pg_pool_sync.restype = i32
+        lib.pg_pool_finish.argtypes = [vp, C.POINTER(PgPoolResult)]; lib.pg_pool_finish.restype = i32
+        lib.pg_pool_format.argtypes = [vp, u32, i32, C.c_char_p, C.c_size_t]; lib.pg_pool_format.restype = C.c_size_t
+        lib.pg_pool_refusal.argtypes = [vp, u32]; lib.pg_pool_refusal.restype = C.c_char_p
     lib.pg_transform_model.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t,
                                        C.POINTER(vp), C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]; lib.pg_transform_model.restype = i32
     lib.pg_transform_free.argtypes = [vp]; lib.pg_transform_free.restype = None

@@ -5,13 +5,17 @@
 //   * one line per name, NAME<TAB>median<TAB>stddev, to -o (truncated) or stdout          scripts/poregen.sh:66-72
 //   * stddev > limit (bc -l on the two texts) prints the limit's text                     scripts/poregen.sh:69-71
 //   * --dwell_model FILE: NAME<TAB>median dwell, appended                                 scripts/poregen.sh:43-45
+//   * --pool START:LEN: one line per sub-k-mer name[START:START+LEN], SUB<TAB>median<TAB>stddev of that group's files read back to back
+//     (pg_pool_*): `cat` of the files | tr | tail | datamash                              scripts/poregen.sh:73-74
 #include "../../../include/pgmove.h"
 #include "../pg_dumphost.h"
 #include "pg_dumpdir.h"
+#include "pg_poolnames.h"
 
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
 #include <future>
 #include <getopt.h>
@@ -27,6 +31,7 @@ const struct option kLongOptions[] = {
     {"output", required_argument, nullptr, 'o'},    // 3
     {"threads", required_argument, nullptr, 't'},   // 4
     {"help", no_argument, nullptr, 'h'},            // 5
+    {"pool", required_argument, nullptr, 0},        // 6
     {nullptr, 0, nullptr, 0}};
 
 void print_help(FILE *fp) {
@@ -37,6 +42,7 @@ void print_help(FILE *fp) {
     fprintf(fp, "   -o FILE                    output to file [stdout]\n");
     fprintf(fp, "   --dwell_model FILE         also append KMER<TAB>median dwell to FILE (scripts/poregen.sh calculate_dwell_times_medians)\n");
     fprintf(fp, "   --keep_first               keep the first value of every file (the pipeline's `tail -n +2` drops it)\n");
+    fprintf(fp, "   --pool START:LEN           pool the files by the LEN bases of their names from 0-based START: SUB<TAB>median<TAB>stddev of each group's files read as one\n");
     fprintf(fp, "   -t INT                     threads that read files [8], at most 16\n");
     fprintf(fp, "   -h                         help\n");
 }
@@ -50,11 +56,55 @@ uint64_t batch_bytes() {
 
 struct Batch { size_t first = 0, n = 0; std::vector<uint8_t> bytes; std::vector<uint64_t> file_off; std::string err; bool ok = true; double secs = 0; };
 
+// --pool START:LEN: the files grouped by name[START:START+LEN], every group's files in name order read as one file
+int pool_main(const std::vector<std::string> &dirs, const char *spec, const char *stdv_limit, const char *out_path, bool keep_first, int n_threads) {
+    using clk = std::chrono::steady_clock;
+    auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+    char *end = nullptr;
+    const long long start = strtoll(spec, &end, 10);
+    if (end == spec || *end != ':' || start < 0) return die("--pool takes START:LEN with START >= 0. You entered %s", spec);
+    const char *lp = end + 1;
+    const long long len = strtoll(lp, &end, 10);
+    if (end == lp || *end || len < 1) return die("--pool takes START:LEN with LEN >= 1. You entered %s", spec);
+    const clk::time_point t_start = clk::now();
+    pgh::DumpSet ds;
+    std::string err;
+    if (!pgh::list_dump_dirs(dirs, n_threads, ds, err)) return die("%s", err);
+    pgh::PoolNames pn;
+    if (!pgh::check_pool_names(ds.names, pn, err)) return die("[model] --pool: %s", err);
+    if ((unsigned long long)start + (unsigned long long)len > pn.k) return die(("[model] --pool %s does not lie inside names of length " + std::to_string(pn.k)).c_str(), spec);
+    const double t_list = secs(t_start, clk::now());
+    // the names are sorted, so are the sub-k-mers of one START when taken in a sorted set
+    std::vector<std::string> subs;
+    for (const std::string &n : ds.names) subs.push_back(n.substr((size_t)start, (size_t)len));
+    std::vector<std::string> uniq(subs);
+    std::sort(uniq.begin(), uniq.end());
+    uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+    std::vector<uint32_t> group_of(subs.size());
+    for (size_t i = 0; i < subs.size(); i++) group_of[i] = (uint32_t)(std::lower_bound(uniq.begin(), uniq.end(), subs[i]) - uniq.begin());
+    pg_pool *h = nullptr; pg_pool_result res; pgh::PoolTimes tm;
+    if (!pgh::run_pool(ds, n_threads, keep_first, {(uint32_t)uniq.size()}, [&](size_t f, uint32_t *g) { g[0] = group_of[f]; }, &h, res, tm, err)) return die("[model] %s", err);
+    uint32_t bad; std::string what;
+    if (pgh::pool_refused(ds, h, res, bad, what)) { fprintf(stderr, "[model] group %s is refused: %s\n", uniq[bad].c_str(), what.c_str()); pg_pool_destroy(h); return EXIT_FAILURE; }
+    const clk::time_point p0 = clk::now();
+    FILE *fp = stdout;
+    if (out_path && !(fp = fopen(out_path, "w"))) { pg_pool_destroy(h); return die("Could not open %s for writing.", out_path); }
+    char a[64], b[64];
+    for (uint32_t g = 0; g < res.n_groups; g++) {
+        pg_pool_format(h, g, PG_MODEL_TEXT_MEDIAN, a, sizeof a); pg_pool_format(h, g, PG_MODEL_TEXT_SSTDEV, b, sizeof b);
+        fprintf(fp, "%s\t%s\t%s\n", uniq[g].c_str(), a, pg_dump_sd_capped(b, stdv_limit) ? stdv_limit : b);
+    }
+    if (out_path) fclose(fp); else fflush(fp);
+    pgh::pool_summary("model", res, tm, t_list, secs(p0, clk::now()), n_threads);
+    pg_pool_destroy(h);
+    return EXIT_SUCCESS;
+}
+
 } // namespace
 
 int model_main(int argc, char **argv) {
     using clk = std::chrono::steady_clock;
-    const char *stdv_limit = "3.1", *out_path = nullptr, *dwell_path = nullptr;
+    const char *stdv_limit = "3.1", *out_path = nullptr, *dwell_path = nullptr, *pool = nullptr;
     bool keep_first = false, help = false;
     int n_threads = 8;
     int c, longindex = 0;
@@ -66,6 +116,7 @@ int model_main(int argc, char **argv) {
         else if (c == 0 && longindex == 0) stdv_limit = optarg;
         else if (c == 0 && longindex == 1) dwell_path = optarg;
         else if (c == 0 && longindex == 2) keep_first = true;
+        else if (c == 0 && longindex == 6) pool = optarg;
         else { print_help(stderr); return EXIT_FAILURE; }
     }
     if (help) { print_help(stdout); return EXIT_SUCCESS; }
@@ -74,6 +125,8 @@ int model_main(int argc, char **argv) {
     if (n_threads < 1) return die("-t must be at least 1. You entered %s", std::to_string(n_threads));
     if (n_threads > 16) n_threads = 16;
     std::vector<std::string> dirs(argv + optind, argv + argc);
+    if (pool && dwell_path) return die("--dwell_model cannot be combined with --pool%s");
+    if (pool) return pool_main(dirs, pool, stdv_limit, out_path, keep_first, n_threads);
 
     const clk::time_point t_start = clk::now();
     auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };

@@ -43,18 +43,7 @@ constexpr uint32_t kMaxBatchFiles = 1u << 24;
 constexpr uint32_t kMinField = PG_DT_MIN_FIELD;   // a file of the strict grammar holds at most bytes / 11 values
 static_assert(kLane == 16 && kTile == 64 * kLane && kBlockBytes % kTile == 0, "a lane is one 16-byte load, a tile one wave of them");
 
-struct DtBatch { // one batch on the device
-    const uint8_t *p; uint64_t n;
-    const uint64_t *file_off; uint32_t n_files;
-    uint32_t n_tiles;
-    uint2 *tile_pre;    // [n_tiles + 1] (separators, ';') per wave tile; after k_dt_scan: in front of it, the totals in the last entry
-    uint32_t *fflags;   // [n_files]
-    uint2 *fstart;      // [n_files + 1] (separators, ';') in front of file_off[f]
-    uint64_t *val_base; // [n_files + 1] values of the files in front of f that count
-    uint64_t *ev_off;   // [n_files + 1] events likewise: the reduction's ev_off
-    int64_t *units; uint64_t *samp_off; uint32_t *ev_len;
-    uint64_t cap_values; // entries of units (samp_off has one more, ev_len as many)
-};
+using DtBatch = PgDtBatch; // one batch on the device (pg_internal.h)
 
 template <bool kAligned> __device__ __forceinline__ uint4 load16(const uint8_t *__restrict__ p, uint64_t o, uint64_t n) {
     if (kAligned && o + 16 <= n) return *reinterpret_cast<const uint4 *>(p + o);
@@ -350,6 +339,29 @@ template <class B> bool too_small(const B &b, size_t bytes) { return bytes > b.c
 
 } // namespace
 
+// the parse kernels of one batch, in order, on st: b.fflags zeroed and b.file_off in place before them
+hipError_t pg_launch_dump_parse(hipStream_t st, const PgDtBatch &b) {
+    const bool al = ((uintptr_t)b.p & 15) == 0;
+    const size_t nf1 = (size_t)b.n_files + 1;
+    const uint32_t byte_blocks = (uint32_t)((b.n + kBlockBytes - 1) / kBlockBytes), file_blocks = (uint32_t)((nf1 + kThreads - 1) / kThreads);
+    (void)hipGetLastError();
+    if (byte_blocks) {
+        if (al) hipLaunchKernelGGL(k_dt_count<true>, dim3(byte_blocks), dim3(kThreads), 0, st, b);
+        else hipLaunchKernelGGL(k_dt_count<false>, dim3(byte_blocks), dim3(kThreads), 0, st, b);
+    }
+    hipLaunchKernelGGL(k_dt_scan, dim3(1), dim3(kScanThreads), 0, st, b);
+    if (al) hipLaunchKernelGGL(k_dt_starts<true>, dim3(file_blocks), dim3(kThreads), 0, st, b);
+    else hipLaunchKernelGGL(k_dt_starts<false>, dim3(file_blocks), dim3(kThreads), 0, st, b);
+    hipLaunchKernelGGL(k_dt_files, dim3(1), dim3(kScanThreads), 0, st, b);
+    if (byte_blocks) {
+        if (al) hipLaunchKernelGGL(k_dt_parse<true>, dim3(byte_blocks), dim3(kThreads), 0, st, b);
+        else hipLaunchKernelGGL(k_dt_parse<false>, dim3(byte_blocks), dim3(kThreads), 0, st, b);
+        const uint32_t ev_blocks = (uint32_t)std::min<uint64_t>((b.cap_values + kThreads - 1) / kThreads, 4096);
+        hipLaunchKernelGGL(k_dt_evlen, dim3(ev_blocks), dim3(kThreads), 0, st, b);
+    }
+    return hipGetLastError();
+}
+
 extern "C" {
 
 const char *pg_dmodel_last_error(const pg_dmodel *h) { return h ? h->err.c_str() : pg_create_error<pg_dmodel>().c_str(); }
@@ -448,25 +460,8 @@ pg_status pg_dmodel_submit(pg_dmodel *h, const void *bytes, const uint64_t *file
     b.val_base = h->d_val_base.as<uint64_t>(); b.ev_off = h->d_ev_off.as<uint64_t>();
     b.units = h->d_units.as<int64_t>(); b.samp_off = h->d_samp_off.as<uint64_t>(); b.ev_len = h->d_ev_len.as<uint32_t>();
     b.cap_values = cap_values;
-    const bool al = ((uintptr_t)p & 15) == 0;
-    const uint32_t byte_blocks = (uint32_t)((n + kBlockBytes - 1) / kBlockBytes), file_blocks = (uint32_t)((nf1 + kThreads - 1) / kThreads);
-    (void)hipGetLastError();
     PG_HIP_TRY(h, hipEventRecord(s.t0, h->st));
-    if (byte_blocks) {
-        if (al) hipLaunchKernelGGL(k_dt_count<true>, dim3(byte_blocks), dim3(kThreads), 0, h->st, b);
-        else hipLaunchKernelGGL(k_dt_count<false>, dim3(byte_blocks), dim3(kThreads), 0, h->st, b);
-    }
-    hipLaunchKernelGGL(k_dt_scan, dim3(1), dim3(kScanThreads), 0, h->st, b);
-    if (al) hipLaunchKernelGGL(k_dt_starts<true>, dim3(file_blocks), dim3(kThreads), 0, h->st, b);
-    else hipLaunchKernelGGL(k_dt_starts<false>, dim3(file_blocks), dim3(kThreads), 0, h->st, b);
-    hipLaunchKernelGGL(k_dt_files, dim3(1), dim3(kScanThreads), 0, h->st, b);
-    if (byte_blocks) {
-        if (al) hipLaunchKernelGGL(k_dt_parse<true>, dim3(byte_blocks), dim3(kThreads), 0, h->st, b);
-        else hipLaunchKernelGGL(k_dt_parse<false>, dim3(byte_blocks), dim3(kThreads), 0, h->st, b);
-        const uint32_t ev_blocks = (uint32_t)std::min<uint64_t>((cap_values + kThreads - 1) / kThreads, 4096);
-        hipLaunchKernelGGL(k_dt_evlen, dim3(ev_blocks), dim3(kThreads), 0, h->st, b);
-    }
-    PG_HIP_TRY(h, hipGetLastError());
+    PG_HIP_TRY(h, pg_launch_dump_parse(h->st, b));
     PG_HIP_TRY(h, hipEventRecord(s.t1, h->st));
     const int all_kinds[PG_MODEL_KINDS] = {1 << 20, 1 << 20, 1 << 20, 1 << 20}; // the counts are not on the host: every kernel looks
     PG_HIP_TRY(h, pg_launch_slot_model_units(h->st, n_files, all_kinds, b.ev_off, b.samp_off, b.ev_len, b.units, (h->flags & PG_MODEL_KEEP_FIRST) ? 0u : 1u,

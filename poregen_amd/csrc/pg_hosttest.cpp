@@ -431,3 +431,21 @@ extern "C" int pgt_dumptext_field(const uint8_t *p, uint64_t sep, uint64_t lo, i
     *units = u; *negzero = nz;
     return ok;
 }
+
+// ---- pools of dump files (pg_pool.h): the tile geometry of the selection and the exact combination of per-file moments ---------------
+#include "pg_pool.h"
+extern "C" void pgt_pool_levels(uint32_t *out4) { out4[0] = PG_POOL_TILE; out4[1] = PG_POOL_DIRECT; out4[2] = PG_POOL_THREADS; out4[3] = PG_POOL_MAX_LABELINGS; }
+// members as (n, origin, s1, s2 lo / hi). out8: status, why, n, origin, s1, s2 lo, s2 hi, 0; num2: n * s2 - s1^2 lo, hi; sd: its sstdev text
+extern "C" int pgt_pool_combine(size_t count, const uint64_t *n, const int64_t *origin, const int64_t *s1, const uint64_t *s2_lo, const uint64_t *s2_hi,
+                                int drop_first, int64_t second, int64_t *out8, uint64_t *num2, char *sd, size_t cap) {
+    std::vector<PgPoolMember> m(count);
+    for (size_t i = 0; i < count; i++) m[i] = PgPoolMember{n[i], origin[i], s1[i], ((unsigned __int128)s2_hi[i] << 64) | s2_lo[i]};
+    PgPoolMoments pm;
+    pg_pool_combine(m.data(), count, drop_first != 0, second, pm);
+    out8[0] = pm.status; out8[1] = pm.why; out8[2] = (int64_t)pm.n; out8[3] = pm.origin; out8[4] = pm.s1;
+    out8[5] = (int64_t)(uint64_t)pm.s2; out8[6] = (int64_t)(uint64_t)(pm.s2 >> 64); out8[7] = 0;
+    num2[0] = (uint64_t)pm.num; num2[1] = (uint64_t)(pm.num >> 64);
+    sd[0] = 0;
+    if (pm.status == PG_POOL_ST_OK) { if (pm.n < 2) snprintf(sd, cap, "nan"); else pg_model_sstdev_text(pm.n, pm.num, sd, cap); }
+    return pm.status;
+}

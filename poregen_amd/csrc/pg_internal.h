@@ -281,6 +281,21 @@ hipError_t pg_launch_slot_model(hipStream_t st, uint32_t n_slots, const int any_
 hipError_t pg_launch_slot_model_units(hipStream_t st, uint32_t n_slots, const int any_kind[4], const uint64_t *ev_off, const uint64_t *samp_off,
                                       const uint32_t *ev_len, const int64_t *units, uint32_t drop_first, PgSlotModel *out, PgSlotDwell *dwell, void *scratch);
 size_t pg_slot_model_scratch_bytes(uint32_t n_slots);
+// one batch of dump text on the device and the buffers its parse fills (pg_dumptext.hip; pg_dmodel_* and pg_pool_* share the kernels)
+struct PgDtBatch {
+    const uint8_t *p; uint64_t n;
+    const uint64_t *file_off; uint32_t n_files;
+    uint32_t n_tiles;   // (n + PG_DT_TILE - 1) / PG_DT_TILE
+    uint2 *tile_pre;    // [n_tiles + 1] (separators, ';') per wave tile; after k_dt_scan: in front of it, the totals in the last entry
+    uint32_t *fflags;   // [n_files]
+    uint2 *fstart;      // [n_files + 1] (separators, ';') in front of file_off[f]
+    uint64_t *val_base; // [n_files + 1] values of the files in front of f that count
+    uint64_t *ev_off;   // [n_files + 1] events likewise: the reduction's ev_off
+    int64_t *units; uint64_t *samp_off; uint32_t *ev_len;
+    uint64_t cap_values; // entries of units (samp_off has one more, ev_len as many): n / PG_DT_MIN_FIELD + 1
+};
+// k_dt_count .. k_dt_evlen of the batch on st; fflags must be zero and file_off uploaded in front of them (stream order)
+hipError_t pg_launch_dump_parse(hipStream_t st, const PgDtBatch &b);
 // the generic walk (one wave per listed read: walk + event loop) over O.gen_list
 hipError_t pg_launch_walk(hipStream_t st, const PgDevBatch &B, const PgWalkParams &W, const PgWalkOut &O);
 // the op-parallel event kernel over ALL op indices: computes the events of direct reads, passes the generic reads' through, and (hist

@@ -1184,6 +1184,189 @@ def model_from_dumps(dirs, limit: str = "3.1", keep_first: bool = False, batch_b
     return m.raw_model_lines(names, limit), m.dwell_lines(names), info
 
 
+@dataclass
+class PoolResult:
+    """pg_pool_finish: `model` has one entry per group, labeling after labeling (dwell fields 0 / NaN; a refused group reads as empty)."""
+    model: "Model"
+    status: np.ndarray        # per group: _abi.PG_POOL_GROUP_OK / _EMPTY / _REFUSED
+    refused_file: np.ndarray  # per group: the first file (submission order) that caused the refusal, else -1
+    n_files: np.ndarray       # per group: members
+    refusal: list             # per group: the message, "" when not refused
+    n_files_total: int
+    n_bytes: int
+    n_values: int             # values in the arena
+    n_batches: int
+    select_ms: float          # device time of the seven histogram passes
+
+
+class DumpPool:
+    """Median and sstdev of POOLS of dump files on the GPU (pg_pool_*): `n_groups[l]` groups in labeling l; submit() takes a batch of files
+    as DumpModel.submit does plus group[l][file] (PG_POOL_NO_GROUP: in none); the files of a group count in submission order, as if
+    concatenated. finish() returns a PoolResult. A group with a file the device path declines is refused: pools have no host path."""
+
+    def __init__(self, n_groups, keep_first: bool = False, max_values: int = 0, device: int = 0):
+        self._lib = _abi.load()
+        ng = np.ascontiguousarray(n_groups, dtype=np.uint32).reshape(-1)
+        h = C.c_void_p()
+        st = self._lib.pg_pool_create(device, ng.size, C.c_void_p(ng.ctypes.data), int(max_values), _abi.PG_MODEL_KEEP_FIRST if keep_first else 0, C.byref(h))
+        if st != 0:
+            raise PgError(st, self._lib.pg_pool_last_error(None).decode())
+        self._h = h
+        self.n_groups = [int(x) for x in ng]
+
+    def _check(self, st):
+        if st != 0:
+            raise PgError(st, self._lib.pg_pool_last_error(self._h).decode())
+
+    def submit(self, data, file_off, group):
+        off = np.ascontiguousarray(file_off, dtype=np.uint64)
+        if off.size < 1:
+            raise ValueError("file_off needs n_files + 1 entries")
+        g = np.ascontiguousarray(group, dtype=np.uint32).reshape(-1)
+        if g.size != len(self.n_groups) * (off.size - 1):
+            raise ValueError("group needs n_labelings * n_files entries")
+        if hasattr(data, "is_cuda") and data.is_cuda:
+            if data.dtype.itemsize != 1 or not data.is_contiguous() or data.numel() < int(off[-1]):
+                raise ValueError("device data must be a contiguous uint8 tensor of file_off[-1] bytes")
+            self._check(self._lib.pg_pool_submit(self._h, C.c_void_p(data.data_ptr()), C.c_void_p(off.ctypes.data), off.size - 1, C.c_void_p(g.ctypes.data), _abi.PG_LOC_DEVICE))
+            return
+        a = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else data, dtype=np.uint8)
+        if a.size < int(off[-1]):
+            raise ValueError("data is shorter than file_off[-1]")
+        self._check(self._lib.pg_pool_submit(self._h, C.c_void_p(a.ctypes.data) if a.size else None, C.c_void_p(off.ctypes.data), off.size - 1,
+                                             C.c_void_p(g.ctypes.data), _abi.PG_LOC_HOST))
+
+    def finish(self) -> PoolResult:
+        r = _abi.PgPoolResult()
+        self._check(self._lib.pg_pool_finish(self._h, C.byref(r)))
+        buf = C.create_string_buffer(64)
+        ng = int(r.n_groups)
+
+        def text_of(s, which):
+            if which == _abi.PG_MODEL_TEXT_DWELL:
+                return ""
+            n = self._lib.pg_pool_format(self._h, s, which, buf, 64)
+            return buf.raw[:n].decode()
+
+        def arr(ptr, dt):
+            return np.frombuffer((C.c_char * (ng * np.dtype(dt).itemsize)).from_address(ptr), dtype=dt).copy() if ng and ptr else np.zeros(0, dt)
+        return PoolResult(model=_model_arrays(r.model, text_of), status=arr(r.status, np.uint32), refused_file=arr(r.refused_file, np.int64),
+                          n_files=arr(r.n_files, np.uint64), refusal=[self._lib.pg_pool_refusal(self._h, g).decode() for g in range(ng)],
+                          n_files_total=int(r.n_files_total), n_bytes=int(r.n_bytes), n_values=int(r.n_values), n_batches=int(r.n_batches),
+                          select_ms=float(r.select_ms))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.pg_pool_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def check_pool_names(names):
+    """(K, alphabet) of dump file names that can be pooled: one length, all over ACGT or all over ACGU. ValueError names the first offender."""
+    if not names:
+        raise ValueError("no dump files")
+    k = len(names[0])
+    for n in names:
+        if len(n) != k:
+            raise ValueError(f"{n}: the names have more than one length ({len(n)} against {k})")
+    alphabet = None
+    for n in names:
+        for c in n:
+            if c not in "ACGTU":
+                raise ValueError(f"{n}: a name that is no k-mer over ACGT or ACGU")
+            if c in "TU":
+                if alphabet is None:
+                    alphabet = c
+                elif alphabet != c:
+                    raise ValueError(f"{n}: the names mix T and U")
+    return k, "ACG" + (alphabet or "T")
+
+
+def _pool_run(dirs, groups_of, n_groups, keep_first, batch_bytes, device, max_values):
+    names, paths = list_dump_dirs(dirs)
+    pool = DumpPool(n_groups, keep_first=keep_first, max_values=max_values, device=device)
+    try:
+        chunks, off, gids = [], [0], []
+
+        def flush():
+            if len(off) > 1:
+                pool.submit(b"".join(chunks), off, np.array(gids, np.uint32).T)
+            chunks.clear(); del off[1:]; gids.clear()
+        for name, ps in zip(names, paths):
+            data = b"".join(open(p, "rb").read() for p in ps)
+            if len(off) > 1 and off[-1] + len(data) > batch_bytes:
+                flush()
+            chunks.append(data); off.append(off[-1] + len(data)); gids.append(groups_of(name))
+        flush()
+        res = pool.finish()
+    finally:
+        pool.close()
+    for g in range(len(res.status)):
+        if res.status[g] == _abi.PG_POOL_GROUP_REFUSED:
+            raise PgError(_abi.PG_ERR_UNSUPPORTED, f"group {g} is refused: {names[int(res.refused_file[g])]}: {res.refusal[g]}")
+    return names, res
+
+
+def _as_dirs(dirs):
+    return [dirs] if isinstance(dirs, (str, bytes)) or hasattr(dirs, "__fspath__") else list(dirs)
+
+
+def pool_from_dumps(dirs, start: int, length: int, limit: str = "3.1", keep_first: bool = False, batch_bytes: int = 64 << 20, device: int = 0, max_values: int = 0):
+    """One-shot `poregen model --pool START:LEN`: (lines, PoolResult) -- SUB<TAB>median<TAB>stddev (capped at `limit`) for every sub-k-mer
+    name[start:start + length] that occurs, its files pooled in the byte order of their names."""
+    dirs = _as_dirs(dirs)
+    names, _ = list_dump_dirs(dirs)
+    k, _ = check_pool_names(names)
+    if start < 0 or length < 1 or start + length > k:
+        raise ValueError(f"--pool {start}:{length} does not lie inside names of length {k}")
+    subs = sorted({n[start:start + length] for n in names}, key=lambda x: x.encode())
+    index = {sub: i for i, sub in enumerate(subs)}
+    names, res = _pool_run(dirs, lambda n: [index[n[start:start + length]]], [len(subs)], keep_first, batch_bytes, device, max_values)
+    return res.model.raw_model_lines(subs, limit), res
+
+
+def offsets_from_dumps(dirs, keep_first: bool = False, batch_bytes: int = 64 << 20, device: int = 0, max_values: int = 0):
+    """One-shot `poregen offsets`: (text, PoolResult) -- the `base`, `spread` and `best` rows the command prints, tab-separated."""
+    dirs = _as_dirs(dirs)
+    names, _ = list_dump_dirs(dirs)
+    k, alphabet = check_pool_names(names)
+    if k > _abi.PG_POOL_MAX_LABELINGS:
+        raise ValueError(f"names of length {k}: offsets takes k-mers of at most {_abi.PG_POOL_MAX_LABELINGS} bases")
+    names, res = _pool_run(dirs, lambda n: [alphabet.index(c) for c in n], [4] * k, keep_first, batch_bytes, device, max_values)
+    m = res.model
+    lines, spreads = [], []
+    for pos in range(k):
+        halves = []
+        for b in range(4):
+            g = 4 * pos + b
+            nv = int(m.n_values[g])
+            lines.append("\t".join(["base", str(pos), alphabet[b], str(int(res.n_files[g])), str(nv), m.median_text[g], m.sstdev_text[g]]))
+            if nv:
+                halves.append(int(m.mid_lo[g]) + int(m.mid_hi[g]))
+        spreads.append(max(halves) - min(halves) if len(halves) >= 2 else None)
+    for pos, sp in enumerate(spreads):
+        lines.append("\t".join(["spread", str(pos), "" if sp is None else _half_units_text(sp)]))
+    if any(sp is not None for sp in spreads):
+        lines.append("best\t%d" % max((pos for pos, sp in enumerate(spreads) if sp is not None), key=lambda p: (spreads[p], -p)))
+    return "".join(l + "\n" for l in lines), res
+
+
+def _half_units_text(s: int) -> str:
+    """"%.14Lg" of s / (2 * 10^8) in long double (s an integer of half units): its 14 significant digits, printed as %g prints them"""
+    from decimal import Decimal
+    x = np.longdouble(s) / np.longdouble(200000000)
+    if x == 0:
+        return "0"
+    mant, exp = np.format_float_scientific(x, precision=13, unique=False, exp_digits=2).split("e")
+    return "%.14g" % float(Decimal(mant).scaleb(int(exp)))
+
+
 def transform_model(raw_text, stdv, mean, stdv_min="2.5", stdv_max="4", stdv_from=None) -> str:
     """`poregen transform` (STEP 7, scripts/poregen.sh:87-148): the final model file from a raw model's KMER<TAB>median<TAB>stddev rows.
     level_mean' = (level_mean * stdv) + mean and level_stdv projected onto [stdv_min, stdv_max], digit for digit as `bc -l` prints them; the
