@@ -83,6 +83,9 @@
  *                                  device                                          scripts/poregen.sh:66-67, 43
  * pg_dmodel_finish / _format       datamash median / sstdev per file               scripts/poregen.sh:66-67, 43
  * pg_dmodel_sync / _last_error     (no counterpart)
+ * pg_dmodel_finish_events /        (no counterpart: per file the median / sstdev of its events' means and of its events' standard
+ * _format_events / _events_*,      deviations, which the pipeline's one sstdev over all samples cannot tell apart; PG_DMODEL_EVENTS)
+ * pg_model_events
  *
  * Pools of dump files -- several files read as one, `cat F1 F2 ... | tr | tail | datamash` -- have one too:
  * pg_pool_create / _destroy        (no counterpart)
@@ -752,6 +755,49 @@ pg_status pg_dmodel_sync(pg_dmodel *h);
 pg_status pg_dmodel_finish(pg_dmodel *h, pg_model_result *out, pg_dmodel_info *info);
 /* pg_model_format for the handle's last finish (which = PG_MODEL_TEXT_*), with the host-finished files' texts as datamash prints them */
 size_t    pg_dmodel_format(const pg_dmodel *h, uint32_t file, int32_t which, char *buf, size_t cap);
+
+/* ---- the event table: per file the median and sstdev of its events' LEVELS and of its events' SPREADS -----------------------------------
+ * pg_dmodel_finish reduces all samples of a file at once, which mixes the noise inside an event with the spread between events. A handle
+ * created with PG_DMODEL_EVENTS also computes, for every event (the values up to a ';'), in 1e-8 units and in exact integer arithmetic,
+ *   mean    m = floor((2 S + n) / (2 n)), S the sum of its n samples: the mean rounded to the nearest unit, halves up
+ *   spread  s = (isqrt(floor(4 N / D)) + 1) div 2, N = n sum d^2 - (sum d)^2, d = sample - first sample, D = n (n - 1): the sample
+ *           standard deviation rounded to the nearest unit, halves up
+ * on the device (a segmented reduction over the parsed values), and reduces a file's m and its s, in file order and
+ * with the first value KEPT whatever PG_MODEL_KEEP_FIRST says, exactly as pg_dmodel_finish reduces samples: `means` and `sds` are
+ * pg_model_result over the same files (dwell_n 0), their texts pg_model_format's. There is NO host path: a file's table is REFUSED --
+ * status[file] != 0, empty columns, a message; the other files are still right -- when pg_dmodel_finish finishes the file on the host,
+ * when one of its events has one sample, more than 4096 samples or a sample 2^41 units or further from its first, or when the reduction
+ * declines its means or spreads. Never a wrong number. Without the flag a handle does none of this and allocates nothing for it. */
+enum { PG_DMODEL_EVENTS = 1u << 9,        /* pg_dmodel_create: also the event table */
+       PG_DMODEL_EVENTS_KEEP = 1u << 10 }; /* ... and keep every event's m and s on the host for pg_dmodel_events_values (implies PG_DMODEL_EVENTS) */
+enum { PG_EVENTS_OK = 0, PG_EVENTS_HOST_FILE = 1, PG_EVENTS_ONE_SAMPLE = 2, PG_EVENTS_TOO_LONG = 4, PG_EVENTS_TOO_WIDE = 8, PG_EVENTS_BAD_VALUE = 16,
+       PG_EVENTS_DECLINED = 32 };          /* status bits of a refused file */
+enum { PG_EVENTS_COL_MEAN_MEDIAN = 0, PG_EVENTS_COL_MEAN_SSTDEV = 1, PG_EVENTS_COL_SD_MEDIAN = 2, PG_EVENTS_COL_SD_SSTDEV = 3 };
+/* The event table of the files of the last pg_dmodel_finish (which it calls when there was none since the last submit). status and n_events
+ * (may be NULL): [n_files], owned by the handle like the results. PG_ERR_INVALID_ARG for a handle without PG_DMODEL_EVENTS. */
+pg_status pg_dmodel_finish_events(pg_dmodel *h, pg_model_result *means, pg_model_result *sds, const uint32_t **status, const uint64_t **n_events);
+/* one field of the table as datamash would print it (column = PG_EVENTS_COL_*): "" for a file without events or a refused one */
+size_t    pg_dmodel_format_events(const pg_dmodel *h, uint32_t file, int32_t column, char *buf, size_t cap);
+/* why the file's table was refused at the last pg_dmodel_finish_events ("" for one that was not); owned by the handle */
+const char *pg_dmodel_events_refusal(const pg_dmodel *h, uint32_t file);
+/* PG_DMODEL_EVENTS_KEEP: m and s of all *n events, file after file: n_events[file] each, the parser's count, so a refused file's events
+ * lie between its neighbours' (s = 0 where there is none; a file outside the strict grammar has no events); owned by the handle */
+pg_status pg_dmodel_events_values(const pg_dmodel *h, const int64_t **mean, const int64_t **sd, uint64_t *n);
+/* PG_DMODEL_PROFILE: device time of the per-event kernels and of the two reductions behind them since the last finish (either may be NULL) */
+pg_status pg_dmodel_events_ms(const pg_dmodel *h, double *event_ms, double *reduce_ms);
+
+/* The event table of a context's kept events (see pg_model: the same events, slot by slot), computed on the device from the kept samples
+ * as the "%.8f" text stands for them. Calls pg_finish first. Arrays are owned by the context until the next pg_model_events / pg_reset /
+ * pg_destroy. Unlike pg_model a refused slot fails nothing here: the caller decides (status as above; PG_EVENTS_HOST_FILE never). */
+typedef struct {
+    pg_model_result means, sds;   /* one slot per k-mer: the reduction of its events' m and of their s */
+    const uint32_t *status;       /* [n_slots] PG_EVENTS_* bits */
+    const uint64_t *n_events;     /* [n_slots] */
+} pg_events_result;
+pg_status pg_model_events(pg_ctx *ctx, uint32_t flags, pg_events_result *out);
+/* the message that goes with a status ("" for PG_EVENTS_OK and for bits this library does not know), in a buffer of the calling thread
+ * that its next call overwrites */
+const char *pg_events_status_text(uint32_t status);
 
 /* ---- pools: median and sstdev of dump files read back to back, parsed, kept and selected on the device --------------------------------
  * A pool is a list of dump files in a fixed order; its numbers are the pipeline's for the files concatenated: `cat F1 F2 ... | tr ';,' '\n'

@@ -29,6 +29,9 @@ PG_FLAG_ONE_STREAM = 1024
 PG_MODEL_KEEP_FIRST = 1
 PG_KFREQ_N_TO_T = 1
 PG_DMODEL_PROFILE = 256
+PG_DMODEL_EVENTS, PG_DMODEL_EVENTS_KEEP = 512, 1024
+PG_EVENTS_OK, PG_EVENTS_HOST_FILE, PG_EVENTS_ONE_SAMPLE, PG_EVENTS_TOO_LONG, PG_EVENTS_TOO_WIDE, PG_EVENTS_BAD_VALUE, PG_EVENTS_DECLINED = 0, 1, 2, 4, 8, 16, 32
+PG_EVENTS_COL_MEAN_MEDIAN, PG_EVENTS_COL_MEAN_SSTDEV, PG_EVENTS_COL_SD_MEDIAN, PG_EVENTS_COL_SD_SSTDEV = 0, 1, 2, 3
 PG_MVOPS_RNA, PG_MVOPS_N_TO_T = 1, 2
 PG_MVOPS_ST_ACCEPTED, PG_MVOPS_ST_NO_MOVE_IN_TABLE, PG_MVOPS_ST_NEGATIVE_TAIL, PG_MVOPS_ST_BASES_LEFT_OVER, PG_MVOPS_ST_BAD_STRIDE = 0, 1, 2, 3, 4
 PG_MODEL_TEXT_MEDIAN, PG_MODEL_TEXT_SSTDEV, PG_MODEL_TEXT_DWELL = 0, 1, 2
@@ -50,6 +53,7 @@ EXPORTS = [
     "pg_pamean_submit_svb", "pg_pamean_svb_samples",
     "pg_sigdec_create", "pg_sigdec_destroy", "pg_sigdec_last_error", "pg_sigdec_counts", "pg_sigdec_decode",
     "pg_dmodel_create", "pg_dmodel_destroy", "pg_dmodel_last_error", "pg_dmodel_submit", "pg_dmodel_sync", "pg_dmodel_finish", "pg_dmodel_format",
+    "pg_dmodel_finish_events", "pg_dmodel_format_events", "pg_dmodel_events_refusal", "pg_dmodel_events_values", "pg_dmodel_events_ms", "pg_model_events", "pg_events_status_text",
     "pg_pool_create", "pg_pool_destroy", "pg_pool_last_error", "pg_pool_submit", "pg_pool_sync", "pg_pool_finish", "pg_pool_format", "pg_pool_refusal",
     "pg_transform_model", "pg_transform_free",
     "pg_mvops_create", "pg_mvops_destroy", "pg_mvops_last_error", "pg_mvops_piece", "pg_mvops_set_stream", "pg_mvops_stream", "pg_mvops_expand",
@@ -108,6 +112,10 @@ class PgModelResult(C.Structure):
         ("mid_lo", C.c_void_p), ("mid_hi", C.c_void_p), ("origin", C.c_void_p), ("sum1", C.c_void_p), ("sum2_lo", C.c_void_p),
         ("sum2_hi", C.c_void_p), ("dwell_n", C.c_void_p), ("dwell_median", C.c_void_p),
     ]
+
+
+class PgEventsResult(C.Structure):
+    _fields_ = [("means", PgModelResult), ("sds", PgModelResult), ("status", C.c_void_p), ("n_events", C.c_void_p)]
 
 
 class PgKfreqResult(C.Structure):
@@ -294,6 +302,14 @@ def load():
     lib.pg_dmodel_sync.argtypes = [vp]; lib.pg_dmodel_sync.restype = i32
     lib.pg_dmodel_finish.argtypes = [vp, C.POINTER(PgModelResult), C.POINTER(PgDmodelInfo)]; lib.pg_dmodel_finish.restype = i32
     lib.pg_dmodel_format.argtypes = [vp, u32, i32, C.c_char_p, C.c_size_t]; lib.pg_dmodel_format.restype = C.c_size_t
+    if hasattr(lib, "pg_dmodel_finish_events"):  # (bench.py --lib may load a library built from an older tree, without the event table)
+        lib.pg_dmodel_finish_events.argtypes = [vp, C.POINTER(PgModelResult), C.POINTER(PgModelResult), C.POINTER(vp), C.POINTER(vp)]; lib.pg_dmodel_finish_events.restype = i32
+        lib.pg_dmodel_format_events.argtypes = [vp, u32, i32, C.c_char_p, C.c_size_t]; lib.pg_dmodel_format_events.restype = C.c_size_t
+        lib.pg_dmodel_events_refusal.argtypes = [vp, u32]; lib.pg_dmodel_events_refusal.restype = C.c_char_p
+        lib.pg_dmodel_events_values.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64)]; lib.pg_dmodel_events_values.restype = i32
+        lib.pg_dmodel_events_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]; lib.pg_dmodel_events_ms.restype = i32
+        lib.pg_model_events.argtypes = [vp, u32, C.POINTER(PgEventsResult)]; lib.pg_model_events.restype = i32
+        lib.pg_events_status_text.argtypes = [u32]; lib.pg_events_status_text.restype = C.c_char_p
     if hasattr(lib, "pg_pool_create"):  # (as above: an earlier round's measurement build lacks the newer entry points)
         lib.pg_pool_create.argtypes = [i32, u32, vp, C.c_uint64, u32, C.POINTER(vp)]; lib.pg_pool_create.restype = i32
         lib.pg_pool_destroy.argtypes = [vp]; lib.pg_pool_destroy.restype = None

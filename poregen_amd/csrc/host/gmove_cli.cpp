@@ -46,7 +46,7 @@ struct option long_options[] = {
     {"batch_reads", required_argument, 0, 0}, {"device", required_argument, 0, 0}, {"lazy_stats", no_argument, 0, 0},
     {"raw_model", required_argument, 0, 0}, {"stdv_limit", required_argument, 0, 0}, {"dwell_model", required_argument, 0, 0},
     {"devices", required_argument, 0, 0}, {"exchange", required_argument, 0, 0},
-    {"reform", no_argument, 0, 0}, {"n_to_t", no_argument, 0, 0},
+    {"reform", no_argument, 0, 0}, {"n_to_t", no_argument, 0, 0}, {"event_model", required_argument, 0, 0},
     {0, 0, 0, 0}};
 
 void print_help(FILE *fp, const Opt &o) { // src/gmove.cpp:80-104
@@ -85,6 +85,8 @@ void print_help(FILE *fp, const Opt &o) { // src/gmove.cpp:80-104
     fprintf(fp, "                              (what scripts/poregen.sh calculate_mean_stddev_all derives from the dump files)\n");
     fprintf(fp, "   --stdv_limit NUM           cap of the stddev column of --raw_model [3.1]\n");
     fprintf(fp, "   --dwell_model FILE         also write KMER<TAB>median dwell (scripts/poregen.sh calculate_dwell_times_medians)\n");
+    fprintf(fp, "   --event_model FILE         also write KMER<TAB>n_events<TAB>mean_median<TAB>mean_sstdev<TAB>sd_median<TAB>sd_sstdev: per k-mer the median and sstdev\n");
+    fprintf(fp, "                              of its kept events' means and of their standard deviations, as `poregen model --event_model` (one device only)\n");
     fprintf(fp, "   --reform                   .bam / .sam only: read the move tables as `poregen reform -c -k 1 --stride 0` would (with --rna: reform --rna)\n");
     fprintf(fp, "                              and collect by the rules of a .paf -- the tables are expanded on the GPU, no PAF and no --fastq needed\n");
     fprintf(fp, "   --n_to_t                   with --reform: an N of a read counts as T (sed '2~4s/N/T/g' on the FASTQ)\n");
@@ -153,7 +155,7 @@ int gmove_main(int argc, char **argv) {
     FILE *fp_help = stderr;
     uint32_t batch_reads = 20000; bool batch_reads_set = false; int device = 0; bool lazy = false;
     std::vector<int32_t> devices; uint32_t exchange = PG_JOB_EXCHANGE_AUTO;
-    const char *raw_model_path = nullptr, *dwell_model_path = nullptr, *stdv_limit = "3.1";
+    const char *raw_model_path = nullptr, *dwell_model_path = nullptr, *stdv_limit = "3.1", *event_model_path = nullptr;
     bool reform_mode = false, n_to_t = false;
     optind = 1;
     while ((c = getopt_long(argc, argv, "k:m:s:d", long_options, &longindex)) >= 0) { // src/gmove.cpp:240-327
@@ -198,6 +200,7 @@ int gmove_main(int argc, char **argv) {
         }
         else if (c == 0 && longindex == 30) reform_mode = true;
         else if (c == 0 && longindex == 31) n_to_t = true;
+        else if (c == 0 && longindex == 32) event_model_path = optarg;
     }
     if (argc - optind != 3 || fp_help == stdout) { // src/gmove.cpp:330-336
         print_help(fp_help, opt);
@@ -210,6 +213,8 @@ int gmove_main(int argc, char **argv) {
         if (reform_mode && !sam_or_bam) { fprintf(stderr, "--reform applies to a .bam or .sam event_alignment_file only\n"); print_help(fp_help, opt); return EXIT_FAILURE; }
         if (n_to_t && !reform_mode) { fprintf(stderr, "--n_to_t applies with --reform only\n"); print_help(fp_help, opt); return EXIT_FAILURE; }
     }
+    if (event_model_path && devices.size() > 1) return die("--event_model works on one device: it cannot be combined with --devices of more than one device");
+    if (event_model_path && devices.size() == 1) { device = devices[0]; devices.clear(); } // (one listed device: the single-device path)
     // --devices cuts every batch into one contiguous shard per device: the default batch grows with the device count, so that a shard
     // stays at the 20 000 reads (160 MB of signal) the one-device pipeline is tuned for instead of shrinking to a latency-bound sliver
     const size_t n_shards = devices.empty() ? 1 : devices.size();
@@ -231,6 +236,8 @@ int gmove_main(int argc, char **argv) {
     std::future<pg_status> rt_ready = std::async(std::launch::async, [first_device]() { return pg_runtime_init(first_device); });
     if (opt.kmer_size <= opt.sig_move_offset) fprintf(stderr, "[gmove::WARNING] signal move offset value should be less than the kmer length\n");
 
+    if (event_model_path && opt.delimit_files) return die("--event_model cannot be combined with -d");
+    if (event_model_path && !pgh::can_write_file(event_model_path)) { fprintf(stderr, "Could not open %s for writing.\n", event_model_path); return EXIT_FAILURE; } // (before the run, not behind it)
     if (raw_model_path && opt.delimit_files) return die("--raw_model cannot be combined with -d: the ':' delimiters are not numbers (datamash stops on them)");
     { char *end = nullptr; (void)strtold(stdv_limit, &end); if (end == stdv_limit || *end) return die("--stdv_limit must be a number. You entered %s", stdv_limit); }
 
@@ -860,6 +867,30 @@ int gmove_main(int argc, char **argv) {
                     }
                 }
                 fprintf(stderr, "\n[gmove] time: k-mer model on the device %.3f s", secs(tm0, clk::now()));
+            }
+            if (status == EXIT_SUCCESS && event_model_path) { // the table `poregen model --event_model` derives from the dump files, from the kept samples
+                pg_events_result er;
+                if (pg_model_events(dev.ctx, 0, &er) != PG_OK) { fprintf(stderr, "[gmove] %s\n", dev.error()); status = EXIT_FAILURE; }
+                else {
+                    std::vector<uint32_t> order(res.n_slots);
+                    for (uint32_t i = 0; i < res.n_slots; i++) order[i] = i;
+                    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return slot_kmers[a] < slot_kmers[b]; });
+                    for (uint32_t i : order)
+                        if (status == EXIT_SUCCESS && er.status[i]) {
+                            fprintf(stderr, "[gmove] the event table of %s is refused: %s\n", slot_kmers[i].c_str(), pg_events_status_text(er.status[i]));
+                            status = EXIT_FAILURE;
+                        }
+                    FILE *fp = status == EXIT_SUCCESS ? fopen(event_model_path, "w") : nullptr;
+                    if (status == EXIT_SUCCESS && !fp) { fprintf(stderr, "Could not open %s for writing.\n", event_model_path); status = EXIT_FAILURE; }
+                    if (fp) {
+                        char c4[4][64];
+                        for (uint32_t i : order) {
+                            for (int col = 0; col < 4; col++) pg_model_format(col < 2 ? &er.means : &er.sds, i, (col & 1) ? PG_MODEL_TEXT_SSTDEV : PG_MODEL_TEXT_MEDIAN, c4[col], sizeof c4[col]);
+                            fprintf(fp, "%s\t%llu\t%s\t%s\t%s\t%s\n", slot_kmers[i].c_str(), (unsigned long long)er.n_events[i], c4[0], c4[1], c4[2], c4[3]);
+                        }
+                        fclose(fp);
+                    }
+                }
             }
             fprintf(stderr, "\n[gmove] time: file indices %.3f s next to device context %.3f s (own thread), waited %.3f s for it at the first batch\n", secs(t_setup0, t_setup1), t_ctx, t_ctx_wait);
             if (is_paf) fprintf(stderr, "[gmove] time: PAF lines %.3f s, parse + decode on the pool %.3f s, one batch from the runs %.3f s\n", t_lines, t_decode, t_concat);

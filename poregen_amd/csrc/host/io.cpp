@@ -80,6 +80,15 @@ bool zstd_record(const unsigned char *src, size_t n, std::vector<unsigned char> 
 
 namespace pgh {
 
+bool can_write_file(const char *path) {
+    struct stat st;
+    if (stat(path, &st) == 0) return !S_ISDIR(st.st_mode) && access(path, W_OK) == 0;
+    const std::string p(path);
+    const size_t slash = p.rfind('/');
+    const std::string dir = slash == std::string::npos ? "." : slash == 0 ? "/" : p.substr(0, slash);
+    return stat(dir.c_str(), &st) == 0 && S_ISDIR(st.st_mode) && access(dir.c_str(), W_OK) == 0;
+}
+
 bool MappedFile::open(const std::string &path) {
     close();
     fd = ::open(path.c_str(), O_RDONLY);

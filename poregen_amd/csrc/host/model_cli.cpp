@@ -7,9 +7,13 @@
 //   * --dwell_model FILE: NAME<TAB>median dwell, appended                                 scripts/poregen.sh:43-45
 //   * --pool START:LEN: one line per sub-k-mer name[START:START+LEN], SUB<TAB>median<TAB>stddev of that group's files read back to back
 //     (pg_pool_*): `cat` of the files | tr | tail | datamash                              scripts/poregen.sh:73-74
+//   * --event_model FILE: NAME<TAB>events<TAB>median and sstdev of the events' means<TAB>median and sstdev of the events' standard
+//     deviations (pg_dmodel_finish_events; no counterpart in the script, which cannot tell the two apart). A file whose table the library
+//     refuses ends the command with status 1 before anything is written
 #include "../../../include/pgmove.h"
 #include "../pg_dumphost.h"
 #include "pg_dumpdir.h"
+#include "pg_host.h"
 #include "pg_poolnames.h"
 
 #include <chrono>
@@ -32,6 +36,7 @@ const struct option kLongOptions[] = {
     {"threads", required_argument, nullptr, 't'},   // 4
     {"help", no_argument, nullptr, 'h'},            // 5
     {"pool", required_argument, nullptr, 0},        // 6
+    {"event_model", required_argument, nullptr, 0}, // 7
     {nullptr, 0, nullptr, 0}};
 
 void print_help(FILE *fp) {
@@ -41,6 +46,8 @@ void print_help(FILE *fp) {
     fprintf(fp, "   --stdv_limit NUM           cap of the stddev column [3.1]\n");
     fprintf(fp, "   -o FILE                    output to file [stdout]\n");
     fprintf(fp, "   --dwell_model FILE         also append KMER<TAB>median dwell to FILE (scripts/poregen.sh calculate_dwell_times_medians)\n");
+    fprintf(fp, "   --event_model FILE         also write KMER<TAB>n_events<TAB>mean_median<TAB>mean_sstdev<TAB>sd_median<TAB>sd_sstdev: per file the median and\n");
+    fprintf(fp, "                              sstdev of its events' means and of its events' standard deviations (an event: the values up to a ';')\n");
     fprintf(fp, "   --keep_first               keep the first value of every file (the pipeline's `tail -n +2` drops it)\n");
     fprintf(fp, "   --pool START:LEN           pool the files by the LEN bases of their names from 0-based START: SUB<TAB>median<TAB>stddev of each group's files read as one\n");
     fprintf(fp, "   -t INT                     threads that read files [8], at most 16\n");
@@ -104,7 +111,7 @@ int pool_main(const std::vector<std::string> &dirs, const char *spec, const char
 
 int model_main(int argc, char **argv) {
     using clk = std::chrono::steady_clock;
-    const char *stdv_limit = "3.1", *out_path = nullptr, *dwell_path = nullptr, *pool = nullptr;
+    const char *stdv_limit = "3.1", *out_path = nullptr, *dwell_path = nullptr, *pool = nullptr, *event_path = nullptr;
     bool keep_first = false, help = false;
     int n_threads = 8;
     int c, longindex = 0;
@@ -117,6 +124,7 @@ int model_main(int argc, char **argv) {
         else if (c == 0 && longindex == 1) dwell_path = optarg;
         else if (c == 0 && longindex == 2) keep_first = true;
         else if (c == 0 && longindex == 6) pool = optarg;
+        else if (c == 0 && longindex == 7) event_path = optarg;
         else { print_help(stderr); return EXIT_FAILURE; }
     }
     if (help) { print_help(stdout); return EXIT_SUCCESS; }
@@ -126,6 +134,8 @@ int model_main(int argc, char **argv) {
     if (n_threads > 16) n_threads = 16;
     std::vector<std::string> dirs(argv + optind, argv + argc);
     if (pool && dwell_path) return die("--dwell_model cannot be combined with --pool%s");
+    if (pool && event_path) return die("--event_model cannot be combined with --pool%s");
+    if (event_path && !pgh::can_write_file(event_path)) return die("Could not open %s for writing.", event_path);
     if (pool) return pool_main(dirs, pool, stdv_limit, out_path, keep_first, n_threads);
 
     const clk::time_point t_start = clk::now();
@@ -157,7 +167,7 @@ int model_main(int argc, char **argv) {
     if (!batches.empty()) next = std::async(std::launch::async, read_batch, (size_t)0);
     const clk::time_point t_dev0 = clk::now();
     pg_dmodel *h = nullptr;
-    if (pg_dmodel_create(0, keep_first ? PG_MODEL_KEEP_FIRST : 0u, &h) != PG_OK) { if (next.valid()) next.wait(); return die("[model] %s", pg_dmodel_last_error(nullptr)); }
+    if (pg_dmodel_create(0, (keep_first ? PG_MODEL_KEEP_FIRST : 0u) | (event_path ? (uint32_t)PG_DMODEL_EVENTS : 0u), &h) != PG_OK) { if (next.valid()) next.wait(); return die("[model] %s", pg_dmodel_last_error(nullptr)); }
     const double t_create = secs(t_dev0, clk::now());
     double t_read = 0, t_wait = 0, t_submit = 0;
     for (size_t k = 0; k < batches.size(); k++) {
@@ -176,6 +186,17 @@ int model_main(int argc, char **argv) {
     const double t_finish = secs(f0, clk::now());
     if (info.n_files != ds.names.size()) { pg_dmodel_destroy(h); return die("[model] internal: %s files came back", std::to_string(info.n_files)); }
 
+    // the event table has no host path: one refused file ends the command before anything is written
+    pg_model_result em, es; const uint32_t *ev_status = nullptr; const uint64_t *ev_n = nullptr;
+    if (event_path) {
+        if (pg_dmodel_finish_events(h, &em, &es, &ev_status, &ev_n) != PG_OK) { const int rc = die("[model] %s", pg_dmodel_last_error(h)); pg_dmodel_destroy(h); return rc; }
+        for (uint32_t i = 0; i < mr.n_slots; i++)
+            if (ev_status[i]) {
+                fprintf(stderr, "[model] the event table of %s is refused: %s\n", ds.names[i].c_str(), pg_dmodel_events_refusal(h, i));
+                pg_dmodel_destroy(h);
+                return EXIT_FAILURE;
+            }
+    }
     const clk::time_point p0 = clk::now();
     int status = EXIT_SUCCESS;
     FILE *fp = stdout;
@@ -192,6 +213,18 @@ int model_main(int argc, char **argv) {
         else {
             for (uint32_t i = 0; i < mr.n_slots; i++) { pg_dmodel_format(h, i, PG_MODEL_TEXT_DWELL, a, sizeof a); fprintf(fd, "%s\t%s\n", ds.names[i].c_str(), a); }
             fclose(fd);
+        }
+    }
+    if (event_path) {
+        FILE *fe = fopen(event_path, "w");
+        if (!fe) { fprintf(stderr, "Could not open %s for writing.\n", event_path); status = EXIT_FAILURE; }
+        else {
+            char c4[4][64];
+            for (uint32_t i = 0; i < mr.n_slots; i++) {
+                for (int32_t col = 0; col < 4; col++) pg_dmodel_format_events(h, i, col, c4[col], sizeof c4[col]);
+                fprintf(fe, "%s\t%llu\t%s\t%s\t%s\t%s\n", ds.names[i].c_str(), (unsigned long long)ev_n[i], c4[0], c4[1], c4[2], c4[3]);
+            }
+            fclose(fe);
         }
     }
     const double t_print = secs(p0, clk::now());

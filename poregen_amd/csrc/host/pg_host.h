@@ -10,6 +10,10 @@
 
 namespace pgh {
 
+// May `path` be written? For an output that is written at the end of a run and is asked about at its start, without creating it: an
+// existing file must be writable, a new one needs a writable directory.
+bool can_write_file(const char *path);
+
 // ---- memory-mapped read-only file ---------------------------------------------------------------------
 struct MappedFile {
     const char *data = nullptr;

@@ -7,6 +7,8 @@
 #include "pg_hip_host.h"
 #include "pg_select.h"
 #include "pg_model.h"
+#include "pg_evstat.h"
+#include "pg_modelcols.h"
 
 #include <algorithm>
 #include <thread>
@@ -127,9 +129,12 @@ struct pg_ctx {
     // pg_model
     std::vector<PgSlotModel> mo_raw;
     std::vector<PgSlotDwell> mo_dw;
-    std::vector<uint64_t> mo_n, mo_s2lo, mo_s2hi, mo_dn;
-    std::vector<int64_t> mo_lo, mo_hi, mo_origin, mo_s1;
-    std::vector<double> mo_med, mo_sd, mo_dmed;
+    PgModelCols mo;
+    // pg_model_events
+    PgDev<> me_mean, me_sd, me_flags, me_carry, me_id_off, me_len1, me_out, me_dw;
+    std::vector<PgSlotModel> me_raw; std::vector<PgSlotDwell> me_rdw; std::vector<uint32_t> me_rflags;
+    PgModelCols me_cm, me_cs;
+    std::vector<uint32_t> me_status; std::vector<uint64_t> me_n;
 
     std::vector<ProfEntry> prof;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_pool;
@@ -1468,35 +1473,25 @@ static pg_status model_run(pg_ctx *c, uint32_t ns, const int any_kind[PG_MODEL_K
         PG_HIP_TRY(c, hipMemcpyAsync(c->mo_dw.data(), c->md_dwell.p, ns * sizeof(PgSlotDwell), hipMemcpyDeviceToHost, c->st));
     }
     PG_HIP_TRY(c, hipStreamSynchronize(c->st));
-    c->mo_n.resize(ns); c->mo_s2lo.resize(ns); c->mo_s2hi.resize(ns); c->mo_dn.resize(ns); c->mo_lo.resize(ns); c->mo_hi.resize(ns);
-    c->mo_origin.resize(ns); c->mo_s1.resize(ns); c->mo_med.resize(ns); c->mo_sd.resize(ns); c->mo_dmed.resize(ns);
+    c->mo.clear();
     for (uint32_t i = 0; i < ns; i++) {
         const PgSlotModel &m = c->mo_raw[i]; const PgSlotDwell &d = c->mo_dw[i];
         if (d.flags & PG_MODEL_BAD_VALUE) return pg_fail(c, PG_ERR_UNSUPPORTED, "pg_model: slot %u holds a non-finite sample or one with |x| >= 4e7", i);
         if (d.flags & PG_MODEL_BAD_COUNT) return pg_fail(c, PG_ERR_UNSUPPORTED, "pg_model: slot %u holds more than 2^23 values", i);
         if (d.flags & PG_MODEL_BAD_SPREAD) return pg_fail(c, PG_ERR_UNSUPPORTED, "pg_model: slot %u holds values further than 2^40 units of 1e-8 from its first one", i);
-        const unsigned __int128 s2 = ((unsigned __int128)m.s2_hh << 40) + ((unsigned __int128)m.s2_hl << 21) + m.s2_ll;
-        c->mo_n[i] = m.n; c->mo_lo[i] = m.mid_lo; c->mo_hi[i] = m.mid_hi; c->mo_origin[i] = m.origin; c->mo_s1[i] = m.s1;
-        c->mo_s2lo[i] = (uint64_t)s2; c->mo_s2hi[i] = (uint64_t)(s2 >> 64);
-        c->mo_med[i] = m.n ? (double)pg_model_median(m) : NAN;
-        c->mo_sd[i] = m.n >= 2 ? (double)(pg_model_sstdev_units(m) / 1e8L) : NAN;
-        c->mo_dn[i] = d.n; c->mo_dmed[i] = d.n ? ((double)d.mid_lo + (double)d.mid_hi) / 2.0 : NAN;
+        c->mo.push(m, &d);
     }
-    out->n_slots = ns; out->flags = flags; out->n_values = c->mo_n.data(); out->median = c->mo_med.data(); out->sstdev = c->mo_sd.data();
-    out->mid_lo = c->mo_lo.data(); out->mid_hi = c->mo_hi.data(); out->origin = c->mo_origin.data(); out->sum1 = c->mo_s1.data();
-    out->sum2_lo = c->mo_s2lo.data(); out->sum2_hi = c->mo_s2hi.data(); out->dwell_n = c->mo_dn.data(); out->dwell_median = c->mo_dmed.data();
+    c->mo.fill(*out, flags);
     return PG_OK;
 }
 
-pg_status pg_model(pg_ctx *c, uint32_t flags, pg_model_result *out) {
-    if (!c || !out) return PG_ERR_INVALID_ARG;
-    pg_result R;
+// the kept events of everything collected so far as device arrays in pg_result layout (R: the host's view of the small arrays)
+static pg_status model_arrays(pg_ctx *c, pg_result &R, const uint64_t *&d_ev_off, const uint64_t *&d_samp_off, const uint32_t *&d_ev_len, const double *&d_samples) {
     // deferred: the small arrays come to the host, the kept samples stay where they are on the device (after pg_finish_deferred + pg_text
     // of the CLI a plain pg_finish here would download the whole k-mer-major stream and, for several batches, upload it again)
     pg_status s = pg_finish_deferred(c, &R);
     if (s != PG_OK) return s;
     const uint32_t ns = c->prm.n_slots;
-    const uint64_t *d_ev_off, *d_samp_off; const uint32_t *d_ev_len; const double *d_samples;
     if (c->batches.size() == 1 && c->have_batch_result && c->cur_n_kept == R.n_events && c->cur_n_samples == R.n_samples) {
         // one batch: its kept events are still on the device, in the same order
         { pg_status su = ensure_unpacked(c); if (su != PG_OK) return su; }
@@ -1515,6 +1510,15 @@ pg_status pg_model(pg_ctx *c, uint32_t flags, pg_model_result *out) {
         }
         d_ev_off = c->md_ev_off.as<uint64_t>(); d_samp_off = c->md_samp_off.as<uint64_t>(); d_ev_len = c->md_ev_len.as<uint32_t>();
     }
+    return PG_OK;
+}
+
+pg_status pg_model(pg_ctx *c, uint32_t flags, pg_model_result *out) {
+    if (!c || !out) return PG_ERR_INVALID_ARG;
+    pg_result R;
+    const uint64_t *d_ev_off, *d_samp_off; const uint32_t *d_ev_len; const double *d_samples;
+    if (pg_status s = model_arrays(c, R, d_ev_off, d_samp_off, d_ev_len, d_samples)) return s;
+    const uint32_t ns = c->prm.n_slots;
     int any_kind[PG_MODEL_KINDS] = {0, 0, 0, 0}; // which of the kernels have work (the host holds the offsets since pg_finish)
     const uint64_t drop = (flags & PG_MODEL_KEEP_FIRST) ? 0 : 1;
     for (uint32_t i = 0; i < ns; i++) {
@@ -1522,6 +1526,54 @@ pg_status pg_model(pg_ctx *c, uint32_t flags, pg_model_result *out) {
         any_kind[pg_model_kind(nv, R.ev_off[i + 1] - R.ev_off[i])]++; // (counts: pg_launch_slot_model)
     }
     return model_run(c, ns, any_kind, d_ev_off, d_samp_off, d_ev_len, d_samples, flags, out);
+}
+
+// The event table of the kept events (include/pgmove.h): k_ev_stats over the kept samples, then the model reduction over the events' means
+// and over their spreads, each event one value (pg_evstat.hip).
+pg_status pg_model_events(pg_ctx *c, uint32_t flags, pg_events_result *out) {
+    if (!c || !out) return PG_ERR_INVALID_ARG;
+    if (flags) return pg_fail(c, PG_ERR_INVALID_ARG, "pg_model_events: unknown flags 0x%x", flags);
+    pg_result R;
+    const uint64_t *d_ev_off, *d_samp_off; const uint32_t *d_ev_len; const double *d_samples;
+    if (pg_status s = model_arrays(c, R, d_ev_off, d_samp_off, d_ev_len, d_samples)) return s;
+    const uint32_t ns = c->prm.n_slots;
+    const uint64_t ne = R.n_events, nv = R.n_samples;
+    // what k_ev_stats rests on (pg_evstat.hip): offsets from 0, no event without a sample (a kept window is never empty: PGR_ERR_WINDOW)
+    if (ne && R.samp_off[0] != 0) return pg_fail(c, PG_ERR_UNSUPPORTED, "pg_model_events: the kept samples' offsets do not begin at 0");
+    for (uint64_t e = 0; e < ne; e++)
+        if (R.ev_len[e] == 0) return pg_fail(c, PG_ERR_UNSUPPORTED, "pg_model_events: kept event %llu holds no sample", (unsigned long long)e);
+    PG_HIP_TRY(c, grow(c->me_mean, (ne + 1) * 8)); PG_HIP_TRY(c, grow(c->me_sd, (ne + 1) * 8)); PG_HIP_TRY(c, grow(c->me_flags, (ns + 1) * 4ull));
+    PG_HIP_TRY(c, grow(c->me_carry, pg_ev_carry_bytes(nv))); PG_HIP_TRY(c, grow(c->me_id_off, (ne + 1) * 8)); PG_HIP_TRY(c, grow(c->me_len1, (ne + 1) * 4));
+    PG_HIP_TRY(c, grow(c->me_out, 2 * (ns + 1ull) * sizeof(PgSlotModel))); PG_HIP_TRY(c, grow(c->me_dw, 2 * (ns + 1ull) * sizeof(PgSlotDwell)));
+    PG_HIP_TRY(c, grow(c->md_class, pg_slot_model_scratch_bytes(ns)));
+    int64_t *ev_mean = c->me_mean.as<int64_t>(), *ev_sd = c->me_sd.as<int64_t>();
+    PgSlotModel *om = c->me_out.as<PgSlotModel>(); PgSlotDwell *od = c->me_dw.as<PgSlotDwell>();
+    PG_HIP_TRY(c, hipMemsetAsync(c->me_flags.p, 0, (ns + 1) * 4ull, c->st));
+    PG_HIP_TRY(c, pg_launch_ev_identity(c->st, ne, c->me_id_off.as<uint64_t>(), c->me_len1.as<uint32_t>()));
+    prof_begin(c, "k_ev_stats", c->st, true);
+    PG_HIP_TRY(c, pg_launch_ev_stats(c->st, ns, d_ev_off, d_samp_off, d_samples, ne, nv, ev_mean, ev_sd, c->me_flags.as<uint32_t>(), c->me_carry.p));
+    prof_end(c, c->st);
+    const int all_kinds[PG_MODEL_KINDS] = {1 << 20, 1 << 20, 1 << 20, 1 << 20};
+    PG_HIP_TRY(c, pg_launch_slot_model_units(c->st, ns, all_kinds, d_ev_off, c->me_id_off.as<uint64_t>(), c->me_len1.as<uint32_t>(), ev_mean, 0u, om, od, c->md_class.p));
+    PG_HIP_TRY(c, pg_launch_slot_model_units(c->st, ns, all_kinds, d_ev_off, c->me_id_off.as<uint64_t>(), c->me_len1.as<uint32_t>(), ev_sd, 0u, om + ns, od + ns, c->md_class.p));
+    c->me_raw.resize(2 * (size_t)ns); c->me_rdw.resize(2 * (size_t)ns); c->me_rflags.resize(ns);
+    if (ns) {
+        PG_HIP_TRY(c, hipMemcpyAsync(c->me_raw.data(), om, 2 * (size_t)ns * sizeof(PgSlotModel), hipMemcpyDeviceToHost, c->st));
+        PG_HIP_TRY(c, hipMemcpyAsync(c->me_rdw.data(), od, 2 * (size_t)ns * sizeof(PgSlotDwell), hipMemcpyDeviceToHost, c->st));
+        PG_HIP_TRY(c, hipMemcpyAsync(c->me_rflags.data(), c->me_flags.p, (size_t)ns * 4, hipMemcpyDeviceToHost, c->st));
+    }
+    PG_HIP_TRY(c, hipStreamSynchronize(c->st));
+    c->me_cm.clear(); c->me_cs.clear(); c->me_status.clear(); c->me_n.clear();
+    for (uint32_t i = 0; i < ns; i++) {
+        const uint32_t declined = (c->me_rdw[i].flags | c->me_rdw[ns + i].flags) & (PG_MODEL_BAD_VALUE | PG_MODEL_BAD_SPREAD | PG_MODEL_BAD_COUNT);
+        uint32_t st = (c->me_rflags[i] & 15u) << 1;
+        if (!st && declined) st = PG_EVENTS_DECLINED;
+        c->me_status.push_back(st); c->me_n.push_back(R.ev_off[i + 1] - R.ev_off[i]);
+        c->me_cm.push(st ? PgSlotModel{} : c->me_raw[i]); c->me_cs.push(st ? PgSlotModel{} : c->me_raw[ns + i]);
+    }
+    c->me_cm.fill(out->means, PG_MODEL_KEEP_FIRST); c->me_cs.fill(out->sds, PG_MODEL_KEEP_FIRST);
+    out->status = c->me_status.data(); out->n_events = c->me_n.data();
+    return PG_OK;
 }
 
 pg_status pg_model_device(pg_ctx *c, uint32_t n_slots, const uint64_t *d_ev_off, const uint64_t *d_samp_off, const uint32_t *d_ev_len,

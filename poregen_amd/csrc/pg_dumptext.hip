@@ -18,6 +18,8 @@
 // then pg_launch_slot_model_units: the tiny / mid / short / long kernels of pg_model.hip over (ev_off, samp_off, ev_len, units).
 // Files the device declines are finished on the host (pg_dumphost.h) when their batch is settled; see include/pgmove.h.
 // The rule for one field and the bytes per lane / tile / workgroup are pg_dumptext.h, which the host test build compiles as well.
+// PG_DMODEL_EVENTS adds the event table per batch: k_ev_stats / k_ev_carry (pg_evstat.hip) over (units, samp_off) leave every event's mean
+// and spread, and the same reduction runs twice more over layouts in which every event is one value.
 #include "../../include/pgmove.h"
 #include <hip/hip_runtime.h>
 #include "pg_hip_host.h"
@@ -25,6 +27,8 @@
 #include "pg_model.h"
 #include "pg_dumphost.h"
 #include "pg_dumptext.h"
+#include "pg_evstat.h"
+#include "pg_modelcols.h"
 
 #include <algorithm>
 #include <cstring>
@@ -244,7 +248,8 @@ struct Slot { // what one batch leaves for its settling
     PgPinned<uint8_t> stage;            // PG_LOC_HOST: the batch's bytes (the upload's source, the host path's input)
     PgPinned<uint64_t> off_stage;
     PgPinned<> dl_model, dl_dwell, dl_flags, dl_totals;
-    PgEvent t0, t1, t2, done;
+    PgPinned<> dl_emean, dl_esd, dl_edw_m, dl_edw_s, dl_eflags, dl_evoff, dl_vmean, dl_vsd; // PG_DMODEL_EVENTS (the last two: PG_DMODEL_EVENTS_KEEP)
+    PgEvent t0, t1, t2, t2e, t3, t4, done;
 };
 
 } // namespace
@@ -258,28 +263,38 @@ struct pg_dmodel {
     // device buffers of the batch in flight (one stream: a batch's kernels run behind the previous batch's downloads)
     PgDev<uint8_t> d_bytes;
     PgDev<> d_file_off, d_tile, d_fflags, d_fstart, d_val_base, d_ev_off, d_units, d_samp_off, d_ev_len, d_out, d_dwell, d_scratch;
+    // PG_DMODEL_EVENTS: every event's mean and spread, the files' refusal flags, the tiles' carries, the one-value-per-event layouts
+    // (filled when they grow: id_n entries hold), the two reductions' results
+    PgDev<> d_ev_mean, d_ev_sd, d_evflags, d_carry, d_id_off, d_len1, d_eout_m, d_eout_s, d_edw_m, d_edw_s;
+    uint64_t id_n = 0;
     // results since the last finish
     bool finished = false;
-    std::vector<uint64_t> r_n, r_s2lo, r_s2hi, r_dn;
-    std::vector<int64_t> r_lo, r_hi, r_origin, r_s1;
-    std::vector<double> r_med, r_sd, r_dmed;
+    PgModelCols r;
     std::vector<uint32_t> host_files;
     std::vector<std::string> host_med, host_sd;
     std::vector<uint8_t> file_buf;
     pg_model_result result{};
     pg_dmodel_info info{};
+    // the event table since the last finish (PG_DMODEL_EVENTS)
+    PgModelCols e_mean, e_sd;
+    std::vector<uint32_t> e_status;
+    std::vector<uint64_t> e_n;
+    std::vector<int64_t> e_vmean, e_vsd; // PG_DMODEL_EVENTS_KEEP: every event's numbers, file after file
+    std::vector<std::string> e_msg;
+    pg_model_result e_rm{}, e_rs{};
+    double event_ms = 0, event_reduce_ms = 0;
     std::string err;
 };
 
 namespace {
 
 void dm_clear(pg_dmodel *h) {
-    for (auto *v : {&h->r_n, &h->r_s2lo, &h->r_s2hi, &h->r_dn}) v->clear();
-    for (auto *v : {&h->r_lo, &h->r_hi, &h->r_origin, &h->r_s1}) v->clear();
-    for (auto *v : {&h->r_med, &h->r_sd, &h->r_dmed}) v->clear();
+    h->r.clear();
     h->host_files.clear(); h->host_med.clear(); h->host_sd.clear();
     h->info = pg_dmodel_info{};
     h->result = pg_model_result{};
+    h->e_mean.clear(); h->e_sd.clear(); h->e_status.clear(); h->e_n.clear(); h->e_vmean.clear(); h->e_vsd.clear(); h->e_msg.clear();
+    h->e_rm = pg_model_result{}; h->e_rs = pg_model_result{}; h->event_ms = 0; h->event_reduce_ms = 0;
     h->finished = false;
 }
 
@@ -288,11 +303,10 @@ void dm_host_file(pg_dmodel *h, const char *bytes, size_t len) {
     PgDumpHostStats hs; PgDumpHostDwell hd;
     pg_dump_host_stats(bytes, len, (h->flags & PG_MODEL_KEEP_FIRST) != 0, hs);
     pg_dump_host_dwell(bytes, len, hd);
-    h->host_files.push_back((uint32_t)h->r_n.size());
+    h->host_files.push_back((uint32_t)h->r.size());
     h->host_med.push_back(hs.median); h->host_sd.push_back(hs.sstdev);
-    h->r_n.push_back(hs.n); h->r_s2lo.push_back(0); h->r_s2hi.push_back(0); h->r_lo.push_back(0); h->r_hi.push_back(0); h->r_origin.push_back(0); h->r_s1.push_back(0);
-    h->r_med.push_back(hs.median.empty() ? NAN : (double)hs.median_ld); h->r_sd.push_back(hs.sstdev.empty() ? NAN : (double)hs.sstdev_ld);
-    h->r_dn.push_back(hd.n); h->r_dmed.push_back(hd.n ? ((double)hd.mid_lo + (double)hd.mid_hi) / 2.0 : NAN);
+    h->r.push_rounded(hs.n, hs.median.empty() ? NAN : (double)hs.median_ld, hs.sstdev.empty() ? NAN : (double)hs.sstdev_ld, hd.n,
+                      hd.n ? ((double)hd.mid_lo + (double)hd.mid_hi) / 2.0 : NAN);
 }
 
 // wait for the slot's batch, take its results over, finish on the host what the device declined
@@ -304,6 +318,16 @@ pg_status dm_settle(pg_dmodel *h, Slot &s) {
         float a = 0, b = 0;
         PG_HIP_TRY(h, hipEventElapsedTime(&a, s.t0, s.t1)); PG_HIP_TRY(h, hipEventElapsedTime(&b, s.t1, s.t2));
         h->info.parse_ms += a; h->info.model_ms += b;
+        if (h->flags & PG_DMODEL_EVENTS) {
+            PG_HIP_TRY(h, hipEventElapsedTime(&a, s.t2e, s.t3)); PG_HIP_TRY(h, hipEventElapsedTime(&b, s.t3, s.t4));
+            h->event_ms += a; h->event_reduce_ms += b;
+        }
+    }
+    const bool events = (h->flags & PG_DMODEL_EVENTS) != 0;
+    if (events && (h->flags & PG_DMODEL_EVENTS_KEEP)) {
+        const uint64_t ne = s.dl_totals.as<uint64_t>()[1];
+        h->e_vmean.insert(h->e_vmean.end(), s.dl_vmean.as<int64_t>(), s.dl_vmean.as<int64_t>() + ne);
+        h->e_vsd.insert(h->e_vsd.end(), s.dl_vsd.as<int64_t>(), s.dl_vsd.as<int64_t>() + ne);
     }
     const PgSlotModel *mo = s.dl_model.as<PgSlotModel>();
     const PgSlotDwell *dw = s.dl_dwell.as<PgSlotDwell>();
@@ -314,6 +338,15 @@ pg_status dm_settle(pg_dmodel *h, Slot &s) {
         const PgSlotModel &m = mo[i]; const PgSlotDwell &d = dw[i];
         const bool host = (fl[i] & DT_BAD) || (d.flags & (PG_MODEL_BAD_VALUE | PG_MODEL_BAD_SPREAD | PG_MODEL_BAD_COUNT)) ||
                           ((fl[i] & DT_NEGZERO) && m.n && m.mid_lo == 0 && m.mid_hi == 0); // datamash would print the median's sign: "-0"
+        if (events) { // no host path: a file the device does not finish, or whose events it refuses, has no event table
+            const PgSlotModel &em = s.dl_emean.as<PgSlotModel>()[i], &es = s.dl_esd.as<PgSlotModel>()[i];
+            const uint32_t declined = (s.dl_edw_m.as<PgSlotDwell>()[i].flags | s.dl_edw_s.as<PgSlotDwell>()[i].flags) & (PG_MODEL_BAD_VALUE | PG_MODEL_BAD_SPREAD | PG_MODEL_BAD_COUNT);
+            uint32_t st = host ? (uint32_t)PG_EVENTS_HOST_FILE : (s.dl_eflags.as<uint32_t>()[i] & 15u) << 1; // (a host file has no events to speak of)
+            if (!st && declined) st = PG_EVENTS_DECLINED;
+            const uint64_t *eo = s.dl_evoff.as<uint64_t>();
+            h->e_status.push_back(st); h->e_n.push_back(eo[i + 1] - eo[i]); // (the parser's count: the slices of pg_dmodel_events_values)
+            h->e_mean.push(st ? PgSlotModel{} : em); h->e_sd.push(st ? PgSlotModel{} : es);
+        }
         if (host) {
             const uint64_t lo = s.file_off[i], len = s.file_off[i + 1] - lo;
             const char *bytes = reinterpret_cast<const char *>(s.stage.p) + lo;
@@ -325,12 +358,7 @@ pg_status dm_settle(pg_dmodel *h, Slot &s) {
             dm_host_file(h, bytes, len);
             continue;
         }
-        const unsigned __int128 s2 = ((unsigned __int128)m.s2_hh << 40) + ((unsigned __int128)m.s2_hl << 21) + m.s2_ll;
-        h->r_n.push_back(m.n); h->r_lo.push_back(m.mid_lo); h->r_hi.push_back(m.mid_hi); h->r_origin.push_back(m.origin); h->r_s1.push_back(m.s1);
-        h->r_s2lo.push_back((uint64_t)s2); h->r_s2hi.push_back((uint64_t)(s2 >> 64));
-        h->r_med.push_back(m.n ? (double)pg_model_median(m) : NAN);
-        h->r_sd.push_back(m.n >= 2 ? (double)(pg_model_sstdev_units(m) / 1e8L) : NAN);
-        h->r_dn.push_back(d.n); h->r_dmed.push_back(d.n ? ((double)d.mid_lo + (double)d.mid_hi) / 2.0 : NAN);
+        h->r.push(m, &d);
     }
     return PG_OK;
 }
@@ -369,14 +397,15 @@ const char *pg_dmodel_last_error(const pg_dmodel *h) { return h ? h->err.c_str()
 pg_status pg_dmodel_create(int32_t device, uint32_t flags, pg_dmodel **out) {
     if (!out) return pg_fail<pg_dmodel>(nullptr, PG_ERR_INVALID_ARG, "pg_dmodel_create: null argument");
     *out = nullptr;
-    if (flags & ~(uint32_t)(PG_MODEL_KEEP_FIRST | PG_DMODEL_PROFILE)) return pg_fail<pg_dmodel>(nullptr, PG_ERR_INVALID_ARG, "pg_dmodel_create: unknown flags 0x%x", flags);
+    if (flags & ~(uint32_t)(PG_MODEL_KEEP_FIRST | PG_DMODEL_PROFILE | PG_DMODEL_EVENTS | PG_DMODEL_EVENTS_KEEP)) return pg_fail<pg_dmodel>(nullptr, PG_ERR_INVALID_ARG, "pg_dmodel_create: unknown flags 0x%x", flags);
     if (pg_status st = pg_select_device<pg_dmodel>(device)) return st;
     pg_dmodel *h = new pg_dmodel();
-    h->device = device; h->flags = flags;
+    h->device = device; h->flags = flags | ((flags & PG_DMODEL_EVENTS_KEEP) ? (uint32_t)PG_DMODEL_EVENTS : 0u);
     auto init = [&]() -> pg_status {
         PG_HIP_TRY(h, hipStreamCreateWithFlags(&h->st.h, hipStreamNonBlocking));
         for (Slot &s : h->slot) {
             for (PgEvent *e : {&s.t0, &s.t1, &s.t2}) PG_HIP_TRY(h, hipEventCreate(&e->h));
+            if (h->flags & PG_DMODEL_EVENTS) for (PgEvent *e : {&s.t2e, &s.t3, &s.t4}) PG_HIP_TRY(h, hipEventCreate(&e->h));
             PG_HIP_TRY(h, hipEventCreateWithFlags(&s.done.h, hipEventDisableTiming));
         }
         return PG_OK;
@@ -406,7 +435,7 @@ pg_status pg_dmodel_submit(pg_dmodel *h, const void *bytes, const uint64_t *file
     const uint64_t n = file_off[n_files];
     if (n > kMaxBatchBytes) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_dmodel_submit: more than 2^31 bytes in one call");
     if (n && !bytes) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_dmodel_submit: null bytes");
-    if (h->r_n.size() + h->slot[0].n_files * h->slot[0].pending + h->slot[1].n_files * h->slot[1].pending + (uint64_t)n_files > 0xffffffffull)
+    if (h->r.size() + h->slot[0].n_files * h->slot[0].pending + h->slot[1].n_files * h->slot[1].pending + (uint64_t)n_files > 0xffffffffull)
         return pg_fail(h, PG_ERR_INVALID_ARG, "pg_dmodel_submit: more than 2^32 files since the last finish");
     PG_HIP_TRY(h, hipSetDevice(h->device));
     if (location == PG_LOC_DEVICE && n && pg_ptr_kind(bytes, h->device) != PG_PTR_DEVICE)
@@ -421,7 +450,12 @@ pg_status pg_dmodel_submit(pg_dmodel *h, const void *bytes, const uint64_t *file
     const size_t nf1 = (size_t)n_files + 1;
     const size_t scratch = pg_slot_model_scratch_bytes(n_files);
     // the device buffers are shared by the batches: one that has to grow is freed, so the batch in flight is settled first
-    const bool grow = too_small(h->d_bytes, n + 64) || too_small(h->d_file_off, nf1 * 8) || too_small(h->d_tile, ((size_t)n_tiles + 1) * 8) ||
+    const bool events = (h->flags & PG_DMODEL_EVENTS) != 0, keep_events = (h->flags & PG_DMODEL_EVENTS_KEEP) != 0;
+    const size_t carry = pg_ev_carry_bytes(cap_values);
+    const bool grow_events = events && (too_small(h->d_ev_mean, cap_values * 8) || too_small(h->d_ev_sd, cap_values * 8) || too_small(h->d_evflags, nf1 * 4) || too_small(h->d_carry, carry) ||
+                                        too_small(h->d_id_off, (cap_values + 1) * 8) || too_small(h->d_len1, cap_values * 4) || too_small(h->d_eout_m, nf1 * sizeof(PgSlotModel)) ||
+                                        too_small(h->d_eout_s, nf1 * sizeof(PgSlotModel)) || too_small(h->d_edw_m, nf1 * sizeof(PgSlotDwell)) || too_small(h->d_edw_s, nf1 * sizeof(PgSlotDwell)));
+    const bool grow = grow_events || too_small(h->d_bytes, n + 64) || too_small(h->d_file_off, nf1 * 8) || too_small(h->d_tile, ((size_t)n_tiles + 1) * 8) ||
                       too_small(h->d_fflags, nf1 * 4) || too_small(h->d_fstart, nf1 * 8) || too_small(h->d_val_base, nf1 * 8) || too_small(h->d_ev_off, nf1 * 8) ||
                       too_small(h->d_units, cap_values * 8) || too_small(h->d_samp_off, (cap_values + 1) * 8) || too_small(h->d_ev_len, cap_values * 4) ||
                       too_small(h->d_out, nf1 * sizeof(PgSlotModel)) || too_small(h->d_dwell, nf1 * sizeof(PgSlotDwell)) || too_small(h->d_scratch, scratch);
@@ -436,6 +470,22 @@ pg_status pg_dmodel_submit(pg_dmodel *h, const void *bytes, const uint64_t *file
         PG_HIP_TRY(h, h->d_samp_off.ensure((cap_values + 1) * 8, room((cap_values + 1) * 8))); PG_HIP_TRY(h, h->d_ev_len.ensure(cap_values * 4, room(cap_values * 4)));
         PG_HIP_TRY(h, h->d_out.ensure(nf1 * sizeof(PgSlotModel), room(nf1 * sizeof(PgSlotModel)))); PG_HIP_TRY(h, h->d_dwell.ensure(nf1 * sizeof(PgSlotDwell), room(nf1 * sizeof(PgSlotDwell))));
         PG_HIP_TRY(h, h->d_scratch.ensure(scratch, room(scratch)));
+        if (events) {
+            PG_HIP_TRY(h, h->d_ev_mean.ensure(cap_values * 8, room(cap_values * 8))); PG_HIP_TRY(h, h->d_ev_sd.ensure(cap_values * 8, room(cap_values * 8)));
+            PG_HIP_TRY(h, h->d_evflags.ensure(nf1 * 4, room(nf1 * 4))); PG_HIP_TRY(h, h->d_carry.ensure(carry, room(carry)));
+            if (too_small(h->d_id_off, (cap_values + 1) * 8) || too_small(h->d_len1, cap_values * 4)) {
+                h->id_n = 0;
+                PG_HIP_TRY(h, h->d_id_off.ensure((cap_values + 1) * 8, room((cap_values + 1) * 8))); PG_HIP_TRY(h, h->d_len1.ensure(cap_values * 4, room(cap_values * 4)));
+            }
+            PG_HIP_TRY(h, h->d_eout_m.ensure(nf1 * sizeof(PgSlotModel), room(nf1 * sizeof(PgSlotModel)))); PG_HIP_TRY(h, h->d_eout_s.ensure(nf1 * sizeof(PgSlotModel), room(nf1 * sizeof(PgSlotModel))));
+            PG_HIP_TRY(h, h->d_edw_m.ensure(nf1 * sizeof(PgSlotDwell), room(nf1 * sizeof(PgSlotDwell)))); PG_HIP_TRY(h, h->d_edw_s.ensure(nf1 * sizeof(PgSlotDwell), room(nf1 * sizeof(PgSlotDwell))));
+        }
+    }
+    if (events) {
+        PG_HIP_TRY(h, s.dl_emean.ensure(nf1 * sizeof(PgSlotModel), nf1 * sizeof(PgSlotModel) * 5 / 4)); PG_HIP_TRY(h, s.dl_esd.ensure(nf1 * sizeof(PgSlotModel), nf1 * sizeof(PgSlotModel) * 5 / 4));
+        PG_HIP_TRY(h, s.dl_edw_m.ensure(nf1 * sizeof(PgSlotDwell), nf1 * sizeof(PgSlotDwell) * 5 / 4)); PG_HIP_TRY(h, s.dl_edw_s.ensure(nf1 * sizeof(PgSlotDwell), nf1 * sizeof(PgSlotDwell) * 5 / 4));
+        PG_HIP_TRY(h, s.dl_eflags.ensure(nf1 * 4, nf1 * 5)); PG_HIP_TRY(h, s.dl_evoff.ensure(nf1 * 8, nf1 * 10));
+        if (keep_events) { PG_HIP_TRY(h, s.dl_vmean.ensure(cap_values * 8, cap_values * 10)); PG_HIP_TRY(h, s.dl_vsd.ensure(cap_values * 8, cap_values * 10)); }
     }
     PG_HIP_TRY(h, s.off_stage.ensure(nf1 * 8, nf1 * 8 + nf1 * 2)); PG_HIP_TRY(h, s.dl_totals.ensure(16));
     PG_HIP_TRY(h, s.dl_model.ensure(nf1 * sizeof(PgSlotModel), nf1 * sizeof(PgSlotModel) * 5 / 4)); PG_HIP_TRY(h, s.dl_dwell.ensure(nf1 * sizeof(PgSlotDwell), nf1 * sizeof(PgSlotDwell) * 5 / 4));
@@ -471,6 +521,33 @@ pg_status pg_dmodel_submit(pg_dmodel *h, const void *bytes, const uint64_t *file
     PG_HIP_TRY(h, hipMemcpyAsync(s.dl_dwell.p, h->d_dwell.p, (size_t)n_files * sizeof(PgSlotDwell), hipMemcpyDeviceToHost, h->st));
     PG_HIP_TRY(h, hipMemcpyAsync(s.dl_flags.p, h->d_fflags.p, (size_t)n_files * 4, hipMemcpyDeviceToHost, h->st));
     PG_HIP_TRY(h, hipMemcpyAsync(s.dl_totals.p, b.val_base + n_files, 8, hipMemcpyDeviceToHost, h->st));
+    if (events) {
+        PG_HIP_TRY(h, hipMemcpyAsync(s.dl_totals.as<uint64_t>() + 1, b.ev_off + n_files, 8, hipMemcpyDeviceToHost, h->st));
+        PG_HIP_TRY(h, hipMemcpyAsync(s.dl_evoff.p, b.ev_off, nf1 * 8, hipMemcpyDeviceToHost, h->st));
+        // the sample reduction's timing ends at t2; from here to t3 the new kernels, to t4 the two reductions over one value per event
+        int64_t *ev_mean = h->d_ev_mean.as<int64_t>(), *ev_sd = h->d_ev_sd.as<int64_t>();
+        uint64_t *id_off = h->d_id_off.as<uint64_t>(); uint32_t *len1 = h->d_len1.as<uint32_t>();
+        if (h->id_n < cap_values) {
+            h->id_n = std::min<uint64_t>(h->d_id_off.cap / 8 - 1, h->d_len1.cap / 4);
+            PG_HIP_TRY(h, pg_launch_ev_identity(h->st, h->id_n, id_off, len1));
+        }
+        PG_HIP_TRY(h, hipMemsetAsync(h->d_evflags.p, 0, nf1 * 4, h->st));
+        PG_HIP_TRY(h, hipEventRecord(s.t2e, h->st)); // (the downloads, the identity layouts and the flags are not the new kernels' time)
+        PG_HIP_TRY(h, pg_launch_ev_stats_units(h->st, n_files, b.ev_off, b.samp_off, b.units, cap_values, cap_values, ev_mean, ev_sd, h->d_evflags.as<uint32_t>(), h->d_carry.p));
+        PG_HIP_TRY(h, hipEventRecord(s.t3, h->st));
+        PG_HIP_TRY(h, pg_launch_slot_model_units(h->st, n_files, all_kinds, b.ev_off, id_off, len1, ev_mean, 0u, h->d_eout_m.as<PgSlotModel>(), h->d_edw_m.as<PgSlotDwell>(), h->d_scratch.p));
+        PG_HIP_TRY(h, pg_launch_slot_model_units(h->st, n_files, all_kinds, b.ev_off, id_off, len1, ev_sd, 0u, h->d_eout_s.as<PgSlotModel>(), h->d_edw_s.as<PgSlotDwell>(), h->d_scratch.p));
+        PG_HIP_TRY(h, hipEventRecord(s.t4, h->st));
+        PG_HIP_TRY(h, hipMemcpyAsync(s.dl_emean.p, h->d_eout_m.p, (size_t)n_files * sizeof(PgSlotModel), hipMemcpyDeviceToHost, h->st));
+        PG_HIP_TRY(h, hipMemcpyAsync(s.dl_esd.p, h->d_eout_s.p, (size_t)n_files * sizeof(PgSlotModel), hipMemcpyDeviceToHost, h->st));
+        PG_HIP_TRY(h, hipMemcpyAsync(s.dl_edw_m.p, h->d_edw_m.p, (size_t)n_files * sizeof(PgSlotDwell), hipMemcpyDeviceToHost, h->st));
+        PG_HIP_TRY(h, hipMemcpyAsync(s.dl_edw_s.p, h->d_edw_s.p, (size_t)n_files * sizeof(PgSlotDwell), hipMemcpyDeviceToHost, h->st));
+        PG_HIP_TRY(h, hipMemcpyAsync(s.dl_eflags.p, h->d_evflags.p, (size_t)n_files * 4, hipMemcpyDeviceToHost, h->st));
+        if (keep_events) {
+            PG_HIP_TRY(h, hipMemcpyAsync(s.dl_vmean.p, ev_mean, cap_values * 8, hipMemcpyDeviceToHost, h->st));
+            PG_HIP_TRY(h, hipMemcpyAsync(s.dl_vsd.p, ev_sd, cap_values * 8, hipMemcpyDeviceToHost, h->st));
+        }
+    }
     PG_HIP_TRY(h, hipEventRecord(s.done, h->st));
     s.pending = true;
     return dm_settle(h, prev); // results stay in submission order: prev was submitted before s
@@ -493,11 +570,8 @@ pg_status pg_dmodel_finish(pg_dmodel *h, pg_model_result *out, pg_dmodel_info *i
     const pg_status st = pg_dmodel_sync(h);
     if (st != PG_OK) { h->slot[0].pending = h->slot[1].pending = false; dm_clear(h); return st; }
     pg_model_result &r = h->result;
-    r.n_slots = (uint32_t)h->r_n.size(); r.flags = h->flags & PG_MODEL_KEEP_FIRST;
-    r.n_values = h->r_n.data(); r.median = h->r_med.data(); r.sstdev = h->r_sd.data(); r.mid_lo = h->r_lo.data(); r.mid_hi = h->r_hi.data();
-    r.origin = h->r_origin.data(); r.sum1 = h->r_s1.data(); r.sum2_lo = h->r_s2lo.data(); r.sum2_hi = h->r_s2hi.data();
-    r.dwell_n = h->r_dn.data(); r.dwell_median = h->r_dmed.data();
-    h->info.n_files = h->r_n.size(); h->info.n_host_files = h->host_files.size(); h->info.host_files = h->host_files.data();
+    h->r.fill(r, h->flags & PG_MODEL_KEEP_FIRST);
+    h->info.n_files = h->r.size(); h->info.n_host_files = h->host_files.size(); h->info.host_files = h->host_files.data();
     *out = r;
     if (info) *info = h->info;
     h->finished = true;
@@ -517,6 +591,58 @@ size_t pg_dmodel_format(const pg_dmodel *h, uint32_t file, int32_t which, char *
         }
     }
     return pg_model_format(&h->result, file, which, buf, cap);
+}
+
+// ---- the event table --------------------------------------------------------------------------------------------------------------------
+const char *pg_events_status_text(uint32_t st) {
+    static thread_local std::string m;
+    m.clear();
+    if (!st) return "";
+    if (st & PG_EVENTS_HOST_FILE) m += " poregen model finishes it on the host (outside the strict grammar, or declined by the reduction);";
+    if (st & PG_EVENTS_ONE_SAMPLE) m += " an event with one sample has no standard deviation;";
+    if (st & PG_EVENTS_TOO_LONG) m += " an event is longer than " + std::to_string(PG_EV_MAX_LEN) + " samples;";
+    if (st & PG_EVENTS_TOO_WIDE) m += " a sample lies 2^41 units or further from its event's first sample;";
+    if (st & PG_EVENTS_BAD_VALUE) m += " a sample is outside the fixed-point view;";
+    if (st & PG_EVENTS_DECLINED) m += " the reduction declines its event means or spreads (more than 2^23 events, or values 2^40 units from the first);";
+    if (m.empty()) return ""; // (bits this library does not know)
+    m.pop_back();
+    return m.c_str() + 1;
+}
+static std::string events_message(uint32_t file, uint32_t st) { return "file " + std::to_string(file) + ": " + pg_events_status_text(st); }
+
+pg_status pg_dmodel_finish_events(pg_dmodel *h, pg_model_result *means, pg_model_result *sds, const uint32_t **status, const uint64_t **n_events) {
+    if (!h) return pg_fail<pg_dmodel>(nullptr, PG_ERR_INVALID_ARG, "pg_dmodel_finish_events: null handle");
+    if (!(h->flags & PG_DMODEL_EVENTS)) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_dmodel_finish_events: the handle was created without PG_DMODEL_EVENTS");
+    if (!means || !sds) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_dmodel_finish_events: null argument");
+    if (!h->finished) { pg_model_result r; if (pg_status st = pg_dmodel_finish(h, &r, nullptr)) return st; }
+    h->e_mean.fill(h->e_rm, PG_MODEL_KEEP_FIRST); h->e_sd.fill(h->e_rs, PG_MODEL_KEEP_FIRST); // (an event table keeps every file's first event)
+    h->e_msg.assign(h->e_status.size(), std::string());
+    for (size_t i = 0; i < h->e_status.size(); i++) if (h->e_status[i]) h->e_msg[i] = events_message((uint32_t)i, h->e_status[i]);
+    *means = h->e_rm; *sds = h->e_rs;
+    if (status) *status = h->e_status.data();
+    if (n_events) *n_events = h->e_n.data();
+    return PG_OK;
+}
+
+size_t pg_dmodel_format_events(const pg_dmodel *h, uint32_t file, int32_t column, char *buf, size_t cap) {
+    if (!h || !h->finished || !buf || cap == 0 || column < 0 || column > PG_EVENTS_COL_SD_SSTDEV) return 0;
+    buf[0] = 0;
+    return pg_model_format(column < PG_EVENTS_COL_SD_MEDIAN ? &h->e_rm : &h->e_rs, file, (column & 1) ? PG_MODEL_TEXT_SSTDEV : PG_MODEL_TEXT_MEDIAN, buf, cap);
+}
+
+const char *pg_dmodel_events_refusal(const pg_dmodel *h, uint32_t file) { return h && file < h->e_msg.size() ? h->e_msg[file].c_str() : ""; }
+
+pg_status pg_dmodel_events_values(const pg_dmodel *h, const int64_t **mean, const int64_t **sd, uint64_t *n) {
+    if (!h || !mean || !sd || !n || !h->finished || !(h->flags & PG_DMODEL_EVENTS_KEEP)) return PG_ERR_INVALID_ARG;
+    *mean = h->e_vmean.data(); *sd = h->e_vsd.data(); *n = h->e_vmean.size();
+    return PG_OK;
+}
+
+pg_status pg_dmodel_events_ms(const pg_dmodel *h, double *event_ms, double *reduce_ms) {
+    if (!h || !h->finished) return PG_ERR_INVALID_ARG;
+    if (event_ms) *event_ms = h->event_ms;
+    if (reduce_ms) *reduce_ms = h->event_reduce_ms;
+    return PG_OK;
 }
 
 } // extern "C"

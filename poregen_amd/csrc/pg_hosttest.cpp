@@ -449,3 +449,20 @@ extern "C" int pgt_pool_combine(size_t count, const uint64_t *n, const int64_t *
     if (pm.status == PG_POOL_ST_OK) { if (pm.n < 2) snprintf(sd, cap, "nan"); else pg_model_sstdev_text(pm.n, pm.num, sd, cap); }
     return pm.status;
 }
+
+// ---- the event table (pg_evstat.h): the geometry of k_ev_stats and the rule for one event, run on the host ------------------------------
+#include "pg_evstat.h"
+extern "C" void pgt_evstat_levels(uint64_t *out5) { out5[0] = PG_EV_MAX_LEN; out5[1] = (uint64_t)PG_EV_MAX_DEV; out5[2] = PG_EV_LANE; out5[3] = PG_EV_TILE; out5[4] = PG_EV_BLOCK; }
+// the refusal code (PG_EV_*) of the event units[0 .. n), n >= 1; *m and *s where they exist, else 0
+extern "C" int pgt_evstat(const int64_t *units, uint64_t n, int64_t *m, int64_t *s) {
+    *m = 0; *s = 0;
+    PgEvSums sums{0, 0, 0};
+    uint32_t code = n > PG_EV_MAX_LEN ? (uint32_t)PG_EV_TOO_LONG : 0u; // (the codes are bits: a long event may be a wide one too)
+    for (uint64_t i = 0; i < n; i++) { const int64_t d = pg_ev_dev(units[i], units[0], code); if (n <= PG_EV_MAX_LEN) pg_ev_add(sums, d); }
+    if (code) return (int)code;
+    return (int)pg_ev_finish(units[0], n, sums, *m, *s);
+}
+// the same over events back to back: event e is units[off[e] .. off[e + 1])
+extern "C" void pgt_evstat_many(const int64_t *units, const uint64_t *off, uint64_t n_events, int64_t *m, int64_t *s, int32_t *code) {
+    for (uint64_t e = 0; e < n_events; e++) code[e] = pgt_evstat(units + off[e], off[e + 1] - off[e], m + e, s + e);
+}

@@ -296,6 +296,18 @@ struct PgDtBatch {
 };
 // k_dt_count .. k_dt_evlen of the batch on st; fflags must be zero and file_off uploaded in front of them (stream order)
 hipError_t pg_launch_dump_parse(hipStream_t st, const PgDtBatch &b);
+// ---- the event table (pg_evstat.hip): mean and spread of every event of pg_result-layout arrays, in 1e-8 units -------------------------
+// ev_off [n_files + 1] and samp_off are device arrays; the counts are read on the device (events <= cap_events, values <= cap_values, the
+// sizes of ev_mean / ev_sd and of the carry). fflags [n_files]: PG_EV_* bits are OR-ed in. carry: pg_ev_carry_bytes(cap_values) of work space.
+// The caller keeps: samp_off[0] = 0, every event holds a sample, units / samples 16-byte aligned (hipErrorInvalidValue otherwise).
+static inline uint64_t pg_ev_tiles(uint64_t cap_values) { return (cap_values + 127) / 128 + 1; } // tiles of PG_EV_TILE values
+size_t pg_ev_carry_bytes(uint64_t cap_values);
+hipError_t pg_launch_ev_stats_units(hipStream_t st, uint32_t n_files, const uint64_t *ev_off, const uint64_t *samp_off, const int64_t *units, uint64_t cap_events,
+                                    uint64_t cap_values, int64_t *ev_mean, int64_t *ev_sd, uint32_t *fflags, void *carry);
+hipError_t pg_launch_ev_stats(hipStream_t st, uint32_t n_files, const uint64_t *ev_off, const uint64_t *samp_off, const double *samples, uint64_t cap_events,
+                              uint64_t cap_values, int64_t *ev_mean, int64_t *ev_sd, uint32_t *fflags, void *carry);
+// id_off[i] = i (n + 1 entries), len1[i] = 1: the layout in which every one of n values is an event of its own
+hipError_t pg_launch_ev_identity(hipStream_t st, uint64_t n, uint64_t *id_off, uint32_t *len1);
 // the generic walk (one wave per listed read: walk + event loop) over O.gen_list
 hipError_t pg_launch_walk(hipStream_t st, const PgDevBatch &B, const PgWalkParams &W, const PgWalkOut &O);
 // the op-parallel event kernel over ALL op indices: computes the events of direct reads, passes the generic reads' through, and (hist

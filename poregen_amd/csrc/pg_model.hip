@@ -211,22 +211,7 @@ __device__ __forceinline__ FileRef file_ref(const uint64_t *__restrict__ ev_off,
     return f;
 }
 
-// pg_fixed8 for the device: below 2.2e7 the correctly rounded product sits in the low mantissa bits of p + 1.5 * 2^52 (|p| < 2^51; the sum
-// rounds to even at an ulp of 1 exactly as rint does), the FMA's error decides an exact tie as in pg_fixed8 -- the same integer, without the
-// conversion sequence (a dozen instructions per value and pass of the kernels below); anything else takes the shared function.
-__device__ __forceinline__ int64_t fixed8_dev(double x, bool &bad) {
-    if (!(fabs(x) < 2.2e7)) return pg_fixed8(x, bad);
-    const double p = x * 1e8, e = fma(x, 1e8, -p);
-    double t = p + 6755399441055744.0;
-    const double f = p - (t - 6755399441055744.0);
-    if (f == 0.5 && e > 0.0) t += 1.0;
-    else if (f == -0.5 && e < 0.0) t -= 1.0;
-    return (int64_t)((uint64_t)__double_as_longlong(t) & ((1ull << 52) - 1)) - (1ll << 51);
-}
-// A sample as the kernels are handed it (S): the double gmove held, converted as above, or -- pg_dumptext.hip, which reads the dump text
-// back -- the integer of 1e-8 units itself, which never passes through a double.
-__device__ __forceinline__ int64_t sample_units(double x, bool &bad) { return fixed8_dev(x, bad); }
-__device__ __forceinline__ int64_t sample_units(int64_t v, bool &bad) { if (!(v > -PG_MODEL_MAX_UNITS && v < PG_MODEL_MAX_UNITS)) bad = true; return v; }
+// (fixed8_dev and sample_units, the conversion of a sample as the kernels are handed it, are in pg_model.h: pg_evstat.hip uses them too)
 
 // The two workgroup kernels, by file size: SHORT (256 threads, <= 4096 values) converts the whole file once into 16 registers per
 // thread; LONG (1024 threads) re-reads the file per pass. Both stride over the list of their slots. Separate kernels because each needs

@@ -199,6 +199,31 @@ class Model:
         return "".join(f"{kmers[i]}\t{self.dwell_text[i]}\n" for i in sorted(range(len(kmers)), key=lambda j: kmers[j]))
 
 
+@dataclass
+class EventModel:
+    """The event table (pg_dmodel_finish_events / pg_model_events): `means` and `sds` are Models with one entry per file or slot -- the
+    reduction of its events' means and of its events' standard deviations, in 1e-8 units; a refused entry reads as empty."""
+    means: "Model"
+    sds: "Model"
+    status: np.ndarray        # per entry: 0, or _abi.PG_EVENTS_* bits of its refusal
+    n_events: np.ndarray
+    refusal: list             # per entry: the message, "" when not refused
+    ev_mean: object           # DumpModel(events=True, keep_events=True): every event's mean / standard deviation, entry after entry, else None
+    ev_sd: object
+    event_ms: float           # DumpModel(profile=True): device time of the per-event kernels / of the two reductions behind them
+    reduce_ms: float
+
+    def lines(self, names) -> str:
+        """NAME<TAB>n_events<TAB>mean_median<TAB>mean_sstdev<TAB>sd_median<TAB>sd_sstdev, sorted by name; ValueError for a refused entry"""
+        out = []
+        for i in sorted(range(len(names)), key=lambda j: names[j].encode()):
+            if self.status[i]:
+                raise ValueError("the event table of %s is refused: %s" % (names[i], self.refusal[i]))
+            out.append("%s\t%d\t%s\t%s\t%s\t%s\n" % (names[i], int(self.n_events[i]), self.means.median_text[i], self.means.sstdev_text[i],
+                                                     self.sds.median_text[i], self.sds.sstdev_text[i]))
+        return "".join(out)
+
+
 def _ptr(a):
     if a is None:
         return None
@@ -394,6 +419,17 @@ class GmoveEngine:
         m = _abi.PgModelResult()
         self._check(self._lib.pg_model(self._h, _abi.PG_MODEL_KEEP_FIRST if keep_first else 0, C.byref(m)))
         return self._model_from(m)
+
+    def model_events(self) -> "EventModel":
+        """The event table of everything collected so far (pg_model_events): per k-mer the reduction of its kept events' means and of their
+        standard deviations, the numbers `poregen model --event_model` derives from the dump files."""
+        r = _abi.PgEventsResult()
+        self._check(self._lib.pg_model_events(self._h, 0, C.byref(r)))
+        ns = r.means.n_slots
+        status = np.ctypeslib.as_array(C.cast(r.status, C.POINTER(C.c_uint32)), (ns,)).copy() if ns else np.zeros(0, np.uint32)
+        n_events = np.ctypeslib.as_array(C.cast(r.n_events, C.POINTER(C.c_uint64)), (ns,)).copy() if ns else np.zeros(0, np.uint64)
+        return EventModel(means=self._model_from(r.means), sds=self._model_from(r.sds), status=status, n_events=n_events,
+                          refusal=[self._lib.pg_events_status_text(int(x)).decode() for x in status], ev_mean=None, ev_sd=None, event_ms=0.0, reduce_ms=0.0)
 
     def model_device(self, counts, ev_len, samples, keep_first: bool = False) -> "Model":
         """The same reduction over torch CUDA tensors in the layout `dist.gather_kept` returns on the writing rank: counts
@@ -1086,10 +1122,12 @@ class DumpModel:
     numpy uint8 array, or a CUDA torch.uint8 tensor (read in place, kept alive until finish) -- and file_off[n_files + 1]; finish()
     returns a Model with one entry per file in submission order, and a DumpModelInfo."""
 
-    def __init__(self, keep_first: bool = False, device: int = 0, profile: bool = False):
+    def __init__(self, keep_first: bool = False, device: int = 0, profile: bool = False, events: bool = False, keep_events: bool = False):
         self._lib = _abi.load()
         h = C.c_void_p()
         flags = (_abi.PG_MODEL_KEEP_FIRST if keep_first else 0) | (_abi.PG_DMODEL_PROFILE if profile else 0)
+        flags |= (_abi.PG_DMODEL_EVENTS if events or keep_events else 0) | (_abi.PG_DMODEL_EVENTS_KEEP if keep_events else 0)
+        self._keep_events = keep_events
         st = self._lib.pg_dmodel_create(device, flags, C.byref(h))
         if st != 0:
             raise PgError(st, self._lib.pg_dmodel_last_error(None).decode())
@@ -1132,6 +1170,38 @@ class DumpModel:
         return _model_arrays(m, text_of), DumpModelInfo(int(info.n_files), int(info.n_bytes), int(info.n_values), nh, hf, int(info.n_batches),
                                                         float(info.parse_ms), float(info.model_ms))
 
+    def finish_events(self) -> "EventModel":
+        """The event table of the files of the last finish() (DumpModel(events=True); finish() is called when it was not): an EventModel with
+        one entry per file in submission order."""
+        em, es = _abi.PgModelResult(), _abi.PgModelResult()
+        st, ne = C.c_void_p(), C.c_void_p()
+        self._check(self._lib.pg_dmodel_finish_events(self._h, C.byref(em), C.byref(es), C.byref(st), C.byref(ne)))
+        self._keep = []
+        nf = em.n_slots
+        buf = C.create_string_buffer(64)
+
+        def side(m, col0):
+            def text_of(s, which):
+                if which == _abi.PG_MODEL_TEXT_DWELL:
+                    return ""
+                n = self._lib.pg_dmodel_format_events(self._h, s, col0 + which, buf, 64)
+                return buf.raw[:n].decode()
+            return _model_arrays(m, text_of)
+        status = np.ctypeslib.as_array(C.cast(st, C.POINTER(C.c_uint32)), (nf,)).copy() if nf else np.zeros(0, np.uint32)
+        n_events = np.ctypeslib.as_array(C.cast(ne, C.POINTER(C.c_uint64)), (nf,)).copy() if nf else np.zeros(0, np.uint64)
+        ev_mean = ev_sd = None
+        if self._keep_events:
+            pm, ps, n = C.c_void_p(), C.c_void_p(), C.c_uint64(0)
+            if self._lib.pg_dmodel_events_values(self._h, C.byref(pm), C.byref(ps), C.byref(n)) != 0:
+                raise PgError(-1, "pg_dmodel_events_values failed")
+            take = lambda p: np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int64)), (n.value,)).copy() if n.value else np.zeros(0, np.int64)
+            ev_mean, ev_sd = take(pm), take(ps)
+        a, b = C.c_double(0), C.c_double(0)
+        self._lib.pg_dmodel_events_ms(self._h, C.byref(a), C.byref(b))
+        return EventModel(means=side(em, _abi.PG_EVENTS_COL_MEAN_MEDIAN), sds=side(es, _abi.PG_EVENTS_COL_SD_MEDIAN), status=status, n_events=n_events,
+                          refusal=[self._lib.pg_dmodel_events_refusal(self._h, f).decode() for f in range(nf)], ev_mean=ev_mean, ev_sd=ev_sd,
+                          event_ms=a.value, reduce_ms=b.value)
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.pg_dmodel_destroy(self._h)
@@ -1158,6 +1228,22 @@ def list_dump_dirs(dirs):
     return [os.fsdecode(n) for n in names], [found[n] for n in names]
 
 
+def _submit_dump_files(dm, paths, batch_bytes):
+    """the files of list_dump_dirs through dm.submit: batches of whole logical files (a name's files back to back), cut at batch_bytes"""
+    chunks, off = [], [0]
+
+    def flush():
+        if len(off) > 1:
+            dm.submit(b"".join(chunks), off)
+        chunks.clear(); del off[1:]
+    for ps in paths:
+        data = b"".join(open(p, "rb").read() for p in ps)
+        if len(off) > 1 and off[-1] + len(data) > batch_bytes:
+            flush()
+        chunks.append(data); off.append(off[-1] + len(data))
+    flush()
+
+
 def model_from_dumps(dirs, limit: str = "3.1", keep_first: bool = False, batch_bytes: int = 64 << 20, device: int = 0, profile: bool = False):
     """One-shot `poregen model`: (raw_lines, dwell_lines, info) of the dump directories -- NAME<TAB>median<TAB>stddev (capped at `limit`) and
     NAME<TAB>median dwell per file name; files of one name in several directories are read back to back."""
@@ -1166,22 +1252,27 @@ def model_from_dumps(dirs, limit: str = "3.1", keep_first: bool = False, batch_b
     names, paths = list_dump_dirs(dirs)
     dm = DumpModel(keep_first=keep_first, device=device, profile=profile)
     try:
-        chunks, off = [], [0]
-
-        def flush():
-            if len(off) > 1:
-                dm.submit(b"".join(chunks), off)
-            chunks.clear(); del off[1:]
-        for ps in paths:
-            data = b"".join(open(p, "rb").read() for p in ps)
-            if len(off) > 1 and off[-1] + len(data) > batch_bytes:
-                flush()
-            chunks.append(data); off.append(off[-1] + len(data))
-        flush()
+        _submit_dump_files(dm, paths, batch_bytes)
         m, info = dm.finish()
     finally:
         dm.close()
     return m.raw_model_lines(names, limit), m.dwell_lines(names), info
+
+
+def event_model_from_dumps(dirs, keep_first: bool = False, batch_bytes: int = 64 << 20, device: int = 0, profile: bool = False, keep_events: bool = False):
+    """One-shot `poregen model --event_model`: (names, EventModel, info) of the dump directories; EventModel.lines(names) is the table's
+    text. keep_first only decides, in rare corners, which files `poregen model` finishes on the host (and whose table is refused for it)."""
+    if isinstance(dirs, (str, bytes)) or hasattr(dirs, "__fspath__"):
+        dirs = [dirs]
+    names, paths = list_dump_dirs(dirs)
+    dm = DumpModel(keep_first=keep_first, device=device, profile=profile, events=True, keep_events=keep_events)
+    try:
+        _submit_dump_files(dm, paths, batch_bytes)
+        _, info = dm.finish()
+        ev = dm.finish_events()
+    finally:
+        dm.close()
+    return names, ev, info
 
 
 @dataclass

@@ -10,6 +10,9 @@ Measured per directory:
   device     the same files through engine.DumpModel(profile=True) from bytes already in host memory: HIP-event time of the parse
              kernels (k_dt_count .. k_dt_evlen) and of the reduction, parse bytes/s, next to the plain streaming-read figure
              of tools/probe/stream_probe.hip on the same machine (its best "A plain" line)
+  events     the same batches through DumpModel(profile=True, events=True): event_ms, the HIP-event time of k_ev_stats + k_ev_carry
+             (pg_evstat.hip) over the parsed values, next to parse_ms and model_ms of the same run; the 8 bytes per value it reads as
+             GB/s and as a fraction of the streaming-read figure; reduce_ms, the two reductions over one value per event behind it
   cpu        oracle/model_oracle stats + dwell over the same directory on one core (the pipeline's tr | tail | datamash restated in C)
 Prints one JSON object and writes it to --out.
 """
@@ -98,6 +101,19 @@ def measure(d, raw, reps):
                     "parse_GBps": round(n_bytes / (info.parse_ms * 1e-3) / 1e9, 2) if info.parse_ms else None}
     dm.close()
     res["device"] = best
+    dm = DumpModel(profile=True, events=True)
+    best = None
+    for _ in range(reps + 1):
+        for data, o in batches:
+            dm.submit(data, o)
+        _, info = dm.finish()
+        ev = dm.finish_events()
+        if best is None or ev.event_ms < best["event_ms"]:
+            best = {"event_ms": round(ev.event_ms, 4), "reduce_ms": round(ev.reduce_ms, 4), "parse_ms": round(info.parse_ms, 4), "model_ms": round(info.model_ms, 4),
+                    "n_values": info.n_values, "n_events": int(ev.n_events.sum()), "n_refused": int((ev.status != 0).sum()),
+                    "event_GBps": round(info.n_values * 8 / (ev.event_ms * 1e-3) / 1e9, 2) if ev.event_ms else None}
+    dm.close()
+    res["events"] = best
     t = time.perf_counter()
     for mode in (["stats", d, "3.1"], ["dwell", d]):
         subprocess.run([ORACLE] + mode, stdout=subprocess.DEVNULL, check=True)
@@ -124,6 +140,9 @@ def main():
         res["k5"] = dict(measure(d5, raw5, a.reps), gmove_s=round(s5, 2), reads=a.reads, sample_limit=5000)
         d9, raw9, s9 = write_dump(tmp, "k9", "dna_r10", a.k9_reads, 9, a.k9_limit, [])
         res["k9"] = dict(measure(d9, raw9, a.reps), gmove_s=round(s9, 2), reads=a.k9_reads, sample_limit=a.k9_limit)
+        for k in ("k5", "k9"):   # the new kernel against the plain streaming read of the same machine
+            gbps = res[k]["events"]["event_GBps"]
+            res[k]["events"]["fraction_of_stream_read"] = round(gbps / (res["stream_read_TBps"] * 1e3), 4) if gbps and res["stream_read_TBps"] else None
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
     line = json.dumps(res)
