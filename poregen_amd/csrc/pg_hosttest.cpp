@@ -412,6 +412,90 @@ extern "C" long pgt_kf_fasta(const uint8_t *data, uint64_t n, const uint64_t *cu
     return (long)i;
 }
 
+// ---- kmer_freq on FASTQ input (pg_kfreq_text.h): the kernels' decomposition on the host -- a unit's newlines counted per tile as k_kf_lines
+// does, then every span of every tile walked from the line index k_kf_count derives for it (the carried state, the tiles in front, the
+// spans in front inside the tile), then the seam and the next unit's state, which workgroup 0 forms. One thread after the other.
+#include "pg_kfreq_text.h"
+namespace {
+struct KfHostSink {
+    uint32_t k; std::map<uint32_t, uint64_t> *hist; std::map<std::string, uint64_t> *odd_map;
+    void dense(uint32_t code) { (*hist)[code]++; }
+    void odd(uint64_t lo, uint32_t hi) {
+        uint32_t key[4];
+        pg_kf_odd_key(lo, hi, k, key);
+        std::string s(k, '\0');
+        for (uint32_t i = 0; i < k; i++) s[i] = (char)(key[i >> 2] >> (8 * (i & 3)));
+        (*odd_map)[s]++;
+    }
+};
+uint32_t kf_host_newlines(const uint8_t *p, uint64_t from, uint64_t to) {
+    uint32_t c = 0;
+    for (uint64_t q = from; q < to; q++) c += p[q] == '\n';
+    return c;
+}
+bool kf_host_unit(const uint8_t *p, uint64_t n, uint32_t k, KfState &st, KfHostSink &sink) {
+    const uint32_t n_tiles = (uint32_t)((n + PG_KF_TILE - 1) / PG_KF_TILE);
+    std::vector<uint32_t> tile_nl(n_tiles);
+    for (uint32_t t = 0; t < n_tiles; t++) tile_nl[t] = kf_host_newlines(p, t * PG_KF_TILE, std::min<uint64_t>(n, (t + 1) * PG_KF_TILE)); // k_kf_lines
+    bool bad = false;
+    uint32_t total_nl = 0;
+    for (uint32_t blk = 0; blk < n_tiles; blk++) { // k_kf_count, block blk
+        const uint32_t upto = blk == 0 ? n_tiles : blk;
+        uint32_t tile_pre = 0;
+        for (uint32_t tid = 0; tid < PG_KF_THREADS; tid++)
+            for (uint32_t i = tid; i < upto; i += PG_KF_THREADS) tile_pre += tile_nl[i];
+        if (blk == 0) { total_nl = tile_pre; tile_pre = 0; }
+        uint32_t excl = 0; // newlines of the spans in front, inside the tile
+        for (uint32_t tid = 0; tid < PG_KF_THREADS; tid++) {
+            const uint64_t base = blk * PG_KF_TILE + tid * (uint64_t)PG_KF_SPAN;
+            if (base >= n) break;
+            FaHostLoad load{p, base, n};
+            bad |= pg_kf_walk(p, base, n, k, (st.mod4 + tile_pre + excl) & 3, load, sink);
+            excl += kf_host_newlines(p, base, std::min<uint64_t>(n, base + PG_KF_SPAN));
+        }
+    }
+    st = pg_kf_seam(st, p, n, k, total_nl, sink); // block 0, thread 0
+    return bad;
+}
+} // namespace
+extern "C" void pgt_kfreq_levels(uint64_t *out6) {
+    out6[0] = PG_KF_SPAN; out6[1] = PG_KF_TILE; out6[2] = PG_KF_UNIT; out6[3] = PG_KF_MAX_K; out6[4] = PG_KF_LDS_MAX_K; out6[5] = PG_KF_ODD_LDS;
+}
+// The FASTQ form on data[0, n), pieces, units and outputs as for pgt_kf_fasta. The window that ends on the stream's last byte is never
+// settled, as in pg_kfreq_finish. *nul = a sequence line holds a NUL byte.
+extern "C" long pgt_kf_text(const uint8_t *data, uint64_t n, const uint64_t *cuts, size_t n_cuts, uint32_t k, uint64_t unit,
+                            uint32_t *dense_codes, uint64_t *dense_counts, size_t dense_cap, uint8_t *odd_keys, uint64_t *odd_counts,
+                            size_t *n_dense, size_t odd_cap, int *nul) {
+    std::map<uint32_t, uint64_t> hist;
+    std::map<std::string, uint64_t> odd;
+    KfHostSink sink{k, &hist, &odd};
+    KfState st{};
+    bool bad = false;
+    uint64_t at = 0;
+    for (size_t c = 0; c < n_cuts; c++) {
+        const uint64_t end = std::min<uint64_t>(cuts[c], n);
+        while (at < end) {
+            const uint64_t m = std::min<uint64_t>(unit, end - at);
+            const std::vector<uint8_t> u(data + at, data + at + m); // a buffer of its own: nothing outside the unit can be read unnoticed
+            bad |= kf_host_unit(u.data(), m, k, st, sink);
+            at += m;
+        }
+    }
+    size_t i = 0;
+    for (const auto &kv : hist) {
+        if (i < dense_cap) { dense_codes[i] = kv.first; dense_counts[i] = kv.second; }
+        i++;
+    }
+    *n_dense = i;
+    i = 0;
+    for (const auto &kv : odd) {
+        if (i < odd_cap) { memcpy(odd_keys + i * k, kv.first.data(), k); odd_counts[i] = kv.second; }
+        i++;
+    }
+    *nul = bad;
+    return (long)i;
+}
+
 // ---- move-table expansion: the per-read rule the kernels of pg_mvops.hip compile (pg_mvops.h), run on the host ----------------------
 #include "pg_mvops.h"
 extern "C" void pgt_mvops_levels(uint32_t *out3) { out3[0] = PG_MVOPS_LANE; out3[1] = PG_MVOPS_STEP; out3[2] = PG_MVOPS_PIECE; }

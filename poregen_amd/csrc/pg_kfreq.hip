@@ -18,6 +18,7 @@
 //                that straddle the previous unit (the "seam") and writes the next unit's carried state (line index mod 4, the
 //                open line's last <= k bytes) into the other slot of a two-slot state: no host round trip between units.
 // Equal codes a thread meets back to back (homopolymers) are added once, as a run.
+// The walk of a span and the seam are pg_kfreq_text.h, which the host test shim compiles too; here are their loader and sinks.
 //
 // Second input form, pg_kfreq_submit_reads: reads as a BAM record stores them, two 4-bit codes per byte (pg_kfreq_codes.h), each read a
 // sequence line of its own. No lines to find, so one launch per submit (or per h->unit windows of it):
@@ -41,6 +42,7 @@
 #include "pg_hip_host.h"
 #include "pg_kfreq_codes.h"
 #include "pg_kfreq_fasta.h"
+#include "pg_kfreq_text.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -52,19 +54,14 @@
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kSpan = 128;                       // bytes per thread
-constexpr uint64_t kTile = (uint64_t)kThreads * kSpan;  // 32 KiB per workgroup
-constexpr uint64_t kUnit = 16ull << 20;          // bytes per unit (512 tiles)
-constexpr uint32_t kMaxK = 12;
-constexpr uint32_t kLdsMaxK = 6;                 // 4^6 u32 = 16 KiB of LDS
+// the geometry of the text kernels and KfState, the state carried across units: pg_kfreq_text.h
+constexpr int kThreads = PG_KF_THREADS;
+constexpr int kSpan = PG_KF_SPAN;                // bytes per thread
+constexpr uint64_t kTile = PG_KF_TILE;           // 32 KiB per workgroup
+constexpr uint64_t kUnit = PG_KF_UNIT;           // bytes per unit (512 tiles)
+constexpr uint32_t kMaxK = PG_KF_MAX_K;
+constexpr uint32_t kLdsMaxK = PG_KF_LDS_MAX_K;   // 4^6 u32 = 16 KiB of LDS
 constexpr int kSnapRing = 64;                    // outstanding odd-count snapshots
-
-struct KfState {       // carried across units; two slots, unit u reads slot u&1 and writes slot (u+1)&1
-    uint32_t mod4;     // index mod 4 of the line open at the unit's first byte
-    uint32_t tail_len; // bytes of that line already seen, capped at k (all of them, if fewer)
-    uint8_t tail[16];  // its last tail_len bytes, oldest first
-};
 
 struct KfFaState {     // the FASTA form's carried state, two slots like KfState; all zero at the start of a stream
     uint32_t kind;     // PG_FA_*: the line open at the unit's first byte (FRESH: it starts there)
@@ -86,8 +83,6 @@ struct KfDev {
     KfFaState *fa_state;       // [2]
     uint64_t odd_cap;
 };
-
-__device__ __forceinline__ int base_code(uint32_t c) { return pg_kf_base_code(c); }
 
 // this thread's kSpan bytes of the unit (or fewer at its end), as four-byte words in registers
 template <bool kAligned>
@@ -137,13 +132,8 @@ __global__ __launch_bounds__(kThreads) void k_kf_lines(const uint8_t *__restrict
 }
 
 __device__ __forceinline__ uint4 odd_key(uint64_t lo, uint32_t hi, uint32_t k) {
-    // lo/hi: the window's bytes, newest in the lowest byte of lo
-    uint32_t key[4] = {0, 0, 0, 0};
-    for (uint32_t i = 0; i < k; i++) {
-        const uint32_t sh = k - 1 - i; // byte i of the key is sh bytes older than the newest
-        const uint32_t b = sh < 8 ? (uint32_t)(lo >> (8 * sh)) & 0xff : (hi >> (8 * (sh - 8))) & 0xff;
-        key[i >> 2] |= b << (8 * (i & 3));
-    }
+    uint32_t key[4];
+    pg_kf_odd_key(lo, hi, k, key);
     return make_uint4(key[0], key[1], key[2], key[3]);
 }
 
@@ -153,7 +143,7 @@ __device__ __forceinline__ void emit_odd(const KfDev &d, uint4 key) {
 }
 
 // odd windows of a workgroup are gathered in LDS and appended with one global add per workgroup; past kOddLds they go out one by one
-constexpr uint32_t kOddLds = 512;
+constexpr uint32_t kOddLds = PG_KF_ODD_LDS;
 __device__ __forceinline__ void stage_odd(const KfDev &d, uint4 *s_odd, uint32_t *s_odd_n, uint4 key) {
     const uint32_t i = atomicAdd(s_odd_n, 1u);
     if (i < kOddLds) s_odd[i] = key;
@@ -197,48 +187,42 @@ __device__ __forceinline__ void kf_flush(const KfDev &d, uint32_t *lds_hist, uin
     }
 }
 
+// The sinks of the walks (pg_kfreq_text.h: pg_kf_walk, pg_kf_seam; pg_kfreq_fasta.h: pg_fa_walk) and the loader of a span's 16-byte chunks.
+// A thread's sink merges equal codes met back to back into a run (kf_flush adds the open one) and stages its odd windows in LDS.
+template <bool kLds>
+struct KfSink {
+    const KfDev &d;
+    uint32_t *lds_hist;
+    uint4 *s_odd;
+    uint32_t *s_odd_n;
+    uint32_t k, run_code, run_cnt;
+    __device__ __forceinline__ void dense(uint32_t code) {
+        if (code == run_code) run_cnt++;
+        else { add_run<kLds>(d, lds_hist, run_code, run_cnt); run_code = code; run_cnt = 1; }
+    }
+    __device__ __forceinline__ void odd(uint64_t lo, uint32_t hi) { stage_odd(d, s_odd, s_odd_n, odd_key(lo, hi, k)); }
+};
+struct KfSeamSink { // block 0, thread 0: a handful of windows per unit, added one by one
+    const KfDev &d;
+    uint32_t k;
+    __device__ __forceinline__ void dense(uint32_t code) { atomicAdd(&d.hist[code], 1ull); }
+    __device__ __forceinline__ void odd(uint64_t lo, uint32_t hi) { emit_odd(d, odd_key(lo, hi, k)); }
+};
+template <bool kAligned>
+struct KfLoad {
+    const uint8_t *p;
+    uint64_t base, n;
+    __device__ __forceinline__ void operator()(uint32_t ch, uint32_t (&ws)[4]) const {
+        const uint4 v = load16<kAligned>(p, base + 16 * ch, n); // second read of the span: served by the cache
+        ws[0] = v.x; ws[1] = v.y; ws[2] = v.z; ws[3] = v.w;
+    }
+};
+
 // block 0, thread 0: windows that start in the carried tail and end in this unit, then the state the next unit starts from
 __device__ void kf_seam(const KfDev &d, const uint8_t *__restrict__ p, uint64_t n, uint32_t k, uint32_t par, uint32_t total_nl) {
     const KfState s = d.state[par];
-    uint8_t v[2 * kMaxK];
-    const uint32_t t = s.tail_len;
-    const uint32_t head = (uint32_t)min<uint64_t>(n, k - 1);
-    for (uint32_t i = 0; i < t; i++) v[i] = s.tail[i];
-    for (uint32_t i = 0; i < head; i++) v[t + i] = p[i];
-    // window ending at v[e]: e >= k-1 (whole), e <= t+k-2 (starts in the tail), e <= t+n-2 (not the stream's last byte so far)
-    if (s.mod4 == 1 && t >= 1) { // (k = 1: only the window of the tail's byte, left open by the last unit)
-        const uint64_t e_hi = min<uint64_t>(t + k - 2, t + n - 2);
-        for (uint64_t e = k - 1; e <= e_hi; e++) {
-            bool nl = false, acgt = true;
-            uint32_t code = 0;
-            uint64_t lo = 0; uint32_t hi = 0;
-            for (uint32_t j = 0; j < k; j++) {
-                const uint32_t c = v[e + 1 - k + j];
-                nl |= c == '\n';
-                const int b = base_code(c);
-                acgt &= b >= 0;
-                code = (code << 2) | (uint32_t)(b & 3);
-                hi = (hi << 8) | (uint32_t)(lo >> 56); lo = (lo << 8) | c;
-            }
-            if (nl) break; // every later window holds the same newline
-            if (acgt) atomicAdd(&d.hist[code], 1ull);
-            else emit_odd(d, odd_key(lo, hi, k));
-        }
-    }
-    // the next state: the open line's last <= k bytes
-    KfState o;
-    o.mod4 = (s.mod4 + total_nl) & 3;
-    int64_t nl = -1; // last newline among the unit's last min(n, k) bytes
-    for (uint64_t i = n; i > 0 && n - i < k; i--)
-        if (p[i - 1] == '\n') { nl = (int64_t)i - 1; break; }
-    uint8_t cat[2 * kMaxK];
-    uint32_t m = 0;
-    if (nl < 0 && n < k) for (uint32_t i = 0; i < t; i++) cat[m++] = s.tail[i]; // the whole unit continues the open line
-    for (uint64_t i = nl >= 0 ? (uint64_t)nl + 1 : (n > k ? n - k : 0); i < n; i++) cat[m++] = p[i];
-    const uint32_t keep = min(m, k);
-    o.tail_len = keep;
-    for (uint32_t i = 0; i < 16; i++) o.tail[i] = i < keep ? cat[m - keep + i] : 0;
-    d.state[par ^ 1] = o;
+    KfSeamSink sink{d, k};
+    d.state[par ^ 1] = pg_kf_seam(s, p, n, k, total_nl, sink);
 }
 
 template <bool kAligned, bool kLds>
@@ -288,56 +272,12 @@ __global__ __launch_bounds__(kThreads) void k_kf_count(KfDev d, const uint8_t *_
     const KfState st = d.state[par];
     uint32_t mod4 = (st.mod4 + tile_pre + excl) & 3;
 
-    uint32_t run_code = 0, run_cnt = 0;
+    KfSink<kLds> sink{d, lds_hist, s_odd, &s_odd_n, k, 0, 0};
     if (base < n) {
-        const uint64_t mask = n_codes - 1;
-        // warm-up: the k-1 bytes in front of this thread's span (inside the unit; earlier ones are the seam's)
-        uint32_t len = 0, run = 0, code = 0;
-        uint64_t lo = 0; uint32_t hi = 0;
-        const uint64_t w0 = base >= k - 1 ? base - (k - 1) : 0;
-        for (uint64_t q = w0; q < base; q++) {
-            const uint32_t c = p[q];
-            if (c == '\n') { len = 0; run = 0; continue; }
-            len++;
-            const int b = base_code(c);
-            run = b >= 0 ? run + 1 : 0;
-            code = (code << 2) | (uint32_t)(b & 3);
-            hi = (hi << 8) | (uint32_t)(lo >> 56); lo = (lo << 8) | c;
-        }
-        bool bad = false;
-        const uint32_t lim = (uint32_t)min<uint64_t>(kSpan, n - base);
-        // the last byte of the unit is not an end of a counted window here: the seam of the next unit (or finish) settles it
-        const uint32_t last_ok = base + lim == n ? lim - 1 : lim;
-        for (uint32_t ch = 0; ch < kSpan / 16; ch++) {
-            if (ch * 16 >= lim) break;
-            const uint4 v = load16<kAligned>(p, base + 16 * ch, n); // second read of the span: served by the cache
-            const uint32_t ws[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (uint32_t j = 0; j < 16; j++) {
-                const uint32_t i = ch * 16 + j;
-                if (i >= lim) break;
-                const uint32_t c = (ws[j >> 2] >> (8 * (j & 3))) & 0xff;
-                if (c == '\n') { mod4 = (mod4 + 1) & 3; len = 0; run = 0; continue; }
-                const bool seq = mod4 == 1;
-                bad |= seq && c == 0;
-                len++;
-                const int b = base_code(c);
-                run = b >= 0 ? run + 1 : 0;
-                code = ((code << 2) | (uint32_t)(b & 3)) & (uint32_t)mask;
-                hi = (hi << 8) | (uint32_t)(lo >> 56); lo = (lo << 8) | c;
-                if (seq && len >= k && i < last_ok) {
-                    if (run >= k) {
-                        if (code == run_code) run_cnt++;
-                        else { add_run<kLds>(d, lds_hist, run_code, run_cnt); run_code = code; run_cnt = 1; }
-                    } else {
-                        stage_odd(d, s_odd, &s_odd_n, odd_key(lo, hi, k));
-                    }
-                }
-            }
-        }
-        if (bad) atomicOr(d.err, 1u);
+        KfLoad<kAligned> load{p, base, n};
+        if (pg_kf_walk(p, base, n, k, mod4, load, sink)) atomicOr(d.err, 1u);
     }
-    kf_flush<kLds>(d, lds_hist, n_codes, run_code, run_cnt, s_odd, &s_odd_n, &s_odd_at);
+    kf_flush<kLds>(d, lds_hist, n_codes, sink.run_code, sink.run_cnt, s_odd, &s_odd_n, &s_odd_at);
 }
 
 // ---- FASTA text ------------------------------------------------------------------------------------------------------------------
@@ -414,29 +354,6 @@ __global__ __launch_bounds__(kThreads) void k_kf_fa_lines(const uint8_t *__restr
     }
 }
 
-template <bool kLds>
-struct KfFaSink {
-    const KfDev &d;
-    uint32_t *lds_hist;
-    uint4 *s_odd;
-    uint32_t *s_odd_n;
-    uint32_t k, run_code, run_cnt;
-    __device__ __forceinline__ void dense(uint32_t code) {
-        if (code == run_code) run_cnt++;
-        else { add_run<kLds>(d, lds_hist, run_code, run_cnt); run_code = code; run_cnt = 1; }
-    }
-    __device__ __forceinline__ void odd(uint64_t lo, uint32_t hi) { stage_odd(d, s_odd, s_odd_n, odd_key(lo, hi, k)); }
-};
-template <bool kAligned>
-struct KfFaLoad {
-    const uint8_t *p;
-    uint64_t base, n;
-    __device__ __forceinline__ void operator()(uint32_t ch, uint32_t (&ws)[4]) const {
-        const uint4 v = load16<kAligned>(p, base + 16 * ch, n); // second read of the span: served by the cache
-        ws[0] = v.x; ws[1] = v.y; ws[2] = v.z; ws[3] = v.w;
-    }
-};
-
 template <bool kAligned, bool kLds>
 __global__ __launch_bounds__(kThreads) void k_kf_fa_count(KfDev d, const uint8_t *__restrict__ p, uint64_t n, uint32_t n_tiles, uint32_t k, uint32_t par) {
     extern __shared__ uint32_t lds_hist[];
@@ -487,9 +404,9 @@ __global__ __launch_bounds__(kThreads) void k_kf_fa_count(KfDev d, const uint8_t
     PgFaSum all;
     const PgFaSum rec = pg_fa_compose(rec_in, block_compose_before(lim ? pg_fa_resolve(kind, first_byte, sp.fa, sp.pb) : pg_fa_empty(), s_w, &all));
 
-    KfFaSink<kLds> sink{d, lds_hist, s_odd, &s_odd_n, k, 0, 0};
+    KfSink<kLds> sink{d, lds_hist, s_odd, &s_odd_n, k, 0, 0};
     if (lim) {
-        KfFaLoad<kAligned> load{p, base, n};
+        KfLoad<kAligned> load{p, base, n};
         if (pg_fa_walk(load, lim, k, kind, rec, sink)) atomicOr(d.err, 1u);
     }
     kf_flush<kLds>(d, lds_hist, n_codes, sink.run_code, sink.run_cnt, s_odd, &s_odd_n, &s_odd_at);
