@@ -98,6 +98,14 @@
  * pg_transform_model               apply_transformation and set_stddev: echo | bc -l per row, datamash min max, cut | paste
  *                                                                                  scripts/poregen.sh:87-148
  * pg_transform_free                (no counterpart)
+ *
+ * Whether a model is any good (the reference asks other tools: scripts/eventaling.sh runs f5c eventalign, scripts/sim.sh squigulator and a
+ * basecaller) is answered by a handle of its own:
+ * pg_fit_create / _destroy /        (no counterpart)
+ * _last_error / _set_stream
+ * pg_fit_parse_model               a model file as `poregen transform` writes it -> levels in 1e-3 pA
+ * pg_fit_set_model / _submit /     per read sample = shift + scale * level over the basecaller's segmentation, then per k-mer how far
+ * _finish / _residuals / _pass_ms  its samples lie from the level the model claims
  */
 #ifndef PGMOVE_H
 #define PGMOVE_H
@@ -857,6 +865,75 @@ const char *pg_pool_refusal(const pg_pool *h, uint32_t group);
 pg_status pg_transform_model(const char *raw, size_t n, const char *A, const char *B, const char *C, const char *D, const char *stdv_from, size_t n_from,
                              char **out, size_t *n_out, char *err, size_t err_cap);
 void      pg_transform_free(char *text);
+
+/* ---- fit: a k-mer model scored against signal and move tables -------------------------------------------------------------------------------
+ * Input: batches laid out as pg_mvops_expand leaves them (every op a match, as many ops as bases), the signal as the collector takes it.
+ * For a read of Lb bases seq, ops n_0 .. n_{Lb-1} and query_start q, event e is the samples [q + n_0 + .. + n_{e-1}, .. + n_e). For
+ * i = 0 .. Lb - k the event e = i + sig_move_offset (if e < Lb) carries the k-mer seq[i, i + k) -- seq[Lb - i - k, Lb - i) with rna -- and
+ * counts when min_dur <= n_e <= max_dur, all its letters are ACGT and the model has a level for it. All device arithmetic is integer.
+ * Pass 1, per read, over the samples r (raw int16) of its counted events, l the event's level in 1e-3 pA: N = sum 1, SL = sum l,
+ * SLL = sum l^2, SR = sum r, SRL = sum r l, SRR = sum r^2 and E, the counted events (pg_fit_sums, exact). The host solves
+ * r = a + b l by least squares: den = N SLL - SL^2, numb = N SRL - SL SR, numa = SR SLL - SL SRL in 128-bit integers,
+ * b = (double)numb / (double)den, a = (double)numa / (double)den. Statuses, tested in this order: out_of_signal (q < 0 or the ops run
+ * past the read's samples), too_long (N > 2^24; only N and E are kept), few_events (E < min_events), flat (den = 0), negative_scale
+ * (numb <= 0). Pass 2, per k-mer, over the samples of the fitted reads: c = llrint(((double)r - a) * (1.0 / b)), d = c - l clamped to
+ * |d| <= 2^18 - 1; per slot (the k-mer's rank in ACGT order) the samples, the events, sum d and sum d^2, exact and independent of order.
+ * No CPU fallback: PG_ERR_NO_DEVICE without a GPU. */
+typedef struct pg_fit pg_fit;
+enum { PG_FIT_ST_OK = 0, PG_FIT_ST_OUT_OF_SIGNAL = 1, PG_FIT_ST_TOO_LONG = 2, PG_FIT_ST_FEW_EVENTS = 3, PG_FIT_ST_FLAT = 4, PG_FIT_ST_NEGATIVE_SCALE = 5,
+       PG_FIT_ST_SKIPPED = 16 };   /* PG_FIT_ST_SKIPPED + c: the caller's skip code c for the read (1 <= c < 2^16) */
+typedef struct {
+    uint32_t struct_size;          /* sizeof(pg_fit_params) */
+    uint32_t sig_move_offset;      /* -m            at most 64 */
+    uint32_t min_dur, max_dur;     /* --min_dur, --max_dur: min_dur <= max_dur <= 2^20 */
+    uint32_t min_events;           /* --min_events */
+    int32_t  rna;                  /* --rna */
+} pg_fit_params;
+typedef struct { int64_t n, sl, sll, sr, srl, srr, e; } pg_fit_sums; /* 56 bytes per read */
+typedef struct {                   /* the reads of one submit; arrays owned by the handle until its next submit / finish / destroy */
+    uint64_t n_reads;
+    const pg_fit_sums *sums;
+    const uint32_t *status;        /* PG_FIT_ST_* */
+    const double *a, *b;           /* 0 unless the status is PG_FIT_ST_OK */
+} pg_fit_reads;
+typedef struct {                   /* every submit since the last finish; arrays owned by the handle until its next submit / finish / destroy */
+    uint32_t kmer_size, reserved;
+    uint64_t n_slots;              /* 4^kmer_size */
+    const uint64_t *n_samples, *n_events; /* [n_slots] */
+    const int64_t  *sum_d;
+    const uint64_t *sum_dd_lo, *sum_dd_hi; /* sum d^2, low and high 64 bits */
+    uint64_t reads, fitted, events, samples, clamped; /* reads submitted and fitted; counted events and samples of the fitted reads; clamped samples */
+} pg_fit_result;
+pg_status pg_fit_create(const pg_fit_params *params, int32_t device, pg_fit **out);
+void      pg_fit_destroy(pg_fit *h);
+const char *pg_fit_last_error(const pg_fit *h); /* h may be NULL: error of the last failed pg_fit_create */
+/* levels: host uint32[4^kmer_size], the level of every slot in 1e-3 pA, 0 < level < 2^18, or 0 for a k-mer without one (its events are
+ * skipped); kmer_size 1 to 9. Not between a submit and the finish behind it (PG_ERR_STATE). */
+pg_status pg_fit_set_model(pg_fit *h, const uint32_t *levels, uint32_t kmer_size);
+/* One batch: both passes, and the solve between them; returns when the batch is done. The batch (PG_LOC_HOST or PG_LOC_DEVICE; digitisation,
+ * offset, range, target_start and target_end are not read) must carry PG_BATCH_ALL_MATCHES; one that holds an I, a D or an unknown op is
+ * refused with PG_ERR_INVALID_ARG (looked for on the device) and counts nothing, the handle stays usable. At most 2^28 samples of signal
+ * (PG_ERR_UNSUPPORTED beyond). skip: NULL, or host uint32[n_reads]: a read with skip != 0 takes no part and is reported with the status
+ * PG_FIT_ST_SKIPPED + skip (pg_mvops_result.status_host fits: the reads reform refuses). */
+pg_status pg_fit_submit(pg_fit *h, const pg_batch *batch, const uint32_t *skip, pg_fit_reads *out);
+/* The per-slot sums and the totals of every submit since the last finish; the handle is reset afterwards (the model stays). */
+pg_status pg_fit_finish(pg_fit *h, pg_fit_result *out);
+/* The kernels and copies of the following calls go to a caller-owned HIP stream (hipStream_t as void*); NULL restores the handle's own. */
+pg_status pg_fit_set_stream(pg_fit *h, void *hip_stream);
+/* HIP-event time of the two passes' kernels since create or the last call of this (either pointer may be NULL) */
+pg_status pg_fit_pass_ms(pg_fit *h, double *pass_one_ms, double *pass_two_ms);
+/* Host only, no device needed. A model file in the format `poregen transform` writes: '#' lines and the "kmer<TAB>..." header line are
+ * skipped, rows are KMER<TAB>level_mean<TAB>level_stdv (further fields ignored, level_stdv not used), all k-mers of one length 1 to 9
+ * (want_k != 0: that length), U read as T. levels_out (cap_slots >= 4^k entries) gets level_mean rounded to the nearest 1e-3 pA, halves up,
+ * exactly, on the decimal text; 0 for a k-mer the file does not hold. *uses_u (may be NULL): the file spells U. PG_ERR_INPUT: the model is
+ * refused as a whole -- a field that is no number, a level outside (0, 262.144) pA, a k-mer twice, a letter outside ACGTU, two lengths, no
+ * k-mer at all -- and err (err_cap bytes, may be NULL) names the line and the reason. */
+pg_status pg_fit_parse_model(const char *text, size_t n, uint32_t want_k, uint32_t *kmer_size_out, uint32_t *levels_out, size_t cap_slots, int32_t *uses_u,
+                             char *err, size_t err_cap);
+/* Host only. A slot's residuals from its sums, n_samples > 0, in 1e-3 pA: mean = floor((2 sum d + n) / (2 n)) and
+ * rms = (isqrt(floor(4 sum d^2 / n)) + 1) div 2, each the nearest unit with halves up. */
+pg_status pg_fit_residuals(uint64_t n_samples, int64_t sum_d, uint64_t sum_dd_lo, uint64_t sum_dd_hi, int64_t *mean, int64_t *rms);
+
 
 #ifdef __cplusplus
 }

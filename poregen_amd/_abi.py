@@ -35,6 +35,7 @@ PG_EVENTS_COL_MEAN_MEDIAN, PG_EVENTS_COL_MEAN_SSTDEV, PG_EVENTS_COL_SD_MEDIAN, P
 PG_MVOPS_RNA, PG_MVOPS_N_TO_T = 1, 2
 PG_MVOPS_ST_ACCEPTED, PG_MVOPS_ST_NO_MOVE_IN_TABLE, PG_MVOPS_ST_NEGATIVE_TAIL, PG_MVOPS_ST_BASES_LEFT_OVER, PG_MVOPS_ST_BAD_STRIDE = 0, 1, 2, 3, 4
 PG_MODEL_TEXT_MEDIAN, PG_MODEL_TEXT_SSTDEV, PG_MODEL_TEXT_DWELL = 0, 1, 2
+PG_FIT_ST_OK, PG_FIT_ST_OUT_OF_SIGNAL, PG_FIT_ST_TOO_LONG, PG_FIT_ST_FEW_EVENTS, PG_FIT_ST_FLAT, PG_FIT_ST_NEGATIVE_SCALE, PG_FIT_ST_SKIPPED = 0, 1, 2, 3, 4, 5, 16
 PG_POOL_NO_GROUP = 0xffffffff
 PG_POOL_MAX_LABELINGS = 16
 PG_POOL_GROUP_OK, PG_POOL_GROUP_EMPTY, PG_POOL_GROUP_REFUSED = 0, 1, 2
@@ -57,6 +58,8 @@ EXPORTS = [
     "pg_pool_create", "pg_pool_destroy", "pg_pool_last_error", "pg_pool_submit", "pg_pool_sync", "pg_pool_finish", "pg_pool_format", "pg_pool_refusal",
     "pg_transform_model", "pg_transform_free",
     "pg_mvops_create", "pg_mvops_destroy", "pg_mvops_last_error", "pg_mvops_piece", "pg_mvops_set_stream", "pg_mvops_stream", "pg_mvops_expand",
+    "pg_fit_create", "pg_fit_destroy", "pg_fit_last_error", "pg_fit_set_model", "pg_fit_submit", "pg_fit_finish", "pg_fit_set_stream", "pg_fit_pass_ms",
+    "pg_fit_parse_model", "pg_fit_residuals",
 ]
 PG_JOB_EXCHANGE_AUTO, PG_JOB_EXCHANGE_HOST, PG_JOB_EXCHANGE_RCCL = 0, 1, 2
 
@@ -177,6 +180,21 @@ class PgMvopsResult(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_ops", C.c_uint64), ("n_seq", C.c_uint64), ("n_refused", C.c_uint64), ("first_refused", C.c_int64),
                 ("op_n", C.c_void_p), ("op_t", C.c_void_p), ("op_off", C.c_void_p), ("query_start", C.c_void_p), ("target_start", C.c_void_p),
                 ("target_end", C.c_void_p), ("seq", C.c_void_p), ("seq_off", C.c_void_p), ("status", C.c_void_p), ("status_host", C.c_void_p)]
+
+
+class PgFitParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("sig_move_offset", C.c_uint32), ("min_dur", C.c_uint32), ("max_dur", C.c_uint32), ("min_events", C.c_uint32),
+                ("rna", C.c_int32)]
+
+
+class PgFitReads(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("sums", C.c_void_p), ("status", C.c_void_p), ("a", C.c_void_p), ("b", C.c_void_p)]
+
+
+class PgFitResult(C.Structure):
+    _fields_ = [("kmer_size", C.c_uint32), ("reserved", C.c_uint32), ("n_slots", C.c_uint64), ("n_samples", C.c_void_p), ("n_events", C.c_void_p),
+                ("sum_d", C.c_void_p), ("sum_dd_lo", C.c_void_p), ("sum_dd_hi", C.c_void_p), ("reads", C.c_uint64), ("fitted", C.c_uint64),
+                ("events", C.c_uint64), ("samples", C.c_uint64), ("clamped", C.c_uint64)]
 
 
 _lib = None
@@ -329,5 +347,16 @@ def load():
     lib.pg_mvops_set_stream.argtypes = [vp, vp]; lib.pg_mvops_set_stream.restype = i32
     lib.pg_mvops_stream.argtypes = [vp]; lib.pg_mvops_stream.restype = vp
     lib.pg_mvops_expand.argtypes = [vp, C.POINTER(PgMvopsBatch), C.POINTER(PgMvopsResult)]; lib.pg_mvops_expand.restype = i32
+    if hasattr(lib, "pg_fit_create"):  # (as above: a library built from an older tree has no fit handle)
+        lib.pg_fit_create.argtypes = [C.POINTER(PgFitParams), i32, C.POINTER(vp)]; lib.pg_fit_create.restype = i32
+        lib.pg_fit_destroy.argtypes = [vp]; lib.pg_fit_destroy.restype = None
+        lib.pg_fit_last_error.argtypes = [vp]; lib.pg_fit_last_error.restype = C.c_char_p
+        lib.pg_fit_set_model.argtypes = [vp, vp, u32]; lib.pg_fit_set_model.restype = i32
+        lib.pg_fit_submit.argtypes = [vp, C.POINTER(PgBatch), vp, C.POINTER(PgFitReads)]; lib.pg_fit_submit.restype = i32
+        lib.pg_fit_finish.argtypes = [vp, C.POINTER(PgFitResult)]; lib.pg_fit_finish.restype = i32
+        lib.pg_fit_set_stream.argtypes = [vp, vp]; lib.pg_fit_set_stream.restype = i32
+        lib.pg_fit_pass_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]; lib.pg_fit_pass_ms.restype = i32
+        lib.pg_fit_parse_model.argtypes = [C.c_char_p, C.c_size_t, u32, C.POINTER(u32), vp, C.c_size_t, C.POINTER(i32), C.c_char_p, C.c_size_t]; lib.pg_fit_parse_model.restype = i32
+        lib.pg_fit_residuals.argtypes = [C.c_uint64, C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]; lib.pg_fit_residuals.restype = i32
     _lib = lib
     return lib

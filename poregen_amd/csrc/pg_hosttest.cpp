@@ -550,3 +550,45 @@ extern "C" int pgt_evstat(const int64_t *units, uint64_t n, int64_t *m, int64_t 
 extern "C" void pgt_evstat_many(const int64_t *units, const uint64_t *off, uint64_t n_events, int64_t *m, int64_t *s, int32_t *code) {
     for (uint64_t e = 0; e < n_events; e++) code[e] = pgt_evstat(units + off[e], off[e + 1] - off[e], m + e, s + e);
 }
+
+// ---- fit (pg_fit.h): the model parser, the walk of one read, the solve and the text rules, run on the host ------------------------------
+#include "pg_fit.h"
+extern "C" void pgt_fit_levels(uint64_t *out8) {
+    out8[0] = PG_FIT_STEP; out8[1] = PG_FIT_PIECE; out8[2] = PG_FIT_THREADS; out8[3] = PG_FIT_LDS_K; out8[4] = PG_FIT_GRID; out8[5] = (uint64_t)PG_FIT_MAX_N;
+    out8[6] = PG_FIT_MAX_LEVEL; out8[7] = (uint64_t)PG_FIT_CLAMP;
+}
+// 0 and k, levels (cap_slots entries), uses_u; or -1 with the reason in err
+extern "C" int pgt_fit_parse_model(const char *text, size_t n, uint32_t want_k, uint32_t *k, uint32_t *levels, size_t cap_slots, int *uses_u, char *err, size_t ecap) {
+    PgFitModel md; std::string why;
+    if (!pg_fit_parse_model_text(text, n, want_k, md, why) || md.levels.size() > cap_slots) { snprintf(err, ecap, "%s", why.c_str()); return -1; }
+    memcpy(levels, md.levels.data(), md.levels.size() * sizeof(uint32_t));
+    *k = md.k; *uses_u = md.uses_u ? 1 : 0;
+    return 0;
+}
+// the counted events of one read (first sample, samples, slot: up to cap of them) and its seven sums; -1: out_of_signal
+extern "C" long pgt_fit_walk(const uint8_t *seq, uint32_t lb, const uint32_t *op_n, int64_t q, const int16_t *sig, uint64_t n_sig, const uint32_t *levels, uint32_t k, uint32_t m,
+                             int rna, uint32_t min_dur, uint32_t max_dur, uint64_t *ev_start, uint32_t *ev_n, int32_t *ev_slot, size_t cap, int64_t *sums7) {
+    std::vector<PgFitEvent> ev; PgFitSums s;
+    if (!pg_fit_walk_host(seq, lb, op_n, q, sig, n_sig, levels, k, m, rna != 0, min_dur, max_dur, ev, s)) return -1;
+    for (size_t i = 0; i < ev.size() && i < cap; i++) { ev_start[i] = ev[i].start; ev_n[i] = ev[i].n; ev_slot[i] = ev[i].slot; }
+    memcpy(sums7, &s, sizeof s);
+    return (long)ev.size();
+}
+// the status; a, b and 1 / b as they go to the device; shift, scale and rms as the per-read table prints them ("%.6f"), 64 bytes each
+extern "C" int pgt_fit_solve(const int64_t *sums7, uint32_t min_events, double dig, double off, double range, double *ab3, char *text3) {
+    PgFitSums s; memcpy(&s, sums7, sizeof s);
+    const PgFitSolve v = pg_fit_solve(s, min_events);
+    ab3[0] = v.a; ab3[1] = v.b; ab3[2] = v.inv_b;
+    text3[0] = text3[64] = text3[128] = 0;
+    if (v.status == PG_FIT_OK) {
+        long double rep[3]; pg_fit_report(s, dig, off, range, rep);
+        for (int i = 0; i < 3; i++) snprintf(text3 + 64 * i, 64, "%.6Lf", rep[i]);
+    }
+    return (int)v.status;
+}
+extern "C" int pgt_fit_resid(int r, double a, double inv_b, int l, int *clamped) { bool c; const int32_t d = pg_fit_resid(r, a, inv_b, l, c); *clamped = c; return d; }
+// the two residual columns of a slot as the k-mer table prints them
+extern "C" void pgt_fit_resid_text(uint64_t n, int64_t sum_d, uint64_t dd_lo, uint64_t dd_hi, char *mean, char *rms, size_t cap) {
+    int64_t m, q; pg_fit_slot_resid(n, sum_d, dd_lo, dd_hi, m, q);
+    snprintf(mean, cap, "%s", pg_fit_units_text(m).c_str()); snprintf(rms, cap, "%s", pg_fit_units_text(q).c_str());
+}

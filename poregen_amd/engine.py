@@ -1606,3 +1606,166 @@ def reform_ops(mv, mv_off, stride, ns, ts, l_seq, flag, seq_bytes, byte_off, rna
         return out
     finally:
         ex.close()
+
+
+# ---- fit: a k-mer model scored against signal and move tables (pg_fit_*) --------------------------------------------------------------
+
+FIT_STATUS_NAMES = {0: "ok", 1: "out_of_signal", 2: "too_long", 3: "few_events", 4: "flat", 5: "negative_scale",
+                    17: "no_move_in_table", 18: "negative_tail", 19: "bases_left_over", 20: "bad_stride"}
+
+
+def units_text(v: int) -> str:
+    """An integer of 1e-3 pA with three decimals, as the k-mer table prints it."""
+    v = int(v)
+    return f"{'-' if v < 0 else ''}{abs(v) // 1000}.{abs(v) % 1000:03d}"
+
+
+def parse_fit_model(text, k: int = 0):
+    """(k, levels uint32[4^k] in 1e-3 pA with 0 for a missing k-mer, uses_u) of a model file in the format `poregen transform` writes
+    (pg_fit_parse_model; no GPU needed). PgError with PG_ERR_INPUT when the model is refused."""
+    lib = _abi.load()
+    data = text.encode() if isinstance(text, str) else bytes(text)
+    levels = np.zeros(4 ** 9, np.uint32)
+    kk, uu, err = C.c_uint32(), C.c_int32(), C.create_string_buffer(400)
+    st = lib.pg_fit_parse_model(data, len(data), k, C.byref(kk), levels.ctypes.data, levels.size, C.byref(uu), err, len(err))
+    if st != 0:
+        raise PgError(st, err.value.decode())
+    return int(kk.value), levels[:4 ** kk.value].copy(), bool(uu.value)
+
+
+@dataclass
+class FitReads:
+    """One submit: per read the seven sums (int64[n, 7]: N, SL, SLL, SR, SRL, SRR, E), the status and the fit sample = a + b * level."""
+    sums: np.ndarray
+    status: np.ndarray
+    a: np.ndarray
+    b: np.ndarray
+
+
+@dataclass
+class FitResult:
+    """Everything since the last finish: per slot (k-mer rank in ACGT order) samples, events, sum d and sum d^2 (Python ints), the totals."""
+    kmer_size: int
+    n_samples: np.ndarray
+    n_events: np.ndarray
+    sum_d: np.ndarray
+    sum_dd: list
+    reads: int
+    fitted: int
+    events: int
+    samples: int
+    clamped: int
+
+    def residuals(self, slot: int):
+        """(mean_resid, rms_resid) of a slot in 1e-3 pA, None when it has no sample (pg_fit_residuals)."""
+        n = int(self.n_samples[slot])
+        if not n:
+            return None
+        return _fit_residuals(n, int(self.sum_d[slot]), self.sum_dd[slot])
+
+    def pooled_rms(self):
+        return _fit_residuals(self.samples, 0, sum(self.sum_dd))[1] if self.samples else None
+
+    def kmer_table(self, levels, uses_u: bool = False) -> str:
+        rows = []
+        for s, kmer in enumerate(generate_kmers(self.kmer_size, rna=uses_u)):
+            r = self.residuals(s)
+            rows.append("\t".join([kmer, str(int(self.n_samples[s])), str(int(self.n_events[s])), units_text(levels[s]) if levels[s] else "",
+                                   units_text(r[0]) if r else "", units_text(r[1]) if r else ""]) + "\n")
+        return "".join(rows)
+
+
+def _fit_residuals(n, sum_d, sum_dd):
+    lib = _abi.load()
+    m, q = C.c_int64(), C.c_int64()
+    st = lib.pg_fit_residuals(n, sum_d, sum_dd & 0xffffffffffffffff, sum_dd >> 64, C.byref(m), C.byref(q))
+    if st != 0:
+        raise PgError(st, "pg_fit_residuals: sums out of range")
+    return int(m.value), int(q.value)
+
+
+class ModelFit:
+    """Scores a k-mer model against batches laid out as MoveExpander leaves them (pg_fit_*): submit() fits every read, finish() returns the
+    per-k-mer residual sums. levels: uint32[4^k] in 1e-3 pA, 0 for a k-mer without a level."""
+
+    def __init__(self, levels, k: int, sig_move_offset: int = 0, rna: bool = False, min_dur: int = 5, max_dur: int = 70, min_events: int = 20, device: int = 0):
+        self._lib = _abi.load()
+        self.device, self._h = device, None
+        p = _abi.PgFitParams(C.sizeof(_abi.PgFitParams), sig_move_offset, min_dur, max_dur, min_events, int(rna))
+        h = C.c_void_p()
+        st = self._lib.pg_fit_create(C.byref(p), device, C.byref(h))
+        if st != 0:
+            raise PgError(st, self._lib.pg_fit_last_error(None).decode())
+        self._h = h
+        self.set_model(levels, k)
+
+    def _check(self, st):
+        if st != 0:
+            raise PgError(st, self._lib.pg_fit_last_error(self._h).decode())
+
+    def set_model(self, levels, k: int):
+        lv = np.ascontiguousarray(levels, dtype=np.uint32)
+        if lv.size != 4 ** k:
+            raise ValueError("levels needs 4^k entries")
+        self._check(self._lib.pg_fit_set_model(self._h, lv.ctypes.data, k))
+        self.kmer_size = k
+
+    def set_stream(self, stream=None):
+        """Run on a caller-owned stream (a torch.cuda.Stream or a raw hipStream_t value); None: the handle's own."""
+        ptr = None if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
+        self._check(self._lib.pg_fit_set_stream(self._h, ptr))
+
+    def submit(self, batch: "Batch", skip=None) -> FitReads:
+        """One batch (host or device) with all_matches set: the caller vouches that it holds match ops only, the device verifies it; a
+        batch without the flag is refused (PG_ERR_INVALID_ARG). skip: per read a code, non-zero = the read takes no part."""
+        cb = _c_batch(batch)
+        sk = None if skip is None else np.ascontiguousarray(skip, dtype=np.uint32)
+        out = _abi.PgFitReads()
+        self._check(self._lib.pg_fit_submit(self._h, C.byref(cb), None if sk is None else sk.ctypes.data, C.byref(out)))
+        n = int(out.n_reads)
+
+        def arr(ptr, count, dt):
+            if not count or not ptr:
+                return np.zeros(0, dt)
+            return np.frombuffer((C.c_char * (count * np.dtype(dt).itemsize)).from_address(ptr), dtype=dt).copy()
+        return FitReads(sums=arr(out.sums, 7 * n, np.int64).reshape(n, 7), status=arr(out.status, n, np.uint32), a=arr(out.a, n, np.float64), b=arr(out.b, n, np.float64))
+
+    def finish(self) -> FitResult:
+        r = _abi.PgFitResult()
+        self._check(self._lib.pg_fit_finish(self._h, C.byref(r)))
+        ns = int(r.n_slots)
+
+        def arr(ptr, dt):
+            return np.frombuffer((C.c_char * (ns * 8)).from_address(ptr), dtype=dt).copy()
+        lo, hi = arr(r.sum_dd_lo, np.uint64), arr(r.sum_dd_hi, np.uint64)
+        return FitResult(kmer_size=int(r.kmer_size), n_samples=arr(r.n_samples, np.uint64), n_events=arr(r.n_events, np.uint64), sum_d=arr(r.sum_d, np.int64),
+                         sum_dd=[(int(h) << 64) | int(l) for l, h in zip(lo, hi)], reads=int(r.reads), fitted=int(r.fitted), events=int(r.events),
+                         samples=int(r.samples), clamped=int(r.clamped))
+
+    def pass_ms(self):
+        """HIP-event time of pass 1 and of pass 2 since the last call."""
+        a, b = C.c_double(), C.c_double()
+        self._check(self._lib.pg_fit_pass_ms(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.pg_fit_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def fit_model(model_text, batches, k: int = 0, sig_move_offset: int = 0, rna: bool = False, min_dur: int = 5, max_dur: int = 70, min_events: int = 20, device: int = 0):
+    """One-shot: parse the model, submit every batch, finish. Returns ([FitReads per batch], FitResult, levels, uses_u)."""
+    kk, levels, uses_u = parse_fit_model(model_text, k)
+    mf = ModelFit(levels, kk, sig_move_offset=sig_move_offset, rna=rna, min_dur=min_dur, max_dur=max_dur, min_events=min_events, device=device)
+    try:
+        reads = [mf.submit(b) for b in batches]
+        return reads, mf.finish(), levels, uses_u
+    finally:
+        mf.close()
