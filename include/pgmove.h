@@ -106,6 +106,12 @@
  * pg_fit_parse_model               a model file as `poregen transform` writes it -> levels in 1e-3 pA
  * pg_fit_set_model / _submit /     per read sample = shift + scale * level over the basecaller's segmentation, then per k-mer how far
  * _finish / _residuals / _pass_ms  its samples lie from the level the model claims
+ *
+ * The reference's `realign` command (src/main.c; src/realign.cpp is a copy of reform that aligns nothing) is a handle that does align:
+ * pg_realign_create / _destroy /   (no counterpart)
+ * _last_error / _set_stream
+ * pg_realign_set_model / _submit / the move table's boundaries moved within a band to where the samples fit the model's levels best
+ * _kernel_ms / _walk
  */
 #ifndef PGMOVE_H
 #define PGMOVE_H
@@ -933,6 +939,60 @@ pg_status pg_fit_parse_model(const char *text, size_t n, uint32_t want_k, uint32
 /* Host only. A slot's residuals from its sums, n_samples > 0, in 1e-3 pA: mean = floor((2 sum d + n) / (2 n)) and
  * rms = (isqrt(floor(4 sum d^2 / n)) + 1) div 2, each the nearest unit with halves up. */
 pg_status pg_fit_residuals(uint64_t n_samples, int64_t sum_d, uint64_t sum_dd_lo, uint64_t sum_dd_hi, int64_t *mean, int64_t *rms);
+
+/* ---- realign: the boundaries of the move table refined against a k-mer model ----------------------------------------------------------------
+ * The move table puts every event boundary on a multiple of the stride; this moves each by up to `band` samples to where the samples fit
+ * the model's levels best. Input: a batch as pg_fit_submit takes it, and per read the status, a and b that pg_fit_submit returned for this
+ * same batch under the same model, sig_move_offset, rna, min_dur and max_dur. Only reads with PG_FIT_ST_OK are refined; every other read
+ * keeps its ops and reports zeros. With B_0 = query_start and B_e = B_{e-1} + n_{e-1}, event e is refinable iff it counts by fit's rule
+ * (level l_e); boundary e, 0 < e < Lb, is free iff events e - 1 and e are both refinable and e % 256 != 0; every other boundary is pinned,
+ * B_0 and B_Lb included. A sample r under level l costs d^2, d fit's pass-2 residual (c = llrint(((double)r - a) * (1.0 / b)), d = c - l
+ * clamped to |d| <= 2^18 - 1). Per maximal run of free boundaries e0 < e < e1 between the pinned P0 = B_e0 and P1 = B_e1 a dynamic program
+ * runs over the candidates p = B_e + j, |j| <= band, that are admissible (P0 + (e - e0) min_len <= p <= P1 - (e1 - e) min_len):
+ * D[e0][P0] = 0, D[e][p] = min over reachable admissible p' with p' + min_len <= p of D[e-1][p'] + cost of event e - 1 on [p', p), a tie
+ * taking the smallest p'; the new boundaries are traced back from P1. The original boundaries are always a solution, so
+ * cost_after <= cost_before. All of it is integer arithmetic behind the residual: results do not depend on the device's scheduling.
+ * No CPU fallback: PG_ERR_NO_DEVICE without a GPU (pg_realign_walk is the rule on the host, for tests). */
+typedef struct pg_realign pg_realign;
+typedef struct {
+    uint32_t struct_size;          /* sizeof(pg_realign_params) */
+    uint32_t sig_move_offset;      /* -m            at most 64 */
+    uint32_t min_dur, max_dur;     /* --min_dur, --max_dur: min_dur <= max_dur <= 4096 */
+    int32_t  rna;                  /* --rna */
+    uint32_t band;                 /* --band        0 .. 31 */
+    uint32_t min_len;              /* --min_len     1 .. min_dur: the fewest samples a refined event keeps */
+    uint32_t reserved;
+} pg_realign_params;
+typedef struct {                   /* one read; the costs are sums of d^2 over its refinable events under the old and the new boundaries */
+    uint32_t n_free, n_moved;      /* free boundaries; those that moved */
+    uint64_t sum_abs_shift;        /* sum of |new - old| over the free boundaries, in samples */
+    uint64_t cost_before_lo, cost_before_hi, cost_after_lo, cost_after_hi; /* low and high 64 bits */
+} pg_realign_read;
+typedef struct {                   /* one submit; arrays owned by the handle until its next submit / destroy */
+    uint32_t struct_size;          /* sizeof(pg_realign_reads), set by the caller */
+    uint32_t reserved;
+    uint64_t n_reads, n_ops;
+    const uint32_t *op_n;          /* DEVICE memory, laid out exactly as the batch's op_n: a pg_batch may point at it */
+    const pg_realign_read *reads;  /* host [n_reads] */
+} pg_realign_reads;
+pg_status pg_realign_create(const pg_realign_params *params, int32_t device, pg_realign **out);
+void      pg_realign_destroy(pg_realign *h);
+const char *pg_realign_last_error(const pg_realign *h); /* h may be NULL: error of the last failed pg_realign_create */
+/* levels and kmer_size as pg_fit_set_model takes them */
+pg_status pg_realign_set_model(pg_realign *h, const uint32_t *levels, uint32_t kmer_size);
+/* The kernels and copies of the following calls go to a caller-owned HIP stream (hipStream_t as void*); NULL restores the handle's own. */
+pg_status pg_realign_set_stream(pg_realign *h, void *hip_stream);
+/* One batch, synchronous. The batch as pg_fit_submit takes it (PG_BATCH_ALL_MATCHES; an I, a D or an unknown op: PG_ERR_INVALID_ARG, the
+ * handle stays usable; at most 2^28 samples). status, a, b: host arrays [n_reads] of pg_fit_reads. A read with PG_FIT_ST_OK whose ops leave
+ * its samples, or whose a or b is no fit's (b not a finite positive number), fails the batch with PG_ERR_INVALID_ARG before any kernel
+ * indexes the signal. */
+pg_status pg_realign_submit(pg_realign *h, const pg_batch *batch, const uint32_t *status, const double *a, const double *b, pg_realign_reads *out);
+/* HIP-event time of the alignment kernel since create or the last call of this */
+pg_status pg_realign_kernel_ms(pg_realign *h, double *ms);
+/* Host only, no device needed: the rule for one fitted read, the recurrence over all pairs of candidates as stated above. seq: lb bases,
+ * op_n: lb ops, sig: the read's n_sig samples. op_out[lb] gets the refined ops. PG_ERR_INPUT: the ops leave the samples. */
+pg_status pg_realign_walk(const pg_realign_params *params, const uint32_t *levels, uint32_t kmer_size, const uint8_t *seq, uint32_t lb, const uint32_t *op_n, int64_t query_start,
+                          const int16_t *sig, uint64_t n_sig, double a, double b, uint32_t *op_out, pg_realign_read *out);
 
 
 #ifdef __cplusplus

@@ -60,6 +60,8 @@ EXPORTS = [
     "pg_mvops_create", "pg_mvops_destroy", "pg_mvops_last_error", "pg_mvops_piece", "pg_mvops_set_stream", "pg_mvops_stream", "pg_mvops_expand",
     "pg_fit_create", "pg_fit_destroy", "pg_fit_last_error", "pg_fit_set_model", "pg_fit_submit", "pg_fit_finish", "pg_fit_set_stream", "pg_fit_pass_ms",
     "pg_fit_parse_model", "pg_fit_residuals",
+    "pg_realign_create", "pg_realign_destroy", "pg_realign_last_error", "pg_realign_set_model", "pg_realign_set_stream", "pg_realign_submit", "pg_realign_kernel_ms",
+    "pg_realign_walk",
 ]
 PG_JOB_EXCHANGE_AUTO, PG_JOB_EXCHANGE_HOST, PG_JOB_EXCHANGE_RCCL = 0, 1, 2
 
@@ -195,6 +197,20 @@ class PgFitResult(C.Structure):
     _fields_ = [("kmer_size", C.c_uint32), ("reserved", C.c_uint32), ("n_slots", C.c_uint64), ("n_samples", C.c_void_p), ("n_events", C.c_void_p),
                 ("sum_d", C.c_void_p), ("sum_dd_lo", C.c_void_p), ("sum_dd_hi", C.c_void_p), ("reads", C.c_uint64), ("fitted", C.c_uint64),
                 ("events", C.c_uint64), ("samples", C.c_uint64), ("clamped", C.c_uint64)]
+
+
+class PgRealignParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("sig_move_offset", C.c_uint32), ("min_dur", C.c_uint32), ("max_dur", C.c_uint32), ("rna", C.c_int32),
+                ("band", C.c_uint32), ("min_len", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PgRealignRead(C.Structure):
+    _fields_ = [("n_free", C.c_uint32), ("n_moved", C.c_uint32), ("sum_abs_shift", C.c_uint64), ("cost_before_lo", C.c_uint64), ("cost_before_hi", C.c_uint64),
+                ("cost_after_lo", C.c_uint64), ("cost_after_hi", C.c_uint64)]
+
+
+class PgRealignReads(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("n_reads", C.c_uint64), ("n_ops", C.c_uint64), ("op_n", C.c_void_p), ("reads", C.c_void_p)]
 
 
 _lib = None
@@ -358,5 +374,15 @@ def load():
         lib.pg_fit_pass_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]; lib.pg_fit_pass_ms.restype = i32
         lib.pg_fit_parse_model.argtypes = [C.c_char_p, C.c_size_t, u32, C.POINTER(u32), vp, C.c_size_t, C.POINTER(i32), C.c_char_p, C.c_size_t]; lib.pg_fit_parse_model.restype = i32
         lib.pg_fit_residuals.argtypes = [C.c_uint64, C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]; lib.pg_fit_residuals.restype = i32
+    if hasattr(lib, "pg_realign_create"):  # (as above: a library built from an older tree has no realign handle)
+        lib.pg_realign_create.argtypes = [C.POINTER(PgRealignParams), i32, C.POINTER(vp)]; lib.pg_realign_create.restype = i32
+        lib.pg_realign_destroy.argtypes = [vp]; lib.pg_realign_destroy.restype = None
+        lib.pg_realign_last_error.argtypes = [vp]; lib.pg_realign_last_error.restype = C.c_char_p
+        lib.pg_realign_set_model.argtypes = [vp, vp, u32]; lib.pg_realign_set_model.restype = i32
+        lib.pg_realign_set_stream.argtypes = [vp, vp]; lib.pg_realign_set_stream.restype = i32
+        lib.pg_realign_submit.argtypes = [vp, C.POINTER(PgBatch), vp, vp, vp, C.POINTER(PgRealignReads)]; lib.pg_realign_submit.restype = i32
+        lib.pg_realign_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]; lib.pg_realign_kernel_ms.restype = i32
+        lib.pg_realign_walk.argtypes = [C.POINTER(PgRealignParams), vp, u32, vp, u32, vp, C.c_int64, vp, C.c_uint64, C.c_double, C.c_double, vp, C.POINTER(PgRealignRead)]
+        lib.pg_realign_walk.restype = i32
     _lib = lib
     return lib

@@ -592,3 +592,17 @@ extern "C" void pgt_fit_resid_text(uint64_t n, int64_t sum_d, uint64_t dd_lo, ui
     int64_t m, q; pg_fit_slot_resid(n, sum_d, dd_lo, dd_hi, m, q);
     snprintf(mean, cap, "%s", pg_fit_units_text(m).c_str()); snprintf(rms, cap, "%s", pg_fit_units_text(q).c_str());
 }
+
+// ---- realign (pg_realign.h): the rule for one fitted read, run on the host ------------------------------------------------------------------
+#include "pg_realign.h"
+extern "C" void pgt_realign_levels(uint64_t *out3) { out3[0] = PG_RL_MAX_BAND; out3[1] = PG_RL_MAX_DUR; out3[2] = PG_FIT_PIECE; }
+extern "C" int pgt_realign_params_ok(uint32_t band, uint32_t min_len, uint32_t min_dur, uint32_t max_dur) { return pg_rl_params_ok(band, min_len, min_dur, max_dur) ? 1 : 0; }
+// 0 and the refined ops (lb of them), out7 = n_free, n_moved, sum_abs_shift, cost_before lo / hi, cost_after lo / hi; -1: out_of_signal
+extern "C" int pgt_realign_walk(const uint8_t *seq, uint32_t lb, const uint32_t *op_n, int64_t q, const int16_t *sig, uint64_t n_sig, const uint32_t *levels, uint32_t k, uint32_t m,
+                                int rna, uint32_t min_dur, uint32_t max_dur, uint32_t band, uint32_t min_len, double a, double b, uint32_t *op_out, uint64_t *out7) {
+    PgRlRead r;
+    if (!pg_rl_walk_host(seq, lb, op_n, q, sig, n_sig, levels, k, m, rna != 0, min_dur, max_dur, band, min_len, a, b, op_out, r)) return -1;
+    out7[0] = r.n_free; out7[1] = r.n_moved; out7[2] = r.sum_abs_shift; out7[3] = (uint64_t)r.cost_before; out7[4] = (uint64_t)(r.cost_before >> 64);
+    out7[5] = (uint64_t)r.cost_after; out7[6] = (uint64_t)(r.cost_after >> 64);
+    return 0;
+}

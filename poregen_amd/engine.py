@@ -1769,3 +1769,127 @@ def fit_model(model_text, batches, k: int = 0, sig_move_offset: int = 0, rna: bo
         return reads, mf.finish(), levels, uses_u
     finally:
         mf.close()
+
+
+# ---- realign: the move table's boundaries refined against a k-mer model (pg_realign_*) ---------------------------------------------------
+
+@dataclass
+class RealignReads:
+    """One submit: op_n, the refined ops laid out as the batch's op_n (a torch uint32-as-int32 CUDA tensor; to_host() gives numpy uint32),
+    and per read n_free, n_moved, sum_abs_shift (numpy) and cost_before / cost_after (lists of Python ints, 128 bits)."""
+    op_n: object
+    n_free: np.ndarray
+    n_moved: np.ndarray
+    sum_abs_shift: np.ndarray
+    cost_before: list
+    cost_after: list
+
+    def to_host(self) -> np.ndarray:
+        return self.op_n.cpu().numpy().view(np.uint32)
+
+
+def _realign_params(sig_move_offset, rna, min_dur, max_dur, band, min_len):
+    return _abi.PgRealignParams(C.sizeof(_abi.PgRealignParams), sig_move_offset, min_dur, max_dur, int(rna), band, min_len, 0)
+
+
+class Realigner:
+    """Refines the ops of batches laid out as MoveExpander leaves them against a k-mer model (pg_realign_*). submit(batch, fit_reads) takes
+    the FitReads that ModelFit.submit returned for the same batch under the same model and parameters; only the reads it fitted move."""
+
+    def __init__(self, levels, k: int, sig_move_offset: int = 0, rna: bool = False, min_dur: int = 5, max_dur: int = 70, band: int = 10, min_len: int = 3, device: int = 0):
+        self._lib = _abi.load()
+        self.device, self._h = device, None
+        p = _realign_params(sig_move_offset, rna, min_dur, max_dur, band, min_len)
+        h = C.c_void_p()
+        st = self._lib.pg_realign_create(C.byref(p), device, C.byref(h))
+        if st != 0:
+            raise PgError(st, self._lib.pg_realign_last_error(None).decode())
+        self._h = h
+        lv = np.ascontiguousarray(levels, dtype=np.uint32)
+        if lv.size != 4 ** k:
+            raise ValueError("levels needs 4^k entries")
+        self._check(self._lib.pg_realign_set_model(self._h, lv.ctypes.data, k))
+        self.kmer_size = k
+
+    def _check(self, st):
+        if st != 0:
+            raise PgError(st, self._lib.pg_realign_last_error(self._h).decode())
+
+    def set_stream(self, stream=None):
+        """Run on a caller-owned stream (a torch.cuda.Stream or a raw hipStream_t value); None: the handle's own."""
+        ptr = None if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
+        self._check(self._lib.pg_realign_set_stream(self._h, ptr))
+
+    def submit(self, batch: "Batch", fit_reads) -> RealignReads:
+        import torch
+        cb = _c_batch(batch)
+        st = np.ascontiguousarray(fit_reads.status, dtype=np.uint32)
+        a = np.ascontiguousarray(fit_reads.a, dtype=np.float64)
+        b = np.ascontiguousarray(fit_reads.b, dtype=np.float64)
+        if not (st.size == a.size == b.size == batch.n_reads):
+            raise ValueError("fit_reads is of another batch")
+        out = _abi.PgRealignReads()
+        out.struct_size = C.sizeof(_abi.PgRealignReads)
+        self._check(self._lib.pg_realign_submit(self._h, C.byref(cb), st.ctypes.data, a.ctypes.data, b.ctypes.data, C.byref(out)))
+        n, n_ops = int(out.n_reads), int(out.n_ops)
+        rd = np.frombuffer((C.c_char * (n * C.sizeof(_abi.PgRealignRead))).from_address(out.reads), dtype=np.uint64).reshape(n, 6).copy() if n else np.zeros((0, 6), np.uint64)
+        dev = torch.device("cuda", self.device)
+        if n_ops:  # the handle's buffer lives until its next submit: the caller gets a copy (the submit is complete, the clone synchronised)
+            class _Alias:
+                __cuda_array_interface__ = {"shape": (n_ops,), "typestr": "<i4", "data": (int(out.op_n), False), "version": 2}
+            op = torch.as_tensor(_Alias(), device=dev).clone()
+            torch.cuda.current_stream(dev).synchronize()
+        else:
+            op = torch.empty(0, dtype=torch.int32, device=dev)
+        return RealignReads(op_n=op, n_free=(rd[:, 0] & 0xffffffff).astype(np.uint32), n_moved=(rd[:, 0] >> 32).astype(np.uint32), sum_abs_shift=rd[:, 1].copy(),
+                            cost_before=[(int(h) << 64) | int(l) for l, h in zip(rd[:, 2], rd[:, 3])], cost_after=[(int(h) << 64) | int(l) for l, h in zip(rd[:, 4], rd[:, 5])])
+
+    def kernel_ms(self) -> float:
+        """HIP-event time of the alignment kernel since the last call."""
+        ms = C.c_double()
+        self._check(self._lib.pg_realign_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.pg_realign_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def realign_ops(levels, k: int, batch: "Batch", fit_reads, **kw):
+    """One-shot Realigner.submit: (refined ops as numpy uint32, RealignReads)."""
+    with Realigner(levels, k, **kw) as ra:
+        r = ra.submit(batch, fit_reads)
+        return r.to_host(), r
+
+
+def realign_walk(levels, k: int, seq, ops, q: int, sig, a: float, b: float, sig_move_offset: int = 0, rna: bool = False, min_dur: int = 5, max_dur: int = 70, band: int = 10,
+                 min_len: int = 3):
+    """The rule for one fitted read on the host (pg_realign_walk; no GPU needed): (refined ops, n_free, n_moved, sum_abs_shift, cost_before,
+    cost_after), or None when the ops leave the samples."""
+    lib = _abi.load()
+    p = _realign_params(sig_move_offset, rna, min_dur, max_dur, band, min_len)
+    lv = np.ascontiguousarray(levels, dtype=np.uint32)
+    s = np.frombuffer(seq.encode() if isinstance(seq, str) else bytes(seq), np.uint8)
+    o = np.ascontiguousarray(ops, dtype=np.uint32)
+    sg = np.ascontiguousarray(sig, dtype=np.int16)
+    new = np.zeros(o.size, np.uint32)
+    rd = _abi.PgRealignRead()
+    st = lib.pg_realign_walk(C.byref(p), lv.ctypes.data, k, s.ctypes.data, o.size, o.ctypes.data, q, sg.ctypes.data, sg.size, a, b, new.ctypes.data, C.byref(rd))
+    if st == _abi.PG_ERR_INPUT:
+        return None
+    if st != 0:
+        raise PgError(st, "pg_realign_walk: bad argument")
+    return new, rd.n_free, rd.n_moved, rd.sum_abs_shift, (rd.cost_before_hi << 64) | rd.cost_before_lo, (rd.cost_after_hi << 64) | rd.cost_after_lo
