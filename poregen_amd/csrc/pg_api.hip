@@ -102,6 +102,7 @@ struct pg_ctx {
     // next batch is expected to want (host batches: counted from sig_off; device batches: what the last settled batch wanted, at least 256)
     PgDev<> long_tab, long_hist; uint32_t long_cap = 0, long_use = 0, long_want = 256; uint64_t long_reads_split = 0, long_helpers_short = 0;
     uint64_t gather_forms[PG_GATHER_FORMS] = {0, 0, 0, 0, 0}; // launches of the chunked gather by the kernel taken (pg_gather_form), for pg_kernel_stats
+    uint64_t sort_scatters = 0; // k_sort_scatter launches queued = passes of the LSD radix sort (the "sort_events" bracket counts once per batch), for pg_kernel_stats
 
     PgDevBatch B{};       // current batch (device view)
     bool have_count = false, have_batch_result = false, downloaded = true;
@@ -876,7 +877,7 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
         }
     } else {
         prof_begin(c, "sort_events", c->st, true);
-        if (N) PG_HIP_TRY(c, pg_launch_sort_events(c->st, O.ev_slot, N, c->key_bits, S, &c->sorted_idx));
+        if (N) PG_HIP_TRY(c, pg_launch_sort_events(c->st, O.ev_slot, N, c->key_bits, S, &c->sorted_idx, &c->sort_scatters));
         else { c->sorted_idx = 0; PG_HIP_TRY(c, hipMemsetAsync(c->scount.p, 0, 8, c->st)); }
         prof_end(c, c->st);
         prof_begin(c, "slot_bounds", c->st, true);
@@ -1637,6 +1638,10 @@ pg_status pg_kernel_stats(pg_ctx *c, pg_kernel_stat *out, uint32_t cap, uint32_t
             if (out && n < cap) { out[n].name = form_names[f]; out[n].launches = c->gather_forms[f]; out[n].total_ms = 0.0; }
             n++;
         }
+    if (c->sort_scatters) { // passes of the LSD radix sort that were queued, all batches together
+        if (out && n < cap) { out[n].name = "k_sort_scatter"; out[n].launches = c->sort_scatters; out[n].total_ms = 0.0; }
+        n++;
+    }
     *n_out = n;
     return PG_OK;
 }
@@ -1648,6 +1653,7 @@ pg_status pg_kernel_stats_reset(pg_ctx *c) {
     prof_drain(c);
     c->prof_acc.clear(); c->prof_names.clear(); c->stats_cancelled = 0; c->long_reads_split = 0; c->long_helpers_short = 0;
     for (uint64_t &f : c->gather_forms) f = 0;
+    c->sort_scatters = 0;
     return PG_OK;
 }
 

@@ -331,8 +331,10 @@ hipError_t pg_launch_rank_direct_emit(hipStream_t st, const uint32_t *ev_slot, u
                                 const uint64_t *keep, const uint64_t *ev_off, const uint64_t *totals, const PgDevBatch &B,
                                 const PgWalkParams &W, const PgWalkOut &O, const PgKeptOut &K);
 // generic ranking: stable LSD radix sort of (ev_slot, index) pairs by slot, dropping PG_INVALID_SLOT; result in
-// S.keys[*sorted_idx]/S.vals[*sorted_idx], number of sorted pairs in S.count[0].
-hipError_t pg_launch_sort_events(hipStream_t st, const uint32_t *ev_slot, uint64_t n, uint32_t key_bits, const PgSortBufs &S, int *sorted_idx);
+// S.keys[*sorted_idx]/S.vals[*sorted_idx], number of sorted pairs in S.count[0]. *scatter_launches (may be null) is advanced by one
+// per k_sort_scatter queued, i.e. per pass (pg_kernel_stats).
+hipError_t pg_launch_sort_events(hipStream_t st, const uint32_t *ev_slot, uint64_t n, uint32_t key_bits, const PgSortBufs &S, int *sorted_idx,
+                                 uint64_t *scatter_launches);
 hipError_t pg_launch_slot_bounds(hipStream_t st, const uint32_t *skey, const uint32_t *m_ptr, uint64_t n_upper,
                            uint32_t *slot_start, uint32_t *slot_end, uint32_t n_slots, uint64_t *acc_cnt, uint64_t *acc_copy);
 // dst_scratch: uint32[n_ops] work space (the radix sort's spare value buffer)

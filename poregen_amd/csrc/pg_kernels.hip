@@ -2597,7 +2597,8 @@ hipError_t pg_launch_rank_direct_emit(hipStream_t st, const uint32_t *ev_slot, u
     return hipSuccess;
 }
 
-hipError_t pg_launch_sort_events(hipStream_t st, const uint32_t *ev_slot, uint64_t n, uint32_t key_bits, const PgSortBufs &S, int *sorted_idx) {
+hipError_t pg_launch_sort_events(hipStream_t st, const uint32_t *ev_slot, uint64_t n, uint32_t key_bits, const PgSortBufs &S, int *sorted_idx,
+                                 uint64_t *scatter_launches) {
     const uint32_t n_tiles = tiles_for(n);
     if (key_bits == 0) key_bits = 1;
     const uint32_t passes = (key_bits + PG_RANK_MAX_BITS - 1) / PG_RANK_MAX_BITS;
@@ -2615,6 +2616,7 @@ hipError_t pg_launch_sort_events(hipStream_t st, const uint32_t *ev_slot, uint64
         PG_LAUNCH(k_sort_dbase, dim3(1), dim3(256), 0, st, (const uint32_t *)S.totals, 1u << nbits, S.dbase, S.count + 1);
         PG_LAUNCH(k_sort_scatter, dim3(n_tiles), dim3(256), 0, st, kin, vin, (uint32_t)n, n_ptr, shift, nbits, n_tiles,
                            (const uint32_t *)S.hist, (const uint32_t *)S.dbase, (const uint32_t *)S.wcnt, S.keys[out], S.vals[out]);
+        if (scatter_launches) ++*scatter_launches;
         // count[0] = number of keys for the next pass (pass 0 drops the invalid ones; later passes keep all)
         PG_HIP(hipMemcpyAsync(S.count, S.count + 1, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
         kin = S.keys[out]; vin = S.vals[out];
