@@ -112,6 +112,13 @@
  * _last_error / _set_stream
  * pg_realign_set_model / _submit / the move table's boundaries moved within a band to where the samples fit the model's levels best
  * _kernel_ms / _walk
+ *
+ * The generative direction (scripts/sim.sh asks squigulator; the rule here is the project's own, fit's inverted):
+ * pg_sim_create / _destroy /        (no counterpart)
+ * _last_error / _set_stream / _stream
+ * pg_sim_parse_model / _parse_dwell a model file with its level_stdv column, the file `poregen model --dwell_model` writes
+ * pg_sim_set_model / _generate /    k-mer model + sequences -> raw signal + the ops that are true by construction, laid out as a pg_batch
+ * _kernel_ms / _walk
  */
 #ifndef PGMOVE_H
 #define PGMOVE_H
@@ -994,6 +1001,89 @@ pg_status pg_realign_kernel_ms(pg_realign *h, double *ms);
  * op_n: lb ops, sig: the read's n_sig samples. op_out[lb] gets the refined ops. PG_ERR_INPUT: the ops leave the samples. */
 pg_status pg_realign_walk(const pg_realign_params *params, const uint32_t *levels, uint32_t kmer_size, const uint8_t *seq, uint32_t lb, const uint32_t *op_n, int64_t query_start,
                           const int16_t *sig, uint64_t n_sig, double a, double b, uint32_t *op_out, pg_realign_read *out);
+
+/* ---- simulate: raw signal and its true alignment drawn from a k-mer model --------------------------------------------------------------------
+ * The generative direction of fit's rule, the project's own (not squigulator's algorithm). Random numbers are Philox4x32-10 with the key
+ * (seed low, seed high) and the counter (i, stream, read low, read high), read = first_read + r: stream 0 per read, stream 1 the dwell of
+ * op i, stream 2 sample i of the read -- every draw is addressed, so the result does not depend on how reads are cut into batches.
+ * Per slot (a k-mer's rank in ACGT order) a level and a stdv in 1e-3 pA (0 < level < 2^18, 0 = no level; 0 <= stdv < 2^18) and a dwell of
+ * 1 to 4096 samples. A read of Lb bases has Lb events; event e takes the slot of the k-mer at i = clamp(e - sig_move_offset, 0, Lb - k):
+ * seq[i, i + k), or seq[Lb - i - k, Lb - i) with rna; U reads as T. Refused, in this order: Lb < k (too_short), a letter outside ACGTU
+ * (bad_base), an event whose k-mer has no level (no_level); a refused read has no ops and no samples.
+ * Dwell of event e, D the slot's: w = D spread_pct div 100, lo = max(1, D - w), hi = D + w, n_e = lo + ((x0 (hi - lo + 1)) >> 32), x0 of
+ * stream 1, i = e. The signal is `lead` samples under (lead_level, lead_stdv), then the events back to back (query_start = lead). Sample j
+ * of the read under level l and spread s: G = the sum of the 12 bytes of x0, x1, x2 of stream 2, i = j, minus 1530;
+ * v = l + floor((s G + 128) / 256); t = (v Q + 2^31) >> 32; raw = clamp(t - off_r, -32768, 32767), with
+ * Q = floor((digitisation 10 2^32 + range_e4 div 2) / range_e4) per run and off_r = offset - off_spread + ((x0 (2 off_spread + 1)) >> 32),
+ * x0 of stream 0, i = 0, per read. All of it is integer arithmetic. No CPU fallback for pg_sim_generate: PG_ERR_NO_DEVICE without a GPU. */
+typedef struct pg_sim pg_sim;
+enum { PG_SIM_ST_OK = 0, PG_SIM_ST_TOO_SHORT = 1, PG_SIM_ST_BAD_BASE = 2, PG_SIM_ST_NO_LEVEL = 3 };
+typedef struct {
+    uint32_t struct_size;          /* sizeof(pg_sim_params) */
+    uint32_t kmer_size;            /* -k            1 to 9 */
+    uint32_t sig_move_offset;      /* -m            at most 64 */
+    int32_t  rna;                  /* --rna */
+    uint64_t seed;                 /* --seed */
+    uint64_t range_e4;             /* --range in 1e-4 pA, above 0; Q (above) must stay below 2^40 */
+    uint32_t digitisation;         /* --digitisation  1 to 65536 */
+    int32_t  offset;               /* --offset        within +-2^20 */
+    uint32_t off_spread;           /* --offset_spread at most 65536 */
+    uint32_t spread_pct;           /* --dwell_spread  0 to 100 */
+    uint32_t lead;                 /* --lead          samples in front of the first event, at most 2^20 */
+    uint32_t lead_level, lead_stdv;/* in 1e-3 pA, below 2^18 */
+    uint32_t reserved;
+} pg_sim_params;
+typedef struct {
+    uint32_t struct_size;          /* sizeof(pg_sim_batch) */
+    int32_t  location;             /* PG_LOC_HOST or PG_LOC_DEVICE: seq and seq_off */
+    uint32_t n_reads, reserved;
+    uint64_t first_read;           /* the global number of read 0 */
+    const uint8_t  *seq;           /* ASCII, the reads 5'->3' as they pass the pore (3'->5' text with rna is the caller's business: see rna above) */
+    const uint64_t *seq_off;       /* [n_reads + 1] */
+} pg_sim_batch;
+typedef struct {                   /* one generate: DEVICE arrays laid out as the arrays of the same names of a pg_batch, op_t all 0 (the batch may be
+                                    * submitted with PG_BATCH_ALL_MATCHES), complete when the call returns, valid until the next pg_sim_generate or
+                                    * pg_sim_destroy on the handle. seq and seq_off are the caller's own arrays for a PG_LOC_DEVICE batch. */
+    uint32_t struct_size, reserved;/* sizeof(pg_sim_result), set by the caller */
+    uint64_t n_reads, n_ops, n_samples, n_seq, n_refused;
+    const int16_t  *sig;           /* 16-byte aligned, 16 bytes of zeros behind the last sample */
+    const uint64_t *sig_off;
+    const double   *digitisation, *offset, *range; /* offset = off_r of the read */
+    const int32_t  *query_start, *target_start, *target_end; /* lead (0 for a refused read); 0 and Lb, or Lb and 0 with rna, as pg_mvops_expand */
+    const uint8_t  *seq;
+    const uint64_t *seq_off;
+    const uint32_t *op_n;
+    const uint8_t  *op_t;
+    const uint64_t *op_off;
+    const uint32_t *status;        /* PG_SIM_ST_* */
+    const uint32_t *status_host;   /* the same on the host */
+} pg_sim_result;
+/* A parameter outside its bounds is refused here (PG_ERR_INVALID_ARG), before a device is asked for. */
+pg_status pg_sim_create(const pg_sim_params *params, int32_t device, pg_sim **out);
+void      pg_sim_destroy(pg_sim *h);
+const char *pg_sim_last_error(const pg_sim *h); /* h may be NULL: error of the last failed pg_sim_create */
+/* The kernels and copies of the following calls go to a caller-owned HIP stream (hipStream_t as void*); NULL restores the handle's own. */
+pg_status pg_sim_set_stream(pg_sim *h, void *hip_stream);
+void     *pg_sim_stream(const pg_sim *h);
+/* levels, stdvs, dwells: host uint32[4^kmer_size], kmer_size the handle's. The stdvs are used as they are: a caller that scales the noise
+ * does it beforehand, stdv <- (stdv noise_q8 + 128) >> 8; all 0 is an ideal signal. */
+pg_status pg_sim_set_model(pg_sim *h, const uint32_t *levels, const uint32_t *stdvs, const uint32_t *dwells, uint32_t kmer_size);
+/* One batch, synchronous. More than 2^28 samples in all: PG_ERR_UNSUPPORTED, nothing of that size is allocated, the handle stays usable. */
+pg_status pg_sim_generate(pg_sim *h, const pg_sim_batch *batch, pg_sim_result *out);
+/* HIP-event time of the two kernels since create or the last call of this (either pointer may be NULL) */
+pg_status pg_sim_kernel_ms(pg_sim *h, double *ops_ms, double *emit_ms);
+/* Host only, no device needed: the rule for one read (its global number `read`), for tests. op_out[lb] gets the ops, *n_samples the
+ * samples, sig_out gets them if sig_cap holds them all, *off_r (may be NULL) the read's offset; a refused read has neither. */
+pg_status pg_sim_walk(const pg_sim_params *params, const uint32_t *levels, const uint32_t *stdvs, const uint32_t *dwells, const uint8_t *seq, uint32_t lb, uint64_t read,
+                      uint32_t *op_out, int16_t *sig_out, uint64_t sig_cap, uint64_t *n_samples, uint32_t *status, int32_t *off_r);
+/* Host only. pg_fit_parse_model with level_stdv kept: rounded to 1e-3 pA with halves up, exactly, on the decimal text; a row without a
+ * level_stdv, or with one that is no number or outside [0, 262.144) pA, refuses the model. */
+pg_status pg_sim_parse_model(const char *text, size_t n, uint32_t want_k, uint32_t *kmer_size_out, uint32_t *levels_out, uint32_t *stdvs_out, size_t cap_slots, int32_t *uses_u,
+                             char *err, size_t err_cap);
+/* Host only. The file `poregen model --dwell_model` writes: rows KMER<TAB>median, a median that ends in .5 is rounded up; a row with an
+ * empty or "nan" median is skipped. dwells_out (cap_slots >= 4^k): 0 for a k-mer the file does not give. PG_ERR_INPUT: refused as a whole
+ * (a median that is no number or outside 1 to 4096, a k-mer twice, a letter outside ACGTU, two lengths, no k-mer), err names the line. */
+pg_status pg_sim_parse_dwell(const char *text, size_t n, uint32_t want_k, uint32_t *kmer_size_out, uint32_t *dwells_out, size_t cap_slots, char *err, size_t err_cap);
 
 
 #ifdef __cplusplus

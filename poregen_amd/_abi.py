@@ -36,6 +36,7 @@ PG_MVOPS_RNA, PG_MVOPS_N_TO_T = 1, 2
 PG_MVOPS_ST_ACCEPTED, PG_MVOPS_ST_NO_MOVE_IN_TABLE, PG_MVOPS_ST_NEGATIVE_TAIL, PG_MVOPS_ST_BASES_LEFT_OVER, PG_MVOPS_ST_BAD_STRIDE = 0, 1, 2, 3, 4
 PG_MODEL_TEXT_MEDIAN, PG_MODEL_TEXT_SSTDEV, PG_MODEL_TEXT_DWELL = 0, 1, 2
 PG_FIT_ST_OK, PG_FIT_ST_OUT_OF_SIGNAL, PG_FIT_ST_TOO_LONG, PG_FIT_ST_FEW_EVENTS, PG_FIT_ST_FLAT, PG_FIT_ST_NEGATIVE_SCALE, PG_FIT_ST_SKIPPED = 0, 1, 2, 3, 4, 5, 16
+PG_SIM_ST_OK, PG_SIM_ST_TOO_SHORT, PG_SIM_ST_BAD_BASE, PG_SIM_ST_NO_LEVEL = 0, 1, 2, 3
 PG_POOL_NO_GROUP = 0xffffffff
 PG_POOL_MAX_LABELINGS = 16
 PG_POOL_GROUP_OK, PG_POOL_GROUP_EMPTY, PG_POOL_GROUP_REFUSED = 0, 1, 2
@@ -62,6 +63,8 @@ EXPORTS = [
     "pg_fit_parse_model", "pg_fit_residuals",
     "pg_realign_create", "pg_realign_destroy", "pg_realign_last_error", "pg_realign_set_model", "pg_realign_set_stream", "pg_realign_submit", "pg_realign_kernel_ms",
     "pg_realign_walk",
+    "pg_sim_create", "pg_sim_destroy", "pg_sim_last_error", "pg_sim_set_stream", "pg_sim_stream", "pg_sim_set_model", "pg_sim_generate", "pg_sim_kernel_ms", "pg_sim_walk",
+    "pg_sim_parse_model", "pg_sim_parse_dwell",
 ]
 PG_JOB_EXCHANGE_AUTO, PG_JOB_EXCHANGE_HOST, PG_JOB_EXCHANGE_RCCL = 0, 1, 2
 
@@ -211,6 +214,24 @@ class PgRealignRead(C.Structure):
 
 class PgRealignReads(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("n_reads", C.c_uint64), ("n_ops", C.c_uint64), ("op_n", C.c_void_p), ("reads", C.c_void_p)]
+
+
+class PgSimParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("kmer_size", C.c_uint32), ("sig_move_offset", C.c_uint32), ("rna", C.c_int32), ("seed", C.c_uint64), ("range_e4", C.c_uint64),
+                ("digitisation", C.c_uint32), ("offset", C.c_int32), ("off_spread", C.c_uint32), ("spread_pct", C.c_uint32), ("lead", C.c_uint32), ("lead_level", C.c_uint32),
+                ("lead_stdv", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PgSimBatch(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("location", C.c_int32), ("n_reads", C.c_uint32), ("reserved", C.c_uint32), ("first_read", C.c_uint64), ("seq", C.c_void_p),
+                ("seq_off", C.c_void_p)]
+
+
+class PgSimResult(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("n_reads", C.c_uint64), ("n_ops", C.c_uint64), ("n_samples", C.c_uint64), ("n_seq", C.c_uint64),
+                ("n_refused", C.c_uint64), ("sig", C.c_void_p), ("sig_off", C.c_void_p), ("digitisation", C.c_void_p), ("offset", C.c_void_p), ("range", C.c_void_p),
+                ("query_start", C.c_void_p), ("target_start", C.c_void_p), ("target_end", C.c_void_p), ("seq", C.c_void_p), ("seq_off", C.c_void_p), ("op_n", C.c_void_p),
+                ("op_t", C.c_void_p), ("op_off", C.c_void_p), ("status", C.c_void_p), ("status_host", C.c_void_p)]
 
 
 _lib = None
@@ -384,5 +405,18 @@ def load():
         lib.pg_realign_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]; lib.pg_realign_kernel_ms.restype = i32
         lib.pg_realign_walk.argtypes = [C.POINTER(PgRealignParams), vp, u32, vp, u32, vp, C.c_int64, vp, C.c_uint64, C.c_double, C.c_double, vp, C.POINTER(PgRealignRead)]
         lib.pg_realign_walk.restype = i32
+    if hasattr(lib, "pg_sim_create"):  # (as above: a library built from an older tree has no simulator)
+        lib.pg_sim_create.argtypes = [C.POINTER(PgSimParams), i32, C.POINTER(vp)]; lib.pg_sim_create.restype = i32
+        lib.pg_sim_destroy.argtypes = [vp]; lib.pg_sim_destroy.restype = None
+        lib.pg_sim_last_error.argtypes = [vp]; lib.pg_sim_last_error.restype = C.c_char_p
+        lib.pg_sim_set_stream.argtypes = [vp, vp]; lib.pg_sim_set_stream.restype = i32
+        lib.pg_sim_stream.argtypes = [vp]; lib.pg_sim_stream.restype = vp
+        lib.pg_sim_set_model.argtypes = [vp, vp, vp, vp, u32]; lib.pg_sim_set_model.restype = i32
+        lib.pg_sim_generate.argtypes = [vp, C.POINTER(PgSimBatch), C.POINTER(PgSimResult)]; lib.pg_sim_generate.restype = i32
+        lib.pg_sim_kernel_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]; lib.pg_sim_kernel_ms.restype = i32
+        lib.pg_sim_walk.argtypes = [C.POINTER(PgSimParams), vp, vp, vp, vp, u32, C.c_uint64, vp, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(u32), C.POINTER(i32)]
+        lib.pg_sim_walk.restype = i32
+        lib.pg_sim_parse_model.argtypes = [C.c_char_p, C.c_size_t, u32, C.POINTER(u32), vp, vp, C.c_size_t, C.POINTER(i32), C.c_char_p, C.c_size_t]; lib.pg_sim_parse_model.restype = i32
+        lib.pg_sim_parse_dwell.argtypes = [C.c_char_p, C.c_size_t, u32, C.POINTER(u32), vp, C.c_size_t, C.c_char_p, C.c_size_t]; lib.pg_sim_parse_dwell.restype = i32
     _lib = lib
     return lib

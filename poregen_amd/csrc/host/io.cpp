@@ -719,3 +719,75 @@ int SamBamReader::next_impl(MoveRec &out, RawMoveRec *raw, std::string &err) {
 }
 
 } // namespace pgh
+
+// ======================================================================================================
+// SLOW5 / BLOW5 writer (poregen simulate)
+// ======================================================================================================
+namespace pgh {
+
+static const char kSlow5Attrs[] = "@asic_id\t.\n@exp_script_purpose\tsequencing_run\n@experiment_type\tsimulated\n@run_id\tporegen_simulate\n@sample_frequency\t";
+static const char kSlow5Cols[] =
+    "#char*\tuint32_t\tdouble\tdouble\tdouble\tdouble\tuint64_t\tint16_t*\n#read_id\tread_group\tdigitisation\toffset\trange\tsampling_rate\tlen_raw_signal\traw_signal\n";
+
+Slow5Writer::~Slow5Writer() { if (fp_) fclose((FILE *)fp_); }
+
+bool Slow5Writer::open(const std::string &path, bool binary, double sampling_rate, std::string &err) {
+    FILE *fp = fopen(path.c_str(), "wb");
+    if (!fp) { err = "Could not open " + path + " for writing."; return false; }
+    fp_ = fp; binary_ = binary; rate_ = sampling_rate;
+    char rate[64]; snprintf(rate, sizeof rate, "%.0f\n", sampling_rate);
+    bool ok;
+    if (binary) {
+        // 64 bytes: magic, version 0.2.0, record compression none, one read group, signal compression none, zeros; then the ASCII header
+        unsigned char head[64] = {'B', 'L', 'O', 'W', '5', 1, 0, 2, 0, 0, 1, 0, 0, 0, 0};
+        const std::string text = std::string(kSlow5Attrs) + rate + kSlow5Cols; // (version and read groups are in the 64 bytes)
+        const uint32_t hlen = (uint32_t)text.size();
+        ok = fwrite(head, 1, 64, fp) == 64 && fwrite(&hlen, 4, 1, fp) == 1 && fwrite(text.data(), 1, text.size(), fp) == text.size();
+    } else
+        ok = fprintf(fp, "#slow5_version\t0.2.0\n#num_read_groups\t1\n%s%s%s", kSlow5Attrs, rate, kSlow5Cols) > 0;
+    if (!ok) err = "Error in writing " + path + ".";
+    return ok;
+}
+
+// a double as the shortest text that reads back as the same double
+static void exact_double(double v, char *buf, size_t cap) {
+    for (int prec = 1; prec <= 17; prec++) { snprintf(buf, cap, "%.*g", prec, v); if (strtod(buf, nullptr) == v) return; }
+}
+
+bool Slow5Writer::add(const std::string &read_id, double digitisation, double offset, double range, const int16_t *raw, uint64_t n, std::string &err) {
+    FILE *fp = (FILE *)fp_;
+    bool ok;
+    if (binary_) {
+        if (read_id.size() > 0xffff) { err = "a read id of more than 65535 bytes"; return false; }
+        const uint16_t il = (uint16_t)read_id.size();
+        const uint32_t group = 0;
+        const double f[4] = {digitisation, offset, range, rate_};
+        const uint64_t size = 2 + (uint64_t)il + 4 + 32 + 8 + n * 2;
+        ok = fwrite(&size, 8, 1, fp) == 1 && fwrite(&il, 2, 1, fp) == 1 && fwrite(read_id.data(), 1, il, fp) == il && fwrite(&group, 4, 1, fp) == 1 && fwrite(f, 8, 4, fp) == 4 &&
+             fwrite(&n, 8, 1, fp) == 1 && (n == 0 || fwrite(raw, 2, n, fp) == n);
+    } else {
+        char d[40], o[40], r[40], s[40];
+        exact_double(digitisation, d, sizeof d); exact_double(offset, o, sizeof o); exact_double(range, r, sizeof r); exact_double(rate_, s, sizeof s);
+        line_.clear();
+        line_ += read_id; line_ += "\t0\t"; line_ += d; line_ += '\t'; line_ += o; line_ += '\t'; line_ += r; line_ += '\t'; line_ += s; line_ += '\t';
+        line_ += std::to_string(n); line_ += '\t';
+        char num[16];
+        for (uint64_t i = 0; i < n; i++) { const int len = snprintf(num, sizeof num, i ? ",%d" : "%d", (int)raw[i]); line_.append(num, (size_t)len); }
+        line_ += '\n';
+        ok = fwrite(line_.data(), 1, line_.size(), fp) == line_.size();
+    }
+    if (!ok) err = "Error in writing the signal file.";
+    return ok;
+}
+
+bool Slow5Writer::close(std::string &err) {
+    FILE *fp = (FILE *)fp_;
+    if (!fp) return true;
+    bool ok = !binary_ || fwrite("5WOLB", 1, 5, fp) == 5;
+    ok = (fclose(fp) == 0) && ok;
+    fp_ = nullptr;
+    if (!ok) err = "Error in writing the signal file.";
+    return ok;
+}
+
+} // namespace pgh

@@ -76,6 +76,21 @@ private:
     bool view_blow5(const Loc &l, RawView &v, std::string &err, std::string *read_id = nullptr) const;
 };
 
+// ---- SLOW5 / BLOW5 writer (`poregen simulate -o`): ASCII SLOW5, or BLOW5 with neither the records nor the signals compressed; one read
+// group; the header lines Slow5File needs to read the file back. Code of its own: nothing of the reading paths is shared or changed.
+class Slow5Writer {
+public:
+    ~Slow5Writer();
+    bool open(const std::string &path, bool binary, double sampling_rate, std::string &err);
+    bool add(const std::string &read_id, double digitisation, double offset, double range, const int16_t *raw, uint64_t n, std::string &err);
+    bool close(std::string &err); // writes the end-of-file marker of a BLOW5 file
+private:
+    void *fp_ = nullptr; // FILE *
+    bool binary_ = false;
+    double rate_ = 4000.0;
+    std::string line_;
+};
+
 // ---- FASTA/FASTQ with faidx semantics (replaces fai_load / faidx_fetch_seq, src/gmove.cpp:724,805) -----
 class FastxIndex {
 public:

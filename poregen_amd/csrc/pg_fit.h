@@ -164,9 +164,26 @@ static inline std::string pg_fit_units_text(int64_t v) {
 
 struct PgFitModel { uint32_t k = 0; bool uses_u = false; std::vector<uint32_t> levels; }; // levels[4^k], 0 = the k-mer is not in the file
 
-// A model file in the format `poregen transform` writes. false: the model is refused, err names the line and the reason.
-static inline bool pg_fit_parse_model_text(const char *text, size_t n, uint32_t want_k, PgFitModel &out, std::string &err) {
+// floor((2 mult |v| + 1) / 2) of a decimal text's value v: the nearest multiple of 1 / mult with halves up, exactly. 0, or 1: too many
+// digits, 2: the result does not fit 32 bits.
+static inline int pg_fit_round_dec(const pgbc::Dec &v, uint32_t mult, uint32_t &q_out) {
+    pgbc::Big num = v.m, den, half, q;
+    den.w[0] = 1; den.n = 1; half = den;
+    if (!pgbc::big_muladd_small(num, 2 * mult, 0) || !pgbc::big_mul_pow10(den, v.scale) || !pgbc::big_mul_pow10(half, v.scale) || !pgbc::big_muladd_small(den, 2, 0) ||
+        !pgbc::big_add(num, half, num))
+        return 1;
+    pgbc::big_div(num, den, q);
+    if (q.n > 1) return 2;
+    q_out = q.n ? q.w[0] : 0u;
+    return 0;
+}
+
+// A model file in the format `poregen transform` writes. false: the model is refused, err names the line and the reason. stdvs (may be
+// null: the column is not kept, a row may lack it): level_stdv of every slot in 1e-3 pA, rounded as the level is; with it a row without a
+// level_stdv below 262.144 pA refuses the model (`poregen simulate`, pg_sim.h).
+static inline bool pg_fit_parse_model_text(const char *text, size_t n, uint32_t want_k, PgFitModel &out, std::string &err, std::vector<uint32_t> *stdvs = nullptr) {
     PgFitModel md;
+    std::vector<uint32_t> sd;
     size_t line_no = 0;
     auto fail = [&](const std::string &why) { err = "line " + std::to_string(line_no) + ": " + why; return false; };
     for (size_t p = 0; p < n;) {
@@ -192,6 +209,7 @@ static inline bool pg_fit_parse_model_text(const char *text, size_t n, uint32_t 
         if (md.k == 0) {
             if (want_k && k != want_k) return fail("the model's k-mers have " + std::to_string(k) + " letters, -k says " + std::to_string(want_k));
             md.k = k; md.levels.assign((size_t)1 << (2 * k), 0u);
+            if (stdvs) sd.assign((size_t)1 << (2 * k), 0u);
         } else if (k != md.k) return fail("k-mers of two lengths");
         uint32_t slot = 0;
         for (uint32_t j = 0; j < k; j++) {
@@ -205,17 +223,21 @@ static inline bool pg_fit_parse_model_text(const char *text, size_t n, uint32_t 
         if (!pgbc::parse(f[1], fl[1], mean)) return fail("level_mean is no number");
         if (nf > 2 && !pgbc::parse(f[2], fl[2], stdv)) return fail("level_stdv is no number");
         // L = floor((2000 m + 10^scale) / (2 * 10^scale)): the level in 1e-3 pA, the nearest unit with halves up, on the decimal text
-        pgbc::Big num = mean.m, den, half, q;
-        den.w[0] = 1; den.n = 1; half = den;
-        if (!pgbc::big_muladd_small(num, 2000, 0) || !pgbc::big_mul_pow10(den, mean.scale) || !pgbc::big_mul_pow10(half, mean.scale) || !pgbc::big_muladd_small(den, 2, 0) ||
-            !pgbc::big_add(num, half, num))
-            return fail("level_mean has too many digits");
-        pgbc::big_div(num, den, q);
-        if (mean.neg || q.n == 0 || q.n > 1 || q.w[0] >= PG_FIT_MAX_LEVEL) return fail("a level outside (0, 262.144) pA");
+        uint32_t lv = 0;
+        const int rc = pg_fit_round_dec(mean, 1000, lv);
+        if (rc == 1) return fail("level_mean has too many digits");
+        if (mean.neg || rc || lv == 0 || lv >= PG_FIT_MAX_LEVEL) return fail("a level outside (0, 262.144) pA");
         if (md.levels[slot]) return fail("a k-mer twice");
-        md.levels[slot] = q.w[0];
+        md.levels[slot] = lv;
+        if (stdvs) {
+            uint32_t sv = 0;
+            if (nf < 3) return fail("a row needs KMER<TAB>level_mean<TAB>level_stdv");
+            if (pg_fit_round_dec(stdv, 1000, sv) || (stdv.neg && sv != 0) || sv >= PG_FIT_MAX_LEVEL) return fail("a level_stdv outside [0, 262.144) pA");
+            sd[slot] = sv;
+        }
     }
     if (md.k == 0) { line_no = 0; err = "the model holds no k-mer"; return false; }
+    if (stdvs) *stdvs = std::move(sd);
     out = std::move(md);
     return true;
 }

@@ -606,3 +606,53 @@ extern "C" int pgt_realign_walk(const uint8_t *seq, uint32_t lb, const uint32_t 
     out7[5] = (uint64_t)r.cost_after; out7[6] = (uint64_t)(r.cost_after >> 64);
     return 0;
 }
+
+// ---- simulate (pg_sim.h): the generator, the rule for one read, the parsers, the command's read drawing and stride rounding -----------------
+#include "pg_sim.h"
+extern "C" void pgt_sim_levels(uint64_t *out6) {
+    out6[0] = PG_SIM_PIECE; out6[1] = PG_SIM_LANE; out6[2] = PG_SIM_MAX_LEVEL; out6[3] = PG_SIM_MAX_DWELL; out6[4] = PG_SIM_BATCH_SAMPLES; out6[5] = PG_SIM_MAX_Q;
+}
+extern "C" void pgt_sim_philox(const uint32_t *ctr4, const uint32_t *key2, uint32_t *out4) {
+    const PgSimX x = pg_sim_philox(ctr4[0], ctr4[1], ctr4[2], ctr4[3], key2[0], key2[1]);
+    out4[0] = x.x0; out4[1] = x.x1; out4[2] = x.x2; out4[3] = x.x3;
+}
+extern "C" uint64_t pgt_sim_q(uint32_t digitisation, uint64_t range_e4) { return pg_sim_q(digitisation, range_e4); }
+// the status; ops (lb of them) and samples (up to cap) of an accepted read; rule11 = k, m, rna, seed, Q, offset, off_spread, spread_pct, lead, lead_level, lead_stdv
+extern "C" int pgt_sim_walk(const int64_t *rule11, const uint32_t *levels, const uint32_t *stdvs, const uint32_t *dwells, const uint8_t *seq, uint32_t lb, uint64_t read, uint32_t *ops,
+                            int16_t *sig, uint64_t cap, uint64_t *n_sig, int32_t *off_r) {
+    const PgSimRule R{(uint32_t)rule11[0], (uint32_t)rule11[1], rule11[2] != 0, (uint64_t)rule11[3], (uint64_t)rule11[4], (int32_t)rule11[5], (uint32_t)rule11[6], (uint32_t)rule11[7],
+                      (uint32_t)rule11[8], (uint32_t)rule11[9], (uint32_t)rule11[10]};
+    std::vector<uint32_t> o; std::vector<int16_t> s;
+    const uint32_t st = pg_sim_walk_host(R, levels, stdvs, dwells, seq, lb, read, o, s, off_r);
+    if (!o.empty()) memcpy(ops, o.data(), o.size() * 4);
+    *n_sig = s.size();
+    if (!s.empty() && s.size() <= cap) memcpy(sig, s.data(), s.size() * 2);
+    return (int)st;
+}
+extern "C" int pgt_sim_parse_dwell(const char *text, size_t n, uint32_t want_k, uint32_t *k, uint32_t *dwells, size_t cap_slots, char *err, size_t ecap) {
+    std::vector<uint32_t> dw; std::string why;
+    if (!pg_sim_parse_dwell_text(text, n, want_k, *k, dw, why) || dw.size() > cap_slots) { snprintf(err, ecap, "%s", why.c_str()); return -1; }
+    memcpy(dwells, dw.data(), dw.size() * 4);
+    return 0;
+}
+extern "C" int pgt_sim_parse_model(const char *text, size_t n, uint32_t want_k, uint32_t *k, uint32_t *levels, uint32_t *stdvs, size_t cap_slots, char *err, size_t ecap) {
+    PgFitModel md; std::vector<uint32_t> sd; std::string why;
+    if (!pg_fit_parse_model_text(text, n, want_k, md, why, &sd) || md.levels.size() > cap_slots) { snprintf(err, ecap, "%s", why.c_str()); return -1; }
+    memcpy(levels, md.levels.data(), md.levels.size() * 4); memcpy(stdvs, sd.data(), sd.size() * 4);
+    *k = md.k;
+    return 0;
+}
+extern "C" void pgt_sim_pick(uint64_t seed, uint64_t read, uint64_t total, uint32_t read_len, int rna, uint64_t *out3) {
+    const PgSimPick p = pg_sim_pick(seed, read, total, read_len, rna != 0);
+    out3[0] = p.pos; out3[1] = p.len; out3[2] = p.reverse ? 1 : 0;
+}
+extern "C" uint64_t pgt_sim_round_stride(uint64_t B, uint32_t lead, uint32_t stride) { return pg_sim_round_stride(B, lead, stride); }
+// the writer behind `simulate -o`: n records (ids NUL-separated) into an ASCII SLOW5 or an uncompressed BLOW5; 0, or -1
+extern "C" int pgt_sim_write_slow5(const char *path, int binary, uint64_t n, const char *ids, const double *dig, const double *off, const double *range, const int16_t *raw,
+                                   const uint64_t *raw_off) {
+    pgh::Slow5Writer w; std::string err;
+    if (!w.open(path, binary != 0, 4000.0, err)) return -1;
+    for (uint64_t i = 0; i < n; i++, ids += strlen(ids) + 1)
+        if (!w.add(ids, dig[i], off[i], range[i], raw + raw_off[i], raw_off[i + 1] - raw_off[i], err)) return -1;
+    return w.close(err) ? 0 : -1;
+}

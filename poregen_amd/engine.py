@@ -1893,3 +1893,205 @@ def realign_walk(levels, k: int, seq, ops, q: int, sig, a: float, b: float, sig_
     if st != 0:
         raise PgError(st, "pg_realign_walk: bad argument")
     return new, rd.n_free, rd.n_moved, rd.sum_abs_shift, (rd.cost_before_hi << 64) | rd.cost_before_lo, (rd.cost_after_hi << 64) | rd.cost_after_lo
+
+
+# ---- simulate: raw signal and its true alignment drawn from a k-mer model (pg_sim_*) --------------------------------------------------------
+
+SIM_STATUS_NAMES = {0: "ok", 1: "too_short", 2: "bad_base", 3: "no_level"}
+
+
+def parse_sim_model(text, k: int = 0):
+    """(k, levels, stdvs, uses_u) of a model file: parse_fit_model with the level_stdv column kept, uint32[4^k] in 1e-3 pA
+    (pg_sim_parse_model; no GPU needed). PgError with PG_ERR_INPUT when the model is refused."""
+    lib = _abi.load()
+    data = text.encode() if isinstance(text, str) else bytes(text)
+    levels, stdvs = np.zeros(4 ** 9, np.uint32), np.zeros(4 ** 9, np.uint32)
+    kk, uu, err = C.c_uint32(), C.c_int32(), C.create_string_buffer(400)
+    st = lib.pg_sim_parse_model(data, len(data), k, C.byref(kk), levels.ctypes.data, stdvs.ctypes.data, levels.size, C.byref(uu), err, len(err))
+    if st != 0:
+        raise PgError(st, err.value.decode())
+    return int(kk.value), levels[:4 ** kk.value].copy(), stdvs[:4 ** kk.value].copy(), bool(uu.value)
+
+
+def parse_dwell_model(text, k: int = 0):
+    """(k, dwells uint32[4^k]) of the file `poregen model --dwell_model` writes, a median of x.5 rounded up, 0 for a k-mer the file does
+    not give (pg_sim_parse_dwell; no GPU needed)."""
+    lib = _abi.load()
+    data = text.encode() if isinstance(text, str) else bytes(text)
+    dw = np.zeros(4 ** 9, np.uint32)
+    kk, err = C.c_uint32(), C.create_string_buffer(400)
+    st = lib.pg_sim_parse_dwell(data, len(data), k, C.byref(kk), dw.ctypes.data, dw.size, err, len(err))
+    if st != 0:
+        raise PgError(st, err.value.decode())
+    return int(kk.value), dw[:4 ** kk.value].copy()
+
+
+def scale_stdvs(stdvs, noise_q8: int):
+    """stdv <- (stdv * noise_q8 + 128) >> 8: the noise scale in 1 / 256, applied before the tables go to the simulator."""
+    return ((np.asarray(stdvs, np.uint64) * np.uint64(noise_q8) + np.uint64(128)) >> np.uint64(8)).astype(np.uint32)
+
+
+def _sim_params(k, sig_move_offset, rna, seed, digitisation, range_e4, offset, off_spread, spread_pct, lead, lead_level, lead_stdv):
+    return _abi.PgSimParams(C.sizeof(_abi.PgSimParams), k, sig_move_offset, int(rna), seed, range_e4, digitisation, offset, off_spread, spread_pct, lead, lead_level, lead_stdv, 0)
+
+
+def _sim_seq_arrays(seqs):
+    data = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+    off = np.zeros(len(data) + 1, np.uint64)
+    off[1:] = np.cumsum([len(d) for d in data], dtype=np.uint64)
+    return np.frombuffer(b"".join(data), np.uint8).copy(), off
+
+
+@dataclass
+class SimReads:
+    """One generate: torch CUDA tensors that alias the simulator's device buffers (valid until its next generate / close), `batch`, a
+    device Batch over them that ModelFit, Realigner and GmoveEngine take in place (all_matches), and the statuses on the host."""
+    batch: "Batch"
+    status: np.ndarray
+    status_device: object
+    n_ops: int
+    n_samples: int
+    n_refused: int
+
+    def to_host(self):
+        b = self.batch
+        return dict(sig=b.sig.cpu().numpy()[:self.n_samples], sig_off=b.sig_off.cpu().numpy().view(np.uint64), digitisation=b.digitisation.cpu().numpy(),
+                    offset=b.offset.cpu().numpy(), range=b.range.cpu().numpy(), query_start=b.query_start.cpu().numpy(), target_start=b.target_start.cpu().numpy(),
+                    target_end=b.target_end.cpu().numpy(), seq=b.seq.cpu().numpy(), seq_off=b.seq_off.cpu().numpy().view(np.uint64),
+                    op_n=b.op_n.cpu().numpy().view(np.uint32), op_t=b.op_t.cpu().numpy(), op_off=b.op_off.cpu().numpy().view(np.uint64), status=self.status.copy(),
+                    status_device=self.status_device.cpu().numpy().view(np.uint32))
+
+
+class SignalSimulator:
+    """Draws raw signal and the ops that are true by construction from a k-mer model (pg_sim_*). levels, stdvs, dwells: uint32[4^k], the
+    first two in 1e-3 pA (a level of 0: the k-mer has none), dwells in samples; range_e4 is the range in 1e-4 pA."""
+
+    def __init__(self, levels, stdvs, dwells, k: int, sig_move_offset: int = 0, rna: bool = False, seed: int = 0, digitisation: int = 8192, range_e4: int = 14676100,
+                 offset: int = 10, off_spread: int = 0, spread_pct: int = 50, lead: int = 0, lead_level=None, lead_stdv=None, device: int = 0):
+        self._lib = _abi.load()
+        self.device, self._h = device, None
+        lv, sd, dw = (np.ascontiguousarray(a, dtype=np.uint32) for a in (levels, stdvs, dwells))
+        if not (lv.size == sd.size == dw.size == 4 ** k):
+            raise ValueError("levels, stdvs and dwells need 4^k entries each")
+        have = lv[lv > 0]
+        if lead_level is None:  # the rounded means of the model's columns
+            lead_level = int((int(have.sum()) * 2 + have.size) // (2 * have.size)) if have.size else 0
+        if lead_stdv is None:
+            lead_stdv = int((int(sd[lv > 0].sum()) * 2 + have.size) // (2 * have.size)) if have.size else 0
+        self.params = _sim_params(k, sig_move_offset, rna, seed, digitisation, range_e4, offset, off_spread, spread_pct, lead, lead_level, lead_stdv)
+        h = C.c_void_p()
+        st = self._lib.pg_sim_create(C.byref(self.params), device, C.byref(h))
+        if st != 0:
+            raise PgError(st, self._lib.pg_sim_last_error(None).decode())
+        self._h = h
+        self._check(self._lib.pg_sim_set_model(self._h, lv.ctypes.data, sd.ctypes.data, dw.ctypes.data, k))
+        self.kmer_size = k
+
+    def _check(self, st):
+        if st != 0:
+            raise PgError(st, self._lib.pg_sim_last_error(self._h).decode())
+
+    def set_stream(self, stream=None):
+        """Run on a caller-owned stream (a torch.cuda.Stream or a raw hipStream_t value); None: the handle's own."""
+        ptr = None if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
+        self._check(self._lib.pg_sim_set_stream(self._h, ptr))
+
+    @property
+    def stream(self) -> int:
+        return int(self._lib.pg_sim_stream(self._h) or 0)
+
+    def generate(self, seqs=None, first_read: int = 0, seq=None, seq_off=None) -> SimReads:
+        """seqs: a list of str / bytes; or seq (uint8) and seq_off (n + 1 offsets) as numpy arrays or as CUDA tensors (uint8, int64)."""
+        import torch
+        if seqs is not None:
+            seq, seq_off = _sim_seq_arrays(seqs)
+        b = _abi.PgSimBatch()
+        b.struct_size = C.sizeof(_abi.PgSimBatch)
+        on_dev = hasattr(seq_off, "is_cuda") and seq_off.is_cuda
+        if on_dev:
+            if not (seq.is_cuda and seq.is_contiguous() and seq_off.is_contiguous() and seq.dtype.itemsize == 1 and seq_off.dtype.itemsize == 8):
+                raise ValueError("device batch: seq must be a contiguous uint8 tensor and seq_off a contiguous int64 tensor")
+            keep = (seq, seq_off)
+            b.location, b.n_reads, b.seq, b.seq_off = _abi.PG_LOC_DEVICE, seq_off.numel() - 1, seq.data_ptr(), seq_off.data_ptr()
+        else:
+            keep = (np.ascontiguousarray(seq, dtype=np.uint8), np.ascontiguousarray(seq_off, dtype=np.uint64))
+            b.location, b.n_reads, b.seq, b.seq_off = _abi.PG_LOC_HOST, keep[1].size - 1, keep[0].ctypes.data, keep[1].ctypes.data
+        b.first_read = first_read
+        res = _abi.PgSimResult()
+        res.struct_size = C.sizeof(_abi.PgSimResult)
+        self._check(self._lib.pg_sim_generate(self._h, C.byref(b), C.byref(res)))
+        dev = torch.device("cuda", self.device)
+
+        class _Alias:  # zero-copy hand-over through the CUDA array interface
+            def __init__(self, ptr, n, typestr):
+                self.__cuda_array_interface__ = {"shape": (int(n),), "typestr": typestr, "data": (int(ptr or 0), False), "version": 2}
+
+        def wrap(ptr, n, typestr, dtype):
+            if n == 0 or not ptr:
+                return torch.empty(0, dtype=dtype, device=dev)
+            return torch.as_tensor(_Alias(ptr, n, typestr), device=dev)
+
+        n, n_ops, n_sig, n_seq = int(res.n_reads), int(res.n_ops), int(res.n_samples), int(res.n_seq)
+        batch = Batch(n_reads=n, sig=wrap(res.sig, n_sig + 8, "<i2", torch.int16), sig_off=wrap(res.sig_off, n + 1, "<i8", torch.int64),
+                      digitisation=wrap(res.digitisation, n, "<f8", torch.float64), offset=wrap(res.offset, n, "<f8", torch.float64), range=wrap(res.range, n, "<f8", torch.float64),
+                      query_start=wrap(res.query_start, n, "<i4", torch.int32), target_start=wrap(res.target_start, n, "<i4", torch.int32),
+                      target_end=wrap(res.target_end, n, "<i4", torch.int32), seq=wrap(res.seq, n_seq, "|u1", torch.uint8), seq_off=wrap(res.seq_off, n + 1, "<i8", torch.int64),
+                      op_n=wrap(res.op_n, n_ops, "<i4", torch.int32), op_t=wrap(res.op_t, n_ops, "|u1", torch.uint8), op_off=wrap(res.op_off, n + 1, "<i8", torch.int64),
+                      on_device=True, n_ops=n_ops, all_matches=True)
+        status = np.ctypeslib.as_array(C.cast(res.status_host, C.POINTER(C.c_uint32)), (n,)).copy() if n else np.zeros(0, np.uint32)
+        self._keep = keep
+        return SimReads(batch=batch, status=status, status_device=wrap(res.status, n, "<i4", torch.int32), n_ops=n_ops, n_samples=n_sig, n_refused=int(res.n_refused))
+
+    def kernel_ms(self):
+        """HIP-event time of k_sim_ops and of k_sim_emit since the last call."""
+        a, b = C.c_double(), C.c_double()
+        self._check(self._lib.pg_sim_kernel_ms(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.pg_sim_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def simulate_reads(levels, stdvs, dwells, k: int, seqs, first_read: int = 0, **kw):
+    """One-shot SignalSimulator.generate: the arrays on the host (SimReads.to_host) plus n_ops, n_samples and n_refused."""
+    with SignalSimulator(levels, stdvs, dwells, k, **kw) as sim:
+        r = sim.generate(seqs, first_read=first_read)
+        out = r.to_host()
+        out.update(n_ops=r.n_ops, n_samples=r.n_samples, n_refused=r.n_refused)
+        return out
+
+
+def sim_walk(levels, stdvs, dwells, k: int, seq, read: int = 0, sig_move_offset: int = 0, rna: bool = False, seed: int = 0, digitisation: int = 8192, range_e4: int = 14676100,
+             offset: int = 10, off_spread: int = 0, spread_pct: int = 50, lead: int = 0, lead_level: int = 0, lead_stdv: int = 0):
+    """The rule for one read on the host (pg_sim_walk; no GPU needed): (status, ops uint32, samples int16, off_r)."""
+    lib = _abi.load()
+    p = _sim_params(k, sig_move_offset, rna, seed, digitisation, range_e4, offset, off_spread, spread_pct, lead, lead_level, lead_stdv)
+    lv, sd, dw = (np.ascontiguousarray(a, dtype=np.uint32) for a in (levels, stdvs, dwells))
+    s = np.frombuffer(seq.encode() if isinstance(seq, str) else bytes(seq), np.uint8)
+    ops = np.zeros(max(s.size, 1), np.uint32)
+    n, st, off = C.c_uint64(), C.c_uint32(), C.c_int32()
+    sig = np.zeros(0, np.int16)
+    for _ in range(2):  # the first call counts the samples
+        rc = lib.pg_sim_walk(C.byref(p), lv.ctypes.data, sd.ctypes.data, dw.ctypes.data, s.ctypes.data, s.size, read, ops.ctypes.data, sig.ctypes.data, sig.size, C.byref(n),
+                             C.byref(st), C.byref(off))
+        if rc != 0:
+            raise PgError(rc, "pg_sim_walk: bad argument")
+        if sig.size >= n.value:
+            break
+        sig = np.zeros(n.value, np.int16)
+    ok = st.value == 0
+    return int(st.value), ops[:s.size if ok else 0].copy(), sig[:n.value].copy(), int(off.value)

@@ -1,4 +1,5 @@
-// stream_probe.hip -- how fast can one MI355X READ a 400 MB int16 buffer with the access shapes k_read_stats could use?
+// stream_probe.hip -- how fast can one MI355X READ a 400 MB int16 buffer with the access shapes k_read_stats could use? (lines W: how fast can it
+// WRITE one; PROBE_ONLY_WRITE=1 stops behind them)
 // build: hipcc --offload-arch=gfx950 -O3 -o stream_probe stream_probe.hip ; run: ./stream_probe
 #include <hip/hip_runtime.h>
 #ifdef PROBE_REAL_KERNEL
@@ -17,6 +18,10 @@ __global__ __launch_bounds__(256) void k_plain(const int4 *__restrict__ v, size_
     uint32_t acc = 0;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) acc ^= fold(v[i]);
     if (acc == 0x12345678u) out[0] = acc;
+}
+// W: plain grid-stride 16-byte WRITES, 256-thread blocks (what a generator such as k_sim_emit can hope for; run before the buffer is read)
+__global__ __launch_bounds__(256) void k_write(int4 *__restrict__ v, size_t n, int x) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) v[i] = make_int4(x, (int)i, x, (int)i);
 }
 // B: one wave (64-thread block) per 8 KB chunk, all 8 loads issued, then consumed
 __global__ __launch_bounds__(64) void k_chunk(const int4 *__restrict__ v, size_t n, uint32_t *out) {
@@ -209,6 +214,12 @@ int main(int argc, char **argv) {
     };
     const bool only_real = getenv("PROBE_ONLY_REAL") != nullptr;
     if (!only_real) {
+    int4 *wbuf; CK(hipMalloc(&wbuf, bytes)); // a buffer of its own: the reads below keep their data
+    time("W plain 16-byte writes, 2048 blocks x256", [&] { hipLaunchKernelGGL(k_write, dim3(2048), dim3(256), 0, 0, wbuf, n, 1); });
+    time("W plain 16-byte writes, 8192 blocks x256", [&] { hipLaunchKernelGGL(k_write, dim3(8192), dim3(256), 0, 0, wbuf, n, 1); });
+    time("W plain, one 16B write per thread (n/256 blocks)", [&] { hipLaunchKernelGGL(k_write, dim3((unsigned)(n / 256)), dim3(256), 0, 0, wbuf, n, 1); });
+    CK(hipFree(wbuf));
+    if (getenv("PROBE_ONLY_WRITE")) return 0;
     time("A plain grid-stride, 2048 blocks x256", [&] { hipLaunchKernelGGL(k_plain, dim3(2048), dim3(256), 0, 0, d, n, o); });
     time("A plain grid-stride, 8192 blocks x256", [&] { hipLaunchKernelGGL(k_plain, dim3(8192), dim3(256), 0, 0, d, n, o); });
     time("A plain, one 16B per thread (n/256 blocks)", [&] { hipLaunchKernelGGL(k_plain, dim3((unsigned)(n / 256)), dim3(256), 0, 0, d, n, o); });
