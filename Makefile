@@ -19,7 +19,7 @@ build/%.o: $(CSRC)/%.hip $(CSRC)/pg_job_rule.h $(CSRC)/pg_internal.h $(CSRC)/pg_
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
-poregen_amd/libpgmove.so: build/pg_kernels.o build/pg_place.o build/pg_api.o build/pg_model.o build/pg_job.o build/pg_text.o build/pg_kfreq.o build/pg_f1.o build/pg_pamean.o build/pg_svb.o build/pg_dumptext.o build/pg_transform.o build/pg_mvops.o build/pg_pool.o build/pg_evstat.o build/pg_fit.o build/pg_realign.o build/pg_sim.o
+poregen_amd/libpgmove.so: build/pg_kernels.o build/pg_place.o build/pg_api.o build/pg_model.o build/pg_job.o build/pg_text.o build/pg_kfreq.o build/pg_f1.o build/pg_pamean.o build/pg_svb.o build/pg_svbenc.o build/pg_dumptext.o build/pg_transform.o build/pg_mvops.o build/pg_pool.o build/pg_evstat.o build/pg_fit.o build/pg_realign.o build/pg_sim.o
 	$(CXX) -shared -o $@ $^ -Wl,--allow-shlib-undefined -ldl -lpthread
 
 poregen_amd/_pg_hosttest.so: $(CSRC)/pg_hosttest.cpp $(CSRC)/pg_job_rule.h $(CSRC)/pg_hostmem.h $(CSRC)/pg_select.h $(CSRC)/pg_model.h $(CSRC)/pg_pamean.h $(CSRC)/pg_svb.h $(CSRC)/pg_dumphost.h $(CSRC)/pg_kfreq_codes.h $(CSRC)/pg_kfreq_fasta.h $(CSRC)/pg_kfreq_text.h $(CSRC)/pg_mvops.h $(CSRC)/pg_dumptext.h $(CSRC)/pg_pool.h $(CSRC)/pg_evstat.h $(CSRC)/pg_fit.h $(CSRC)/pg_realign.h $(CSRC)/pg_sim.h $(CSRC)/pg_bcdec.h $(CSRC)/host/pg_dumpdir.h $(CSRC)/host/io.cpp $(CSRC)/host/dump.cpp $(CSRC)/host/pg_host.h
@@ -34,14 +34,14 @@ bin/poregen: $(CSRC)/pg_fit.h $(CSRC)/pg_realign.h $(CSRC)/pg_sim.h $(CSRC)/pg_e
 # measurement build: counts the reads whose selection leaves the fast path (tools/count_fallbacks.py)
 fallback_probe:
 	@mkdir -p build/fb
-	for f in pg_kernels pg_place pg_api pg_model pg_job pg_text pg_kfreq pg_f1 pg_pamean pg_svb pg_dumptext pg_transform pg_mvops pg_pool pg_evstat pg_fit pg_realign pg_sim; do $(HIPCC) $(HIPFLAGS) -DPG_COUNT_FALLBACKS -c -o build/fb/$$f.o $(CSRC)/$$f.hip || exit 1; done
-	$(CXX) -shared -o build/fb/libpgmove_fb.so build/fb/pg_kernels.o build/fb/pg_place.o build/fb/pg_api.o build/fb/pg_model.o build/fb/pg_job.o build/fb/pg_text.o build/fb/pg_kfreq.o build/fb/pg_f1.o build/fb/pg_pamean.o build/fb/pg_svb.o build/fb/pg_dumptext.o build/fb/pg_transform.o build/fb/pg_mvops.o build/fb/pg_pool.o build/fb/pg_evstat.o build/fb/pg_fit.o build/fb/pg_realign.o build/fb/pg_sim.o -Wl,--allow-shlib-undefined
+	for f in pg_kernels pg_place pg_api pg_model pg_job pg_text pg_kfreq pg_f1 pg_pamean pg_svb pg_svbenc pg_dumptext pg_transform pg_mvops pg_pool pg_evstat pg_fit pg_realign pg_sim; do $(HIPCC) $(HIPFLAGS) -DPG_COUNT_FALLBACKS -c -o build/fb/$$f.o $(CSRC)/$$f.hip || exit 1; done
+	$(CXX) -shared -o build/fb/libpgmove_fb.so build/fb/pg_kernels.o build/fb/pg_place.o build/fb/pg_api.o build/fb/pg_model.o build/fb/pg_job.o build/fb/pg_text.o build/fb/pg_kfreq.o build/fb/pg_f1.o build/fb/pg_pamean.o build/fb/pg_svb.o build/fb/pg_svbenc.o build/fb/pg_dumptext.o build/fb/pg_transform.o build/fb/pg_mvops.o build/fb/pg_pool.o build/fb/pg_evstat.o build/fb/pg_fit.o build/fb/pg_realign.o build/fb/pg_sim.o -Wl,--allow-shlib-undefined
 
 # A/B builds: `make variant NAME=x EXTRA="-DPG_..."` -> build/x/libpgmove.so (bench.py --lib, tools/ab_lib.sh)
 variant:
 	@mkdir -p build/$(NAME)
-	for f in pg_kernels pg_place pg_api pg_model pg_job pg_text pg_kfreq pg_f1 pg_pamean pg_svb pg_dumptext pg_transform pg_mvops pg_pool pg_evstat pg_fit pg_realign pg_sim; do $(HIPCC) $(HIPFLAGS) $(EXTRA) -c -o build/$(NAME)/$$f.o $(CSRC)/$$f.hip || exit 1; done
-	$(CXX) -shared -o build/$(NAME)/libpgmove.so build/$(NAME)/pg_kernels.o build/$(NAME)/pg_place.o build/$(NAME)/pg_api.o build/$(NAME)/pg_model.o build/$(NAME)/pg_job.o build/$(NAME)/pg_text.o build/$(NAME)/pg_kfreq.o build/$(NAME)/pg_f1.o build/$(NAME)/pg_pamean.o build/$(NAME)/pg_svb.o build/$(NAME)/pg_dumptext.o build/$(NAME)/pg_transform.o build/$(NAME)/pg_mvops.o build/$(NAME)/pg_pool.o build/$(NAME)/pg_evstat.o build/$(NAME)/pg_fit.o build/$(NAME)/pg_realign.o build/$(NAME)/pg_sim.o -Wl,--allow-shlib-undefined -ldl -lpthread
+	for f in pg_kernels pg_place pg_api pg_model pg_job pg_text pg_kfreq pg_f1 pg_pamean pg_svb pg_svbenc pg_dumptext pg_transform pg_mvops pg_pool pg_evstat pg_fit pg_realign pg_sim; do $(HIPCC) $(HIPFLAGS) $(EXTRA) -c -o build/$(NAME)/$$f.o $(CSRC)/$$f.hip || exit 1; done
+	$(CXX) -shared -o build/$(NAME)/libpgmove.so build/$(NAME)/pg_kernels.o build/$(NAME)/pg_place.o build/$(NAME)/pg_api.o build/$(NAME)/pg_model.o build/$(NAME)/pg_job.o build/$(NAME)/pg_text.o build/$(NAME)/pg_kfreq.o build/$(NAME)/pg_f1.o build/$(NAME)/pg_pamean.o build/$(NAME)/pg_svb.o build/$(NAME)/pg_svbenc.o build/$(NAME)/pg_dumptext.o build/$(NAME)/pg_transform.o build/$(NAME)/pg_mvops.o build/$(NAME)/pg_pool.o build/$(NAME)/pg_evstat.o build/$(NAME)/pg_fit.o build/$(NAME)/pg_realign.o build/$(NAME)/pg_sim.o -Wl,--allow-shlib-undefined -ldl -lpthread
 
 oracle_build:
 	$(MAKE) -C oracle

@@ -119,6 +119,12 @@
  * pg_sim_parse_model / _parse_dwell a model file with its level_stdv column, the file `poregen model --dwell_model` writes
  * pg_sim_set_model / _generate /    k-mer model + sequences -> raw signal + the ops that are true by construction, laid out as a pg_batch
  * _kernel_ms / _walk
+ *
+ * The writing side of the svb-zd signal blocks pg_sigdec_* reads (slow5lib's svb-zd press on the host):
+ * pg_sigenc_create / _destroy /     (no counterpart)
+ * _last_error / _set_stream / _stream
+ * pg_sigenc_bound / _encode /       int16 samples on the device -> the shortest svb-zd block of every read, back to back
+ * _kernel_ms
  */
 #ifndef PGMOVE_H
 #define PGMOVE_H
@@ -1084,6 +1090,39 @@ pg_status pg_sim_parse_model(const char *text, size_t n, uint32_t want_k, uint32
  * empty or "nan" median is skipped. dwells_out (cap_slots >= 4^k): 0 for a k-mer the file does not give. PG_ERR_INPUT: refused as a whole
  * (a median that is no number or outside 1 to 4096, a k-mer twice, a letter outside ACGTU, two lengths, no k-mer), err names the line. */
 pg_status pg_sim_parse_dwell(const char *text, size_t n, uint32_t want_k, uint32_t *kmer_size_out, uint32_t *dwells_out, size_t cap_slots, char *err, size_t err_cap);
+
+/* ---- svb-zd signal blocks encoded on the device -----------------------------------------------------------------------------------
+ * The block of a read of n int16 samples (the layout pg_sigdec_* reads) is the shortest one, which is what slow5lib writes:
+ * d_i = s_i - s_{i-1} in int32 from s_{-1} = 0, v_i = (d_i << 1) ^ (d_i >> 31), each v_i in the fewest of 1, 2 or 3 little-endian bytes
+ * (int16 samples cannot give a 4-byte value), the unused bits of the last control byte 0 and nothing behind the data bytes; n = 0 is the
+ * 4-byte block. The blocks of a batch lie back to back in read order, at whatever byte offsets that gives.
+ * No CPU fallback: PG_ERR_NO_DEVICE without a GPU. */
+typedef struct pg_sigenc pg_sigenc;
+typedef struct {
+    uint32_t struct_size, reserved;/* sizeof(pg_sigenc_result), set by the caller */
+    uint64_t n_block_bytes;        /* = block_off[n_reads] */
+    const uint8_t *blocks;         /* DEVICE memory of the handle: complete when the call returns, valid until the next pg_sigenc_encode or
+                                    * pg_sigenc_destroy on the handle */
+    const uint64_t *block_off;     /* HOST memory of the handle, n_reads + 1 offsets into blocks, valid as long. blocks, n_block_bytes and
+                                    * block_off are directly usable as a pg_svb_batch with PG_LOC_DEVICE. */
+} pg_sigenc_result;
+pg_status pg_sigenc_create(int32_t device, pg_sigenc **out);
+void      pg_sigenc_destroy(pg_sigenc *h);
+const char *pg_sigenc_last_error(const pg_sigenc *h); /* h may be NULL: error of the last failed pg_sigenc_create */
+/* Run on a caller-owned hipStream_t (waits for the work the handle has on the stream in use first); NULL restores the handle's own. */
+pg_status pg_sigenc_set_stream(pg_sigenc *h, void *hip_stream);
+void     *pg_sigenc_stream(const pg_sigenc *h);
+/* Host only. No batch with these offsets encodes to more bytes: the sum of 4 + ceil(n / 4) + 3 n over its reads. UINT64_MAX for
+ * offsets that decrease (or null offsets with n_reads > 0). */
+uint64_t  pg_sigenc_bound(const uint64_t *sig_off, uint64_t n_reads);
+/* Read r is sig[sig_off[r] ... sig_off[r + 1]); sig_off is host memory, n_reads + 1 non-decreasing offsets. location says where sig
+ * lies: PG_LOC_HOST, any host memory (copied to a buffer of the handle), or PG_LOC_DEVICE, memory of the handle's device, complete
+ * before the call; it is read in place. Returns when the blocks are there. Refused before anything is allocated: offsets that decrease
+ * (PG_ERR_INPUT), a read of more than 2^32 - 1 samples, more than 2^28 samples in one call (both PG_ERR_UNSUPPORTED: encode fewer
+ * reads at a time); the handle stays usable. */
+pg_status pg_sigenc_encode(pg_sigenc *h, const int16_t *sig, const uint64_t *sig_off, uint64_t n_reads, int32_t location, pg_sigenc_result *out);
+/* HIP-event time of the sizes kernel and of the emit kernel since the last call of this function, in ms. */
+pg_status pg_sigenc_kernel_ms(pg_sigenc *h, double *lens_ms, double *emit_ms);
 
 
 #ifdef __cplusplus

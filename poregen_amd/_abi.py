@@ -65,6 +65,7 @@ EXPORTS = [
     "pg_realign_walk",
     "pg_sim_create", "pg_sim_destroy", "pg_sim_last_error", "pg_sim_set_stream", "pg_sim_stream", "pg_sim_set_model", "pg_sim_generate", "pg_sim_kernel_ms", "pg_sim_walk",
     "pg_sim_parse_model", "pg_sim_parse_dwell",
+    "pg_sigenc_create", "pg_sigenc_destroy", "pg_sigenc_last_error", "pg_sigenc_set_stream", "pg_sigenc_stream", "pg_sigenc_bound", "pg_sigenc_encode", "pg_sigenc_kernel_ms",
 ]
 PG_JOB_EXCHANGE_AUTO, PG_JOB_EXCHANGE_HOST, PG_JOB_EXCHANGE_RCCL = 0, 1, 2
 
@@ -153,6 +154,10 @@ class PgPameanBatch(C.Structure):
 
 class PgPameanResult(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_fallback", C.c_uint64), ("n_samples", C.c_uint64), ("mean", C.c_double), ("sstdev", C.c_double)]
+
+
+class PgSigencResult(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("n_block_bytes", C.c_uint64), ("blocks", C.c_void_p), ("block_off", C.c_void_p)]
 
 
 class PgSvbBatch(C.Structure):
@@ -418,5 +423,14 @@ def load():
         lib.pg_sim_walk.restype = i32
         lib.pg_sim_parse_model.argtypes = [C.c_char_p, C.c_size_t, u32, C.POINTER(u32), vp, vp, C.c_size_t, C.POINTER(i32), C.c_char_p, C.c_size_t]; lib.pg_sim_parse_model.restype = i32
         lib.pg_sim_parse_dwell.argtypes = [C.c_char_p, C.c_size_t, u32, C.POINTER(u32), vp, C.c_size_t, C.c_char_p, C.c_size_t]; lib.pg_sim_parse_dwell.restype = i32
+    if hasattr(lib, "pg_sigenc_create"):  # (as above: a library built from an older tree has no encoder)
+        lib.pg_sigenc_create.argtypes = [i32, C.POINTER(vp)]; lib.pg_sigenc_create.restype = i32
+        lib.pg_sigenc_destroy.argtypes = [vp]; lib.pg_sigenc_destroy.restype = None
+        lib.pg_sigenc_last_error.argtypes = [vp]; lib.pg_sigenc_last_error.restype = C.c_char_p
+        lib.pg_sigenc_set_stream.argtypes = [vp, vp]; lib.pg_sigenc_set_stream.restype = i32
+        lib.pg_sigenc_stream.argtypes = [vp]; lib.pg_sigenc_stream.restype = vp
+        lib.pg_sigenc_bound.argtypes = [vp, C.c_uint64]; lib.pg_sigenc_bound.restype = C.c_uint64
+        lib.pg_sigenc_encode.argtypes = [vp, vp, vp, C.c_uint64, i32, C.POINTER(PgSigencResult)]; lib.pg_sigenc_encode.restype = i32
+        lib.pg_sigenc_kernel_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]; lib.pg_sigenc_kernel_ms.restype = i32
     _lib = lib
     return lib

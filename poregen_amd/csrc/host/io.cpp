@@ -18,7 +18,9 @@ struct Zstd {
     struct Buf { const void *src; size_t size, pos; };
     struct OBuf { void *dst; size_t size, pos; };
     size_t (*decompress_stream)(void *, OBuf *, Buf *) = nullptr;
-    bool ok = false;
+    size_t (*compress)(void *, size_t, const void *, size_t, int) = nullptr; // the writer's (Slow5Writer, REC_ZSTD)
+    size_t (*compress_bound)(size_t) = nullptr;
+    bool ok = false, can_compress = false;
     Zstd() {
         void *h = nullptr;
         for (const char *n : {"libzstd.so.1", "libzstd.so"}) if ((h = dlopen(n, RTLD_NOW | RTLD_LOCAL))) break;
@@ -31,6 +33,9 @@ struct Zstd {
         init_dstream = (decltype(init_dstream))dlsym(h, "ZSTD_initDStream");
         decompress_stream = (decltype(decompress_stream))dlsym(h, "ZSTD_decompressStream");
         ok = decompress && frame_size && is_error && create_dstream && free_dstream && init_dstream && decompress_stream;
+        compress = (decltype(compress))dlsym(h, "ZSTD_compress");
+        compress_bound = (decltype(compress_bound))dlsym(h, "ZSTD_compressBound");
+        can_compress = compress && compress_bound && is_error;
     }
 };
 const Zstd &zstd() { static const Zstd z; return z; }
@@ -68,6 +73,8 @@ bool zstd_record(const unsigned char *src, size_t n, std::vector<unsigned char> 
 }
 } // namespace
 
+#include <algorithm>
+#include <atomic>
 #include <cctype>
 #include <cstdio>
 #include <cstdlib>
@@ -75,6 +82,7 @@ bool zstd_record(const unsigned char *src, size_t n, std::vector<unsigned char> 
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
+#include <thread>
 #include <unistd.h>
 #include <zlib.h>
 
@@ -323,7 +331,7 @@ bool Slow5File::decode_blow5(const Loc &l, Slow5Rec &out, std::string &err, std:
     if (sig_press_ == 0) {
         if (len > (blen - p) / 2) { err = "corrupt BLOW5 record (signal)"; return false; } // (before the vector is sized by a number the file supplied)
         out.raw.resize(len);
-        memcpy(out.raw.data(), body + p, len * 2);
+        if (len) memcpy(out.raw.data(), body + p, len * 2); // (an empty read: the vector has no storage to name)
         return true;
     }
     // svb-zd: in the record len_raw_signal holds the BYTE length of the compressed signal; the compressed
@@ -731,15 +739,29 @@ static const char kSlow5Cols[] =
 
 Slow5Writer::~Slow5Writer() { if (fp_) fclose((FILE *)fp_); }
 
-bool Slow5Writer::open(const std::string &path, bool binary, double sampling_rate, std::string &err) {
+bool Slow5Writer::parse_rec_press(const char *name, RecPress &out) {
+    if (!strcmp(name, "none")) out = REC_NONE; else if (!strcmp(name, "zlib")) out = REC_ZLIB; else if (!strcmp(name, "zstd")) out = REC_ZSTD; else return false;
+    return true;
+}
+bool Slow5Writer::parse_sig_press(const char *name, SigPress &out) {
+    if (!strcmp(name, "none")) out = SIG_NONE; else if (!strcmp(name, "svb-zd")) out = SIG_SVB_ZD; else return false;
+    return true;
+}
+bool Slow5Writer::zstd_available() { return zstd().can_compress; }
+
+bool Slow5Writer::open(const std::string &path, bool binary, double sampling_rate, std::string &err) { return open(path, binary, sampling_rate, REC_NONE, SIG_NONE, 1, err); }
+
+bool Slow5Writer::open(const std::string &path, bool binary, double sampling_rate, RecPress rec, SigPress sig, unsigned threads, std::string &err) {
+    if (!binary && (rec != REC_NONE || sig != SIG_NONE)) { err = "an ASCII SLOW5 file is not compressed"; return false; }
+    if (rec == REC_ZSTD && !zstd_available()) { err = "zstd record compression needs libzstd.so.1, which was not found on this machine"; return false; }
     FILE *fp = fopen(path.c_str(), "wb");
     if (!fp) { err = "Could not open " + path + " for writing."; return false; }
-    fp_ = fp; binary_ = binary; rate_ = sampling_rate;
+    fp_ = fp; binary_ = binary; rate_ = sampling_rate; rec_ = rec; sig_ = sig; threads_ = threads ? threads : 1;
     char rate[64]; snprintf(rate, sizeof rate, "%.0f\n", sampling_rate);
     bool ok;
     if (binary) {
-        // 64 bytes: magic, version 0.2.0, record compression none, one read group, signal compression none, zeros; then the ASCII header
-        unsigned char head[64] = {'B', 'L', 'O', 'W', '5', 1, 0, 2, 0, 0, 1, 0, 0, 0, 0};
+        // 64 bytes: magic, version 0.2.0, record compression, one read group, signal compression, zeros; then the ASCII header
+        unsigned char head[64] = {'B', 'L', 'O', 'W', '5', 1, 0, 2, 0, (unsigned char)rec, 1, 0, 0, 0, (unsigned char)sig};
         const std::string text = std::string(kSlow5Attrs) + rate + kSlow5Cols; // (version and read groups are in the 64 bytes)
         const uint32_t hlen = (uint32_t)text.size();
         ok = fwrite(head, 1, 64, fp) == 64 && fwrite(&hlen, 4, 1, fp) == 1 && fwrite(text.data(), 1, text.size(), fp) == text.size();
@@ -749,6 +771,70 @@ bool Slow5Writer::open(const std::string &path, bool binary, double sampling_rat
     return ok;
 }
 
+// one BLOW5 record: written as it is, or kept until enough records wait for the threads
+bool Slow5Writer::put_body(const std::string &read_id, double digitisation, double offset, double range, uint64_t len_field, const void *signal, uint64_t bytes, std::string &err) {
+    FILE *fp = (FILE *)fp_;
+    if (read_id.size() > 0xffff) { err = "a read id of more than 65535 bytes"; return false; }
+    const uint16_t il = (uint16_t)read_id.size();
+    const uint32_t group = 0;
+    const double f[4] = {digitisation, offset, range, rate_};
+    const uint64_t size = 2 + (uint64_t)il + 4 + 32 + 8 + bytes;
+    if (rec_ == REC_NONE) {
+        const bool ok = fwrite(&size, 8, 1, fp) == 1 && fwrite(&il, 2, 1, fp) == 1 && fwrite(read_id.data(), 1, il, fp) == il && fwrite(&group, 4, 1, fp) == 1 && fwrite(f, 8, 4, fp) == 4 &&
+                        fwrite(&len_field, 8, 1, fp) == 1 && (bytes == 0 || fwrite(signal, 1, bytes, fp) == bytes);
+        if (!ok) err = "Error in writing the signal file.";
+        return ok;
+    }
+    if (size > 0x7fffffffull) { err = "a record of 2 GiB or more cannot be compressed"; return false; } // (zlib counts in 32 bits)
+    std::string body;
+    body.reserve(size);
+    body.append((const char *)&il, 2); body += read_id; body.append((const char *)&group, 4); body.append((const char *)f, 32); body.append((const char *)&len_field, 8);
+    body.append((const char *)signal, bytes);
+    waiting_bytes_ += body.size();
+    waiting_.push_back(std::move(body));
+    if (waiting_.size() >= 64 * (size_t)threads_ || waiting_bytes_ >= ((size_t)64 << 20)) return flush(err);
+    return true;
+}
+
+bool Slow5Writer::flush(std::string &err) {
+    FILE *fp = (FILE *)fp_;
+    const size_t n = waiting_.size();
+    if (!n) return true;
+    std::vector<std::string> out(n);
+    std::atomic<size_t> next{0};
+    std::atomic<bool> failed{false};
+    auto work = [&]() {
+        for (size_t i; (i = next.fetch_add(1)) < n;) {
+            const std::string &in = waiting_[i];
+            std::string &o = out[i];
+            if (rec_ == REC_ZLIB) {
+                uLongf dl = compressBound((uLong)in.size());
+                o.resize(dl);
+                if (compress2((Bytef *)&o[0], &dl, (const Bytef *)in.data(), (uLong)in.size(), Z_DEFAULT_COMPRESSION) != Z_OK) { failed = true; return; }
+                o.resize(dl);
+            } else {
+                const Zstd &z = zstd();
+                o.resize(z.compress_bound(in.size()));
+                const size_t got = z.compress(&o[0], o.size(), in.data(), in.size(), 1); // one frame, its content size in the frame header
+                if (z.is_error(got)) { failed = true; return; }
+                o.resize(got);
+            }
+        }
+    };
+    const size_t nt = std::min<size_t>(threads_, n);
+    std::vector<std::thread> pool;
+    for (size_t t = 1; t < nt; t++) pool.emplace_back(work);
+    work();
+    for (std::thread &t : pool) t.join();
+    waiting_.clear(); waiting_bytes_ = 0;
+    if (failed) { err = "Error in compressing a record of the signal file."; return false; }
+    for (size_t i = 0; i < n; i++) {
+        const uint64_t size = out[i].size();
+        if (fwrite(&size, 8, 1, fp) != 1 || fwrite(out[i].data(), 1, out[i].size(), fp) != out[i].size()) { err = "Error in writing the signal file."; return false; }
+    }
+    return true;
+}
+
 // a double as the shortest text that reads back as the same double
 static void exact_double(double v, char *buf, size_t cap) {
     for (int prec = 1; prec <= 17; prec++) { snprintf(buf, cap, "%.*g", prec, v); if (strtod(buf, nullptr) == v) return; }
@@ -756,37 +842,34 @@ static void exact_double(double v, char *buf, size_t cap) {
 
 bool Slow5Writer::add(const std::string &read_id, double digitisation, double offset, double range, const int16_t *raw, uint64_t n, std::string &err) {
     FILE *fp = (FILE *)fp_;
-    bool ok;
-    if (binary_) {
-        if (read_id.size() > 0xffff) { err = "a read id of more than 65535 bytes"; return false; }
-        const uint16_t il = (uint16_t)read_id.size();
-        const uint32_t group = 0;
-        const double f[4] = {digitisation, offset, range, rate_};
-        const uint64_t size = 2 + (uint64_t)il + 4 + 32 + 8 + n * 2;
-        ok = fwrite(&size, 8, 1, fp) == 1 && fwrite(&il, 2, 1, fp) == 1 && fwrite(read_id.data(), 1, il, fp) == il && fwrite(&group, 4, 1, fp) == 1 && fwrite(f, 8, 4, fp) == 4 &&
-             fwrite(&n, 8, 1, fp) == 1 && (n == 0 || fwrite(raw, 2, n, fp) == n);
-    } else {
-        char d[40], o[40], r[40], s[40];
-        exact_double(digitisation, d, sizeof d); exact_double(offset, o, sizeof o); exact_double(range, r, sizeof r); exact_double(rate_, s, sizeof s);
-        line_.clear();
-        line_ += read_id; line_ += "\t0\t"; line_ += d; line_ += '\t'; line_ += o; line_ += '\t'; line_ += r; line_ += '\t'; line_ += s; line_ += '\t';
-        line_ += std::to_string(n); line_ += '\t';
-        char num[16];
-        for (uint64_t i = 0; i < n; i++) { const int len = snprintf(num, sizeof num, i ? ",%d" : "%d", (int)raw[i]); line_.append(num, (size_t)len); }
-        line_ += '\n';
-        ok = fwrite(line_.data(), 1, line_.size(), fp) == line_.size();
-    }
+    if (sig_ != SIG_NONE) { err = "a file with svb-zd signals takes finished blocks"; return false; }
+    if (binary_) return put_body(read_id, digitisation, offset, range, n, raw, n * 2, err);
+    char d[40], o[40], r[40], s[40];
+    exact_double(digitisation, d, sizeof d); exact_double(offset, o, sizeof o); exact_double(range, r, sizeof r); exact_double(rate_, s, sizeof s);
+    line_.clear();
+    line_ += read_id; line_ += "\t0\t"; line_ += d; line_ += '\t'; line_ += o; line_ += '\t'; line_ += r; line_ += '\t'; line_ += s; line_ += '\t';
+    line_ += std::to_string(n); line_ += '\t';
+    char num[16];
+    for (uint64_t i = 0; i < n; i++) { const int len = snprintf(num, sizeof num, i ? ",%d" : "%d", (int)raw[i]); line_.append(num, (size_t)len); }
+    line_ += '\n';
+    const bool ok = fwrite(line_.data(), 1, line_.size(), fp) == line_.size();
     if (!ok) err = "Error in writing the signal file.";
     return ok;
+}
+
+bool Slow5Writer::add_block(const std::string &read_id, double digitisation, double offset, double range, const unsigned char *block, uint64_t len, std::string &err) {
+    if (!binary_ || sig_ != SIG_SVB_ZD) { err = "only a BLOW5 file with svb-zd signals takes blocks"; return false; }
+    return put_body(read_id, digitisation, offset, range, len, block, len, err);
 }
 
 bool Slow5Writer::close(std::string &err) {
     FILE *fp = (FILE *)fp_;
     if (!fp) return true;
-    bool ok = !binary_ || fwrite("5WOLB", 1, 5, fp) == 5;
+    bool ok = flush(err);
+    ok = (!binary_ || fwrite("5WOLB", 1, 5, fp) == 5) && ok;
     ok = (fclose(fp) == 0) && ok;
     fp_ = nullptr;
-    if (!ok) err = "Error in writing the signal file.";
+    if (!ok && err.empty()) err = "Error in writing the signal file.";
     return ok;
 }
 

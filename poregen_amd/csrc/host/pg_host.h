@@ -76,19 +76,37 @@ private:
     bool view_blow5(const Loc &l, RawView &v, std::string &err, std::string *read_id = nullptr) const;
 };
 
-// ---- SLOW5 / BLOW5 writer (`poregen simulate -o`): ASCII SLOW5, or BLOW5 with neither the records nor the signals compressed; one read
-// group; the header lines Slow5File needs to read the file back. Code of its own: nothing of the reading paths is shared or changed.
+// ---- SLOW5 / BLOW5 writer (`poregen simulate -o`): ASCII SLOW5, or BLOW5 -- as it is, or with the records compressed (zlib, zstd) and / or
+// the signals as svb-zd blocks (pg_svb.h) that the caller has encoded; one read group; the header lines Slow5File needs to read the file
+// back. Code of its own: nothing of the reading paths is shared or changed.
 class Slow5Writer {
 public:
+    enum RecPress { REC_NONE = 0, REC_ZLIB = 1, REC_ZSTD = 2 }; // header byte 9
+    enum SigPress { SIG_NONE = 0, SIG_SVB_ZD = 1 };            // header byte 14
+    static bool parse_rec_press(const char *name, RecPress &out); // "none", "zlib", "zstd"
+    static bool parse_sig_press(const char *name, SigPress &out); // "none", "svb-zd"
+    static bool zstd_available();                                 // libzstd.so.1 with what REC_ZSTD needs is on this machine
     ~Slow5Writer();
-    bool open(const std::string &path, bool binary, double sampling_rate, std::string &err);
-    bool add(const std::string &read_id, double digitisation, double offset, double range, const int16_t *raw, uint64_t n, std::string &err);
+    bool open(const std::string &path, bool binary, double sampling_rate, std::string &err); // nothing compressed
+    // BLOW5 with the two methods; threads: records are compressed on that many threads (each record on its own, written in the order they
+    // were added: the file does not depend on the number). An ASCII file takes REC_NONE and SIG_NONE alone.
+    bool open(const std::string &path, bool binary, double sampling_rate, RecPress rec, SigPress sig, unsigned threads, std::string &err);
+    bool add(const std::string &read_id, double digitisation, double offset, double range, const int16_t *raw, uint64_t n, std::string &err); // SIG_NONE
+    // SIG_SVB_ZD: a finished block of `len` bytes; the record's len_raw_signal holds len
+    bool add_block(const std::string &read_id, double digitisation, double offset, double range, const unsigned char *block, uint64_t len, std::string &err);
     bool close(std::string &err); // writes the end-of-file marker of a BLOW5 file
 private:
+    bool put_body(const std::string &read_id, double digitisation, double offset, double range, uint64_t len_field, const void *signal, uint64_t bytes, std::string &err);
+    bool flush(std::string &err); // compresses and writes the waiting records
     void *fp_ = nullptr; // FILE *
     bool binary_ = false;
     double rate_ = 4000.0;
+    RecPress rec_ = REC_NONE;
+    SigPress sig_ = SIG_NONE;
+    unsigned threads_ = 1;
     std::string line_;
+    std::vector<std::string> waiting_; // record bodies not yet compressed
+    size_t waiting_bytes_ = 0;
 };
 
 // ---- FASTA/FASTQ with faidx semantics (replaces fai_load / faidx_fetch_seq, src/gmove.cpp:724,805) -----

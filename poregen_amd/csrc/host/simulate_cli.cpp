@@ -2,7 +2,8 @@
 // asks squigulator (scripts/sim.sh); the rule here is this project's own, fit's inverted (csrc/pg_sim.h, pg_sim_* of include/pgmove.h), and
 // no squigulator output is reproduced. Reads are drawn from the reference sequences on the host (stream 0 of the generator), the signal and
 // the ops come from the device, batch after batch; the files that belong together are written from them:
-//   -o reads.slow5 / .blow5   the signal (ASCII SLOW5, or BLOW5 with nothing compressed)
+//   -o reads.slow5 / .blow5   the signal (ASCII SLOW5, or BLOW5: as it is, or with --compress zlib|zstd records and / or --sig_compress svb-zd
+//                             signals, whose blocks are encoded on the device (pg_sigenc_*) and copied back in place of the samples)
 //   -c FILE                   the TRUE alignment, as the PAF `poregen reform -c -k 1 -m 0 --stride 0 [--rna]` prints
 //   -q FILE                   the reads as FASTQ
 //   --moves FILE              a headerless SAM as a basecaller writes it: mv:B:c with every true boundary rounded to the stride from ts
@@ -18,6 +19,7 @@
 #include <cstring>
 #include <getopt.h>
 #include <string>
+#include <thread>
 #include <vector>
 
 namespace {
@@ -41,6 +43,8 @@ const struct option kLongOptions[] = {
     {"stride", required_argument, nullptr, 0},        // 15
     {"batch_reads", required_argument, nullptr, 0},   // 16
     {"device", required_argument, nullptr, 0},        // 17
+    {"compress", required_argument, nullptr, 0},      // 18
+    {"sig_compress", required_argument, nullptr, 0},  // 19
     {"help", no_argument, nullptr, 'h'},
     {nullptr, 0, nullptr, 0}};
 
@@ -65,7 +69,10 @@ void print_help(FILE *fp) {
     fprintf(fp, "   --offset INT               [10]\n");
     fprintf(fp, "   --offset_spread INT        a read's offset is uniform within +-INT of --offset [10]\n");
     fprintf(fp, "   --lead INT                 samples in front of the first event [0]\n");
-    fprintf(fp, "   -o FILE                    the signal: .slow5 (ASCII) or .blow5 (uncompressed)\n");
+    fprintf(fp, "   -o FILE                    the signal: .slow5 (ASCII) or .blow5\n");
+    fprintf(fp, "   --compress STR             .blow5: record compression, none, zlib or zstd [none]\n");
+    fprintf(fp, "   --sig_compress STR         .blow5: signal compression, none or svb-zd (encoded on the device) [none]\n");
+    fprintf(fp, "   -t INT                     threads that compress records, at most 16 [the smaller of 16 and the machine's]\n");
     fprintf(fp, "   -c FILE                    the true alignment: PAF with ss:Z:\n");
     fprintf(fp, "   -q FILE                    the reads: FASTQ\n");
     fprintf(fp, "   --moves FILE               SAM with mv:B:c, ts:i: and ns:i:, the boundaries rounded to --stride\n");
@@ -128,14 +135,16 @@ char complement(char c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C
 
 int simulate_main(int argc, char **argv) {
     long long k_opt = 0, m = 0, n_reads = 1000, read_len = 4000, dwell_mean = 10, spread = 50, digitisation = 8192, offset = 10, off_spread = 10, lead = 0, stride = 0, batch_reads = 2000,
-              device = 0;
+              device = 0, threads = 0;
+    pgh::Slow5Writer::RecPress rec_press = pgh::Slow5Writer::REC_NONE;
+    pgh::Slow5Writer::SigPress sig_press = pgh::Slow5Writer::SIG_NONE;
     unsigned long long seed = 0;
     uint32_t noise_q8 = 256, range_e4 = 14676100;
     bool rna = false, full = false, ideal = false, help = false;
     const char *out_path = nullptr, *paf_path = nullptr, *fq_path = nullptr, *sam_path = nullptr, *dwell_path = nullptr;
     int c, longindex = 0;
     optind = 1;
-    while ((c = getopt_long(argc, argv, "k:m:n:o:c:q:h", kLongOptions, &longindex)) >= 0) {
+    while ((c = getopt_long(argc, argv, "k:m:n:o:c:q:t:h", kLongOptions, &longindex)) >= 0) {
         bool ok = true;
         if (c == 'k') ok = whole_int(optarg, 1, PG_FIT_MAX_K, k_opt);
         else if (c == 'm') ok = whole_int(optarg, 0, 64, m);
@@ -143,6 +152,7 @@ int simulate_main(int argc, char **argv) {
         else if (c == 'o') out_path = optarg;
         else if (c == 'c') paf_path = optarg;
         else if (c == 'q') fq_path = optarg;
+        else if (c == 't') ok = whole_int(optarg, 1, 1 << 20, threads);
         else if (c == 'h') help = true;
         else if (c == 0 && longindex == 0) rna = true;
         else if (c == 0 && longindex == 1) ok = whole_u64(optarg, seed);
@@ -162,6 +172,8 @@ int simulate_main(int argc, char **argv) {
         else if (c == 0 && longindex == 15) ok = whole_int(optarg, 1, 127, stride);
         else if (c == 0 && longindex == 16) ok = whole_int(optarg, 1, 1 << 20, batch_reads);
         else if (c == 0 && longindex == 17) ok = whole_int(optarg, 0, 1024, device);
+        else if (c == 0 && longindex == 18) ok = pgh::Slow5Writer::parse_rec_press(optarg, rec_press);
+        else if (c == 0 && longindex == 19) ok = pgh::Slow5Writer::parse_sig_press(optarg, sig_press);
         else { print_help(stderr); return EXIT_FAILURE; }
         if (!ok) {
             fprintf(stderr, "[simulate] %s%s: '%s' is not a value it takes\n", c ? "-" : "--", c ? std::string(1, (char)c).c_str() : kLongOptions[longindex].name, optarg);
@@ -173,6 +185,13 @@ int simulate_main(int argc, char **argv) {
     if (!out_path) return die("[simulate] -o reads.slow5 or reads.blow5 is required");
     const bool blow5 = ends_with(out_path, ".blow5");
     if (!blow5 && !ends_with(out_path, ".slow5")) return die("[simulate] the signal goes to a .slow5 or .blow5 file, not %s", out_path);
+    const bool svb = sig_press == pgh::Slow5Writer::SIG_SVB_ZD;
+    if (!blow5 && (svb || rec_press != pgh::Slow5Writer::REC_NONE)) return die("[simulate] --compress and --sig_compress are for a .blow5 file; %s is ASCII", out_path);
+    if (rec_press == pgh::Slow5Writer::REC_ZSTD && !pgh::Slow5Writer::zstd_available())
+        return die("[simulate] --compress zstd needs libzstd.so.1, which was not found on this machine");
+    // (a command may use 16 CPUs where the machine shows many times as many)
+    if (!threads) threads = std::max(1u, std::thread::hardware_concurrency());
+    threads = std::min(threads, 16ll);
     if (!stride) stride = rna ? 10 : 5;
     const char *model_path = argv[optind], *ref_path = argv[optind + 1];
     if (!pg_sim_q((uint32_t)digitisation, range_e4)) return die("[simulate] --digitisation / --range is too large (digitisation 10 2^32 / range in 1e-4 pA must stay below 2^40)");
@@ -227,7 +246,7 @@ int simulate_main(int argc, char **argv) {
     prm.lead_stdv = n_level ? (uint32_t)((2 * sum_stdv + n_level) / (2 * n_level)) : 0u;
 
     pgh::Slow5Writer s5;
-    if (!s5.open(out_path, blow5, 4000.0, err)) return die("%s", err);
+    if (!s5.open(out_path, blow5, 4000.0, rec_press, sig_press, (unsigned)threads, err)) return die("%s", err);
     FILE *paf = nullptr, *fq = nullptr, *sam = nullptr;
     auto close_all = [&]() { bool ok = true; for (FILE **f : {&paf, &fq, &sam}) if (*f) { ok = (fclose(*f) == 0) && ok; *f = nullptr; } return ok; };
     for (auto pf : {std::make_pair(paf_path, &paf), std::make_pair(fq_path, &fq), std::make_pair(sam_path, &sam)})
@@ -237,9 +256,12 @@ int simulate_main(int argc, char **argv) {
     if (pg_sim_create(&prm, (int32_t)device, &sim) != PG_OK) { fprintf(stderr, "[simulate] %s\n", pg_sim_last_error(nullptr)); close_all(); return EXIT_FAILURE; }
     int status = EXIT_SUCCESS;
     if (pg_sim_set_model(sim, levels.data(), stdvs.data(), dwells.data(), k) != PG_OK) { fprintf(stderr, "[simulate] %s\n", pg_sim_last_error(sim)); status = EXIT_FAILURE; }
+    pg_sigenc *enc = nullptr;
+    if (svb && status == EXIT_SUCCESS && pg_sigenc_create((int32_t)device, &enc) != PG_OK) { fprintf(stderr, "[simulate] %s\n", pg_sigenc_last_error(nullptr)); status = EXIT_FAILURE; }
 
     const uint64_t want = full ? contigs.size() : (uint64_t)n_reads;
-    uint64_t written = 0, refused[4] = {0, 0, 0, 0}, samples = 0, bases = 0;
+    uint64_t written = 0, refused[4] = {0, 0, 0, 0}, samples = 0, bases = 0, sig_copied = 0;
+    std::vector<uint8_t> blocks; const uint64_t *block_off = nullptr;
     std::vector<uint8_t> seq; std::vector<uint64_t> seq_off; std::vector<int16_t> sig; std::vector<uint32_t> ops; std::vector<uint64_t> sig_off, op_off; std::vector<double> offs;
     std::string line;
     for (uint64_t first = 0; first < want && status == EXIT_SUCCESS;) {
@@ -266,12 +288,24 @@ int simulate_main(int argc, char **argv) {
         pg_status st = pg_sim_generate(sim, &b, &res);
         if (st == PG_ERR_UNSUPPORTED && batch_reads > 1) { batch_reads = (batch_reads + 1) / 2; continue; } // too many samples at once: the same reads in smaller batches
         if (st != PG_OK) { fprintf(stderr, "[simulate] %s\n", pg_sim_last_error(sim)); status = EXIT_FAILURE; break; }
-        sig.resize(res.n_samples); ops.resize(res.n_ops); sig_off.resize(n + 1); op_off.resize(n + 1); offs.resize(n);
+        ops.resize(res.n_ops); sig_off.resize(n + 1); op_off.resize(n + 1); offs.resize(n);
         auto hip_ok = [&](hipError_t e) { if (e == hipSuccess) return true; fprintf(stderr, "[simulate] hipMemcpy: %s\n", hipGetErrorString(e)); status = EXIT_FAILURE; return false; };
-        if ((res.n_samples && !hip_ok(hipMemcpy(sig.data(), res.sig, res.n_samples * 2, hipMemcpyDeviceToHost))) || (res.n_ops && !hip_ok(hipMemcpy(ops.data(), res.op_n, res.n_ops * 4, hipMemcpyDeviceToHost))) ||
+        if ((res.n_ops && !hip_ok(hipMemcpy(ops.data(), res.op_n, res.n_ops * 4, hipMemcpyDeviceToHost))) ||
             !hip_ok(hipMemcpy(sig_off.data(), res.sig_off, (n + 1) * 8, hipMemcpyDeviceToHost)) || !hip_ok(hipMemcpy(op_off.data(), res.op_off, (n + 1) * 8, hipMemcpyDeviceToHost)) ||
             (n && !hip_ok(hipMemcpy(offs.data(), res.offset, n * 8, hipMemcpyDeviceToHost))))
             break;
+        if (svb) {
+            // the samples stay where the simulator left them: their blocks are encoded there, and the blocks are what crosses to the host
+            pg_sigenc_result er; memset(&er, 0, sizeof er); er.struct_size = sizeof er;
+            if (pg_sigenc_encode(enc, res.sig, sig_off.data(), n, PG_LOC_DEVICE, &er) != PG_OK) { fprintf(stderr, "[simulate] %s\n", pg_sigenc_last_error(enc)); status = EXIT_FAILURE; break; }
+            blocks.resize(er.n_block_bytes); block_off = er.block_off;
+            if (er.n_block_bytes && !hip_ok(hipMemcpy(blocks.data(), er.blocks, er.n_block_bytes, hipMemcpyDeviceToHost))) break;
+            sig_copied += er.n_block_bytes;
+        } else {
+            sig.resize(res.n_samples);
+            if (res.n_samples && !hip_ok(hipMemcpy(sig.data(), res.sig, res.n_samples * 2, hipMemcpyDeviceToHost))) break;
+            sig_copied += res.n_samples * 2;
+        }
         for (uint64_t i = 0; i < n && status == EXIT_SUCCESS; i++) {
             const uint32_t rs = res.status_host[i];
             if (rs != PG_SIM_ST_OK) { refused[rs < 4 ? rs : 0]++; continue; }
@@ -279,7 +313,9 @@ int simulate_main(int argc, char **argv) {
             const uint64_t ns = sig_off[i + 1] - sig_off[i], lb = op_off[i + 1] - op_off[i];
             const uint32_t *o = ops.data() + op_off[i];
             const char *bases_p = (const char *)seq.data() + seq_off[i];
-            if (!s5.add(id, (double)digitisation, offs[i], (double)range_e4 / 10000.0, sig.data() + sig_off[i], ns, err)) { status = die("%s", err); break; }
+            const double range = (double)range_e4 / 10000.0;
+            if (!(svb ? s5.add_block(id, (double)digitisation, offs[i], range, blocks.data() + block_off[i], block_off[i + 1] - block_off[i], err)
+                      : s5.add(id, (double)digitisation, offs[i], range, sig.data() + sig_off[i], ns, err))) { status = die("%s", err); break; }
             if (paf) {
                 line = id + "\t" + std::to_string(ns) + "\t" + std::to_string(lead) + "\t" + std::to_string(ns) + "\t+\t" + id + "\t" + std::to_string(lb) + "\t" +
                        std::to_string(rna ? lb : 0) + "\t" + std::to_string(rna ? 0 : lb) + "\t" + std::to_string(lb) + "\t" + std::to_string(lb) + "\t255\tss:Z:";
@@ -311,6 +347,10 @@ int simulate_main(int argc, char **argv) {
         fprintf(stderr, "[simulate] k=%u reads=%llu written=%llu refused=%llu (too_short=%llu bad_base=%llu no_level=%llu) bases=%llu samples=%llu\n", k, (unsigned long long)want,
                 (unsigned long long)written, (unsigned long long)(want - written), (unsigned long long)refused[1], (unsigned long long)refused[2], (unsigned long long)refused[3],
                 (unsigned long long)bases, (unsigned long long)samples);
+    if (status == EXIT_SUCCESS && (svb || rec_press != pgh::Slow5Writer::REC_NONE))
+        fprintf(stderr, "[simulate] signal: sig_compress=%s compress=%s threads=%lld signal bytes copied from the device=%llu\n", svb ? "svb-zd" : "none",
+                rec_press == pgh::Slow5Writer::REC_ZLIB ? "zlib" : rec_press == pgh::Slow5Writer::REC_ZSTD ? "zstd" : "none", threads, (unsigned long long)sig_copied);
+    pg_sigenc_destroy(enc);
     pg_sim_destroy(sim);
     return status;
 }

@@ -656,3 +656,29 @@ extern "C" int pgt_sim_write_slow5(const char *path, int binary, uint64_t n, con
         if (!w.add(ids, dig[i], off[i], range[i], raw + raw_off[i], raw_off[i + 1] - raw_off[i], err)) return -1;
     return w.close(err) ? 0 : -1;
 }
+
+// ---- svb-zd written (pg_svb.h: the encoder's rule; host/io.cpp: the writer that takes the blocks) -------------------------------------
+extern "C" uint64_t pgt_svb_bound(uint64_t n) { return pg_svb_bound(n); }
+extern "C" uint32_t pgt_svb_max_v(void) { return PG_SVB_MAX_V; }
+// the block of one read into out (cap >= pg_svb_bound(n), else nothing is written); returns its bytes
+extern "C" uint64_t pgt_svb_encode(const int16_t *s, uint32_t n, uint8_t *out, uint64_t cap) {
+    return cap >= pg_svb_bound(n) ? pg_svb_encode_host(s, n, out) : 0;
+}
+extern "C" int pgt_zstd_can_compress(void) { return pgh::Slow5Writer::zstd_available() ? 1 : 0; }
+// the writer with its two methods by name: n records from raw samples (sig "none") or from finished blocks (sig "svb-zd", sig_off then
+// counts bytes); 0, -1 (errbuf), or -2 for a name the writer does not know
+extern "C" int pgt_sim_write_blow5(const char *path, int binary, const char *rec, const char *sig, unsigned threads, uint64_t n, const char *ids, const double *dig,
+                                   const double *off, const double *range, const void *signal, const uint64_t *sig_off, char *errbuf, size_t ecap) {
+    pgh::Slow5Writer::RecPress rp; pgh::Slow5Writer::SigPress sp;
+    if (!pgh::Slow5Writer::parse_rec_press(rec, rp) || !pgh::Slow5Writer::parse_sig_press(sig, sp)) return -2;
+    pgh::Slow5Writer w; std::string err;
+    if (!w.open(path, binary != 0, 4000.0, rp, sp, threads, err)) { put_err(err, errbuf, ecap); return -1; }
+    for (uint64_t i = 0; i < n; i++, ids += strlen(ids) + 1) {
+        const uint64_t len = sig_off[i + 1] - sig_off[i];
+        const bool ok = sp == pgh::Slow5Writer::SIG_SVB_ZD ? w.add_block(ids, dig[i], off[i], range[i], (const unsigned char *)signal + sig_off[i], len, err)
+                                                           : w.add(ids, dig[i], off[i], range[i], (const int16_t *)signal + sig_off[i], len, err);
+        if (!ok) { put_err(err, errbuf, ecap); return -1; }
+    }
+    if (!w.close(err)) { put_err(err, errbuf, ecap); return -1; }
+    return 0;
+}

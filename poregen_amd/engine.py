@@ -1088,6 +1088,97 @@ def decode_svb_zd(blocks, block_off, device: int = 0):
         dec.close()
 
 
+class SignalEncoder:
+    """int16 samples encoded into svb-zd signal blocks on the GPU (pg_sigenc_*), the shortest block of every read as slow5lib writes it:
+    read r is sig[sig_off[r]:sig_off[r + 1]], samples in a numpy array or, read in place, in a CUDA tensor."""
+
+    def __init__(self, device: int = 0):
+        self._lib = _abi.load()
+        h = C.c_void_p()
+        st = self._lib.pg_sigenc_create(device, C.byref(h))
+        if st != 0:
+            raise PgError(st, self._lib.pg_sigenc_last_error(None).decode())
+        self._h = h
+        self._device = device
+
+    def _check(self, st):
+        if st != 0:
+            raise PgError(st, self._lib.pg_sigenc_last_error(self._h).decode())
+
+    def set_stream(self, stream=None):
+        """Run on a caller-owned stream (a torch.cuda.Stream or a raw hipStream_t value); None: the handle's own."""
+        ptr = None if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
+        self._check(self._lib.pg_sigenc_set_stream(self._h, ptr))
+
+    @property
+    def stream(self) -> int:
+        return int(self._lib.pg_sigenc_stream(self._h) or 0)
+
+    def bound(self, sig_off) -> int:
+        """no batch with these offsets encodes to more bytes (host only)"""
+        soff = np.ascontiguousarray(sig_off, np.uint64)
+        return int(self._lib.pg_sigenc_bound(soff.ctypes.data, max(soff.size - 1, 0)))
+
+    def encode(self, sig, sig_off):
+        """(blocks, block_off): a uint8 CUDA tensor that aliases the encoder's buffer (valid until its next encode / close) and the
+        n + 1 block offsets (uint64, a copy). Both go to SignalDecoder.decode and SignalMeans.submit_svb as they are. The offsets are
+        handed to the library as given: it refuses the ones that decrease, a read beyond 2^32 - 1 samples and more than 2^28 samples."""
+        import torch
+        soff = np.ascontiguousarray(sig_off, np.uint64)
+        if soff.ndim != 1 or soff.size < 1:
+            raise ValueError("need n + 1 sample offsets")
+        n = soff.size - 1
+        if hasattr(sig, "is_cuda") and sig.is_cuda:
+            if sig.dtype != torch.int16 or not sig.is_contiguous():
+                raise ValueError("device samples: a contiguous int16 tensor")
+            loc = _abi.PG_LOC_DEVICE
+        else:
+            sig = np.ascontiguousarray(sig, np.int16)
+            loc = _abi.PG_LOC_HOST
+        if (soff[1:] >= soff[:-1]).all() and int(soff[-1]) > _size(sig) and int(soff[-1]) - int(soff[0]) <= (1 << 28):
+            raise ValueError("sig_off runs past the samples")  # (the kernels trust the offsets: never let them point past the samples)
+        res = _abi.PgSigencResult()
+        res.struct_size = C.sizeof(_abi.PgSigencResult)
+        self._check(self._lib.pg_sigenc_encode(self._h, _ptr(sig) if _size(sig) else None, soff.ctypes.data, n, loc, C.byref(res)))
+        nb = int(res.n_block_bytes)
+        boff = np.ctypeslib.as_array(C.cast(res.block_off, C.POINTER(C.c_uint64)), (n + 1,)).copy()
+        dev = torch.device("cuda", self._device)
+        if not nb:
+            return torch.empty(0, dtype=torch.uint8, device=dev), boff
+
+        class _Alias:  # zero-copy hand-over through the CUDA array interface
+            __cuda_array_interface__ = {"shape": (nb,), "typestr": "|u1", "data": (int(res.blocks), False), "version": 2}
+
+        return torch.as_tensor(_Alias(), device=dev), boff
+
+    def kernel_ms(self):
+        """HIP-event time of the sizes kernel and of the emit kernel since the last call."""
+        a, b = C.c_double(), C.c_double()
+        self._check(self._lib.pg_sigenc_kernel_ms(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.pg_sigenc_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def encode_svb_zd(sig, sig_off, device: int = 0):
+    """One-shot SignalEncoder: (blocks, block_off) of one batch of reads; blocks is a CUDA tensor of its own."""
+    enc = SignalEncoder(device)
+    try:
+        blocks, boff = enc.encode(sig, sig_off)
+        return blocks.clone(), boff
+    finally:
+        enc.close()
+
+
 # ---- model: the k-mer model from the text of dump files (pg_dmodel_*) ------------------------------------------------------------------
 
 @dataclass
