@@ -1,9 +1,8 @@
 // gmove_cli.cpp -- `poregen gmove`: the reference's command line and output layout (src/gmove.cpp:213-537)
 // over libpgmove (include/pgmove.h). Host work here: option handling, k-mer list and slice, SLOW5/PAF/FASTQ
 // parsing into batches, writing the dump directory. The per-read computation runs on the GPU.
-#include "../../../include/pgmove.h"
-#include "pg_host.h"
-#include "../pg_hip_host.h"
+#include "pg_cli.h"
+#include "pg_moverecs.h"
 #include <future>
 #include <algorithm>
 
@@ -123,8 +122,6 @@ struct HostBatch {
     }
 };
 
-int die(const char *fmt, const std::string &a = "") { fprintf(stderr, fmt, a.c_str()); fputc('\n', stderr); return EXIT_FAILURE; }
-
 // the device side of the run: one context (--device) or one job over several GPUs (--devices), same calls either way
 struct Backend {
     pg_ctx *ctx = nullptr; pg_job *job = nullptr;
@@ -207,12 +204,8 @@ int gmove_main(int argc, char **argv) {
         return fp_help == stdout ? EXIT_SUCCESS : EXIT_FAILURE;
     }
     const char *slow5file = argv[optind], *move_table = argv[optind + 1], *output_dir = argv[optind + 2];
-    {
-        const size_t ml = strlen(move_table);
-        const bool sam_or_bam = ml >= 4 && (!strcmp(move_table + ml - 4, ".bam") || !strcmp(move_table + ml - 4, ".sam"));
-        if (reform_mode && !sam_or_bam) { fprintf(stderr, "--reform applies to a .bam or .sam event_alignment_file only\n"); print_help(fp_help, opt); return EXIT_FAILURE; }
-        if (n_to_t && !reform_mode) { fprintf(stderr, "--n_to_t applies with --reform only\n"); print_help(fp_help, opt); return EXIT_FAILURE; }
-    }
+    if (reform_mode && !is_sam_or_bam(move_table)) { fprintf(stderr, "--reform applies to a .bam or .sam event_alignment_file only\n"); print_help(fp_help, opt); return EXIT_FAILURE; }
+    if (n_to_t && !reform_mode) { fprintf(stderr, "--n_to_t applies with --reform only\n"); print_help(fp_help, opt); return EXIT_FAILURE; }
     if (event_model_path && devices.size() > 1) return die("--event_model works on one device: it cannot be combined with --devices of more than one device");
     if (event_model_path && devices.size() == 1) { device = devices[0]; devices.clear(); } // (one listed device: the single-device path)
     // --devices cuts every batch into one contiguous shard per device: the default batch grows with the device count, so that a shard
@@ -295,9 +288,7 @@ int gmove_main(int argc, char **argv) {
     else if (signal_scale == 1) { scaling = 1; fprintf(stderr, "scaling: %s\n", "medmad scale"); }
     else { print_help(fp_help, opt); return EXIT_FAILURE; }
 
-    const std::string mt(move_table); // src/gmove.cpp:505-521
-    const std::string ext = mt.size() >= 4 ? mt.substr(mt.size() - 4) : "";
-    const bool is_paf = ext == ".paf", is_bam = ext == ".bam" || ext == ".sam";
+    const bool is_paf = ends_with(move_table, ".paf"), is_bam = is_sam_or_bam(move_table); // src/gmove.cpp:505-521
 
     // ---- device context: created on its own thread while this one builds the file indices (the HIP runtime takes 0.1-0.2 s
     // to come up, about as long as indexing a compressed BLOW5) -------------------------------------------------------------
@@ -615,40 +606,24 @@ int gmove_main(int argc, char **argv) {
         unsigned nt = std::thread::hardware_concurrency(); if (nt > 16) nt = 16; if (nt < 1) nt = 1;
         struct Slot { pg_mvops *ex = nullptr; PgDev<int16_t> sig; PgDev<uint64_t> sig_off; PgDev<double> cal; };
         Slot slots[2];
-        struct Recs {
-            std::vector<std::string> names; std::vector<int8_t> mv; std::vector<uint64_t> mv_off{0}, ns, ts, boff; std::vector<int32_t> stride;
-            std::vector<uint32_t> l_seq, flag; std::vector<uint8_t> seqb;
-            void clear() { names.clear(); mv.clear(); mv_off.assign(1, 0); ns.clear(); ts.clear(); boff.clear(); stride.clear(); l_seq.clear(); flag.clear(); seqb.clear(); }
-        } rb;
+        pgh::MoveRecs rb;
         std::vector<pgh::Slow5File::RawView> views; std::vector<pgh::Slow5Rec> recs; std::vector<std::string> fetch_err;
         std::vector<double> cal;
         std::vector<uint32_t> h_opn; // --devices: the expansion comes back to the host, which cuts the batch into the job's shards
         pgh::RawMoveRec raw;
-        auto reform_msg = [](const char *msg, const std::string &id) { char b[600]; snprintf(b, sizeof b, "[reform::ERROR]\033[1;31m %s Read_id: %s\033[0m", msg, id.c_str()); return std::string(b); };
-        static const char *const kRefusal[] = {"", "the move table holds fewer moves than sig_move_offset + 1.", "Error in calcuation. (ns - ((i-1)*EXPECTED_STRIDE + ts)) > 0 is not valid.",
-                                               "Error in the implementation. Please report the command with minimal reproducible data.", "the stride of the move table (mv[0]) is less than 1."};
         auto release = [&]() { for (Slot &sl : slots) { if (sl.ex) pg_mvops_destroy(sl.ex); sl.ex = nullptr; sl.sig.release(); sl.sig_off.release(); sl.cal.release(); } };
         bool eof = false;
         while (!stop && !eof && status == EXIT_SUCCESS) {
             // ---- the records: the first one that cannot be taken ends the batch in front of it
             rb.clear();
             std::string bad; // why the record behind the batch's last read cannot be taken (empty: nothing wrong)
-            while (rb.names.size() < this_batch_reads && rb.mv.size() < ((size_t)1 << 30)) {
-                const int nr = sam.next_raw(raw, err);
-                if (nr == 0) { eof = true; break; }
-                if (nr < 0) { bad = "[gmove] " + err; break; }
-                if (raw.flag & 0x900u) continue; // secondary / supplementary: `samtools fastq` does not print them
-                if (!raw.has_ns) { bad = reform_msg("tag 'ns' is not found. Please check your SAM/BAM file:", raw.qname); break; }
-                if (!raw.has_ts) { bad = reform_msg("tag 'ts' is not found. Please check your SAM/BAM file:", raw.qname); break; }
-                if (!raw.has_mv) { bad = reform_msg("NULL returned for tag mv:", raw.qname); break; }
-                if (!raw.mv_is_Bc) { bad = reform_msg("tag 'mv' specification is incorrect.", raw.qname); break; }
-                if (raw.mv_len == 0) { bad = reform_msg("mv array length is 0:", raw.qname); break; }
-                rb.names.push_back(raw.qname);
-                rb.mv.insert(rb.mv.end(), raw.mv, raw.mv + (raw.mv_len - 1)); rb.mv_off.push_back(rb.mv.size());
-                rb.stride.push_back(raw.stride); rb.ns.push_back(raw.ns); rb.ts.push_back(raw.ts); rb.l_seq.push_back(raw.l_seq); rb.flag.push_back(raw.flag);
-                rb.boff.push_back(rb.seqb.size()); rb.seqb.insert(rb.seqb.end(), raw.packed, raw.packed + ((size_t)raw.l_seq + 1) / 2);
+            while (rb.size() < this_batch_reads && rb.mv.size() < ((size_t)1 << 30)) {
+                const int nr = pgh::next_move_record(sam, raw, "gmove", bad);
+                if (nr == 0) eof = true;
+                if (nr <= 0) break;
+                rb.push(raw);
             }
-            size_t n = rb.names.size();
+            size_t n = rb.size();
             // ---- the signals, on the pool: where each read's samples lie (or the samples, decoded), then one copy to their place
             const bool can_place = s5.has_raw_views();
             views.assign(can_place ? n : 0, {}); recs.resize(can_place ? 0 : n); fetch_err.assign(nt, std::string());
@@ -687,12 +662,10 @@ int gmove_main(int argc, char **argv) {
                 Slot &sl = slots[cur];
                 const int ex_device = devices.empty() ? device : devices[0];
                 if (!sl.ex && pg_mvops_create(ex_device, &sl.ex) != PG_OK) { fprintf(stderr, "[gmove] %s\n", pg_mvops_last_error(nullptr)); status = EXIT_FAILURE; break; }
-                pg_mvops_batch mb; memset(&mb, 0, sizeof mb);
-                mb.n_reads = n; mb.location = PG_LOC_HOST; mb.flags = (opt.flag_rna ? PG_MVOPS_RNA : 0) | (n_to_t ? PG_MVOPS_N_TO_T : 0);
-                mb.mv = rb.mv.data(); mb.n_mv_bytes = rb.mv_off[n]; mb.mv_off = rb.mv_off.data(); mb.stride = rb.stride.data(); mb.ns = rb.ns.data(); mb.ts = rb.ts.data();
-                mb.l_seq = rb.l_seq.data(); mb.flag = rb.flag.data(); mb.seq_bytes = rb.seqb.data(); mb.n_seq_bytes = rb.seqb.size(); mb.byte_off = rb.boff.data();
+                pg_mvops_batch mb;
+                rb.fill(mb, n, (opt.flag_rna ? PG_MVOPS_RNA : 0) | (n_to_t ? PG_MVOPS_N_TO_T : 0));
                 pg_mvops_result mr;
-                auto hip_ok = [&](hipError_t e, const char *what) { if (e == hipSuccess) return true; fprintf(stderr, "[gmove] %s: %s\n", what, hipGetErrorString(e)); status = EXIT_FAILURE; return false; };
+                const HipOk hip_ok{"gmove", &status};
                 hipStream_t xs = (hipStream_t)pg_mvops_stream(sl.ex);
                 if (!dev.job) { // the signal and its calibration go up in front of the expansion, on its stream: complete when it returns
                     const size_t sb = hb.sig_off[n] * sizeof(int16_t);
@@ -706,10 +679,8 @@ int gmove_main(int argc, char **argv) {
                 }
                 if (pg_mvops_expand(sl.ex, &mb, &mr) != PG_OK) { fprintf(stderr, "[gmove] %s\n", pg_mvops_last_error(sl.ex)); status = EXIT_FAILURE; break; }
                 if (mr.first_refused >= 0) { // reform returns -1 on this record: the reads in front of it are the batch
-                    const size_t f = (size_t)mr.first_refused;
-                    const uint32_t code = mr.status_host[f];
-                    bad = reform_msg(kRefusal[code < 5 ? code : 3], rb.names[f]);
-                    n = f; eof = false;
+                    n = (size_t)mr.first_refused; eof = false;
+                    bad = pgh::reform_error(pgh::reform_refusal(mr.status_host[n]), rb.names[n]);
                 }
                 uint64_t n_ops = 0, n_seq = 0; // an accepted read has as many ops as bases
                 for (size_t i = 0; i < n; i++) { n_ops += rb.l_seq[i]; n_seq += rb.l_seq[i]; }

@@ -10,10 +10,9 @@
 //   * --event_model FILE: NAME<TAB>events<TAB>median and sstdev of the events' means<TAB>median and sstdev of the events' standard
 //     deviations (pg_dmodel_finish_events; no counterpart in the script, which cannot tell the two apart). A file whose table the library
 //     refuses ends the command with status 1 before anything is written
-#include "../../../include/pgmove.h"
 #include "../pg_dumphost.h"
+#include "pg_cli.h"
 #include "pg_dumpdir.h"
-#include "pg_host.h"
 #include "pg_poolnames.h"
 
 #include <chrono>
@@ -53,8 +52,6 @@ void print_help(FILE *fp) {
     fprintf(fp, "   -t INT                     threads that read files [8], at most 16\n");
     fprintf(fp, "   -h                         help\n");
 }
-
-int die(const char *fmt, const std::string &a = "") { fprintf(stderr, fmt, a.c_str()); fputc('\n', stderr); return EXIT_FAILURE; }
 
 uint64_t batch_bytes() {
     if (const char *s = getenv("POREGEN_MODEL_BATCH")) { const long long v = atoll(s); if (v >= 1) return (uint64_t)v; }

@@ -6,7 +6,7 @@
 //   base    POS  B  n_files  n_values  median  stddev      4K rows, POS 0..K-1, B in the order A C G T (or U)
 //   spread  POS  S                                         K rows: largest - smallest median of the position's groups that have a value
 //   best    POS                                            the position with the largest S (ties: the lowest); omitted when no POS has one
-#include "../../../include/pgmove.h"
+#include "pg_cli.h"
 #include "pg_dumpdir.h"
 #include "pg_poolnames.h"
 
@@ -35,8 +35,6 @@ void print_help(FILE *fp) {
     fprintf(fp, "   -t INT                     threads that read files [8], at most 16\n");
     fprintf(fp, "   -h                         help\n");
 }
-
-int die(const char *fmt, const std::string &a = "") { fprintf(stderr, fmt, a.c_str()); fputc('\n', stderr); return EXIT_FAILURE; }
 
 } // namespace
 

@@ -7,20 +7,13 @@
 //   -c FILE                   the TRUE alignment, as the PAF `poregen reform -c -k 1 -m 0 --stride 0 [--rna]` prints
 //   -q FILE                   the reads as FASTQ
 //   --moves FILE              a headerless SAM as a basecaller writes it: mv:B:c with every true boundary rounded to the stride from ts
-#include "../../../include/pgmove.h"
 #include "../pg_sim.h"
-#include "../pg_hip_host.h"
-#include "pg_host.h"
+#include "pg_cli.h"
 
 #include <algorithm>
 #include <cerrno>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <getopt.h>
-#include <string>
 #include <thread>
-#include <vector>
 
 namespace {
 
@@ -82,14 +75,6 @@ void print_help(FILE *fp) {
     fprintf(fp, "   -h                         help\n");
 }
 
-int die(const char *fmt, const std::string &a = "") { fprintf(stderr, fmt, a.c_str()); fputc('\n', stderr); return EXIT_FAILURE; }
-
-bool whole_int(const char *s, long long min, long long max, long long &v) {
-    char *end = nullptr;
-    if (!s || !*s || *s == '+') return false;
-    v = strtoll(s, &end, 10);
-    return *end == 0 && v >= min && v <= max;
-}
 bool whole_u64(const char *s, unsigned long long &v) {
     char *end = nullptr;
     if (!s || !*s || *s == '+' || *s == '-') return false;
@@ -102,7 +87,6 @@ bool decimal_times(const char *s, uint32_t mult, uint32_t &out) {
     pgbc::Dec d;
     return s && *s && pgbc::parse(s, strlen(s), d) && !d.neg && pg_fit_round_dec(d, mult, out) == 0;
 }
-bool ends_with(const char *s, const char *suffix) { const size_t a = strlen(s), b = strlen(suffix); return a >= b && !strcmp(s + a - b, suffix); }
 
 struct Contig { std::string name, seq; };
 // a FASTA: names up to the first blank, sequence lines joined and upper-cased
@@ -289,7 +273,7 @@ int simulate_main(int argc, char **argv) {
         if (st == PG_ERR_UNSUPPORTED && batch_reads > 1) { batch_reads = (batch_reads + 1) / 2; continue; } // too many samples at once: the same reads in smaller batches
         if (st != PG_OK) { fprintf(stderr, "[simulate] %s\n", pg_sim_last_error(sim)); status = EXIT_FAILURE; break; }
         ops.resize(res.n_ops); sig_off.resize(n + 1); op_off.resize(n + 1); offs.resize(n);
-        auto hip_ok = [&](hipError_t e) { if (e == hipSuccess) return true; fprintf(stderr, "[simulate] hipMemcpy: %s\n", hipGetErrorString(e)); status = EXIT_FAILURE; return false; };
+        auto hip_ok = [&](hipError_t e) { return HipOk{"simulate", &status}(e, "hipMemcpy"); };
         if ((res.n_ops && !hip_ok(hipMemcpy(ops.data(), res.op_n, res.n_ops * 4, hipMemcpyDeviceToHost))) ||
             !hip_ok(hipMemcpy(sig_off.data(), res.sig_off, (n + 1) * 8, hipMemcpyDeviceToHost)) || !hip_ok(hipMemcpy(op_off.data(), res.op_off, (n + 1) * 8, hipMemcpyDeviceToHost)) ||
             (n && !hip_ok(hipMemcpy(offs.data(), res.offset, n * 8, hipMemcpyDeviceToHost))))

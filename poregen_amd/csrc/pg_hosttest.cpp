@@ -682,3 +682,39 @@ extern "C" int pgt_sim_write_blow5(const char *path, int binary, const char *rec
     if (!w.close(err)) { put_err(err, errbuf, ecap); return -1; }
     return 0;
 }
+
+// ---- the record and signal batches of fit and realign (host/pg_moverecs.h), run to the end of the files ---------------------------------
+#include "host/pg_moverecs.h"
+// Per batch that holds a read its reads and samples; per read, in the order taken, the id (0-terminated, back to back), seven numbers --
+// stride, ns, ts, l_seq, elements of the table behind the stride, samples, sum of the samples --, the offset of the calibration, the
+// table's elements and the packed bases (both back to back); `bad`: why the run ended, empty at the end of the files. Returns the number
+// of batches, -1 (bad: why a file cannot be opened) or -2 when an array is too small.
+extern "C" long pgt_move_batches(const char *sam_path, const char *slow5_path, size_t max_reads, size_t soft, size_t hard, uint64_t *batch_reads, uint64_t *batch_samples,
+                                 size_t batch_cap, char *ids, size_t ids_cap, int64_t *nums7, double *offset, size_t reads_cap, int8_t *mv, size_t mv_cap, uint8_t *packed,
+                                 size_t packed_cap, char *bad, size_t bad_cap) {
+    pgh::SamBamReader sam; pgh::Slow5File s5; std::string why;
+    if (!sam.open(sam_path, why) || !s5.open(slow5_path, why)) { put_err(why, bad, bad_cap); return -1; }
+    pgh::MoveSignalBatches in(sam, s5, "hosttest", max_reads, soft, hard);
+    size_t nb = 0, nr = 0, ni = 0, nm = 0, np = 0;
+    for (bool more = true; more && !in.done();) {
+        more = in.next(why);
+        const pgh::MoveRecs &rb = in.recs;
+        if (!rb.size()) continue;
+        if (nb == batch_cap || nr + rb.size() > reads_cap || nm + rb.mv.size() > mv_cap || np + rb.seqb.size() > packed_cap) return -2;
+        batch_reads[nb] = rb.size(); batch_samples[nb++] = in.sig.size();
+        for (size_t i = 0; i < rb.size(); i++, nr++) {
+            if (ni + rb.names[i].size() + 1 > ids_cap) return -2;
+            memcpy(ids + ni, rb.names[i].c_str(), rb.names[i].size() + 1); ni += rb.names[i].size() + 1;
+            int64_t sum = 0;
+            for (uint64_t s = in.sig_off[i]; s < in.sig_off[i + 1]; s++) sum += in.sig[s];
+            const int64_t v[7] = {rb.stride[i], (int64_t)rb.ns[i], (int64_t)rb.ts[i], rb.l_seq[i], (int64_t)(rb.mv_off[i + 1] - rb.mv_off[i]), (int64_t)(in.sig_off[i + 1] - in.sig_off[i]), sum};
+            memcpy(nums7 + 7 * nr, v, sizeof v);
+            offset[nr] = in.off[i];
+        }
+        if (rb.mv.size()) memcpy(mv + nm, rb.mv.data(), rb.mv.size());
+        if (rb.seqb.size()) memcpy(packed + np, rb.seqb.data(), rb.seqb.size());
+        nm += rb.mv.size(); np += rb.seqb.size();
+    }
+    put_err(why, bad, bad_cap);
+    return (long)nb;
+}
