@@ -724,7 +724,9 @@ template <int COUNT, bool LT> __global__ __launch_bounds__(1024) __attribute__((
             sh = 63u - 2u * k; step = -2; tb2 = 0u;
         }
         const uint32_t mask2 = ((1u << (2u * k)) - 1u) << 1;
-        const char *lbase = reinterpret_cast<const char *>(ltab);
+        // (an LDS pointer by its type: through a plain volatile pointer the 16 look-ups are flat loads, which wait on the global-memory counter too)
+        typedef const volatile __attribute__((address_space(3))) char lds_char;
+        lds_char *lbase = (lds_char *)reinterpret_cast<const char *>(ltab);
         uint32_t *cbase = &cnt[tq][0];
         const uint32_t dummy = PG_RANK_MAX_DIGITS + ((uint32_t)lane & 31u);
         uint32_t pk[8];
@@ -736,7 +738,7 @@ template <int COUNT, bool LT> __global__ __launch_bounds__(1024) __attribute__((
                 const int j = 4 * v + u;
                 const uint32_t off = ((uint32_t)(S64 >> (sh + (uint32_t)(step * j))) & mask2) | tb2;
                 const uint32_t m = (uint32_t)((int32_t)(cm << (31 - j)) >> 31);
-                t16[u] = *reinterpret_cast<const volatile uint16_t *>(lbase + ((off & m) | (4096u & ~m)));
+                t16[u] = *(const volatile __attribute__((address_space(3))) uint16_t *)(lbase + ((off & m) | (4096u & ~m)));
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) atomicAdd(cbase + (t16[u] < dummy ? t16[u] : dummy), 1u);
