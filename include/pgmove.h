@@ -500,7 +500,9 @@ pg_status   pg_job_model(pg_job *job, uint32_t flags, pg_model_result *out);
 pg_status   pg_job_kernel_stats(pg_job *job, uint32_t shard, pg_kernel_stat *out, uint32_t cap, uint32_t *n_out);
 
 /* profiling (PG_FLAG_PROFILE): per-kernel launch counts and HIP-event times since the last reset. With or without the flag, counters
- * follow as entries of 0 ms when they are not 0: stats_cancelled_on_device, long_reads_split, long_helpers_short_batches, and the
+ * follow as entries of 0 ms when they are not 0: stats_cancelled_on_device, long_reads_split, long_helpers_short_batches,
+ * front_complete / front_missed (settled pg_submit batches whose events were counted front first: the first tiles completed every k-mer and
+ * the tiles behind them were not walked / did not, and were; PGMOVE_FRONT_TILES=n sets the front in tiles of 4096 ops, 0 = never), and the
  * gathers for many kept events by the kernel queued: gather_form_wave, gather_form_evpair, gather_form_lanes4 / 8 / 16; k_sort_scatter:
  * passes of the LSD radix sort queued (more than 2^20 slots; the entry "sort_events" counts the whole sort once per batch) */
 pg_status pg_kernel_stats(pg_ctx *ctx, pg_kernel_stat *out, uint32_t cap, uint32_t *n_out);

@@ -88,6 +88,9 @@ struct pg_ctx {
     PgRareArgs rare{};      // the rare statistics launch of the current batch ...
     bool rare_pending = false; // ... still to be issued: with the sample-offset scan of pg_collect
     bool in_submit = false, plan_done = false; // pg_submit: the sample_limit cut was applied inside the tile scan's launch (no k_slot_plan)
+    // front-first count phase (front_tiles_for): the current batch's front in tiles (0: one pass), and the settled batches whose front did /
+    // did not complete every k-mer
+    uint32_t front_tiles = 0; uint64_t front_complete = 0, front_missed = 0;
     uint32_t gen_reads = 0; // generic reads of the last settled batch
     bool batch_all_matches = false; // PG_BATCH_ALL_MATCHES of the current batch (and not PG_FLAG_DEBUG_SPLIT_WALK)
     PgDev<> job_total, job_freq; bool have_job_totals = false; // pg_collect_gathered / pg_job_totals_device
@@ -364,8 +367,8 @@ pg_status pg_create(const pg_params *p, pg_ctx **out) {
     PG_HIP_TRY(c, grow(c->acc_cnt, ns * 8ull)); PG_HIP_TRY(c, grow(c->running, ns * 8ull)); PG_HIP_TRY(c, grow(c->keep, ns * 8ull)); PG_HIP_TRY(c, grow(c->tile_last, ns * 4ull));
     PG_HIP_TRY(c, grow(c->ev_off, (ns + 1) * 8ull)); PG_HIP_TRY(c, grow(c->plan_totals, 64)); PG_HIP_TRY(c, grow(c->base_stage, ns * 8ull));
     PG_HIP_TRY(c, grow(c->job_total, ns * 8ull)); PG_HIP_TRY(c, grow(c->job_freq, ns * 8ull)); // allocated once: callers may cache the pointers
-    PG_HIP_TRY(c, grow(c->totals, 256 * 4)); PG_HIP_TRY(c, grow(c->dbase, 256 * 4)); PG_HIP_TRY(c, grow(c->scount, 16)); PG_HIP_TRY(c, grow(c->errflag, 32));
-    PG_HIP_TRY(c, hipMemset(c->errflag.p, 0, 32)); // [0] u64 error word, [8] i32 layout flag, [16] u32 gen_count[2] (PgWalkOut), [24] u32 ticket (k_rank_scan)
+    PG_HIP_TRY(c, grow(c->totals, 256 * 4)); PG_HIP_TRY(c, grow(c->dbase, 256 * 4)); PG_HIP_TRY(c, grow(c->scount, 16)); PG_HIP_TRY(c, grow(c->errflag, 48));
+    PG_HIP_TRY(c, hipMemset(c->errflag.p, 0, 48)); // [0] u64 error word, [8] i32 layout flag, [16] u32 gen_count[2] (PgWalkOut), [24] u32 ticket (k_rank_scan), [32] u32 PgFront::word[2]
     PG_HIP_TRY(c, grow(c->stat_err[0], 32)); PG_HIP_TRY(c, grow(c->stat_err[1], 32)); // [0..2] statistics flags, [3] pg_div_domain_ok failed (the long-read counters live in long_ring)
     PG_HIP_TRY(c, hipMemset(c->stat_err[0].p, 0, 32)); PG_HIP_TRY(c, hipMemset(c->stat_err[1].p, 0, 32));
     PG_HIP_TRY(c, grow(c->long_ring, 64)); PG_HIP_TRY(c, hipMemset(c->long_ring.p, 0, 64));
@@ -674,6 +677,26 @@ static bool dense_direct(const pg_ctx *c, uint64_t n_ops) {
     return c->prm.n_slots <= PG_DIRECT_MAX_SLOTS && std::min<uint64_t>(n_ops, (uint64_t)c->prm.n_slots * c->prm.sample_limit) > dense_min();
 }
 
+// Front-first count phase (PgFront): the front of the batch in tiles, 0 = one pass over the whole batch. For pg_submit's direct
+// ranking with few kept events, where the cut rides in the scan's launch and nothing exposes the batch's uncapped counts: pg_count's result
+// is those counts; the dense path prefixes the block sums of the whole batch; at limit 0 nothing ever completes; with a sig_move_offset a kept
+// event's window start reads the block sums of the tile behind its own. Then a front of an eighth of the tiles, if the batch has at least 64
+// tiles and the front could hold four times the events that are kept at most: a front that does not complete costs its own pass on top of the
+// single pass's work (one workgroup's chain through the event kernel and the scan, ~23 us on the headline workload).
+// PGMOVE_FRONT_TILES=n (tests, A/B) sets the front itself, rounded up to a multiple of 4, for any size; 0 = never.
+static uint32_t front_tiles_for(const pg_ctx *c, uint64_t n_ops, bool counts_wanted) {
+    if (!c->in_submit || counts_wanted || n_ops == 0 || c->prm.n_slots > PG_DIRECT_MAX_SLOTS || dense_direct(c, n_ops)) return 0;
+    if (c->prm.sample_limit == 0 || c->prm.sig_move_offset != 0) return 0;
+    const uint32_t n_tiles = pg_tiles(n_ops, true);
+    uint64_t f;
+    if (const char *ov = getenv("PGMOVE_FRONT_TILES")) f = (strtoull(ov, nullptr, 10) + 3) & ~3ull;
+    else {
+        f = ((n_tiles + 7) / 8 + 3) & ~3ull;
+        if (n_tiles < 64 || f * PG_SORT_TILE < 4ull * c->prm.n_slots * c->prm.sample_limit) return 0;
+    }
+    return f > 0 && f < n_tiles ? (uint32_t)f : 0; // (a front of every tile is the single pass)
+}
+
 static void fill_part(pg_ctx *c, PgPartBufs &P, uint64_t n_ops) {
     P.elemA = c->part_elem.as<uint4>(); P.loA = c->part_lodig.as<uint16_t>(); P.hist = c->hist.as<uint32_t>(); P.totals = c->totals.as<uint32_t>(); P.rbase = c->part_rbase.as<uint32_t>();
     P.tile_region = c->part_tile_region.as<uint32_t>(); P.n_tilesB = c->part_ntiles.as<uint32_t>(); P.histB = c->part_histB.as<uint32_t>();
@@ -750,7 +773,11 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
         PG_HIP_TRY(c, grow(c->gen_flag, (n + 1) * 4ull));
         if (c->gen_flag.cap != before) PG_HIP_TRY(c, hipMemsetAsync(c->gen_flag.p, 0, c->gen_flag.cap, c->st));
     }
-    if (++c->batch_id == 0) { c->batch_id = 1; PG_HIP_TRY(c, hipMemsetAsync(c->gen_flag.p, 0, c->gen_flag.cap, c->st)); }
+    if (++c->batch_id == 0) { // (PgFront::word[1] is compared with the serial number as well)
+        c->batch_id = 1;
+        PG_HIP_TRY(c, hipMemsetAsync(c->gen_flag.p, 0, c->gen_flag.cap, c->st));
+        PG_HIP_TRY(c, hipMemsetAsync(c->errflag.as<uint32_t>() + 8, 0, 8, c->st));
+    }
     PG_HIP_TRY(c, grow(c->meta, (n + 1) * sizeof(PgReadMeta))); PG_HIP_TRY(c, grow(c->status, (n + 1) * 4ull));
     PG_HIP_TRY(c, grow(c->read_needed, n + 2ull));
     const uint32_t n_tiles = pg_tiles(Nn, direct);
@@ -805,11 +832,13 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
     PgLongState LS{};
     ++c->long_seq; // this batch's entry of the long-read counter ring
     { pg_status sl_ = fill_long(c, LS, true); if (sl_ != PG_OK) return sl_; }
+    c->front_tiles = front_tiles_for(c, N, counts_out != nullptr);
+    const PgFront FR{c->front_tiles, c->errflag.as<uint32_t>() + 8};
     prof_begin(c, "k_batch_init", c->st);
     PG_HIP_TRY(c, pg_launch_batch_init(c->st, n, c->read_needed.as<uint8_t>(), c->running.as<uint64_t>(), c->prm.n_slots,
                          c->zero_running ? 1 : 0, overlap ? nullptr : c->stat_err[c->slot].as<int32_t>(), c->B, c->prm.pa_min, c->prm.pa_max,
                          c->plan_in_init ? c->read_plan[c->slot].p : nullptr, c->plan_in_init ? c->stat_status[c->slot].as<int32_t>() : nullptr,
-                         W, O, force_generic ? 1 : 0, LS));
+                         W, O, force_generic ? 1 : 0, LS, FR.tiles ? FR.word + 1 : nullptr));
     prof_end(c, c->st);
     c->stat_flags_reset = !overlap;
     c->zero_running = false;
@@ -828,7 +857,8 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
     PgSortBufs S{};
     fill_sort(c, S, n_tiles);
     prof_begin(c, "k_events", c->st);
-    PG_HIP_TRY(c, pg_launch_events(c->st, c->B, W, O, c->prm.n_slots, (direct || c->part_mode) ? S.hist : nullptr, c->part_mode ? c->part_hi : 0u, c->part_lo));
+    PG_HIP_TRY(c, pg_launch_events(c->st, c->B, W, O, c->prm.n_slots, (direct || c->part_mode) ? S.hist : nullptr, c->part_mode ? c->part_hi : 0u, c->part_lo,
+                                   FR, FR.tiles ? PG_PASS_FRONT : PG_PASS_WHOLE));
     prof_end(c, c->st);
     uint64_t *acc_copy = (counts_out && counts_location == PG_LOC_DEVICE) ? counts_out : nullptr; // written by the counting kernels
     if (direct) {
@@ -838,8 +868,19 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
         PG_HIP_TRY(c, pg_launch_rank_direct_count(c->st, O.ev_slot, N, c->prm.n_slots, S, c->acc_cnt.as<uint64_t>(), c->running.as<uint64_t>(), c->prm.sample_limit,
                                     c->tile_last.as<int32_t>(), acc_copy, fuse_plan ? c->keep.as<uint64_t>() : nullptr, c->ev_off.as<uint64_t>(),
                                     c->plan_totals.as<uint64_t>(), c->errflag.as<uint32_t>() + 6, &c->plan_done,
-                                    O.btot, dense_direct(c, N) ? c->part_Bp.as<uint32_t>() : nullptr, dense_direct(c, N) ? c->chunk_part.as<uint64_t>() : nullptr));
+                                    O.btot, dense_direct(c, N) ? c->part_Bp.as<uint32_t>() : nullptr, dense_direct(c, N) ? c->chunk_part.as<uint64_t>() : nullptr,
+                                    FR, FR.tiles ? PG_PASS_FRONT : PG_PASS_WHOLE, c->batch_id));
         prof_end(c, c->st);
+        if (FR.tiles) { // the tiles behind the front: queued regardless, empty launches if the front has completed every k-mer (PgFront)
+            prof_begin(c, "k_events_tail", c->st);
+            PG_HIP_TRY(c, pg_launch_events(c->st, c->B, W, O, c->prm.n_slots, S.hist, 0u, 0u, FR, PG_PASS_TAIL));
+            prof_end(c, c->st);
+            prof_begin(c, "rank_scan_tail", c->st);
+            PG_HIP_TRY(c, pg_launch_rank_direct_count(c->st, O.ev_slot, N, c->prm.n_slots, S, c->acc_cnt.as<uint64_t>(), c->running.as<uint64_t>(), c->prm.sample_limit,
+                                        c->tile_last.as<int32_t>(), nullptr, c->keep.as<uint64_t>(), c->ev_off.as<uint64_t>(), c->plan_totals.as<uint64_t>(),
+                                        c->errflag.as<uint32_t>() + 6, &c->plan_done, O.btot, nullptr, nullptr, FR, PG_PASS_TAIL, c->batch_id));
+            prof_end(c, c->st);
+        }
     } else if (c->part_mode) {
         // partitioned ranking, pass A and the counts of pass B (pg_place.hip): everything pg_count's result needs
         PgPartBufs P{};
@@ -1130,9 +1171,11 @@ static pg_status settle_batch(pg_ctx *c) {
     // into host-mapped memory instead of four blocking copies of 8-24 bytes, ~80 -> ~10 us per call)
     if (c->st2) PG_HIP_TRY(c, hipStreamSynchronize(c->st2));
     PG_HIP_TRY(c, pg_launch_settle_pack(c->st, c->errflag.as<uint32_t>(), c->stat_err[c->slot].as<int32_t>(), c->long_ring.as<int32_t>() + 4u * (c->long_seq & 3u), c->plan_totals.as<uint64_t>(),
-                                     c->samp_off.as<uint64_t>(), c->samp_off.cap / 8, c->cancel_pending ? c->cancel_flag.as<uint32_t>() : nullptr, c->settle_host.p));
+                                     c->samp_off.as<uint64_t>(), c->samp_off.cap / 8, c->cancel_pending ? c->cancel_flag.as<uint32_t>() : nullptr,
+                                     c->front_tiles ? c->errflag.as<uint32_t>() + 8 : nullptr, c->settle_host.p));
     PG_HIP_TRY(c, hipStreamSynchronize(c->st));
     const PgSettlePack pk = *c->settle_host.p;
+    if (c->front_tiles) { if (pk.front[0]) c->front_complete++; else c->front_missed++; } // (a batch that fails was counted front first all the same)
     pg_status s = check_read_errors(c, pk);
     if (s != PG_OK) { c->have_batch_result = false; c->downloaded = true; return s; }
     const uint64_t tot[2] = {pk.n_kept, pk.full_slots};
@@ -1628,6 +1671,14 @@ pg_status pg_kernel_stats(pg_ctx *c, pg_kernel_stat *out, uint32_t cap, uint32_t
         if (out && n < cap) { out[n].name = "long_reads_split"; out[n].launches = c->long_reads_split; out[n].total_ms = 0.0; }
         n++;
     }
+    if (c->front_complete) { // settled batches counted front first (PgFront) whose front completed every k-mer: the tiles behind it were not walked
+        if (out && n < cap) { out[n].name = "front_complete"; out[n].launches = c->front_complete; out[n].total_ms = 0.0; }
+        n++;
+    }
+    if (c->front_missed) { // ... and whose front did not: the two launches behind it did the rest of the single pass
+        if (out && n < cap) { out[n].name = "front_missed"; out[n].launches = c->front_missed; out[n].total_ms = 0.0; }
+        n++;
+    }
     if (c->long_helpers_short) { // settled batches that wanted more helper waves than were launched (their surplus long reads ran on one wave each)
         if (out && n < cap) { out[n].name = "long_helpers_short_batches"; out[n].launches = c->long_helpers_short; out[n].total_ms = 0.0; }
         n++;
@@ -1651,7 +1702,7 @@ pg_status pg_kernel_stats_reset(pg_ctx *c) {
     PG_HIP_TRY(c, hipStreamSynchronize(c->st));
     if (c->st2) PG_HIP_TRY(c, hipStreamSynchronize(c->st2));
     prof_drain(c);
-    c->prof_acc.clear(); c->prof_names.clear(); c->stats_cancelled = 0; c->long_reads_split = 0; c->long_helpers_short = 0;
+    c->prof_acc.clear(); c->prof_names.clear(); c->stats_cancelled = 0; c->long_reads_split = 0; c->long_helpers_short = 0; c->front_complete = 0; c->front_missed = 0;
     for (uint64_t &f : c->gather_forms) f = 0;
     c->sort_scatters = 0;
     return PG_OK;

@@ -242,6 +242,15 @@ struct PgGathered {
     uint32_t world, rank;
     uint64_t *total, *freq; // [n_slots] the job's accepted events per slot and min(total, sample_limit) (pg_job_totals_device)
 };
+// ---- front-first count phase (pg_submit, direct ranking, few kept events) ------------------------------------------------
+// The event kernel and the tile scan run over tiles [0, tiles) first, and the scan's last workgroup, which applies the sample_limit cut,
+// says in word[0] whether every k-mer is complete after them. The same two launches over the tiles behind the front are queued
+// regardless; every workgroup of theirs loads word[0] and leaves if it is set -- otherwise they finish the single pass's work bit for
+// bit. word[1] == batch_id: the batch holds an op of PG_OP_N_LIMIT samples or more (k_batch_init looks when it is given the word); the
+// front then never counts as complete, so the event kernel reports that op's read exactly as a pass over the whole batch does.
+// Only the two tail launches and k_settle_pack may read word[0]; the host never waits for it.
+struct PgFront { uint32_t tiles; uint32_t *word; }; // tiles = 0: one pass over the whole batch; else a multiple of 4 below the batch's tiles
+enum { PG_PASS_WHOLE = 0, PG_PASS_FRONT = 1, PG_PASS_TAIL = 2 };
 // ---- launchers (all asynchronous on `st`; the result is hipGetLastError() behind the launch / the queued copy's status) -----------------------------------------------------------
 // a kept event in the batch's final (k-mer-major) order: ONE 16-byte record, so that the kernels that place events -- each at a
 // position of its own -- pay one memory transaction per event, not three (round 2 kept three arrays: 3 x 32-byte write requests per
@@ -265,7 +274,9 @@ hipError_t pg_launch_batch_init(hipStream_t st, uint32_t n_reads, uint8_t *read_
                           // plan_buf (may be null): also write the statistics record of every read (what k_read_plan does, needed == null)
                           const PgDevBatch &B, double pa_min, double pa_max, void *plan_buf, int32_t *stat_status,
                           // the per-read records, the owner index and the classification of the reads (PgWalkOut)
-                          const PgWalkParams &W, const PgWalkOut &O, int force_generic, const PgLongState &LS);
+                          const PgWalkParams &W, const PgWalkOut &O, int force_generic, const PgLongState &LS,
+                          // big_op (may be null): set to O.batch_id if any op of the batch has PG_OP_N_LIMIT samples or more (PgFront::word + 1)
+                          uint32_t *big_op = nullptr);
 // tiles of PG_SORT_TILE events; in direct mode (n_slots <= PG_DIRECT_MAX_SLOTS) the count is padded to a multiple of 4:
 // k_rank_count_direct handles 4 tiles per workgroup and writes their counts of a slot as one 16-byte store
 static inline uint32_t pg_tiles(uint64_t n_events, bool direct) {
@@ -314,7 +325,7 @@ hipError_t pg_launch_walk(hipStream_t st, const PgDevBatch &B, const PgWalkParam
 // != null, direct ranking) counts the accepted events per tile and slot as pg_launch_rank_direct_count's first kernel would
 // part_hi_bits != 0 (partitioned ranking, pg_place.hip): hist = P.hist, counts per (tile, slot >> part_lo_bits)
 hipError_t pg_launch_events(hipStream_t st, const PgDevBatch &B, const PgWalkParams &W, const PgWalkOut &O, uint32_t n_slots, uint32_t *hist,
-                            uint32_t part_hi_bits, uint32_t part_lo_bits);
+                            uint32_t part_hi_bits, uint32_t part_lo_bits, const PgFront &F = PgFront{}, int pass = PG_PASS_WHOLE);
 // SAM/BAM front-end: reads with an out-of-range sample become skipped reads (behind the statistics, in front of the walk)
 hipError_t pg_launch_apply_oor(hipStream_t st, const PgDevBatch &B, const PgWalkOut &O);
 // direct ranking (n_slots <= PG_DIRECT_MAX_SLOTS): tile prefix of the per-tile per-slot counts pg_launch_events left in S.hist;
@@ -326,7 +337,9 @@ hipError_t pg_launch_rank_direct_count(hipStream_t st, const uint32_t *ev_slot, 
                                  // launch (its last workgroup does pg_launch_slot_plan's work); *plan_done says whether it did
                                  uint64_t *plan_keep, uint64_t *plan_ev_off, uint64_t *plan_totals, uint32_t *plan_ticket, bool *plan_done,
                                  const uint32_t *btot /* PgWalkOut::btot */, uint32_t *Bp /* may be null: its prefix, for pg_launch_rank_emit2 */,
-                                 uint64_t *zero64 /* with Bp: PG_CHUNK_PART_N chunk sums, zeroed by the same extra workgroup (may be null) */);
+                                 uint64_t *zero64 /* with Bp: PG_CHUNK_PART_N chunk sums, zeroed by the same extra workgroup (may be null) */,
+                                 // pass != PG_PASS_WHOLE (needs plan_keep, no acc_copy, no Bp): the scan over the front's tiles / over the tiles behind it
+                                 const PgFront &F = PgFront{}, int pass = PG_PASS_WHOLE, uint32_t batch_id = 0);
 hipError_t pg_launch_rank_direct_emit(hipStream_t st, const uint32_t *ev_slot, uint64_t n, uint32_t n_slots, const PgSortBufs &S,
                                 const uint64_t *keep, const uint64_t *ev_off, const uint64_t *totals, const PgDevBatch &B,
                                 const PgWalkParams &W, const PgWalkOut &O, const PgKeptOut &K);
@@ -375,9 +388,10 @@ hipError_t pg_launch_scan_u32_u64(hipStream_t st, const uint32_t *in, uint32_t s
                                   const PgRareArgs *rare, uint64_t *total_out);
 hipError_t pg_launch_read_stats_rare(hipStream_t st, const PgRareArgs &A);
 // the host's view of a finished batch, packed by one launch into host-mapped memory (pg_api.hip: settle_batch)
-struct PgSettlePack { uint32_t errflag[6]; int32_t stat_err[6]; uint64_t n_kept, full_slots, n_samples; uint32_t cancel[2]; };
+struct PgSettlePack { uint32_t errflag[6]; int32_t stat_err[6]; uint64_t n_kept, full_slots, n_samples; uint32_t cancel[2]; uint32_t front[2]; };
+// front_word (may be null): PgFront::word of a batch counted front first -> front[0]
 hipError_t pg_launch_settle_pack(hipStream_t st, const uint32_t *errflag, const int32_t *stat_err, const int32_t *long_cnt, const uint64_t *totals, const uint64_t *samp_off,
-                                 uint64_t samp_off_entries, const uint32_t *cancel_flag, PgSettlePack *out);
+                                 uint64_t samp_off_entries, const uint32_t *cancel_flag, const uint32_t *front_word, PgSettlePack *out);
 // flag[0] = some slot still open below this rank (sum of rows_below rows of all_counts < limit), flag[1] = statistics cancelled; if none
 // is open, the reads' statistics records (plan_buf) are set to "skip"
 hipError_t pg_launch_stats_cancel_if_full(hipStream_t st, const uint64_t *all_counts, uint32_t rows_below, uint32_t n_slots, uint64_t limit, uint32_t *flag, void *plan_buf, uint32_t n_reads);

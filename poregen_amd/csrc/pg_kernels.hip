@@ -487,7 +487,13 @@ __device__ __forceinline__ uint32_t event_slot_scalar(const PgDevBatch &B, const
 // LT: both slot tables (<= 1024 codes each: k <= 5; <= 1024 slots: COUNT) as 16-bit entries in LDS -- 16 look-ups per thread at LDS latency
 // COUNT: 0 = slots only; 1 = direct ranking: counts per (tile, slot), the event's read in the upper bits of its slot word; 2 = partitioned
 // ranking (pg_place.hip): counts per (tile, high digit of the slot = slot >> cshift), plain slot words
-template <int COUNT, bool LT> __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(COUNT == 1 ? 8 : (COUNT == 2 ? PG_EV2_WAVES : 4), 8))) void k_events(PgDevBatch B, PgWalkParams W, PgWalkOut O, int nbits, uint32_t n_tiles, uint32_t *__restrict__ hist, uint32_t cshift) {
+template <int COUNT, bool LT> __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(COUNT == 1 ? 8 : (COUNT == 2 ? PG_EV2_WAVES : 4), 8))) void k_events(PgDevBatch B, PgWalkParams W, PgWalkOut O, int nbits, uint32_t n_tiles, uint32_t *__restrict__ hist, uint32_t cshift,
+        uint32_t blk0, const uint32_t *__restrict__ front_word) {
+    // front-first count phase (pg_launch_events' tile range): workgroup blockIdx.x takes the four tiles from 4 (blk0 + blockIdx.x); the launch
+    // over the tiles behind the front has nothing to do once the front has completed every k-mer (PgFront) -- one uniform load per workgroup,
+    // in front of every barrier
+    if (front_word && front_word[0]) return;
+    const uint32_t bx = blk0 + blockIdx.x;
     constexpr int TBL = PG_EV_TBL;
     __shared__ uint16_t ltab[LT ? 2048 + 2 : 2]; // [2048]: 0xFFFF, where a position that is no candidate looks itself up
     __shared__ uint32_t cnt[COUNT ? 4 : 1][COUNT ? PG_RANK_MAX_DIGITS + 32 : 1]; // + 32 dummy bins: positions that are no event
@@ -500,7 +506,7 @@ template <int COUNT, bool LT> __global__ __launch_bounds__(1024) __attribute__((
     __shared__ stage_t stage[4][16][256];
     constexpr uint32_t STAGE_INVALID = COUNT == 1 ? 0xFFFFu : PG_INVALID_SLOT;
     __shared__ uint32_t sh_rf[5], sh_R[4], sh_over[4];
-    const uint32_t tid = threadIdx.x, tile0 = blockIdx.x * 4u, k = W.k, tq = tid >> 8, lt = tid & 255u;
+    const uint32_t tid = threadIdx.x, tile0 = bx * 4u, k = W.k, tq = tid >> 8, lt = tid & 255u;
     const int lane = lane_id();
     const uint64_t N = B.n_ops;
     // the op arrays are only read below NL: a caller's n_ops that is too large (reported by k_batch_init) is not followed behind them
@@ -929,7 +935,7 @@ template <int COUNT, bool LT> __global__ __launch_bounds__(1024) __attribute__((
         for (uint32_t d = tid; d < (1u << nbits); d += 1024)
             *reinterpret_cast<uint4 *>(hist + (uint64_t)d * n_tiles + tile0) = make_uint4(cnt[0][d], cnt[1][d], cnt[2][d], cnt[3][d]);
     }
-    PG_PROBE_END(1, blockIdx.x * 16u + (tid >> 6));
+    PG_PROBE_END(1, bx * 16u + (tid >> 6));
 }
 
 // SAM/BAM front-end (gmove.cpp:1149-1160): a read with an out-of-range sample is a skipped read (no events, no ':')
@@ -999,6 +1005,58 @@ struct PgScanPlan {
     uint32_t *ticket;
 };
 #define PG_SCAN_WAVES 16 // digits (= waves) per workgroup of k_rank_scan: 64 workgroups for 1024 slots, 64 adds to the ticket
+// the end of a scan workgroup whose launch carries the cut: signal, and -- the workgroup that draws last_ticket -- apply the cut.
+// front_word (the front's scan of a front-first count phase, else null): see PgFront and the end of this function
+__device__ __forceinline__ void rank_scan_cut(const PgScanPlan &plan, uint64_t *__restrict__ acc_cnt, int32_t *__restrict__ tile_last, const uint64_t *running,
+                                              uint32_t limit, uint32_t n_slots, uint32_t last_ticket, uint32_t *front_word, uint32_t batch_id) {
+    const int lane = lane_id();
+    __shared__ uint32_t sh_ticket, wsum[PG_SCAN_WAVES], wfull[PG_SCAN_WAVES]; __shared__ int wmax[PG_SCAN_WAVES];
+    __builtin_amdgcn_s_waitcnt(0); // every storing wave: its two stores have left ...
+    __syncthreads();               // ... before the one lane that signals for the workgroup adds to the counter
+    if (threadIdx.x == 0) sh_ticket = __hip_atomic_fetch_add(plan.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    if (sh_ticket != last_ticket) return;
+    // ---- the last workgroup: keep = min(cnt, limit - running), offsets, totals (as k_slot_plan with base == running) ---------------
+    const uint32_t tid = threadIdx.x, w = tid >> 6;
+    uint32_t carry = 0, full = 0; int tmax = -1;
+    for (uint32_t c = 0; c < n_slots; c += PG_SCAN_WAVES * WAVE) {
+        const uint32_t s_ = c + tid;
+        uint32_t kp = 0; bool isfull = false; int tl = -1;
+        if (s_ < n_slots) {
+            const uint64_t cnt = __hip_atomic_load(reinterpret_cast<unsigned long long *>(acc_cnt + s_), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            tl = __hip_atomic_load(tile_last + s_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint64_t b = running[s_];
+            const uint64_t rm = b >= limit ? 0 : (uint64_t)limit - b;
+            kp = (uint32_t)(cnt < rm ? cnt : rm);
+            isfull = limit > 0 && b + cnt >= limit; // at limit 0 no k-mer ever completes (gmove.cpp:925-927 skips every event)
+            if (!front_word) plan.running_out[s_] = b + cnt;
+            plan.keep[s_] = kp;
+        }
+        const uint32_t inc = wave_incl_scan_u32(kp); // kept events of a batch number < 2^31
+        const uint32_t nf = (uint32_t)__popcll(__ballot(isfull));
+        for (int o = 32; o >= 1; o >>= 1) { const int t = __shfl_xor(tl, o, WAVE); tl = t > tl ? t : tl; }
+        if (lane == WAVE - 1) { wsum[w] = inc; wfull[w] = nf; wmax[w] = tl; }
+        __syncthreads();
+        uint32_t off = 0, tot = 0;
+        for (uint32_t ww = 0; ww < PG_SCAN_WAVES; ++ww) { if (ww < w) off += wsum[ww]; tot += wsum[ww]; full += wfull[ww]; tmax = wmax[ww] > tmax ? wmax[ww] : tmax; }
+        if (s_ < n_slots) plan.ev_off[s_] = (uint64_t)carry + off + inc - kp;
+        carry += tot;
+        __syncthreads();
+    }
+    if (front_word) { // the front's scan: the running counts move on only if the front has completed every k-mer (else the scan behind it starts from them)
+        const bool complete = limit > 0 && full == n_slots && front_word[1] != batch_id;
+        if (complete)
+            for (uint32_t s_ = tid; s_ < n_slots; s_ += PG_SCAN_WAVES * WAVE)
+                plan.running_out[s_] = running[s_] + __hip_atomic_load(reinterpret_cast<unsigned long long *>(acc_cnt + s_), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) front_word[0] = complete ? 1u : 0u;
+    }
+    if (tid == 0) {
+        plan.ev_off[n_slots] = carry; plan.plan_totals[0] = carry; plan.plan_totals[1] = full;
+        plan.plan_totals[3] = (uint64_t)(int64_t)tmax; // read as a signed tile index by k_rank_emit
+        __hip_atomic_store(plan.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // for the next batch
+    }
+}
+
 __global__ __launch_bounds__(PG_SCAN_WAVES * WAVE) void k_rank_scan(uint32_t *__restrict__ hist, uint32_t n_tiles, uint32_t *__restrict__ totals,
                                                   uint64_t *__restrict__ acc_cnt, uint32_t n_slots, uint32_t n_digits, const uint64_t *running,
                                                   uint32_t limit, int32_t *__restrict__ tile_last, uint64_t *__restrict__ acc_copy, PgScanPlan plan,
@@ -1088,44 +1146,65 @@ __global__ __launch_bounds__(PG_SCAN_WAVES * WAVE) void k_rank_scan(uint32_t *__
         }
     }
     if (!plan.keep) return; // (block-uniform)
-    __shared__ uint32_t sh_ticket, wsum[PG_SCAN_WAVES], wfull[PG_SCAN_WAVES]; __shared__ int wmax[PG_SCAN_WAVES];
-    __builtin_amdgcn_s_waitcnt(0); // every storing wave: its two stores have left ...
-    __syncthreads();               // ... before the one lane that signals for the workgroup adds to the counter
-    if (threadIdx.x == 0) sh_ticket = __hip_atomic_fetch_add(plan.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if (sh_ticket != gridDim.x - (bp_out ? 2u : 1u)) return; // (the block-sum workgroup, if any, takes no ticket)
-    // ---- the last workgroup: keep = min(cnt, limit - running), offsets, totals (as k_slot_plan with base == running) ---------------
-    const uint32_t tid = threadIdx.x, w = tid >> 6;
-    uint32_t carry = 0, full = 0; int tmax = -1;
-    for (uint32_t c = 0; c < n_slots; c += PG_SCAN_WAVES * WAVE) {
-        const uint32_t s_ = c + tid;
-        uint32_t kp = 0; bool isfull = false; int tl = -1;
-        if (s_ < n_slots) {
-            const uint64_t cnt = __hip_atomic_load(reinterpret_cast<unsigned long long *>(acc_cnt + s_), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            tl = __hip_atomic_load(tile_last + s_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const uint64_t b = running[s_];
-            const uint64_t rm = b >= limit ? 0 : (uint64_t)limit - b;
-            kp = (uint32_t)(cnt < rm ? cnt : rm);
-            isfull = limit > 0 && b + cnt >= limit; // at limit 0 no k-mer ever completes (gmove.cpp:925-927 skips every event)
-            plan.running_out[s_] = b + cnt;
-            plan.keep[s_] = kp;
+    rank_scan_cut(plan, acc_cnt, tile_last, running, limit, n_slots, gridDim.x - (bp_out ? 2u : 1u), nullptr, 0u); // (the block-sum workgroup, if any, takes no ticket)
+}
+
+// The tile scan of the front-first count phase (PgFront; direct ranking, the cut in the launch). TAIL = false: columns [0, F) of every row,
+// and the cut as if the batch ended there -- if that completes every k-mer, keep / ev_off / the totals / the last useful tile are what the
+// whole batch gives (a full k-mer keeps limit - running events, the first ones in tile order, whatever follows), and the running counts move
+// on by the front's counts: at least the limit either way, which is all any reader asks of a full k-mer. TAIL = true: leaves at once behind a
+// complete front; else columns [F, n_tiles) with each row's carry = the front's total, the last useful tile over the whole row (the front's
+// answer stands where no column here qualifies: see below), and the cut over the whole row from the running counts the front left alone.
+template <bool TAIL> __global__ __launch_bounds__(PG_SCAN_WAVES * WAVE) void k_rank_scan_part(uint32_t *__restrict__ hist, uint32_t n_tiles, uint32_t F, uint32_t *__restrict__ totals,
+                                                  uint64_t *__restrict__ acc_cnt, uint32_t n_slots, uint32_t n_digits, const uint64_t *running,
+                                                  uint32_t limit, int32_t *__restrict__ tile_last, PgScanPlan plan, uint32_t *front_word, uint32_t batch_id) {
+    if (TAIL && front_word[0]) return; // (block-uniform, in front of every barrier)
+    const uint32_t d = blockIdx.x * PG_SCAN_WAVES + (threadIdx.x >> 6); // one wave per digit
+    const int lane = lane_id();
+    if (d < n_digits) {
+        const uint32_t c_begin = TAIL ? F : 0u, c_end = TAIL ? n_tiles : F;
+        uint32_t run = TAIL ? totals[d] : 0u;
+        const bool want_last = d < n_slots;
+        const uint64_t base0 = want_last ? running[d] : 0;
+        const uint32_t room = base0 >= limit ? 0u : limit - (uint32_t)base0;
+        int candA = -1, candB = -1;
+        uint32_t *__restrict__ row = hist + (uint64_t)d * n_tiles;
+        for (uint32_t c0 = c_begin; c0 < c_end; c0 += 8 * WAVE) { // as k_rank_scan
+            uint32_t v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) { const uint32_t i = c0 + u * WAVE + lane; v[u] = i < c_end ? row[i] : 0u; }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const uint32_t i = c0 + u * WAVE + lane;
+                const uint32_t inc = wave_incl_scan_u32(v[u]);
+                const uint32_t excl = run + inc - v[u];
+                if (i < c_end) {
+                    row[i] = excl;
+                    if (excl < room) candA = (int)i;
+                    if (v[u] > 0) candB = (int)i;
+                }
+                run += (uint32_t)__builtin_amdgcn_readlane((int)inc, WAVE - 1);
+            }
         }
-        const uint32_t inc = wave_incl_scan_u32(kp); // kept events of a batch number < 2^31
-        const uint32_t nf = (uint32_t)__popcll(__ballot(isfull));
-        for (int o = 32; o >= 1; o >>= 1) { const int t = __shfl_xor(tl, o, WAVE); tl = t > tl ? t : tl; }
-        if (lane == WAVE - 1) { wsum[w] = inc; wfull[w] = nf; wmax[w] = tl; }
-        __syncthreads();
-        uint32_t off = 0, tot = 0;
-        for (uint32_t ww = 0; ww < PG_SCAN_WAVES; ++ww) { if (ww < w) off += wsum[ww]; tot += wsum[ww]; full += wfull[ww]; tmax = wmax[ww] > tmax ? wmax[ww] : tmax; }
-        if (s_ < n_slots) plan.ev_off[s_] = (uint64_t)carry + off + inc - kp;
-        carry += tot;
-        __syncthreads();
+        int last = -1;
+        if (want_last) {
+            last = run >= room ? candA : candB;
+            for (int o = 32; o >= 1; o >>= 1) { const int t = __shfl_xor(last, o, WAVE); last = t > last ? t : last; }
+            // no column behind the front qualifies: the row's answer lies in the front. If the row fills the room, that is the front's largest
+            // tile with a prefix below the room -- which the front left, because it filled the room already (else column F qualifies here);
+            // if not, the front's last non-empty tile -- which the front left, because it did not fill the room either.
+            if (TAIL && last < 0) last = __hip_atomic_load(tile_last + d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (room == 0 || run == 0) last = -1;
+        }
+        if (lane == 0) {
+            totals[d] = run;
+            if (d < n_slots) { // sc1: read back by the last workgroup
+                __hip_atomic_store(reinterpret_cast<unsigned long long *>(acc_cnt + d), (unsigned long long)run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(tile_last + d, last, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
     }
-    if (tid == 0) {
-        plan.ev_off[n_slots] = carry; plan.plan_totals[0] = carry; plan.plan_totals[1] = full;
-        plan.plan_totals[3] = (uint64_t)(int64_t)tmax; // read as a signed tile index by k_rank_emit
-        __hip_atomic_store(plan.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // for the next batch
-    }
+    rank_scan_cut(plan, acc_cnt, tile_last, running, limit, n_slots, gridDim.x - 1u, TAIL ? nullptr : front_word, batch_id);
 }
 
 // generic mode: exclusive prefix over the digits (<= 1024) -> first output index of each digit
@@ -2476,7 +2555,7 @@ __global__ __launch_bounds__(256) void k_batch_init(uint32_t n_reads, uint8_t *_
                                                     uint64_t *__restrict__ running, uint32_t n_slots, int zero_running,
                                                     int32_t *__restrict__ stat_flags, PgDevBatch B, double pa_min, double pa_max,
                                                     PgStatRec *__restrict__ plan_rec, int32_t *__restrict__ stat_status,
-                                                    PgWalkParams W, PgWalkOut O, int force_generic, int op_t_aligned, PgLongState LS) {
+                                                    PgWalkParams W, PgWalkOut O, int force_generic, int op_t_aligned, PgLongState LS, uint32_t *__restrict__ big_op) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i < n_reads) read_head_one(B, W, O, i, force_generic);
     if (plan_rec && i < n_reads) read_plan_one(B, i, nullptr, pa_min, pa_max, plan_rec, stat_status, LS); // eager statistics: see read_plan_one
@@ -2503,6 +2582,16 @@ __global__ __launch_bounds__(256) void k_batch_init(uint32_t n_reads, uint8_t *_
                     if (r != last) { list_generic(O, r); last = r; }
                 }
         }
+        // front-first count phase (PgFront): is there an op of PG_OP_N_LIMIT samples or more anywhere in the batch? k_events reports such an
+        // op of a direct read, and it may not skip a tile that holds one. (A stale mark never equals this batch's serial number.)
+        if (big_op) {
+            uint32_t orv = 0;
+            if (a + 16 <= ops_end) { // op_n is 16-byte aligned (checked by the host)
+#pragma unroll
+                for (int v = 0; v < 4; ++v) { const uint4 x = *reinterpret_cast<const uint4 *>(B.op_n + a + 4 * v); orv |= x.x | x.y | x.z | x.w; }
+            } else for (uint64_t x = a; x < ops_end; ++x) orv |= B.op_n[x];
+            if (orv >= PG_OP_N_LIMIT) *big_op = O.batch_id;
+        }
     }
 }
 
@@ -2518,13 +2607,13 @@ thread_local hipEvent_t pg_prof_start = nullptr, pg_prof_stop = nullptr;
 
 hipError_t pg_launch_batch_init(hipStream_t st, uint32_t n_reads, uint8_t *read_needed, uint64_t *running, uint32_t n_slots,
                           int zero_running, int32_t *stat_flags, const PgDevBatch &B, double pa_min, double pa_max, void *plan_buf,
-                          int32_t *stat_status, const PgWalkParams &W, const PgWalkOut &O, int force_generic, const PgLongState &LS) {
+                          int32_t *stat_status, const PgWalkParams &W, const PgWalkOut &O, int force_generic, const PgLongState &LS, uint32_t *big_op) {
     uint64_t n = (n_reads + 1 > n_slots ? n_reads + 1 : n_slots);
     const uint64_t n_op_threads = (B.n_ops + 15) / 16;
     if (n_op_threads > n) n = n_op_threads;
     const int op_t_aligned = ((uintptr_t)B.op_t & 15) == 0;
     PG_LAUNCH(k_batch_init, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, n_reads, read_needed, running, n_slots, zero_running,
-              stat_flags, B, pa_min, pa_max, reinterpret_cast<PgStatRec *>(plan_buf), stat_status, W, O, force_generic, op_t_aligned, LS);
+              stat_flags, B, pa_min, pa_max, reinterpret_cast<PgStatRec *>(plan_buf), stat_status, W, O, force_generic, op_t_aligned, LS, big_op);
     return hipSuccess;
 }
 
@@ -2538,15 +2627,22 @@ hipError_t pg_launch_walk(hipStream_t st, const PgDevBatch &B, const PgWalkParam
 }
 
 hipError_t pg_launch_events(hipStream_t st, const PgDevBatch &B, const PgWalkParams &W, const PgWalkOut &O, uint32_t n_slots, uint32_t *hist,
-                            uint32_t part_hi_bits, uint32_t part_lo_bits) {
+                            uint32_t part_hi_bits, uint32_t part_lo_bits, const PgFront &F, int pass) {
     if (B.n_reads == 0 || B.n_ops == 0) return hipSuccess;
     const uint32_t n_tiles = pg_tiles(B.n_ops, hist != nullptr);
-    const uint32_t blocks = (n_tiles + 3) / 4;
     int nbits = 1; while ((1u << nbits) < n_slots) ++nbits;
-    if (hist && part_hi_bits) PG_LAUNCH((k_events<2, false>), dim3(blocks), dim3(1024), 0, st, B, W, O, (int)part_hi_bits, n_tiles, hist, part_lo_bits);
-    else if (hist && W.n_codes <= 1024) PG_LAUNCH((k_events<1, true>), dim3(blocks), dim3(1024), 0, st, B, W, O, nbits, n_tiles, hist, 0u);
-    else if (hist) PG_LAUNCH((k_events<1, false>), dim3(blocks), dim3(1024), 0, st, B, W, O, nbits, n_tiles, hist, 0u);
-    else PG_LAUNCH((k_events<0, false>), dim3(blocks), dim3(1024), 0, st, B, W, O, nbits, n_tiles, (uint32_t *)nullptr, 0u);
+    // the workgroups of this launch: all of them, the front's, or the ones behind the front (which look at the front's word first)
+    uint32_t blk0 = 0, blocks = (n_tiles + 3) / 4;
+    const uint32_t *word = nullptr;
+    if (pass != PG_PASS_WHOLE) {
+        if (!hist || part_hi_bits || !F.word || F.tiles == 0 || (F.tiles & 3u) || F.tiles >= n_tiles) return hipErrorInvalidValue;
+        if (pass == PG_PASS_FRONT) blocks = F.tiles / 4;
+        else { blk0 = F.tiles / 4; blocks -= blk0; word = F.word; }
+    }
+    if (hist && part_hi_bits) PG_LAUNCH((k_events<2, false>), dim3(blocks), dim3(1024), 0, st, B, W, O, (int)part_hi_bits, n_tiles, hist, part_lo_bits, 0u, (const uint32_t *)nullptr);
+    else if (hist && W.n_codes <= 1024) PG_LAUNCH((k_events<1, true>), dim3(blocks), dim3(1024), 0, st, B, W, O, nbits, n_tiles, hist, 0u, blk0, word);
+    else if (hist) PG_LAUNCH((k_events<1, false>), dim3(blocks), dim3(1024), 0, st, B, W, O, nbits, n_tiles, hist, 0u, blk0, word);
+    else PG_LAUNCH((k_events<0, false>), dim3(blocks), dim3(1024), 0, st, B, W, O, nbits, n_tiles, (uint32_t *)nullptr, 0u, 0u, (const uint32_t *)nullptr);
     return hipSuccess;
 }
 
@@ -2561,10 +2657,19 @@ static uint32_t tiles_for(uint64_t n) { return pg_tiles(n, false); }
 hipError_t pg_launch_rank_direct_count(hipStream_t st, const uint32_t *ev_slot, uint64_t n, uint32_t n_slots, const PgSortBufs &S,
                                  uint64_t *acc_cnt, uint64_t *running, uint32_t limit, int32_t *tile_last, uint64_t *acc_copy,
                                  uint64_t *plan_keep, uint64_t *plan_ev_off, uint64_t *plan_totals, uint32_t *plan_ticket, bool *plan_done,
-                                 const uint32_t *btot, uint32_t *Bp, uint64_t *zero64) {
+                                 const uint32_t *btot, uint32_t *Bp, uint64_t *zero64, const PgFront &F, int pass, uint32_t batch_id) {
     int nbits = 1; while ((1u << nbits) < n_slots) ++nbits;
     const uint32_t n_tiles = pg_tiles(n, true);
     *plan_done = false;
+    if (pass != PG_PASS_WHOLE) { // front-first count phase: the scan over the front's tiles, or over the ones behind it
+        if (!plan_keep || acc_copy || Bp || !F.word || F.tiles == 0 || (F.tiles & 3u) || F.tiles >= n_tiles) return hipErrorInvalidValue;
+        const PgScanPlan P{plan_keep, plan_ev_off, plan_totals, running, plan_ticket};
+        const dim3 grid(((1u << nbits) + PG_SCAN_WAVES - 1) / PG_SCAN_WAVES), block(PG_SCAN_WAVES * WAVE);
+        if (pass == PG_PASS_FRONT) PG_LAUNCH(k_rank_scan_part<false>, grid, block, 0, st, S.hist, n_tiles, F.tiles, S.totals, acc_cnt, n_slots, 1u << nbits, (const uint64_t *)running, limit, tile_last, P, F.word, batch_id);
+        else PG_LAUNCH(k_rank_scan_part<true>, grid, block, 0, st, S.hist, n_tiles, F.tiles, S.totals, acc_cnt, n_slots, 1u << nbits, (const uint64_t *)running, limit, tile_last, P, F.word, batch_id);
+        *plan_done = true;
+        return hipSuccess;
+    }
     if (n_tiles) { // the counts are in S.hist (k_events<true>)
         PgScanPlan P{};
         if (plan_keep) { P.keep = plan_keep; P.ev_off = plan_ev_off; P.plan_totals = plan_totals; P.running_out = running; P.ticket = plan_ticket; *plan_done = true; }
@@ -2713,7 +2818,8 @@ hipError_t pg_launch_stats_cancel_if_full(hipStream_t st, const uint64_t *all_co
 // cancel flag -- as ONE record in host-mapped memory: four blocking 8..24-byte hipMemcpy calls cost ~80 us per pg_sync (4 us per step of a
 // 20-step timed block); one single-thread kernel and the stream synchronisation that follows anyway cost ~10.
 __global__ void k_settle_pack(const uint32_t *__restrict__ errflag, const int32_t *__restrict__ stat_err, const int32_t *__restrict__ long_cnt, const uint64_t *__restrict__ totals,
-                              const uint64_t *__restrict__ samp_off, uint64_t samp_off_entries, const uint32_t *__restrict__ cancel_flag, PgSettlePack *__restrict__ out) {
+                              const uint64_t *__restrict__ samp_off, uint64_t samp_off_entries, const uint32_t *__restrict__ cancel_flag, const uint32_t *__restrict__ front_word,
+                              PgSettlePack *__restrict__ out) {
     PgSettlePack p;
     for (int i = 0; i < 6; ++i) p.errflag[i] = errflag[i];
     for (int i = 0; i < 4; ++i) p.stat_err[i] = stat_err ? stat_err[i] : (i == 0 ? INT_MAX : 0);
@@ -2721,11 +2827,12 @@ __global__ void k_settle_pack(const uint32_t *__restrict__ errflag, const int32_
     p.n_kept = totals[0]; p.full_slots = totals[1];
     p.n_samples = p.n_kept < samp_off_entries ? samp_off[p.n_kept] : 0; // (a failed batch may leave any total: the host looks at the error words first)
     p.cancel[0] = cancel_flag ? cancel_flag[0] : 0u; p.cancel[1] = cancel_flag ? cancel_flag[1] : 0u;
+    p.front[0] = front_word ? front_word[0] : 0u; p.front[1] = 0u; // the front of a front-first count phase completed every k-mer (PgFront)
     *out = p;
 }
 hipError_t pg_launch_settle_pack(hipStream_t st, const uint32_t *errflag, const int32_t *stat_err, const int32_t *long_cnt, const uint64_t *totals, const uint64_t *samp_off,
-                                 uint64_t samp_off_entries, const uint32_t *cancel_flag, PgSettlePack *out) {
-    PG_LAUNCH(k_settle_pack, dim3(1), dim3(1), 0, st, errflag, stat_err, long_cnt, totals, samp_off, samp_off_entries, cancel_flag, out);
+                                 uint64_t samp_off_entries, const uint32_t *cancel_flag, const uint32_t *front_word, PgSettlePack *out) {
+    PG_LAUNCH(k_settle_pack, dim3(1), dim3(1), 0, st, errflag, stat_err, long_cnt, totals, samp_off, samp_off_entries, cancel_flag, front_word, out);
     return hipSuccess;
 }
 
