@@ -961,7 +961,7 @@ pg_status pg_fit_residuals(uint64_t n_samples, int64_t sum_d, uint64_t sum_dd_lo
  * the model's levels best. Input: a batch as pg_fit_submit takes it, and per read the status, a and b that pg_fit_submit returned for this
  * same batch under the same model, sig_move_offset, rna, min_dur and max_dur. Only reads with PG_FIT_ST_OK are refined; every other read
  * keeps its ops and reports zeros. With B_0 = query_start and B_e = B_{e-1} + n_{e-1}, event e is refinable iff it counts by fit's rule
- * (level l_e); boundary e, 0 < e < Lb, is free iff events e - 1 and e are both refinable and e % 256 != 0; every other boundary is pinned,
+ * (level l_e); boundary e, 0 < e < Lb, is free iff events e - 1 and e are both refinable and e % 256 != phase (0 unless asked for); every other boundary is pinned,
  * B_0 and B_Lb included. A sample r under level l costs d^2, d fit's pass-2 residual (c = llrint(((double)r - a) * (1.0 / b)), d = c - l
  * clamped to |d| <= 2^18 - 1). Per maximal run of free boundaries e0 < e < e1 between the pinned P0 = B_e0 and P1 = B_e1 a dynamic program
  * runs over the candidates p = B_e + j, |j| <= band, that are admissible (P0 + (e - e0) min_len <= p <= P1 - (e1 - e) min_len):
@@ -977,14 +977,14 @@ typedef struct {
     int32_t  rna;                  /* --rna */
     uint32_t band;                 /* --band        0 .. 31 */
     uint32_t min_len;              /* --min_len     1 .. min_dur: the fewest samples a refined event keeps */
-    uint32_t reserved;
+    uint32_t phase;                /* 0 .. 255: the boundaries e with e % 256 == phase are the pinned ones; 0 (a zeroed struct) is the rule above */
 } pg_realign_params;
 typedef struct {                   /* one read; the costs are sums of d^2 over its refinable events under the old and the new boundaries */
     uint32_t n_free, n_moved;      /* free boundaries; those that moved */
     uint64_t sum_abs_shift;        /* sum of |new - old| over the free boundaries, in samples */
     uint64_t cost_before_lo, cost_before_hi, cost_after_lo, cost_after_hi; /* low and high 64 bits */
 } pg_realign_read;
-typedef struct {                   /* one submit; arrays owned by the handle until its next submit / destroy */
+typedef struct {                   /* one submit; reads is owned by the handle until its next submit / destroy, op_n until the submit after the next */
     uint32_t struct_size;          /* sizeof(pg_realign_reads), set by the caller */
     uint32_t reserved;
     uint64_t n_reads, n_ops;
@@ -998,10 +998,15 @@ const char *pg_realign_last_error(const pg_realign *h); /* h may be NULL: error 
 pg_status pg_realign_set_model(pg_realign *h, const uint32_t *levels, uint32_t kmer_size);
 /* The kernels and copies of the following calls go to a caller-owned HIP stream (hipStream_t as void*); NULL restores the handle's own. */
 pg_status pg_realign_set_stream(pg_realign *h, void *hip_stream);
+/* The pinned period's phase for the following submits (pg_realign_params.phase), so that one handle serves rounds that alternate it: the
+ * boundaries a round with phase 0 pins, at multiples of 256, are free in a round with phase 128. PG_ERR_INVALID_ARG above 255. Not while
+ * a submit runs. */
+pg_status pg_realign_set_phase(pg_realign *h, uint32_t phase);
 /* One batch, synchronous. The batch as pg_fit_submit takes it (PG_BATCH_ALL_MATCHES; an I, a D or an unknown op: PG_ERR_INVALID_ARG, the
  * handle stays usable; at most 2^28 samples). status, a, b: host arrays [n_reads] of pg_fit_reads. A read with PG_FIT_ST_OK whose ops leave
  * its samples, or whose a or b is no fit's (b not a finite positive number), fails the batch with PG_ERR_INVALID_ARG before any kernel
- * indexes the signal. */
+ * indexes the signal. A handle has two output arrays and alternates them: the batch's op_n may be the op_n the handle's previous submit
+ * returned (rounds: fit the refined ops, realign them again), and that array stays valid until the submit after this one. */
 pg_status pg_realign_submit(pg_realign *h, const pg_batch *batch, const uint32_t *status, const double *a, const double *b, pg_realign_reads *out);
 /* HIP-event time of the alignment kernel since create or the last call of this */
 pg_status pg_realign_kernel_ms(pg_realign *h, double *ms);

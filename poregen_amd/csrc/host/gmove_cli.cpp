@@ -1,6 +1,7 @@
 // gmove_cli.cpp -- `poregen gmove`: the reference's command line and output layout (src/gmove.cpp:213-537)
 // over libpgmove (include/pgmove.h). Host work here: option handling, k-mer list and slice, SLOW5/PAF/FASTQ
 // parsing into batches, writing the dump directory. The per-read computation runs on the GPU.
+#include "../pg_realign.h"
 #include "pg_cli.h"
 #include "pg_moverecs.h"
 #include <future>
@@ -46,6 +47,9 @@ struct option long_options[] = {
     {"raw_model", required_argument, 0, 0}, {"stdv_limit", required_argument, 0, 0}, {"dwell_model", required_argument, 0, 0},
     {"devices", required_argument, 0, 0}, {"exchange", required_argument, 0, 0},
     {"reform", no_argument, 0, 0}, {"n_to_t", no_argument, 0, 0}, {"event_model", required_argument, 0, 0},
+    {"realign", required_argument, 0, 0}, {"realign_rounds", required_argument, 0, 0}, {"band", required_argument, 0, 0},                 // 33 .. 35
+    {"min_len", required_argument, 0, 0}, {"min_events", required_argument, 0, 0}, {"realign_m", required_argument, 0, 0},                // 36 .. 38
+    {"realign_table", required_argument, 0, 0},                                                                                          // 39
     {0, 0, 0, 0}};
 
 void print_help(FILE *fp, const Opt &o) { // src/gmove.cpp:80-104
@@ -89,6 +93,15 @@ void print_help(FILE *fp, const Opt &o) { // src/gmove.cpp:80-104
     fprintf(fp, "   --reform                   .bam / .sam only: read the move tables as `poregen reform -c -k 1 --stride 0` would (with --rna: reform --rna)\n");
     fprintf(fp, "                              and collect by the rules of a .paf -- the tables are expanded on the GPU, no PAF and no --fastq needed\n");
     fprintf(fp, "   --n_to_t                   with --reform: an N of a read counts as T (sed '2~4s/N/T/g' on the FASTQ)\n");
+    fprintf(fp, "   --realign MODEL            with --reform, one device: refine every batch's event boundaries against the k-mer model on the GPU before\n");
+    fprintf(fp, "                              collecting, as `poregen realign MODEL` followed by gmove on its PAF; --min_dur, --max_dur, --rna and --n_to_t\n");
+    fprintf(fp, "                              are the fit's and the aligner's too; the model's k is its own, independent of -k\n");
+    fprintf(fp, "   --realign_rounds INT       with --realign: rounds of fit and refinement, 1 to 8, as `poregen realign --rounds` [1]\n");
+    fprintf(fp, "   --band INT                 with --realign: how far a boundary may move, in samples, 0 to %u [10]\n", PG_RL_MAX_BAND);
+    fprintf(fp, "   --min_len INT              with --realign: fewest samples a refined event keeps, 1 to --min_dur [3]\n");
+    fprintf(fp, "   --min_events INT           with --realign: counted events a read needs to be fitted [20]\n");
+    fprintf(fp, "   --realign_m INT            with --realign: the model's move start offset, as `poregen realign -m` [0]\n");
+    fprintf(fp, "   --realign_table FILE       with --realign: the per-read table `poregen realign --read_table` writes, for the reads taken\n");
 }
 
 // The signal of a batch is hundreds of MB: a std::vector would zero every byte on resize (one thread, and the page faults
@@ -154,13 +167,16 @@ int gmove_main(int argc, char **argv) {
     std::vector<int32_t> devices; uint32_t exchange = PG_JOB_EXCHANGE_AUTO;
     const char *raw_model_path = nullptr, *dwell_model_path = nullptr, *stdv_limit = "3.1", *event_model_path = nullptr;
     bool reform_mode = false, n_to_t = false;
+    const char *realign_model = nullptr, *realign_table = nullptr, *realign_extra = nullptr; // realign_extra: the first option given that needs --realign
+    long long realign_rounds = 1, realign_band = 10, realign_min_len = 3, realign_min_events = 20, realign_m = 0;
+    int verbose = 3;
     optind = 1;
-    while ((c = getopt_long(argc, argv, "k:m:s:d", long_options, &longindex)) >= 0) { // src/gmove.cpp:240-327
+    while ((c = getopt_long(argc, argv, "k:m:s:dv:", long_options, &longindex)) >= 0) { // src/gmove.cpp:240-327
         if (c == 'k') { if (atoi(optarg) < 1) { fprintf(stderr, "Kmer length should be larger than 0. You entered %d\n", atoi(optarg)); return EXIT_FAILURE; } opt.kmer_size = atoi(optarg); }
         else if (c == 'm') { if (atoi(optarg) < 0) { fprintf(stderr, "signal move offset value must not be less than zero. You entered %d\n", atoi(optarg)); return EXIT_FAILURE; } opt.sig_move_offset = atoi(optarg); }
         else if (c == 's') { if (atoi(optarg) < 1) { fprintf(stderr, "Kmer offset should be larger than 0. You entered %d\n", atoi(optarg)); return EXIT_FAILURE; } opt.kmer_start_offset = atoi(optarg); }
         else if (c == 'd') opt.delimit_files = 1;
-        else if (c == 'v') {}
+        else if (c == 'v') verbose = atoi(optarg);
         else if (c == 'V') { fprintf(stdout, "gmove %s\n", POREGEN_VERSION); return EXIT_SUCCESS; }
         else if (c == 'h') fp_help = stdout;
         else if (c == 0 && longindex == 3) signal_scale = atoi(optarg);
@@ -198,6 +214,21 @@ int gmove_main(int argc, char **argv) {
         else if (c == 0 && longindex == 30) reform_mode = true;
         else if (c == 0 && longindex == 31) n_to_t = true;
         else if (c == 0 && longindex == 32) event_model_path = optarg;
+        else if (c == 0 && longindex == 33) realign_model = optarg;
+        else if (c == 0 && longindex >= 34 && longindex <= 39) {
+            bool ok = true;
+            if (!realign_extra) realign_extra = long_options[longindex].name;
+            if (longindex == 34) ok = whole_int(optarg, 1, 8, realign_rounds);
+            else if (longindex == 35) ok = whole_int(optarg, 0, 0xffffffffll, realign_band);
+            else if (longindex == 36) ok = whole_int(optarg, 0, 0xffffffffll, realign_min_len);
+            else if (longindex == 37) ok = whole_int(optarg, 0, 0xffffffffll, realign_min_events);
+            else if (longindex == 38) ok = whole_int(optarg, 0, 64, realign_m);
+            else realign_table = optarg;
+            if (!ok) {
+                fprintf(stderr, "--%s: '%s' is not a value it takes (--realign_rounds 1..8, --realign_m 0..64, whole numbers)\n", long_options[longindex].name, optarg);
+                print_help(stderr, opt); return EXIT_FAILURE;
+            }
+        }
     }
     if (argc - optind != 3 || fp_help == stdout) { // src/gmove.cpp:330-336
         print_help(fp_help, opt);
@@ -206,6 +237,22 @@ int gmove_main(int argc, char **argv) {
     const char *slow5file = argv[optind], *move_table = argv[optind + 1], *output_dir = argv[optind + 2];
     if (reform_mode && !is_sam_or_bam(move_table)) { fprintf(stderr, "--reform applies to a .bam or .sam event_alignment_file only\n"); print_help(fp_help, opt); return EXIT_FAILURE; }
     if (n_to_t && !reform_mode) { fprintf(stderr, "--n_to_t applies with --reform only\n"); print_help(fp_help, opt); return EXIT_FAILURE; }
+    // --realign: every usage error ends here, before a device is asked for and before the output directory exists
+    std::vector<uint32_t> realign_levels; uint32_t realign_k = 0; int32_t realign_uses_u = 0;
+    {
+        const char *why = nullptr;
+        char text[400];
+        if (realign_model && !reform_mode) why = "--realign applies with --reform only";
+        else if (realign_extra && !realign_model) { snprintf(text, sizeof text, "--%s applies with --realign only", realign_extra); why = text; }
+        else if (realign_model && !devices.empty()) why = "--realign works on one device: it cannot be combined with --devices";
+        else if (realign_model && !pg_rl_params_ok((uint32_t)realign_band, (uint32_t)realign_min_len, (uint32_t)opt.min_dur, (uint32_t)opt.max_dur)) {
+            snprintf(text, sizeof text, "--realign: band <= %u, 1 <= min_len <= min_dur <= max_dur <= %u are required (got band %u, min_len %u, min_dur %u, max_dur %u)", PG_RL_MAX_BAND,
+                     PG_RL_MAX_DUR, (uint32_t)realign_band, (uint32_t)realign_min_len, (uint32_t)opt.min_dur, (uint32_t)opt.max_dur);
+            why = text;
+        }
+        if (why) fprintf(stderr, "%s\n", why);
+        if (why || (realign_model && !load_level_model("gmove", realign_model, 0, realign_levels, realign_k, realign_uses_u))) { print_help(fp_help, opt); return EXIT_FAILURE; }
+    }
     if (event_model_path && devices.size() > 1) return die("--event_model works on one device: it cannot be combined with --devices of more than one device");
     if (event_model_path && devices.size() == 1) { device = devices[0]; devices.clear(); } // (one listed device: the single-device path)
     // --devices cuts every batch into one contiguous shard per device: the default batch grows with the device count, so that a shard
@@ -604,14 +651,41 @@ int gmove_main(int argc, char **argv) {
         // batch by the PAF front-end's rules. Per batch the host reads the records, fetches the signals (pool threads), uploads, expands
         // and submits. Two expanders take turns: the ops of batch i are read by the device until batch i + 1 has been submitted.
         unsigned nt = std::thread::hardware_concurrency(); if (nt > 16) nt = 16; if (nt < 1) nt = 1;
-        struct Slot { pg_mvops *ex = nullptr; PgDev<int16_t> sig; PgDev<uint64_t> sig_off; PgDev<double> cal; };
+        // With --realign every slot also has a fit and a realign handle on its expander's stream: the refined ops are the realign handle's
+        // array, which like the expander's lives until the slot's next batch -- behind the submit of the batch in between.
+        struct Slot { pg_mvops *ex = nullptr; pg_fit *fit = nullptr; pg_realign *ra = nullptr; PgDev<int16_t> sig; PgDev<uint64_t> sig_off; PgDev<double> cal; };
         Slot slots[2];
         pgh::MoveRecs rb;
         std::vector<pgh::Slow5File::RawView> views; std::vector<pgh::Slow5Rec> recs; std::vector<std::string> fetch_err;
         std::vector<double> cal;
         std::vector<uint32_t> h_opn; // --devices: the expansion comes back to the host, which cuts the batch into the job's shards
         pgh::RawMoveRec raw;
-        auto release = [&]() { for (Slot &sl : slots) { if (sl.ex) pg_mvops_destroy(sl.ex); sl.ex = nullptr; sl.sig.release(); sl.sig_off.release(); sl.cal.release(); } };
+        auto release = [&]() {
+            for (Slot &sl : slots) {
+                if (sl.fit) pg_fit_destroy(sl.fit);
+                if (sl.ra) pg_realign_destroy(sl.ra);
+                if (sl.ex) pg_mvops_destroy(sl.ex);
+                sl.fit = nullptr; sl.ra = nullptr; sl.ex = nullptr; sl.sig.release(); sl.sig_off.release(); sl.cal.release();
+            }
+        };
+        RealignRounds rounds;
+        uint64_t realign_reads = 0;
+        FILE *rt = nullptr;
+        if (realign_table && !(rt = fopen(realign_table, "w"))) { fprintf(stderr, "Could not open %s for writing.\n", realign_table); status = EXIT_FAILURE; }
+        // the handles of a slot that has an expander and none yet
+        auto realign_handles = [&](Slot &sl, int on_device) {
+            if (sl.ra) return true;
+            pg_fit_params fp; memset(&fp, 0, sizeof fp);
+            fp.struct_size = sizeof fp; fp.sig_move_offset = (uint32_t)realign_m; fp.min_dur = (uint32_t)opt.min_dur; fp.max_dur = (uint32_t)opt.max_dur; fp.min_events = (uint32_t)realign_min_events; fp.rna = opt.flag_rna;
+            pg_realign_params rp; memset(&rp, 0, sizeof rp);
+            rp.struct_size = sizeof rp; rp.sig_move_offset = (uint32_t)realign_m; rp.min_dur = (uint32_t)opt.min_dur; rp.max_dur = (uint32_t)opt.max_dur; rp.rna = opt.flag_rna; rp.band = (uint32_t)realign_band; rp.min_len = (uint32_t)realign_min_len;
+            void *xs = pg_mvops_stream(sl.ex);
+            if (pg_fit_create(&fp, on_device, &sl.fit) != PG_OK) { fprintf(stderr, "[gmove] %s\n", pg_fit_last_error(nullptr)); return false; }
+            if (pg_realign_create(&rp, on_device, &sl.ra) != PG_OK) { fprintf(stderr, "[gmove] %s\n", pg_realign_last_error(nullptr)); return false; }
+            if (pg_fit_set_model(sl.fit, realign_levels.data(), realign_k) != PG_OK || pg_fit_set_stream(sl.fit, xs) != PG_OK) { fprintf(stderr, "[gmove] %s\n", pg_fit_last_error(sl.fit)); return false; }
+            if (pg_realign_set_model(sl.ra, realign_levels.data(), realign_k) != PG_OK || pg_realign_set_stream(sl.ra, xs) != PG_OK) { fprintf(stderr, "[gmove] %s\n", pg_realign_last_error(sl.ra)); return false; }
+            return true;
+        };
         bool eof = false;
         while (!stop && !eof && status == EXIT_SUCCESS) {
             // ---- the records: the first one that cannot be taken ends the batch in front of it
@@ -707,6 +781,13 @@ int gmove_main(int argc, char **argv) {
                     b.query_start = mr.query_start; b.target_start = mr.target_start; b.target_end = mr.target_end; b.seq = mr.seq; b.seq_off = mr.seq_off;
                     b.op_n = mr.op_n; b.op_t = mr.op_t; b.op_off = mr.op_off;
                     b.flags = PG_BATCH_ALL_MATCHES; // every op is a match and a read has as many ops as bases: what `reform` writes
+                    if (realign_model) { // the rounds on the device batch; the collector takes the last round's ops
+                        if (!realign_handles(sl, ex_device)) { status = EXIT_FAILURE; break; }
+                        if (!rounds.run(sl.fit, sl.fit, sl.ra, b, realign_rounds)) { fprintf(stderr, "[gmove] %s\n", rounds.err.c_str()); status = EXIT_FAILURE; break; }
+                        b.op_n = rounds.op_n;
+                        realign_reads += n;
+                        if (rt) for (size_t i = 0; i < n; i++) rounds.row(rt, rb.names[i].c_str(), i);
+                    }
                     if (dev.submit(&b) != PG_OK) { fprintf(stderr, "[gmove] %s\n", dev.error()); status = EXIT_FAILURE; break; }
                     t_device += secs(tf0, clk::now());
                     cur ^= 1;
@@ -729,6 +810,10 @@ int gmove_main(int argc, char **argv) {
         // the device has read the last batch's ops before the expanders go
         if (dev.ok() && dev.sync() != PG_OK && status == EXIT_SUCCESS) { fprintf(stderr, "[gmove] %s\n", dev.error()); status = EXIT_FAILURE; }
         release();
+        if (rt && fclose(rt) != 0 && status == EXIT_SUCCESS) { fprintf(stderr, "Error in writing %s.\n", realign_table); status = EXIT_FAILURE; }
+        if (realign_model && verbose >= 4)
+            fprintf(stderr, "[gmove] realign: k=%u band=%lld rounds=%lld reads=%llu refined=%llu free=%llu moved=%llu\n", realign_k, realign_band, realign_rounds,
+                    (unsigned long long)realign_reads, (unsigned long long)rounds.refined, (unsigned long long)rounds.n_free, (unsigned long long)rounds.n_moved);
         hbs[0].clear(); hbs[1].clear(); // (nothing is left for the flush behind the loops)
     } else
     for (;;) {

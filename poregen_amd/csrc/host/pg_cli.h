@@ -1,5 +1,6 @@
 // pg_cli.h -- what the subcommands that run on the device share besides the file readers (pg_host.h): the error exit, option values,
-// file suffixes, the HIP check, and for `fit` and `realign` the model, the batch handed to pg_fit_* and the per-k-mer table.
+// file suffixes, the HIP check, and for `fit` and `realign` the model, the batch handed to pg_fit_* and the per-k-mer table; the rounds of
+// fit and realign that `realign --rounds` and `gmove --reform --realign` share.
 // (`transform` words its errors its own way and is built without HIP: it does not include this.)
 #pragma once
 #include "../../../include/pgmove.h"
@@ -86,6 +87,49 @@ inline std::string pooled_rms(const pg_fit_result &r, uint64_t n_slots) { // ove
     for (uint64_t s = 0; s < n_slots; s++) dd += ((unsigned __int128)r.sum_dd_hi[s] << 64) | r.sum_dd_lo[s];
     return rms_text(r.samples, (uint64_t)dd, (uint64_t)(dd >> 64));
 }
+
+// The rounds of `realign --rounds` and `gmove --reform --realign` over one device batch: round t fits the ops of round t - 1 (ops_0: the
+// batch's) and refines them with that fit, at phase 0 when t is odd and 128 when it is even, so that what one round pins the next one
+// refines. Nothing but the ops goes from round to round. fit1 fits round 1, fit_more the rounds behind it (the same handle where nobody
+// pools round 1's sums). op_n: the last round's ops, the realign handle's array, valid until the handle's submit after the next.
+struct RealignRounds {
+    std::vector<pg_realign_read> acc;  // per read: the counts summed over the rounds, cost_before of round 1, cost_after of the last round
+    std::vector<uint32_t> status;      // per read: round 1's fit
+    std::vector<uint64_t> ns_before, ns_after; // per read: the counted samples of round 1's and of the last round's fit, 0 unless that fit is ok
+    const uint32_t *op_n = nullptr;
+    uint64_t refined = 0, n_free = 0, n_moved = 0; // over every batch: reads round 1 fits; free and moved boundaries, summed over the rounds
+    std::string err;
+
+    bool run(pg_fit *fit1, pg_fit *fit_more, pg_realign *ra, const pg_batch &b, long long rounds) {
+        const size_t n = b.n_reads;
+        pg_batch cur = b;
+        acc.assign(n, pg_realign_read{0, 0, 0, 0, 0, 0, 0}); status.assign(n, 0); ns_before.assign(n, 0); ns_after.assign(n, 0);
+        for (long long t = 1; t <= rounds; t++) {
+            pg_fit *fit = t == 1 ? fit1 : fit_more;
+            pg_fit_reads f;
+            pg_realign_reads rr; memset(&rr, 0, sizeof rr); rr.struct_size = sizeof rr;
+            if (pg_fit_submit(fit, &cur, nullptr, &f) != PG_OK) { err = pg_fit_last_error(fit); return false; }
+            if (pg_realign_set_phase(ra, t % 2 ? 0u : 128u) != PG_OK || pg_realign_submit(ra, &cur, f.status, f.a, f.b, &rr) != PG_OK) { err = pg_realign_last_error(ra); return false; }
+            for (size_t i = 0; i < n; i++) {
+                const pg_realign_read &q = rr.reads[i];
+                pg_realign_read &o = acc[i];
+                const uint64_t ns = f.status[i] == PG_FIT_ST_OK ? (uint64_t)f.sums[i].n : 0;
+                o.n_free += q.n_free; o.n_moved += q.n_moved; o.sum_abs_shift += q.sum_abs_shift;
+                if (t == 1) { o.cost_before_lo = q.cost_before_lo; o.cost_before_hi = q.cost_before_hi; status[i] = f.status[i]; ns_before[i] = ns; refined += f.status[i] == PG_FIT_ST_OK; }
+                o.cost_after_lo = q.cost_after_lo; o.cost_after_hi = q.cost_after_hi; ns_after[i] = ns;
+                n_free += q.n_free; n_moved += q.n_moved;
+            }
+            cur.op_n = op_n = rr.op_n;
+        }
+        return true;
+    }
+    // read_id  status  n_free  n_moved  sum_abs_shift  rms_before  rms_after
+    void row(FILE *fp, const char *id, size_t i) const {
+        const pg_realign_read &q = acc[i];
+        fprintf(fp, "%s\t%s\t%u\t%u\t%llu\t%s\t%s\n", id, fit_status_name(status[i]), q.n_free, q.n_moved, (unsigned long long)q.sum_abs_shift,
+                rms_text(ns_before[i], q.cost_before_lo, q.cost_before_hi).c_str(), rms_text(ns_after[i], q.cost_after_lo, q.cost_after_hi).c_str());
+    }
+};
 
 // KMER  n_samples  n_events  level  mean_resid  rms_resid for every k-mer in ACGT order; EXIT_SUCCESS, or EXIT_FAILURE with the reason on stderr
 inline int write_kmer_table(const char *path, uint32_t k, bool uses_u, const std::vector<uint32_t> &levels, const pg_fit_result &res) {

@@ -3,6 +3,8 @@
 // (src/realign.cpp) is a copy of reform that aligns nothing. The records are read as `poregen fit` reads them; per batch the move tables
 // are expanded (pg_mvops_expand), every read is calibrated against the model (pg_fit_submit), its free boundaries are refined within
 // --band samples (pg_realign_submit; the rule: csrc/pg_realign.h) and the refined segmentation is scored again by a second fit handle.
+// With --rounds R the last two steps repeat: round t fits the ops of round t - 1 and refines them at phase 0 (t odd) or 128 (t even), so
+// that the boundaries one round pins at multiples of 256 are free in the next; a read that is not fitted in a round keeps its ops in it.
 //   -o            per read the PAF line `poregen reform -c -k 1 -m 0 --stride 0 [--rna]` prints, with the refined durations in ss:Z:
 //   --read_table  read_id  status  n_free  n_moved  sum_abs_shift  rms_before  rms_after      (pA with three decimals, empty unless ok)
 //   --kmer_table  fit's per-k-mer table on the refined segmentation
@@ -27,7 +29,8 @@ const struct option kLongOptions[] = {
     {"min_len", required_argument, nullptr, 0},    // 8
     {"band", required_argument, nullptr, 0},       // 9
     {"read_table", required_argument, nullptr, 0}, // 10
-    {"help", no_argument, nullptr, 'h'},           // 11
+    {"rounds", required_argument, nullptr, 0},     // 11
+    {"help", no_argument, nullptr, 'h'},           // 12
     {nullptr, 0, nullptr, 0}};
 
 void print_help(FILE *fp) {
@@ -43,8 +46,10 @@ void print_help(FILE *fp) {
     fprintf(fp, "   --min_events INT           counted events a read needs to be fitted [20]\n");
     fprintf(fp, "   --min_len INT              fewest samples a refined event keeps, 1 to --min_dur [3]\n");
     fprintf(fp, "   --band INT                 how far a boundary may move, in samples, 0 to %u [10]\n", PG_RL_MAX_BAND);
-    fprintf(fp, "   -o FILE                    the refined PAF [stdout]\n");
-    fprintf(fp, "   --read_table FILE          the per-read table\n");
+    fprintf(fp, "   --rounds INT               rounds of fit and refinement, 1 to 8; even rounds pin the boundaries at 128 + 256 i instead of 256 i [1]\n");
+    fprintf(fp, "   -o FILE                    the refined PAF of the last round [stdout]\n");
+    fprintf(fp, "   --read_table FILE          the per-read table: status and rms_before of round 1, rms_after of the last round; n_free, n_moved and\n");
+    fprintf(fp, "                              sum_abs_shift are sums over the rounds (a boundary free in two rounds counts twice)\n");
     fprintf(fp, "   --kmer_table FILE          the per-k-mer table of the refined segmentation\n");
     fprintf(fp, "   --batch_reads INT          reads per device batch [4000]\n");
     fprintf(fp, "   --device INT               HIP device [0]\n");
@@ -54,7 +59,7 @@ void print_help(FILE *fp) {
 } // namespace
 
 int realign_main(int argc, char **argv) {
-    long long k_opt = 0, m = 0, min_dur = 5, max_dur = 70, min_events = 20, batch_reads = 4000, device = 0, min_len = 3, band = 10;
+    long long k_opt = 0, m = 0, min_dur = 5, max_dur = 70, min_events = 20, batch_reads = 4000, device = 0, min_len = 3, band = 10, rounds = 1;
     bool rna = false, n_to_t = false, help = false;
     const char *out_path = nullptr, *kmer_path = nullptr, *read_path = nullptr;
     int c, longindex = 0;
@@ -76,9 +81,10 @@ int realign_main(int argc, char **argv) {
         else if (c == 0 && longindex == 8) ok = whole_int(optarg, 1, PG_RL_MAX_DUR, min_len);
         else if (c == 0 && longindex == 9) ok = whole_int(optarg, 0, PG_RL_MAX_BAND, band);
         else if (c == 0 && longindex == 10) read_path = optarg;
+        else if (c == 0 && longindex == 11) ok = whole_int(optarg, 1, 8, rounds);
         else { print_help(stderr); return EXIT_FAILURE; }
         if (!ok) {
-            fprintf(stderr, "[realign] %s%s: '%s' is not a value it takes (-k 1..9, -m 0..64, durations 0..%u, --min_len from 1, --band 0..%u)\n", c ? "-" : "--",
+            fprintf(stderr, "[realign] %s%s: '%s' is not a value it takes (-k 1..9, -m 0..64, durations 0..%u, --min_len from 1, --band 0..%u, --rounds 1..8)\n", c ? "-" : "--",
                     c ? std::string(1, (char)c).c_str() : kLongOptions[longindex].name, optarg, PG_RL_MAX_DUR, PG_RL_MAX_BAND);
             return EXIT_FAILURE;
         }
@@ -108,23 +114,24 @@ int realign_main(int argc, char **argv) {
     prm.struct_size = sizeof prm; prm.sig_move_offset = (uint32_t)m; prm.min_dur = (uint32_t)min_dur; prm.max_dur = (uint32_t)max_dur; prm.min_events = (uint32_t)min_events; prm.rna = rna;
     pg_realign_params rp; memset(&rp, 0, sizeof rp);
     rp.struct_size = sizeof rp; rp.sig_move_offset = (uint32_t)m; rp.min_dur = (uint32_t)min_dur; rp.max_dur = (uint32_t)max_dur; rp.rna = rna; rp.band = (uint32_t)band; rp.min_len = (uint32_t)min_len;
-    pg_fit *fit = nullptr, *fit2 = nullptr; pg_realign *ra = nullptr; pg_mvops *ex = nullptr;
+    pg_fit *fit = nullptr, *fit2 = nullptr, *fitm = nullptr; pg_realign *ra = nullptr; pg_mvops *ex = nullptr; // fitm: the fits of rounds 2 .. R, which no table pools
     int status = EXIT_SUCCESS;
-    auto release = [&]() { if (fit) pg_fit_destroy(fit); if (fit2) pg_fit_destroy(fit2); if (ra) pg_realign_destroy(ra); if (ex) pg_mvops_destroy(ex); };
-    if (pg_fit_create(&prm, (int32_t)device, &fit) != PG_OK || pg_fit_create(&prm, (int32_t)device, &fit2) != PG_OK) { fprintf(stderr, "[realign] %s\n", pg_fit_last_error(nullptr)); status = EXIT_FAILURE; }
+    auto release = [&]() { if (fit) pg_fit_destroy(fit); if (fit2) pg_fit_destroy(fit2); if (fitm) pg_fit_destroy(fitm); if (ra) pg_realign_destroy(ra); if (ex) pg_mvops_destroy(ex); };
+    if (pg_fit_create(&prm, (int32_t)device, &fit) != PG_OK || pg_fit_create(&prm, (int32_t)device, &fit2) != PG_OK || (rounds > 1 && pg_fit_create(&prm, (int32_t)device, &fitm) != PG_OK)) { fprintf(stderr, "[realign] %s\n", pg_fit_last_error(nullptr)); status = EXIT_FAILURE; }
     else if (pg_realign_create(&rp, (int32_t)device, &ra) != PG_OK) { fprintf(stderr, "[realign] %s\n", pg_realign_last_error(nullptr)); status = EXIT_FAILURE; }
     else if (pg_mvops_create((int32_t)device, &ex) != PG_OK) { fprintf(stderr, "[realign] %s\n", pg_mvops_last_error(nullptr)); status = EXIT_FAILURE; }
     else if (pg_fit_set_model(fit, levels.data(), k) != PG_OK) { fprintf(stderr, "[realign] %s\n", pg_fit_last_error(fit)); status = EXIT_FAILURE; }
     else if (pg_fit_set_model(fit2, levels.data(), k) != PG_OK) { fprintf(stderr, "[realign] %s\n", pg_fit_last_error(fit2)); status = EXIT_FAILURE; }
+    else if (fitm && pg_fit_set_model(fitm, levels.data(), k) != PG_OK) { fprintf(stderr, "[realign] %s\n", pg_fit_last_error(fitm)); status = EXIT_FAILURE; }
     else if (pg_realign_set_model(ra, levels.data(), k) != PG_OK) { fprintf(stderr, "[realign] %s\n", pg_realign_last_error(ra)); status = EXIT_FAILURE; }
     if (status != EXIT_SUCCESS) { release(); finish_files(); return status; }
     // the expander's stream carries the signal's upload, the expansion, both fits and the alignment: one queue, in order
     const hipStream_t xs = (hipStream_t)pg_mvops_stream(ex);
-    if (pg_fit_set_stream(fit, xs) != PG_OK || pg_fit_set_stream(fit2, xs) != PG_OK || pg_realign_set_stream(ra, xs) != PG_OK) { fprintf(stderr, "[realign] cannot share the expander's stream\n"); status = EXIT_FAILURE; }
+    if (pg_fit_set_stream(fit, xs) != PG_OK || pg_fit_set_stream(fit2, xs) != PG_OK || (fitm && pg_fit_set_stream(fitm, xs) != PG_OK) || pg_realign_set_stream(ra, xs) != PG_OK) { fprintf(stderr, "[realign] cannot share the expander's stream\n"); status = EXIT_FAILURE; }
 
     PgDev<int16_t> d_sig; PgDev<uint64_t> d_sigoff;
     std::vector<uint32_t> h_ops; std::vector<int32_t> h_qs;
-    uint64_t total_free = 0, total_moved = 0;
+    RealignRounds rr;
     pgh::MoveSignalBatches in(sam, s5, "realign", (size_t)batch_reads, (size_t)(PG_FIT_BATCH_SAMPLES / 2), (size_t)PG_FIT_BATCH_SAMPLES);
     const pgh::MoveRecs &rb = in.recs;
     const HipOk hip_ok{"realign", &status};
@@ -148,10 +155,8 @@ int realign_main(int argc, char **argv) {
             if (n_ops > 0xffffffffull) { fprintf(stderr, "[realign] a batch of more than 2^32 - 1 bases: use a smaller --batch_reads\n"); status = EXIT_FAILURE; break; }
             if (n) {
                 const pg_batch b = device_batch(mr, n, n_ops, d_sig.p, d_sigoff.p);
-                pg_fit_reads fr, fr2;
-                pg_realign_reads rr; memset(&rr, 0, sizeof rr); rr.struct_size = sizeof rr;
-                if (pg_fit_submit(fit, &b, nullptr, &fr) != PG_OK) { fprintf(stderr, "[realign] %s\n", pg_fit_last_error(fit)); status = EXIT_FAILURE; break; }
-                if (pg_realign_submit(ra, &b, fr.status, fr.a, fr.b, &rr) != PG_OK) { fprintf(stderr, "[realign] %s\n", pg_realign_last_error(ra)); status = EXIT_FAILURE; break; }
+                pg_fit_reads fr2;
+                if (!rr.run(fit, fitm, ra, b, rounds)) { fprintf(stderr, "[realign] %s\n", rr.err.c_str()); status = EXIT_FAILURE; break; }
                 pg_batch b2 = b; b2.op_n = rr.op_n;
                 if (pg_fit_submit(fit2, &b2, nullptr, &fr2) != PG_OK) { fprintf(stderr, "[realign] %s\n", pg_fit_last_error(fit2)); status = EXIT_FAILURE; break; }
                 h_ops.resize(n_ops); h_qs.resize(n);
@@ -168,14 +173,7 @@ int realign_main(int argc, char **argv) {
                     for (uint32_t e = 0; e < lb; e++) fprintf(fp, "%" PRIu32 ",", h_ops[at + e]);
                     fputc('\n', fp);
                     at += lb;
-                    const pg_realign_read &q = rr.reads[i];
-                    total_free += q.n_free; total_moved += q.n_moved;
-                    if (rf) {
-                        const bool ok = fr.status[i] == PG_FIT_ST_OK;
-                        const uint64_t ns = ok ? (uint64_t)fr.sums[i].n : 0;
-                        fprintf(rf, "%s\t%s\t%u\t%u\t%llu\t%s\t%s\n", id, fit_status_name(fr.status[i]), q.n_free, q.n_moved, (unsigned long long)q.sum_abs_shift,
-                                rms_text(ns, q.cost_before_lo, q.cost_before_hi).c_str(), rms_text(ns, q.cost_after_lo, q.cost_after_hi).c_str());
-                    }
+                    if (rf) rr.row(rf, id, i);
                 }
             }
         }
@@ -185,8 +183,9 @@ int realign_main(int argc, char **argv) {
     if (status == EXIT_SUCCESS && (pg_fit_finish(fit, &res) != PG_OK || pg_fit_finish(fit2, &res2) != PG_OK)) { fprintf(stderr, "[realign] %s%s\n", pg_fit_last_error(fit), pg_fit_last_error(fit2)); status = EXIT_FAILURE; }
     if (status == EXIT_SUCCESS) {
         if (kmer_path) status = write_kmer_table(kmer_path, k, uses_u != 0, levels, res2);
-        fprintf(stderr, "[realign] k=%u band=%lld min_len=%lld reads=%llu refined=%llu free=%llu moved=%llu rms_resid_before=%s rms_resid_after=%s\n", k, band, min_len,
-                (unsigned long long)res.reads, (unsigned long long)res.fitted, (unsigned long long)total_free, (unsigned long long)total_moved, pooled_rms(res, n_slots).c_str(),
+        const std::string rounds_text = rounds > 1 ? " rounds=" + std::to_string(rounds) : std::string();
+        fprintf(stderr, "[realign] k=%u band=%lld min_len=%lld%s reads=%llu refined=%llu free=%llu moved=%llu rms_resid_before=%s rms_resid_after=%s\n", k, band, min_len,
+                rounds_text.c_str(), (unsigned long long)res.reads, (unsigned long long)res.fitted, (unsigned long long)rr.n_free, (unsigned long long)rr.n_moved, pooled_rms(res, n_slots).c_str(),
                 pooled_rms(res2, n_slots).c_str());
     }
     finish_files();

@@ -601,10 +601,17 @@ extern "C" int pgt_realign_params_ok(uint32_t band, uint32_t min_len, uint32_t m
 extern "C" int pgt_realign_walk(const uint8_t *seq, uint32_t lb, const uint32_t *op_n, int64_t q, const int16_t *sig, uint64_t n_sig, const uint32_t *levels, uint32_t k, uint32_t m,
                                 int rna, uint32_t min_dur, uint32_t max_dur, uint32_t band, uint32_t min_len, double a, double b, uint32_t *op_out, uint64_t *out7) {
     PgRlRead r;
-    if (!pg_rl_walk_host(seq, lb, op_n, q, sig, n_sig, levels, k, m, rna != 0, min_dur, max_dur, band, min_len, a, b, op_out, r)) return -1;
+    if (!pg_rl_walk_host(seq, lb, op_n, q, sig, n_sig, levels, k, m, rna != 0, min_dur, max_dur, band, min_len, 0, a, b, op_out, r)) return -1;
     out7[0] = r.n_free; out7[1] = r.n_moved; out7[2] = r.sum_abs_shift; out7[3] = (uint64_t)r.cost_before; out7[4] = (uint64_t)(r.cost_before >> 64);
     out7[5] = (uint64_t)r.cost_after; out7[6] = (uint64_t)(r.cost_after >> 64);
     return 0;
+}
+// the pieces a read of lb ops is cut into under a phase: out[2 j] = first op, out[2 j + 1] = ops of piece j; returns their number (or -1: cap)
+extern "C" long pgt_realign_pieces(uint32_t lb, uint32_t phase, uint32_t *out, size_t cap) {
+    const uint64_t np = pg_rl_pieces(lb, phase);
+    if (np > cap) return -1;
+    for (uint32_t j = 0; j < np; j++) pg_rl_piece(lb, phase, j, out[2 * j], out[2 * j + 1]);
+    return (long)np;
 }
 
 // ---- simulate (pg_sim.h): the generator, the rule for one read, the parsers, the command's read drawing and stride rounding -----------------

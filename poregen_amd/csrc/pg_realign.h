@@ -8,7 +8,10 @@
 //
 // Boundaries. B_0 = q, B_e = q + n_0 + .. + n_{e-1}. Event e is REFINABLE iff it counts by fit's rule (pg_fit_kmer_at, pg_fit_code, a
 // level, pg_fit_dur_ok); l_e is its level. Boundary e, 0 < e < Lb, is FREE iff events e - 1 and e are both refinable and
-// e % PG_FIT_PIECE != 0; every other boundary is PINNED (B_0 and B_Lb too) and keeps its position.
+// e % PG_FIT_PIECE != phase (0 .. PG_FIT_PIECE - 1; 0 unless the caller asks); every other boundary is PINNED (B_0 and B_Lb too) and keeps
+// its position. The pinned period cuts a read into PIECES that no run of free boundaries leaves: ops [0, min(phase, Lb)) when phase > 0,
+// then [phase + 256 i, phase + 256 (i + 1)) cut at Lb (pg_rl_pieces, pg_rl_piece). Rounds that alternate the phase between 0 and 128 refine
+// in one round what the other pins.
 //
 // Cost. A sample r_t under level l costs d^2, d = pg_fit_resid(r_t, a, 1.0 / b, l): fit's pass-2 residual, clamp included. Event e - 1
 // laid on [p', p) costs the sum of those squares under l_{e-1}.
@@ -24,8 +27,8 @@
 // samples, each d^2 <= (2^18 - 1)^2 < 2^36: every D < 2^57, an int64. (The kernel drops what is constant per boundary and works with the
 // window sums alone: 2 W < 2^6 samples per boundary, |value| < 2^8 * 2^6 * 2^36 = 2^50; it packs the lane into the low 6 bits of the
 // value it scans: < 2^56.) A piece's cost is at most 2^8 * 2^13 * 2^36 = 2^57: a uint64 per piece on the device. A read of 2^24 counted
-// samples, every boundary moved out by 31, has up to 2^24 + 62 * 2^24 samples: 2^30 * 2^36 passes 2^64, so the host adds the pieces'
-// sums per read in 128 bits.
+// samples, every boundary moved out by 31, has up to 2^24 + 62 * 2^24 samples: 2^30 * 2^36 passes 2^64, so the pieces' sums are
+// added per read in 128 bits (k_rl_reads on the device, pg_rl_walk_host here).
 #pragma once
 #include "pg_fit.h"
 
@@ -49,7 +52,21 @@ template <class Seq> PG_FIT_HD uint32_t pg_rl_level(const Seq seq, uint32_t lb, 
     const int32_t code = pg_fit_code(seq, first, k);
     return code < 0 ? 0u : levels[code];
 }
-PG_FIT_HD bool pg_rl_free(uint32_t e, uint32_t lb, uint32_t lvl_before, uint32_t lvl_at) { return e > 0 && e < lb && lvl_before && lvl_at && e % PG_FIT_PIECE != 0; }
+PG_FIT_HD bool pg_rl_free(uint32_t e, uint32_t lb, uint32_t lvl_before, uint32_t lvl_at, uint32_t phase) {
+    return e > 0 && e < lb && lvl_before && lvl_at && e % PG_FIT_PIECE != phase;
+}
+// the pieces of a read of lb ops: one in front of the first pinned boundary when 0 < phase, then one per period
+PG_FIT_HD uint64_t pg_rl_pieces(uint64_t lb, uint32_t phase) {
+    const uint64_t head = phase < lb ? phase : lb;
+    return (head ? 1u : 0u) + (lb - head + PG_FIT_PIECE - 1) / PG_FIT_PIECE;
+}
+// piece j < pg_rl_pieces(lb, phase): its first op and its ops (1 .. PG_FIT_PIECE)
+PG_FIT_HD void pg_rl_piece(uint32_t lb, uint32_t phase, uint32_t j, uint32_t &e0, uint32_t &cnt) {
+    const uint32_t head = phase < lb ? phase : lb;
+    if (head && j == 0) { e0 = 0; cnt = head; return; }
+    e0 = head + (j - (head ? 1u : 0u)) * PG_FIT_PIECE;
+    cnt = lb - e0 < PG_FIT_PIECE ? lb - e0 : PG_FIT_PIECE;
+}
 // the admissible positions of boundary e of the run (e0, e1) between P0 and P1: [lo, hi]
 PG_FIT_HD void pg_rl_admissible(int64_t P0, int64_t P1, uint32_t e0, uint32_t e1, uint32_t e, uint32_t min_len, int64_t &lo, int64_t &hi) {
     lo = P0 + (int64_t)(e - e0) * min_len; hi = P1 - (int64_t)(e1 - e) * min_len;
@@ -61,7 +78,8 @@ struct PgRlRead { uint32_t n_free = 0, n_moved = 0; uint64_t sum_abs_shift = 0; 
 
 // op_out[lb]: the refined ops. false: out_of_signal (such a read has no fit), nothing is written.
 static inline bool pg_rl_walk_host(const uint8_t *seq, uint32_t lb, const uint32_t *op_n, int64_t q, const int16_t *sig, uint64_t n_sig, const uint32_t *levels, uint32_t k, uint32_t m,
-                                   bool rna, uint32_t min_dur, uint32_t max_dur, uint32_t band, uint32_t min_len, double a, double b, uint32_t *op_out, PgRlRead &out) {
+                                   bool rna, uint32_t min_dur, uint32_t max_dur, uint32_t band, uint32_t min_len, uint32_t phase, double a, double b, uint32_t *op_out,
+                                   PgRlRead &out) {
     out = PgRlRead();
     uint64_t total = 0;
     for (uint32_t e = 0; e < lb; e++) total += op_n[e];
@@ -73,7 +91,7 @@ static inline bool pg_rl_walk_host(const uint8_t *seq, uint32_t lb, const uint32
     B[0] = q;
     for (uint32_t e = 0; e < lb; e++) { B[e + 1] = B[e] + op_n[e]; lvl[e] = pg_rl_level(seq, lb, op_n[e], e, levels, k, m, rna, min_dur, max_dur); }
     Bn = B;
-    auto is_free = [&](uint32_t e) { return e > 0 && e < lb && pg_rl_free(e, lb, lvl[e - 1], lvl[e]); };
+    auto is_free = [&](uint32_t e) { return e > 0 && e < lb && pg_rl_free(e, lb, lvl[e - 1], lvl[e], phase); };
     auto cost = [&](uint32_t e, int64_t lo, int64_t hi) { unsigned __int128 s = 0; for (int64_t t = lo; t < hi; t++) s += pg_rl_cost(sig[t], a, inv_b, lvl[e]); return s; };
     const size_t nc = (size_t)(2 * W + 1);
     for (uint32_t e0 = 0; e0 < lb;) {

@@ -1,11 +1,12 @@
 // pg_realign.hip -- `poregen realign`: the boundaries of the basecaller's move table refined against a k-mer model (the rule: pg_realign.h).
 //
-// A batch is laid out as for pg_fit.hip, and the unit of work is the same: a read is cut into pieces of PG_FIT_PIECE = 256 ops, a WAVE
-// takes a piece, a workgroup is four waves. Boundaries at multiples of 256 are pinned, so a run of free boundaries never leaves its piece
-// and no wave needs another.
-//   k_rl_span    per piece the sum of its ops' lengths and a look at op_t (a batch with an op that is no match is refused). The host scans
-//                the sums into every piece's first sample and refuses a fitted read whose ops leave its samples before any kernel indexes
-//                the signal by them.
+// A batch is laid out as for pg_fit.hip, and the unit of work is the same: a read is cut into pieces of at most PG_FIT_PIECE = 256 ops, a
+// WAVE takes a piece, a workgroup is four waves. The pieces end on the pinned boundaries, e % 256 == phase (pg_rl_piece: with a phase the
+// first piece is the ops in front of boundary `phase`), so a run of free boundaries never leaves its piece and no wave needs another.
+//   k_rl_span    per piece the sum of its ops' lengths and a look at op_t (a batch with an op that is no match is refused).
+//   k_rl_starts  one wave per read: the sums scanned into every piece's first sample; a fitted read whose ops leave its samples raises the
+//                refusal. The host waits for that word (and the op_t flag beside it) before any kernel indexes the signal.
+//   k_rl_reads   one wave per read: the pieces' records of k_rl_align added into the read's 48 bytes, which is all that comes back.
 //   k_rl_align   one piece by one wave:
 //     1. lane j owns op j of a step of 64: its length, its level (0: not refinable), its first sample by a wave scan; the positions, levels
 //        and the free boundaries (four 64-bit masks from ballots) go to the wave's LDS.
@@ -23,7 +24,7 @@
 //     3. the back-pointers, one byte per (boundary, lane), are in the wave's LDS (16 KiB per piece: no scratch buffer to size, no global
 //        round trip in the sequential part); the traceback is a chain of wave-uniform reads that leaves every boundary's shift in LDS.
 //     4. the refined ops, the counts, and both costs: lane j takes the samples of the union of the old and the new span of ITS event of a
-//        step once and adds d^2 to either sum. Per piece two 64-bit sums; the host adds a read's pieces in 128 bits.
+//        step once and adds d^2 to either sum. Per piece two 64-bit sums; k_rl_reads adds a read's pieces in 128 bits.
 // Every number is an integer behind pg_fit_resid; nothing depends on the order of execution. No workgroup waits for another, and the four
 // waves of a workgroup never meet.
 #include "../../include/pgmove.h"
@@ -58,9 +59,10 @@ struct RlBatch {
     const uint32_t *piece_read, *piece_first; // the read of every piece; the first piece of every read (n_reads + 1)
     const uint64_t *piece_start;              // the first sample of the piece's first op, counted in its read (query_start included)
     const uint8_t *part;                      // per read: it is refined
+    const int32_t *qs;                        // per read: query_start
     const uint32_t *levels;
     const double *ab;                         // a and 1 / b of every read
-    uint32_t n_reads, n_pieces, k, m, rna, min_dur, max_dur, band, min_len;
+    uint32_t n_reads, n_pieces, k, m, rna, min_dur, max_dur, band, min_len, phase;
 };
 struct RlPiece { uint32_t n_free, n_moved; u64 sum_abs, cost_before, cost_after; }; // 32 bytes per piece
 static_assert(sizeof(RlPiece) == 32, "the pieces' results come back as 32 bytes each");
@@ -118,8 +120,8 @@ __device__ __forceinline__ RlGeo rl_geo(const RlBatch &B, uint32_t pid) {
     g.r = B.piece_read[pid];
     g.o0 = B.op_off[g.r];
     g.lb = (uint32_t)(B.op_off[g.r + 1] - g.o0);
-    g.e0 = (pid - B.piece_first[g.r]) * kPiece;
-    g.cnt = min(kPiece, g.lb - g.e0);
+    pg_rl_piece(g.lb, B.phase, pid - B.piece_first[g.r], g.e0, g.cnt);
+    g.cnt = min(kPiece, g.cnt);                                           // (it is: said once more where the compiler sees it, as before the phase)
     g.s0 = B.seq_off[g.r]; g.sig0 = B.sig_off[g.r];
     return g;
 }
@@ -133,6 +135,25 @@ __global__ __launch_bounds__(kThreads) void k_rl_span(const RlBatch B, uint64_t 
     s = wave_sum(s);
     if (__any(bad != 0) && lane == 0) atomicOr(flag, 1u);
     if (lane == 0) psum[pid] = s;
+}
+
+// One wave per read: the pieces' sums scanned into every piece's first sample, 64 pieces a step. A read that is to be refined and does not
+// lie inside its samples raises the refusal: the smallest such read's index into flag[1], which starts at UINT32_MAX. Nothing here indexes
+// the signal. A read has fewer than 2^31 ops of fewer than 2^32 samples and a query_start below 2^31: every sum stays below 2^64.
+static_assert(31 + 32 < 64, "a read's samples, summed over its ops, fit a uint64");
+__global__ __launch_bounds__(kThreads) void k_rl_starts(const RlBatch B, const uint64_t *__restrict__ psum, uint64_t *__restrict__ piece_start, uint32_t *__restrict__ flag) {
+    const uint32_t lane = threadIdx.x & (kWave - 1), r = blockIdx.x * kWaves + threadIdx.x / kWave;
+    if (r >= B.n_reads) return;                                           // (the whole wave)
+    const uint32_t p0 = B.piece_first[r], p1 = B.piece_first[r + 1];
+    const int32_t q = B.qs[r];
+    uint64_t at = q < 0 ? 0ull : (uint64_t)q;
+    for (uint32_t p = p0; p < p1; p += kWave) {                           // (uniform)
+        const uint32_t i = p + lane;
+        const uint64_t v = i < p1 ? psum[i] : 0ull, incl = wave_incl_scan_u64(v);
+        if (i < p1) piece_start[i] = at + (incl - v);
+        at += __shfl(incl, kWave - 1, kWave);
+    }
+    if (lane == 0 && B.part[r] && (q < 0 || at > B.sig_off[r + 1] - B.sig_off[r])) atomicMin(flag + 1, r);
 }
 
 // the first set bit of the 256 at or behind i, or 256; with `clear`, the first bit that is not set
@@ -181,7 +202,7 @@ __global__ __launch_bounds__(kThreads) void k_rl_align(const RlBatch B, uint32_t
     }
     uint32_t n_free = 0;
 #pragma unroll
-    for (uint32_t st = 0; st < kSteps; st++) { // boundary i is free iff ops i - 1 and i are refinable; boundary 0 is e % 256 == 0, bits from cnt on are clear
+    for (uint32_t st = 0; st < kSteps; st++) { // boundary i is free iff ops i - 1 and i are refinable; boundary 0 of a piece is a pinned one (pg_rl_piece), bits from cnt on are clear
         const uint64_t fm = ref[st] & ((ref[st] << 1) | (st ? ref[st - 1] >> 63 : 0ull));
         if (lane == 0) L.freem[st] = fm;
         n_free += (uint32_t)__popcll(fm);
@@ -263,6 +284,36 @@ __global__ __launch_bounds__(kThreads) void k_rl_align(const RlBatch B, uint32_t
     if (lane == 0) pstats[pid] = RlPiece{n_free, (uint32_t)moved, abs_shift, cost_before, cost_after};
 }
 
+// One wave per read: its pieces' records added into the read's. A read has fewer than 2^31 ops, so fewer than 2^24 pieces (phase 0: 2^23;
+// a phase adds one): the counts stay below 2^31, the shifts below 2^31 * 31 < 2^36. A piece's cost is below 2^57 (pg_realign.h); the low
+// and the high 32 bits of the pieces' costs are summed apart -- below 2^32 * 2^24 and 2^25 * 2^24, a uint64 each over the whole read, in
+// any order -- and put together as a 128-bit number at the end: lo + hi * 2^32, with the carry.
+static_assert(PG_FIT_PIECE == 256 && 31 - 8 + 1 <= 24 && 32 + 24 < 64 && 57 - 32 + 24 < 64, "the halves of the pieces' costs add up in 64 bits");
+__device__ __forceinline__ void put_128(u64 lo_sum, u64 hi_sum, uint64_t &lo, uint64_t &hi) {
+    lo = lo_sum + (hi_sum << 32);
+    hi = (hi_sum >> 32) + (lo < lo_sum ? 1ull : 0ull);
+}
+__global__ __launch_bounds__(kThreads) void k_rl_reads(const RlBatch B, const RlPiece *__restrict__ pstats, pg_realign_read *__restrict__ reads) {
+    const uint32_t lane = threadIdx.x & (kWave - 1), r = blockIdx.x * kWaves + threadIdx.x / kWave;
+    if (r >= B.n_reads) return;                                           // (the whole wave)
+    const uint32_t p0 = B.piece_first[r], p1 = B.piece_first[r + 1];
+    u64 n_free = 0, n_moved = 0, sum_abs = 0, b_lo = 0, b_hi = 0, a_lo = 0, a_hi = 0;
+    for (uint32_t p = p0 + lane; p < p1; p += kWave) {
+        const RlPiece q = pstats[p];
+        n_free += q.n_free; n_moved += q.n_moved; sum_abs += q.sum_abs;
+        b_lo += q.cost_before & 0xffffffffull; b_hi += q.cost_before >> 32;
+        a_lo += q.cost_after & 0xffffffffull; a_hi += q.cost_after >> 32;
+    }
+    n_free = wave_sum(n_free); n_moved = wave_sum(n_moved); sum_abs = wave_sum(sum_abs);
+    b_lo = wave_sum(b_lo); b_hi = wave_sum(b_hi); a_lo = wave_sum(a_lo); a_hi = wave_sum(a_hi);
+    if (lane == 0) {
+        pg_realign_read o;
+        o.n_free = (uint32_t)n_free; o.n_moved = (uint32_t)n_moved; o.sum_abs_shift = sum_abs;
+        put_128(b_lo, b_hi, o.cost_before_lo, o.cost_before_hi); put_128(a_lo, a_hi, o.cost_after_lo, o.cost_after_hi);
+        reads[r] = o;
+    }
+}
+
 } // namespace
 
 struct pg_realign {
@@ -273,18 +324,21 @@ struct pg_realign {
     PgEvent ev[2];
     uint32_t k = 0;
     double ms = 0;
-    PgDev<uint32_t> d_levels, d_opn, d_pread, d_pfirst, d_out, d_flag;
+    int cur = 0;                   // d_out[cur] holds the last submit's ops; the next one writes the other
+    bool busy = false;             // a submit left work queued (it failed half way)
+    PgDev<uint32_t> d_levels, d_opn, d_pread, d_pfirst, d_out[2], d_flag;
     PgDev<int16_t> d_sig;
+    PgDev<int32_t> d_qs;
     PgDev<uint64_t> d_sigoff, d_seqoff, d_opoff, d_pstart, d_psum;
     PgDev<uint8_t> d_seq, d_opt, d_part;
     PgDev<RlPiece> d_pstats;
+    PgDev<pg_realign_read> d_reads;
     PgDev<double> d_ab;
-    std::vector<uint64_t> sig_off, seq_off, op_off, psum, pstart;
+    std::vector<uint64_t> sig_off, seq_off, op_off;
     std::vector<int32_t> qs;
     std::vector<uint32_t> piece_read, piece_first;
     std::vector<uint8_t> part;
     std::vector<double> ab;
-    std::vector<RlPiece> pstats;
     std::vector<pg_realign_read> reads;
     std::string err;
 };
@@ -295,6 +349,7 @@ static pg_status rl_check_params(pg_realign *h, const pg_realign_params *p, cons
         return pg_fail(h, PG_ERR_INVALID_ARG, "%s: band <= %u, 1 <= min_len <= min_dur <= max_dur <= %u are required (got band %u, min_len %u, min_dur %u, max_dur %u)", who, PG_RL_MAX_BAND,
                        PG_RL_MAX_DUR, p->band, p->min_len, p->min_dur, p->max_dur);
     if (p->sig_move_offset > 64) return pg_fail(h, PG_ERR_INVALID_ARG, "%s: sig_move_offset %u (at most 64)", who, p->sig_move_offset);
+    if (p->phase >= kPiece) return pg_fail(h, PG_ERR_INVALID_ARG, "%s: phase %u (0 to %u)", who, p->phase, kPiece - 1);
     return PG_OK;
 }
 
@@ -335,6 +390,13 @@ pg_status pg_realign_set_stream(pg_realign *h, void *hip_stream) {
     return PG_OK;
 }
 
+pg_status pg_realign_set_phase(pg_realign *h, uint32_t phase) {
+    if (!h) return pg_fail<pg_realign>(nullptr, PG_ERR_INVALID_ARG, "pg_realign_set_phase: null handle");
+    if (phase >= kPiece) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_set_phase: phase %u (0 to %u)", phase, kPiece - 1);
+    h->prm.phase = phase;
+    return PG_OK;
+}
+
 pg_status pg_realign_kernel_ms(pg_realign *h, double *ms) {
     if (!h) return pg_fail<pg_realign>(nullptr, PG_ERR_INVALID_ARG, "pg_realign_kernel_ms: null handle");
     if (ms) *ms = h->ms;
@@ -351,7 +413,7 @@ pg_status pg_realign_set_model(pg_realign *h, const uint32_t *levels, uint32_t k
     PG_HIP_TRY(h, hipSetDevice(h->device));
     PG_HIP_TRY(h, hipStreamSynchronize(h->s));
     PG_HIP_TRY(h, h->d_levels.ensure(ns * sizeof(uint32_t)));
-    PG_HIP_TRY(h, h->d_flag.ensure(sizeof(uint32_t)));
+    PG_HIP_TRY(h, h->d_flag.ensure(2 * sizeof(uint32_t)));
     PG_HIP_TRY(h, hipMemcpyAsync(h->d_levels.p, levels, ns * sizeof(uint32_t), hipMemcpyHostToDevice, h->s));
     PG_HIP_TRY(h, hipStreamSynchronize(h->s));
     h->k = k;
@@ -368,6 +430,7 @@ pg_status pg_realign_submit(pg_realign *h, const pg_batch *b, const uint32_t *st
     if (b->location != PG_LOC_HOST && b->location != PG_LOC_DEVICE) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_submit: location must be PG_LOC_HOST or PG_LOC_DEVICE");
     if (!(b->flags & PG_BATCH_ALL_MATCHES)) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_submit: the batch must carry PG_BATCH_ALL_MATCHES (every op a match, as `reform` writes them)");
     const uint64_t n = b->n_reads;
+    if (n > 0x7fffffffull) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_submit: batch too large");
     if (!b->sig_off || !b->seq_off || !b->op_off || (n && (!b->query_start || !status || !a || !bb))) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_submit: null array");
     PG_HIP_TRY(h, hipSetDevice(h->device));
     const hipStream_t s = h->s;
@@ -381,7 +444,6 @@ pg_status pg_realign_submit(pg_realign *h, const pg_batch *b, const uint32_t *st
         PG_HIP_TRY(h, hipMemcpyAsync(h->sig_off.data(), b->sig_off, (n + 1) * 8, hipMemcpyDeviceToHost, s));
         PG_HIP_TRY(h, hipMemcpyAsync(h->seq_off.data(), b->seq_off, (n + 1) * 8, hipMemcpyDeviceToHost, s));
         PG_HIP_TRY(h, hipMemcpyAsync(h->op_off.data(), b->op_off, (n + 1) * 8, hipMemcpyDeviceToHost, s));
-        if (n) PG_HIP_TRY(h, hipMemcpyAsync(h->qs.data(), b->query_start, n * 4, hipMemcpyDeviceToHost, s));
         PG_HIP_TRY(h, hipStreamSynchronize(s));
     } else {
         memcpy(h->sig_off.data(), b->sig_off, (n + 1) * 8); memcpy(h->seq_off.data(), b->seq_off, (n + 1) * 8); memcpy(h->op_off.data(), b->op_off, (n + 1) * 8);
@@ -402,7 +464,7 @@ pg_status pg_realign_submit(pg_realign *h, const pg_batch *b, const uint32_t *st
             h->part[r] = 1; h->ab[2 * r] = a[r]; h->ab[2 * r + 1] = 1.0 / bb[r];
         }
         h->piece_first[r] = (uint32_t)h->piece_read.size();
-        const uint64_t np = (lb + kPiece - 1) / kPiece;                   // every read has pieces: the ops of one that is not refined are copied
+        const uint64_t np = pg_rl_pieces(lb, h->prm.phase);               // every read has pieces: the ops of one that is not refined are copied
         if (h->piece_read.size() + np > 0x7fffffffull) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_submit: batch too large");
         h->piece_read.insert(h->piece_read.end(), np, (uint32_t)r);
     }
@@ -416,16 +478,22 @@ pg_status pg_realign_submit(pg_realign *h, const pg_batch *b, const uint32_t *st
 
     RlBatch B{};
     B.n_reads = (uint32_t)n; B.n_pieces = (uint32_t)n_pieces; B.k = h->k; B.m = h->prm.sig_move_offset; B.rna = h->prm.rna ? 1 : 0; B.min_dur = h->prm.min_dur; B.max_dur = h->prm.max_dur;
-    B.band = h->prm.band; B.min_len = h->prm.min_len;
+    B.band = h->prm.band; B.min_len = h->prm.min_len; B.phase = h->prm.phase;
     B.levels = h->d_levels.p;
     auto room = [](size_t bytes) { return bytes + bytes / 4 + 256; };
 #define RL_ENSURE(buf, bytes) PG_HIP_TRY(h, (buf).ensure((bytes) ? (bytes) : 1, room(bytes)))
-    PG_HIP_TRY(h, hipStreamSynchronize(s)); // (nothing queued earlier still reads the buffers about to be refilled or regrown)
+    // (every submit ends behind its last copy: nothing queued earlier still reads the buffers about to be refilled or regrown, unless a
+    // submit failed half way)
+    if (h->busy) { PG_HIP_TRY(h, hipStreamSynchronize(s)); h->busy = false; }
+    const int tgt = h->cur ^ 1;              // the ops go to the array that does not hold the last submit's: the batch's op_n may be that one
     if (dev) {
         const void *must[] = {n_sig ? (const void *)b->sig : nullptr, n_seq ? (const void *)b->seq : nullptr, n_ops ? (const void *)b->op_n : nullptr, n_ops ? (const void *)b->op_t : nullptr};
         for (const void *q : must)
             if (q && pg_ptr_kind(q, h->device) != PG_PTR_DEVICE) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_submit: PG_LOC_DEVICE arrays must be device memory of device %d", h->device);
+        if (n_ops && h->d_out[tgt].p && (const void *)b->op_n >= (const void *)h->d_out[tgt].p && (const char *)b->op_n < (const char *)h->d_out[tgt].p + h->d_out[tgt].cap)
+            return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_submit: op_n is the array of the submit before the last one (a result's op_n is valid until the submit after the next)");
         B.sig = b->sig; B.sig_off = b->sig_off; B.seq = b->seq; B.seq_off = b->seq_off; B.op_n = b->op_n; B.op_t = b->op_t; B.op_off = b->op_off;
+        B.qs = b->query_start;
     } else {
         RL_ENSURE(h->d_sig, n_sig * 2); RL_ENSURE(h->d_seq, n_seq); RL_ENSURE(h->d_opn, n_ops * 4); RL_ENSURE(h->d_opt, n_ops);
         RL_ENSURE(h->d_sigoff, (n + 1) * 8); RL_ENSURE(h->d_seqoff, (n + 1) * 8); RL_ENSURE(h->d_opoff, (n + 1) * 8);
@@ -438,69 +506,68 @@ pg_status pg_realign_submit(pg_realign *h, const pg_batch *b, const uint32_t *st
         PG_HIP_TRY(h, hipMemcpyAsync(h->d_sigoff.p, h->sig_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
         PG_HIP_TRY(h, hipMemcpyAsync(h->d_seqoff.p, h->seq_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
         PG_HIP_TRY(h, hipMemcpyAsync(h->d_opoff.p, h->op_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+        RL_ENSURE(h->d_qs, n * 4);
+        if (n) PG_HIP_TRY(h, hipMemcpyAsync(h->d_qs.p, h->qs.data(), n * 4, hipMemcpyHostToDevice, s));
+        B.qs = h->d_qs.p;
         B.sig = h->d_sig.p; B.sig_off = h->d_sigoff.p; B.seq = h->d_seq.p; B.seq_off = h->d_seqoff.p; B.op_n = h->d_opn.p; B.op_t = h->d_opt.p; B.op_off = h->d_opoff.p;
     }
     RL_ENSURE(h->d_pfirst, (n + 1) * 4); RL_ENSURE(h->d_pread, n_pieces * 4); RL_ENSURE(h->d_pstart, n_pieces * 8); RL_ENSURE(h->d_psum, n_pieces * 8);
-    RL_ENSURE(h->d_part, n); RL_ENSURE(h->d_ab, n * 16); RL_ENSURE(h->d_out, n_ops * 4); RL_ENSURE(h->d_pstats, n_pieces * sizeof(RlPiece));
+    RL_ENSURE(h->d_part, n); RL_ENSURE(h->d_ab, n * 16); RL_ENSURE(h->d_out[tgt], n_ops * 4); RL_ENSURE(h->d_pstats, n_pieces * sizeof(RlPiece));
+    RL_ENSURE(h->d_reads, n * sizeof(pg_realign_read));
 #undef RL_ENSURE
     B.piece_first = h->d_pfirst.p; B.piece_read = h->d_pread.p; B.piece_start = h->d_pstart.p; B.part = h->d_part.p; B.ab = h->d_ab.p;
     const uint32_t blocks = (uint32_t)((n_pieces + kWaves - 1) / kWaves);
     (void)hipGetLastError();
     h->reads.assign(n, pg_realign_read{0, 0, 0, 0, 0, 0, 0});
     if (n_pieces) {
-        // ---- the spans of the pieces, and the look at op_t
-        uint32_t flag = 0;
-        h->psum.assign(n_pieces, 0);
+        // ---- the spans of the pieces and the look at op_t; every piece's first sample. flag[0]: an op that is no match; flag[1]: the
+        // first read that is to be refined and does not lie inside its samples. One copy of both, and the one wait of the submit that is
+        // not its end: behind it no kernel indexes the signal of a refused batch.
+        uint32_t flag[2] = {0, 0};
+        const uint32_t read_blocks = (uint32_t)((n + kWaves - 1) / kWaves);
+        h->busy = true;
         PG_HIP_TRY(h, hipMemcpyAsync(h->d_pfirst.p, h->piece_first.data(), (n + 1) * 4, hipMemcpyHostToDevice, s));
         PG_HIP_TRY(h, hipMemcpyAsync(h->d_pread.p, h->piece_read.data(), n_pieces * 4, hipMemcpyHostToDevice, s));
-        PG_HIP_TRY(h, hipMemsetAsync(h->d_flag.p, 0, sizeof(uint32_t), s));
-        hipLaunchKernelGGL(k_rl_span, dim3(blocks), dim3(kThreads), 0, s, B, h->d_psum.p, h->d_flag.p);
-        PG_HIP_TRY(h, hipGetLastError());
-        PG_HIP_TRY(h, hipMemcpyAsync(h->psum.data(), h->d_psum.p, n_pieces * 8, hipMemcpyDeviceToHost, s));
-        PG_HIP_TRY(h, hipMemcpyAsync(&flag, h->d_flag.p, sizeof flag, hipMemcpyDeviceToHost, s));
-        PG_HIP_TRY(h, hipStreamSynchronize(s));
-        if (flag) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_submit: the batch carries PG_BATCH_ALL_MATCHES but holds an op that is no match (an I, a D or an unknown op)");
-        // ---- every piece's first sample; a read that is to be refined lies inside its samples, or no kernel indexes the signal
-        h->pstart.resize(n_pieces);
-        for (uint64_t r = 0; r < n; r++) {
-            const uint64_t len = h->sig_off[r + 1] - h->sig_off[r];
-            uint64_t at = h->qs[r] < 0 ? 0 : (uint64_t)h->qs[r];
-            for (uint32_t p = h->piece_first[r]; p < h->piece_first[r + 1]; p++) { h->pstart[p] = at; at += h->psum[p]; }
-            if (h->part[r] && (h->qs[r] < 0 || at > len))
-                return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_submit: read %llu has the status ok, but its ops leave its samples (the status of another batch?)", (unsigned long long)r);
-        }
-        // ---- the alignment
-        h->pstats.resize(n_pieces);
-        PG_HIP_TRY(h, hipMemcpyAsync(h->d_pstart.p, h->pstart.data(), n_pieces * 8, hipMemcpyHostToDevice, s));
         PG_HIP_TRY(h, hipMemcpyAsync(h->d_part.p, h->part.data(), n, hipMemcpyHostToDevice, s));
         PG_HIP_TRY(h, hipMemcpyAsync(h->d_ab.p, h->ab.data(), n * 16, hipMemcpyHostToDevice, s));
+        PG_HIP_TRY(h, hipMemsetAsync(h->d_flag.p, 0, sizeof(uint32_t), s));
+        PG_HIP_TRY(h, hipMemsetAsync(h->d_flag.p + 1, 0xff, sizeof(uint32_t), s));
+        hipLaunchKernelGGL(k_rl_span, dim3(blocks), dim3(kThreads), 0, s, B, h->d_psum.p, h->d_flag.p);
+        PG_HIP_TRY(h, hipGetLastError());
+        hipLaunchKernelGGL(k_rl_starts, dim3(read_blocks), dim3(kThreads), 0, s, B, h->d_psum.p, h->d_pstart.p, h->d_flag.p);
+        PG_HIP_TRY(h, hipGetLastError());
+        PG_HIP_TRY(h, hipMemcpyAsync(flag, h->d_flag.p, sizeof flag, hipMemcpyDeviceToHost, s));
+        PG_HIP_TRY(h, hipStreamSynchronize(s));
+        h->busy = false;
+        if (flag[0]) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_submit: the batch carries PG_BATCH_ALL_MATCHES but holds an op that is no match (an I, a D or an unknown op)");
+        if (flag[1] != 0xffffffffu)
+            return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_submit: read %llu has the status ok, but its ops leave its samples (the status of another batch?)", (unsigned long long)flag[1]);
+        // ---- the alignment, and the reads' records
+        h->busy = true;
         PG_HIP_TRY(h, hipEventRecord(h->ev[0], s));
-        hipLaunchKernelGGL(k_rl_align, dim3(blocks), dim3(kThreads), 0, s, B, h->d_out.p, h->d_pstats.p);
+        hipLaunchKernelGGL(k_rl_align, dim3(blocks), dim3(kThreads), 0, s, B, h->d_out[tgt].p, h->d_pstats.p);
         PG_HIP_TRY(h, hipGetLastError());
         PG_HIP_TRY(h, hipEventRecord(h->ev[1], s));
-        PG_HIP_TRY(h, hipMemcpyAsync(h->pstats.data(), h->d_pstats.p, n_pieces * sizeof(RlPiece), hipMemcpyDeviceToHost, s));
+        hipLaunchKernelGGL(k_rl_reads, dim3(read_blocks), dim3(kThreads), 0, s, B, h->d_pstats.p, h->d_reads.p);
+        PG_HIP_TRY(h, hipGetLastError());
+        PG_HIP_TRY(h, hipMemcpyAsync(h->reads.data(), h->d_reads.p, n * sizeof(pg_realign_read), hipMemcpyDeviceToHost, s));
         PG_HIP_TRY(h, hipStreamSynchronize(s));
+        h->busy = false;
         float ms = 0; PG_HIP_TRY(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1])); h->ms += ms;
-        for (uint64_t r = 0; r < n; r++) {
-            unsigned __int128 cb = 0, ca = 0;
-            pg_realign_read &o = h->reads[r];
-            for (uint32_t p = h->piece_first[r]; p < h->piece_first[r + 1]; p++) {
-                const RlPiece &q = h->pstats[p];
-                o.n_free += q.n_free; o.n_moved += q.n_moved; o.sum_abs_shift += q.sum_abs; cb += q.cost_before; ca += q.cost_after;
-            }
-            o.cost_before_lo = (uint64_t)cb; o.cost_before_hi = (uint64_t)(cb >> 64); o.cost_after_lo = (uint64_t)ca; o.cost_after_hi = (uint64_t)(ca >> 64);
-        }
     }
-    out->n_reads = n; out->n_ops = n_ops; out->op_n = h->d_out.p; out->reads = h->reads.data();
+    h->cur = tgt;
+    out->n_reads = n; out->n_ops = n_ops; out->op_n = h->d_out[tgt].p; out->reads = h->reads.data();
     return PG_OK;
 }
 
 pg_status pg_realign_walk(const pg_realign_params *p, const uint32_t *levels, uint32_t k, const uint8_t *seq, uint32_t lb, const uint32_t *op_n, int64_t q, const int16_t *sig,
                           uint64_t n_sig, double a, double b, uint32_t *op_out, pg_realign_read *out) {
     if (!p || !levels || !out || (lb && (!seq || !op_n || !op_out)) || (n_sig && !sig) || k < 1 || k > PG_FIT_MAX_K) return PG_ERR_INVALID_ARG;
-    if (p->struct_size != sizeof(pg_realign_params) || !pg_rl_params_ok(p->band, p->min_len, p->min_dur, p->max_dur) || p->sig_move_offset > 64) return PG_ERR_INVALID_ARG;
+    if (p->struct_size != sizeof(pg_realign_params) || !pg_rl_params_ok(p->band, p->min_len, p->min_dur, p->max_dur) || p->sig_move_offset > 64 || p->phase >= PG_FIT_PIECE)
+        return PG_ERR_INVALID_ARG;
     PgRlRead r;
-    if (!pg_rl_walk_host(seq, lb, op_n, q, sig, n_sig, levels, k, p->sig_move_offset, p->rna != 0, p->min_dur, p->max_dur, p->band, p->min_len, a, b, op_out, r)) return PG_ERR_INPUT;
+    if (!pg_rl_walk_host(seq, lb, op_n, q, sig, n_sig, levels, k, p->sig_move_offset, p->rna != 0, p->min_dur, p->max_dur, p->band, p->min_len, p->phase, a, b, op_out, r))
+        return PG_ERR_INPUT;
     *out = pg_realign_read{r.n_free, r.n_moved, r.sum_abs_shift, (uint64_t)r.cost_before, (uint64_t)(r.cost_before >> 64), (uint64_t)r.cost_after, (uint64_t)(r.cost_after >> 64)};
     return PG_OK;
 }

@@ -1879,18 +1879,20 @@ class RealignReads:
         return self.op_n.cpu().numpy().view(np.uint32)
 
 
-def _realign_params(sig_move_offset, rna, min_dur, max_dur, band, min_len):
-    return _abi.PgRealignParams(C.sizeof(_abi.PgRealignParams), sig_move_offset, min_dur, max_dur, int(rna), band, min_len, 0)
+def _realign_params(sig_move_offset, rna, min_dur, max_dur, band, min_len, phase=0):
+    return _abi.PgRealignParams(C.sizeof(_abi.PgRealignParams), sig_move_offset, min_dur, max_dur, int(rna), band, min_len, phase)
 
 
 class Realigner:
     """Refines the ops of batches laid out as MoveExpander leaves them against a k-mer model (pg_realign_*). submit(batch, fit_reads) takes
-    the FitReads that ModelFit.submit returned for the same batch under the same model and parameters; only the reads it fitted move."""
+    the FitReads that ModelFit.submit returned for the same batch under the same model and parameters; only the reads it fitted move.
+    phase (0 .. 255): the boundaries e with e % 256 == phase are the pinned ones."""
 
-    def __init__(self, levels, k: int, sig_move_offset: int = 0, rna: bool = False, min_dur: int = 5, max_dur: int = 70, band: int = 10, min_len: int = 3, device: int = 0):
+    def __init__(self, levels, k: int, sig_move_offset: int = 0, rna: bool = False, min_dur: int = 5, max_dur: int = 70, band: int = 10, min_len: int = 3, device: int = 0,
+                 phase: int = 0):
         self._lib = _abi.load()
         self.device, self._h = device, None
-        p = _realign_params(sig_move_offset, rna, min_dur, max_dur, band, min_len)
+        p = _realign_params(sig_move_offset, rna, min_dur, max_dur, band, min_len, phase)
         h = C.c_void_p()
         st = self._lib.pg_realign_create(C.byref(p), device, C.byref(h))
         if st != 0:
@@ -1911,7 +1913,13 @@ class Realigner:
         ptr = None if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
         self._check(self._lib.pg_realign_set_stream(self._h, ptr))
 
-    def submit(self, batch: "Batch", fit_reads) -> RealignReads:
+    def set_phase(self, phase: int):
+        """The pinned period's phase for the following submits (rounds alternate 0 and 128)."""
+        self._check(self._lib.pg_realign_set_phase(self._h, phase))
+
+    def submit(self, batch: "Batch", fit_reads, copy: bool = True) -> RealignReads:
+        """copy=False: op_n aliases the handle's own array, which stays valid until the submit after the next one -- a batch whose op_n it
+        is may be submitted again (rounds)."""
         import torch
         cb = _c_batch(batch)
         st = np.ascontiguousarray(fit_reads.status, dtype=np.uint32)
@@ -1928,8 +1936,10 @@ class Realigner:
         if n_ops:  # the handle's buffer lives until its next submit: the caller gets a copy (the submit is complete, the clone synchronised)
             class _Alias:
                 __cuda_array_interface__ = {"shape": (n_ops,), "typestr": "<i4", "data": (int(out.op_n), False), "version": 2}
-            op = torch.as_tensor(_Alias(), device=dev).clone()
-            torch.cuda.current_stream(dev).synchronize()
+            op = torch.as_tensor(_Alias(), device=dev)
+            if copy:
+                op = op.clone()
+                torch.cuda.current_stream(dev).synchronize()
         else:
             op = torch.empty(0, dtype=torch.int32, device=dev)
         return RealignReads(op_n=op, n_free=(rd[:, 0] & 0xffffffff).astype(np.uint32), n_moved=(rd[:, 0] >> 32).astype(np.uint32), sum_abs_shift=rd[:, 1].copy(),
@@ -1966,12 +1976,40 @@ def realign_ops(levels, k: int, batch: "Batch", fit_reads, **kw):
         return r.to_host(), r
 
 
+def realign_rounds(levels, k: int, batch: "Batch", rounds: int, sig_move_offset: int = 0, rna: bool = False, min_dur: int = 5, max_dur: int = 70, min_events: int = 20,
+                   band: int = 10, min_len: int = 3, device: int = 0):
+    """`rounds` (1 .. 8) rounds of fit and realign over one batch: round t fits ops_{t-1} (ops_0: the batch's), and refines them with that
+    fit at phase 0 when t is odd, 128 when it is even; a read that is not fitted in a round keeps its ops in it. Returns (ops_R as numpy
+    uint32, [RealignReads of every round], [FitReads of every round]). The batch is put on the device and left as it was handed in."""
+    import copy as _copy
+    if not 1 <= rounds <= 8:
+        raise ValueError("rounds: 1 to 8")
+    b = _copy.copy(batch if batch.on_device else batch.to_device(f"cuda:{device}"))
+    fit = ModelFit(levels, k, sig_move_offset=sig_move_offset, rna=rna, min_dur=min_dur, max_dur=max_dur, min_events=min_events, device=device)
+    try:
+        with Realigner(levels, k, sig_move_offset=sig_move_offset, rna=rna, min_dur=min_dur, max_dur=max_dur, band=band, min_len=min_len, device=device) as ra:
+            per_round, fits = [], []
+            for t in range(1, rounds + 1):
+                fr = fit.submit(b)
+                fit.finish()
+                ra.set_phase(0 if t % 2 else 128)
+                got = ra.submit(b, fr, copy=False)
+                b.op_n = got.op_n
+                per_round.append(got); fits.append(fr)
+            ops = per_round[-1].to_host().copy()
+            for got in per_round:                                          # (the handle's arrays go with it)
+                got.op_n = None
+            return ops, per_round, fits
+    finally:
+        fit.close()
+
+
 def realign_walk(levels, k: int, seq, ops, q: int, sig, a: float, b: float, sig_move_offset: int = 0, rna: bool = False, min_dur: int = 5, max_dur: int = 70, band: int = 10,
-                 min_len: int = 3):
+                 min_len: int = 3, phase: int = 0):
     """The rule for one fitted read on the host (pg_realign_walk; no GPU needed): (refined ops, n_free, n_moved, sum_abs_shift, cost_before,
     cost_after), or None when the ops leave the samples."""
     lib = _abi.load()
-    p = _realign_params(sig_move_offset, rna, min_dur, max_dur, band, min_len)
+    p = _realign_params(sig_move_offset, rna, min_dur, max_dur, band, min_len, phase)
     lv = np.ascontiguousarray(levels, dtype=np.uint32)
     s = np.frombuffer(seq.encode() if isinstance(seq, str) else bytes(seq), np.uint8)
     o = np.ascontiguousarray(ops, dtype=np.uint32)

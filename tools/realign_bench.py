@@ -11,7 +11,15 @@
     bytes                 what the kernel must read at least once (2 bytes per sample, 4 per op, 1 per base, the level table) and write (4 per
                           op); align_share_of_stream_read: those bytes over align_ms beside the best plain streaming read of
                           tools/probe/stream_probe.hip in the same run
-    submit_ms             wall time of the whole pg_realign_submit: the span kernel, the host scan, the kernel and the copies
+    submit_c_ms           wall time of the library's pg_realign_submit alone; submit_ms is Realigner.submit, which also clones the ops and
+                          turns 2 x 128 bits per read into Python ints
+    submit_ms             wall time of the whole Realigner.submit: the span and starts kernels, the one wait between them and the alignment,
+                          the alignment, the per-read reduction and the copy of 48 bytes per read
+    align_ms_reps / submit_ms_reps   every repetition behind the warm-up: their spread is the margin of an A/B (--lib) on the same box
+    rounds_ms             with --rounds R > 1: wall time of R rounds of pg_fit_submit + pg_realign_submit on one pair of handles, the phase
+                          alternating between 0 and 128, every round's ops the next one's input
+  --phase sets the pinned period's phase of the timed submits; --lib loads another build of libpgmove.so (one from before the phase
+  takes phase 0 only).
   static: per kernel the registers, scratch, LDS and static instruction counts of tools/isa_stats.py and the occupancy of the compiler's
   resource remarks (None when hipcc is not there).
 Prints one JSON object and writes it to --out.
@@ -55,8 +63,10 @@ def static_picture():
     return out
 
 
-def bench(name, read_samples, k, bands, reps, stream_tbps):
+def bench(name, read_samples, k, bands, reps, stream_tbps, phase=0, rounds=1):
     import torch
+    import ctypes as C
+    from poregen_amd import _abi, engine
     from poregen_amd.engine import ModelFit, Realigner
     rng = np.random.default_rng(k)
     levels = rng.integers(60000, 130000, 4 ** k).astype(np.uint32)
@@ -77,8 +87,8 @@ def bench(name, read_samples, k, bands, reps, stream_tbps):
     out = dict(shape=name, k=k, reads=len(read_samples), samples=n_samples, ops=n_ops, pieces=int(np.sum((np.diff(hb.op_off.astype(np.int64)) + 255) // 256)),
                fitted_reads=int((fr.status == 0).sum()), bytes=moved_bytes, pass1_ms=p1, pass2_ms=p2, bands=[])
     for band in bands:
-        ra = Realigner(levels, k, band=band)
-        ms = wall = None
+        ra = Realigner(levels, k, band=band, phase=phase)
+        all_ms, all_wall = [], []
         for i in range(reps + 1):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -86,11 +96,43 @@ def bench(name, read_samples, k, bands, reps, stream_tbps):
             dt = time.perf_counter() - t0
             t = ra.kernel_ms()
             if i:
-                ms = t if ms is None else min(ms, t); wall = dt if wall is None else min(wall, dt)
+                all_ms.append(t); all_wall.append(dt * 1e3)
+        ms, wall = min(all_ms), min(all_wall) * 1e-3
+        # the library call alone, without what the Python layer does with its result (the clone of the ops, 128-bit costs as Python ints)
+        cb = engine._c_batch(db)
+        st_, a_, b_ = (np.ascontiguousarray(x, dtype=t) for x, t in ((fr.status, np.uint32), (fr.a, np.float64), (fr.b, np.float64)))
+        res = _abi.PgRealignReads()
+        all_c = []
+        for i in range(reps + 1):
+            res.struct_size = C.sizeof(_abi.PgRealignReads)
+            t0 = time.perf_counter()
+            rc = ra._lib.pg_realign_submit(ra._h, C.byref(cb), st_.ctypes.data, a_.ctypes.data, b_.ctypes.data, C.byref(res))
+            dt = (time.perf_counter() - t0) * 1e3
+            assert rc == 0
+            ra.kernel_ms()
+            if i:
+                all_c.append(dt)
+        rounds_ms = None
+        if rounds > 1:
+            import copy
+            fit2 = ModelFit(levels, k)
+            for i in range(reps + 1):
+                b = copy.copy(db)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for t in range(1, rounds + 1):
+                    f = fit2.submit(b)
+                    ra.set_phase(0 if t % 2 else 128)
+                    b.op_n = ra.submit(b, f, copy=False).op_n
+                dt = (time.perf_counter() - t0) * 1e3
+                fit2.finish()
+                if i:
+                    rounds_ms = dt if rounds_ms is None else min(rounds_ms, dt)
+            fit2.close()
         ra.close()
         free, n_moved = int(r.n_free.sum()), int(r.n_moved.sum())
         before, after = sum(r.cost_before), sum(r.cost_after)
-        out["bands"].append(dict(band=band, min_len=3, align_ms=ms, submit_ms=wall * 1e3, free=free, moved=n_moved, ns_per_free_boundary=ms * 1e6 / max(free, 1),
+        out["bands"].append(dict(band=band, min_len=3, phase=phase, align_ms=ms, submit_ms=wall * 1e3, align_ms_reps=all_ms, submit_ms_reps=all_wall, submit_c_ms=min(all_c), submit_c_ms_reps=all_c, rounds=rounds, rounds_ms=rounds_ms, free=free, moved=n_moved, ns_per_free_boundary=ms * 1e6 / max(free, 1),
                                  align_over_pass2=ms / p2, align_bytes_per_s=moved_bytes / (ms * 1e-3), align_share_of_stream_read=moved_bytes / (ms * 1e-3) / stream if stream else None,
                                  cost_after_over_before=after / before if before else None))
     return out
@@ -104,16 +146,23 @@ def main():
     ap.add_argument("--ks", default="5,9")
     ap.add_argument("--bands", default="10,31")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--phase", type=int, default=0)
+    ap.add_argument("--rounds", type=int, default=1)
+    ap.add_argument("--lib", default=None)
+    ap.add_argument("--no-static", action="store_true")
     args = ap.parse_args()
+    if args.lib:
+        from poregen_amd import _abi
+        _abi.LIB_PATH = os.path.abspath(args.lib)
     total = args.reads * args.read_samples
     rng = np.random.default_rng(3)
     ragged = np.clip(rng.lognormal(8.3, 1.2, 4 * args.reads), 400, 1000000).astype(np.int64)
     ragged = ragged[:int(np.searchsorted(np.cumsum(ragged), total)) + 1]
     bands = [int(x) for x in args.bands.split(",")]
-    out = {"stream_read_tbps": stream_read_tbps(), "static": static_picture(), "runs": []}
+    out = {"stream_read_tbps": stream_read_tbps(), "static": None if args.no_static else static_picture(), "lib": args.lib, "runs": []}
     for k in (int(x) for x in args.ks.split(",")):
-        out["runs"].append(bench(f"configs[1]: {args.reads} x {args.read_samples}", np.full(args.reads, args.read_samples, np.int64), k, bands, args.reps, out["stream_read_tbps"]))
-        out["runs"].append(bench("ragged 400..1000000", ragged, k, bands, args.reps, out["stream_read_tbps"]))
+        out["runs"].append(bench(f"configs[1]: {args.reads} x {args.read_samples}", np.full(args.reads, args.read_samples, np.int64), k, bands, args.reps, out["stream_read_tbps"], args.phase, args.rounds))
+        out["runs"].append(bench("ragged 400..1000000", ragged, k, bands, args.reps, out["stream_read_tbps"], args.phase, args.rounds))
     text = json.dumps(out, indent=1)
     print(text)
     if args.out:
