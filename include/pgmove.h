@@ -66,6 +66,10 @@
  * pg_mvops_create / _destroy       (no counterpart)
  * pg_mvops_expand                  the PAF branch of reform() for a batch of      src/reform.cpp:284-358
  *                                  records, and `samtools fastq` of their bases
+ * pg_mvops_project                 those ops carried through the records' CIGARs   README.md, first paragraph ("signal-to-read
+ *                                  onto the reference: the PAF that gmove's PAF    or signal-to-reference"); src/gmove.cpp:792-860
+ *                                  walk reads against a reference FASTA (the       reads such a PAF, src/realign.cpp, which was
+ *                                  reference leaves making it to squigualiser)     to write it, is an empty copy of reform
  * pg_mvops_piece / _set_stream /   (no counterpart)
  * _stream / _last_error
  *
@@ -746,6 +750,53 @@ uint32_t  pg_mvops_piece(const pg_mvops *h);        /* h may be NULL */
 pg_status pg_mvops_set_stream(pg_mvops *h, void *hip_stream);
 void     *pg_mvops_stream(const pg_mvops *h);
 pg_status pg_mvops_expand(pg_mvops *h, const pg_mvops_batch *batch, pg_mvops_result *out);
+
+/* The ops of a batch carried through the records' CIGARs onto the reference (`poregen reform -c --to_ref`; the rule: csrc/pg_refops.h).
+ * Input: the ops to project as DEVICE arrays of device `h` was created on, whatever `location` says -- op_n, op_off[n_reads + 1], query_start
+ * and status as pg_mvops_expand leaves them (every op a match, op j of a read belongs to base j of SEQ, or to base L - 1 - j with
+ * PG_MVOPS_RNA; n_ops = the elements of op_n) -- and the CIGARs: read r's words are cigar[cigar_off[r] .. cigar_off[r + 1]) as a BAM record
+ * stores them (len << 4 | op, op 0..8 = MIDNSHP=X), pos[r] its 0-based position. location: where cigar, cigar_off and pos lie; host arrays
+ * are free for reuse when the call returns. Along a read's words (in reverse order with PG_MVOPS_RNA), q counting the bases used: an S in
+ * front of the first M/=/X/I/D/N adds ops q .. q + len to query_start; an S behind it drops them; M, = and X copy them; an I writes one
+ * op I of their sum (uint32); D and N write one op D of len; H, P and every word of length 0 do nothing. ref_len = the M/=/X/D/N lengths,
+ * target_start / target_end = pos, pos + ref_len (PG_MVOPS_RNA: the other way round), n_match = the match ops, query_end = the new
+ * query_start + every value written as a match or an I. Statuses: a read the expansion refused keeps its code; no word:
+ * PG_MVOPS_ST_NO_CIGAR; the M/I/S/=/X lengths do not come to the read's ops: PG_MVOPS_ST_CIGAR_LENGTH; an op code above 8:
+ * PG_MVOPS_ST_CIGAR_OP -- the first of these decides. A refused read has no ops, ref_len, n_match and the target columns 0 and keeps
+ * its query_start (= query_end). cigar_off that decreases or runs past n_cigar (op_off likewise) is PG_ERR_INVALID_ARG, decided before
+ * any kernel reads a word. The result lies in device memory of the handle, laid out as the arrays of the same names of a pg_batch --
+ * seq / seq_off of that batch are the caller's: the reference slices [min, max) of the target columns -- which is submitted WITHOUT
+ * PG_BATCH_ALL_MATCHES; complete when the call returns, valid until the next pg_mvops_project or pg_mvops_destroy on the handle. It
+ * shares nothing with the result of pg_mvops_expand, which it may read in place and leaves as it is. Reads are cut into pieces of
+ * pg_mvops_piece bases, one wave of the device each. No CPU fallback: PG_ERR_NO_DEVICE without a GPU (at pg_mvops_create). */
+enum { PG_MVOPS_ST_NO_CIGAR = 5, PG_MVOPS_ST_CIGAR_LENGTH = 6, PG_MVOPS_ST_CIGAR_OP = 7 };
+typedef struct {
+    uint64_t n_reads;
+    int32_t  location;           /* of cigar, cigar_off and pos: PG_LOC_HOST or PG_LOC_DEVICE */
+    uint32_t flags;              /* PG_MVOPS_RNA */
+    const uint32_t *op_n;        /* device */
+    uint64_t n_ops;              /* elements of op_n; op_off[n_reads] may not exceed it */
+    const uint64_t *op_off;      /* device [n_reads + 1] */
+    const int32_t  *query_start; /* device [n_reads] */
+    const uint32_t *status;      /* device [n_reads], PG_MVOPS_ST_* */
+    const uint32_t *cigar;
+    uint64_t n_cigar;            /* words of cigar; cigar_off[n_reads] may not exceed it */
+    const uint64_t *cigar_off;   /* [n_reads + 1] */
+    const int32_t  *pos;         /* [n_reads], 0-based */
+} pg_mvops_cigars;
+typedef struct {
+    uint64_t n_reads, n_ops;         /* n_ops = op_off[n_reads] */
+    uint64_t n_refused;
+    int64_t  first_refused;          /* the first read with a status other than 0, or -1 */
+    const uint32_t *op_n;            /* device, dense */
+    const uint8_t  *op_t;            /* device: 0 match, 1 I, 2 D */
+    const uint64_t *op_off;          /* device [n_reads + 1] */
+    const int32_t  *query_start, *target_start, *target_end, *query_end; /* device [n_reads] */
+    const uint32_t *ref_len, *n_match, *status;                          /* device [n_reads] */
+    const uint32_t *status_host, *ref_len_host, *n_match_host;           /* the same in host memory of the handle */
+    const int32_t  *query_end_host;
+} pg_mvops_projection;
+pg_status pg_mvops_project(pg_mvops *h, const pg_mvops_cigars *cigars, pg_mvops_projection *out);
 
 /* ---- model: the k-mer model from the TEXT of dump files, parsed and reduced on the device ---------------------------------------------
  * What scripts/poregen.sh:54-85 (tr ';,' '\n' | tail -n +2 | datamash median 1 / sstdev 1) and :33-52 (awk comma counts | datamash

@@ -34,6 +34,7 @@ PG_EVENTS_OK, PG_EVENTS_HOST_FILE, PG_EVENTS_ONE_SAMPLE, PG_EVENTS_TOO_LONG, PG_
 PG_EVENTS_COL_MEAN_MEDIAN, PG_EVENTS_COL_MEAN_SSTDEV, PG_EVENTS_COL_SD_MEDIAN, PG_EVENTS_COL_SD_SSTDEV = 0, 1, 2, 3
 PG_MVOPS_RNA, PG_MVOPS_N_TO_T = 1, 2
 PG_MVOPS_ST_ACCEPTED, PG_MVOPS_ST_NO_MOVE_IN_TABLE, PG_MVOPS_ST_NEGATIVE_TAIL, PG_MVOPS_ST_BASES_LEFT_OVER, PG_MVOPS_ST_BAD_STRIDE = 0, 1, 2, 3, 4
+PG_MVOPS_ST_NO_CIGAR, PG_MVOPS_ST_CIGAR_LENGTH, PG_MVOPS_ST_CIGAR_OP = 5, 6, 7
 PG_MODEL_TEXT_MEDIAN, PG_MODEL_TEXT_SSTDEV, PG_MODEL_TEXT_DWELL = 0, 1, 2
 PG_FIT_ST_OK, PG_FIT_ST_OUT_OF_SIGNAL, PG_FIT_ST_TOO_LONG, PG_FIT_ST_FEW_EVENTS, PG_FIT_ST_FLAT, PG_FIT_ST_NEGATIVE_SCALE, PG_FIT_ST_SKIPPED = 0, 1, 2, 3, 4, 5, 16
 PG_SIM_ST_OK, PG_SIM_ST_TOO_SHORT, PG_SIM_ST_BAD_BASE, PG_SIM_ST_NO_LEVEL = 0, 1, 2, 3
@@ -58,7 +59,7 @@ EXPORTS = [
     "pg_dmodel_finish_events", "pg_dmodel_format_events", "pg_dmodel_events_refusal", "pg_dmodel_events_values", "pg_dmodel_events_ms", "pg_model_events", "pg_events_status_text",
     "pg_pool_create", "pg_pool_destroy", "pg_pool_last_error", "pg_pool_submit", "pg_pool_sync", "pg_pool_finish", "pg_pool_format", "pg_pool_refusal",
     "pg_transform_model", "pg_transform_free",
-    "pg_mvops_create", "pg_mvops_destroy", "pg_mvops_last_error", "pg_mvops_piece", "pg_mvops_set_stream", "pg_mvops_stream", "pg_mvops_expand",
+    "pg_mvops_create", "pg_mvops_destroy", "pg_mvops_last_error", "pg_mvops_piece", "pg_mvops_set_stream", "pg_mvops_stream", "pg_mvops_expand", "pg_mvops_project",
     "pg_fit_create", "pg_fit_destroy", "pg_fit_last_error", "pg_fit_set_model", "pg_fit_submit", "pg_fit_finish", "pg_fit_set_stream", "pg_fit_pass_ms",
     "pg_fit_parse_model", "pg_fit_residuals",
     "pg_realign_create", "pg_realign_destroy", "pg_realign_last_error", "pg_realign_set_model", "pg_realign_set_stream", "pg_realign_submit", "pg_realign_kernel_ms",
@@ -190,6 +191,18 @@ class PgMvopsResult(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_ops", C.c_uint64), ("n_seq", C.c_uint64), ("n_refused", C.c_uint64), ("first_refused", C.c_int64),
                 ("op_n", C.c_void_p), ("op_t", C.c_void_p), ("op_off", C.c_void_p), ("query_start", C.c_void_p), ("target_start", C.c_void_p),
                 ("target_end", C.c_void_p), ("seq", C.c_void_p), ("seq_off", C.c_void_p), ("status", C.c_void_p), ("status_host", C.c_void_p)]
+
+
+class PgMvopsCigars(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("location", C.c_int32), ("flags", C.c_uint32), ("op_n", C.c_void_p), ("n_ops", C.c_uint64), ("op_off", C.c_void_p),
+                ("query_start", C.c_void_p), ("status", C.c_void_p), ("cigar", C.c_void_p), ("n_cigar", C.c_uint64), ("cigar_off", C.c_void_p), ("pos", C.c_void_p)]
+
+
+class PgMvopsProjection(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("n_ops", C.c_uint64), ("n_refused", C.c_uint64), ("first_refused", C.c_int64),
+                ("op_n", C.c_void_p), ("op_t", C.c_void_p), ("op_off", C.c_void_p), ("query_start", C.c_void_p), ("target_start", C.c_void_p),
+                ("target_end", C.c_void_p), ("query_end", C.c_void_p), ("ref_len", C.c_void_p), ("n_match", C.c_void_p), ("status", C.c_void_p),
+                ("status_host", C.c_void_p), ("ref_len_host", C.c_void_p), ("n_match_host", C.c_void_p), ("query_end_host", C.c_void_p)]
 
 
 class PgFitParams(C.Structure):
@@ -389,6 +402,7 @@ def load():
     lib.pg_mvops_set_stream.argtypes = [vp, vp]; lib.pg_mvops_set_stream.restype = i32
     lib.pg_mvops_stream.argtypes = [vp]; lib.pg_mvops_stream.restype = vp
     lib.pg_mvops_expand.argtypes = [vp, C.POINTER(PgMvopsBatch), C.POINTER(PgMvopsResult)]; lib.pg_mvops_expand.restype = i32
+    lib.pg_mvops_project.argtypes = [vp, C.POINTER(PgMvopsCigars), C.POINTER(PgMvopsProjection)]; lib.pg_mvops_project.restype = i32
     if hasattr(lib, "pg_fit_create"):  # (as above: a library built from an older tree has no fit handle)
         lib.pg_fit_create.argtypes = [C.POINTER(PgFitParams), i32, C.POINTER(vp)]; lib.pg_fit_create.restype = i32
         lib.pg_fit_destroy.argtypes = [vp]; lib.pg_fit_destroy.restype = None

@@ -49,7 +49,7 @@ struct option long_options[] = {
     {"reform", no_argument, 0, 0}, {"n_to_t", no_argument, 0, 0}, {"event_model", required_argument, 0, 0},
     {"realign", required_argument, 0, 0}, {"realign_rounds", required_argument, 0, 0}, {"band", required_argument, 0, 0},                 // 33 .. 35
     {"min_len", required_argument, 0, 0}, {"min_events", required_argument, 0, 0}, {"realign_m", required_argument, 0, 0},                // 36 .. 38
-    {"realign_table", required_argument, 0, 0},                                                                                          // 39
+    {"realign_table", required_argument, 0, 0}, {"ref", required_argument, 0, 0},                                                        // 39, 40
     {0, 0, 0, 0}};
 
 void print_help(FILE *fp, const Opt &o) { // src/gmove.cpp:80-104
@@ -93,6 +93,11 @@ void print_help(FILE *fp, const Opt &o) { // src/gmove.cpp:80-104
     fprintf(fp, "   --reform                   .bam / .sam only: read the move tables as `poregen reform -c -k 1 --stride 0` would (with --rna: reform --rna)\n");
     fprintf(fp, "                              and collect by the rules of a .paf -- the tables are expanded on the GPU, no PAF and no --fastq needed\n");
     fprintf(fp, "   --n_to_t                   with --reform: an N of a read counts as T (sed '2~4s/N/T/g' on the FASTQ)\n");
+    fprintf(fp, "   --ref REF.fa               with --reform, a MAPPED .bam / .sam (dorado --reference, dorado aligner): file every event under the k-mer the\n");
+    fprintf(fp, "                              REFERENCE spells -- the ops are carried through each record's CIGAR on the GPU (I and D ops, --kmer_pick_margin\n");
+    fprintf(fp, "                              applies) and the sequence is the record's slice of REF.fa, as `poregen reform -c -k 1 --stride 0 --to_ref` followed\n");
+    fprintf(fp, "                              by gmove on its PAF with --fastq REF.fa. Unmapped and reverse-strand records (flag 0x4, no RNAME, flag 0x10) are\n");
+    fprintf(fp, "                              skipped and counted; not with --realign or --n_to_t\n");
     fprintf(fp, "   --realign MODEL            with --reform, one device: refine every batch's event boundaries against the k-mer model on the GPU before\n");
     fprintf(fp, "                              collecting, as `poregen realign MODEL` followed by gmove on its PAF; --min_dur, --max_dur, --rna and --n_to_t\n");
     fprintf(fp, "                              are the fit's and the aligner's too; the model's k is its own, independent of -k\n");
@@ -167,6 +172,7 @@ int gmove_main(int argc, char **argv) {
     std::vector<int32_t> devices; uint32_t exchange = PG_JOB_EXCHANGE_AUTO;
     const char *raw_model_path = nullptr, *dwell_model_path = nullptr, *stdv_limit = "3.1", *event_model_path = nullptr;
     bool reform_mode = false, n_to_t = false;
+    const char *ref_path = nullptr; // --ref: the FASTA the records are mapped to
     const char *realign_model = nullptr, *realign_table = nullptr, *realign_extra = nullptr; // realign_extra: the first option given that needs --realign
     long long realign_rounds = 1, realign_band = 10, realign_min_len = 3, realign_min_events = 20, realign_m = 0;
     int verbose = 3;
@@ -215,6 +221,7 @@ int gmove_main(int argc, char **argv) {
         else if (c == 0 && longindex == 31) n_to_t = true;
         else if (c == 0 && longindex == 32) event_model_path = optarg;
         else if (c == 0 && longindex == 33) realign_model = optarg;
+        else if (c == 0 && longindex == 40) ref_path = optarg;
         else if (c == 0 && longindex >= 34 && longindex <= 39) {
             bool ok = true;
             if (!realign_extra) realign_extra = long_options[longindex].name;
@@ -237,6 +244,16 @@ int gmove_main(int argc, char **argv) {
     const char *slow5file = argv[optind], *move_table = argv[optind + 1], *output_dir = argv[optind + 2];
     if (reform_mode && !is_sam_or_bam(move_table)) { fprintf(stderr, "--reform applies to a .bam or .sam event_alignment_file only\n"); print_help(fp_help, opt); return EXIT_FAILURE; }
     if (n_to_t && !reform_mode) { fprintf(stderr, "--n_to_t applies with --reform only\n"); print_help(fp_help, opt); return EXIT_FAILURE; }
+    // --ref: every usage error ends here too, an unreadable FASTA among them
+    pgh::FastxIndex ref_fai;
+    if (ref_path) {
+        const char *why = !reform_mode ? "--ref applies with --reform only" : realign_model ? "--ref cannot be combined with --realign: fit and realign take batches of matches only" :
+                          n_to_t ? "--ref cannot be combined with --n_to_t: the sequence is the reference's, there is nothing to rewrite" : nullptr;
+        std::string ferr;
+        if (why) fprintf(stderr, "%s\n", why);
+        else if (!ref_fai.load(ref_path, ferr)) { fprintf(stderr, "Error in loading the reference %s%s%s\n", ref_path, ferr.empty() ? "" : ": ", ferr.c_str()); why = ""; }
+        if (why) { print_help(fp_help, opt); return EXIT_FAILURE; }
+    }
     // --realign: every usage error ends here, before a device is asked for and before the output directory exists
     std::vector<uint32_t> realign_levels; uint32_t realign_k = 0; int32_t realign_uses_u = 0;
     {
@@ -653,7 +670,12 @@ int gmove_main(int argc, char **argv) {
         unsigned nt = std::thread::hardware_concurrency(); if (nt > 16) nt = 16; if (nt < 1) nt = 1;
         // With --realign every slot also has a fit and a realign handle on its expander's stream: the refined ops are the realign handle's
         // array, which like the expander's lives until the slot's next batch -- behind the submit of the batch in between.
-        struct Slot { pg_mvops *ex = nullptr; pg_fit *fit = nullptr; pg_realign *ra = nullptr; PgDev<int16_t> sig; PgDev<uint64_t> sig_off; PgDev<double> cal; };
+        // With --ref the ops are carried through the records' CIGARs onto the reference on the expander (pg_mvops_project), the host fetches
+        // every read's slice of the FASTA, and the batch -- I and D ops among its matches -- goes to the collector's generic walk.
+        struct Slot { pg_mvops *ex = nullptr; pg_fit *fit = nullptr; pg_realign *ra = nullptr; PgDev<int16_t> sig; PgDev<uint64_t> sig_off; PgDev<double> cal;
+                      PgDev<uint8_t> seq; PgDev<uint64_t> seq_off; };
+        uint64_t to_ref_skipped = 0;
+        std::string slice;
         Slot slots[2];
         pgh::MoveRecs rb;
         std::vector<pgh::Slow5File::RawView> views; std::vector<pgh::Slow5Rec> recs; std::vector<std::string> fetch_err;
@@ -665,7 +687,7 @@ int gmove_main(int argc, char **argv) {
                 if (sl.fit) pg_fit_destroy(sl.fit);
                 if (sl.ra) pg_realign_destroy(sl.ra);
                 if (sl.ex) pg_mvops_destroy(sl.ex);
-                sl.fit = nullptr; sl.ra = nullptr; sl.ex = nullptr; sl.sig.release(); sl.sig_off.release(); sl.cal.release();
+                sl.fit = nullptr; sl.ra = nullptr; sl.ex = nullptr; sl.sig.release(); sl.sig_off.release(); sl.cal.release(); sl.seq.release(); sl.seq_off.release();
             }
         };
         RealignRounds rounds;
@@ -692,7 +714,7 @@ int gmove_main(int argc, char **argv) {
             rb.clear();
             std::string bad; // why the record behind the batch's last read cannot be taken (empty: nothing wrong)
             while (rb.size() < this_batch_reads && rb.mv.size() < ((size_t)1 << 30)) {
-                const int nr = pgh::next_move_record(sam, raw, "gmove", bad);
+                const int nr = pgh::next_move_record(sam, raw, "gmove", bad, ref_path ? &to_ref_skipped : nullptr);
                 if (nr == 0) eof = true;
                 if (nr <= 0) break;
                 rb.push(raw);
@@ -752,25 +774,64 @@ int gmove_main(int argc, char **argv) {
                         !hip_ok(hipMemcpyAsync(sl.cal.p, cal.data(), 3 * n * 8, hipMemcpyHostToDevice, xs), "hipMemcpyAsync")) break;
                 }
                 if (pg_mvops_expand(sl.ex, &mb, &mr) != PG_OK) { fprintf(stderr, "[gmove] %s\n", pg_mvops_last_error(sl.ex)); status = EXIT_FAILURE; break; }
-                if (mr.first_refused >= 0) { // reform returns -1 on this record: the reads in front of it are the batch
+                // what the collector takes: the expansion's arrays, or with --ref the projection's and the slices of the reference
+                const uint32_t *d_opn = mr.op_n; const uint8_t *d_opt = mr.op_t, *d_seq = mr.seq; const uint64_t *d_opoff = mr.op_off, *d_seqoff = mr.seq_off;
+                const int32_t *d_qs = mr.query_start, *d_ts = mr.target_start, *d_te = mr.target_end;
+                pg_mvops_projection pr; memset(&pr, 0, sizeof pr);
+                if (ref_path) {
+                    pg_mvops_cigars cg; memset(&cg, 0, sizeof cg);
+                    cg.n_reads = n; cg.location = PG_LOC_HOST; cg.flags = opt.flag_rna ? PG_MVOPS_RNA : 0;
+                    cg.op_n = mr.op_n; cg.n_ops = mr.n_ops; cg.op_off = mr.op_off; cg.query_start = mr.query_start; cg.status = mr.status;
+                    cg.cigar = rb.cigar.data(); cg.n_cigar = rb.cigar_off[n]; cg.cigar_off = rb.cigar_off.data(); cg.pos = rb.pos.data();
+                    if (pg_mvops_project(sl.ex, &cg, &pr) != PG_OK) { fprintf(stderr, "[gmove] %s\n", pg_mvops_last_error(sl.ex)); status = EXIT_FAILURE; break; }
+                    d_opn = pr.op_n; d_opt = pr.op_t; d_opoff = pr.op_off; d_qs = pr.query_start; d_ts = pr.target_start; d_te = pr.target_end;
+                    if (pr.first_refused >= 0) { // reform --to_ref ends on this record: the reads in front of it are the batch
+                        n = (size_t)pr.first_refused; eof = false;
+                        const uint32_t code = pr.status_host[n];
+                        bad = pgh::reform_error((std::string(pgh::to_ref_refusal(code)) + " (status " + std::to_string(code) + ")").c_str(), rb.names[n]);
+                    }
+                } else if (mr.first_refused >= 0) { // reform returns -1 on this record: the reads in front of it are the batch
                     n = (size_t)mr.first_refused; eof = false;
                     bad = pgh::reform_error(pgh::reform_refusal(mr.status_host[n]), rb.names[n]);
                 }
                 uint64_t n_ops = 0, n_seq = 0; // an accepted read has as many ops as bases
                 for (size_t i = 0; i < n; i++) { n_ops += rb.l_seq[i]; n_seq += rb.l_seq[i]; }
+                if (ref_path && n) {
+                    // faidx_fetch_seq(m_fai, tid, st_k, end_k - 1) with st_k / end_k = min / max of the target columns, as the PAF front-end
+                    // does it; a name the FASTA does not hold gives an empty slice, and the device skips the read
+                    hb.seq.clear(); hb.seq_off.assign(1, 0);
+                    for (size_t i = 0; i < n; i++) {
+                        const int32_t lo = rb.pos[i], hi = (int32_t)((uint32_t)rb.pos[i] + pr.ref_len_host[i]);
+                        const int64_t a = opt.flag_rna ? hi : lo, b2 = opt.flag_rna ? lo : hi;
+                        const int64_t st_k = (uint64_t)a > (uint64_t)b2 ? b2 : a, end_k = (uint64_t)a > (uint64_t)b2 ? a : b2;
+                        ref_fai.fetch(rb.rname[i], (int)st_k, (int)(end_k - 1), slice);
+                        hb.seq.insert(hb.seq.end(), slice.begin(), slice.end()); hb.seq_off.push_back(hb.seq.size());
+                    }
+                    n_seq = hb.seq.size();
+                    if (!hip_ok(hipMemcpy(&n_ops, pr.op_off + n, sizeof n_ops, hipMemcpyDeviceToHost), "hipMemcpy")) break;
+                    if (!dev.job) {
+                        if (!hip_ok(sl.seq.ensure(n_seq ? n_seq : 1, n_seq + n_seq / 4 + 256), "hipMalloc") || !hip_ok(sl.seq_off.ensure((n + 1) * 8, (n + 1) * 10), "hipMalloc") ||
+                            (n_seq && !hip_ok(hipMemcpyAsync(sl.seq.p, hb.seq.data(), n_seq, hipMemcpyHostToDevice, xs), "hipMemcpyAsync")) ||
+                            !hip_ok(hipMemcpyAsync(sl.seq_off.p, hb.seq_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, xs), "hipMemcpyAsync") ||
+                            !hip_ok(hipStreamSynchronize(xs), "hipStreamSynchronize")) break;
+                        d_seq = sl.seq.p; d_seqoff = sl.seq_off.p;
+                    }
+                }
                 total_samples += hb.sig_off[n];
                 for (size_t i = 0; i < n; i++) if (++count_reads % 10000 == 0) fprintf(stderr, "*"); // PROGRESS_BATCH_SIZE
                 if (n && dev.job) {
                     hb.sig.resize(hb.sig_off[n]); hb.sig_off.resize(n + 1); hb.dig.resize(n); hb.off.resize(n); hb.range.resize(n);
                     h_opn.resize(n_ops); hb.op_t.assign(n_ops, 0); hb.op_off.resize(n + 1); hb.seq.resize(n_seq); hb.seq_off.resize(n + 1); hb.qs.resize(n); hb.ts.resize(n); hb.te.resize(n);
-                    if ((n_ops && !hip_ok(hipMemcpy(h_opn.data(), mr.op_n, n_ops * 4, hipMemcpyDeviceToHost), "hipMemcpy")) ||
-                        (n_seq && !hip_ok(hipMemcpy(hb.seq.data(), mr.seq, n_seq, hipMemcpyDeviceToHost), "hipMemcpy")) ||
-                        !hip_ok(hipMemcpy(hb.op_off.data(), mr.op_off, (n + 1) * 8, hipMemcpyDeviceToHost), "hipMemcpy") ||
-                        !hip_ok(hipMemcpy(hb.seq_off.data(), mr.seq_off, (n + 1) * 8, hipMemcpyDeviceToHost), "hipMemcpy") ||
-                        !hip_ok(hipMemcpy(hb.qs.data(), mr.query_start, n * 4, hipMemcpyDeviceToHost), "hipMemcpy") ||
-                        !hip_ok(hipMemcpy(hb.ts.data(), mr.target_start, n * 4, hipMemcpyDeviceToHost), "hipMemcpy") ||
-                        !hip_ok(hipMemcpy(hb.te.data(), mr.target_end, n * 4, hipMemcpyDeviceToHost), "hipMemcpy")) break;
+                    if ((n_ops && !hip_ok(hipMemcpy(h_opn.data(), d_opn, n_ops * 4, hipMemcpyDeviceToHost), "hipMemcpy")) ||
+                        (ref_path && n_ops && !hip_ok(hipMemcpy(hb.op_t.data(), d_opt, n_ops, hipMemcpyDeviceToHost), "hipMemcpy")) ||
+                        (!ref_path && n_seq && !hip_ok(hipMemcpy(hb.seq.data(), d_seq, n_seq, hipMemcpyDeviceToHost), "hipMemcpy")) || // (--ref: the slices are the host's)
+                        !hip_ok(hipMemcpy(hb.op_off.data(), d_opoff, (n + 1) * 8, hipMemcpyDeviceToHost), "hipMemcpy") ||
+                        (!ref_path && !hip_ok(hipMemcpy(hb.seq_off.data(), d_seqoff, (n + 1) * 8, hipMemcpyDeviceToHost), "hipMemcpy")) ||
+                        !hip_ok(hipMemcpy(hb.qs.data(), d_qs, n * 4, hipMemcpyDeviceToHost), "hipMemcpy") ||
+                        !hip_ok(hipMemcpy(hb.ts.data(), d_ts, n * 4, hipMemcpyDeviceToHost), "hipMemcpy") ||
+                        !hip_ok(hipMemcpy(hb.te.data(), d_te, n * 4, hipMemcpyDeviceToHost), "hipMemcpy")) break;
                     hb.op_n.swap(h_opn);
+                    if (ref_path) batch_all_matches = false; // (I and D ops: the generic walk)
                     t_device += secs(tf0, clk::now());
                     if (!flush()) { status = EXIT_FAILURE; break; }
                 } else if (n) {
@@ -778,9 +839,9 @@ int gmove_main(int argc, char **argv) {
                     b.struct_size = sizeof b; b.location = PG_LOC_DEVICE; b.n_reads = (uint32_t)n; b.n_ops = (uint32_t)n_ops;
                     if (n_ops > 0xffffffffull) { fprintf(stderr, "[gmove] a batch of %llu ops: use a smaller --batch_reads\n", (unsigned long long)n_ops); status = EXIT_FAILURE; break; }
                     b.sig = sl.sig.p; b.sig_off = sl.sig_off.p; b.digitisation = sl.cal.p; b.offset = sl.cal.p + mr.n_reads; b.range = sl.cal.p + 2 * mr.n_reads;
-                    b.query_start = mr.query_start; b.target_start = mr.target_start; b.target_end = mr.target_end; b.seq = mr.seq; b.seq_off = mr.seq_off;
-                    b.op_n = mr.op_n; b.op_t = mr.op_t; b.op_off = mr.op_off;
-                    b.flags = PG_BATCH_ALL_MATCHES; // every op is a match and a read has as many ops as bases: what `reform` writes
+                    b.query_start = d_qs; b.target_start = d_ts; b.target_end = d_te; b.seq = d_seq; b.seq_off = d_seqoff;
+                    b.op_n = d_opn; b.op_t = d_opt; b.op_off = d_opoff;
+                    if (!ref_path) b.flags = PG_BATCH_ALL_MATCHES; // every op is a match and a read has as many ops as bases: what `reform` writes
                     if (realign_model) { // the rounds on the device batch; the collector takes the last round's ops
                         if (!realign_handles(sl, ex_device)) { status = EXIT_FAILURE; break; }
                         if (!rounds.run(sl.fit, sl.fit, sl.ra, b, realign_rounds)) { fprintf(stderr, "[gmove] %s\n", rounds.err.c_str()); status = EXIT_FAILURE; break; }
@@ -810,6 +871,7 @@ int gmove_main(int argc, char **argv) {
         // the device has read the last batch's ops before the expanders go
         if (dev.ok() && dev.sync() != PG_OK && status == EXIT_SUCCESS) { fprintf(stderr, "[gmove] %s\n", dev.error()); status = EXIT_FAILURE; }
         release();
+        if (ref_path) pgh::print_to_ref_skipped("gmove", to_ref_skipped);
         if (rt && fclose(rt) != 0 && status == EXIT_SUCCESS) { fprintf(stderr, "Error in writing %s.\n", realign_table); status = EXIT_FAILURE; }
         if (realign_model && verbose >= 4)
             fprintf(stderr, "[gmove] realign: k=%u band=%lld rounds=%lld reads=%llu refined=%llu free=%llu moved=%llu\n", realign_k, realign_band, realign_rounds,

@@ -541,8 +541,25 @@ static char seq_letter(char c) { // gmove.cpp:1128-1134: alphabet "NACNGNNNT" ov
 bool SamBamReader::open(const std::string &path, std::string &err) {
     if (!f_.open(path)) { err = "cannot open " + path; return false; }
     bam_ = f_.size >= 4 && (unsigned char)f_.data[0] == 0x1f && (unsigned char)f_.data[1] == 0x8b;
-    pos_ = 0; buf_.clear(); bpos_ = 0;
-    if (!bam_) return true;
+    pos_ = 0; buf_.clear(); bpos_ = 0; refs_.clear(); sq_.clear();
+    if (!bam_) { // the @SQ lines of the header: SN and LN
+        const char *p = f_.data, *e = f_.data + f_.size;
+        while (p < e && *p == '@') {
+            const char *nl = (const char *)memchr(p, '\n', (size_t)(e - p)), *le = nl ? nl : e;
+            if (le - p >= 4 && memcmp(p, "@SQ\t", 4) == 0) {
+                std::string sn; int64_t ln = 0;
+                for (const char *q = p + 4; q < le;) {
+                    const char *t = (const char *)memchr(q, '\t', (size_t)(le - q)); if (!t) t = le;
+                    if (t - q > 3 && memcmp(q, "SN:", 3) == 0) { sn.assign(q + 3, t); if (!sn.empty() && sn.back() == '\r') sn.pop_back(); }
+                    else if (t - q > 3 && memcmp(q, "LN:", 3) == 0) ln = strtoll(std::string(q + 3, t).c_str(), nullptr, 10);
+                    q = t < le ? t + 1 : le;
+                }
+                if (!sn.empty()) sq_.emplace(sn, ln); // (the first line of a name wins)
+            }
+            p = nl ? nl + 1 : e;
+        }
+        return true;
+    }
     // BAM header: magic, l_text, text, n_ref, references
     if (!fill(12, err)) { if (err.empty()) err = "truncated BAM header"; return false; }
     if (memcmp(buf_.data(), "BAM\1", 4) != 0) { err = "not a BAM file"; return false; }
@@ -555,6 +572,8 @@ bool SamBamReader::open(const std::string &path, std::string &err) {
         if (!fill(bpos_ + 4, err)) { if (err.empty()) err = "truncated BAM header"; return false; }
         int32_t l_name; memcpy(&l_name, buf_.data() + bpos_, 4);
         if (l_name < 0 || !fill(bpos_ + 8 + (size_t)l_name, err)) { if (err.empty()) err = "truncated BAM header"; return false; }
+        int32_t l_ref; memcpy(&l_ref, buf_.data() + bpos_ + 4 + (size_t)l_name, 4);
+        refs_.emplace_back(std::string((const char *)buf_.data() + bpos_ + 4, l_name ? (size_t)l_name - 1 : 0), (int64_t)l_ref);
         bpos_ += 4 + (size_t)l_name + 4;
     }
     return true;
@@ -599,6 +618,7 @@ int SamBamReader::next(MoveRec &out, std::string &err) { return next_impl(out, n
 int SamBamReader::next_raw(RawMoveRec &raw, std::string &err) {
     MoveRec head; // the fields the two forms share
     raw.flag = 0; raw.l_seq = 0; raw.mv = nullptr; raw.packed = nullptr; raw.mv_store.clear(); raw.packed_store.clear();
+    raw.cigar.clear(); raw.pos = -1; raw.rname.clear(); raw.ref_len = 0;
     const int rc = next_impl(head, &raw, err);
     raw.qname.swap(head.qname);
     raw.stride = head.stride; raw.mv_len = head.mv_len; raw.ns = head.ns; raw.ts = head.ts;
@@ -623,6 +643,23 @@ int SamBamReader::next_impl(MoveRec &out, RawMoveRec *raw, std::string &err) {
                 const char *t = (const char *)memchr(p, '\t', (size_t)(le - p)); if (!t) t = le;
                 if (col == 0) out.qname.assign(p, t);
                 else if (col == 1 && raw) raw->flag = (uint32_t)strtoul(std::string(p, t).c_str(), nullptr, 0);
+                else if (col == 2 && raw) {
+                    if (!(t - p == 1 && *p == '*')) raw->rname.assign(p, t);
+                    const auto it = sq_.find(raw->rname);
+                    if (it != sq_.end()) raw->ref_len = it->second;
+                }
+                else if (col == 3 && raw) raw->pos = (int32_t)(strtoll(std::string(p, t).c_str(), nullptr, 10) - 1);
+                else if (col == 5 && raw && !(t - p == 1 && *p == '*')) { // the words a BAM record would hold
+                    static const char ops[] = "MIDNSHP=X";
+                    for (const char *q = p; q < t;) {
+                        uint64_t len = 0; const char *d = q;
+                        while (q < t && *q >= '0' && *q <= '9' && len < (1ull << 28)) len = len * 10 + (uint64_t)(*q++ - '0');
+                        if (q == d || q >= t || len >= (1ull << 28)) { err = "malformed CIGAR in SAM record"; return -1; }
+                        const char *at = (const char *)memchr(ops, *q, 9);
+                        raw->cigar.push_back((uint32_t)len << 4 | (at ? (uint32_t)(at - ops) : 15u));
+                        q++;
+                    }
+                }
                 else if (col == 9 && raw) { // packed by htslib's rule, as a BAM record would hold it
                     size_t n = (size_t)(t - p); if (n == 1 && *p == '*') n = 0;
                     if (n > 0x7fffffffu) { err = "SAM record with more than 2^31 - 1 bases"; return -1; }
@@ -675,6 +712,13 @@ int SamBamReader::next_impl(MoveRec &out, RawMoveRec *raw, std::string &err) {
     if ((size_t)l_read_name > left()) { err = "corrupt BAM record"; return -1; }
     out.qname.assign((const char *)p, l_read_name ? l_read_name - 1 : 0); p += l_read_name;
     if (4u * (size_t)n_cigar > left()) { err = "corrupt BAM record"; return -1; }
+    if (raw) {
+        int32_t ref_id, pos; memcpy(&ref_id, r, 4); memcpy(&pos, r + 4, 4);
+        raw->pos = pos;
+        if (ref_id >= 0 && (size_t)ref_id < refs_.size()) { raw->rname = refs_[(size_t)ref_id].first; raw->ref_len = refs_[(size_t)ref_id].second; }
+        raw->cigar.resize(n_cigar);
+        if (n_cigar) memcpy(raw->cigar.data(), p, 4u * (size_t)n_cigar);
+    }
     p += 4u * (size_t)n_cigar;
     if (l_seq < 0 || ((size_t)l_seq + 1) / 2 + (size_t)l_seq > left()) { err = "corrupt BAM record"; return -1; }
     static const char code[] = "=ACMGRSVTWYHKDBN";

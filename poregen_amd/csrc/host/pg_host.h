@@ -157,6 +157,13 @@ struct RawMoveRec {
     uint64_t ns = 0, ts = 0;
     bool has_ns = false, has_ts = false, has_mv = false, mv_is_Bc = false;
     std::vector<int8_t> mv_store; std::vector<uint8_t> packed_store; // SAM
+    // where the record is mapped: the CIGAR as a BAM record stores it (words len << 4 | op, op 0..8 = MIDNSHP=X; a SAM line's text is
+    // parsed into the same words, a letter that is none of the nine into op 15), the 0-based position (-1: none), the reference's name
+    // (empty: none, SAM's `*`) and its length from @SQ / the BAM header's reference list (0: not listed)
+    std::vector<uint32_t> cigar;
+    int32_t pos = -1;
+    std::string rname;
+    int64_t ref_len = 0;
 };
 class SamBamReader {
 public:
@@ -170,6 +177,8 @@ private:
     size_t pos_ = 0;                 // SAM: offset into the file; BAM: offset of the next BGZF block
     std::vector<unsigned char> buf_; // BAM: inflated bytes not yet consumed
     size_t bpos_ = 0;
+    std::vector<std::pair<std::string, int64_t>> refs_; // BAM: the header's reference list, by refID
+    std::unordered_map<std::string, int64_t> sq_;        // SAM: LN of every @SQ line, by SN
     bool fill(size_t need, std::string &err);
 };
 

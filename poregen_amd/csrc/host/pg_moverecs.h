@@ -22,14 +22,30 @@ inline const char *reform_refusal(uint32_t code) {
                                            "Error in the implementation. Please report the command with minimal reproducible data.", "the stride of the move table (mv[0]) is less than 1."};
     return kRefusal[code < 5 ? code : 3];
 }
+// ... and of a read whose CIGAR the projection onto the reference refuses (codes 5 to 7); the expansion's codes keep their texts
+inline const char *to_ref_refusal(uint32_t code) {
+    return code == 5 ? "the record has no CIGAR." : code == 6 ? "the M/I/S/=/X lengths of the CIGAR do not come to the bases of the read." :
+           code == 7 ? "the CIGAR holds an operation that is none of MIDNSHP=X." : reform_refusal(code);
+}
+// the line both commands print at the end of a run that projected onto a reference
+inline void print_to_ref_skipped(const char *tool, uint64_t n) {
+    fprintf(stderr, "[%s] %llu records skipped: unmapped (flag 0x4 or no reference name) or on the reverse strand (flag 0x10)\n", tool, (unsigned long long)n);
+}
 
 // the records of a batch, back to back, in the layout pg_mvops_batch takes
 struct MoveRecs {
     std::vector<std::string> names; std::vector<int8_t> mv; std::vector<uint64_t> mv_off{0}, ns, ts, boff; std::vector<int32_t> stride;
     std::vector<uint32_t> l_seq, flag; std::vector<uint8_t> seqb;
+    // where the records are mapped (pg_mvops_cigars): the CIGAR words back to back, the 0-based positions, the references' names and lengths
+    std::vector<uint32_t> cigar; std::vector<uint64_t> cigar_off{0}; std::vector<int32_t> pos; std::vector<std::string> rname; std::vector<int64_t> ref_len;
     size_t size() const { return names.size(); }
-    void clear() { names.clear(); mv.clear(); mv_off.assign(1, 0); ns.clear(); ts.clear(); boff.clear(); stride.clear(); l_seq.clear(); flag.clear(); seqb.clear(); }
+    void clear() {
+        names.clear(); mv.clear(); mv_off.assign(1, 0); ns.clear(); ts.clear(); boff.clear(); stride.clear(); l_seq.clear(); flag.clear(); seqb.clear();
+        cigar.clear(); cigar_off.assign(1, 0); pos.clear(); rname.clear(); ref_len.clear();
+    }
     void push(const RawMoveRec &raw) {
+        cigar.insert(cigar.end(), raw.cigar.begin(), raw.cigar.end()); cigar_off.push_back(cigar.size());
+        pos.push_back(raw.pos); rname.push_back(raw.rname); ref_len.push_back(raw.ref_len);
         names.push_back(raw.qname);
         mv.insert(mv.end(), raw.mv, raw.mv + (raw.mv_len - 1)); mv_off.push_back(mv.size());
         stride.push_back(raw.stride); ns.push_back(raw.ns); ts.push_back(raw.ts); l_seq.push_back(raw.l_seq); flag.push_back(raw.flag);
@@ -45,12 +61,15 @@ struct MoveRecs {
 
 // The next record a batch takes: 1 with the record in `raw`, 0 at the end of the file, -1 with `bad` saying why the record (or the file
 // behind it) cannot be taken -- the first such record ends the run behind the reads in front of it, with gmove --reform's message.
-inline int next_move_record(SamBamReader &sam, RawMoveRec &raw, const char *tool, std::string &bad) {
+// to_ref_skipped (gmove --reform --ref, reform --to_ref): records that are not mapped to the forward strand of a reference -- flag 0x4, no
+// RNAME, flag 0x10 -- are stepped over and counted there.
+inline int next_move_record(SamBamReader &sam, RawMoveRec &raw, const char *tool, std::string &bad, uint64_t *to_ref_skipped = nullptr) {
     for (std::string err;;) {
         const int nr = sam.next_raw(raw, err);
         if (nr == 0) return 0;
         if (nr < 0) { bad = "[" + std::string(tool) + "] " + err; return -1; }
         if (raw.flag & 0x900u) continue; // secondary / supplementary: `samtools fastq` does not print them
+        if (to_ref_skipped && ((raw.flag & 0x14u) || raw.rname.empty())) { ++*to_ref_skipped; continue; }
         const char *why = !raw.has_ns ? "tag 'ns' is not found. Please check your SAM/BAM file:" : !raw.has_ts ? "tag 'ts' is not found. Please check your SAM/BAM file:" :
                           !raw.has_mv ? "NULL returned for tag mv:" : !raw.mv_is_Bc ? "tag 'mv' specification is incorrect." : raw.mv_len == 0 ? "mv array length is 0:" : nullptr;
         if (!why) return 1;

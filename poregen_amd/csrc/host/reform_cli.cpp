@@ -5,7 +5,8 @@
 // array per read, far below anything worth a kernel launch. The output is derived from the list of move
 // positions of each read instead of the reference's three interleaved scans; the bytes written are the same
 // (pinned by the reference's own expected files, tests/golden/reform/).
-#include "pg_host.h"
+#include "../pg_refops.h"
+#include "pg_moverecs.h"
 
 #include <cinttypes>
 #include <cstdio>
@@ -40,6 +41,7 @@ const struct option kLongOptions[] = {
     {"debug-break", required_argument, nullptr, 0},
     {"rna", no_argument, nullptr, 0},
     {"stride", required_argument, nullptr, 0},
+    {"to_ref", no_argument, nullptr, 0},
     {nullptr, 0, nullptr, 0}};
 
 void usage(FILE *fp, uint32_t k, uint32_t m) {
@@ -53,6 +55,40 @@ void usage(FILE *fp, uint32_t k, uint32_t m) {
     fprintf(fp, "   --version                  print version\n");
     fprintf(fp, "   --rna                      dataset is rna: PAF target columns n_kmers, 0 and a k-mer index that counts down\n");
     fprintf(fp, "   --stride INT               expected stride of the move table, 0 = any [%u]\n", kDefaultStride);
+    fprintf(fp, "   --to_ref                   mapped SAM/BAM (dorado --reference, dorado aligner), with -c -k 1 -m 0: carry the ops through every record's\n");
+    fprintf(fp, "                              CIGAR onto the reference -- the PAF of the signal-to-reference alignment that `gmove FILE.paf --fastq REF.fa`\n");
+    fprintf(fp, "                              reads: qname, ns, query_start, query_end, +, RNAME, its length, target_start, target_end, n_match, ref_len,\n");
+    fprintf(fp, "                              255, ss:Z: with N, / NI / ND (with --rna: the CIGAR in reverse order, target_start > target_end). Unmapped\n");
+    fprintf(fp, "                              and reverse-strand records (flag 0x4, no RNAME, flag 0x10) are skipped and counted, secondary and\n");
+    fprintf(fp, "                              supplementary ones (0x900) dropped; a read whose table or CIGAR is refused ends the run\n");
+}
+
+// --to_ref: every record through the two rules the kernels compile (pg_mvops.h, pg_refops.h), on the host. 0, or 1 behind the message.
+int to_ref(FILE *out, pgh::SamBamReader &rd, const Extra &x) {
+    pgh::RawMoveRec raw;
+    std::string bad;
+    std::vector<uint32_t> ops, op_n; std::vector<uint8_t> seq, op_t;
+    uint64_t skipped = 0;
+    int got;
+    while ((got = pgh::next_move_record(rd, raw, "reform", bad, &skipped)) > 0) {
+        if (x.stride && raw.stride != (int)x.stride) { fprintf(stderr, "[reform::ERROR]\033[1;31m expected stride of %u is missing. Read_id: %s\033[0m\n", x.stride, raw.qname.c_str()); return 1; }
+        const uint32_t L = raw.l_seq, nw = (uint32_t)raw.cigar.size();
+        ops.assign((size_t)L + 1, 0); seq.resize((size_t)L + 1); op_n.resize((size_t)L + nw + 1); op_t.resize((size_t)L + nw + 1);
+        uint32_t n_ops = 0; int32_t qs = 0;
+        const uint32_t st = pg_mv_expand_host((const uint8_t *)raw.mv, raw.mv_len - 1, raw.stride, raw.ns, raw.ts, L, raw.packed, false, false, ops.data(), &n_ops, &qs, seq.data());
+        const PgRfHost h = pg_refops_host(ops.data(), n_ops, qs, st, raw.cigar.data(), nw, raw.pos, x.rna, op_n.data(), op_t.data());
+        if (h.status) {
+            fprintf(stderr, "%s\n", pgh::reform_error((std::string(pgh::to_ref_refusal(h.status)) + " (status " + std::to_string(h.status) + ")").c_str(), raw.qname).c_str());
+            return 1;
+        }
+        fprintf(out, "%s\t%" PRIu64 "\t%d\t%d\t+\t%s\t%" PRId64 "\t%d\t%d\t%" PRIu32 "\t%" PRIu32 "\t255\tss:Z:", raw.qname.c_str(), raw.ns, h.query_start, h.query_end,
+                raw.rname.c_str(), raw.ref_len, h.target_start, h.target_end, h.n_match, h.ref_len);
+        for (uint32_t i = 0; i < h.n_ops; i++) fprintf(out, "%" PRIu32 "%c", op_n[i], ",ID"[op_t[i]]);
+        fputc('\n', out);
+    }
+    if (got < 0) { fprintf(stderr, "%s\n", bad.c_str()); return 1; }
+    pgh::print_to_ref_skipped("reform", skipped);
+    return 0;
 }
 
 int fail(const char *msg) {
@@ -139,7 +175,7 @@ int reform_record(FILE *out, const pgh::MoveRec &r, uint32_t k, uint32_t m, bool
 
 int reform_main(int argc, char **argv) {
     uint32_t k = 9, m = 0; // init_opt, src/poregen.cpp:209-237
-    bool paf = false, help_to_stdout = false;
+    bool paf = false, help_to_stdout = false, to_ref_mode = false;
     Extra extra;
     const char *out_path = nullptr;
     int c, longindex = 0;
@@ -154,6 +190,7 @@ int reform_main(int argc, char **argv) {
         else if (c == 'V') { fprintf(stdout, "subtool0 0.1.0\n"); exit(EXIT_SUCCESS); }
         else if (c == 'h') help_to_stdout = true;
         else if (c == 0 && !strcmp(kLongOptions[longindex].name, "rna")) extra.rna = true;
+        else if (c == 0 && !strcmp(kLongOptions[longindex].name, "to_ref")) to_ref_mode = true;
         else if (c == 0 && !strcmp(kLongOptions[longindex].name, "stride")) {
             if (atoi(optarg) < 0) { fail("Stride should not be negative."); exit(EXIT_FAILURE); }
             extra.stride = (uint32_t)atoi(optarg);
@@ -161,6 +198,7 @@ int reform_main(int argc, char **argv) {
     }
     if (k < 1) return fail("kmer length must be a positive integer");
     if (k <= m) return fail("signal move offset value must less than the kmer length");
+    if (to_ref_mode && !help_to_stdout && (!paf || k != 1 || m != 0)) { fail("--to_ref requires -c -k 1 -m 0"); usage(stderr, k, m); return EXIT_FAILURE; }
     if (argc - optind != 1 || help_to_stdout) {
         fail("not enough arguments");
         usage(help_to_stdout ? stdout : stderr, k, m);
@@ -178,6 +216,11 @@ int reform_main(int argc, char **argv) {
     pgh::SamBamReader rd;
     std::string err;
     if (!rd.open(in_path, err)) { fprintf(stderr, "[reform::ERROR]\033[1;31m %s: %s\033[0m\n", in_path, err.c_str()); exit(EXIT_FAILURE); }
+    if (to_ref_mode) {
+        const int rc = to_ref(out, rd, extra);
+        if (out_path) fclose(out); else fflush(out);
+        return rc;
+    }
     pgh::MoveRec rec;
     int got, ret = 0;
     while ((got = rd.next(rec, err)) > 0)

@@ -505,6 +505,15 @@ extern "C" int pgt_mvops_expand(const uint8_t *mv, uint32_t n, int32_t stride, u
     return (int)pg_mv_expand_host(mv, n, stride, ns, ts, l_seq, packed, reverse != 0, n_to_t != 0, ops, n_ops, query_start, seq);
 }
 
+// ---- ops through a CIGAR onto the reference: the per-read rule the kernels of pg_refops.hip compile (pg_refops.h), run on the host ------
+#include "pg_refops.h"
+// out8: status, n_ops, ref_len, n_match, query_start, query_end, target_start, target_end; op_n / op_t have room for L + n_words values
+extern "C" void pgt_refops(const uint32_t *o, uint32_t L, int32_t query_start, uint32_t status_in, const uint32_t *cigar, uint32_t n_words, int32_t pos, int rna,
+                           uint32_t *op_n, uint8_t *op_t, int64_t *out8) {
+    const PgRfHost h = pg_refops_host(o, L, query_start, status_in, cigar, n_words, pos, rna != 0, op_n, op_t);
+    out8[0] = h.status; out8[1] = h.n_ops; out8[2] = h.ref_len; out8[3] = h.n_match; out8[4] = h.query_start; out8[5] = h.query_end; out8[6] = h.target_start; out8[7] = h.target_end;
+}
+
 // ---- the dump-text parser (pg_dumptext.h): the geometry of its kernels and the field rule they compile, run on the host ----------------
 #include "pg_dumptext.h"
 extern "C" void pgt_dumptext_levels(uint32_t *out4) { out4[0] = PG_DT_LANE; out4[1] = PG_DT_TILE; out4[2] = PG_DT_BLOCK; out4[3] = PG_DT_MIN_FIELD; }

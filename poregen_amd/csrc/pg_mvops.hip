@@ -19,11 +19,9 @@
 #include <hip/hip_runtime.h>
 #include "pg_mvops.h"
 #include "pg_dev.h"
-#include "pg_hip_host.h"
+#include "pg_mvops_handle.h"
 
 #include <cstring>
-#include <string>
-#include <vector>
 
 namespace {
 
@@ -197,21 +195,6 @@ __global__ __launch_bounds__(kReadThreads) void k_mv_seq(const MvBatch B, const 
 }
 
 } // namespace
-
-struct pg_mvops {
-    int device = 0;
-    PgStream own;
-    hipStream_t s = nullptr;
-    // the batch on the device (host batches), the piece list, the work arrays, the result
-    PgDev<uint8_t> d_mv, d_seqb, d_opt, d_seq;
-    PgDev<uint64_t> d_mvoff, d_ns, d_ts, d_boff, d_opoff, d_seqoff, d_totals;
-    PgDev<int32_t> d_stride, d_qs, d_t0, d_t1;
-    PgDev<uint32_t> d_lseq, d_flag, d_pfirst, d_pread, d_piece5, d_read3, d_opn, d_status;
-    PgPinned<uint8_t> h_back;
-    std::vector<uint64_t> mv_off, byte_off;
-    std::vector<uint32_t> l_seq, piece_first, piece_read, status;
-    std::string err;
-};
 
 extern "C" {
 

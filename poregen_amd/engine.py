@@ -1614,6 +1614,54 @@ class MoveOps:
                     seq=self.seq.cpu().numpy(), seq_off=self.seq_off.cpu().numpy().view(np.uint64), status=self.status_device.cpu().numpy().view(np.uint32))
 
 
+class RefOps:
+    """The result of MoveExpander.project: CUDA tensors that alias the expander's device buffers (valid until its next project / close), in
+    the layout of a pg_batch -- op_n uint32 (as int32 bits), op_t uint8, op_off int64[n + 1], query_start / target_start / target_end /
+    query_end int32[n], ref_len / n_match / status int32[n] -- plus n_ops, n_refused, first_refused and, on the host (numpy), status,
+    ref_len, n_match (uint32[n]) and query_end (int32[n])."""
+
+    def __init__(self, res, device):
+        import torch
+
+        class _Alias:  # zero-copy hand-over through the CUDA array interface
+            def __init__(self, ptr, n, typestr):
+                self.__cuda_array_interface__ = {"shape": (int(n),), "typestr": typestr, "data": (int(ptr or 0), False), "version": 2}
+
+        dev = torch.device("cuda", device)
+
+        def wrap(ptr, n, typestr, dtype):
+            if n == 0 or not ptr:
+                return torch.empty(0, dtype=dtype, device=dev)
+            return torch.as_tensor(_Alias(ptr, n, typestr), device=dev)
+
+        def host(ptr, ctype, dtype):
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), (n,)).copy() if n else np.zeros(0, dtype)
+
+        n = int(res.n_reads)
+        self.n_reads, self.n_ops = n, int(res.n_ops)
+        self.n_refused, self.first_refused = int(res.n_refused), int(res.first_refused)
+        self.op_n = wrap(res.op_n, self.n_ops, "<i4", torch.int32)
+        self.op_t = wrap(res.op_t, self.n_ops, "|u1", torch.uint8)
+        self.op_off = wrap(res.op_off, n + 1, "<i8", torch.int64)
+        for name in ("query_start", "target_start", "target_end", "query_end", "ref_len", "n_match"):
+            setattr(self, name, wrap(getattr(res, name), n, "<i4", torch.int32))
+        self.status_device = wrap(res.status, n, "<i4", torch.int32)
+        self.status = host(res.status_host, C.c_uint32, np.uint32)
+        self.ref_len_host = host(res.ref_len_host, C.c_uint32, np.uint32)
+        self.n_match_host = host(res.n_match_host, C.c_uint32, np.uint32)
+        self.query_end_host = host(res.query_end_host, C.c_int32, np.int32)
+
+    def to_host(self):
+        """Every device array as numpy, in the widths of the ABI (op_n, ref_len, n_match, status uint32, op_off uint64)."""
+        out = dict(op_n=self.op_n.cpu().numpy().view(np.uint32), op_t=self.op_t.cpu().numpy(), op_off=self.op_off.cpu().numpy().view(np.uint64),
+                   status=self.status_device.cpu().numpy().view(np.uint32))
+        for name in ("query_start", "target_start", "target_end", "query_end"):
+            out[name] = getattr(self, name).cpu().numpy()
+        for name in ("ref_len", "n_match"):
+            out[name] = getattr(self, name).cpu().numpy().view(np.uint32)
+        return out
+
+
 class MoveExpander:
     """Expands the move tables of a batch of BAM records into the ss ops `poregen reform -c -k 1 -m 0` prints (pg_mvops_*). The nine
     arrays of expand() are numpy arrays, or contiguous CUDA tensors of the same widths (read in place)."""
@@ -1675,6 +1723,50 @@ class MoveExpander:
             raise PgError(st, self._lib.pg_mvops_last_error(self._h).decode())
         return MoveOps(res, self.device)
 
+    def project(self, ops, cigar, cigar_off, pos, rna: bool = False) -> RefOps:
+        """Carries ops through the records' CIGARs onto the reference (pg_mvops_project). ops: a MoveOps (read in place), or a tuple of
+        CUDA tensors (op_n, op_off, query_start, status) of 4, 8, 4 and 4-byte integers. cigar (uint32 words len << 4 | op), cigar_off
+        (uint64[n + 1]) and pos (int32[n], 0-based) are three numpy arrays or three contiguous CUDA tensors of the same widths."""
+        op_n, op_off, qs, status = (ops.op_n, ops.op_off, ops.query_start, ops.status_device) if isinstance(ops, MoveOps) else ops
+        for a, size, name in ((op_n, 4, "op_n"), (op_off, 8, "op_off"), (qs, 4, "query_start"), (status, 4, "status")):
+            if not (hasattr(a, "is_cuda") and a.is_cuda) or a.dtype.itemsize != size or not a.is_contiguous():
+                raise ValueError(f"project: {name} must be a contiguous CUDA tensor of {size}-byte integers")
+        n = op_off.numel() - 1
+        if n < 0 or qs.numel() != n or status.numel() != n:
+            raise ValueError("project: op_off needs n + 1 entries, query_start and status one per read")
+        given = (cigar, cigar_off, pos)
+        widths = (("cigar", 4, np.uint32), ("cigar_off", 8, np.uint64), ("pos", 4, np.int32))
+        on_dev = [hasattr(a, "is_cuda") and a.is_cuda for a in given]
+        c = _abi.PgMvopsCigars()
+        if all(on_dev):
+            for a, (name, size, _) in zip(given, widths):
+                if a.dtype.itemsize != size or not a.is_contiguous():
+                    raise ValueError(f"device CIGARs: {name} must be a contiguous tensor of {size}-byte integers")
+            keep = given
+            ptrs = [C.c_void_p(a.data_ptr()) if a.numel() else None for a in given]
+            sizes = [a.numel() for a in given]
+            c.location = _abi.PG_LOC_DEVICE
+        elif any(on_dev):
+            raise ValueError("project takes three host arrays or three device tensors of CIGARs, not a mixture")
+        else:
+            keep = [np.ascontiguousarray(a, dtype=dt) for a, (_, _, dt) in zip(given, widths)]
+            ptrs = [C.c_void_p(a.ctypes.data) if a.size else None for a in keep]
+            sizes = [a.size for a in keep]
+            c.location = _abi.PG_LOC_HOST
+        if sizes[1] != n + 1 or sizes[2] != n:
+            raise ValueError("project: cigar_off needs n + 1 entries, pos one per read")
+        c.n_reads, c.flags = n, (_abi.PG_MVOPS_RNA if rna else 0)
+        c.op_n, c.n_ops, c.op_off = (C.c_void_p(op_n.data_ptr()) if op_n.numel() else None), op_n.numel(), C.c_void_p(op_off.data_ptr())
+        c.query_start, c.status = (C.c_void_p(qs.data_ptr()) if n else None), (C.c_void_p(status.data_ptr()) if n else None)
+        c.cigar, c.cigar_off, c.pos = ptrs
+        c.n_cigar = sizes[0]
+        res = _abi.PgMvopsProjection()
+        st = self._lib.pg_mvops_project(self._h, C.byref(c), C.byref(res))
+        del keep
+        if st != 0:
+            raise PgError(st, self._lib.pg_mvops_last_error(self._h).decode())
+        return RefOps(res, self.device)
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.pg_mvops_destroy(self._h)
@@ -1692,6 +1784,23 @@ def reform_ops(mv, mv_off, stride, ns, ts, l_seq, flag, seq_bytes, byte_off, rna
     ex = MoveExpander(device)
     try:
         r = ex.expand(mv, mv_off, stride, ns, ts, l_seq, flag, seq_bytes, byte_off, rna=rna, n_to_t=n_to_t)
+        out = r.to_host()
+        out.update(n_ops=r.n_ops, n_refused=r.n_refused, first_refused=r.first_refused)
+        return out
+    finally:
+        ex.close()
+
+
+def project_ops(op_n, op_off, query_start, status, cigar, cigar_off, pos, rna: bool = False, device: int = 0):
+    """One-shot MoveExpander.project of host arrays (op_n uint32, op_off uint64[n + 1], query_start int32[n], status uint32[n], and the
+    CIGAR arrays): the result's arrays on the host (RefOps.to_host) plus n_ops, n_refused and first_refused."""
+    import torch
+    ex = MoveExpander(device)
+    try:
+        dev = torch.device("cuda", device)
+        up = [torch.from_numpy(np.ascontiguousarray(a, dtype=dt).view(vt)).to(dev)
+              for a, dt, vt in ((op_n, np.uint32, np.int32), (op_off, np.uint64, np.int64), (query_start, np.int32, np.int32), (status, np.uint32, np.int32))]
+        r = ex.project(tuple(up), cigar, cigar_off, pos, rna=rna)
         out = r.to_host()
         out.update(n_ops=r.n_ops, n_refused=r.n_refused, first_refused=r.first_refused)
         return out

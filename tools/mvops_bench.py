@@ -8,11 +8,18 @@
            8 TB/s HBM peak DESIGN.md uses.
   cli      wall time, median of --runs, of `gmove --reform reads.bam` against the two-step route on the same files:
            `reform -c -k 1 --stride 0` plus `gmove --fastq reads.fastq reads.paf`, both commands' times added.
+  ref      (--cases ref, or --ref) the projection onto the reference (pg_mvops_project) beside the expansion on the same device batches: the two
+           shapes above with CIGARs drawn at 5 % edits, and the ragged shape with clean single-word CIGARs. Per call the HIP-event time
+           on the expander's stream (the kernels, the small copies of offsets and statuses between them and the host's share in between)
+           and the wall time, best of --reps after one warm-up. Bytes per second over 4 B read plus 5 B written per output op plus, per
+           CIGAR word, its 4 B and its two 4-byte prefixes written once and read once; beside it the best plain streaming read of
+           tools/probe/stream_probe.hip in the same run. One box, one run: a first look, not a bound -- no counters were read.
 Prints one JSON object and writes it to --out.
 """
 import argparse
 import json
 import os
+import re
 import shutil
 import statistics
 import subprocess
@@ -67,6 +74,80 @@ def bench_device(name, lengths, reps):
                 bytes_per_s=moved / best, share_of_hbm_peak=moved / best / HBM_PEAK)
 
 
+def stream_read_tbps():
+    """the best plain 16-byte streaming read of the probe, TB/s (None when the probe cannot be built or run)"""
+    exe = os.path.join(ROOT, "tools", "probe", "stream_probe")
+    if not os.path.exists(exe):
+        r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-o", exe, exe + ".hip"], capture_output=True, text=True)
+        if r.returncode:
+            return None
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    best = [float(m.group(1)) for m in re.finditer(r"^A plain.*?([0-9.]+) TB/s", r.stdout, re.M)]
+    return max(best) if best else None
+
+
+def cigars(l_seq, rate, seed=5):
+    """One CIGAR per read over its l_seq bases: M runs of geometric length with a 1..3-base I or D between them (rate = 0: one word LM)."""
+    rng = np.random.default_rng(seed)
+    words, off = [], [0]
+    for L in l_seq.tolist():
+        if rate <= 0 or L < 4:
+            w = [L << 4]
+        else:
+            n_runs = max(1, int(L * rate))
+            cuts = np.sort(rng.choice(np.arange(1, L), size=min(n_runs, L - 1), replace=False))
+            runs = np.diff(np.concatenate([[0], cuts, [L]]))
+            w, kinds, lens = [], rng.random(len(runs)), rng.integers(1, 4, len(runs))
+            for i, m in enumerate(runs.tolist()):
+                if i and kinds[i] < 0.5 and m > int(lens[i]):
+                    w.append(int(lens[i]) << 4 | 1); m -= int(lens[i])
+                elif i:
+                    w.append(int(lens[i]) << 4 | 2)
+                w.append(m << 4)
+        words += w; off.append(len(words))
+    return np.array(words, np.uint32), np.array(off, np.uint64), rng.integers(0, 1 << 24, len(l_seq)).astype(np.int32)
+
+
+def bench_ref(name, lengths, rate, reps):
+    import torch
+    from poregen_amd.engine import MoveExpander
+    a = tables(lengths)
+    t = {k: torch.from_numpy(v).cuda() for k, v in a.items()}
+    cg, cg_off, pos = cigars(a["l_seq"], rate)
+    d_cg, d_off, d_pos = torch.from_numpy(cg.view(np.int32)).cuda(), torch.from_numpy(cg_off.view(np.int64)).cuda(), torch.from_numpy(pos).cuda()
+    ex = MoveExpander()
+    stream = torch.cuda.Stream()
+    ex.set_stream(stream)
+    best = dict(expand_event_ms=None, expand_wall_ms=None, project_event_ms=None, project_wall_ms=None)
+
+    def timed(key, fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record(stream)
+        r = fn()
+        e1.record(stream)
+        e1.synchronize()
+        wall, ev = (time.perf_counter() - t0) * 1e3, e0.elapsed_time(e1)
+        return r, wall, ev
+
+    for i in range(reps + 1):
+        mo, w, e = timed("expand", lambda: ex.expand(t["mv"], t["mv_off"], t["stride"], t["ns"], t["ts"], t["l_seq"], t["flag"], t["seq_bytes"], t["byte_off"], rna=True))
+        if i:
+            best["expand_wall_ms"] = min(w, best["expand_wall_ms"] or w); best["expand_event_ms"] = min(e, best["expand_event_ms"] or e)
+        pr, w, e = timed("project", lambda: ex.project(mo, d_cg, d_off, d_pos, rna=True))
+        if i:
+            best["project_wall_ms"] = min(w, best["project_wall_ms"] or w); best["project_event_ms"] = min(e, best["project_event_ms"] or e)
+    assert mo.n_refused == 0 and pr.n_refused == 0 and int(pr.n_match_host.sum()) + int(((cg & 15) == 1).sum()) + int(((cg & 15) == 2).sum()) == pr.n_ops
+    moved = pr.n_ops * (4 + 5) + cg.size * (4 + 2 * 4 * 2)
+    out = dict(shape=name, cigars="clean: one word per read" if rate <= 0 else f"{rate:.0%} edits", reads=len(lengths), ops_in=int(mo.n_ops), ops_out=int(pr.n_ops),
+               cigar_words=int(cg.size), bytes_moved=int(moved), **best)
+    out["project_bytes_per_s"] = moved / (best["project_event_ms"] * 1e-3)
+    out["project_share_of_hbm_peak"] = out["project_bytes_per_s"] / HBM_PEAK
+    ex.close()
+    return out
+
+
 def bench_cli(n_reads, runs, tmp):
     from poregen_amd import synth
     b = synth.make_batch_fast(n_reads, kind="rna004", seed=11)
@@ -109,14 +190,24 @@ def main():
     ap.add_argument("--cases", default="device,cli")
     ap.add_argument("--tmp", default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--ref", action="store_true", help="the projection onto the reference beside the expansion (= --cases ref)")
     args = ap.parse_args()
+    if args.ref:
+        args.cases = "ref"
     out = {}
-    if "device" in args.cases:
+    if "ref" in args.cases.split(","):
+        rng = np.random.default_rng(3)
+        ragged = np.clip(rng.lognormal(7.6, 1.0, 200000), 400, 200000).astype(np.int64)
+        ragged = ragged[:int(np.searchsorted(np.cumsum(ragged), 50000 * 800)) + 1]
+        out["ref"] = [bench_ref("configs[1]: 50000 x 800", np.full(50000, 800, np.int64), 0.05, args.reps), bench_ref("ragged 400..200000", ragged, 0.05, args.reps),
+                      bench_ref("ragged 400..200000", ragged, 0.0, args.reps)]
+        out["stream_read_tbps"] = stream_read_tbps()
+    if "device" in args.cases.split(","):
         rng = np.random.default_rng(3)
         ragged = np.clip(rng.lognormal(7.6, 1.0, 200000), 400, 200000).astype(np.int64)
         ragged = ragged[:int(np.searchsorted(np.cumsum(ragged), 50000 * 800)) + 1]
         out["device"] = [bench_device("configs[1]: 50000 x 800", np.full(50000, 800, np.int64), args.reps), bench_device("ragged 400..200000", ragged, args.reps)]
-    if "cli" in args.cases:
+    if "cli" in args.cases.split(","):
         tmp = tempfile.mkdtemp(prefix="mvops_bench", dir=args.tmp)
         try:
             out["cli"] = bench_cli(args.cli_reads, args.runs, tmp)
