@@ -158,8 +158,16 @@ enum { PG_LOC_HOST = 0, PG_LOC_DEVICE = 1 };
 enum {
     PG_FLAG_LAZY_STATS = 1u << 0, /* compute median/MAD only for reads that contribute a kept event
                                      (legal: event acceptance is signal-independent in the PAF path);
-                                     default is to touch every read's signal like the reference does */
-    PG_FLAG_PROFILE = 1u << 1,    /* record HIP events around every kernel (pg_kernel_stats) */
+                                     default (eager) is to compute them for every read of the batch, with one exception: a
+                                     pg_submit batch that is counted front first (pg_kernel_stats: front_complete) and whose front
+                                     completes every k-mer starts its statistics behind the front's scan and leaves out the reads
+                                     behind the last one that can own a kept event -- the reference does not touch the reads behind
+                                     the completing one either (gmove.cpp:733-735). Their d_med / d_mad are NaN, no result changes.
+                                     A read with an unusable calibration fails the batch wherever it lies; reads long enough to be
+                                     cut into slices are always computed. Not with PG_FLAG_SKIP_OUT_OF_RANGE or PG_FLAG_PROFILE. */
+    PG_FLAG_PROFILE = 1u << 1,    /* record HIP events around every kernel (pg_kernel_stats). Each kernel is timed over the WHOLE
+                                     batch: a profiling context never leaves reads out of the statistics (see PG_FLAG_LAZY_STATS),
+                                     so bytes of the batch / time of k_read_stats (bench.py's roofline object) means what it says */
     PG_FLAG_ONE_STREAM = 1u << 10, /* every kernel of a batch on ONE stream. Since round 3 the DEFAULT is the two-stream mode below
                                      (PG_FLAG_OVERLAP) whenever the context computes eager statistics and none of PG_FLAG_PROFILE /
                                      _LAZY_STATS / _SKIP_OUT_OF_RANGE / _DEFER_STATS / _OVERLAP_TAIL is set: batches that follow each other
@@ -396,8 +404,8 @@ typedef struct {
     const uint32_t *d_ev_read;  /* read index inside the batch */
     const uint64_t *d_samp_off;
     const double   *d_samples;
-    const double   *d_med;      /* [n_reads] (scaling==1; NaN where not computed) */
-    const double   *d_mad;
+    const double   *d_med;      /* [n_reads] (scaling==1; NaN where not computed: reads without a kept event under PG_FLAG_LAZY_STATS, */
+    const double   *d_mad;      /* and the reads from the cut read on behind a complete front: PG_FLAG_LAZY_STATS, stats_cut_batches) */
 } pg_device_view;
 pg_status pg_last_batch_device(pg_ctx *ctx, pg_device_view *out);
 
@@ -506,7 +514,9 @@ pg_status   pg_job_kernel_stats(pg_job *job, uint32_t shard, pg_kernel_stat *out
 /* profiling (PG_FLAG_PROFILE): per-kernel launch counts and HIP-event times since the last reset. With or without the flag, counters
  * follow as entries of 0 ms when they are not 0: stats_cancelled_on_device, long_reads_split, long_helpers_short_batches,
  * front_complete / front_missed (settled pg_submit batches whose events were counted front first: the first tiles completed every k-mer and
- * the tiles behind them were not walked / did not, and were; PGMOVE_FRONT_TILES=n sets the front in tiles of 4096 ops, 0 = never), and the
+ * the tiles behind them were not walked / did not, and were; PGMOVE_FRONT_TILES=n sets the front in tiles of 4096 ops, 0 = never),
+ * stats_cut_batches / stats_cut_reads (those of the front_complete batches whose eager statistics were ordered behind the front's scan, and
+ * the reads from their cut reads on, whose samples the statistics did not touch: PG_FLAG_LAZY_STATS), and the
  * gathers for many kept events by the kernel queued: gather_form_wave, gather_form_evpair, gather_form_lanes4 / 8 / 16; k_sort_scatter:
  * passes of the LSD radix sort queued (more than 2^20 slots; the entry "sort_events" counts the whole sort once per batch) */
 pg_status pg_kernel_stats(pg_ctx *ctx, pg_kernel_stat *out, uint32_t cap, uint32_t *n_out);

@@ -91,6 +91,11 @@ struct pg_ctx {
     // front-first count phase (front_tiles_for): the current batch's front in tiles (0: one pass), and the settled batches whose front did /
     // did not complete every k-mer
     uint32_t front_tiles = 0; uint64_t front_complete = 0, front_missed = 0;
+    // ... whose eager statistics are ordered behind the front's scan and skip the reads from the cut read on (PgFront; decided in pg_count):
+    // the current batch is such a batch / its statistics stream still has to wait for ev_front / settled ones whose front completed
+    // (stats_cut_batches) and the reads from their cut reads on (stats_cut_reads)
+    bool stats_behind_cut = false, wait_front = false; uint64_t stats_cut_batches = 0, stats_cut_reads = 0;
+    PgEvent ev_front; // recorded behind the front's scan
     uint32_t gen_reads = 0; // generic reads of the last settled batch
     bool batch_all_matches = false; // PG_BATCH_ALL_MATCHES of the current batch (and not PG_FLAG_DEBUG_SPLIT_WALK)
     PgDev<> job_total, job_freq; bool have_job_totals = false; // pg_collect_gathered / pg_job_totals_device
@@ -338,7 +343,7 @@ pg_status pg_create(const pg_params *p, pg_ctx **out) {
         return hipEventCreateWithFlags(ev, hipEventDisableTiming);
     };
     for (int i = 0; i < 2; i++) { PG_HIP_TRY(c, make_event(&c->ev_join[i].h)); PG_HIP_TRY(c, make_event(&c->ev_gathered[i].h)); }
-    PG_HIP_TRY(c, make_event(&c->ev_fork.h));
+    PG_HIP_TRY(c, make_event(&c->ev_fork.h)); PG_HIP_TRY(c, make_event(&c->ev_front.h));
     PG_HIP_TRY(c, c->settle_host.ensure(sizeof(PgSettlePack)));
     const size_t tb = (size_t)c->n_codes * sizeof(int32_t);
     // one allocation, the U-spelled table right behind the T-spelled one: a kernel reaches both from ONE uniform base with a 32-bit
@@ -367,8 +372,8 @@ pg_status pg_create(const pg_params *p, pg_ctx **out) {
     PG_HIP_TRY(c, grow(c->acc_cnt, ns * 8ull)); PG_HIP_TRY(c, grow(c->running, ns * 8ull)); PG_HIP_TRY(c, grow(c->keep, ns * 8ull)); PG_HIP_TRY(c, grow(c->tile_last, ns * 4ull));
     PG_HIP_TRY(c, grow(c->ev_off, (ns + 1) * 8ull)); PG_HIP_TRY(c, grow(c->plan_totals, 64)); PG_HIP_TRY(c, grow(c->base_stage, ns * 8ull));
     PG_HIP_TRY(c, grow(c->job_total, ns * 8ull)); PG_HIP_TRY(c, grow(c->job_freq, ns * 8ull)); // allocated once: callers may cache the pointers
-    PG_HIP_TRY(c, grow(c->totals, 256 * 4)); PG_HIP_TRY(c, grow(c->dbase, 256 * 4)); PG_HIP_TRY(c, grow(c->scount, 16)); PG_HIP_TRY(c, grow(c->errflag, 48));
-    PG_HIP_TRY(c, hipMemset(c->errflag.p, 0, 48)); // [0] u64 error word, [8] i32 layout flag, [16] u32 gen_count[2] (PgWalkOut), [24] u32 ticket (k_rank_scan), [32] u32 PgFront::word[2]
+    PG_HIP_TRY(c, grow(c->totals, 256 * 4)); PG_HIP_TRY(c, grow(c->dbase, 256 * 4)); PG_HIP_TRY(c, grow(c->scount, 16)); PG_HIP_TRY(c, grow(c->errflag, 56));
+    PG_HIP_TRY(c, hipMemset(c->errflag.p, 0, 56)); // [0] u64 error word, [8] i32 layout flag, [16] u32 gen_count[2] (PgWalkOut), [24] u32 ticket (k_rank_scan), [32] u32 PgFront::word[2], [40] u64 PgFront's cut-read word
     PG_HIP_TRY(c, grow(c->stat_err[0], 32)); PG_HIP_TRY(c, grow(c->stat_err[1], 32)); // [0..2] statistics flags, [3] pg_div_domain_ok failed (the long-read counters live in long_ring)
     PG_HIP_TRY(c, hipMemset(c->stat_err[0].p, 0, 32)); PG_HIP_TRY(c, hipMemset(c->stat_err[1].p, 0, 32));
     PG_HIP_TRY(c, grow(c->long_ring, 64)); PG_HIP_TRY(c, hipMemset(c->long_ring.p, 0, 64));
@@ -581,10 +586,14 @@ static pg_status launch_stats(pg_ctx *c, hipStream_t st, const uint8_t *needed, 
         prof_end(c, st);
     }
     const int win = (c->prm.flags & PG_FLAG_DEBUG_NARROW) ? 0 : 15;
+    // stats_behind_cut: the cut-read word is final before k_read_stats starts -- on the chain's stream by stream order, on the statistics
+    // stream by the event behind the front's scan (the record pass in front of it needs nothing of the chain and does not wait)
+    if (c->wait_front && st != c->st) { PG_HIP_TRY(c, hipStreamWaitEvent(st, c->ev_front, 0)); c->wait_front = false; }
+    const bool cut = c->stats_behind_cut && !needed;
     prof_begin(c, "k_read_stats", st);
     PG_HIP_TRY(c, pg_launch_read_stats(st, c->B, c->read_plan[sl].p, c->med[sl].as<double>(), c->mad[sl].as<double>(),
                          c->stat_status[sl].as<int32_t>(), flags, win, c->wide_list[sl].as<uint32_t>(), flags + 1, oor, range_only,
-                         c->gcal[sl].as<double>(), LS));
+                         c->gcal[sl].as<double>(), LS, cut ? c->errflag.as<unsigned long long>() + 5 : nullptr, c->batch_id));
     prof_end(c, st);
     // the rare reads (in-range interval wider than 1024 codes; usually none): their workers ride in the launch of the sample-offset
     // scan when that comes next on the same stream (rare_pending); otherwise a launch of their own, here
@@ -773,10 +782,10 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
         PG_HIP_TRY(c, grow(c->gen_flag, (n + 1) * 4ull));
         if (c->gen_flag.cap != before) PG_HIP_TRY(c, hipMemsetAsync(c->gen_flag.p, 0, c->gen_flag.cap, c->st));
     }
-    if (++c->batch_id == 0) { // (PgFront::word[1] is compared with the serial number as well)
+    if (++c->batch_id == 0) { // (PgFront::word[1] and the tag of the cut-read word are compared with the serial number as well)
         c->batch_id = 1;
         PG_HIP_TRY(c, hipMemsetAsync(c->gen_flag.p, 0, c->gen_flag.cap, c->st));
-        PG_HIP_TRY(c, hipMemsetAsync(c->errflag.as<uint32_t>() + 8, 0, 8, c->st));
+        PG_HIP_TRY(c, hipMemsetAsync(c->errflag.as<uint32_t>() + 8, 0, 16, c->st));
     }
     PG_HIP_TRY(c, grow(c->meta, (n + 1) * sizeof(PgReadMeta))); PG_HIP_TRY(c, grow(c->status, (n + 1) * 4ull));
     PG_HIP_TRY(c, grow(c->read_needed, n + 2ull));
@@ -834,6 +843,12 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
     { pg_status sl_ = fill_long(c, LS, true); if (sl_ != PG_OK) return sl_; }
     c->front_tiles = front_tiles_for(c, N, counts_out != nullptr);
     const PgFront FR{c->front_tiles, c->errflag.as<uint32_t>() + 8};
+    // Eager statistics of a batch counted front first start behind the front's scan and read its cut-read word (PgFront): behind a complete
+    // front, the reads that own no kept event are not streamed -- the reference never reads them (gmove.cpp:733-735). Not with
+    // PG_FLAG_SKIP_OUT_OF_RANGE (the walk waits for the statistics' verdict), and not in a PG_FLAG_PROFILE context: its passes time each
+    // kernel over the whole batch (include/pgmove.h). Every other batch queues its statistics where it always did.
+    c->stats_behind_cut = FR.tiles && eager_stats && !skip_oor && c->prm.scaling == 1 && !(c->prm.flags & PG_FLAG_PROFILE);
+    c->wait_front = false;
     prof_begin(c, "k_batch_init", c->st);
     PG_HIP_TRY(c, pg_launch_batch_init(c->st, n, c->read_needed.as<uint8_t>(), c->running.as<uint64_t>(), c->prm.n_slots,
                          c->zero_running ? 1 : 0, overlap ? nullptr : c->stat_err[c->slot].as<int32_t>(), c->B, c->prm.pa_min, c->prm.pa_max,
@@ -869,8 +884,12 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
                                     c->tile_last.as<int32_t>(), acc_copy, fuse_plan ? c->keep.as<uint64_t>() : nullptr, c->ev_off.as<uint64_t>(),
                                     c->plan_totals.as<uint64_t>(), c->errflag.as<uint32_t>() + 6, &c->plan_done,
                                     O.btot, dense_direct(c, N) ? c->part_Bp.as<uint32_t>() : nullptr, dense_direct(c, N) ? c->chunk_part.as<uint64_t>() : nullptr,
-                                    FR, FR.tiles ? PG_PASS_FRONT : PG_PASS_WHOLE, c->batch_id));
+                                    FR, FR.tiles ? PG_PASS_FRONT : PG_PASS_WHOLE, c->batch_id, O.tile_read, n));
         prof_end(c, c->st);
+        if (c->stats_behind_cut && overlap) { // the statistics stream starts k_read_stats behind this scan (launch_stats); one stream: queued behind it anyway
+            PG_HIP_TRY(c, hipEventRecord(c->ev_front, c->st));
+            c->wait_front = true;
+        }
         if (FR.tiles) { // the tiles behind the front: queued regardless, empty launches if the front has completed every k-mer (PgFront)
             prof_begin(c, "k_events_tail", c->st);
             PG_HIP_TRY(c, pg_launch_events(c->st, c->B, W, O, c->prm.n_slots, S.hist, 0u, 0u, FR, PG_PASS_TAIL));
@@ -1176,6 +1195,7 @@ static pg_status settle_batch(pg_ctx *c) {
     PG_HIP_TRY(c, hipStreamSynchronize(c->st));
     const PgSettlePack pk = *c->settle_host.p;
     if (c->front_tiles) { if (pk.front[0]) c->front_complete++; else c->front_missed++; } // (a batch that fails was counted front first all the same)
+    if (c->stats_behind_cut && pk.front[0]) { c->stats_cut_batches++; c->stats_cut_reads += c->B.n_reads - std::min(pk.front[1], c->B.n_reads); } // its statistics left out the reads from pk.front[1] on
     pg_status s = check_read_errors(c, pk);
     if (s != PG_OK) { c->have_batch_result = false; c->downloaded = true; return s; }
     const uint64_t tot[2] = {pk.n_kept, pk.full_slots};
@@ -1679,6 +1699,12 @@ pg_status pg_kernel_stats(pg_ctx *c, pg_kernel_stat *out, uint32_t cap, uint32_t
         if (out && n < cap) { out[n].name = "front_missed"; out[n].launches = c->front_missed; out[n].total_ms = 0.0; }
         n++;
     }
+    if (c->stats_cut_batches) { // ... whose front completed and whose statistics, ordered behind its scan, left out the reads from the cut read on
+        if (out && n < cap) { out[n].name = "stats_cut_batches"; out[n].launches = c->stats_cut_batches; out[n].total_ms = 0.0; }
+        n++;
+        if (out && n < cap) { out[n].name = "stats_cut_reads"; out[n].launches = c->stats_cut_reads; out[n].total_ms = 0.0; } // reads from the cut read on, all those batches together
+        n++;
+    }
     if (c->long_helpers_short) { // settled batches that wanted more helper waves than were launched (their surplus long reads ran on one wave each)
         if (out && n < cap) { out[n].name = "long_helpers_short_batches"; out[n].launches = c->long_helpers_short; out[n].total_ms = 0.0; }
         n++;
@@ -1702,7 +1728,7 @@ pg_status pg_kernel_stats_reset(pg_ctx *c) {
     PG_HIP_TRY(c, hipStreamSynchronize(c->st));
     if (c->st2) PG_HIP_TRY(c, hipStreamSynchronize(c->st2));
     prof_drain(c);
-    c->prof_acc.clear(); c->prof_names.clear(); c->stats_cancelled = 0; c->long_reads_split = 0; c->long_helpers_short = 0; c->front_complete = 0; c->front_missed = 0;
+    c->prof_acc.clear(); c->prof_names.clear(); c->stats_cancelled = 0; c->long_reads_split = 0; c->long_helpers_short = 0; c->front_complete = 0; c->front_missed = 0; c->stats_cut_batches = 0; c->stats_cut_reads = 0;
     for (uint64_t &f : c->gather_forms) f = 0;
     c->sort_scatters = 0;
     return PG_OK;

@@ -249,6 +249,10 @@ struct PgGathered {
 // bit. word[1] == batch_id: the batch holds an op of PG_OP_N_LIMIT samples or more (k_batch_init looks when it is given the word); the
 // front then never counts as complete, so the event kernel reports that op's read exactly as a pass over the whole batch does.
 // Only the two tail launches and k_settle_pack may read word[0]; the host never waits for it.
+// Behind the two words, one 8-byte word {batch_id << 32 | cut_read}, written by the same workgroup only when the front is complete: every
+// kept event of the batch belongs to a read below cut_read (0: nothing is kept here; n_reads: the last useful tile is the front's last one,
+// whose end nobody looked up). Its readers are k_settle_pack and k_read_stats of a batch whose statistics are ordered behind the front's scan
+// (pg_api.hip: stats_behind_cut) -- a plain load, the word is final before their launch starts; a stale word carries another batch's number.
 struct PgFront { uint32_t tiles; uint32_t *word; }; // tiles = 0: one pass over the whole batch; else a multiple of 4 below the batch's tiles
 enum { PG_PASS_WHOLE = 0, PG_PASS_FRONT = 1, PG_PASS_TAIL = 2 };
 // ---- launchers (all asynchronous on `st`; the result is hipGetLastError() behind the launch / the queued copy's status) -----------------------------------------------------------
@@ -339,7 +343,9 @@ hipError_t pg_launch_rank_direct_count(hipStream_t st, const uint32_t *ev_slot, 
                                  const uint32_t *btot /* PgWalkOut::btot */, uint32_t *Bp /* may be null: its prefix, for pg_launch_rank_emit2 */,
                                  uint64_t *zero64 /* with Bp: PG_CHUNK_PART_N chunk sums, zeroed by the same extra workgroup (may be null) */,
                                  // pass != PG_PASS_WHOLE (needs plan_keep, no acc_copy, no Bp): the scan over the front's tiles / over the tiles behind it
-                                 const PgFront &F = PgFront{}, int pass = PG_PASS_WHOLE, uint32_t batch_id = 0);
+                                 const PgFront &F = PgFront{}, int pass = PG_PASS_WHOLE, uint32_t batch_id = 0,
+                                 // PG_PASS_FRONT: PgWalkOut::tile_read and the batch's reads, for the cut read of a complete front (PgFront)
+                                 const uint32_t *tile_read = nullptr, uint32_t n_reads = 0);
 hipError_t pg_launch_rank_direct_emit(hipStream_t st, const uint32_t *ev_slot, uint64_t n, uint32_t n_slots, const PgSortBufs &S,
                                 const uint64_t *keep, const uint64_t *ev_off, const uint64_t *totals, const PgDevBatch &B,
                                 const PgWalkParams &W, const PgWalkOut &O, const PgKeptOut &K);
@@ -403,7 +409,10 @@ hipError_t pg_launch_read_plan(hipStream_t st, const PgDevBatch &B, const uint8_
 // the main statistics launch (one wave per read, 1024 LDS bins); reads that need more put themselves on wide_list
 // gcal (may be null): double[4 * n_reads], per read {offset, scale, median, MAD} for k_gather
 hipError_t pg_launch_read_stats(hipStream_t st, const PgDevBatch &B, const void *plan_buf, double *med, double *mad, int32_t *status, int32_t *err, int win,
-                                uint32_t *wide_list, int32_t *wide_count, uint8_t *oor, int range_only, double *gcal, const PgLongState &LS);
+                                uint32_t *wide_list, int32_t *wide_count, uint8_t *oor, int range_only, double *gcal, const PgLongState &LS,
+                                // cut_word (may be null: every read gets its statistics): PgFront's cut-read word, final on `st` before this launch;
+                                // if its tag is batch_id, the reads from its cut read on get NaN and none of their samples is touched
+                                const unsigned long long *cut_word = nullptr, uint32_t batch_id = 0);
 // pg_finish over several batches: a batch's kept samples stay on the device until then; (k-mer, batch) segments are copied into the
 // job's k-mer-major order by one launch and leave the device once
 struct PgSeg { const double *src; uint64_t dst_off, n; };

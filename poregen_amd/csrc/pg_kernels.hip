@@ -1008,7 +1008,8 @@ struct PgScanPlan {
 // the end of a scan workgroup whose launch carries the cut: signal, and -- the workgroup that draws last_ticket -- apply the cut.
 // front_word (the front's scan of a front-first count phase, else null): see PgFront and the end of this function
 __device__ __forceinline__ void rank_scan_cut(const PgScanPlan &plan, uint64_t *__restrict__ acc_cnt, int32_t *__restrict__ tile_last, const uint64_t *running,
-                                              uint32_t limit, uint32_t n_slots, uint32_t last_ticket, uint32_t *front_word, uint32_t batch_id) {
+                                              uint32_t limit, uint32_t n_slots, uint32_t last_ticket, uint32_t *front_word, uint32_t batch_id,
+                                              const uint32_t *tile_read = nullptr, uint32_t F = 0u, uint32_t n_reads = 0u) {
     const int lane = lane_id();
     __shared__ uint32_t sh_ticket, wsum[PG_SCAN_WAVES], wfull[PG_SCAN_WAVES]; __shared__ int wmax[PG_SCAN_WAVES];
     __builtin_amdgcn_s_waitcnt(0); // every storing wave: its two stores have left ...
@@ -1049,6 +1050,13 @@ __device__ __forceinline__ void rank_scan_cut(const PgScanPlan &plan, uint64_t *
             for (uint32_t s_ = tid; s_ < n_slots; s_ += PG_SCAN_WAVES * WAVE)
                 plan.running_out[s_] = running[s_] + __hip_atomic_load(reinterpret_cast<unsigned long long *>(acc_cnt + s_), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (tid == 0) front_word[0] = complete ? 1u : 0u;
+        // ... and the cut read (PgFront): every kept event of the batch belongs to a read below it. tmax is the last tile that places an event,
+        // and the read that holds the first op of the tile behind it (written by the front's k_events) is the last one that can own an op of
+        // tile tmax. tmax == F - 1: the tile behind it belongs to the tail, which does not run -- nothing is skipped (rare; not searched for).
+        if (tid == 0 && complete && tile_read) {
+            const uint32_t cut = tmax < 0 ? 0u : ((uint32_t)tmax + 1u < F ? tile_read[tmax + 1] + 1u : n_reads);
+            *reinterpret_cast<unsigned long long *>(front_word + 2) = (unsigned long long)batch_id << 32 | (cut < n_reads ? cut : n_reads);
+        }
     }
     if (tid == 0) {
         plan.ev_off[n_slots] = carry; plan.plan_totals[0] = carry; plan.plan_totals[1] = full;
@@ -1157,7 +1165,8 @@ __global__ __launch_bounds__(PG_SCAN_WAVES * WAVE) void k_rank_scan(uint32_t *__
 // answer stands where no column here qualifies: see below), and the cut over the whole row from the running counts the front left alone.
 template <bool TAIL> __global__ __launch_bounds__(PG_SCAN_WAVES * WAVE) void k_rank_scan_part(uint32_t *__restrict__ hist, uint32_t n_tiles, uint32_t F, uint32_t *__restrict__ totals,
                                                   uint64_t *__restrict__ acc_cnt, uint32_t n_slots, uint32_t n_digits, const uint64_t *running,
-                                                  uint32_t limit, int32_t *__restrict__ tile_last, PgScanPlan plan, uint32_t *front_word, uint32_t batch_id) {
+                                                  uint32_t limit, int32_t *__restrict__ tile_last, PgScanPlan plan, uint32_t *front_word, uint32_t batch_id,
+                                                  const uint32_t *tile_read, uint32_t n_reads) {
     if (TAIL && front_word[0]) return; // (block-uniform, in front of every barrier)
     const uint32_t d = blockIdx.x * PG_SCAN_WAVES + (threadIdx.x >> 6); // one wave per digit
     const int lane = lane_id();
@@ -1204,7 +1213,7 @@ template <bool TAIL> __global__ __launch_bounds__(PG_SCAN_WAVES * WAVE) void k_r
             }
         }
     }
-    rank_scan_cut(plan, acc_cnt, tile_last, running, limit, n_slots, gridDim.x - 1u, TAIL ? nullptr : front_word, batch_id);
+    rank_scan_cut(plan, acc_cnt, tile_last, running, limit, n_slots, gridDim.x - 1u, TAIL ? nullptr : front_word, batch_id, tile_read, F, n_reads);
 }
 
 // generic mode: exclusive prefix over the digits (<= 1024) -> first output index of each digit
@@ -2355,7 +2364,8 @@ __device__ __forceinline__ void stats_one_read(uint32_t *hist, const PgDevBatch 
 __global__ __launch_bounds__(64 * PG_STATS_WPB) __attribute__((amdgpu_waves_per_eu(PG_STATS_WAVES_PER_EU, PG_STATS_WAVES_PER_EU))) void k_read_stats(PgDevBatch B, const PgStatRec *__restrict__ rec, double *__restrict__ med,
                                                    double *__restrict__ mad, int32_t *__restrict__ status, int32_t *__restrict__ err,
                                                    int win, uint8_t *__restrict__ oor, int range_only, uint32_t *__restrict__ wide_list,
-                                                   int32_t *__restrict__ wide_count, uint32_t keep_cached, double *__restrict__ gcal, PgLongState LS) {
+                                                   int32_t *__restrict__ wide_count, uint32_t keep_cached, double *__restrict__ gcal, PgLongState LS,
+                                                   const unsigned long long *__restrict__ cut_word, uint32_t batch_id) {
     __shared__ __attribute__((aligned(16))) uint32_t hist_all[PG_STATS_WPB][StatsGeom<1024>::LDS_WORDS];
     static_assert(StatsGeom<1024>::LDS_WORDS + 1 <= PG_LONG_WORDS, "a long read's histogram in global memory");
 #if PG_STATS_WPB == 1
@@ -2380,6 +2390,13 @@ __global__ __launch_bounds__(64 * PG_STATS_WPB) __attribute__((amdgpu_waves_per_
     const PgStatRec m = rec[r]; // everything this read needs besides its samples: one scalar load
     PG_MARK(0, 0); // the record
     if (m.mode != PG_STAT_RUN) { if (slice == 0) stats_no_result(lane, r, m.mode == PG_STAT_BAD ? PGR_ERR_SCALE : 0, med, mad, gcal, status, err); return; }
+    // a read behind the cut read of a complete front (PgFront) owns no kept event: no sample of it is touched, as the reference never reads
+    // it (gmove.cpp:733-735). Behind the report of an unusable calibration, in front of the wide list; never a long read (m.split: its slices
+    // meet in a shared histogram and a counter that the last one leaves zeroed). The word was final before this launch started: a plain load.
+    if (cut_word && m.split == 0) {
+        const unsigned long long cw = *cut_word;
+        if ((uint32_t)(cw >> 32) == batch_id && r >= (uint32_t)cw) { stats_no_result(lane, r, 0, med, mad, gcal, status, err); return; }
+    }
     if (m.span > 1024) { if (lane == 0) stats_list_wide(r, m.span, B.n_reads, wide_list, wide_count); return; } // for the wider launch (never split)
     const int16_t *__restrict__ sig = B.sig;
     const int c_lo = m.c_lo;
@@ -2657,7 +2674,8 @@ static uint32_t tiles_for(uint64_t n) { return pg_tiles(n, false); }
 hipError_t pg_launch_rank_direct_count(hipStream_t st, const uint32_t *ev_slot, uint64_t n, uint32_t n_slots, const PgSortBufs &S,
                                  uint64_t *acc_cnt, uint64_t *running, uint32_t limit, int32_t *tile_last, uint64_t *acc_copy,
                                  uint64_t *plan_keep, uint64_t *plan_ev_off, uint64_t *plan_totals, uint32_t *plan_ticket, bool *plan_done,
-                                 const uint32_t *btot, uint32_t *Bp, uint64_t *zero64, const PgFront &F, int pass, uint32_t batch_id) {
+                                 const uint32_t *btot, uint32_t *Bp, uint64_t *zero64, const PgFront &F, int pass, uint32_t batch_id,
+                                 const uint32_t *tile_read, uint32_t n_reads) {
     int nbits = 1; while ((1u << nbits) < n_slots) ++nbits;
     const uint32_t n_tiles = pg_tiles(n, true);
     *plan_done = false;
@@ -2665,8 +2683,8 @@ hipError_t pg_launch_rank_direct_count(hipStream_t st, const uint32_t *ev_slot, 
         if (!plan_keep || acc_copy || Bp || !F.word || F.tiles == 0 || (F.tiles & 3u) || F.tiles >= n_tiles) return hipErrorInvalidValue;
         const PgScanPlan P{plan_keep, plan_ev_off, plan_totals, running, plan_ticket};
         const dim3 grid(((1u << nbits) + PG_SCAN_WAVES - 1) / PG_SCAN_WAVES), block(PG_SCAN_WAVES * WAVE);
-        if (pass == PG_PASS_FRONT) PG_LAUNCH(k_rank_scan_part<false>, grid, block, 0, st, S.hist, n_tiles, F.tiles, S.totals, acc_cnt, n_slots, 1u << nbits, (const uint64_t *)running, limit, tile_last, P, F.word, batch_id);
-        else PG_LAUNCH(k_rank_scan_part<true>, grid, block, 0, st, S.hist, n_tiles, F.tiles, S.totals, acc_cnt, n_slots, 1u << nbits, (const uint64_t *)running, limit, tile_last, P, F.word, batch_id);
+        if (pass == PG_PASS_FRONT) PG_LAUNCH(k_rank_scan_part<false>, grid, block, 0, st, S.hist, n_tiles, F.tiles, S.totals, acc_cnt, n_slots, 1u << nbits, (const uint64_t *)running, limit, tile_last, P, F.word, batch_id, tile_read, n_reads);
+        else PG_LAUNCH(k_rank_scan_part<true>, grid, block, 0, st, S.hist, n_tiles, F.tiles, S.totals, acc_cnt, n_slots, 1u << nbits, (const uint64_t *)running, limit, tile_last, P, F.word, batch_id, (const uint32_t *)nullptr, 0u);
         *plan_done = true;
         return hipSuccess;
     }
@@ -2827,7 +2845,8 @@ __global__ void k_settle_pack(const uint32_t *__restrict__ errflag, const int32_
     p.n_kept = totals[0]; p.full_slots = totals[1];
     p.n_samples = p.n_kept < samp_off_entries ? samp_off[p.n_kept] : 0; // (a failed batch may leave any total: the host looks at the error words first)
     p.cancel[0] = cancel_flag ? cancel_flag[0] : 0u; p.cancel[1] = cancel_flag ? cancel_flag[1] : 0u;
-    p.front[0] = front_word ? front_word[0] : 0u; p.front[1] = 0u; // the front of a front-first count phase completed every k-mer (PgFront)
+    p.front[0] = front_word ? front_word[0] : 0u; // the front of a front-first count phase completed every k-mer (PgFront) ...
+    p.front[1] = front_word && front_word[0] ? front_word[2] : 0u; // ... and its cut read (the low half of the word behind the two; its tag is this batch's)
     *out = p;
 }
 hipError_t pg_launch_settle_pack(hipStream_t st, const uint32_t *errflag, const int32_t *stat_err, const int32_t *long_cnt, const uint64_t *totals, const uint64_t *samp_off,
@@ -2905,12 +2924,13 @@ hipError_t pg_launch_read_plan(hipStream_t st, const PgDevBatch &B, const uint8_
 }
 
 hipError_t pg_launch_read_stats(hipStream_t st, const PgDevBatch &B, const void *plan_buf, double *med, double *mad, int32_t *status, int32_t *err, int win,
-                                uint32_t *wide_list, int32_t *wide_count, uint8_t *oor, int range_only, double *gcal, const PgLongState &LS) {
+                                uint32_t *wide_list, int32_t *wide_count, uint8_t *oor, int range_only, double *gcal, const PgLongState &LS,
+                                const unsigned long long *cut_word, uint32_t batch_id) {
     if (B.n_reads == 0) return hipSuccess;
     const PgStatRec *plan = reinterpret_cast<const PgStatRec *>(plan_buf);
     static_assert(PG_STATS_WPB == 1, "the helpers of long reads are addressed as workgroups behind the reads' own");
     PG_LAUNCH(k_read_stats, dim3(B.n_reads + (LS.tab ? LS.cap : 0u)), dim3(64 * PG_STATS_WPB), 0, st, B, plan, med, mad, status, err, win, oor, range_only, wide_list, wide_count,
-              B.n_reads / PG_STATS_CACHED_FRACTION, gcal, LS);
+              B.n_reads / PG_STATS_CACHED_FRACTION, gcal, LS, cut_word, batch_id);
     return hipSuccess;
 }
 
