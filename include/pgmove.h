@@ -172,7 +172,8 @@ enum {
                                      (PG_FLAG_OVERLAP) whenever the context computes eager statistics and none of PG_FLAG_PROFILE /
                                      _LAZY_STATS / _SKIP_OUT_OF_RANGE / _DEFER_STATS / _OVERLAP_TAIL is set: batches that follow each other
                                      run 14-17 % faster (0.161 -> 0.139 ms per 50 000-read batch). This flag keeps the one-stream form:
-                                     short jobs (a hardware queue takes 15-20 ms to create: the CLI sets it), clean per-kernel timings. */
+                                     short jobs (a hardware queue takes 15-20 ms to create: the CLI sets it), clean per-kernel timings.
+                                     Both flags are defaults PER BATCH since round 10: see PG_FLAG_OVERLAP. */
     PG_FLAG_OVERLAP = 1u << 2,    /* two-stream mode, THE DEFAULT since round 3 (see PG_FLAG_ONE_STREAM for when it applies): the statistics
                                      kernels of batch i+1 run on a second stream next to the event / rank / emit chain of batches i and
                                      i+1; that stream is created with a quarter of the compute units (of every XCD) withheld, so that the
@@ -180,7 +181,13 @@ enum {
                                      batch). Every kernel then shares the chip: per-kernel timings (PG_FLAG_PROFILE, bench.py's roofline
                                      object) are taken on one stream. Setting the flag explicitly asks for the mode where it is not the
                                      default. The gather stays on the chain's stream (beside the chain of batch i+1 it was worth 0-5 %,
-                                     profiles/r04_side_gather.txt). */
+                                     profiles/r04_side_gather.txt).
+                                     Since round 10 the mode is a default PER BATCH: the flag gives the context its second stream, and a
+                                     pg_submit batch whose statistics are ordered behind the front's scan (see PG_FLAG_LAZY_STATS) is
+                                     queued on the chain's stream alone, exactly as a PG_FLAG_ONE_STREAM context queues it -- behind a
+                                     complete front there is too little left to overlap (pg_kernel_stats: front_one_stream;
+                                     PGMOVE_FRONT_TWO_STREAMS=1 keeps such batches on two streams: tests, A/B). Every other batch of the
+                                     context uses both streams as before. No result depends on the mode. */
     PG_FLAG_SHORT_READS_OK = 1u << 4, /* a read with fewer than k matched bases simply has no events (move-table front-end,
                                         where that is well defined); default: PG_ERR_INPUT, because the PAF path of the
                                         reference has undefined behaviour there (src/gmove.cpp:891) */
@@ -516,7 +523,8 @@ pg_status   pg_job_kernel_stats(pg_job *job, uint32_t shard, pg_kernel_stat *out
  * front_complete / front_missed (settled pg_submit batches whose events were counted front first: the first tiles completed every k-mer and
  * the tiles behind them were not walked / did not, and were; PGMOVE_FRONT_TILES=n sets the front in tiles of 4096 ops, 0 = never),
  * stats_cut_batches / stats_cut_reads (those of the front_complete batches whose eager statistics were ordered behind the front's scan, and
- * the reads from their cut reads on, whose samples the statistics did not touch: PG_FLAG_LAZY_STATS), and the
+ * the reads from their cut reads on, whose samples the statistics did not touch: PG_FLAG_LAZY_STATS), front_one_stream (settled batches
+ * of a two-stream context that were queued on the chain's stream alone: PG_FLAG_OVERLAP), and the
  * gathers for many kept events by the kernel queued: gather_form_wave, gather_form_evpair, gather_form_lanes4 / 8 / 16; k_sort_scatter:
  * passes of the LSD radix sort queued (more than 2^20 slots; the entry "sort_events" counts the whole sort once per batch) */
 pg_status pg_kernel_stats(pg_ctx *ctx, pg_kernel_stat *out, uint32_t cap, uint32_t *n_out);

@@ -96,6 +96,11 @@ struct pg_ctx {
     // (stats_cut_batches) and the reads from their cut reads on (stats_cut_reads)
     bool stats_behind_cut = false, wait_front = false; uint64_t stats_cut_batches = 0, stats_cut_reads = 0;
     PgEvent ev_front; // recorded behind the front's scan
+    // Stream mode per batch (pg_count): in a PG_FLAG_OVERLAP context a stats_behind_cut batch is queued on the chain's stream
+    // alone, as a PG_FLAG_ONE_STREAM context queues it -- behind a complete front its statistics stream 28 MB, and the second stream's
+    // hand-overs and launches cost more than they hide. batch_one_stream: the current batch is one / prev_one_stream: the batch in front of it
+    // was (the statistics stream then waits for the chain's stream before it touches what both share) / settled ones (front_one_stream)
+    bool batch_one_stream = false, prev_one_stream = false; uint64_t front_one_stream = 0;
     uint32_t gen_reads = 0; // generic reads of the last settled batch
     bool batch_all_matches = false; // PG_BATCH_ALL_MATCHES of the current batch (and not PG_FLAG_DEBUG_SPLIT_WALK)
     PgDev<> job_total, job_freq; bool have_job_totals = false; // pg_collect_gathered / pg_job_totals_device
@@ -590,10 +595,17 @@ static pg_status launch_stats(pg_ctx *c, hipStream_t st, const uint8_t *needed, 
     // stream by the event behind the front's scan (the record pass in front of it needs nothing of the chain and does not wait)
     if (c->wait_front && st != c->st) { PG_HIP_TRY(c, hipStreamWaitEvent(st, c->ev_front, 0)); c->wait_front = false; }
     const bool cut = c->stats_behind_cut && !needed;
+    // a cut launch handles the reads behind what the front's ops cover (and a margin) in groups (k_read_stats); PGMOVE_STATS_GROUP_FROM=n
+    // (tests, A/B; read per batch) sets that index itself, n >= n_reads: no group
+    uint32_t group_from = 0xffffffffu;
+    if (cut) {
+        const char *ov = getenv("PGMOVE_STATS_GROUP_FROM");
+        group_from = ov ? (uint32_t)std::min<unsigned long long>(strtoull(ov, nullptr, 10), 0xffffffffull) : pg_stats_group_from(c->B.n_reads, c->B.n_ops, c->front_tiles);
+    }
     prof_begin(c, "k_read_stats", st);
     PG_HIP_TRY(c, pg_launch_read_stats(st, c->B, c->read_plan[sl].p, c->med[sl].as<double>(), c->mad[sl].as<double>(),
                          c->stat_status[sl].as<int32_t>(), flags, win, c->wide_list[sl].as<uint32_t>(), flags + 1, oor, range_only,
-                         c->gcal[sl].as<double>(), LS, cut ? c->errflag.as<unsigned long long>() + 5 : nullptr, c->batch_id));
+                         c->gcal[sl].as<double>(), LS, cut ? c->errflag.as<unsigned long long>() + 5 : nullptr, c->batch_id, group_from));
     prof_end(c, st);
     // the rare reads (in-range interval wider than 1024 codes; usually none): their workers ride in the launch of the sample-offset
     // scan when that comes next on the same stream (rare_pending); otherwise a launch of their own, here
@@ -817,19 +829,43 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
     c->slot ^= 1; // this batch's statistics buffers
     const bool skip_oor = (c->prm.flags & PG_FLAG_SKIP_OUT_OF_RANGE) != 0; // statistics first: the walk needs their verdict
     const bool eager_stats = skip_oor || (c->prm.scaling == 1 && !(c->prm.flags & PG_FLAG_LAZY_STATS));
-    const bool overlap = !skip_oor && (c->prm.flags & PG_FLAG_OVERLAP) != 0;
+    c->front_tiles = front_tiles_for(c, N, counts_out != nullptr);
+    const PgFront FR{c->front_tiles, c->errflag.as<uint32_t>() + 8};
+    // Eager statistics of a batch counted front first start behind the front's scan and read its cut-read word (PgFront): behind a complete
+    // front, the reads that own no kept event are not streamed -- the reference never reads them (gmove.cpp:733-735). Not with
+    // PG_FLAG_SKIP_OUT_OF_RANGE (the walk waits for the statistics' verdict), and not in a PG_FLAG_PROFILE context: its passes time each
+    // kernel over the whole batch (include/pgmove.h). Every other batch queues its statistics where it always did.
+    c->stats_behind_cut = FR.tiles && eager_stats && !skip_oor && c->prm.scaling == 1 && !(c->prm.flags & PG_FLAG_PROFILE);
+    c->wait_front = false;
+    // The stream mode is decided per batch: the context's flag says that a second stream exists, and such a batch does not use it. Its
+    // statistics wait for the front's scan anyway, and behind a complete front little is left to overlap: the two event hand-overs, the
+    // record pass's own launch and the empty rare launch cost more than the second stream hides.
+    // PGMOVE_FRONT_TWO_STREAMS=1 (tests, A/B; read per batch) keeps it on two streams.
+    const bool ctx_overlap = !skip_oor && (c->prm.flags & PG_FLAG_OVERLAP) != 0;
+    c->batch_one_stream = ctx_overlap && c->stats_behind_cut && !getenv("PGMOVE_FRONT_TWO_STREAMS");
+    const bool overlap = ctx_overlap && !c->batch_one_stream;
+    // (a two-stream batch that was counted and never collected: nothing on the chain's stream has waited for its statistics yet, and this
+    // batch's k_batch_init writes the long-read table they read)
+    if (c->batch_one_stream && c->stats_in_flight) PG_HIP_TRY(c, hipStreamWaitEvent(c->st, c->ev_join[c->slot ^ 1], 0));
     if (eager_stats && overlap) {
         // The statistics stream only needs the batch to be resident: after the staging copies of a host batch, or
         // after the producer of a device batch when the caller drives us on its own stream. A device batch on the
         // context's own stream must be complete when pg_count is called, so nothing on `st` has to be awaited and
         // the statistics of this batch overlap the tail (plan/emit/scan/gather) of the previous one.
-        if (c->batch_is_host || (c->user_stream && !(b->flags & PG_BATCH_RESIDENT))) { // (PG_BATCH_RESIDENT: the caller vouches that nothing on its stream produces the batch)
+        // Behind a one-stream batch it waits as well: that batch's statistics ran on the chain's stream, so the order of the statistics
+        // stream no longer puts this batch's record pass behind them, and both use the long-read table, its histograms and the rare
+        // launch's scratch. (The event stands behind everything queued so far, the previous batch's gather included.)
+        if (c->batch_is_host || (c->user_stream && !(b->flags & PG_BATCH_RESIDENT)) || c->prev_one_stream) { // (PG_BATCH_RESIDENT: the caller vouches that nothing on its stream produces the batch)
             PG_HIP_TRY(c, hipEventRecord(c->ev_fork, c->st));
             PG_HIP_TRY(c, hipStreamWaitEvent(c->st2, c->ev_fork, 0));
         }
         // ... and the buffers of this slot to be free: the gather of the batch that used them two batches ago
         if (c->slot_used[c->slot]) PG_HIP_TRY(c, hipStreamWaitEvent(c->st2, c->ev_gathered[c->slot], 0));
     }
+    // Not per-job state: pg_reset does not clear it, because it waits for nothing -- the one-stream batch of the job in front may still be
+    // running when the next job's first batch is queued. pg_set_stream, which waits for both streams, does. Left set by a pg_count that
+    // fails behind this line, it costs the next two-stream batch one wait it did not need.
+    c->prev_one_stream = c->batch_one_stream;
     // eager statistics on the main stream (or forked from it later): k_batch_init also writes the statistics record of every
     // read -- k_read_plan's work, one kernel boundary less. The second-stream mode plans on its own stream; lazy statistics
     // plan behind the emit kernel (they need its flags).
@@ -841,14 +877,6 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
     PgLongState LS{};
     ++c->long_seq; // this batch's entry of the long-read counter ring
     { pg_status sl_ = fill_long(c, LS, true); if (sl_ != PG_OK) return sl_; }
-    c->front_tiles = front_tiles_for(c, N, counts_out != nullptr);
-    const PgFront FR{c->front_tiles, c->errflag.as<uint32_t>() + 8};
-    // Eager statistics of a batch counted front first start behind the front's scan and read its cut-read word (PgFront): behind a complete
-    // front, the reads that own no kept event are not streamed -- the reference never reads them (gmove.cpp:733-735). Not with
-    // PG_FLAG_SKIP_OUT_OF_RANGE (the walk waits for the statistics' verdict), and not in a PG_FLAG_PROFILE context: its passes time each
-    // kernel over the whole batch (include/pgmove.h). Every other batch queues its statistics where it always did.
-    c->stats_behind_cut = FR.tiles && eager_stats && !skip_oor && c->prm.scaling == 1 && !(c->prm.flags & PG_FLAG_PROFILE);
-    c->wait_front = false;
     prof_begin(c, "k_batch_init", c->st);
     PG_HIP_TRY(c, pg_launch_batch_init(c->st, n, c->read_needed.as<uint8_t>(), c->running.as<uint64_t>(), c->prm.n_slots,
                          c->zero_running ? 1 : 0, overlap ? nullptr : c->stat_err[c->slot].as<int32_t>(), c->B, c->prm.pa_min, c->prm.pa_max,
@@ -949,11 +977,12 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
     // Statistics only need the signal: in eager mode they run on the second stream, overlapping the
     // latency-bound walk/rank chain above; pg_collect joins the two streams before the gather.
     c->stats_in_flight = false;
-    c->stats_deferred = eager_stats && !skip_oor && !overlap && (c->prm.flags & PG_FLAG_DEFER_STATS) != 0;
+    // (both flags below are ignored with PG_FLAG_OVERLAP: by the CONTEXT's flag, also for a batch of such a context that stays on one stream)
+    c->stats_deferred = eager_stats && !skip_oor && !ctx_overlap && (c->prm.flags & PG_FLAG_DEFER_STATS) != 0;
     // PG_FLAG_OVERLAP_TAIL: the statistics fork off HERE, behind the counting kernels, onto the second stream; the sample_limit
     // cut, the emit kernel and the offset scan of pg_collect -- small launches that keep a fraction of the chip busy -- run
     // next to the streaming kernel, and pg_collect joins the two streams in front of the gather (the only consumer of med/MAD).
-    const bool tail = eager_stats && !skip_oor && !overlap && !c->stats_deferred && (c->prm.flags & PG_FLAG_OVERLAP_TAIL) != 0;
+    const bool tail = eager_stats && !skip_oor && !ctx_overlap && !c->stats_deferred && (c->prm.flags & PG_FLAG_OVERLAP_TAIL) != 0;
     if (eager_stats && !skip_oor && !c->stats_deferred) {
         hipStream_t ss = (overlap || tail) ? c->st2 : c->st;
         if (tail) {
@@ -1195,6 +1224,7 @@ static pg_status settle_batch(pg_ctx *c) {
     PG_HIP_TRY(c, hipStreamSynchronize(c->st));
     const PgSettlePack pk = *c->settle_host.p;
     if (c->front_tiles) { if (pk.front[0]) c->front_complete++; else c->front_missed++; } // (a batch that fails was counted front first all the same)
+    if (c->batch_one_stream) c->front_one_stream++; // ... and was queued on the chain's stream alone in a two-stream context, complete or not
     if (c->stats_behind_cut && pk.front[0]) { c->stats_cut_batches++; c->stats_cut_reads += c->B.n_reads - std::min(pk.front[1], c->B.n_reads); } // its statistics left out the reads from pk.front[1] on
     pg_status s = check_read_errors(c, pk);
     if (s != PG_OK) { c->have_batch_result = false; c->downloaded = true; return s; }
@@ -1241,6 +1271,7 @@ pg_status pg_set_stream(pg_ctx *c, void *hip_stream) {
     PG_HIP_TRY(c, hipSetDevice(c->device));
     PG_HIP_TRY(c, hipStreamSynchronize(c->st));
     if (c->st2) PG_HIP_TRY(c, hipStreamSynchronize(c->st2));
+    c->prev_one_stream = false; // both streams are idle
     c->st = hip_stream ? (hipStream_t)hip_stream : c->own_st;
     c->user_stream = hip_stream != nullptr;
     return PG_OK;
@@ -1705,6 +1736,10 @@ pg_status pg_kernel_stats(pg_ctx *c, pg_kernel_stat *out, uint32_t cap, uint32_t
         if (out && n < cap) { out[n].name = "stats_cut_reads"; out[n].launches = c->stats_cut_reads; out[n].total_ms = 0.0; } // reads from the cut read on, all those batches together
         n++;
     }
+    if (c->front_one_stream) { // settled batches of a two-stream context that were queued on the chain's stream alone (pg_count: stream mode per batch)
+        if (out && n < cap) { out[n].name = "front_one_stream"; out[n].launches = c->front_one_stream; out[n].total_ms = 0.0; }
+        n++;
+    }
     if (c->long_helpers_short) { // settled batches that wanted more helper waves than were launched (their surplus long reads ran on one wave each)
         if (out && n < cap) { out[n].name = "long_helpers_short_batches"; out[n].launches = c->long_helpers_short; out[n].total_ms = 0.0; }
         n++;
@@ -1728,7 +1763,7 @@ pg_status pg_kernel_stats_reset(pg_ctx *c) {
     PG_HIP_TRY(c, hipStreamSynchronize(c->st));
     if (c->st2) PG_HIP_TRY(c, hipStreamSynchronize(c->st2));
     prof_drain(c);
-    c->prof_acc.clear(); c->prof_names.clear(); c->stats_cancelled = 0; c->long_reads_split = 0; c->long_helpers_short = 0; c->front_complete = 0; c->front_missed = 0; c->stats_cut_batches = 0; c->stats_cut_reads = 0;
+    c->prof_acc.clear(); c->prof_names.clear(); c->stats_cancelled = 0; c->long_reads_split = 0; c->long_helpers_short = 0; c->front_complete = 0; c->front_missed = 0; c->stats_cut_batches = 0; c->stats_cut_reads = 0; c->front_one_stream = 0;
     for (uint64_t &f : c->gather_forms) f = 0;
     c->sort_scatters = 0;
     return PG_OK;

@@ -412,7 +412,10 @@ hipError_t pg_launch_read_stats(hipStream_t st, const PgDevBatch &B, const void 
                                 uint32_t *wide_list, int32_t *wide_count, uint8_t *oor, int range_only, double *gcal, const PgLongState &LS,
                                 // cut_word (may be null: every read gets its statistics): PgFront's cut-read word, final on `st` before this launch;
                                 // if its tag is batch_id, the reads from its cut read on get NaN and none of their samples is touched
-                                const unsigned long long *cut_word = nullptr, uint32_t batch_id = 0);
+                                // group_from (cut launches only): the reads from this index on are handled by group workgroups, one wave for
+                                // PG_STATS_GROUP consecutive reads (pg_stats_group_from; any value is correct, it decides speed only)
+                                const unsigned long long *cut_word = nullptr, uint32_t batch_id = 0, uint32_t group_from = 0xffffffffu);
+uint32_t pg_stats_group_from(uint32_t n_reads, uint64_t n_ops, uint32_t front_tiles);
 // pg_finish over several batches: a batch's kept samples stay on the device until then; (k-mer, batch) segments are copied into the
 // job's k-mer-major order by one launch and leave the device once
 struct PgSeg { const double *src; uint64_t dst_off, n; };

@@ -2285,13 +2285,16 @@ __device__ __forceinline__ void stats_finish(uint32_t *hist, int lane, uint32_t 
 }
 
 // a read that gets no statistics: skipped, unusable calibration, or wider than the widest histogram
+// (the calling lane's own read: the group workgroups of k_read_stats, a lane per read, consecutive reads in consecutive lanes)
+__device__ __forceinline__ void stats_no_result_lane(uint32_t r, int code, double *__restrict__ med, double *__restrict__ mad, double *__restrict__ gcal,
+                                                     int32_t *__restrict__ status, int32_t *__restrict__ err) {
+    med[r] = __builtin_nan(""); mad[r] = __builtin_nan("");
+    if (gcal) *reinterpret_cast<double4 *>(gcal + 4ull * r) = make_double4(__builtin_nan(""), __builtin_nan(""), __builtin_nan(""), __builtin_nan(""));
+    if (code) { status[r] = code; atomicMin(&err[0], (int)r); }
+}
 __device__ __forceinline__ void stats_no_result(int lane, uint32_t r, int code, double *__restrict__ med, double *__restrict__ mad, double *__restrict__ gcal,
                                                 int32_t *__restrict__ status, int32_t *__restrict__ err) {
-    if (lane == 0) {
-        med[r] = __builtin_nan(""); mad[r] = __builtin_nan("");
-        if (gcal) *reinterpret_cast<double4 *>(gcal + 4ull * r) = make_double4(__builtin_nan(""), __builtin_nan(""), __builtin_nan(""), __builtin_nan(""));
-        if (code) { status[r] = code; atomicMin(&err[0], (int)r); }
-    }
+    if (lane == 0) stats_no_result_lane(r, code, med, mad, gcal, status, err);
 }
 
 // One read, start to finish, by one wave (the wide / huge launches: rare reads, no cross-read pipelining).
@@ -2361,42 +2364,20 @@ __device__ __forceinline__ void stats_one_read(uint32_t *hist, const PgDevBatch 
 #ifndef PG_STATS_WAVES_PER_EU
 #define PG_STATS_WAVES_PER_EU 6 // measured on one box (tools/ab_lib.sh): 8 waves per SIMD 82 us, 6: 76.7, 5: 77.7, 4: 78.2 -- the memory system queues less behind fewer waves
 #endif
-__global__ __launch_bounds__(64 * PG_STATS_WPB) __attribute__((amdgpu_waves_per_eu(PG_STATS_WAVES_PER_EU, PG_STATS_WAVES_PER_EU))) void k_read_stats(PgDevBatch B, const PgStatRec *__restrict__ rec, double *__restrict__ med,
-                                                   double *__restrict__ mad, int32_t *__restrict__ status, int32_t *__restrict__ err,
-                                                   int win, uint8_t *__restrict__ oor, int range_only, uint32_t *__restrict__ wide_list,
-                                                   int32_t *__restrict__ wide_count, uint32_t keep_cached, double *__restrict__ gcal, PgLongState LS,
-                                                   const unsigned long long *__restrict__ cut_word, uint32_t batch_id) {
-    __shared__ __attribute__((aligned(16))) uint32_t hist_all[PG_STATS_WPB][StatsGeom<1024>::LDS_WORDS];
-    static_assert(StatsGeom<1024>::LDS_WORDS + 1 <= PG_LONG_WORDS, "a long read's histogram in global memory");
-#if PG_STATS_WPB == 1
-    uint32_t *hist = hist_all[0];
-    uint32_t r = blockIdx.x; // uniform: the record and everything derived from it stay in scalar registers
-#else
-    uint32_t *hist = hist_all[threadIdx.x >> 6];
-    uint32_t r = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * PG_STATS_WPB + (threadIdx.x >> 6)));
+#ifndef PG_STATS_GROUP
+#define PG_STATS_GROUP 8 // reads of a group workgroup (k_read_stats). Measured (profiles/r10_stream_mode.txt 8): complete front 8 / 16 / 32: 0.0829 / 0.0827 / 0.0826 ms,
+                         // inside each other's spread; a miss 0.1898 / 0.1928 / 0.2338 -- 16 and 32 are measurably dearer there, so 8
 #endif
-    // the workgroups behind the reads' own are HELPERS: slice `slice` of the long read the table names (PgLongState), or nothing
-    uint32_t slice = 0;
-    if (r >= B.n_reads) {
-        const uint32_t h = r - B.n_reads;
-        const uint32_t reserved = LS.tab ? (uint32_t)LS.cnt[0] : 0u;
-        if (h >= LS.cap || h >= reserved) return;
-        const uint2 e = LS.tab[h];
-        if (e.x == PG_LONG_INVALID) return;
-        r = (uint32_t)__builtin_amdgcn_readfirstlane((int)e.x); slice = (uint32_t)__builtin_amdgcn_readfirstlane((int)e.y);
-    }
-    const int lane = lane_id();
+static_assert(PG_STATS_GROUP >= 1 && PG_STATS_GROUP <= 64, "a lane per read of the group");
+// One read (or slice `slice` of a long one) that is to be computed, start to finish, by the calling wave: the wide-list hand-off, the
+// streaming loop, the slice merge and the selection. r, slice and the record m are uniform. Called from ONE place in k_read_stats (the
+// long-read merge below exists once in the code object: tools/isa_stats.py --check-long-merge); a wave that calls it for several reads
+// in turn separates two calls itself (the histogram is cleared here, behind the first loads of the read).
+__device__ __forceinline__ void stats_read_body(uint32_t *hist, const PgDevBatch &B, const uint32_t r, const uint32_t slice, const PgStatRec &m, const int lane,
+                                                double *__restrict__ med, double *__restrict__ mad, int32_t *__restrict__ status, int32_t *__restrict__ err,
+                                                int win, uint8_t *__restrict__ oor, int range_only, uint32_t *__restrict__ wide_list,
+                                                int32_t *__restrict__ wide_count, uint32_t keep_cached, double *__restrict__ gcal, const PgLongState &LS) {
     PG_PROBE_BEGIN(0);
-    const PgStatRec m = rec[r]; // everything this read needs besides its samples: one scalar load
-    PG_MARK(0, 0); // the record
-    if (m.mode != PG_STAT_RUN) { if (slice == 0) stats_no_result(lane, r, m.mode == PG_STAT_BAD ? PGR_ERR_SCALE : 0, med, mad, gcal, status, err); return; }
-    // a read behind the cut read of a complete front (PgFront) owns no kept event: no sample of it is touched, as the reference never reads
-    // it (gmove.cpp:733-735). Behind the report of an unusable calibration, in front of the wide list; never a long read (m.split: its slices
-    // meet in a shared histogram and a counter that the last one leaves zeroed). The word was final before this launch started: a plain load.
-    if (cut_word && m.split == 0) {
-        const unsigned long long cw = *cut_word;
-        if ((uint32_t)(cw >> 32) == batch_id && r >= (uint32_t)cw) { stats_no_result(lane, r, 0, med, mad, gcal, status, err); return; }
-    }
     if (m.span > 1024) { if (lane == 0) stats_list_wide(r, m.span, B.n_reads, wide_list, wide_count); return; } // for the wider launch (never split)
     const int16_t *__restrict__ sig = B.sig;
     const int c_lo = m.c_lo;
@@ -2491,6 +2472,76 @@ __global__ __launch_bounds__(64 * PG_STATS_WPB) __attribute__((amdgpu_waves_per_
     stats_finish<1024>(hist, lane, r, m, med, mad, gcal, win, oor, range_only PG_PROBE_ARG);
     PG_MARK(0, 4); // selection + stores (slot 3: the prefix scan, marked inside stats_finish)
     PG_PROBE_END(0, r);
+}
+
+// The grid: workgroups [0, r1) are one read each; [r1, r1 + n_groups) one wave for PG_STATS_GROUP consecutive reads from r1 on (launches with
+// a cut word: behind a complete front nearly all of those reads are skipped, and a lane each stores their NaNs; the others are computed by the
+// wave one after the other, in index order); the workgroups behind them are the HELPERS of long reads. Every other launch has r1 = n_reads
+// and no group. Both kinds of workgroup are correct for any read: r1 only decides speed (pg_stats_group_from).
+__global__ __launch_bounds__(64 * PG_STATS_WPB) __attribute__((amdgpu_waves_per_eu(PG_STATS_WAVES_PER_EU, PG_STATS_WAVES_PER_EU))) void k_read_stats(PgDevBatch B, const PgStatRec *__restrict__ rec, double *__restrict__ med,
+                                                   double *__restrict__ mad, int32_t *__restrict__ status, int32_t *__restrict__ err,
+                                                   int win, uint8_t *__restrict__ oor, int range_only, uint32_t *__restrict__ wide_list,
+                                                   int32_t *__restrict__ wide_count, uint32_t keep_cached, double *__restrict__ gcal, PgLongState LS,
+                                                   const unsigned long long *__restrict__ cut_word, uint32_t batch_id, uint32_t r1, uint32_t n_groups) {
+    __shared__ __attribute__((aligned(16))) uint32_t hist_all[PG_STATS_WPB][StatsGeom<1024>::LDS_WORDS];
+    static_assert(StatsGeom<1024>::LDS_WORDS + 1 <= PG_LONG_WORDS, "a long read's histogram in global memory");
+    static_assert(PG_STATS_WPB == 1, "the group workgroups and the helpers of long reads are found from blockIdx.x: [0, r1) reads, [r1, r1 + n_groups) groups, then helper blockIdx.x - r1 - n_groups");
+    uint32_t *hist = hist_all[0];
+    const uint32_t b = blockIdx.x;
+    const int lane = lane_id();
+    uint32_t r = b; // uniform: the record and everything derived from it stay in scalar registers
+    uint32_t slice = 0, base = 0;
+    unsigned long long todo = 0; // group workgroups: the reads of the group that are still to be computed, bit i = read base + i
+    const bool grouped = b >= r1 && b - r1 < n_groups;
+    unsigned long long cw = 0;
+    if (grouped) {
+        base = r1 + (b - r1) * (uint32_t)PG_STATS_GROUP;
+        const uint32_t rl = base + (uint32_t)lane;
+        const bool mine = lane < PG_STATS_GROUP && rl < B.n_reads;
+        int32_t mode = PG_STAT_SKIP; uint32_t split = 0;
+        if (mine) { mode = rec[rl].mode; split = rec[rl].split; } // a lane per read; the word's load below is in flight with these
+        if (cut_word) cw = *cut_word;
+        bool compute = false;
+        if (mine) {
+            // the order of the per-read workgroups: the report of an unusable calibration, then the skip (never a long read), then the rest
+            if (mode != PG_STAT_RUN) stats_no_result_lane(rl, mode == PG_STAT_BAD ? PGR_ERR_SCALE : 0, med, mad, gcal, status, err);
+            else if (split == 0 && (uint32_t)(cw >> 32) == batch_id && cut_word && rl >= (uint32_t)cw) stats_no_result_lane(rl, 0, med, mad, gcal, status, err);
+            else compute = true;
+        }
+        todo = __ballot(compute);
+        if (todo == 0) return;
+    } else if (b >= r1) {
+        // the workgroups behind the reads' own and the groups are HELPERS: slice `slice` of the long read the table names (PgLongState), or nothing
+        const uint32_t h = b - r1 - n_groups;
+        const uint32_t reserved = LS.tab ? (uint32_t)LS.cnt[0] : 0u;
+        if (h >= LS.cap || h >= reserved) return;
+        const uint2 e = LS.tab[h];
+        if (e.x == PG_LONG_INVALID) return;
+        r = (uint32_t)__builtin_amdgcn_readfirstlane((int)e.x); slice = (uint32_t)__builtin_amdgcn_readfirstlane((int)e.y);
+    }
+    for (;;) {
+        if (grouped) {
+            const int i = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            r = (uint32_t)__builtin_amdgcn_readfirstlane((int)(base + (uint32_t)i));
+        }
+        const PgStatRec m = rec[r]; // everything this read needs besides its samples: one scalar load
+        if (!grouped) {
+            if (cut_word) cw = *cut_word; // issued with the record's load, in front of the mode test
+            if (m.mode != PG_STAT_RUN) { if (slice == 0) stats_no_result(lane, r, m.mode == PG_STAT_BAD ? PGR_ERR_SCALE : 0, med, mad, gcal, status, err); return; }
+            // a read behind the cut read of a complete front (PgFront) owns no kept event: no sample of it is touched, as the reference never reads
+            // it (gmove.cpp:733-735). Behind the report of an unusable calibration, in front of the wide list; never a long read (m.split: its slices
+            // meet in a shared histogram and a counter that the last one leaves zeroed). The word was final before this launch started: a plain load.
+            if (cut_word && m.split == 0 && (uint32_t)(cw >> 32) == batch_id && r >= (uint32_t)cw) { stats_no_result(lane, r, 0, med, mad, gcal, status, err); return; }
+        }
+        stats_read_body(hist, B, r, slice, m, lane, med, mad, status, err, win, oor, range_only, wide_list, wide_count, keep_cached, gcal, LS);
+        if (!grouped || todo == 0) return;
+        // the next read of the group: its histogram clear (inside the body, behind its first loads) must follow this read's selection, which
+        // reads the histogram -- one wave, LDS operations in program order; the fence keeps the compiler from moving them
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (PG_STATS_SETPRIO) __builtin_amdgcn_s_setprio(0); // back to streaming
+    }
 }
 
 // The rare reads: in-range interval wider than 1024 codes. ONE launch covers both lists (usually both are empty, and an
@@ -2925,13 +2976,23 @@ hipError_t pg_launch_read_plan(hipStream_t st, const PgDevBatch &B, const uint8_
 
 hipError_t pg_launch_read_stats(hipStream_t st, const PgDevBatch &B, const void *plan_buf, double *med, double *mad, int32_t *status, int32_t *err, int win,
                                 uint32_t *wide_list, int32_t *wide_count, uint8_t *oor, int range_only, double *gcal, const PgLongState &LS,
-                                const unsigned long long *cut_word, uint32_t batch_id) {
+                                const unsigned long long *cut_word, uint32_t batch_id, uint32_t group_from) {
     if (B.n_reads == 0) return hipSuccess;
     const PgStatRec *plan = reinterpret_cast<const PgStatRec *>(plan_buf);
-    static_assert(PG_STATS_WPB == 1, "the helpers of long reads are addressed as workgroups behind the reads' own");
-    PG_LAUNCH(k_read_stats, dim3(B.n_reads + (LS.tab ? LS.cap : 0u)), dim3(64 * PG_STATS_WPB), 0, st, B, plan, med, mad, status, err, win, oor, range_only, wide_list, wide_count,
-              B.n_reads / PG_STATS_CACHED_FRACTION, gcal, LS, cut_word, batch_id);
+    static_assert(PG_STATS_WPB == 1, "the group workgroups and the helpers of long reads are addressed as workgroups behind the reads' own");
+    // only a launch that gets a cut word has group workgroups; every other launch keeps one workgroup per read
+    const uint32_t r1 = cut_word ? std::min(group_from, B.n_reads) : B.n_reads;
+    const uint32_t n_groups = (B.n_reads - r1 + PG_STATS_GROUP - 1) / PG_STATS_GROUP;
+    PG_LAUNCH(k_read_stats, dim3(r1 + n_groups + (LS.tab ? LS.cap : 0u)), dim3(64 * PG_STATS_WPB), 0, st, B, plan, med, mad, status, err, win, oor, range_only, wide_list, wide_count,
+              B.n_reads / PG_STATS_CACHED_FRACTION, gcal, LS, cut_word, batch_id, r1, n_groups);
     return hipSuccess;
+}
+// pg_api.hip: the first read of a cut launch that is handled by a group workgroup -- the reads that hold the front's ops if the reads are
+// even, and a margin: R_est = ceil(n_reads * F * 4096 / n_ops), R1 = min(n_reads, R_est + R_est / 4 + 64)
+uint32_t pg_stats_group_from(uint32_t n_reads, uint64_t n_ops, uint32_t front_tiles) {
+    if (n_ops == 0) return n_reads;
+    const uint64_t est = ((uint64_t)n_reads * front_tiles * PG_SORT_TILE + n_ops - 1) / n_ops;
+    return (uint32_t)std::min<uint64_t>(n_reads, est + est / 4 + 64);
 }
 
 // several batches' (or, for a pg_job, several ranks') kept samples into the k-mer-major order of the whole job, on the device: one
