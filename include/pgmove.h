@@ -70,8 +70,16 @@
  *                                  onto the reference: the PAF that gmove's PAF    or signal-to-reference"); src/gmove.cpp:792-860
  *                                  walk reads against a reference FASTA (the       reads such a PAF, src/realign.cpp, which was
  *                                  reference leaves making it to squigualiser)     to write it, is an empty copy of reform
+ * pg_mvops_project_stranded        the same for records of either strand: a        (no counterpart: the reference has no
+ *                                  reverse record is a forward record on the       projection; src/gmove.cpp:792-805 fetches
+ *                                  reverse complement of its contig                whatever contig a PAF names)
  * pg_mvops_piece / _set_stream /   (no counterpart)
  * _stream / _last_error
+ * pg_refseq_create / _destroy /    (no counterpart)
+ * _add / _set_stream / _last_error
+ * pg_refseq_slice                  faidx_fetch_seq(m_fai, tid, st_k, end_k - 1)    src/gmove.cpp:792-805
+ *                                  for a batch of reads, reverse-complemented for
+ *                                  reverse-strand ones
  *
  * The F1-score metric (src/f1_score/f1score.py) has one too:
  * pg_fscore_create / _destroy     args.rna / args.threshold / args.region         src/f1_score/f1score.py:59-66, 234-246
@@ -815,6 +823,53 @@ typedef struct {
     const int32_t  *query_end_host;
 } pg_mvops_projection;
 pg_status pg_mvops_project(pg_mvops *h, const pg_mvops_cigars *cigars, pg_mvops_projection *out);
+
+/* The same with the records' strands. A reverse-strand record (flag 0x10) is a forward record on the reverse complement of its contig:
+ * with reverse[r] != 0 op j of read r belongs to base L - 1 - j of the stored SEQ (with PG_MVOPS_RNA: to base j), so the words are walked
+ * in reverse order iff PG_MVOPS_RNA is set for a forward read and iff it is not for a reverse one, and pos' = contig_len[r] - pos[r] -
+ * ref_len (uint32 arithmetic, cast to int32) stands where pos[r] stood in target_start / target_end. A reverse read whose contig_len is
+ * <= 0 (no @SQ line; a length above 2^31 - 1 is to be passed as 0) gets PG_MVOPS_ST_NO_CONTIG_LEN, decided behind the seven other
+ * codes. Everything else is pg_mvops_project's, which is this call with strands == NULL; a pg_mvops_strands whose two pointers are NULL
+ * is the same. reverse and contig_len lie where cigars->location says; one of the two alone is PG_ERR_INVALID_ARG. */
+enum { PG_MVOPS_ST_NO_CONTIG_LEN = 8 };
+typedef struct {
+    const uint8_t *reverse;      /* [n_reads]: 0 forward, anything else reverse */
+    const int32_t *contig_len;   /* [n_reads]: the length of the read's reference sequence */
+} pg_mvops_strands;
+pg_status pg_mvops_project_stranded(pg_mvops *h, const pg_mvops_cigars *cigars, const pg_mvops_strands *strands, pg_mvops_projection *out);
+
+/* ---- refseq: the reference slices of mapped reads, gathered on the device ---------------------------------------------------------------
+ * What `gmove --reform --ref` hands the collector as seq / seq_off of a pg_batch: for every read the bases [st_k, end_k) of its contig
+ * (st_k / end_k = the smaller / larger of pos and pos + ref_len under an unsigned compare), fetched as htslib 1.17's faidx_fetch_seq(st_k,
+ * end_k - 1) fetches them -- clamped into the contig; ref_len == 0 gives the ONE base at pos - 1, faidx_adjust_position's quirk (the rule:
+ * csrc/pg_refseq.h). With reverse[r] != 0 the slice is those bases in reverse order, each complemented (A<->T, C<->G in either case,
+ * U -> A, u -> a, every other byte as it is): the slice of the contig's reverse complement.
+ * Contigs are added one by one, whenever a caller first needs them: `bases` are the contig's bytes with the line ends removed, copied to a
+ * device buffer of their own when pg_refseq_add returns; *index is the number pg_refseq_reads::contig names it by. A contig index of -1
+ * is "no such contig" and gives an empty slice. location: where contig, pos, ref_len and reverse lie. An index outside [-1, n_contigs)
+ * is PG_ERR_INVALID_ARG for host arrays and is taken as -1 for device arrays. The result lies in device memory of the handle, as
+ * pg_batch::seq / seq_off take it; complete when the call returns, valid until the next pg_refseq_slice or pg_refseq_destroy. No load
+ * leaves a contig, no store a read's span. No CPU fallback: PG_ERR_NO_DEVICE without a GPU. */
+typedef struct pg_refseq pg_refseq;
+typedef struct {
+    uint64_t n_reads;
+    int32_t  location;           /* PG_LOC_HOST or PG_LOC_DEVICE */
+    const int32_t  *contig;      /* [n_reads]: the index pg_refseq_add gave, or -1 */
+    const int32_t  *pos;         /* [n_reads], 0-based */
+    const uint32_t *ref_len;     /* [n_reads] */
+    const uint8_t  *reverse;     /* [n_reads], or NULL: every read forward */
+} pg_refseq_reads;
+typedef struct {
+    const uint8_t  *seq;         /* device, read r's slice at seq_off[r] .. seq_off[r + 1] */
+    const uint64_t *seq_off;     /* device [n_reads + 1] */
+    uint64_t n_seq;              /* = seq_off[n_reads] */
+} pg_refseq_slices;
+pg_status pg_refseq_create(int32_t device, pg_refseq **out);
+void      pg_refseq_destroy(pg_refseq *h);
+const char *pg_refseq_last_error(const pg_refseq *h); /* h may be NULL: error of the last failed pg_refseq_create */
+pg_status pg_refseq_set_stream(pg_refseq *h, void *hip_stream); /* as pg_mvops_set_stream */
+pg_status pg_refseq_add(pg_refseq *h, const uint8_t *bases, uint64_t n, int32_t *index);
+pg_status pg_refseq_slice(pg_refseq *h, const pg_refseq_reads *reads, pg_refseq_slices *out);
 
 /* ---- model: the k-mer model from the TEXT of dump files, parsed and reduced on the device ---------------------------------------------
  * What scripts/poregen.sh:54-85 (tr ';,' '\n' | tail -n +2 | datamash median 1 / sstdev 1) and :33-52 (awk comma counts | datamash

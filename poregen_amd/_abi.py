@@ -60,6 +60,7 @@ EXPORTS = [
     "pg_pool_create", "pg_pool_destroy", "pg_pool_last_error", "pg_pool_submit", "pg_pool_sync", "pg_pool_finish", "pg_pool_format", "pg_pool_refusal",
     "pg_transform_model", "pg_transform_free",
     "pg_mvops_create", "pg_mvops_destroy", "pg_mvops_last_error", "pg_mvops_piece", "pg_mvops_set_stream", "pg_mvops_stream", "pg_mvops_expand", "pg_mvops_project",
+    "pg_mvops_project_stranded", "pg_refseq_create", "pg_refseq_destroy", "pg_refseq_last_error", "pg_refseq_set_stream", "pg_refseq_add", "pg_refseq_slice",
     "pg_fit_create", "pg_fit_destroy", "pg_fit_last_error", "pg_fit_set_model", "pg_fit_submit", "pg_fit_finish", "pg_fit_set_stream", "pg_fit_pass_ms",
     "pg_fit_parse_model", "pg_fit_residuals",
     "pg_realign_create", "pg_realign_destroy", "pg_realign_last_error", "pg_realign_set_model", "pg_realign_set_stream", "pg_realign_submit", "pg_realign_kernel_ms",
@@ -203,6 +204,18 @@ class PgMvopsProjection(C.Structure):
                 ("op_n", C.c_void_p), ("op_t", C.c_void_p), ("op_off", C.c_void_p), ("query_start", C.c_void_p), ("target_start", C.c_void_p),
                 ("target_end", C.c_void_p), ("query_end", C.c_void_p), ("ref_len", C.c_void_p), ("n_match", C.c_void_p), ("status", C.c_void_p),
                 ("status_host", C.c_void_p), ("ref_len_host", C.c_void_p), ("n_match_host", C.c_void_p), ("query_end_host", C.c_void_p)]
+
+
+class PgMvopsStrands(C.Structure):
+    _fields_ = [("reverse", C.c_void_p), ("contig_len", C.c_void_p)]
+
+
+class PgRefseqReads(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("location", C.c_int32), ("contig", C.c_void_p), ("pos", C.c_void_p), ("ref_len", C.c_void_p), ("reverse", C.c_void_p)]
+
+
+class PgRefseqSlices(C.Structure):
+    _fields_ = [("seq", C.c_void_p), ("seq_off", C.c_void_p), ("n_seq", C.c_uint64)]
 
 
 class PgFitParams(C.Structure):
@@ -403,6 +416,13 @@ def load():
     lib.pg_mvops_stream.argtypes = [vp]; lib.pg_mvops_stream.restype = vp
     lib.pg_mvops_expand.argtypes = [vp, C.POINTER(PgMvopsBatch), C.POINTER(PgMvopsResult)]; lib.pg_mvops_expand.restype = i32
     lib.pg_mvops_project.argtypes = [vp, C.POINTER(PgMvopsCigars), C.POINTER(PgMvopsProjection)]; lib.pg_mvops_project.restype = i32
+    lib.pg_mvops_project_stranded.argtypes = [vp, C.POINTER(PgMvopsCigars), C.POINTER(PgMvopsStrands), C.POINTER(PgMvopsProjection)]; lib.pg_mvops_project_stranded.restype = i32
+    lib.pg_refseq_create.argtypes = [i32, C.POINTER(vp)]; lib.pg_refseq_create.restype = i32
+    lib.pg_refseq_destroy.argtypes = [vp]; lib.pg_refseq_destroy.restype = None
+    lib.pg_refseq_last_error.argtypes = [vp]; lib.pg_refseq_last_error.restype = C.c_char_p
+    lib.pg_refseq_set_stream.argtypes = [vp, vp]; lib.pg_refseq_set_stream.restype = i32
+    lib.pg_refseq_add.argtypes = [vp, vp, C.c_uint64, C.POINTER(i32)]; lib.pg_refseq_add.restype = i32
+    lib.pg_refseq_slice.argtypes = [vp, C.POINTER(PgRefseqReads), C.POINTER(PgRefseqSlices)]; lib.pg_refseq_slice.restype = i32
     if hasattr(lib, "pg_fit_create"):  # (as above: a library built from an older tree has no fit handle)
         lib.pg_fit_create.argtypes = [C.POINTER(PgFitParams), i32, C.POINTER(vp)]; lib.pg_fit_create.restype = i32
         lib.pg_fit_destroy.argtypes = [vp]; lib.pg_fit_destroy.restype = None

@@ -16,6 +16,8 @@
 #include <chrono>
 #include <atomic>
 #include <functional>
+#include <unordered_map>
+#include <cstdint>
 #include <vector>
 
 #define POREGEN_VERSION "0.1.0"
@@ -50,6 +52,7 @@ struct option long_options[] = {
     {"realign", required_argument, 0, 0}, {"realign_rounds", required_argument, 0, 0}, {"band", required_argument, 0, 0},                 // 33 .. 35
     {"min_len", required_argument, 0, 0}, {"min_events", required_argument, 0, 0}, {"realign_m", required_argument, 0, 0},                // 36 .. 38
     {"realign_table", required_argument, 0, 0}, {"ref", required_argument, 0, 0},                                                        // 39, 40
+    {"both_strands", no_argument, 0, 0},                                                                                                  // 41
     {0, 0, 0, 0}};
 
 void print_help(FILE *fp, const Opt &o) { // src/gmove.cpp:80-104
@@ -97,7 +100,11 @@ void print_help(FILE *fp, const Opt &o) { // src/gmove.cpp:80-104
     fprintf(fp, "                              REFERENCE spells -- the ops are carried through each record's CIGAR on the GPU (I and D ops, --kmer_pick_margin\n");
     fprintf(fp, "                              applies) and the sequence is the record's slice of REF.fa, as `poregen reform -c -k 1 --stride 0 --to_ref` followed\n");
     fprintf(fp, "                              by gmove on its PAF with --fastq REF.fa. Unmapped and reverse-strand records (flag 0x4, no RNAME, flag 0x10) are\n");
-    fprintf(fp, "                              skipped and counted; not with --realign or --n_to_t\n");
+    fprintf(fp, "                              skipped and counted (reverse-strand ones: unless --both_strands); not with --realign or --n_to_t\n");
+    fprintf(fp, "   --both_strands             with --ref: reverse-strand records (flag 0x10) are taken too, each as a forward record on the reverse complement\n");
+    fprintf(fp, "                              of its reference sequence, as `reform --to_ref --both_strands` followed by gmove on its PAF with a FASTA that holds\n");
+    fprintf(fp, "                              every sequence and its reverse complement; every read's slice of REF.fa is gathered (and for a reverse-strand\n");
+    fprintf(fp, "                              record reversed and complemented) on the GPU. Needs the @SQ lengths\n");
     fprintf(fp, "   --realign MODEL            with --reform, one device: refine every batch's event boundaries against the k-mer model on the GPU before\n");
     fprintf(fp, "                              collecting, as `poregen realign MODEL` followed by gmove on its PAF; --min_dur, --max_dur, --rna and --n_to_t\n");
     fprintf(fp, "                              are the fit's and the aligner's too; the model's k is its own, independent of -k\n");
@@ -173,6 +180,7 @@ int gmove_main(int argc, char **argv) {
     const char *raw_model_path = nullptr, *dwell_model_path = nullptr, *stdv_limit = "3.1", *event_model_path = nullptr;
     bool reform_mode = false, n_to_t = false;
     const char *ref_path = nullptr; // --ref: the FASTA the records are mapped to
+    bool both_strands = false;      // --both_strands: reverse-strand records are taken, the reference slices come from the device
     const char *realign_model = nullptr, *realign_table = nullptr, *realign_extra = nullptr; // realign_extra: the first option given that needs --realign
     long long realign_rounds = 1, realign_band = 10, realign_min_len = 3, realign_min_events = 20, realign_m = 0;
     int verbose = 3;
@@ -222,6 +230,7 @@ int gmove_main(int argc, char **argv) {
         else if (c == 0 && longindex == 32) event_model_path = optarg;
         else if (c == 0 && longindex == 33) realign_model = optarg;
         else if (c == 0 && longindex == 40) ref_path = optarg;
+        else if (c == 0 && longindex == 41) both_strands = true;
         else if (c == 0 && longindex >= 34 && longindex <= 39) {
             bool ok = true;
             if (!realign_extra) realign_extra = long_options[longindex].name;
@@ -246,6 +255,7 @@ int gmove_main(int argc, char **argv) {
     if (n_to_t && !reform_mode) { fprintf(stderr, "--n_to_t applies with --reform only\n"); print_help(fp_help, opt); return EXIT_FAILURE; }
     // --ref: every usage error ends here too, an unreadable FASTA among them
     pgh::FastxIndex ref_fai;
+    if (both_strands && !ref_path) { fprintf(stderr, "--both_strands applies with --ref only\n"); print_help(fp_help, opt); return EXIT_FAILURE; }
     if (ref_path) {
         const char *why = !reform_mode ? "--ref applies with --reform only" : realign_model ? "--ref cannot be combined with --realign: fit and realign take batches of matches only" :
                           n_to_t ? "--ref cannot be combined with --n_to_t: the sequence is the reference's, there is nothing to rewrite" : nullptr;
@@ -674,8 +684,13 @@ int gmove_main(int argc, char **argv) {
         // every read's slice of the FASTA, and the batch -- I and D ops among its matches -- goes to the collector's generic walk.
         struct Slot { pg_mvops *ex = nullptr; pg_fit *fit = nullptr; pg_realign *ra = nullptr; PgDev<int16_t> sig; PgDev<uint64_t> sig_off; PgDev<double> cal;
                       PgDev<uint8_t> seq; PgDev<uint64_t> seq_off; };
-        uint64_t to_ref_skipped = 0;
+        uint64_t to_ref_skipped = 0, reverse_taken = 0;
         std::string slice;
+        // --both_strands: the contigs go to the device the first time a batch names them (a name the FASTA lacks: index -1), and every
+        // read's slice is cut there (pg_refseq_slice), reversed and complemented for a reverse-strand record
+        pg_refseq *refseq = nullptr;
+        std::unordered_map<std::string, int32_t> contig_index;
+        std::vector<int32_t> rs_contig, rs_clen; std::vector<uint8_t> rs_reverse;
         Slot slots[2];
         pgh::MoveRecs rb;
         std::vector<pgh::Slow5File::RawView> views; std::vector<pgh::Slow5Rec> recs; std::vector<std::string> fetch_err;
@@ -687,6 +702,7 @@ int gmove_main(int argc, char **argv) {
                 if (sl.fit) pg_fit_destroy(sl.fit);
                 if (sl.ra) pg_realign_destroy(sl.ra);
                 if (sl.ex) pg_mvops_destroy(sl.ex);
+                if (refseq) { pg_refseq_destroy(refseq); refseq = nullptr; }
                 sl.fit = nullptr; sl.ra = nullptr; sl.ex = nullptr; sl.sig.release(); sl.sig_off.release(); sl.cal.release(); sl.seq.release(); sl.seq_off.release();
             }
         };
@@ -714,7 +730,7 @@ int gmove_main(int argc, char **argv) {
             rb.clear();
             std::string bad; // why the record behind the batch's last read cannot be taken (empty: nothing wrong)
             while (rb.size() < this_batch_reads && rb.mv.size() < ((size_t)1 << 30)) {
-                const int nr = pgh::next_move_record(sam, raw, "gmove", bad, ref_path ? &to_ref_skipped : nullptr);
+                const int nr = pgh::next_move_record(sam, raw, "gmove", bad, ref_path ? &to_ref_skipped : nullptr, both_strands ? &reverse_taken : nullptr);
                 if (nr == 0) eof = true;
                 if (nr <= 0) break;
                 rb.push(raw);
@@ -783,7 +799,13 @@ int gmove_main(int argc, char **argv) {
                     cg.n_reads = n; cg.location = PG_LOC_HOST; cg.flags = opt.flag_rna ? PG_MVOPS_RNA : 0;
                     cg.op_n = mr.op_n; cg.n_ops = mr.n_ops; cg.op_off = mr.op_off; cg.query_start = mr.query_start; cg.status = mr.status;
                     cg.cigar = rb.cigar.data(); cg.n_cigar = rb.cigar_off[n]; cg.cigar_off = rb.cigar_off.data(); cg.pos = rb.pos.data();
-                    if (pg_mvops_project(sl.ex, &cg, &pr) != PG_OK) { fprintf(stderr, "[gmove] %s\n", pg_mvops_last_error(sl.ex)); status = EXIT_FAILURE; break; }
+                    pg_mvops_strands strands; memset(&strands, 0, sizeof strands);
+                    if (both_strands) { // the strand from the flag, the contig's length from the header, as reform --to_ref --both_strands has them
+                        rs_reverse.resize(n); rs_clen.resize(n);
+                        for (size_t i = 0; i < n; i++) { rs_reverse[i] = (rb.flag[i] & 0x10u) ? 1 : 0; rs_clen[i] = pgh::contig_len_of(rb.ref_len[i]); }
+                        strands.reverse = rs_reverse.data(); strands.contig_len = rs_clen.data();
+                    }
+                    if (pg_mvops_project_stranded(sl.ex, &cg, both_strands ? &strands : nullptr, &pr) != PG_OK) { fprintf(stderr, "[gmove] %s\n", pg_mvops_last_error(sl.ex)); status = EXIT_FAILURE; break; }
                     d_opn = pr.op_n; d_opt = pr.op_t; d_opoff = pr.op_off; d_qs = pr.query_start; d_ts = pr.target_start; d_te = pr.target_end;
                     if (pr.first_refused >= 0) { // reform --to_ref ends on this record: the reads in front of it are the batch
                         n = (size_t)pr.first_refused; eof = false;
@@ -796,7 +818,34 @@ int gmove_main(int argc, char **argv) {
                 }
                 uint64_t n_ops = 0, n_seq = 0; // an accepted read has as many ops as bases
                 for (size_t i = 0; i < n; i++) { n_ops += rb.l_seq[i]; n_seq += rb.l_seq[i]; }
-                if (ref_path && n) {
+                if (both_strands && n) {
+                    if (!refseq && pg_refseq_create(ex_device, &refseq) != PG_OK) { fprintf(stderr, "[gmove] %s\n", pg_refseq_last_error(nullptr)); status = EXIT_FAILURE; break; }
+                    rs_contig.resize(n);
+                    bool ok = pg_refseq_set_stream(refseq, xs) == PG_OK;
+                    for (size_t i = 0; ok && i < n; i++) {
+                        auto it = contig_index.find(rb.rname[i]);
+                        if (it == contig_index.end()) {
+                            int32_t idx = -1; // the whole contig, its line ends stripped; a name the FASTA does not hold stays -1
+                            if (ref_fai.fetch(rb.rname[i], 0, INT64_MAX / 4, slice)) ok = pg_refseq_add(refseq, (const uint8_t *)slice.data(), slice.size(), &idx) == PG_OK;
+                            it = contig_index.emplace(rb.rname[i], idx).first;
+                        }
+                        rs_contig[i] = it->second;
+                    }
+                    pg_refseq_reads rr; memset(&rr, 0, sizeof rr);
+                    rr.n_reads = n; rr.location = PG_LOC_HOST; rr.contig = rs_contig.data(); rr.pos = rb.pos.data(); rr.ref_len = pr.ref_len_host; rr.reverse = rs_reverse.data();
+                    pg_refseq_slices rsl; memset(&rsl, 0, sizeof rsl);
+                    if (!ok || pg_refseq_slice(refseq, &rr, &rsl) != PG_OK) { fprintf(stderr, "[gmove] %s\n", pg_refseq_last_error(refseq)); status = EXIT_FAILURE; break; }
+                    n_seq = rsl.n_seq;
+                    if (!hip_ok(hipMemcpy(&n_ops, pr.op_off + n, sizeof n_ops, hipMemcpyDeviceToHost), "hipMemcpy")) break;
+                    d_seq = rsl.seq; d_seqoff = rsl.seq_off; // the handle's, until its next batch
+                    if (!dev.job) { // two batches are in flight: the slices move to the slot's own buffers, on the expander's stream
+                        if (!hip_ok(sl.seq.ensure(n_seq ? n_seq : 1, n_seq + n_seq / 4 + 256), "hipMalloc") || !hip_ok(sl.seq_off.ensure((n + 1) * 8, (n + 1) * 10), "hipMalloc") ||
+                            (n_seq && !hip_ok(hipMemcpyAsync(sl.seq.p, rsl.seq, n_seq, hipMemcpyDeviceToDevice, xs), "hipMemcpyAsync")) ||
+                            !hip_ok(hipMemcpyAsync(sl.seq_off.p, rsl.seq_off, (n + 1) * 8, hipMemcpyDeviceToDevice, xs), "hipMemcpyAsync") ||
+                            !hip_ok(hipStreamSynchronize(xs), "hipStreamSynchronize")) break;
+                        d_seq = sl.seq.p; d_seqoff = sl.seq_off.p;
+                    }
+                } else if (ref_path && n) {
                     // faidx_fetch_seq(m_fai, tid, st_k, end_k - 1) with st_k / end_k = min / max of the target columns, as the PAF front-end
                     // does it; a name the FASTA does not hold gives an empty slice, and the device skips the read
                     hb.seq.clear(); hb.seq_off.assign(1, 0);
@@ -824,9 +873,9 @@ int gmove_main(int argc, char **argv) {
                     h_opn.resize(n_ops); hb.op_t.assign(n_ops, 0); hb.op_off.resize(n + 1); hb.seq.resize(n_seq); hb.seq_off.resize(n + 1); hb.qs.resize(n); hb.ts.resize(n); hb.te.resize(n);
                     if ((n_ops && !hip_ok(hipMemcpy(h_opn.data(), d_opn, n_ops * 4, hipMemcpyDeviceToHost), "hipMemcpy")) ||
                         (ref_path && n_ops && !hip_ok(hipMemcpy(hb.op_t.data(), d_opt, n_ops, hipMemcpyDeviceToHost), "hipMemcpy")) ||
-                        (!ref_path && n_seq && !hip_ok(hipMemcpy(hb.seq.data(), d_seq, n_seq, hipMemcpyDeviceToHost), "hipMemcpy")) || // (--ref: the slices are the host's)
+                        ((!ref_path || both_strands) && n_seq && !hip_ok(hipMemcpy(hb.seq.data(), d_seq, n_seq, hipMemcpyDeviceToHost), "hipMemcpy")) || // (--ref alone: the slices are the host's)
                         !hip_ok(hipMemcpy(hb.op_off.data(), d_opoff, (n + 1) * 8, hipMemcpyDeviceToHost), "hipMemcpy") ||
-                        (!ref_path && !hip_ok(hipMemcpy(hb.seq_off.data(), d_seqoff, (n + 1) * 8, hipMemcpyDeviceToHost), "hipMemcpy")) ||
+                        ((!ref_path || both_strands) && !hip_ok(hipMemcpy(hb.seq_off.data(), d_seqoff, (n + 1) * 8, hipMemcpyDeviceToHost), "hipMemcpy")) ||
                         !hip_ok(hipMemcpy(hb.qs.data(), d_qs, n * 4, hipMemcpyDeviceToHost), "hipMemcpy") ||
                         !hip_ok(hipMemcpy(hb.ts.data(), d_ts, n * 4, hipMemcpyDeviceToHost), "hipMemcpy") ||
                         !hip_ok(hipMemcpy(hb.te.data(), d_te, n * 4, hipMemcpyDeviceToHost), "hipMemcpy")) break;
@@ -871,7 +920,8 @@ int gmove_main(int argc, char **argv) {
         // the device has read the last batch's ops before the expanders go
         if (dev.ok() && dev.sync() != PG_OK && status == EXIT_SUCCESS) { fprintf(stderr, "[gmove] %s\n", dev.error()); status = EXIT_FAILURE; }
         release();
-        if (ref_path) pgh::print_to_ref_skipped("gmove", to_ref_skipped);
+        if (both_strands) pgh::print_both_strands_skipped("gmove", to_ref_skipped, reverse_taken);
+        else if (ref_path) pgh::print_to_ref_skipped("gmove", to_ref_skipped);
         if (rt && fclose(rt) != 0 && status == EXIT_SUCCESS) { fprintf(stderr, "Error in writing %s.\n", realign_table); status = EXIT_FAILURE; }
         if (realign_model && verbose >= 4)
             fprintf(stderr, "[gmove] realign: k=%u band=%lld rounds=%lld reads=%llu refined=%llu free=%llu moved=%llu\n", realign_k, realign_band, realign_rounds,

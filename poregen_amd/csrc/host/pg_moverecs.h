@@ -25,11 +25,19 @@ inline const char *reform_refusal(uint32_t code) {
 // ... and of a read whose CIGAR the projection onto the reference refuses (codes 5 to 7); the expansion's codes keep their texts
 inline const char *to_ref_refusal(uint32_t code) {
     return code == 5 ? "the record has no CIGAR." : code == 6 ? "the M/I/S/=/X lengths of the CIGAR do not come to the bases of the read." :
-           code == 7 ? "the CIGAR holds an operation that is none of MIDNSHP=X." : reform_refusal(code);
+           code == 7 ? "the CIGAR holds an operation that is none of MIDNSHP=X." :
+           code == 8 ? "the length of the reference sequence is not known (no @SQ line), a reverse-strand record cannot be placed." : reform_refusal(code);
 }
+// the contig length the projection takes for a record (pg_refops.h): 0 stands for "not known", a length above 2^31 - 1 among them
+inline int32_t contig_len_of(int64_t ref_len) { return ref_len > 0 && ref_len <= 0x7fffffffll ? (int32_t)ref_len : 0; }
 // the line both commands print at the end of a run that projected onto a reference
 inline void print_to_ref_skipped(const char *tool, uint64_t n) {
     fprintf(stderr, "[%s] %llu records skipped: unmapped (flag 0x4 or no reference name) or on the reverse strand (flag 0x10)\n", tool, (unsigned long long)n);
+}
+// ... with --both_strands
+inline void print_both_strands_skipped(const char *tool, uint64_t n, uint64_t reverse_taken) {
+    fprintf(stderr, "[%s] %llu records skipped: unmapped (flag 0x4 or no reference name); %llu reverse-strand records taken\n", tool, (unsigned long long)n,
+            (unsigned long long)reverse_taken);
 }
 
 // the records of a batch, back to back, in the layout pg_mvops_batch takes
@@ -62,14 +70,16 @@ struct MoveRecs {
 // The next record a batch takes: 1 with the record in `raw`, 0 at the end of the file, -1 with `bad` saying why the record (or the file
 // behind it) cannot be taken -- the first such record ends the run behind the reads in front of it, with gmove --reform's message.
 // to_ref_skipped (gmove --reform --ref, reform --to_ref): records that are not mapped to the forward strand of a reference -- flag 0x4, no
-// RNAME, flag 0x10 -- are stepped over and counted there.
-inline int next_move_record(SamBamReader &sam, RawMoveRec &raw, const char *tool, std::string &bad, uint64_t *to_ref_skipped = nullptr) {
+// RNAME, flag 0x10 -- are stepped over and counted there. reverse_taken (--both_strands, with to_ref_skipped): mapped records with flag 0x10
+// are taken instead and counted there.
+inline int next_move_record(SamBamReader &sam, RawMoveRec &raw, const char *tool, std::string &bad, uint64_t *to_ref_skipped = nullptr, uint64_t *reverse_taken = nullptr) {
     for (std::string err;;) {
         const int nr = sam.next_raw(raw, err);
         if (nr == 0) return 0;
         if (nr < 0) { bad = "[" + std::string(tool) + "] " + err; return -1; }
         if (raw.flag & 0x900u) continue; // secondary / supplementary: `samtools fastq` does not print them
-        if (to_ref_skipped && ((raw.flag & 0x14u) || raw.rname.empty())) { ++*to_ref_skipped; continue; }
+        if (to_ref_skipped && ((raw.flag & (reverse_taken ? 0x4u : 0x14u)) || raw.rname.empty())) { ++*to_ref_skipped; continue; }
+        if (to_ref_skipped && reverse_taken && (raw.flag & 0x10u)) ++*reverse_taken;
         const char *why = !raw.has_ns ? "tag 'ns' is not found. Please check your SAM/BAM file:" : !raw.has_ts ? "tag 'ts' is not found. Please check your SAM/BAM file:" :
                           !raw.has_mv ? "NULL returned for tag mv:" : !raw.mv_is_Bc ? "tag 'mv' specification is incorrect." : raw.mv_len == 0 ? "mv array length is 0:" : nullptr;
         if (!why) return 1;

@@ -25,6 +25,8 @@ constexpr uint32_t kDefaultStride = 5; // EXPECTED_STRIDE, src/reform.cpp:22
 struct Extra {
     bool rna = false;
     uint32_t stride = kDefaultStride; // the stride mv[0] has to hold; 0: whatever it holds, from 1 up (the gmove BAM path takes any)
+    bool both_strands = false;        // --to_ref --both_strands: reverse-strand records are written against RNAME + rc_suffix
+    std::string rc_suffix = "_rc";
 };
 
 const struct option kLongOptions[] = {
@@ -42,6 +44,8 @@ const struct option kLongOptions[] = {
     {"rna", no_argument, nullptr, 0},
     {"stride", required_argument, nullptr, 0},
     {"to_ref", no_argument, nullptr, 0},
+    {"both_strands", no_argument, nullptr, 0},
+    {"rc_suffix", required_argument, nullptr, 0},
     {nullptr, 0, nullptr, 0}};
 
 void usage(FILE *fp, uint32_t k, uint32_t m) {
@@ -61,6 +65,11 @@ void usage(FILE *fp, uint32_t k, uint32_t m) {
     fprintf(fp, "                              255, ss:Z: with N, / NI / ND (with --rna: the CIGAR in reverse order, target_start > target_end). Unmapped\n");
     fprintf(fp, "                              and reverse-strand records (flag 0x4, no RNAME, flag 0x10) are skipped and counted, secondary and\n");
     fprintf(fp, "                              supplementary ones (0x900) dropped; a read whose table or CIGAR is refused ends the run\n");
+    fprintf(fp, "   --both_strands             with --to_ref: reverse-strand records (flag 0x10) are written too, as forward records on the reverse\n");
+    fprintf(fp, "                              complement of their reference: strand -, target name RNAME + the suffix, target columns counted from the\n");
+    fprintf(fp, "                              other end (length - pos - ref_len). `gmove FILE.paf --fastq BOTH.fa` reads the file when BOTH.fa holds every\n");
+    fprintf(fp, "                              sequence and, under the suffixed name, its reverse complement. Needs the @SQ lengths\n");
+    fprintf(fp, "   --rc_suffix STR            with --both_strands: the suffix [_rc]\n");
 }
 
 // --to_ref: every record through the two rules the kernels compile (pg_mvops.h, pg_refops.h), on the host. 0, or 1 behind the message.
@@ -68,26 +77,27 @@ int to_ref(FILE *out, pgh::SamBamReader &rd, const Extra &x) {
     pgh::RawMoveRec raw;
     std::string bad;
     std::vector<uint32_t> ops, op_n; std::vector<uint8_t> seq, op_t;
-    uint64_t skipped = 0;
+    uint64_t skipped = 0, reverse_taken = 0;
     int got;
-    while ((got = pgh::next_move_record(rd, raw, "reform", bad, &skipped)) > 0) {
+    while ((got = pgh::next_move_record(rd, raw, "reform", bad, &skipped, x.both_strands ? &reverse_taken : nullptr)) > 0) {
         if (x.stride && raw.stride != (int)x.stride) { fprintf(stderr, "[reform::ERROR]\033[1;31m expected stride of %u is missing. Read_id: %s\033[0m\n", x.stride, raw.qname.c_str()); return 1; }
         const uint32_t L = raw.l_seq, nw = (uint32_t)raw.cigar.size();
         ops.assign((size_t)L + 1, 0); seq.resize((size_t)L + 1); op_n.resize((size_t)L + nw + 1); op_t.resize((size_t)L + nw + 1);
         uint32_t n_ops = 0; int32_t qs = 0;
         const uint32_t st = pg_mv_expand_host((const uint8_t *)raw.mv, raw.mv_len - 1, raw.stride, raw.ns, raw.ts, L, raw.packed, false, false, ops.data(), &n_ops, &qs, seq.data());
-        const PgRfHost h = pg_refops_host(ops.data(), n_ops, qs, st, raw.cigar.data(), nw, raw.pos, x.rna, op_n.data(), op_t.data());
+        const bool reverse = (raw.flag & 0x10u) != 0; // (taken with --both_strands only)
+        const PgRfHost h = pg_refops_host(ops.data(), n_ops, qs, st, raw.cigar.data(), nw, raw.pos, x.rna, op_n.data(), op_t.data(), reverse, pgh::contig_len_of(raw.ref_len));
         if (h.status) {
             fprintf(stderr, "%s\n", pgh::reform_error((std::string(pgh::to_ref_refusal(h.status)) + " (status " + std::to_string(h.status) + ")").c_str(), raw.qname).c_str());
             return 1;
         }
-        fprintf(out, "%s\t%" PRIu64 "\t%d\t%d\t+\t%s\t%" PRId64 "\t%d\t%d\t%" PRIu32 "\t%" PRIu32 "\t255\tss:Z:", raw.qname.c_str(), raw.ns, h.query_start, h.query_end,
-                raw.rname.c_str(), raw.ref_len, h.target_start, h.target_end, h.n_match, h.ref_len);
+        fprintf(out, "%s\t%" PRIu64 "\t%d\t%d\t%c\t%s%s\t%" PRId64 "\t%d\t%d\t%" PRIu32 "\t%" PRIu32 "\t255\tss:Z:", raw.qname.c_str(), raw.ns, h.query_start, h.query_end,
+                reverse ? '-' : '+', raw.rname.c_str(), reverse ? x.rc_suffix.c_str() : "", raw.ref_len, h.target_start, h.target_end, h.n_match, h.ref_len);
         for (uint32_t i = 0; i < h.n_ops; i++) fprintf(out, "%" PRIu32 "%c", op_n[i], ",ID"[op_t[i]]);
         fputc('\n', out);
     }
     if (got < 0) { fprintf(stderr, "%s\n", bad.c_str()); return 1; }
-    pgh::print_to_ref_skipped("reform", skipped);
+    if (x.both_strands) pgh::print_both_strands_skipped("reform", skipped, reverse_taken); else pgh::print_to_ref_skipped("reform", skipped);
     return 0;
 }
 
@@ -175,7 +185,7 @@ int reform_record(FILE *out, const pgh::MoveRec &r, uint32_t k, uint32_t m, bool
 
 int reform_main(int argc, char **argv) {
     uint32_t k = 9, m = 0; // init_opt, src/poregen.cpp:209-237
-    bool paf = false, help_to_stdout = false, to_ref_mode = false;
+    bool paf = false, help_to_stdout = false, to_ref_mode = false, have_rc_suffix = false;
     Extra extra;
     const char *out_path = nullptr;
     int c, longindex = 0;
@@ -191,6 +201,8 @@ int reform_main(int argc, char **argv) {
         else if (c == 'h') help_to_stdout = true;
         else if (c == 0 && !strcmp(kLongOptions[longindex].name, "rna")) extra.rna = true;
         else if (c == 0 && !strcmp(kLongOptions[longindex].name, "to_ref")) to_ref_mode = true;
+        else if (c == 0 && !strcmp(kLongOptions[longindex].name, "both_strands")) extra.both_strands = true;
+        else if (c == 0 && !strcmp(kLongOptions[longindex].name, "rc_suffix")) { extra.rc_suffix = optarg; have_rc_suffix = true; }
         else if (c == 0 && !strcmp(kLongOptions[longindex].name, "stride")) {
             if (atoi(optarg) < 0) { fail("Stride should not be negative."); exit(EXIT_FAILURE); }
             extra.stride = (uint32_t)atoi(optarg);
@@ -199,6 +211,8 @@ int reform_main(int argc, char **argv) {
     if (k < 1) return fail("kmer length must be a positive integer");
     if (k <= m) return fail("signal move offset value must less than the kmer length");
     if (to_ref_mode && !help_to_stdout && (!paf || k != 1 || m != 0)) { fail("--to_ref requires -c -k 1 -m 0"); usage(stderr, k, m); return EXIT_FAILURE; }
+    if (extra.both_strands && !to_ref_mode && !help_to_stdout) { fail("--both_strands applies with --to_ref only"); usage(stderr, k, m); return EXIT_FAILURE; }
+    if (have_rc_suffix && !extra.both_strands && !help_to_stdout) { fail("--rc_suffix applies with --both_strands only"); usage(stderr, k, m); return EXIT_FAILURE; }
     if (argc - optind != 1 || help_to_stdout) {
         fail("not enough arguments");
         usage(help_to_stdout ? stdout : stderr, k, m);

@@ -513,6 +513,28 @@ extern "C" void pgt_refops(const uint32_t *o, uint32_t L, int32_t query_start, u
     const PgRfHost h = pg_refops_host(o, L, query_start, status_in, cigar, n_words, pos, rna != 0, op_n, op_t);
     out8[0] = h.status; out8[1] = h.n_ops; out8[2] = h.ref_len; out8[3] = h.n_match; out8[4] = h.query_start; out8[5] = h.query_end; out8[6] = h.target_start; out8[7] = h.target_end;
 }
+// the same with the record's strand: reverse (flag 0x10) and the length of its contig
+extern "C" void pgt_refops_strand(const uint32_t *o, uint32_t L, int32_t query_start, uint32_t status_in, const uint32_t *cigar, uint32_t n_words, int32_t pos, int rna,
+                                  int reverse, int32_t contig_len, uint32_t *op_n, uint8_t *op_t, int64_t *out8) {
+    const PgRfHost h = pg_refops_host(o, L, query_start, status_in, cigar, n_words, pos, rna != 0, op_n, op_t, reverse != 0, contig_len);
+    out8[0] = h.status; out8[1] = h.n_ops; out8[2] = h.ref_len; out8[3] = h.n_match; out8[4] = h.query_start; out8[5] = h.query_end; out8[6] = h.target_start; out8[7] = h.target_end;
+}
+
+// ---- reference slices (pg_refseq.h): the clamp and the complement the kernels of pg_refseq.hip compile, run on the host -----------------
+#include "pg_refseq.h"
+// out2: the first base and the number of bases of the slice; contig_len < 0: no such contig
+extern "C" void pgt_refseq_clamp(int32_t pos, uint32_t ref_len, int64_t contig_len, int64_t *out2) {
+    const PgRsSpan sp = pg_rs_clamp(pos, ref_len, contig_len);
+    out2[0] = sp.beg; out2[1] = sp.n;
+}
+extern "C" void pgt_refseq_complement(const uint8_t *in, uint8_t *out, uint64_t n) { for (uint64_t i = 0; i < n; i++) out[i] = pg_rs_complement(in[i]); }
+// one read's slice of `contig`, as the copy kernel writes it; returns its length, or -1 where it would leave the contig or `cap`
+extern "C" long pgt_refseq_slice(const uint8_t *contig, int64_t contig_len, int32_t pos, uint32_t ref_len, int reverse, uint8_t *out, uint64_t cap) {
+    const PgRsSpan sp = pg_rs_clamp(pos, ref_len, contig_len);
+    if (sp.n && (sp.beg < 0 || sp.beg + sp.n > contig_len || (uint64_t)sp.n > cap)) return -1;
+    for (int64_t k = 0; k < sp.n; k++) out[k] = reverse ? pg_rs_complement(contig[sp.beg + sp.n - 1 - k]) : contig[sp.beg + k];
+    return (long)sp.n;
+}
 
 // ---- the dump-text parser (pg_dumptext.h): the geometry of its kernels and the field rule they compile, run on the host ----------------
 #include "pg_dumptext.h"

@@ -22,8 +22,8 @@ struct pg_mvops {
     // the result -- none of them shared with the expansion, whose result a projection reads in place
     PgDev<uint32_t> r_cigar, r_pfirst, r_pread, r_pre, r_read, r_psum, r_opn, r_status;
     PgDev<uint64_t> r_cgoff, r_opoff, r_totals;
-    PgDev<int32_t> r_pos, r_scal;
-    PgDev<uint8_t> r_opt;
+    PgDev<int32_t> r_pos, r_scal, r_clen;
+    PgDev<uint8_t> r_opt, r_rev;
     PgPinned<uint8_t> r_back;
     std::vector<uint64_t> r_cgoff_h, r_opoff_h;
     std::vector<uint32_t> r_pfirst_h, r_pread_h, r_status_h, r_reflen_h, r_nmatch_h;

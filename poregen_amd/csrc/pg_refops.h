@@ -15,6 +15,12 @@
 // the match ops, query_end = the new query_start + every value written as a match or an I. A read the expansion refused keeps its
 // status; then: no word 5, the M/I/S/=/X lengths do not come to L 6, an op code above 8 7 -- the first of these decides. A refused
 // read has no ops, ref_len, n_match and the target columns 0, and its query_start (= query_end) as it came.
+//
+// A reverse-strand record (flag 0x10) is a forward record on the reverse complement of its contig: its stored SEQ and its CIGAR are in
+// reference order, so signal-order op j belongs to base L - 1 - j of SEQ (with rna: to base j), and the words are taken in reverse order
+// iff rna != reverse (pg_rf_backwards). Its target columns are those of the mirrored contig: pos' = contig_len - pos - ref_len (uint32,
+// cast to int32) stands where pos stood. A reverse read whose contig_len is not known (<= 0: no @SQ line, or a length above 2^31 - 1)
+// gets status 8, behind the seven above. Clips, I sums, D / N, query_start / query_end, n_match and ref_len keep their rules.
 #pragma once
 #include <stdint.h>
 #include "pg_mvops.h"
@@ -24,7 +30,8 @@
 enum { // = PG_MVOPS_ST_* of include/pgmove.h, behind the expansion's
     PG_REFOPS_ST_NO_CIGAR = 5,
     PG_REFOPS_ST_LENGTH = 6,
-    PG_REFOPS_ST_BAD_OP = 7
+    PG_REFOPS_ST_BAD_OP = 7,
+    PG_REFOPS_ST_NO_CONTIG_LEN = 8
 };
 enum { PG_RF_M = 0, PG_RF_I = 1, PG_RF_D = 2, PG_RF_N = 3, PG_RF_S = 4, PG_RF_H = 5, PG_RF_P = 6, PG_RF_EQ = 7, PG_RF_X = 8 };
 
@@ -47,6 +54,8 @@ PG_RF_HD uint32_t pg_rf_ops(uint32_t w) { return pg_rf_matches(w) + (pg_rf_in(PG
 PG_RF_HD bool pg_rf_anchor(uint32_t w) { return pg_rf_in(PG_RF_SET_ANCHOR, w) && pg_rf_len(w) != 0; }
 // word i of the walk, of the n words at p
 PG_RF_HD uint32_t pg_rf_word(const uint32_t *p, uint32_t n, uint32_t i, bool rna) { return p[rna ? n - 1u - i : i]; }
+// whether the walk takes the words in reverse order: RNA is sequenced 3' first, a reverse-strand record is stored reversed
+PG_RF_HD bool pg_rf_backwards(bool rna, bool reverse) { return rna != reverse; }
 
 // What a read comes to, from the sums of the count pass: the words, the bases they use (64 bits: the lengths of a bad CIGAR may come
 // to more than 2^32), whether an op code above 8 was met, the ops they write, ref_len and n_match.
@@ -55,12 +64,13 @@ struct PgRfRead {
     int32_t target_start, target_end;
 };
 PG_RF_HD PgRfRead pg_rf_read(uint32_t status_in, uint32_t L, uint32_t n_words, uint64_t query_sum, bool bad_op, uint32_t n_ops, uint32_t ref_len, uint32_t n_match,
-                             int32_t pos, bool rna) {
+                             int32_t pos, bool rna, bool reverse = false, int32_t contig_len = 0) {
     PgRfRead o; o.n_ops = 0; o.ref_len = 0; o.n_match = 0; o.target_start = 0; o.target_end = 0;
     o.status = status_in != PG_MVOPS_ST_OK ? status_in : n_words == 0 ? (uint32_t)PG_REFOPS_ST_NO_CIGAR : query_sum != (uint64_t)L ? (uint32_t)PG_REFOPS_ST_LENGTH :
-               bad_op ? (uint32_t)PG_REFOPS_ST_BAD_OP : (uint32_t)PG_MVOPS_ST_OK;
+               bad_op ? (uint32_t)PG_REFOPS_ST_BAD_OP : reverse && contig_len <= 0 ? (uint32_t)PG_REFOPS_ST_NO_CONTIG_LEN : (uint32_t)PG_MVOPS_ST_OK;
     if (o.status != PG_MVOPS_ST_OK) return o;
     o.n_ops = n_ops; o.ref_len = ref_len; o.n_match = n_match;
+    if (reverse) pos = (int32_t)((uint32_t)contig_len - (uint32_t)pos - ref_len); // the read's place on the mirrored contig
     const int32_t end = (int32_t)((uint32_t)pos + ref_len);
     o.target_start = rna ? end : pos; o.target_end = rna ? pos : end;
     return o;
@@ -73,19 +83,19 @@ struct PgRfHost {
     int32_t query_start, query_end, target_start, target_end;
 };
 static inline PgRfHost pg_refops_host(const uint32_t *o, uint32_t L, int32_t query_start, uint32_t status_in, const uint32_t *cigar, uint32_t n_words, int32_t pos,
-                                      bool rna, uint32_t *op_n, uint8_t *op_t) {
+                                      bool rna, uint32_t *op_n, uint8_t *op_t, bool reverse = false, int32_t contig_len = 0) {
     uint64_t query_sum = 0; uint32_t n_ops = 0, ref_len = 0, n_match = 0; bool bad = false;
     for (uint32_t i = 0; i < n_words; i++) {
         const uint32_t w = cigar[i];
         query_sum += pg_rf_query(w); n_ops += pg_rf_ops(w); ref_len += pg_rf_ref(w); n_match += pg_rf_matches(w); bad = bad || pg_rf_op(w) > 8u;
     }
-    const PgRfRead rd = pg_rf_read(status_in, L, n_words, query_sum, bad, n_ops, ref_len, n_match, pos, rna);
+    const PgRfRead rd = pg_rf_read(status_in, L, n_words, query_sum, bad, n_ops, ref_len, n_match, pos, rna, reverse, contig_len);
     PgRfHost h; h.status = rd.status; h.n_ops = rd.n_ops; h.ref_len = rd.ref_len; h.n_match = rd.n_match; h.target_start = rd.target_start; h.target_end = rd.target_end;
     h.query_start = h.query_end = query_start;
     if (rd.status != PG_MVOPS_ST_OK) return h;
     uint32_t q = 0, k = 0, lead = 0, body = 0; bool anchored = false;
     for (uint32_t i = 0; i < n_words; i++) {
-        const uint32_t w = pg_rf_word(cigar, n_words, i, rna), len = pg_rf_len(w), op = pg_rf_op(w);
+        const uint32_t w = pg_rf_word(cigar, n_words, i, pg_rf_backwards(rna, reverse)), len = pg_rf_len(w), op = pg_rf_op(w);
         if (!len) continue;
         anchored = anchored || pg_rf_anchor(w);
         if (pg_rf_in(PG_RF_SET_MATCH, w)) for (uint32_t j = 0; j < len; j++) { op_n[k] = o[q + j]; op_t[k++] = 0; body += o[q + j]; }

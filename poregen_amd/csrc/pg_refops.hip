@@ -4,7 +4,8 @@
 //
 // A read's CIGAR is a handful of words for a clean read (one word `200000M`) and one word per ten bases at 5 % edits; the ops it copies
 // are as many as the read has bases. One wave (= one workgroup) everywhere but in the offset scan:
-//   k_cg_scan    : per read, the words in steps of 64, one per lane, in the order of the walk (reversed with rna): wave scans give every
+//   k_cg_scan    : per read, the words in steps of 64, one per lane, in the order of the walk (reversed iff rna != the read's strand,
+//                  pg_rf_backwards: one byte per read, the same for the whole wave): wave scans give every
 //                  word its exclusive prefix of bases used and of ops written (a carry goes from step to step), kept in a work buffer of
 //                  n_words + 1 entries per read; the totals give the read's status, op count, ref_len, n_match, target columns and the
 //                  word that ends the leading clip (pg_rf_read)
@@ -18,7 +19,8 @@
 //                  written are summed per piece
 //   k_cg_ends    : per read (one thread), the pieces' sums -> query_start, query_end
 // Nothing is handed from workgroup to workgroup inside a launch. No load leaves an input array (a read's words, its ops), no store a
-// read's span of ops; op_t is written beside op_n.
+// read's span of ops; op_t is written beside op_n. pg_mvops_project_stranded adds two per-read inputs, reverse and contig_len, read by
+// k_cg_scan (status 8, the mirrored target columns) and, reverse alone, by k_cg_emit; without them (pg_mvops_project) neither is touched.
 #include "../../include/pgmove.h"
 #include <hip/hip_runtime.h>
 #include "pg_refops.h"
@@ -42,6 +44,8 @@ struct CgBatch {
     const uint32_t *cigar;
     const uint64_t *cigar_off;   // n_reads + 1
     const int32_t *pos;
+    const uint8_t *reverse;      // per read, or null: every read forward (pg_mvops_project)
+    const int32_t *contig_len;   // per read, with reverse
     const uint32_t *piece_first; // n_reads + 1: the first piece of every read
     const uint32_t *piece_read;  // n_pieces
     uint32_t n_reads, n_pieces, rna;
@@ -60,6 +64,9 @@ struct CgOut {
     uint64_t *totals;            // n_ops
 };
 
+// whether read r is a reverse-strand record: one byte, the same for every lane of the wave that serves the read or a piece of it
+__device__ __forceinline__ bool cg_reverse(const CgBatch &B, uint32_t r) { return B.reverse != nullptr && B.reverse[r] != 0; }
+
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
@@ -70,6 +77,7 @@ __global__ __launch_bounds__(kWave) void k_cg_scan(const CgBatch B, const CgWork
     const uint64_t c0 = B.cigar_off[r];
     const uint32_t nw = (uint32_t)(B.cigar_off[r + 1] - c0), L = (uint32_t)(B.in_off[r + 1] - B.in_off[r]);
     const uint32_t *__restrict__ words = B.cigar + c0;
+    const bool reverse = cg_reverse(B, r), back = pg_rf_backwards(B.rna != 0, reverse); // (uniform)
     uint32_t *__restrict__ qpre = W.qpre + c0 + r, *__restrict__ opre = W.opre + c0 + r;
     uint64_t carry_q = 0;
     uint32_t carry_o = 0, ref_len = 0, n_match = 0, lead_word = nw;
@@ -77,7 +85,7 @@ __global__ __launch_bounds__(kWave) void k_cg_scan(const CgBatch B, const CgWork
     for (uint32_t i0 = 0; i0 < nw; i0 += kWave) {                      // (uniform: the scans need every lane)
         const uint32_t i = i0 + lane;
         const bool valid = i < nw;
-        const uint32_t w = valid ? pg_rf_word(words, nw, i, B.rna != 0) : 0u;
+        const uint32_t w = valid ? pg_rf_word(words, nw, i, back) : 0u;
         const uint32_t qb = pg_rf_query(w), no = pg_rf_ops(w);
         const uint64_t iq = wave_incl_scan_u64(qb);
         const uint32_t io = wave_incl_scan_u32(no);
@@ -90,7 +98,7 @@ __global__ __launch_bounds__(kWave) void k_cg_scan(const CgBatch B, const CgWork
     }
     if (lane != 0) return;
     qpre[nw] = (uint32_t)carry_q; opre[nw] = carry_o;
-    const PgRfRead o = pg_rf_read(B.in_status[r], L, nw, carry_q, bad, carry_o, ref_len, n_match, B.pos[r], B.rna != 0);
+    const PgRfRead o = pg_rf_read(B.in_status[r], L, nw, carry_q, bad, carry_o, ref_len, n_match, B.pos[r], B.rna != 0, reverse, reverse ? B.contig_len[r] : 0);
     O.status[r] = o.status; O.t0[r] = o.target_start; O.t1[r] = o.target_end;
     W.n_ops[r] = o.n_ops; W.ref_len[r] = o.ref_len; W.n_match[r] = o.n_match; W.lead_word[r] = lead_word;
 }
@@ -117,6 +125,7 @@ __global__ __launch_bounds__(kWave) void k_cg_emit(const CgBatch B, const CgWork
     const uint64_t c0 = B.cigar_off[r];
     const uint32_t nw = (uint32_t)(B.cigar_off[r + 1] - c0), L = (uint32_t)(B.in_off[r + 1] - B.in_off[r]);
     const uint32_t *__restrict__ words = B.cigar + c0;
+    const bool back = pg_rf_backwards(B.rna != 0, cg_reverse(B, r));    // (uniform)
     const uint32_t *__restrict__ qpre = W.qpre + c0 + r, *__restrict__ opre = W.opre + c0 + r; // nw + 1 entries each
     const uint32_t *__restrict__ in = B.in_op + B.in_off[r];
     uint32_t *__restrict__ out_n = O.op_n + O.op_off[r];
@@ -133,7 +142,7 @@ __global__ __launch_bounds__(kWave) void k_cg_emit(const CgBatch B, const CgWork
         if (!(wq0 < q1 || last)) break;                                 // the word starts in a later piece, and so does every word behind it
         const uint32_t wi = w0 + lane, nwc = min((uint32_t)kWave, nw - w0);
         const bool have = lane < nwc;
-        const uint32_t w = have ? pg_rf_word(words, nw, wi, B.rna != 0) : 0u;
+        const uint32_t w = have ? pg_rf_word(words, nw, wi, back) : 0u;
         const uint32_t wq = have ? qpre[wi] : 0xffffffffu, wo = have ? opre[wi] : 0u, len = pg_rf_len(w), op = pg_rf_op(w);
         const bool mine = have && len != 0 && wq >= q0 && (wq < q1 || last); // the word starts in this piece: its one op is this piece's
         // ---- one op per word: D and N, short I by the lane, long I by the wave
@@ -190,7 +199,9 @@ __global__ __launch_bounds__(kReadThreads) void k_cg_ends(const CgBatch B, const
 
 } // namespace
 
-extern "C" pg_status pg_mvops_project(pg_mvops *h, const pg_mvops_cigars *c, pg_mvops_projection *out) {
+extern "C" pg_status pg_mvops_project(pg_mvops *h, const pg_mvops_cigars *c, pg_mvops_projection *out) { return pg_mvops_project_stranded(h, c, nullptr, out); }
+
+extern "C" pg_status pg_mvops_project_stranded(pg_mvops *h, const pg_mvops_cigars *c, const pg_mvops_strands *st, pg_mvops_projection *out) {
     if (!h) return pg_fail<pg_mvops>(nullptr, PG_ERR_INVALID_ARG, "pg_mvops_project: null handle");
     if (!c || !out) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_mvops_project: null argument");
     memset(out, 0, sizeof *out);
@@ -200,12 +211,15 @@ extern "C" pg_status pg_mvops_project(pg_mvops *h, const pg_mvops_cigars *c, pg_
     if (n >= (1ull << 31)) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_mvops_project: %llu reads in one batch (at most 2^31 - 1)", (unsigned long long)n);
     if (!c->op_off || !c->cigar_off || (n && (!c->query_start || !c->status || !c->pos)) || (c->n_ops && !c->op_n) || (c->n_cigar && !c->cigar))
         return pg_fail(h, PG_ERR_INVALID_ARG, "pg_mvops_project: null array");
+    if (st && !st->reverse != !st->contig_len) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_mvops_project_stranded: reverse and contig_len go together");
+    const bool stranded = st && st->reverse && n; // (no reads: nothing to look at)
     PG_HIP_TRY(h, hipSetDevice(h->device));
     const hipStream_t s = h->s;
     const bool dev = c->location == PG_LOC_DEVICE;
     {
         const void *must[] = {c->op_off, n ? (const void *)c->query_start : nullptr, n ? (const void *)c->status : nullptr, c->n_ops ? (const void *)c->op_n : nullptr,
-                              dev ? (const void *)c->cigar_off : nullptr, dev && n ? (const void *)c->pos : nullptr, dev && c->n_cigar ? (const void *)c->cigar : nullptr};
+                              dev ? (const void *)c->cigar_off : nullptr, dev && n ? (const void *)c->pos : nullptr, dev && c->n_cigar ? (const void *)c->cigar : nullptr,
+                              dev && stranded ? (const void *)st->reverse : nullptr, dev && stranded ? (const void *)st->contig_len : nullptr};
         for (const void *q : must)
             if (q && pg_ptr_kind(q, h->device) != PG_PTR_DEVICE)
                 return pg_fail(h, PG_ERR_INVALID_ARG, "pg_mvops_project: the op arrays, and PG_LOC_DEVICE CIGAR arrays, must be device memory of device %d", h->device);
@@ -242,7 +256,7 @@ extern "C" pg_status pg_mvops_project(pg_mvops *h, const pg_mvops_cigars *c, pg_
     B.in_op = c->op_n; B.in_off = c->op_off; B.in_qs = c->query_start; B.in_status = c->status;
     auto room = [](size_t bytes) { return bytes + bytes / 4 + 256; };
 #define RF_ENSURE(buf, bytes) PG_HIP_TRY(h, (buf).ensure((bytes) ? (bytes) : 1, room(bytes)))
-    if (dev) { B.cigar = c->cigar; B.cigar_off = c->cigar_off; B.pos = c->pos; }
+    if (dev) { B.cigar = c->cigar; B.cigar_off = c->cigar_off; B.pos = c->pos; if (stranded) { B.reverse = st->reverse; B.contig_len = st->contig_len; } }
     else {
         RF_ENSURE(h->r_cigar, cg_end * sizeof(uint32_t)); RF_ENSURE(h->r_cgoff, (n + 1) * sizeof(uint64_t)); RF_ENSURE(h->r_pos, n * sizeof(int32_t));
         // the words keep their offsets (nothing in front of cigar_off[0] is copied)
@@ -250,6 +264,12 @@ extern "C" pg_status pg_mvops_project(pg_mvops *h, const pg_mvops_cigars *c, pg_
         PG_HIP_TRY(h, hipMemcpyAsync(h->r_cgoff.p, c->cigar_off, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
         if (n) PG_HIP_TRY(h, hipMemcpyAsync(h->r_pos.p, c->pos, n * sizeof(int32_t), hipMemcpyHostToDevice, s));
         B.cigar = h->r_cigar.p; B.cigar_off = h->r_cgoff.p; B.pos = h->r_pos.p;
+        if (stranded) { // beside pos
+            RF_ENSURE(h->r_rev, n); RF_ENSURE(h->r_clen, n * sizeof(int32_t));
+            PG_HIP_TRY(h, hipMemcpyAsync(h->r_rev.p, st->reverse, n, hipMemcpyHostToDevice, s));
+            PG_HIP_TRY(h, hipMemcpyAsync(h->r_clen.p, st->contig_len, n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            B.reverse = h->r_rev.p; B.contig_len = h->r_clen.p;
+        }
     }
     RF_ENSURE(h->r_pfirst, (n + 1) * sizeof(uint32_t)); RF_ENSURE(h->r_pread, n_pieces * sizeof(uint32_t));
     RF_ENSURE(h->r_pre, 2 * n_pre * sizeof(uint32_t)); RF_ENSURE(h->r_read, 4 * n * sizeof(uint32_t)); RF_ENSURE(h->r_psum, 2 * n_pieces * sizeof(uint32_t));

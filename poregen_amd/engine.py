@@ -1723,10 +1723,14 @@ class MoveExpander:
             raise PgError(st, self._lib.pg_mvops_last_error(self._h).decode())
         return MoveOps(res, self.device)
 
-    def project(self, ops, cigar, cigar_off, pos, rna: bool = False) -> RefOps:
+    def project(self, ops, cigar, cigar_off, pos, rna: bool = False, reverse=None, contig_len=None) -> RefOps:
         """Carries ops through the records' CIGARs onto the reference (pg_mvops_project). ops: a MoveOps (read in place), or a tuple of
         CUDA tensors (op_n, op_off, query_start, status) of 4, 8, 4 and 4-byte integers. cigar (uint32 words len << 4 | op), cigar_off
-        (uint64[n + 1]) and pos (int32[n], 0-based) are three numpy arrays or three contiguous CUDA tensors of the same widths."""
+        (uint64[n + 1]) and pos (int32[n], 0-based) are three numpy arrays or three contiguous CUDA tensors of the same widths.
+        reverse (uint8[n], non-zero: a reverse-strand record) and contig_len (int32[n]), given together and lying where the CIGAR arrays
+        lie, make it pg_mvops_project_stranded: a reverse read is placed on the reverse complement of its contig."""
+        if (reverse is None) != (contig_len is None):
+            raise ValueError("project: reverse and contig_len go together")
         op_n, op_off, qs, status = (ops.op_n, ops.op_off, ops.query_start, ops.status_device) if isinstance(ops, MoveOps) else ops
         for a, size, name in ((op_n, 4, "op_n"), (op_off, 8, "op_off"), (qs, 4, "query_start"), (status, 4, "status")):
             if not (hasattr(a, "is_cuda") and a.is_cuda) or a.dtype.itemsize != size or not a.is_contiguous():
@@ -1734,8 +1738,8 @@ class MoveExpander:
         n = op_off.numel() - 1
         if n < 0 or qs.numel() != n or status.numel() != n:
             raise ValueError("project: op_off needs n + 1 entries, query_start and status one per read")
-        given = (cigar, cigar_off, pos)
-        widths = (("cigar", 4, np.uint32), ("cigar_off", 8, np.uint64), ("pos", 4, np.int32))
+        given = (cigar, cigar_off, pos) + (() if reverse is None else (reverse, contig_len))
+        widths = (("cigar", 4, np.uint32), ("cigar_off", 8, np.uint64), ("pos", 4, np.int32), ("reverse", 1, np.uint8), ("contig_len", 4, np.int32))
         on_dev = [hasattr(a, "is_cuda") and a.is_cuda for a in given]
         c = _abi.PgMvopsCigars()
         if all(on_dev):
@@ -1747,21 +1751,26 @@ class MoveExpander:
             sizes = [a.numel() for a in given]
             c.location = _abi.PG_LOC_DEVICE
         elif any(on_dev):
-            raise ValueError("project takes three host arrays or three device tensors of CIGARs, not a mixture")
+            raise ValueError("project takes host arrays or device tensors of CIGARs (and strands), not a mixture")
         else:
             keep = [np.ascontiguousarray(a, dtype=dt) for a, (_, _, dt) in zip(given, widths)]
             ptrs = [C.c_void_p(a.ctypes.data) if a.size else None for a in keep]
             sizes = [a.size for a in keep]
             c.location = _abi.PG_LOC_HOST
-        if sizes[1] != n + 1 or sizes[2] != n:
-            raise ValueError("project: cigar_off needs n + 1 entries, pos one per read")
+        if sizes[1] != n + 1 or any(x != n for x in sizes[2:]):
+            raise ValueError("project: cigar_off needs n + 1 entries, pos (reverse, contig_len) one per read")
         c.n_reads, c.flags = n, (_abi.PG_MVOPS_RNA if rna else 0)
         c.op_n, c.n_ops, c.op_off = (C.c_void_p(op_n.data_ptr()) if op_n.numel() else None), op_n.numel(), C.c_void_p(op_off.data_ptr())
         c.query_start, c.status = (C.c_void_p(qs.data_ptr()) if n else None), (C.c_void_p(status.data_ptr()) if n else None)
-        c.cigar, c.cigar_off, c.pos = ptrs
+        c.cigar, c.cigar_off, c.pos = ptrs[:3]
         c.n_cigar = sizes[0]
         res = _abi.PgMvopsProjection()
-        st = self._lib.pg_mvops_project(self._h, C.byref(c), C.byref(res))
+        if reverse is None:
+            st = self._lib.pg_mvops_project(self._h, C.byref(c), C.byref(res))
+        else:
+            strands = _abi.PgMvopsStrands()
+            strands.reverse, strands.contig_len = ptrs[3:]
+            st = self._lib.pg_mvops_project_stranded(self._h, C.byref(c), C.byref(strands), C.byref(res))
         del keep
         if st != 0:
             raise PgError(st, self._lib.pg_mvops_last_error(self._h).decode())
@@ -1791,21 +1800,133 @@ def reform_ops(mv, mv_off, stride, ns, ts, l_seq, flag, seq_bytes, byte_off, rna
         ex.close()
 
 
-def project_ops(op_n, op_off, query_start, status, cigar, cigar_off, pos, rna: bool = False, device: int = 0):
-    """One-shot MoveExpander.project of host arrays (op_n uint32, op_off uint64[n + 1], query_start int32[n], status uint32[n], and the
-    CIGAR arrays): the result's arrays on the host (RefOps.to_host) plus n_ops, n_refused and first_refused."""
+def project_ops(op_n, op_off, query_start, status, cigar, cigar_off, pos, rna: bool = False, device: int = 0, reverse=None, contig_len=None):
+    """One-shot MoveExpander.project of host arrays (op_n uint32, op_off uint64[n + 1], query_start int32[n], status uint32[n], the
+    CIGAR arrays and, for records of either strand, reverse and contig_len): the result's arrays on the host (RefOps.to_host) plus n_ops,
+    n_refused and first_refused."""
     import torch
     ex = MoveExpander(device)
     try:
         dev = torch.device("cuda", device)
         up = [torch.from_numpy(np.ascontiguousarray(a, dtype=dt).view(vt)).to(dev)
               for a, dt, vt in ((op_n, np.uint32, np.int32), (op_off, np.uint64, np.int64), (query_start, np.int32, np.int32), (status, np.uint32, np.int32))]
-        r = ex.project(tuple(up), cigar, cigar_off, pos, rna=rna)
+        r = ex.project(tuple(up), cigar, cigar_off, pos, rna=rna, reverse=reverse, contig_len=contig_len)
         out = r.to_host()
         out.update(n_ops=r.n_ops, n_refused=r.n_refused, first_refused=r.first_refused)
         return out
     finally:
         ex.close()
+
+
+# ---- refseq: the reference slices of mapped reads, gathered on the device (pg_refseq_*) ------------------------------------------------
+
+class RefSlices:
+    """The result of RefSeq.slices: seq (uint8) and seq_off (int64[n + 1]) as CUDA tensors that alias the handle's device buffers (valid
+    until its next slices / close), laid out as a pg_batch takes them, and n_seq."""
+
+    def __init__(self, res, n, device):
+        import torch
+
+        class _Alias:  # zero-copy hand-over through the CUDA array interface
+            def __init__(self, ptr, n, typestr):
+                self.__cuda_array_interface__ = {"shape": (int(n),), "typestr": typestr, "data": (int(ptr or 0), False), "version": 2}
+
+        dev = torch.device("cuda", device)
+        self.n_reads, self.n_seq = int(n), int(res.n_seq)
+        self.seq = torch.as_tensor(_Alias(res.seq, self.n_seq, "|u1"), device=dev) if self.n_seq else torch.empty(0, dtype=torch.uint8, device=dev)
+        self.seq_off = torch.as_tensor(_Alias(res.seq_off, n + 1, "<i8"), device=dev)
+
+    def to_host(self):
+        """[bytes] per read."""
+        seq, off = self.seq.cpu().numpy().tobytes(), self.seq_off.cpu().numpy()
+        return [seq[int(off[r]):int(off[r + 1])] for r in range(self.n_reads)]
+
+
+class RefSeq:
+    """Reference contigs on the device, added one by one, and the slices mapped reads take of them (pg_refseq_*): what `gmove --reform
+    --ref` fetches per read, reversed and complemented for a reverse-strand read."""
+
+    def __init__(self, device: int = 0):
+        self._lib = _abi.load()
+        self.device = device
+        h = C.c_void_p()
+        st = self._lib.pg_refseq_create(device, C.byref(h))
+        if st != 0:
+            raise PgError(st, self._lib.pg_refseq_last_error(None).decode())
+        self._h = h
+
+    def set_stream(self, stream=None):
+        """Run on a caller-owned stream (a torch.cuda.Stream or a raw hipStream_t value); None: the handle's own."""
+        ptr = None if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
+        st = self._lib.pg_refseq_set_stream(self._h, ptr)
+        if st != 0:
+            raise PgError(st, self._lib.pg_refseq_last_error(self._h).decode())
+
+    def add(self, bases) -> int:
+        """A contig's bases (bytes, line ends removed); returns the index reads name it by."""
+        b = bytes(bases)
+        idx = C.c_int32(-1)
+        st = self._lib.pg_refseq_add(self._h, C.cast(C.c_char_p(b), C.c_void_p) if b else None, len(b), C.byref(idx))
+        if st != 0:
+            raise PgError(st, self._lib.pg_refseq_last_error(self._h).decode())
+        return int(idx.value)
+
+    def slices(self, contig, pos, ref_len, reverse=None) -> RefSlices:
+        """contig (int32[n], -1: no such contig), pos (int32[n]), ref_len (uint32[n]) and reverse (uint8[n] or None): numpy arrays, or
+        contiguous CUDA tensors of the same widths."""
+        given = (contig, pos, ref_len) + (() if reverse is None else (reverse,))
+        widths = (("contig", 4, np.int32), ("pos", 4, np.int32), ("ref_len", 4, np.uint32), ("reverse", 1, np.uint8))
+        on_dev = [hasattr(a, "is_cuda") and a.is_cuda for a in given]
+        rd = _abi.PgRefseqReads()
+        if all(on_dev):
+            for a, (name, size, _) in zip(given, widths):
+                if a.dtype.itemsize != size or not a.is_contiguous():
+                    raise ValueError(f"device reads: {name} must be a contiguous tensor of {size}-byte integers")
+            keep = given
+            ptrs = [C.c_void_p(a.data_ptr()) if a.numel() else None for a in given]
+            sizes = [a.numel() for a in given]
+            rd.location = _abi.PG_LOC_DEVICE
+        elif any(on_dev):
+            raise ValueError("slices takes host arrays or device tensors, not a mixture")
+        else:
+            keep = [np.ascontiguousarray(a, dtype=dt) for a, (_, _, dt) in zip(given, widths)]
+            ptrs = [C.c_void_p(a.ctypes.data) if a.size else None for a in keep]
+            sizes = [a.size for a in keep]
+            rd.location = _abi.PG_LOC_HOST
+        n = sizes[0]
+        if any(x != n for x in sizes):
+            raise ValueError("slices: contig, pos, ref_len (and reverse) hold one entry per read")
+        rd.n_reads = n
+        rd.contig, rd.pos, rd.ref_len = ptrs[:3]
+        rd.reverse = ptrs[3] if reverse is not None else None
+        res = _abi.PgRefseqSlices()
+        st = self._lib.pg_refseq_slice(self._h, C.byref(rd), C.byref(res))
+        del keep
+        if st != 0:
+            raise PgError(st, self._lib.pg_refseq_last_error(self._h).decode())
+        return RefSlices(res, n, self.device)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.pg_refseq_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ref_slices(contigs, contig, pos, ref_len, reverse=None, device: int = 0):
+    """One-shot RefSeq: contigs (a list of bytes) go up in order, so `contig` indexes the list; returns the slices as a list of bytes."""
+    rs = RefSeq(device)
+    try:
+        for c in contigs:
+            rs.add(c)
+        return rs.slices(contig, pos, ref_len, reverse).to_host()
+    finally:
+        rs.close()
 
 
 # ---- fit: a k-mer model scored against signal and move tables (pg_fit_*) --------------------------------------------------------------

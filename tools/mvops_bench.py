@@ -14,6 +14,15 @@
            and the wall time, best of --reps after one warm-up. Bytes per second over 4 B read plus 5 B written per output op plus, per
            CIGAR word, its 4 B and its two 4-byte prefixes written once and read once; beside it the best plain streaming read of
            tools/probe/stream_probe.hip in the same run. One box, one run: a first look, not a bound -- no counters were read.
+  strands  (--ref --strands) pg_mvops_project_stranded beside pg_mvops_project on the same device batch -- every read forward, and every
+           second read reversed -- as HIP-event times on the expander's stream, best of --reps after one warm-up, every repeat kept (their
+           spread is the noise floor of the box). With --lib PATH the library at PATH is loaded instead; one that lacks the stranded entry
+           point (the parent commit's, `make variant`) is timed on pg_mvops_project alone: run the two alternating, tools/ab_lib.sh style.
+           Then pg_refseq_slice: the slices of the same reads (ref_len from the projection, every second read reversed) cut from
+           contigs in HBM, device arrays in, HIP-event and wall time per call and bytes of slice per second over them -- the KERNEL time
+           is rocprofv3's, from a run of its own -- beside what today's host loop does for the same reads: per read a slice of the contig
+           appended to one buffer (numpy on the host here; the product's is FastxIndex::fetch + vector::insert), then one upload and a
+           synchronise, on the host clock.
 Prints one JSON object and writes it to --out.
 """
 import argparse
@@ -148,6 +157,90 @@ def bench_ref(name, lengths, rate, reps):
     return out
 
 
+def _event_timed(stream, fn):
+    import torch
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    e0.record(stream)
+    r = fn()
+    e1.record(stream)
+    e1.synchronize()
+    return r, (time.perf_counter() - t0) * 1e3, e0.elapsed_time(e1)
+
+
+def bench_strands(name, lengths, rate, reps):
+    import torch
+    from poregen_amd.engine import MoveExpander
+    a = tables(lengths)
+    t = {k: torch.from_numpy(v).cuda() for k, v in a.items()}
+    cg, cg_off, pos = cigars(a["l_seq"], rate)
+    n = len(lengths)
+    d_cg, d_off, d_pos = torch.from_numpy(cg.view(np.int32)).cuda(), torch.from_numpy(cg_off.view(np.int64)).cuda(), torch.from_numpy(pos).cuda()
+    fwd, half = torch.zeros(n, dtype=torch.uint8).cuda(), torch.from_numpy((np.arange(n) % 2).astype(np.uint8)).cuda()
+    clen = torch.full((n,), 1 << 26, dtype=torch.int32).cuda()
+    ex = MoveExpander()
+    stream = torch.cuda.Stream()
+    ex.set_stream(stream)
+    mo = ex.expand(t["mv"], t["mv_off"], t["stride"], t["ns"], t["ts"], t["l_seq"], t["flag"], t["seq_bytes"], t["byte_off"], rna=False)
+    calls = {"project": lambda: ex.project(mo, d_cg, d_off, d_pos)}
+    if hasattr(ex._lib, "pg_mvops_project_stranded") and not getattr(ex._lib.pg_mvops_project_stranded, "missing", False):
+        calls["stranded_all_forward"] = lambda: ex.project(mo, d_cg, d_off, d_pos, reverse=fwd, contig_len=clen)
+        calls["stranded_half_reverse"] = lambda: ex.project(mo, d_cg, d_off, d_pos, reverse=half, contig_len=clen)
+    ev = {k: [] for k in calls}
+    for i in range(reps + 1):
+        for k, fn in calls.items():                        # alternating: every call sees the same box
+            pr, _, e = _event_timed(stream, fn)
+            assert pr.n_refused == 0
+            if i:
+                ev[k].append(e)
+    ref_len, n_ops = pr.ref_len_host.copy(), int(pr.n_ops)
+    ex.close()
+    out = dict(shape=name, cigars=f"{rate:.0%} edits", reads=n, ops_out=n_ops, cigar_words=int(cg.size))
+    for k, v in ev.items():
+        out[k + "_event_ms"] = dict(best=min(v), median=statistics.median(v), worst=max(v), all=[round(x, 4) for x in v])
+    return out, pos, ref_len
+
+
+def bench_refseq(pos, ref_len, reps, n_contigs=8, contig_bases=1 << 25):
+    import torch
+    from poregen_amd.engine import RefSeq
+    rng = np.random.default_rng(9)
+    n = len(pos)
+    contigs = [np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, contig_bases)] for _ in range(n_contigs)]
+    contig = (np.arange(n) % n_contigs).astype(np.int32)
+    reverse = (np.arange(n) % 2).astype(np.uint8)
+    rs = RefSeq()
+    stream = torch.cuda.Stream()
+    rs.set_stream(stream)
+    for c in contigs:
+        rs.add(c.tobytes())
+    d = [torch.from_numpy(x).cuda() for x in (contig, pos.astype(np.int32), ref_len.astype(np.uint32).view(np.int32), reverse)]
+    ev, wall = [], []
+    for i in range(reps + 1):
+        r, w, e = _event_timed(stream, lambda: rs.slices(*d))
+        if i:
+            ev.append(e); wall.append(w)
+    n_seq = r.n_seq
+    # today's host loop for the same reads (all forward: it has no complement): slice, append, upload, synchronise
+    host = []
+    for i in range(3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        parts = [contigs[c][p:p + m] for c, p, m in zip(contig.tolist(), pos.tolist(), ref_len.tolist())]
+        buf = np.concatenate(parts)
+        off = np.concatenate([[0], np.cumsum(ref_len.astype(np.int64))])
+        torch.from_numpy(buf).cuda(); torch.from_numpy(off).cuda()
+        torch.cuda.synchronize()
+        host.append((time.perf_counter() - t0) * 1e3)
+    assert buf.size == n_seq
+    rs.close()
+    return dict(reads=n, slice_bytes=int(n_seq), contigs=n_contigs, contig_bases=contig_bases, half_reversed=True,
+                slice_event_ms=dict(best=min(ev), median=statistics.median(ev), worst=max(ev)), slice_wall_ms=dict(best=min(wall), median=statistics.median(wall)),
+                slice_bytes_per_s_over_event_time=n_seq / (min(ev) * 1e-3), host_loop_numpy_wall_ms=dict(best=min(host), all=[round(x, 3) for x in host]),
+                hbm_peak_bytes_per_s=HBM_PEAK, note="event time holds three launches, the 8-byte read-back and two stream synchronises; the copy kernel's own time is rocprofv3's")
+
+
 def bench_cli(n_reads, runs, tmp):
     from poregen_amd import synth
     b = synth.make_batch_fast(n_reads, kind="rna004", seed=11)
@@ -191,10 +284,35 @@ def main():
     ap.add_argument("--tmp", default=None)
     ap.add_argument("--out", default=None)
     ap.add_argument("--ref", action="store_true", help="the projection onto the reference beside the expansion (= --cases ref)")
+    ap.add_argument("--strands", action="store_true", help="with --ref: pg_mvops_project_stranded beside pg_mvops_project, and pg_refseq_slice (= --cases strands)")
+    ap.add_argument("--lib", default=None, help="another libpgmove build to load (make variant); one without the stranded entry points is timed on pg_mvops_project alone")
     args = ap.parse_args()
     if args.ref:
-        args.cases = "ref"
+        args.cases = "strands" if args.strands else "ref"
+    if args.lib:
+        import ctypes
+        from poregen_amd import _abi
+
+        class _Missing:                                      # a symbol the library at --lib does not have: bound, never called
+            missing = True
+
+        class _Older(ctypes.CDLL):
+            def __getattr__(self, name):
+                try:
+                    return super().__getattr__(name)
+                except AttributeError:
+                    if name.startswith("pg_"):
+                        return _Missing()
+                    raise
+        _abi.LIB_PATH = os.path.abspath(args.lib)
+        _abi.C.CDLL = _Older
     out = {}
+    if "strands" in args.cases.split(","):
+        st, pos, ref_len = bench_strands("configs[1]: 50000 x 800", np.full(50000, 800, np.int64), 0.05, args.reps)
+        out["strands"] = st
+        out["lib"] = args.lib or "poregen_amd/libpgmove.so"
+        if not args.lib:
+            out["refseq"] = bench_refseq(pos, ref_len, args.reps)
     if "ref" in args.cases.split(","):
         rng = np.random.default_rng(3)
         ragged = np.clip(rng.lognormal(7.6, 1.0, 200000), 400, 200000).astype(np.int64)
