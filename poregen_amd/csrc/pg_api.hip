@@ -6,6 +6,7 @@
 #include "pg_hostmem.h"
 #include "pg_hip_host.h"
 #include "pg_select.h"
+#include "pg_stats_plan.h"
 #include "pg_model.h"
 #include "pg_evstat.h"
 #include "pg_modelcols.h"
@@ -41,6 +42,19 @@ struct HostBatchResult { // one collected batch, downloaded
 
 struct ProfEntry { const char *name; hipEvent_t a, b; bool bracket; };
 
+// What the context knows of the current batch alone: valid from the batch's pg_count, which value-initialises it behind the settling of the
+// batch in front, to its settle_batch. A pg_count that fails half-way leaves nothing of the batch in front behind.
+struct BatchState {
+    PgStatsPlan plan{};          // where this batch's statistics run and who writes their records (pg_stats_plan.h)
+    uint32_t front_tiles = 0;    // front-first count phase (front_tiles_for): the front in tiles, 0 = one pass
+    bool in_submit = false;      // counted by pg_submit: the base is the context's running counts
+    bool all_matches = false;    // PG_BATCH_ALL_MATCHES (and not PG_FLAG_DEBUG_SPLIT_WALK)
+    bool cut_in_scan = false;    // the sample_limit cut was applied inside the tile / region scan's launch: no k_slot_plan
+    bool stats_pending = false;  // PG_STATS_DEFERRED and not queued yet: pg_stats / pgi_stats_gathered / pg_collect queue them, pgi_skip_stats drops them
+    bool rare_pending = false;   // the rare statistics launch is still to be issued, with the sample-offset scan of pg_collect ...
+    PgRareArgs rare{};           // ... from these arguments
+};
+
 } // namespace
 
 struct pg_ctx {
@@ -50,9 +64,9 @@ struct pg_ctx {
     PgStream st2, own_st;
     PgEvent ev_fork;
     PgEvent ev_join[2], ev_gathered[2]; // per statistics slot
-    bool slot_used[2] = {false, false};
+    bool slot_used[2] = {false, false}; // crosses batches: a gather has read this slot's buffers (ev_gathered is recorded)
     PgPinned<PgSettlePack> settle_host; // host-mapped: what settle_batch learns of a finished batch, packed by one launch (k_settle_pack)
-    int slot = 0; // statistics buffers are double-buffered so that batch i+1's statistics overlap batch i's tail
+    int slot = 0; // statistics buffers are double-buffered so that batch i+1's statistics overlap batch i's tail: flips with every batch
     bool user_stream = false, batch_is_host = false;
     std::string err;
     uint32_t n_codes = 0, key_bits = 1;
@@ -73,7 +87,6 @@ struct pg_ctx {
     bool part_mode = false; uint32_t part_hi = 0, part_lo = 0;
     PgDev<> part_elem, part_lodig, part_rbase, part_tile_region, part_ntiles, part_histB, part_Bp, chunk_part, region_state; uint32_t region_epoch = 0; // region_state / region_epoch: k_region_scan_cut
     PgDev<> med[2], mad[2], gcal[2], read_plan[2], stat_status[2], stat_err[2], wide_list[2];
-    bool stat_flags_reset = false; // stat_err[slot] was reset by k_batch_init of the current batch
     // long-read counters (PgLongState::cnt), a ring of four entries of four words: batch number b uses entry b & 3 and its k_batch_init zeroes
     // entry (b + 2) & 3. Round 5 kept them beside the statistics flags of the two slots, zeroed by the batch in front -- but the reservations
     // of batch b + 1 (k_read_plan on the statistics stream, released by the gather of batch b - 1) are not ordered behind k_batch_init of
@@ -81,35 +94,22 @@ struct pg_ctx {
     // zeroing in front of the gather the reserving launch waits for. They also put it behind the entry's last reader: k_read_stats of batch b
     // (statistics stream) precedes ev_join of batch b, the gather of batch b (chain's stream) waits for that event, and k_batch_init of batch
     // b + 2, which zeroes entry b & 3, follows that gather on the chain's stream.
-    PgDev<> long_ring; uint32_t long_seq = 0;
+    PgDev<> long_ring; uint32_t long_seq = 0; // (long_seq crosses batches: it numbers them for the ring)
     PgDev<> meta, huge_scratch, oor;
     PgDev<> blk_read, gen_flag, gen_list, cum, btot, tile_read; // PgWalkOut: owner index, generic-read list, block sums of op_n
-    uint32_t batch_id = 0;  // serial number of the batch being counted (tags gen_flag entries and the error word)
-    PgRareArgs rare{};      // the rare statistics launch of the current batch ...
-    bool rare_pending = false; // ... still to be issued: with the sample-offset scan of pg_collect
-    bool in_submit = false, plan_done = false; // pg_submit: the sample_limit cut was applied inside the tile scan's launch (no k_slot_plan)
-    // front-first count phase (front_tiles_for): the current batch's front in tiles (0: one pass), and the settled batches whose front did /
-    // did not complete every k-mer
-    uint32_t front_tiles = 0; uint64_t front_complete = 0, front_missed = 0;
-    // ... whose eager statistics are ordered behind the front's scan and skip the reads from the cut read on (PgFront; decided in pg_count):
-    // the current batch is such a batch / its statistics stream still has to wait for ev_front / settled ones whose front completed
-    // (stats_cut_batches) and the reads from their cut reads on (stats_cut_reads)
-    bool stats_behind_cut = false, wait_front = false; uint64_t stats_cut_batches = 0, stats_cut_reads = 0;
+    uint32_t batch_id = 0;  // serial number of the batch being counted (tags gen_flag entries and the error word); crosses batches: it counts them
+    BatchState bt;          // the current batch
+    // pg_kernel_stats' counters of settled batches: counted front first and the front did / did not complete every k-mer; statistics behind
+    // the cut (PgStatsPlan::behind_cut) whose front completed, and the reads from their cut reads on; one-stream batches of a two-stream context
+    uint64_t front_complete = 0, front_missed = 0, stats_cut_batches = 0, stats_cut_reads = 0, front_one_stream = 0;
     PgEvent ev_front; // recorded behind the front's scan
-    // Stream mode per batch (pg_count): in a PG_FLAG_OVERLAP context a stats_behind_cut batch is queued on the chain's stream
-    // alone, as a PG_FLAG_ONE_STREAM context queues it -- behind a complete front its statistics stream 28 MB, and the second stream's
-    // hand-overs and launches cost more than they hide. batch_one_stream: the current batch is one / prev_one_stream: the batch in front of it
-    // was (the statistics stream then waits for the chain's stream before it touches what both share) / settled ones (front_one_stream)
-    bool batch_one_stream = false, prev_one_stream = false; uint64_t front_one_stream = 0;
+    bool prev_one_stream = false; // crosses batches: the batch in FRONT of the current one was a one-stream batch (the statistics stream then waits for the chain's stream before it touches what both share)
     uint32_t gen_reads = 0; // generic reads of the last settled batch
-    bool batch_all_matches = false; // PG_BATCH_ALL_MATCHES of the current batch (and not PG_FLAG_DEBUG_SPLIT_WALK)
     PgDev<> job_total, job_freq; bool have_job_totals = false; // pg_collect_gathered / pg_job_totals_device
     PgDev<> md_ev_off, md_samp_off, md_ev_len, md_samples, md_out, md_dwell, md_class; // pg_model
-    bool zero_running = false;
-    bool stats_in_flight = false, totals_known = false;
+    bool zero_running = false, totals_known = false;
+    bool stats_in_flight = false; // crosses batches: statistics on the second stream that no gather has joined yet -- the next pg_count reads it before it queues its own
     uint32_t wide_blocks = 0;    // wide-list length of the last settled batch (sizes the next rare launch)
-    bool plan_in_init = false;   // this batch's statistics records were written by its k_batch_init
-    bool stats_deferred = false; // PG_FLAG_DEFER_STATS: pg_count left the statistics to pg_stats / pg_collect
     PgDev<> cancel_flag; bool cancel_pending = false; uint64_t stats_cancelled = 0; // pgi_stats_gathered: the device's own rank-level early-out
     // long reads (PgLongState): helper table + per-read histograms in global memory, sized for long_cap helpers; long_want = helpers the
     // next batch is expected to want (host batches: counted from sig_off; device batches: what the last settled batch wanted, at least 256)
@@ -516,7 +516,7 @@ static pg_status check_read_errors(pg_ctx *c, const PgSettlePack &pk) {
     if (ef.layout) return pg_fail(c, PG_ERR_INVALID_ARG, "pg_batch.n_ops (%llu) is not op_off[n_reads] of the device batch", (unsigned long long)c->B.n_ops);
     if ((uint32_t)(ef.word >> 32) == c->batch_id) errv[0] = (int32_t)(0xFFFFFFFFu - (uint32_t)ef.word); // PgWalkOut::err
     c->gen_reads = ef.gen_count[c->batch_id & 1u];
-    if (c->batch_all_matches && c->gen_reads) return pg_fail(c, PG_ERR_INVALID_ARG, "pg_batch.flags says PG_BATCH_ALL_MATCHES but %u reads hold I / D / unknown ops (or fewer ops than k, or more than bases)", c->gen_reads);
+    if (c->bt.all_matches && c->gen_reads) return pg_fail(c, PG_ERR_INVALID_ARG, "pg_batch.flags says PG_BATCH_ALL_MATCHES but %u reads hold I / D / unknown ops (or fewer ops than k, or more than bases)", c->gen_reads);
     memcpy(errs, pk.stat_err, sizeof errs);
     // long reads (PgLongState): what this batch wanted sizes a device batch's next launch; a host batch is counted before it is staged
     if (errs[4] > 0 || errs[5] > 0) {
@@ -527,7 +527,7 @@ static pg_status check_read_errors(pg_ctx *c, const PgSettlePack &pk) {
     // the rare statistics launch of the NEXT batch is sized by what this one needed (its blocks stride over the list: the
     // size only decides how fast a wide list is worked off; jobs without wide reads pay for 128 workgroups, not 2112)
     c->wide_blocks = errs[1] > 0 ? (uint32_t)errs[1] : 0u;
-    if (c->prm.scaling != 1 && !(c->prm.flags & PG_FLAG_SKIP_OUT_OF_RANGE)) errs[0] = INT_MAX;
+    if (c->bt.plan.place == PG_STATS_NONE) errs[0] = INT_MAX;
     if (errv[0] == INT_MAX && errs[0] == INT_MAX) return PG_OK;
     const bool walk = errv[0] <= errs[0];
     const int32_t idx = walk ? errv[0] : errs[0];
@@ -571,36 +571,36 @@ static pg_status ensure_stats_buffers(pg_ctx *c) {
 static pg_status fill_long(pg_ctx *c, PgLongState &LS, bool ensure);
 // statistics of every read of the current batch: both LDS-histogram variants are queued back to back, each
 // handles the reads whose in-range code interval fits it (no host decision, no sync)
-// plan_done: the records (and the flag reset) were written by this batch's k_batch_init
-static pg_status launch_stats(pg_ctx *c, hipStream_t st, const uint8_t *needed, bool forked_behind_init = false, bool plan_done = false, bool rare_with_scan = false) {
-    // by this batch's k_batch_init, on the same stream (or on the stream this one was forked from, behind that kernel)
-    const bool flags_are_reset = (st == c->st || forked_behind_init) && c->stat_flags_reset;
-    c->stat_flags_reset = false;
+// the batch's plan says where: on which stream, whether k_batch_init has written the records and reset the flags in front of them (on the
+// same stream, or on the stream this one was forked from, behind that kernel), and whether the rare workers ride in the next scan
+static pg_status launch_stats(pg_ctx *c) {
+    const PgStatsPlan &P = c->bt.plan;
+    hipStream_t st = pg_stats_on_second_stream(P.place) ? c->st2.h : c->st;
+    const uint8_t *needed = P.place == PG_STATS_LAZY ? c->read_needed.as<uint8_t>() : nullptr; // only the reads that own a kept event
     const int sl = c->slot;
-    const bool skip_oor = (c->prm.flags & PG_FLAG_SKIP_OUT_OF_RANGE) != 0;
     pg_status se = ensure_stats_buffers(c);
     if (se != PG_OK) return se;
-    uint8_t *oor = skip_oor ? c->oor.as<uint8_t>() : nullptr;
+    uint8_t *oor = P.place == PG_STATS_OOR_FIRST ? c->oor.as<uint8_t>() : nullptr;
     const int range_only = c->prm.scaling != 1; // only the out-of-range flags are wanted
     int32_t *flags = c->stat_err[sl].as<int32_t>(); // [0] lowest failing read, [1] / [2] lengths of the wide / huge list
     PgLongState LS{};
     { pg_status sl_ = fill_long(c, LS, false); if (sl_ != PG_OK) return sl_; }
-    if (!plan_done) {
+    if (!P.records_in_init) {
         prof_begin(c, "k_read_plan", st);
-        PG_HIP_TRY(c, pg_launch_read_plan(st, c->B, needed, c->prm.pa_min, c->prm.pa_max, c->read_plan[sl].p, flags, c->stat_status[sl].as<int32_t>(), flags_are_reset, LS));
+        PG_HIP_TRY(c, pg_launch_read_plan(st, c->B, needed, c->prm.pa_min, c->prm.pa_max, c->read_plan[sl].p, flags, c->stat_status[sl].as<int32_t>(), P.flags_in_init, LS));
         prof_end(c, st);
     }
     const int win = (c->prm.flags & PG_FLAG_DEBUG_NARROW) ? 0 : 15;
-    // stats_behind_cut: the cut-read word is final before k_read_stats starts -- on the chain's stream by stream order, on the statistics
-    // stream by the event behind the front's scan (the record pass in front of it needs nothing of the chain and does not wait)
-    if (c->wait_front && st != c->st) { PG_HIP_TRY(c, hipStreamWaitEvent(st, c->ev_front, 0)); c->wait_front = false; }
-    const bool cut = c->stats_behind_cut && !needed;
+    // behind_cut: the cut-read word is final before k_read_stats starts -- on the chain's stream by stream order, on the statistics stream by
+    // the event pg_count recorded behind the front's scan (the record pass in front of it needs nothing of the chain and does not wait)
+    const bool cut = P.behind_cut;
+    if (cut && P.place == PG_STATS_SECOND_STREAM) PG_HIP_TRY(c, hipStreamWaitEvent(st, c->ev_front, 0));
     // a cut launch handles the reads behind what the front's ops cover (and a margin) in groups (k_read_stats); PGMOVE_STATS_GROUP_FROM=n
     // (tests, A/B; read per batch) sets that index itself, n >= n_reads: no group
     uint32_t group_from = 0xffffffffu;
     if (cut) {
         const char *ov = getenv("PGMOVE_STATS_GROUP_FROM");
-        group_from = ov ? (uint32_t)std::min<unsigned long long>(strtoull(ov, nullptr, 10), 0xffffffffull) : pg_stats_group_from(c->B.n_reads, c->B.n_ops, c->front_tiles);
+        group_from = ov ? (uint32_t)std::min<unsigned long long>(strtoull(ov, nullptr, 10), 0xffffffffull) : pg_stats_group_from(c->B.n_reads, c->B.n_ops, c->bt.front_tiles);
     }
     prof_begin(c, "k_read_stats", st);
     PG_HIP_TRY(c, pg_launch_read_stats(st, c->B, c->read_plan[sl].p, c->med[sl].as<double>(), c->mad[sl].as<double>(),
@@ -609,11 +609,11 @@ static pg_status launch_stats(pg_ctx *c, hipStream_t st, const uint8_t *needed, 
     prof_end(c, st);
     // the rare reads (in-range interval wider than 1024 codes; usually none): their workers ride in the launch of the sample-offset
     // scan when that comes next on the same stream (rare_pending); otherwise a launch of their own, here
-    PgRareArgs &A = c->rare;
+    PgRareArgs &A = c->bt.rare;
     A.B = c->B; A.plan = c->read_plan[sl].as<PgStatRec>(); A.med = c->med[sl].as<double>(); A.mad = c->mad[sl].as<double>(); A.gcal = c->gcal[sl].as<double>();
     A.status = c->stat_status[sl].as<int32_t>(); A.err = flags; A.win = win; A.wide_list = c->wide_list[sl].as<uint32_t>(); A.wide_count = flags + 1;
     A.scratch = c->huge_scratch.as<uint32_t>(); A.oor = oor; A.range_only = range_only; A.wide_blocks = c->wide_blocks;
-    if (rare_with_scan && st == c->st) c->rare_pending = true;
+    if (P.rare_with_scan) c->bt.rare_pending = true;
     else {
         prof_begin(c, "k_read_stats_rare", st);
         PG_HIP_TRY(c, pg_launch_read_stats_rare(st, A));
@@ -626,7 +626,7 @@ static void fill_walk(pg_ctx *c, PgWalkParams &W, PgWalkOut &O) {
     W.k = c->prm.kmer_size; W.sig_move_offset = c->prm.sig_move_offset; W.print_margin = c->prm.signal_print_margin;
     W.max_dur = c->prm.max_dur; W.min_dur = c->prm.min_dur; W.pick_margin = c->prm.kmer_pick_margin; W.allow_rna = c->prm.allow_rna;
     W.short_ok = (c->prm.flags & PG_FLAG_SHORT_READS_OK) ? 1 : 0;
-    W.no_generic = c->batch_all_matches ? 1 : 0;
+    W.no_generic = c->bt.all_matches ? 1 : 0;
     W.n_codes = c->n_codes; W.table_t = c->table_t.as<int32_t>(); W.table_u = c->table_t.as<int32_t>() + c->n_codes;
     for (int x = 0; x < 2; x++) { W.aff_ok[x] = c->tab_ok[x]; W.aff_lo[x] = c->tab_lo[x]; W.aff_hi[x] = c->tab_hi[x]; W.aff_delta[x] = c->tab_delta[x]; }
     O.m_start = c->m_start.as<uint32_t>(); O.m_len = c->m_len.as<uint32_t>(); O.m_base = c->m_base.as<uint8_t>();
@@ -706,7 +706,7 @@ static bool dense_direct(const pg_ctx *c, uint64_t n_ops) {
 // single pass's work (one workgroup's chain through the event kernel and the scan, ~23 us on the headline workload).
 // PGMOVE_FRONT_TILES=n (tests, A/B) sets the front itself, rounded up to a multiple of 4, for any size; 0 = never.
 static uint32_t front_tiles_for(const pg_ctx *c, uint64_t n_ops, bool counts_wanted) {
-    if (!c->in_submit || counts_wanted || n_ops == 0 || c->prm.n_slots > PG_DIRECT_MAX_SLOTS || dense_direct(c, n_ops)) return 0;
+    if (!c->bt.in_submit || counts_wanted || n_ops == 0 || c->prm.n_slots > PG_DIRECT_MAX_SLOTS || dense_direct(c, n_ops)) return 0;
     if (c->prm.sample_limit == 0 || c->prm.sig_move_offset != 0) return 0;
     const uint32_t n_tiles = pg_tiles(n_ops, true);
     uint64_t f;
@@ -734,7 +734,9 @@ static pg_status ensure_unpacked(pg_ctx *c) {
     return PG_OK;
 }
 
-pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t counts_location) {
+// pg_count, and the count phase of pg_submit (in_submit: the base is this context's running counts, so the sample_limit cut can ride in
+// the scan's launch and the batch can be counted front first)
+static pg_status count_impl(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t counts_location, bool in_submit) {
     if (!c || !b) return PG_ERR_INVALID_ARG;
     if (b->struct_size != sizeof(pg_batch)) return pg_fail(c, PG_ERR_INVALID_ARG, "pg_batch.struct_size mismatch");
     PG_HIP_TRY(c, hipSetDevice(c->device));
@@ -747,12 +749,14 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
             hb.in_ctx = false; c->merged_valid = false; c->fin_dev = nullptr;
         }
     if (c->have_batch_result) { c->reads_before += c->B.n_reads; c->have_batch_result = false; }
-    c->have_count = false; c->rare_pending = false; c->plan_done = false;
+    c->have_count = false;
+    c->bt = BatchState{}; // the batch in front is settled (download_last): from here on the state is this batch's
+    c->bt.in_submit = in_submit;
     const uint32_t n = b->n_reads;
 
     double tmark_ = timing_on() ? wall_now() : 0.0;
     c->batch_is_host = b->location == PG_LOC_HOST;
-    c->batch_all_matches = (b->flags & PG_BATCH_ALL_MATCHES) != 0 && !(c->prm.flags & PG_FLAG_DEBUG_SPLIT_WALK);
+    c->bt.all_matches = (b->flags & PG_BATCH_ALL_MATCHES) != 0 && !(c->prm.flags & PG_FLAG_DEBUG_SPLIT_WALK);
     if (b->location == PG_LOC_HOST) {
         s = stage_host_batch(c, b);
         if (s != PG_OK) return s;
@@ -827,27 +831,20 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
     PG_TMARK("count: work buffers");
     c->full_before_batch = c->full_slots == c->prm.n_slots && c->prm.n_slots > 0;
     c->slot ^= 1; // this batch's statistics buffers
-    const bool skip_oor = (c->prm.flags & PG_FLAG_SKIP_OUT_OF_RANGE) != 0; // statistics first: the walk needs their verdict
-    const bool eager_stats = skip_oor || (c->prm.scaling == 1 && !(c->prm.flags & PG_FLAG_LAZY_STATS));
-    c->front_tiles = front_tiles_for(c, N, counts_out != nullptr);
-    const PgFront FR{c->front_tiles, c->errflag.as<uint32_t>() + 8};
-    // Eager statistics of a batch counted front first start behind the front's scan and read its cut-read word (PgFront): behind a complete
-    // front, the reads that own no kept event are not streamed -- the reference never reads them (gmove.cpp:733-735). Not with
-    // PG_FLAG_SKIP_OUT_OF_RANGE (the walk waits for the statistics' verdict), and not in a PG_FLAG_PROFILE context: its passes time each
-    // kernel over the whole batch (include/pgmove.h). Every other batch queues its statistics where it always did.
-    c->stats_behind_cut = FR.tiles && eager_stats && !skip_oor && c->prm.scaling == 1 && !(c->prm.flags & PG_FLAG_PROFILE);
-    c->wait_front = false;
-    // The stream mode is decided per batch: the context's flag says that a second stream exists, and such a batch does not use it. Its
+    c->bt.front_tiles = front_tiles_for(c, N, counts_out != nullptr);
+    const PgFront FR{c->bt.front_tiles, c->errflag.as<uint32_t>() + 8};
+    // Where this batch's statistics run (pg_stats_plan.h: the one statement of the rule). Eager statistics of a batch counted front first
+    // start behind the front's scan and read its cut-read word (PgFront): behind a complete front, the reads that own no kept event are not
+    // streamed -- the reference never reads them (gmove.cpp:733-735). Every other batch queues its statistics where it always did.
+    // The stream mode is decided per batch: the context's flag says that a second stream exists, and a behind_cut batch does not use it. Its
     // statistics wait for the front's scan anyway, and behind a complete front little is left to overlap: the two event hand-overs, the
     // record pass's own launch and the empty rare launch cost more than the second stream hides.
     // PGMOVE_FRONT_TWO_STREAMS=1 (tests, A/B; read per batch) keeps it on two streams.
-    const bool ctx_overlap = !skip_oor && (c->prm.flags & PG_FLAG_OVERLAP) != 0;
-    c->batch_one_stream = ctx_overlap && c->stats_behind_cut && !getenv("PGMOVE_FRONT_TWO_STREAMS");
-    const bool overlap = ctx_overlap && !c->batch_one_stream;
+    const PgStatsPlan P = c->bt.plan = pg_stats_plan(c->prm.flags, c->prm.scaling, FR.tiles, n, getenv("PGMOVE_FRONT_TWO_STREAMS") != nullptr);
     // (a two-stream batch that was counted and never collected: nothing on the chain's stream has waited for its statistics yet, and this
     // batch's k_batch_init writes the long-read table they read)
-    if (c->batch_one_stream && c->stats_in_flight) PG_HIP_TRY(c, hipStreamWaitEvent(c->st, c->ev_join[c->slot ^ 1], 0));
-    if (eager_stats && overlap) {
+    if (P.one_stream_batch && c->stats_in_flight) PG_HIP_TRY(c, hipStreamWaitEvent(c->st, c->ev_join[c->slot ^ 1], 0));
+    if (P.place == PG_STATS_SECOND_STREAM) {
         // The statistics stream only needs the batch to be resident: after the staging copies of a host batch, or
         // after the producer of a device batch when the caller drives us on its own stream. A device batch on the
         // context's own stream must be complete when pg_count is called, so nothing on `st` has to be awaited and
@@ -855,7 +852,7 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
         // Behind a one-stream batch it waits as well: that batch's statistics ran on the chain's stream, so the order of the statistics
         // stream no longer puts this batch's record pass behind them, and both use the long-read table, its histograms and the rare
         // launch's scratch. (The event stands behind everything queued so far, the previous batch's gather included.)
-        if (c->batch_is_host || (c->user_stream && !(b->flags & PG_BATCH_RESIDENT)) || c->prev_one_stream) { // (PG_BATCH_RESIDENT: the caller vouches that nothing on its stream produces the batch)
+        if (pg_stats_fork_waits(c->batch_is_host, c->user_stream, (b->flags & PG_BATCH_RESIDENT) != 0, c->prev_one_stream)) { // (PG_BATCH_RESIDENT: the caller vouches that nothing on its stream produces the batch)
             PG_HIP_TRY(c, hipEventRecord(c->ev_fork, c->st));
             PG_HIP_TRY(c, hipStreamWaitEvent(c->st2, c->ev_fork, 0));
         }
@@ -865,12 +862,9 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
     // Not per-job state: pg_reset does not clear it, because it waits for nothing -- the one-stream batch of the job in front may still be
     // running when the next job's first batch is queued. pg_set_stream, which waits for both streams, does. Left set by a pg_count that
     // fails behind this line, it costs the next two-stream batch one wait it did not need.
-    c->prev_one_stream = c->batch_one_stream;
-    // eager statistics on the main stream (or forked from it later): k_batch_init also writes the statistics record of every
-    // read -- k_read_plan's work, one kernel boundary less. The second-stream mode plans on its own stream; lazy statistics
-    // plan behind the emit kernel (they need its flags).
-    c->plan_in_init = eager_stats && !overlap && n > 0;
-    if (c->plan_in_init) { pg_status se = ensure_stats_buffers(c); if (se != PG_OK) return se; }
+    c->prev_one_stream = P.one_stream_batch;
+    // k_batch_init also writes the statistics record of every read: k_read_plan's work, one kernel boundary less
+    if (P.records_in_init) { pg_status se = ensure_stats_buffers(c); if (se != PG_OK) return se; }
     PgWalkParams W{}; PgWalkOut O{};
     fill_walk(c, W, O);
     const bool force_generic = (c->prm.flags & PG_FLAG_DEBUG_SPLIT_WALK) != 0;
@@ -879,19 +873,18 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
     { pg_status sl_ = fill_long(c, LS, true); if (sl_ != PG_OK) return sl_; }
     prof_begin(c, "k_batch_init", c->st);
     PG_HIP_TRY(c, pg_launch_batch_init(c->st, n, c->read_needed.as<uint8_t>(), c->running.as<uint64_t>(), c->prm.n_slots,
-                         c->zero_running ? 1 : 0, overlap ? nullptr : c->stat_err[c->slot].as<int32_t>(), c->B, c->prm.pa_min, c->prm.pa_max,
-                         c->plan_in_init ? c->read_plan[c->slot].p : nullptr, c->plan_in_init ? c->stat_status[c->slot].as<int32_t>() : nullptr,
+                         c->zero_running ? 1 : 0, P.flags_in_init ? c->stat_err[c->slot].as<int32_t>() : nullptr, c->B, c->prm.pa_min, c->prm.pa_max,
+                         P.records_in_init ? c->read_plan[c->slot].p : nullptr, P.records_in_init ? c->stat_status[c->slot].as<int32_t>() : nullptr,
                          W, O, force_generic ? 1 : 0, LS, FR.tiles ? FR.word + 1 : nullptr));
     prof_end(c, c->st);
-    c->stat_flags_reset = !overlap;
     c->zero_running = false;
 
-    if (skip_oor) {
-        pg_status s2 = launch_stats(c, c->st, nullptr, false, c->plan_in_init); if (s2 != PG_OK) return s2;
+    if (P.place == PG_STATS_OOR_FIRST) { // statistics first: the walk needs their verdict
+        pg_status s2 = launch_stats(c); if (s2 != PG_OK) return s2;
         PG_HIP_TRY(c, pg_launch_apply_oor(c->st, c->B, O));
     }
     // the generic walk over the list k_batch_init has just built; not launched when the caller vouches for a batch of matches only
-    if (!c->batch_all_matches) {
+    if (!c->bt.all_matches) {
         prof_begin(c, "k_walk", c->st);
         PG_HIP_TRY(c, pg_launch_walk(c->st, c->B, W, O));
         prof_end(c, c->st);
@@ -907,17 +900,15 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
     if (direct) {
         prof_begin(c, "rank_scan", c->st);
         // pg_submit (base = this context's running counts): the sample_limit cut rides in the tile scan's launch
-        const bool fuse_plan = c->in_submit;
+        const bool fuse_plan = c->bt.in_submit;
         PG_HIP_TRY(c, pg_launch_rank_direct_count(c->st, O.ev_slot, N, c->prm.n_slots, S, c->acc_cnt.as<uint64_t>(), c->running.as<uint64_t>(), c->prm.sample_limit,
                                     c->tile_last.as<int32_t>(), acc_copy, fuse_plan ? c->keep.as<uint64_t>() : nullptr, c->ev_off.as<uint64_t>(),
-                                    c->plan_totals.as<uint64_t>(), c->errflag.as<uint32_t>() + 6, &c->plan_done,
+                                    c->plan_totals.as<uint64_t>(), c->errflag.as<uint32_t>() + 6, &c->bt.cut_in_scan,
                                     O.btot, dense_direct(c, N) ? c->part_Bp.as<uint32_t>() : nullptr, dense_direct(c, N) ? c->chunk_part.as<uint64_t>() : nullptr,
                                     FR, FR.tiles ? PG_PASS_FRONT : PG_PASS_WHOLE, c->batch_id, O.tile_read, n));
         prof_end(c, c->st);
-        if (c->stats_behind_cut && overlap) { // the statistics stream starts k_read_stats behind this scan (launch_stats); one stream: queued behind it anyway
-            PG_HIP_TRY(c, hipEventRecord(c->ev_front, c->st));
-            c->wait_front = true;
-        }
+        // the statistics stream starts k_read_stats behind this scan (launch_stats); one stream: queued behind it anyway
+        if (P.behind_cut && P.place == PG_STATS_SECOND_STREAM) PG_HIP_TRY(c, hipEventRecord(c->ev_front, c->st));
         if (FR.tiles) { // the tiles behind the front: queued regardless, empty launches if the front has completed every k-mer (PgFront)
             prof_begin(c, "k_events_tail", c->st);
             PG_HIP_TRY(c, pg_launch_events(c->st, c->B, W, O, c->prm.n_slots, S.hist, 0u, 0u, FR, PG_PASS_TAIL));
@@ -925,7 +916,7 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
             prof_begin(c, "rank_scan_tail", c->st);
             PG_HIP_TRY(c, pg_launch_rank_direct_count(c->st, O.ev_slot, N, c->prm.n_slots, S, c->acc_cnt.as<uint64_t>(), c->running.as<uint64_t>(), c->prm.sample_limit,
                                         c->tile_last.as<int32_t>(), nullptr, c->keep.as<uint64_t>(), c->ev_off.as<uint64_t>(), c->plan_totals.as<uint64_t>(),
-                                        c->errflag.as<uint32_t>() + 6, &c->plan_done, O.btot, nullptr, nullptr, FR, PG_PASS_TAIL, c->batch_id));
+                                        c->errflag.as<uint32_t>() + 6, &c->bt.cut_in_scan, O.btot, nullptr, nullptr, FR, PG_PASS_TAIL, c->batch_id));
             prof_end(c, c->st);
         }
     } else if (c->part_mode) {
@@ -944,7 +935,7 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
             prof_end(c, c->st);
             // pg_submit (base = this context's running counts): the sample_limit cut rides in the region scan's launch, as in the direct ranking
             PgRegionCutArgs cut{};
-            const bool fuse_cut = c->in_submit && !acc_copy && !getenv("PGMOVE_NO_FUSED_CUT");
+            const bool fuse_cut = c->bt.in_submit && !acc_copy && !getenv("PGMOVE_NO_FUSED_CUT");
             if (fuse_cut) {
                 const size_t before = c->region_state.cap;
                 PG_HIP_TRY(c, grow(c->region_state, ((size_t)(1u << c->part_hi) + 2) * 8));
@@ -957,7 +948,7 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
             prof_begin(c, "region_counts", c->st, true);
             PG_HIP_TRY(c, pg_launch_region_counts(c->st, P, c->prm.n_slots, c->acc_cnt.as<uint64_t>(), acc_copy, fuse_cut ? &cut : nullptr));
             prof_end(c, c->st);
-            c->plan_done = fuse_cut;
+            c->bt.cut_in_scan = fuse_cut;
         } else {
             PG_HIP_TRY(c, hipMemsetAsync(c->acc_cnt.p, 0, c->prm.n_slots * 8ull, c->st));
             if (acc_copy) PG_HIP_TRY(c, hipMemsetAsync(acc_copy, 0, c->prm.n_slots * 8ull, c->st));
@@ -977,22 +968,21 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
     // Statistics only need the signal: in eager mode they run on the second stream, overlapping the
     // latency-bound walk/rank chain above; pg_collect joins the two streams before the gather.
     c->stats_in_flight = false;
-    // (both flags below are ignored with PG_FLAG_OVERLAP: by the CONTEXT's flag, also for a batch of such a context that stays on one stream)
-    c->stats_deferred = eager_stats && !skip_oor && !ctx_overlap && (c->prm.flags & PG_FLAG_DEFER_STATS) != 0;
-    // PG_FLAG_OVERLAP_TAIL: the statistics fork off HERE, behind the counting kernels, onto the second stream; the sample_limit
-    // cut, the emit kernel and the offset scan of pg_collect -- small launches that keep a fraction of the chip busy -- run
-    // next to the streaming kernel, and pg_collect joins the two streams in front of the gather (the only consumer of med/MAD).
-    const bool tail = eager_stats && !skip_oor && !ctx_overlap && !c->stats_deferred && (c->prm.flags & PG_FLAG_OVERLAP_TAIL) != 0;
-    if (eager_stats && !skip_oor && !c->stats_deferred) {
-        hipStream_t ss = (overlap || tail) ? c->st2 : c->st;
-        if (tail) {
+    c->bt.stats_pending = P.place == PG_STATS_DEFERRED;
+    if (P.place == PG_STATS_SECOND_STREAM || P.place == PG_STATS_CHAIN || P.place == PG_STATS_TAIL_FORK) {
+        // PG_FLAG_OVERLAP_TAIL: the statistics fork off HERE, behind the counting kernels, onto the second stream; the sample_limit
+        // cut, the emit kernel and the offset scan of pg_collect -- small launches that keep a fraction of the chip busy -- run
+        // next to the streaming kernel, and pg_collect joins the two streams in front of the gather (the only consumer of med/MAD).
+        if (P.place == PG_STATS_TAIL_FORK) {
             PG_HIP_TRY(c, hipEventRecord(c->ev_fork, c->st));
             PG_HIP_TRY(c, hipStreamWaitEvent(c->st2, c->ev_fork, 0));
         }
-        pg_status s2 = launch_stats(c, ss, nullptr, tail, c->plan_in_init, /*rare_with_scan=*/ss == c->st);
+        pg_status s2 = launch_stats(c);
         if (s2 != PG_OK) return s2;
-        if (overlap || tail) PG_HIP_TRY(c, hipEventRecord(c->ev_join[c->slot], c->st2));
-        c->stats_in_flight = overlap || tail;
+        if (pg_stats_on_second_stream(P.place)) {
+            PG_HIP_TRY(c, hipEventRecord(c->ev_join[c->slot], c->st2));
+            c->stats_in_flight = true;
+        }
     }
 
     if (counts_out && counts_location != PG_LOC_DEVICE) { // a device output has been written by the counting kernels themselves
@@ -1007,13 +997,22 @@ pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t c
 
 static pg_status collect_impl(pg_ctx *c, const uint64_t *base, int32_t base_location, const uint64_t *all_counts, uint32_t world, uint32_t rank);
 
+pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t counts_location) { return count_impl(c, b, counts_out, counts_location, false); }
+
+// PG_STATS_DEFERRED: the statistics pg_count left out, queued now on the chain's stream -- by whoever comes first of pg_stats,
+// pgi_stats_gathered and pg_collect (the device is set)
+static pg_status launch_pending_stats(pg_ctx *c) {
+    if (!c->bt.stats_pending) return PG_OK;
+    c->bt.stats_pending = false;
+    return launch_stats(c);
+}
+
 pg_status pg_stats(pg_ctx *c) {
     if (!c) return PG_ERR_INVALID_ARG;
     if (!c->have_count) return pg_fail(c, PG_ERR_STATE, "pg_stats without a preceding pg_count");
-    if (!c->stats_deferred) return PG_OK;
+    if (!c->bt.stats_pending) return PG_OK;
     PG_HIP_TRY(c, hipSetDevice(c->device));
-    c->stats_deferred = false;
-    return launch_stats(c, c->st, nullptr, false, c->plan_in_init, true);
+    return launch_pending_stats(c);
 }
 
 // pg_job.hip, RCCL exchange: pg_stats for a rank whose base is only known on the device. all_counts / world / rank as pg_collect_gathered
@@ -1023,16 +1022,15 @@ pg_status pgi_stats_gathered(pg_ctx *c, const uint64_t *all_counts, uint32_t wor
     if (!c) return PG_ERR_INVALID_ARG;
     if (!c->have_count) return pg_fail(c, PG_ERR_STATE, "pgi_stats_gathered without a preceding pg_count");
     if (!all_counts || rank >= world) return pg_fail(c, PG_ERR_INVALID_ARG, "pgi_stats_gathered: all_counts / world / rank");
-    if (!c->stats_deferred) return PG_OK;
-    if (rank == 0 || c->prm.sample_limit == 0 || !c->plan_in_init) return pg_stats(c); // nothing below this rank / nothing is ever complete / no records yet
+    if (!c->bt.stats_pending) return PG_OK;
+    if (rank == 0 || c->prm.sample_limit == 0 || !c->bt.plan.records_in_init) return pg_stats(c); // nothing below this rank / nothing is ever complete / no records yet
     PG_HIP_TRY(c, hipSetDevice(c->device));
-    c->stats_deferred = false;
     { pg_status se = ensure_stats_buffers(c); if (se != PG_OK) return se; }
     PG_HIP_TRY(c, grow(c->cancel_flag, 16));
     PG_HIP_TRY(c, pg_launch_stats_cancel_if_full(c->st, all_counts, rank, c->prm.n_slots, c->prm.sample_limit, c->cancel_flag.as<uint32_t>(),
                                               c->read_plan[c->slot].p, c->B.n_reads));
     c->cancel_pending = true;
-    return launch_stats(c, c->st, nullptr, false, true, true);
+    return launch_pending_stats(c);
 }
 
 pg_status pg_collect(pg_ctx *c, const uint64_t *base, int32_t base_location) { return collect_impl(c, base, base_location, nullptr, 0, 0); }
@@ -1048,11 +1046,7 @@ static pg_status collect_impl(pg_ctx *c, const uint64_t *base, int32_t base_loca
     if (!c->have_count) return pg_fail(c, PG_ERR_STATE, "pg_collect without a preceding pg_count");
     PG_HIP_TRY(c, hipSetDevice(c->device));
     double tmark_ = timing_on() ? wall_now() : 0.0;
-    if (c->stats_deferred) { // PG_FLAG_DEFER_STATS and the caller did not place them with pg_stats
-        c->stats_deferred = false;
-        pg_status s2 = launch_stats(c, c->st, nullptr, false, c->plan_in_init, true);
-        if (s2 != PG_OK) return s2;
-    }
+    { pg_status s2 = launch_pending_stats(c); if (s2 != PG_OK) return s2; } // PG_FLAG_DEFER_STATS and the caller did not place them with pg_stats
     const uint32_t ns = c->prm.n_slots;
     const uint64_t N = c->B.n_ops;
     const bool direct = ns <= PG_DIRECT_MAX_SLOTS;
@@ -1077,8 +1071,8 @@ static pg_status collect_impl(pg_ctx *c, const uint64_t *base, int32_t base_loca
         if (c->scan_scratch.cap != before) PG_HIP_TRY(c, hipMemsetAsync(c->scan_scratch.p, 0, c->scan_scratch.cap, c->st)); // chained-scan state
     }
     if (!direct) PG_HIP_TRY(c, grow(c->keep32, ns * 4ull));
-    const bool plan_in_scan = c->plan_done && !all_counts && !base;
-    c->plan_done = false;
+    const bool plan_in_scan = c->bt.cut_in_scan && !all_counts && !base;
+    c->bt.cut_in_scan = false;
     if (!plan_in_scan) {
     prof_begin(c, "k_slot_plan", c->st, true);
     PG_HIP_TRY(c, pg_launch_slot_plan(c->st, c->acc_cnt.as<uint64_t>(), d_base, c->running.as<uint64_t>(), c->prm.sample_limit, ns,
@@ -1099,7 +1093,7 @@ static pg_status collect_impl(pg_ctx *c, const uint64_t *base, int32_t base_loca
     PgKeptOut K{};
     K.rec = c->ev_rec.as<PgKeptRec>();
     // the per-read "owns a kept event" flags are only consumed by the lazy statistics: no scattered byte stores otherwise
-    K.read_needed = (c->prm.scaling == 1 && (c->prm.flags & PG_FLAG_LAZY_STATS) && !(c->prm.flags & PG_FLAG_SKIP_OUT_OF_RANGE)) ? c->read_needed.as<uint8_t>() : nullptr;
+    K.read_needed = c->bt.plan.place == PG_STATS_LAZY ? c->read_needed.as<uint8_t>() : nullptr;
     // Many kept events (nearly every accepted event kept: large sample_limit, k = 9): the offset scan happens inside the gather's
     // workgroups (pg_place.hip). Few (the default limit: 10^5 events): the one-launch chained scan + the strided gather of round 2.
     const bool chunked = ke_cap > dense_min() && (win_cap + 1) * 4096 < (1ull << 32);
@@ -1130,8 +1124,7 @@ static pg_status collect_impl(pg_ctx *c, const uint64_t *base, int32_t base_loca
     }
 
     // lazy statistics: only the reads that own a kept event (flags written above)
-    const bool lazy = c->prm.scaling == 1 && (c->prm.flags & PG_FLAG_LAZY_STATS) && !(c->prm.flags & PG_FLAG_SKIP_OUT_OF_RANGE);
-    if (lazy) { pg_status s2 = launch_stats(c, c->st, c->read_needed.as<uint8_t>(), false, false, true); if (s2 != PG_OK) return s2; }
+    if (c->bt.plan.place == PG_STATS_LAZY) { pg_status s2 = launch_stats(c); if (s2 != PG_OK) return s2; }
 
     uint64_t gather_cap = ke_cap;
     if (chunked) {
@@ -1142,19 +1135,19 @@ static pg_status collect_impl(pg_ctx *c, const uint64_t *base, int32_t base_loca
             // ranking, whose placing kernel has filled them by now), else here (the radix-sort ranking)
             if (!(direct && dense_direct(c, N)) && !c->part_mode) PG_HIP_TRY(c, hipMemsetAsync(c->chunk_part.p, 0, PG_CHUNK_PART_N * 8, c->st));
             prof_begin(c, "len_partials", c->st);
-            PG_HIP_TRY(c, pg_launch_len_partials(c->st, ke_cap, totals, c->ev_rec.as<PgKeptRec>(), c->chunk_part.as<uint64_t>(), c->rare_pending ? &c->rare : nullptr));
+            PG_HIP_TRY(c, pg_launch_len_partials(c->st, ke_cap, totals, c->ev_rec.as<PgKeptRec>(), c->chunk_part.as<uint64_t>(), c->bt.rare_pending ? &c->bt.rare : nullptr));
             prof_end(c, c->st);
-        } else if (c->rare_pending) {
+        } else if (c->bt.rare_pending) {
             prof_begin(c, "k_read_stats_rare", c->st);
-            PG_HIP_TRY(c, pg_launch_read_stats_rare(c->st, c->rare));
+            PG_HIP_TRY(c, pg_launch_read_stats_rare(c->st, c->bt.rare));
             prof_end(c, c->st);
         }
-        c->rare_pending = false;
+        c->bt.rare_pending = false;
     } else {
         prof_begin(c, "scan_ev_len", c->st, /*bracket=*/(ke_cap + 4095) / 4096 > 64); // long inputs: three launches (pg_launch_scan_u32_u64)
         PG_HIP_TRY(c, pg_launch_scan_u32_u64(c->st, reinterpret_cast<const uint32_t *>(c->ev_rec.p) + 2, 4, ke_cap, totals, c->samp_off.as<uint64_t>(), c->scan_scratch.as<uint64_t>(),
-                                          c->rare_pending ? &c->rare : nullptr, totals + 2));
-        c->rare_pending = false;
+                                          c->bt.rare_pending ? &c->bt.rare : nullptr, totals + 2));
+        c->bt.rare_pending = false;
         prof_end(c, c->st);
     }
 
@@ -1220,12 +1213,12 @@ static pg_status settle_batch(pg_ctx *c) {
     if (c->st2) PG_HIP_TRY(c, hipStreamSynchronize(c->st2));
     PG_HIP_TRY(c, pg_launch_settle_pack(c->st, c->errflag.as<uint32_t>(), c->stat_err[c->slot].as<int32_t>(), c->long_ring.as<int32_t>() + 4u * (c->long_seq & 3u), c->plan_totals.as<uint64_t>(),
                                      c->samp_off.as<uint64_t>(), c->samp_off.cap / 8, c->cancel_pending ? c->cancel_flag.as<uint32_t>() : nullptr,
-                                     c->front_tiles ? c->errflag.as<uint32_t>() + 8 : nullptr, c->settle_host.p));
+                                     c->bt.front_tiles ? c->errflag.as<uint32_t>() + 8 : nullptr, c->settle_host.p));
     PG_HIP_TRY(c, hipStreamSynchronize(c->st));
     const PgSettlePack pk = *c->settle_host.p;
-    if (c->front_tiles) { if (pk.front[0]) c->front_complete++; else c->front_missed++; } // (a batch that fails was counted front first all the same)
-    if (c->batch_one_stream) c->front_one_stream++; // ... and was queued on the chain's stream alone in a two-stream context, complete or not
-    if (c->stats_behind_cut && pk.front[0]) { c->stats_cut_batches++; c->stats_cut_reads += c->B.n_reads - std::min(pk.front[1], c->B.n_reads); } // its statistics left out the reads from pk.front[1] on
+    if (c->bt.front_tiles) { if (pk.front[0]) c->front_complete++; else c->front_missed++; } // (a batch that fails was counted front first all the same)
+    if (c->bt.plan.one_stream_batch) c->front_one_stream++; // ... and was queued on the chain's stream alone in a two-stream context, complete or not
+    if (c->bt.plan.behind_cut && pk.front[0]) { c->stats_cut_batches++; c->stats_cut_reads += c->B.n_reads - std::min(pk.front[1], c->B.n_reads); } // its statistics left out the reads from pk.front[1] on
     pg_status s = check_read_errors(c, pk);
     if (s != PG_OK) { c->have_batch_result = false; c->downloaded = true; return s; }
     const uint64_t tot[2] = {pk.n_kept, pk.full_slots};
@@ -1243,9 +1236,7 @@ static pg_status settle_batch(pg_ctx *c) {
 
 pg_status pg_submit(pg_ctx *c, const pg_batch *b) {
     if (!c) return PG_ERR_INVALID_ARG;
-    c->in_submit = true;
-    pg_status s = pg_count(c, b, nullptr, PG_LOC_HOST);
-    c->in_submit = false;
+    pg_status s = count_impl(c, b, nullptr, PG_LOC_HOST, true);
     if (s != PG_OK) return s;
     return pg_collect(c, nullptr, PG_LOC_HOST);
 }
@@ -1286,7 +1277,7 @@ const double *pgi_fin_dev(pg_ctx *c) { return c && c->merged_valid ? c->fin_dev 
 pg_status pgi_skip_stats(pg_ctx *c) {
     if (!c) return PG_ERR_INVALID_ARG;
     if (!c->have_count) return pg_fail(c, PG_ERR_STATE, "pgi_skip_stats without a preceding pg_count");
-    c->stats_deferred = false;
+    c->bt.stats_pending = false;
     return PG_OK;
 }
 

@@ -215,6 +215,16 @@ extern "C" int pgt_job_stats_rule(uint32_t rank, const uint64_t *shard_ops, cons
     return (int)pg_job_stats_place(rank, shard_ops, shard_reads, n_slots, sample_limit, have_batch != 0, full_slots_prev, mode && *mode ? mode : nullptr);
 }
 
+// where a batch's per-read statistics run (pg_stats_plan.h): out6 = place, behind_cut, one_stream_batch, records_in_init, flags_in_init, rare_with_scan
+#include "pg_stats_plan.h"
+extern "C" void pgt_stats_plan(uint32_t ctx_flags, int32_t scaling, uint32_t front_tiles, uint32_t n_reads, int front_two_streams, int32_t *out6) {
+    const PgStatsPlan p = pg_stats_plan(ctx_flags, scaling, front_tiles, n_reads, front_two_streams != 0);
+    out6[0] = p.place; out6[1] = p.behind_cut; out6[2] = p.one_stream_batch; out6[3] = p.records_in_init; out6[4] = p.flags_in_init; out6[5] = p.rare_with_scan;
+}
+extern "C" int pgt_stats_fork_waits(int batch_is_host, int user_stream, int batch_resident, int prev_one_stream) {
+    return pg_stats_fork_waits(batch_is_host != 0, user_stream != 0, batch_resident != 0, prev_one_stream != 0) ? 1 : 0;
+}
+
 // ---- subtool0 / pa_stats (pg_pamean.h, host/io.cpp) ----------------------------------------------------------------------------
 #include "pg_pamean.h"
 extern "C" int pgt_pa_shift(double offset) { return pg_pa_shift(offset); }

@@ -132,3 +132,122 @@ def test_where_a_ranks_statistics_go_relative_to_the_count_exchange():
     assert place(0, c2_ops, c2_reads, 1024, 100, mode=b"behind") == FRONT and place(3, c2_ops, c2_reads, 1024, 0, mode=b"behind") == FRONT
     assert place(3, c2_ops, c2_reads, 1024, 100, mode=b"front") == FRONT and place(3, k9_ops, k9_reads, 262144, 1000, mode=b"behind") == BEHIND
     assert place(3, c2_ops, c2_reads, 1024, 100, mode=b"auto") == BEHIND
+
+
+# ---- pg_stats_plan.h: where a batch's per-read statistics run ------------------------------------------------------------------------
+NONE, OOR_FIRST, SECOND_STREAM, CHAIN, TAIL_FORK, DEFERRED, LAZY = range(7)
+
+
+def _stats_plan_lib():
+    from poregen_amd import _abi
+    h = C.CDLL(os.environ.get("PG_HOSTTEST_SO") or os.path.join(ROOT, "poregen_amd", "_pg_hosttest.so"))
+    h.pgt_stats_plan.argtypes = [C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_int32)]
+    h.pgt_stats_plan.restype = None
+
+    def plan(flags, scaling, front_tiles, n_reads, two):
+        out = (C.c_int32 * 6)()
+        h.pgt_stats_plan(flags, scaling, front_tiles, n_reads, int(two), out)
+        return dict(place=out[0], behind_cut=bool(out[1]), one_stream_batch=bool(out[2]), records_in_init=bool(out[3]), flags_in_init=bool(out[4]),
+                    rare_with_scan=bool(out[5]))
+    return h, plan, _abi
+
+
+def _stats_plan_restated(A, flags, scaling, front_tiles, n_reads, two):
+    """what pg_count, launch_stats and collect_impl computed, flag by flag, before the rule had a header of its own; returns the plan and
+    every place the statistics would be queued at (exactly one, or none: no statistics)"""
+    skip_oor = bool(flags & A.PG_FLAG_SKIP_OUT_OF_RANGE)
+    eager = skip_oor or (scaling == 1 and not flags & A.PG_FLAG_LAZY_STATS)
+    behind_cut = bool(front_tiles) and eager and not skip_oor and scaling == 1 and not flags & A.PG_FLAG_PROFILE
+    ctx_overlap = not skip_oor and bool(flags & A.PG_FLAG_OVERLAP)
+    one_stream_batch = ctx_overlap and behind_cut and not two
+    overlap = ctx_overlap and not one_stream_batch
+    records_in_init = eager and not overlap and n_reads > 0
+    deferred = eager and not skip_oor and not ctx_overlap and bool(flags & A.PG_FLAG_DEFER_STATS)
+    tail = eager and not skip_oor and not ctx_overlap and not deferred and bool(flags & A.PG_FLAG_OVERLAP_TAIL)
+    lazy = scaling == 1 and bool(flags & A.PG_FLAG_LAZY_STATS) and not skip_oor
+    places, rare = [], False
+    if skip_oor:                                    # pg_count, behind k_batch_init: a rare launch of its own
+        places.append(OOR_FIRST)
+    if eager and not skip_oor and not deferred:     # pg_count, behind the counting kernels: the rare workers ride if the stream is the chain's
+        places.append(SECOND_STREAM if overlap else TAIL_FORK if tail else CHAIN)
+        rare = not (overlap or tail)
+    if deferred:                                    # pg_stats / pgi_stats_gathered / pg_collect, on the chain's stream
+        places.append(DEFERRED)
+        rare = True
+    if lazy:                                        # pg_collect, behind the emit kernel, on the chain's stream
+        places.append(LAZY)
+        rare = True
+    want = dict(place=places[0] if places else NONE, behind_cut=behind_cut, one_stream_batch=one_stream_batch, records_in_init=records_in_init,
+                flags_in_init=not overlap, rare_with_scan=rare)
+    return want, places
+
+
+def test_where_a_batchs_statistics_run_the_whole_truth_table():
+    """pg_stats_plan.h against a restatement of the parent's conditions over every subset of the seven context flags that enter it x scaling
+    x front x reads x PGMOVE_FRONT_TWO_STREAMS, and the invariants the launch sequence relies on"""
+    import itertools
+    h, plan, A = _stats_plan_lib()
+    seven = [A.PG_FLAG_LAZY_STATS, A.PG_FLAG_PROFILE, A.PG_FLAG_ONE_STREAM, A.PG_FLAG_OVERLAP, A.PG_FLAG_SKIP_OUT_OF_RANGE, A.PG_FLAG_OVERLAP_TAIL,
+             A.PG_FLAG_DEFER_STATS]
+    n_cases, seen = 0, set()
+    for bits in itertools.product((0, 1), repeat=7):
+        flags = sum(f for f, b in zip(seven, bits) if b)
+        for scaling, front, n, two in itertools.product((0, 1), (0, 4), (0, 400), (False, True)):
+            case = (flags, scaling, front, n, two)
+            got = plan(*case)
+            want, places = _stats_plan_restated(A, *case)
+            assert got == want, (case, got, want)
+            assert len(places) <= 1 and (got["place"] == NONE) == (not places), (case, places)      # exactly one place per batch
+            if got["one_stream_batch"]:
+                assert got["behind_cut"] and got["place"] == CHAIN and got["records_in_init"] == (n > 0) and got["rare_with_scan"], case
+            if got["place"] == SECOND_STREAM:
+                assert not got["records_in_init"] and not got["flags_in_init"], case
+            if flags & A.PG_FLAG_SKIP_OUT_OF_RANGE:
+                assert got["place"] == OOR_FIRST and not got["behind_cut"], case
+            if flags & A.PG_FLAG_PROFILE:
+                assert not got["behind_cut"], case
+            if got["behind_cut"]:   # launch_stats takes a LAZY batch's read_needed flags and a behind_cut batch's cut-read word: never both
+                assert got["place"] in (SECOND_STREAM, CHAIN, TAIL_FORK, DEFERRED), case
+            if got["place"] == SECOND_STREAM and got["behind_cut"]:     # the one batch that waits for the event behind the front's scan
+                assert two and flags & A.PG_FLAG_OVERLAP, case
+            assert (got["place"] == OOR_FIRST) == bool(flags & A.PG_FLAG_SKIP_OUT_OF_RANGE), case
+            n_cases += 1
+            seen.add(got["place"])
+    assert n_cases == 2048 and seen == set(range(7))
+
+
+def test_the_statistics_plans_of_the_configurations_the_project_runs():
+    """the five contexts that bench.py, pg_job.hip and the CLI create, by name; the flags as pg_create leaves them (its defaulting of
+    PG_FLAG_OVERLAP restated here), with a front (bench.py's headline batch has one) and without"""
+    h, plan, A = _stats_plan_lib()
+
+    def effective(flags, scaling=1):
+        placed = A.PG_FLAG_ONE_STREAM | A.PG_FLAG_PROFILE | A.PG_FLAG_LAZY_STATS | A.PG_FLAG_SKIP_OUT_OF_RANGE | A.PG_FLAG_DEFER_STATS | A.PG_FLAG_OVERLAP_TAIL
+        return flags | (A.PG_FLAG_OVERLAP if not flags & placed and scaling == 1 else 0)
+
+    def p(flags, front, scaling=1, two=False):
+        return plan(effective(flags, scaling), scaling, front, 50000, two)
+    yes = dict(records_in_init=True, flags_in_init=True)
+    # bench.py's default: two streams; the headline batch is counted front first and stays on the chain's stream
+    assert p(0, 0) == dict(place=SECOND_STREAM, behind_cut=False, one_stream_batch=False, records_in_init=False, flags_in_init=False, rare_with_scan=False)
+    assert p(0, 28) == dict(place=CHAIN, behind_cut=True, one_stream_batch=True, rare_with_scan=True, **yes)
+    assert p(0, 28, two=True) == dict(place=SECOND_STREAM, behind_cut=True, one_stream_batch=False, records_in_init=False, flags_in_init=False, rare_with_scan=False)
+    # overlap=False (PG_FLAG_ONE_STREAM): the same launches on the chain's stream, not counted as a one-stream batch of a two-stream context
+    for front in (0, 28):
+        assert p(A.PG_FLAG_ONE_STREAM, front) == dict(place=CHAIN, behind_cut=front > 0, one_stream_batch=False, rare_with_scan=True, **yes)
+    # defer_stats=True as pg_job.hip and bench.py --gpus set it (pg_job.hip adds PG_FLAG_ONE_STREAM; pg_count has no front: not a pg_submit)
+    for flags in (A.PG_FLAG_DEFER_STATS, A.PG_FLAG_DEFER_STATS | A.PG_FLAG_ONE_STREAM):
+        assert p(flags, 0) == dict(place=DEFERRED, behind_cut=False, one_stream_batch=False, rare_with_scan=True, **yes)
+    # lazy_stats=True: planned and computed in pg_collect, for the reads that own a kept event
+    for front in (0, 28):
+        assert p(A.PG_FLAG_LAZY_STATS, front) == dict(place=LAZY, behind_cut=False, one_stream_batch=False, records_in_init=False, flags_in_init=True, rare_with_scan=True)
+    # the CLI's context for BAM input: one stream, whole reads skipped on the statistics' verdict -- with either scaling
+    for scaling in (0, 1):
+        cli = A.PG_FLAG_ONE_STREAM | A.PG_FLAG_STOP_WHEN_FULL | A.PG_FLAG_SHORT_READS_OK | A.PG_FLAG_SKIP_OUT_OF_RANGE
+        assert p(cli, 28, scaling) == dict(place=OOR_FIRST, behind_cut=False, one_stream_batch=False, rare_with_scan=False, **yes)
+    # scaling 0 without the flag: nothing
+    assert p(A.PG_FLAG_ONE_STREAM, 28, scaling=0)["place"] == NONE
+
+    # the statistics stream waits for the chain's stream: a host batch, a caller's stream without PG_BATCH_RESIDENT, behind a one-stream batch
+    w = h.pgt_stats_fork_waits
+    assert [w(0, 0, 0, 0), w(1, 0, 0, 0), w(0, 1, 0, 0), w(0, 1, 1, 0), w(0, 0, 1, 0), w(0, 0, 0, 1), w(0, 1, 1, 1)] == [0, 1, 1, 0, 0, 1, 1]
