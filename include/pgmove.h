@@ -298,6 +298,10 @@ enum {
                                     * job's steady state). Without it the statistics stream waits for everything the caller's stream holds in
                                     * front of pg_count, which includes the previous batch's gather: the statistics of a batch then start a whole
                                     * chain later than on the context's own stream (156 -> 13x us per step of the one-rank RCCL step). */
+    ,
+    PG_BATCH_GAPPED = 1u << 2      /* pg_fit_submit and pg_realign_submit: the ops are the signal-to-reference alignment -- op_t 0 (match), 1 (I) or
+                                    * 2 (D) -- and seq / seq_off hold every read's reference slice, as pg_mvops_project and pg_refseq leave them.
+                                    * Not together with PG_BATCH_ALL_MATCHES (PG_ERR_INVALID_ARG). The collector (pg_submit) ignores it. */
 };
 
 /* Host-side view of everything collected so far, in reference order: for slot s, its kept events are
@@ -1027,6 +1031,7 @@ void      pg_transform_free(char *text);
  * No CPU fallback: PG_ERR_NO_DEVICE without a GPU. */
 typedef struct pg_fit pg_fit;
 enum { PG_FIT_ST_OK = 0, PG_FIT_ST_OUT_OF_SIGNAL = 1, PG_FIT_ST_TOO_LONG = 2, PG_FIT_ST_FEW_EVENTS = 3, PG_FIT_ST_FLAT = 4, PG_FIT_ST_NEGATIVE_SCALE = 5,
+       PG_FIT_ST_REF_LENGTH = 6,   /* gapped batches: the reference slice has not as many bases as the ops have columns */
        PG_FIT_ST_SKIPPED = 16 };   /* PG_FIT_ST_SKIPPED + c: the caller's skip code c for the read (1 <= c < 2^16) */
 typedef struct {
     uint32_t struct_size;          /* sizeof(pg_fit_params) */
@@ -1060,7 +1065,14 @@ pg_status pg_fit_set_model(pg_fit *h, const uint32_t *levels, uint32_t kmer_size
  * offset, range, target_start and target_end are not read) must carry PG_BATCH_ALL_MATCHES; one that holds an I, a D or an unknown op is
  * refused with PG_ERR_INVALID_ARG (looked for on the device) and counts nothing, the handle stays usable. At most 2^28 samples of signal
  * (PG_ERR_UNSUPPORTED beyond). skip: NULL, or host uint32[n_reads]: a read with skip != 0 takes no part and is reported with the status
- * PG_FIT_ST_SKIPPED + skip (pg_mvops_result.status_host fits: the reads reform refuses). */
+ * PG_FIT_ST_SKIPPED + skip (pg_mvops_result.status_host fits: the reads reform refuses).
+ * Or the batch carries PG_BATCH_GAPPED (both flags: PG_ERR_INVALID_ARG): ops on the signal-to-reference alignment, op_t 0 (match), 1 (I)
+ * or 2 (D; a code above 2: PG_ERR_INVALID_ARG), seq / seq_off the reads' reference slices (at most 2^32 - 1 bases each). A match of n and
+ * an I of n take n samples, a D none; a match takes one reference column, a D of n takes n, an I none. With c_j the column in front of op
+ * j, C a read's total and S its slice's length, event j counts iff it is a match, ops j - m .. j - m + k - 1 all exist and are matches,
+ * min_dur <= n_j <= max_dur, and its k-mer -- seq[c_j - m, c_j - m + k), with rna seq[S - (c_j - m) - k, S - (c_j - m)) -- lies in the slice,
+ * has ACGT letters and a level. A read with S != C (an empty slice, a contig the FASTA lacks) is PG_FIT_ST_REF_LENGTH, ranked behind
+ * out_of_signal; no kernel reads its seq. Everything behind the pairing is as above. */
 pg_status pg_fit_submit(pg_fit *h, const pg_batch *batch, const uint32_t *skip, pg_fit_reads *out);
 /* The per-slot sums and the totals of every submit since the last finish; the handle is reset afterwards (the model stays). */
 pg_status pg_fit_finish(pg_fit *h, pg_fit_result *out);
@@ -1130,7 +1142,10 @@ pg_status pg_realign_set_phase(pg_realign *h, uint32_t phase);
  * handle stays usable; at most 2^28 samples). status, a, b: host arrays [n_reads] of pg_fit_reads. A read with PG_FIT_ST_OK whose ops leave
  * its samples, or whose a or b is no fit's (b not a finite positive number), fails the batch with PG_ERR_INVALID_ARG before any kernel
  * indexes the signal. A handle has two output arrays and alternates them: the batch's op_n may be the op_n the handle's previous submit
- * returned (rounds: fit the refined ops, realign them again), and that array stays valid until the submit after this one. */
+ * returned (rounds: fit the refined ops, realign them again), and that array stays valid until the submit after this one.
+ * With PG_BATCH_GAPPED (as pg_fit_submit takes it): an I or a D is never refinable, so both boundaries beside it are pinned, and a D has no
+ * samples between them; the refined ops keep op_t and the op_n of every I and D; the pinned period counts ops. A read with
+ * PG_FIT_ST_OK whose slice has not as many bases as its ops have columns fails the batch like one whose ops leave its samples. */
 pg_status pg_realign_submit(pg_realign *h, const pg_batch *batch, const uint32_t *status, const double *a, const double *b, pg_realign_reads *out);
 /* HIP-event time of the alignment kernel since create or the last call of this */
 pg_status pg_realign_kernel_ms(pg_realign *h, double *ms);
@@ -1138,6 +1153,12 @@ pg_status pg_realign_kernel_ms(pg_realign *h, double *ms);
  * op_n: lb ops, sig: the read's n_sig samples. op_out[lb] gets the refined ops. PG_ERR_INPUT: the ops leave the samples. */
 pg_status pg_realign_walk(const pg_realign_params *params, const uint32_t *levels, uint32_t kmer_size, const uint8_t *seq, uint32_t lb, const uint32_t *op_n, int64_t query_start,
                           const int16_t *sig, uint64_t n_sig, double a, double b, uint32_t *op_out, pg_realign_read *out);
+/* The same for one read of a PG_BATCH_GAPPED batch: seq is its reference slice of n_seq bases, op_t its op codes. op_out keeps the op_n of
+ * every I and D. PG_ERR_INPUT: the ops leave the samples, or the slice has not as many bases as the ops have columns (such a read has no
+ * fit); PG_ERR_INVALID_ARG: an op code above 2. */
+pg_status pg_realign_walk_gapped(const pg_realign_params *params, const uint32_t *levels, uint32_t kmer_size, const uint8_t *seq, uint64_t n_seq, const uint32_t *op_n,
+                                 const uint8_t *op_t, uint32_t lb, int64_t query_start, const int16_t *sig, uint64_t n_sig, double a, double b, uint32_t *op_out,
+                                 pg_realign_read *out);
 
 /* ---- simulate: raw signal and its true alignment drawn from a k-mer model --------------------------------------------------------------------
  * The generative direction of fit's rule, the project's own (not squigulator's algorithm). Random numbers are Philox4x32-10 with the key

@@ -64,7 +64,7 @@ EXPORTS = [
     "pg_fit_create", "pg_fit_destroy", "pg_fit_last_error", "pg_fit_set_model", "pg_fit_submit", "pg_fit_finish", "pg_fit_set_stream", "pg_fit_pass_ms",
     "pg_fit_parse_model", "pg_fit_residuals",
     "pg_realign_create", "pg_realign_destroy", "pg_realign_last_error", "pg_realign_set_model", "pg_realign_set_stream", "pg_realign_submit", "pg_realign_kernel_ms",
-    "pg_realign_walk", "pg_realign_set_phase",
+    "pg_realign_walk", "pg_realign_walk_gapped", "pg_realign_set_phase",
     "pg_sim_create", "pg_sim_destroy", "pg_sim_last_error", "pg_sim_set_stream", "pg_sim_stream", "pg_sim_set_model", "pg_sim_generate", "pg_sim_kernel_ms", "pg_sim_walk",
     "pg_sim_parse_model", "pg_sim_parse_dwell",
     "pg_sigenc_create", "pg_sigenc_destroy", "pg_sigenc_last_error", "pg_sigenc_set_stream", "pg_sigenc_stream", "pg_sigenc_bound", "pg_sigenc_encode", "pg_sigenc_kernel_ms",
@@ -95,6 +95,7 @@ class PgBatch(C.Structure):
 
 PG_BATCH_ALL_MATCHES = 1
 PG_BATCH_RESIDENT = 2
+PG_BATCH_GAPPED = 4
 
 
 class PgResult(C.Structure):
@@ -444,6 +445,10 @@ def load():
         lib.pg_realign_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]; lib.pg_realign_kernel_ms.restype = i32
         lib.pg_realign_walk.argtypes = [C.POINTER(PgRealignParams), vp, u32, vp, u32, vp, C.c_int64, vp, C.c_uint64, C.c_double, C.c_double, vp, C.POINTER(PgRealignRead)]
         lib.pg_realign_walk.restype = i32
+        if hasattr(lib, "pg_realign_walk_gapped"):  # (a library built from the tree before gapped batches: --lib A/B runs of the all-matches submits)
+            lib.pg_realign_walk_gapped.argtypes = [C.POINTER(PgRealignParams), vp, u32, vp, C.c_uint64, vp, vp, u32, C.c_int64, vp, C.c_uint64, C.c_double, C.c_double, vp,
+                                                   C.POINTER(PgRealignRead)]
+            lib.pg_realign_walk_gapped.restype = i32
         if hasattr(lib, "pg_realign_set_phase"):  # (a library built from the tree before the phase: --lib A/B runs at phase 0)
             lib.pg_realign_set_phase.argtypes = [vp, u32]; lib.pg_realign_set_phase.restype = i32
     if hasattr(lib, "pg_sim_create"):  # (as above: a library built from an older tree has no simulator)

@@ -22,16 +22,24 @@ const struct option kLongOptions[] = {
     {"batch_reads", required_argument, nullptr, 0},// 6
     {"device", required_argument, nullptr, 0},     // 7
     {"help", no_argument, nullptr, 'h'},           // 8
+    {"ref", required_argument, nullptr, 0},        // 9
+    {"both_strands", no_argument, nullptr, 0},     // 10
     {nullptr, 0, nullptr, 0}};
 
 void print_help(FILE *fp) {
     fprintf(fp, "Usage: poregen fit [options] MODEL reads.slow5/blow5 reads.bam/sam\n");
+    fprintf(fp, "       poregen fit --ref REF.fa [--both_strands] [options] MODEL reads.slow5/blow5 mapped.bam/sam\n");
     fprintf(fp, "\nscore a k-mer model against the signal and the move tables: per read sample = shift + scale * level, per k-mer the residuals\n");
     fprintf(fp, "\noptions:\n");
     fprintf(fp, "   -k INT                     k-mer length; must be the model's [the model's]\n");
     fprintf(fp, "   -m INT                     move start offset [0]\n");
     fprintf(fp, "   --rna                      the dataset is direct RNA\n");
     fprintf(fp, "   --n_to_t                   an N of a read counts as T\n");
+    fprintf(fp, "   --ref REF.fa               a MAPPED .bam / .sam: score the model against the k-mers the REFERENCE spells -- the ops are carried through each\n");
+    fprintf(fp, "                              record's CIGAR on the GPU and the sequence is the record's slice of REF.fa, as `gmove --reform --ref` takes them;\n");
+    fprintf(fp, "                              an event counts when the k ops of its window are matches. Unmapped and reverse-strand records are skipped and\n");
+    fprintf(fp, "                              counted; a read whose slice REF.fa lacks has the status ref_length. Not with --n_to_t\n");
+    fprintf(fp, "   --both_strands             with --ref: reverse-strand records are taken too, as `gmove --reform --ref --both_strands` takes them\n");
     fprintf(fp, "   --min_dur INT              minimum number of samples of an event [5]\n");
     fprintf(fp, "   --max_dur INT              maximum number of samples of an event [70]\n");
     fprintf(fp, "   --min_events INT           counted events a read needs to be fitted [20]\n");
@@ -47,7 +55,8 @@ void print_help(FILE *fp) {
 int fit_main(int argc, char **argv) {
     long long k_opt = 0, m = 0, min_dur = 5, max_dur = 70, min_events = 20, batch_reads = 4000, device = 0;
     bool rna = false, n_to_t = false, help = false;
-    const char *out_path = nullptr, *kmer_path = nullptr;
+    const char *out_path = nullptr, *kmer_path = nullptr, *ref_path = nullptr;
+    bool both_strands = false;
     int c, longindex = 0;
     optind = 1;
     while ((c = getopt_long(argc, argv, "k:m:o:h", kLongOptions, &longindex)) >= 0) {
@@ -64,6 +73,8 @@ int fit_main(int argc, char **argv) {
         else if (c == 0 && longindex == 5) kmer_path = optarg;
         else if (c == 0 && longindex == 6) ok = whole_int(optarg, 1, 1 << 24, batch_reads);
         else if (c == 0 && longindex == 7) ok = whole_int(optarg, 0, 1024, device);
+        else if (c == 0 && longindex == 9) ref_path = optarg;
+        else if (c == 0 && longindex == 10) both_strands = true;
         else { print_help(stderr); return EXIT_FAILURE; }
         if (!ok) {
             fprintf(stderr, "[fit] %s%s: '%s' is not a value it takes (-k 1..9, -m 0..64, durations 0..%u)\n", c ? "-" : "--", c ? std::string(1, (char)c).c_str() : kLongOptions[longindex].name,
@@ -74,11 +85,19 @@ int fit_main(int argc, char **argv) {
     if (help) { print_help(stdout); return EXIT_SUCCESS; }
     if (argc - optind != 3) { print_help(stderr); return EXIT_FAILURE; }
     if (min_dur > max_dur) return die("[fit] --min_dur may not exceed --max_dur");
+    if (both_strands && !ref_path) return die("[fit] --both_strands applies with --ref only");
+    if (ref_path && n_to_t) return die("[fit] --ref cannot be combined with --n_to_t: the sequence is the reference's, there is nothing to rewrite");
     const char *model_path = argv[optind], *slow5_path = argv[optind + 1], *sam_path = argv[optind + 2];
     if (!is_sam_or_bam(sam_path)) return die("[fit] the records come from a .bam or .sam file, not %s", sam_path);
     std::vector<uint32_t> levels;
     uint32_t k = 0; int32_t uses_u = 0;
     if (!load_level_model("fit", model_path, k_opt, levels, k, uses_u)) return EXIT_FAILURE;
+    RefRoute route; // --ref: the FASTA, the projection and the slices of every batch
+    route.both_strands = both_strands; route.rna = rna;
+    if (ref_path) {
+        std::string ferr;
+        if (!route.fai.load(ref_path, ferr)) { fprintf(stderr, "Error in loading the reference %s%s%s\n", ref_path, ferr.empty() ? "" : ": ", ferr.c_str()); return EXIT_FAILURE; }
+    }
     const uint64_t n_slots = 1ull << (2 * k);
     std::string err;
     pgh::Slow5File s5;
@@ -101,23 +120,32 @@ int fit_main(int argc, char **argv) {
     const hipStream_t xs = (hipStream_t)pg_mvops_stream(ex);
     if (pg_fit_set_stream(fit, xs) != PG_OK) { fprintf(stderr, "[fit] %s\n", pg_fit_last_error(fit)); status = EXIT_FAILURE; }
 
-    PgDev<int16_t> d_sig; PgDev<uint64_t> d_sigoff;
+    PgDev<int16_t> d_sig; PgDev<uint64_t> d_sigoff; PgDev<uint8_t> d_seq; PgDev<uint64_t> d_seqoff;
     pgh::MoveSignalBatches in(sam, s5, "fit", (size_t)batch_reads, (size_t)(PG_FIT_BATCH_SAMPLES / 2), (size_t)PG_FIT_BATCH_SAMPLES);
     const HipOk hip_ok{"fit", &status};
+    if (ref_path) { in.to_ref_skipped = route.skipped_counter(); in.reverse_taken = route.reverse_counter(); }
     while (!in.done() && status == EXIT_SUCCESS) {
         // ---- the records: the first one that cannot be taken ends the run behind the reads in front of it, with gmove --reform's message
         std::string bad;
         in.next(bad);
-        const size_t n = in.recs.size();
+        size_t n = in.recs.size();
         if (n) {
             if (!hip_ok(hipSetDevice((int)device), "hipSetDevice") || !upload_signal(hip_ok, d_sig, d_sigoff, in.sig, in.sig_off, xs)) break;
             pg_mvops_batch mb;
             in.recs.fill(mb, n, (rna ? PG_MVOPS_RNA : 0) | (n_to_t ? PG_MVOPS_N_TO_T : 0));
             pg_mvops_result mr;
             if (pg_mvops_expand(ex, &mb, &mr) != PG_OK) { fprintf(stderr, "[fit] %s\n", pg_mvops_last_error(ex)); status = EXIT_FAILURE; break; }
-            const pg_batch b = device_batch(mr, n, 0, d_sig.p, d_sigoff.p);
-            pg_fit_reads fr;
-            if (pg_fit_submit(fit, &b, mr.status_host, &fr) != PG_OK) { fprintf(stderr, "[fit] %s\n", pg_fit_last_error(fit)); status = EXIT_FAILURE; break; }
+            pg_batch b = device_batch(mr, n, 0, d_sig.p, d_sigoff.p);
+            const uint32_t *skip = mr.status_host;
+            if (ref_path) { // the ops onto the reference, the slices of REF.fa: a gapped batch; a record reform --to_ref ends on ends the run
+                bool cut = false;
+                if (!route.project("fit", ex, in.recs, mr, n, bad, cut)) { status = EXIT_FAILURE; break; }
+                if (!route.slices("fit", hip_ok, (int)device, xs, in.recs, n) || (n && !route.to_device(hip_ok, xs, n, d_seq, d_seqoff))) { status = EXIT_FAILURE; break; }
+                b = route.gapped_batch(n, d_sig.p, d_sigoff.p, d_seq.p, d_seqoff.p);
+                skip = nullptr; // (every read in front of a refused one is accepted)
+            }
+            pg_fit_reads fr; memset(&fr, 0, sizeof fr);
+            if (n && pg_fit_submit(fit, &b, skip, &fr) != PG_OK) { fprintf(stderr, "[fit] %s\n", pg_fit_last_error(fit)); status = EXIT_FAILURE; break; }
             for (size_t i = 0; i < n; i++) {
                 const pg_fit_sums &q = fr.sums[i];
                 fprintf(fp, "%s\t%s\t%lld\t%lld\t", in.recs.names[i].c_str(), fit_status_name(fr.status[i]), (long long)q.e, (long long)q.n);
@@ -137,8 +165,10 @@ int fit_main(int argc, char **argv) {
         fprintf(stderr, "[fit] k=%u reads=%llu fitted=%llu events=%llu samples=%llu clamped=%llu rms_resid=%s\n", k, (unsigned long long)res.reads, (unsigned long long)res.fitted,
                 (unsigned long long)res.events, (unsigned long long)res.samples, (unsigned long long)res.clamped, pooled_rms(res, n_slots).c_str());
     }
+    if (ref_path) route.print_skipped("fit");
     finish_files();
     pg_fit_destroy(fit);
+    route.release();
     pg_mvops_destroy(ex);
     return status;
 }

@@ -100,7 +100,8 @@ void print_help(FILE *fp, const Opt &o) { // src/gmove.cpp:80-104
     fprintf(fp, "                              REFERENCE spells -- the ops are carried through each record's CIGAR on the GPU (I and D ops, --kmer_pick_margin\n");
     fprintf(fp, "                              applies) and the sequence is the record's slice of REF.fa, as `poregen reform -c -k 1 --stride 0 --to_ref` followed\n");
     fprintf(fp, "                              by gmove on its PAF with --fastq REF.fa. Unmapped and reverse-strand records (flag 0x4, no RNAME, flag 0x10) are\n");
-    fprintf(fp, "                              skipped and counted (reverse-strand ones: unless --both_strands); not with --realign or --n_to_t\n");
+    fprintf(fp, "                              skipped and counted (reverse-strand ones: unless --both_strands); not with --n_to_t. With --realign the boundaries\n");
+    fprintf(fp, "                              are refined on the projected ops, against the k-mers the reference spells: an I or a D pins the boundaries beside it\n");
     fprintf(fp, "   --both_strands             with --ref: reverse-strand records (flag 0x10) are taken too, each as a forward record on the reverse complement\n");
     fprintf(fp, "                              of its reference sequence, as `reform --to_ref --both_strands` followed by gmove on its PAF with a FASTA that holds\n");
     fprintf(fp, "                              every sequence and its reverse complement; every read's slice of REF.fa is gathered (and for a reverse-strand\n");
@@ -254,14 +255,14 @@ int gmove_main(int argc, char **argv) {
     if (reform_mode && !is_sam_or_bam(move_table)) { fprintf(stderr, "--reform applies to a .bam or .sam event_alignment_file only\n"); print_help(fp_help, opt); return EXIT_FAILURE; }
     if (n_to_t && !reform_mode) { fprintf(stderr, "--n_to_t applies with --reform only\n"); print_help(fp_help, opt); return EXIT_FAILURE; }
     // --ref: every usage error ends here too, an unreadable FASTA among them
-    pgh::FastxIndex ref_fai;
+    RefRoute route; // --ref: the FASTA, the projection and the slices of every batch (pg_cli.h)
     if (both_strands && !ref_path) { fprintf(stderr, "--both_strands applies with --ref only\n"); print_help(fp_help, opt); return EXIT_FAILURE; }
     if (ref_path) {
-        const char *why = !reform_mode ? "--ref applies with --reform only" : realign_model ? "--ref cannot be combined with --realign: fit and realign take batches of matches only" :
+        const char *why = !reform_mode ? "--ref applies with --reform only" :
                           n_to_t ? "--ref cannot be combined with --n_to_t: the sequence is the reference's, there is nothing to rewrite" : nullptr;
         std::string ferr;
         if (why) fprintf(stderr, "%s\n", why);
-        else if (!ref_fai.load(ref_path, ferr)) { fprintf(stderr, "Error in loading the reference %s%s%s\n", ref_path, ferr.empty() ? "" : ": ", ferr.c_str()); why = ""; }
+        else if (!route.fai.load(ref_path, ferr)) { fprintf(stderr, "Error in loading the reference %s%s%s\n", ref_path, ferr.empty() ? "" : ": ", ferr.c_str()); why = ""; }
         if (why) { print_help(fp_help, opt); return EXIT_FAILURE; }
     }
     // --realign: every usage error ends here, before a device is asked for and before the output directory exists
@@ -278,7 +279,11 @@ int gmove_main(int argc, char **argv) {
             why = text;
         }
         if (why) fprintf(stderr, "%s\n", why);
-        if (why || (realign_model && !load_level_model("gmove", realign_model, 0, realign_levels, realign_k, realign_uses_u))) { print_help(fp_help, opt); return EXIT_FAILURE; }
+        bool model_ok = true;
+        if (!why && realign_model) model_ok = load_level_model("gmove", realign_model, 0, realign_levels, realign_k, realign_uses_u);
+        // the combination with --ref stands on the model's levels alone (the sequence is the reference's): said with the refusal
+        if (!model_ok && ref_path) fprintf(stderr, "--ref cannot be combined with --realign %s: a k-mer model with levels is required, as `poregen transform` writes it\n", realign_model);
+        if (why || !model_ok) { print_help(fp_help, opt); return EXIT_FAILURE; }
     }
     if (event_model_path && devices.size() > 1) return die("--event_model works on one device: it cannot be combined with --devices of more than one device");
     if (event_model_path && devices.size() == 1) { device = devices[0]; devices.clear(); } // (one listed device: the single-device path)
@@ -684,13 +689,7 @@ int gmove_main(int argc, char **argv) {
         // every read's slice of the FASTA, and the batch -- I and D ops among its matches -- goes to the collector's generic walk.
         struct Slot { pg_mvops *ex = nullptr; pg_fit *fit = nullptr; pg_realign *ra = nullptr; PgDev<int16_t> sig; PgDev<uint64_t> sig_off; PgDev<double> cal;
                       PgDev<uint8_t> seq; PgDev<uint64_t> seq_off; };
-        uint64_t to_ref_skipped = 0, reverse_taken = 0;
-        std::string slice;
-        // --both_strands: the contigs go to the device the first time a batch names them (a name the FASTA lacks: index -1), and every
-        // read's slice is cut there (pg_refseq_slice), reversed and complemented for a reverse-strand record
-        pg_refseq *refseq = nullptr;
-        std::unordered_map<std::string, int32_t> contig_index;
-        std::vector<int32_t> rs_contig, rs_clen; std::vector<uint8_t> rs_reverse;
+        route.both_strands = both_strands; route.rna = opt.flag_rna != 0;
         Slot slots[2];
         pgh::MoveRecs rb;
         std::vector<pgh::Slow5File::RawView> views; std::vector<pgh::Slow5Rec> recs; std::vector<std::string> fetch_err;
@@ -702,7 +701,7 @@ int gmove_main(int argc, char **argv) {
                 if (sl.fit) pg_fit_destroy(sl.fit);
                 if (sl.ra) pg_realign_destroy(sl.ra);
                 if (sl.ex) pg_mvops_destroy(sl.ex);
-                if (refseq) { pg_refseq_destroy(refseq); refseq = nullptr; }
+                route.release();
                 sl.fit = nullptr; sl.ra = nullptr; sl.ex = nullptr; sl.sig.release(); sl.sig_off.release(); sl.cal.release(); sl.seq.release(); sl.seq_off.release();
             }
         };
@@ -730,7 +729,7 @@ int gmove_main(int argc, char **argv) {
             rb.clear();
             std::string bad; // why the record behind the batch's last read cannot be taken (empty: nothing wrong)
             while (rb.size() < this_batch_reads && rb.mv.size() < ((size_t)1 << 30)) {
-                const int nr = pgh::next_move_record(sam, raw, "gmove", bad, ref_path ? &to_ref_skipped : nullptr, both_strands ? &reverse_taken : nullptr);
+                const int nr = pgh::next_move_record(sam, raw, "gmove", bad, ref_path ? route.skipped_counter() : nullptr, route.reverse_counter());
                 if (nr == 0) eof = true;
                 if (nr <= 0) break;
                 rb.push(raw);
@@ -793,78 +792,26 @@ int gmove_main(int argc, char **argv) {
                 // what the collector takes: the expansion's arrays, or with --ref the projection's and the slices of the reference
                 const uint32_t *d_opn = mr.op_n; const uint8_t *d_opt = mr.op_t, *d_seq = mr.seq; const uint64_t *d_opoff = mr.op_off, *d_seqoff = mr.seq_off;
                 const int32_t *d_qs = mr.query_start, *d_ts = mr.target_start, *d_te = mr.target_end;
-                pg_mvops_projection pr; memset(&pr, 0, sizeof pr);
                 if (ref_path) {
-                    pg_mvops_cigars cg; memset(&cg, 0, sizeof cg);
-                    cg.n_reads = n; cg.location = PG_LOC_HOST; cg.flags = opt.flag_rna ? PG_MVOPS_RNA : 0;
-                    cg.op_n = mr.op_n; cg.n_ops = mr.n_ops; cg.op_off = mr.op_off; cg.query_start = mr.query_start; cg.status = mr.status;
-                    cg.cigar = rb.cigar.data(); cg.n_cigar = rb.cigar_off[n]; cg.cigar_off = rb.cigar_off.data(); cg.pos = rb.pos.data();
-                    pg_mvops_strands strands; memset(&strands, 0, sizeof strands);
-                    if (both_strands) { // the strand from the flag, the contig's length from the header, as reform --to_ref --both_strands has them
-                        rs_reverse.resize(n); rs_clen.resize(n);
-                        for (size_t i = 0; i < n; i++) { rs_reverse[i] = (rb.flag[i] & 0x10u) ? 1 : 0; rs_clen[i] = pgh::contig_len_of(rb.ref_len[i]); }
-                        strands.reverse = rs_reverse.data(); strands.contig_len = rs_clen.data();
-                    }
-                    if (pg_mvops_project_stranded(sl.ex, &cg, both_strands ? &strands : nullptr, &pr) != PG_OK) { fprintf(stderr, "[gmove] %s\n", pg_mvops_last_error(sl.ex)); status = EXIT_FAILURE; break; }
+                    bool cut = false;
+                    if (!route.project("gmove", sl.ex, rb, mr, n, bad, cut)) { status = EXIT_FAILURE; break; }
+                    if (cut) eof = false;
+                    const pg_mvops_projection &pr = route.pr;
                     d_opn = pr.op_n; d_opt = pr.op_t; d_opoff = pr.op_off; d_qs = pr.query_start; d_ts = pr.target_start; d_te = pr.target_end;
-                    if (pr.first_refused >= 0) { // reform --to_ref ends on this record: the reads in front of it are the batch
-                        n = (size_t)pr.first_refused; eof = false;
-                        const uint32_t code = pr.status_host[n];
-                        bad = pgh::reform_error((std::string(pgh::to_ref_refusal(code)) + " (status " + std::to_string(code) + ")").c_str(), rb.names[n]);
-                    }
                 } else if (mr.first_refused >= 0) { // reform returns -1 on this record: the reads in front of it are the batch
                     n = (size_t)mr.first_refused; eof = false;
                     bad = pgh::reform_error(pgh::reform_refusal(mr.status_host[n]), rb.names[n]);
                 }
                 uint64_t n_ops = 0, n_seq = 0; // an accepted read has as many ops as bases
                 for (size_t i = 0; i < n; i++) { n_ops += rb.l_seq[i]; n_seq += rb.l_seq[i]; }
-                if (both_strands && n) {
-                    if (!refseq && pg_refseq_create(ex_device, &refseq) != PG_OK) { fprintf(stderr, "[gmove] %s\n", pg_refseq_last_error(nullptr)); status = EXIT_FAILURE; break; }
-                    rs_contig.resize(n);
-                    bool ok = pg_refseq_set_stream(refseq, xs) == PG_OK;
-                    for (size_t i = 0; ok && i < n; i++) {
-                        auto it = contig_index.find(rb.rname[i]);
-                        if (it == contig_index.end()) {
-                            int32_t idx = -1; // the whole contig, its line ends stripped; a name the FASTA does not hold stays -1
-                            if (ref_fai.fetch(rb.rname[i], 0, INT64_MAX / 4, slice)) ok = pg_refseq_add(refseq, (const uint8_t *)slice.data(), slice.size(), &idx) == PG_OK;
-                            it = contig_index.emplace(rb.rname[i], idx).first;
-                        }
-                        rs_contig[i] = it->second;
-                    }
-                    pg_refseq_reads rr; memset(&rr, 0, sizeof rr);
-                    rr.n_reads = n; rr.location = PG_LOC_HOST; rr.contig = rs_contig.data(); rr.pos = rb.pos.data(); rr.ref_len = pr.ref_len_host; rr.reverse = rs_reverse.data();
-                    pg_refseq_slices rsl; memset(&rsl, 0, sizeof rsl);
-                    if (!ok || pg_refseq_slice(refseq, &rr, &rsl) != PG_OK) { fprintf(stderr, "[gmove] %s\n", pg_refseq_last_error(refseq)); status = EXIT_FAILURE; break; }
-                    n_seq = rsl.n_seq;
-                    if (!hip_ok(hipMemcpy(&n_ops, pr.op_off + n, sizeof n_ops, hipMemcpyDeviceToHost), "hipMemcpy")) break;
-                    d_seq = rsl.seq; d_seqoff = rsl.seq_off; // the handle's, until its next batch
+                if (ref_path && n) {
+                    if (!route.slices("gmove", hip_ok, ex_device, xs, rb, n)) { status = EXIT_FAILURE; break; }
+                    n_ops = route.n_ops; n_seq = route.n_seq;
+                    d_seq = route.d_seq; d_seqoff = route.d_seqoff; // --both_strands: the refseq handle's, until its next batch (--ref alone: the slices are the host's)
                     if (!dev.job) { // two batches are in flight: the slices move to the slot's own buffers, on the expander's stream
-                        if (!hip_ok(sl.seq.ensure(n_seq ? n_seq : 1, n_seq + n_seq / 4 + 256), "hipMalloc") || !hip_ok(sl.seq_off.ensure((n + 1) * 8, (n + 1) * 10), "hipMalloc") ||
-                            (n_seq && !hip_ok(hipMemcpyAsync(sl.seq.p, rsl.seq, n_seq, hipMemcpyDeviceToDevice, xs), "hipMemcpyAsync")) ||
-                            !hip_ok(hipMemcpyAsync(sl.seq_off.p, rsl.seq_off, (n + 1) * 8, hipMemcpyDeviceToDevice, xs), "hipMemcpyAsync") ||
-                            !hip_ok(hipStreamSynchronize(xs), "hipStreamSynchronize")) break;
+                        if (!route.to_device(hip_ok, xs, n, sl.seq, sl.seq_off)) break;
                         d_seq = sl.seq.p; d_seqoff = sl.seq_off.p;
-                    }
-                } else if (ref_path && n) {
-                    // faidx_fetch_seq(m_fai, tid, st_k, end_k - 1) with st_k / end_k = min / max of the target columns, as the PAF front-end
-                    // does it; a name the FASTA does not hold gives an empty slice, and the device skips the read
-                    hb.seq.clear(); hb.seq_off.assign(1, 0);
-                    for (size_t i = 0; i < n; i++) {
-                        const int32_t lo = rb.pos[i], hi = (int32_t)((uint32_t)rb.pos[i] + pr.ref_len_host[i]);
-                        const int64_t a = opt.flag_rna ? hi : lo, b2 = opt.flag_rna ? lo : hi;
-                        const int64_t st_k = (uint64_t)a > (uint64_t)b2 ? b2 : a, end_k = (uint64_t)a > (uint64_t)b2 ? a : b2;
-                        ref_fai.fetch(rb.rname[i], (int)st_k, (int)(end_k - 1), slice);
-                        hb.seq.insert(hb.seq.end(), slice.begin(), slice.end()); hb.seq_off.push_back(hb.seq.size());
-                    }
-                    n_seq = hb.seq.size();
-                    if (!hip_ok(hipMemcpy(&n_ops, pr.op_off + n, sizeof n_ops, hipMemcpyDeviceToHost), "hipMemcpy")) break;
-                    if (!dev.job) {
-                        if (!hip_ok(sl.seq.ensure(n_seq ? n_seq : 1, n_seq + n_seq / 4 + 256), "hipMalloc") || !hip_ok(sl.seq_off.ensure((n + 1) * 8, (n + 1) * 10), "hipMalloc") ||
-                            (n_seq && !hip_ok(hipMemcpyAsync(sl.seq.p, hb.seq.data(), n_seq, hipMemcpyHostToDevice, xs), "hipMemcpyAsync")) ||
-                            !hip_ok(hipMemcpyAsync(sl.seq_off.p, hb.seq_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, xs), "hipMemcpyAsync") ||
-                            !hip_ok(hipStreamSynchronize(xs), "hipStreamSynchronize")) break;
-                        d_seq = sl.seq.p; d_seqoff = sl.seq_off.p;
-                    }
+                    } else if (!both_strands) { hb.seq = route.h_seq; hb.seq_off = route.h_seqoff; }
                 }
                 total_samples += hb.sig_off[n];
                 for (size_t i = 0; i < n; i++) if (++count_reads % 10000 == 0) fprintf(stderr, "*"); // PROGRESS_BATCH_SIZE
@@ -891,6 +838,7 @@ int gmove_main(int argc, char **argv) {
                     b.query_start = d_qs; b.target_start = d_ts; b.target_end = d_te; b.seq = d_seq; b.seq_off = d_seqoff;
                     b.op_n = d_opn; b.op_t = d_opt; b.op_off = d_opoff;
                     if (!ref_path) b.flags = PG_BATCH_ALL_MATCHES; // every op is a match and a read has as many ops as bases: what `reform` writes
+                    else if (realign_model) b.flags = PG_BATCH_GAPPED; // fit and realign walk the projected ops over the reference slices; the collector ignores the flag
                     if (realign_model) { // the rounds on the device batch; the collector takes the last round's ops
                         if (!realign_handles(sl, ex_device)) { status = EXIT_FAILURE; break; }
                         if (!rounds.run(sl.fit, sl.fit, sl.ra, b, realign_rounds)) { fprintf(stderr, "[gmove] %s\n", rounds.err.c_str()); status = EXIT_FAILURE; break; }
@@ -920,8 +868,7 @@ int gmove_main(int argc, char **argv) {
         // the device has read the last batch's ops before the expanders go
         if (dev.ok() && dev.sync() != PG_OK && status == EXIT_SUCCESS) { fprintf(stderr, "[gmove] %s\n", dev.error()); status = EXIT_FAILURE; }
         release();
-        if (both_strands) pgh::print_both_strands_skipped("gmove", to_ref_skipped, reverse_taken);
-        else if (ref_path) pgh::print_to_ref_skipped("gmove", to_ref_skipped);
+        if (ref_path) route.print_skipped("gmove");
         if (rt && fclose(rt) != 0 && status == EXIT_SUCCESS) { fprintf(stderr, "Error in writing %s.\n", realign_table); status = EXIT_FAILURE; }
         if (realign_model && verbose >= 4)
             fprintf(stderr, "[gmove] realign: k=%u band=%lld rounds=%lld reads=%llu refined=%llu free=%llu moved=%llu\n", realign_k, realign_band, realign_rounds,

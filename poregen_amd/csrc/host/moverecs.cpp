@@ -18,7 +18,7 @@ bool MoveSignalBatches::next(std::string &bad) {
             take();
             continue;
         }
-        const int nr = next_move_record(sam_, raw_, tool_, bad);
+        const int nr = next_move_record(sam_, raw_, tool_, bad, to_ref_skipped, reverse_taken);
         if (nr == 0) eof_ = true;
         if (nr <= 0) return nr == 0;
         std::string e2;

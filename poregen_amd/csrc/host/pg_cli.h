@@ -1,17 +1,22 @@
 // pg_cli.h -- what the subcommands that run on the device share besides the file readers (pg_host.h): the error exit, option values,
 // file suffixes, the HIP check, and for `fit` and `realign` the model, the batch handed to pg_fit_* and the per-k-mer table; the rounds of
-// fit and realign that `realign --rounds` and `gmove --reform --realign` share.
+// fit and realign that `realign --rounds` and `gmove --reform --realign` share; the --ref route (RefRoute) that `gmove --reform --ref`,
+// `fit --ref` and `realign --ref` share.
 // (`transform` words its errors its own way and is built without HIP: it does not include this.)
 #pragma once
 #include "../../../include/pgmove.h"
 #include "../pg_fit.h"
 #include "../pg_hip_host.h"
 #include "pg_host.h"
+#include "pg_moverecs.h"
 
+#include <climits>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 inline int die(const char *fmt, const std::string &a = "") { fprintf(stderr, fmt, a.c_str()); fputc('\n', stderr); return EXIT_FAILURE; }
@@ -68,9 +73,9 @@ inline bool load_level_model(const char *tool, const char *path, long long k_opt
 
 // a read's status as the tables print it: fit's own, or the code of the expansion for a read reform refuses (PG_FIT_ST_SKIPPED + code)
 inline const char *fit_status_name(uint32_t st) {
-    static const char *const kFit[] = {"ok", "out_of_signal", "too_long", "few_events", "flat", "negative_scale"};
+    static const char *const kFit[] = {"ok", "out_of_signal", "too_long", "few_events", "flat", "negative_scale", "ref_length"};
     static const char *const kReform[] = {"", "no_move_in_table", "negative_tail", "bases_left_over", "bad_stride"};
-    if (st < 6) return kFit[st];
+    if (st < 7) return kFit[st];
     if (st > PG_FIT_ST_SKIPPED && st < PG_FIT_ST_SKIPPED + 5) return kReform[st - PG_FIT_ST_SKIPPED];
     return "refused";
 }
@@ -148,3 +153,107 @@ inline int write_kmer_table(const char *path, uint32_t k, bool uses_u, const std
     }
     return fclose(kf) == 0 ? EXIT_SUCCESS : die("Error in writing %s.", path);
 }
+
+// ---- the --ref route that `gmove --reform --ref`, `fit --ref` and `realign --ref` share ----------------------------------------------------
+// Per batch, behind pg_mvops_expand: the ops are carried through the records' CIGARs onto the reference on the expander
+// (pg_mvops_project[_stranded]), and every read's slice of the FASTA is fetched -- on the host (faidx_fetch_seq over the target columns,
+// as the PAF front-end does it), or with --both_strands cut on the device (pg_refseq_slice), reversed and complemented for a
+// reverse-strand record. The records that are not taken are skipped and counted by pgh::next_move_record.
+struct RefRoute {
+    pgh::FastxIndex fai;
+    bool both_strands = false, rna = false;
+    uint64_t skipped = 0, reverse_taken = 0;   // the counters next_move_record fills
+    pg_mvops_projection pr;                    // the last batch's projection: the expander's arrays, until its next project
+    uint64_t n_ops = 0, n_seq = 0;             // the last batch's ops and bases
+    std::vector<uint8_t> h_seq; std::vector<uint64_t> h_seqoff; // the slices on the host (without --both_strands)
+    const uint8_t *d_seq = nullptr; const uint64_t *d_seqoff = nullptr; // --both_strands: the slices on the device, the refseq handle's until its next batch
+    pg_refseq *refseq = nullptr;
+    std::unordered_map<std::string, int32_t> contig_index;
+    std::vector<int32_t> contig, clen; std::vector<uint8_t> reverse;
+    std::string slice;
+    RefRoute() { memset(&pr, 0, sizeof pr); }
+    ~RefRoute() { release(); }
+    RefRoute(const RefRoute &) = delete; RefRoute &operator=(const RefRoute &) = delete;
+    void release() { if (refseq) { pg_refseq_destroy(refseq); refseq = nullptr; } }
+    uint64_t *skipped_counter() { return &skipped; }
+    uint64_t *reverse_counter() { return both_strands ? &reverse_taken : nullptr; }
+    void print_skipped(const char *tool) const {
+        if (both_strands) pgh::print_both_strands_skipped(tool, skipped, reverse_taken); else pgh::print_to_ref_skipped(tool, skipped);
+    }
+    // The projection of the first n records of rb, expanded into mr on ex. A record reform --to_ref ends on cuts the batch in front of
+    // it: n shrinks and `bad` gets reform's line. false: the library's error is on stderr.
+    bool project(const char *tool, pg_mvops *ex, const pgh::MoveRecs &rb, const pg_mvops_result &mr, size_t &n, std::string &bad, bool &cut) {
+        pg_mvops_cigars cg; memset(&cg, 0, sizeof cg);
+        cg.n_reads = n; cg.location = PG_LOC_HOST; cg.flags = rna ? PG_MVOPS_RNA : 0;
+        cg.op_n = mr.op_n; cg.n_ops = mr.n_ops; cg.op_off = mr.op_off; cg.query_start = mr.query_start; cg.status = mr.status;
+        cg.cigar = rb.cigar.data(); cg.n_cigar = rb.cigar_off[n]; cg.cigar_off = rb.cigar_off.data(); cg.pos = rb.pos.data();
+        pg_mvops_strands strands; memset(&strands, 0, sizeof strands);
+        if (both_strands) { // the strand from the flag, the contig's length from the header, as reform --to_ref --both_strands has them
+            reverse.resize(n); clen.resize(n);
+            for (size_t i = 0; i < n; i++) { reverse[i] = (rb.flag[i] & 0x10u) ? 1 : 0; clen[i] = pgh::contig_len_of(rb.ref_len[i]); }
+            strands.reverse = reverse.data(); strands.contig_len = clen.data();
+        }
+        cut = false;
+        if (pg_mvops_project_stranded(ex, &cg, both_strands ? &strands : nullptr, &pr) != PG_OK) { fprintf(stderr, "[%s] %s\n", tool, pg_mvops_last_error(ex)); return false; }
+        if (pr.first_refused >= 0) { // reform --to_ref ends on this record: the reads in front of it are the batch
+            n = (size_t)pr.first_refused; cut = true;
+            const uint32_t code = pr.status_host[n];
+            bad = pgh::reform_error((std::string(pgh::to_ref_refusal(code)) + " (status " + std::to_string(code) + ")").c_str(), rb.names[n]);
+        }
+        return true;
+    }
+    // The slices of the first n records (behind project), and n_ops / n_seq. false: the error is on stderr (HIP's through hip_ok).
+    bool slices(const char *tool, const HipOk &hip_ok, int device, hipStream_t xs, const pgh::MoveRecs &rb, size_t n) {
+        n_ops = n_seq = 0; d_seq = nullptr; d_seqoff = nullptr;
+        if (!n) return true;
+        if (both_strands) {
+            if (!refseq && pg_refseq_create(device, &refseq) != PG_OK) { fprintf(stderr, "[%s] %s\n", tool, pg_refseq_last_error(nullptr)); *hip_ok.status = EXIT_FAILURE; return false; }
+            contig.resize(n);
+            bool ok = pg_refseq_set_stream(refseq, xs) == PG_OK;
+            for (size_t i = 0; ok && i < n; i++) {
+                auto it = contig_index.find(rb.rname[i]);
+                if (it == contig_index.end()) {
+                    int32_t idx = -1; // the whole contig, its line ends stripped; a name the FASTA does not hold stays -1
+                    if (fai.fetch(rb.rname[i], 0, INT64_MAX / 4, slice)) ok = pg_refseq_add(refseq, (const uint8_t *)slice.data(), slice.size(), &idx) == PG_OK;
+                    it = contig_index.emplace(rb.rname[i], idx).first;
+                }
+                contig[i] = it->second;
+            }
+            pg_refseq_reads rr; memset(&rr, 0, sizeof rr);
+            rr.n_reads = n; rr.location = PG_LOC_HOST; rr.contig = contig.data(); rr.pos = rb.pos.data(); rr.ref_len = pr.ref_len_host; rr.reverse = reverse.data();
+            pg_refseq_slices rsl; memset(&rsl, 0, sizeof rsl);
+            if (!ok || pg_refseq_slice(refseq, &rr, &rsl) != PG_OK) { fprintf(stderr, "[%s] %s\n", tool, pg_refseq_last_error(refseq)); *hip_ok.status = EXIT_FAILURE; return false; }
+            n_seq = rsl.n_seq; d_seq = rsl.seq; d_seqoff = rsl.seq_off;
+        } else {
+            // faidx_fetch_seq(m_fai, tid, st_k, end_k - 1) with st_k / end_k = min / max of the target columns, as the PAF front-end
+            // does it; a name the FASTA does not hold gives an empty slice, and the device skips the read
+            h_seq.clear(); h_seqoff.assign(1, 0);
+            for (size_t i = 0; i < n; i++) {
+                const int32_t lo = rb.pos[i], hi = (int32_t)((uint32_t)rb.pos[i] + pr.ref_len_host[i]);
+                const int64_t a = rna ? hi : lo, b2 = rna ? lo : hi;
+                const int64_t st_k = (uint64_t)a > (uint64_t)b2 ? b2 : a, end_k = (uint64_t)a > (uint64_t)b2 ? a : b2;
+                fai.fetch(rb.rname[i], (int)st_k, (int)(end_k - 1), slice);
+                h_seq.insert(h_seq.end(), slice.begin(), slice.end()); h_seqoff.push_back(h_seq.size());
+            }
+            n_seq = h_seq.size();
+        }
+        return hip_ok(hipMemcpy(&n_ops, pr.op_off + n, sizeof n_ops, hipMemcpyDeviceToHost), "hipMemcpy");
+    }
+    // The slices in the caller's own device buffers, on stream xs, complete when this returns (two batches may be in flight).
+    bool to_device(const HipOk &hip_ok, hipStream_t xs, size_t n, PgDev<uint8_t> &seq, PgDev<uint64_t> &seq_off) {
+        const void *src = both_strands ? (const void *)d_seq : (const void *)h_seq.data(), *src_off = both_strands ? (const void *)d_seqoff : (const void *)h_seqoff.data();
+        const hipMemcpyKind kind = both_strands ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+        return hip_ok(seq.ensure(n_seq ? n_seq : 1, n_seq + n_seq / 4 + 256), "hipMalloc") && hip_ok(seq_off.ensure((n + 1) * 8, (n + 1) * 10), "hipMalloc") &&
+               (!n_seq || hip_ok(hipMemcpyAsync(seq.p, src, n_seq, kind, xs), "hipMemcpyAsync")) && hip_ok(hipMemcpyAsync(seq_off.p, src_off, (n + 1) * 8, kind, xs), "hipMemcpyAsync") &&
+               hip_ok(hipStreamSynchronize(xs), "hipStreamSynchronize");
+    }
+    // the batch fit and realign take: the projection's ops over the slices in `seq` / `seq_off` (to_device), flagged PG_BATCH_GAPPED
+    pg_batch gapped_batch(size_t n, const int16_t *sig, const uint64_t *sig_off, const uint8_t *seq, const uint64_t *seq_off) const {
+        pg_batch b; memset(&b, 0, sizeof b);
+        b.struct_size = sizeof b; b.location = PG_LOC_DEVICE; b.n_reads = (uint32_t)n; b.n_ops = (uint32_t)n_ops;
+        b.sig = sig; b.sig_off = sig_off; b.query_start = pr.query_start; b.target_start = pr.target_start; b.target_end = pr.target_end;
+        b.seq = seq; b.seq_off = seq_off; b.op_n = pr.op_n; b.op_t = pr.op_t; b.op_off = pr.op_off;
+        b.flags = PG_BATCH_GAPPED;
+        return b;
+    }
+};

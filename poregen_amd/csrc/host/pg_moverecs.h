@@ -97,6 +97,8 @@ public:
         : sam_(sam), s5_(s5), tool_(tool), max_reads_(max_reads), soft_(soft), hard_(hard) {}
     // the batch: record i's samples are sig[sig_off[i] .. sig_off[i + 1])
     MoveRecs recs; std::vector<int16_t> sig; std::vector<uint64_t> sig_off{0}; std::vector<double> dig, off, range;
+    // --ref: the records next_move_record steps over are counted here (null: every record is taken, as without --ref)
+    uint64_t *to_ref_skipped = nullptr, *reverse_taken = nullptr;
     // Fills the next batch. false: `bad` says why the run ends behind this batch, which still holds the reads in front of the record.
     bool next(std::string &bad);
     bool done() const { return eof_ && !pending_; }

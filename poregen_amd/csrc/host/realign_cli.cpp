@@ -31,16 +31,26 @@ const struct option kLongOptions[] = {
     {"read_table", required_argument, nullptr, 0}, // 10
     {"rounds", required_argument, nullptr, 0},     // 11
     {"help", no_argument, nullptr, 'h'},           // 12
+    {"ref", required_argument, nullptr, 0},        // 13
+    {"both_strands", no_argument, nullptr, 0},     // 14
+    {"rc_suffix", required_argument, nullptr, 0},  // 15
     {nullptr, 0, nullptr, 0}};
 
 void print_help(FILE *fp) {
     fprintf(fp, "Usage: poregen realign [options] MODEL reads.slow5/blow5 reads.bam/sam\n");
+    fprintf(fp, "       poregen realign --ref REF.fa [--both_strands] [--rc_suffix STR] [options] MODEL reads.slow5/blow5 mapped.bam/sam\n");
     fprintf(fp, "\nrefine the event boundaries of the move table against a k-mer model; writes PAF with ss:Z: as `reform -c -k 1` does\n");
     fprintf(fp, "\noptions:\n");
     fprintf(fp, "   -k INT                     k-mer length; must be the model's [the model's]\n");
     fprintf(fp, "   -m INT                     move start offset [0]\n");
     fprintf(fp, "   --rna                      the dataset is direct RNA\n");
     fprintf(fp, "   --n_to_t                   an N of a read counts as T\n");
+    fprintf(fp, "   --ref REF.fa               a MAPPED .bam / .sam: refine the signal-to-reference alignment -- the ops carried through each record's CIGAR on the\n");
+    fprintf(fp, "                              GPU, the k-mers the record's slice of REF.fa spells; an I or a D pins the boundaries beside it and keeps its length.\n");
+    fprintf(fp, "                              -o is the PAF `reform -c -k 1 -m 0 --stride 0 --to_ref` prints, with the refined durations (--band 0: that PAF).\n");
+    fprintf(fp, "                              Unmapped and reverse-strand records are skipped and counted. Not with --n_to_t\n");
+    fprintf(fp, "   --both_strands             with --ref: reverse-strand records are taken too, as `reform --to_ref --both_strands` writes them\n");
+    fprintf(fp, "   --rc_suffix STR            with --both_strands: the suffix of a reverse-strand record's target name [_rc]\n");
     fprintf(fp, "   --min_dur INT              minimum number of samples of an event that is refined [5]\n");
     fprintf(fp, "   --max_dur INT              maximum number of samples of an event that is refined, at most %u [70]\n", PG_RL_MAX_DUR);
     fprintf(fp, "   --min_events INT           counted events a read needs to be fitted [20]\n");
@@ -61,7 +71,8 @@ void print_help(FILE *fp) {
 int realign_main(int argc, char **argv) {
     long long k_opt = 0, m = 0, min_dur = 5, max_dur = 70, min_events = 20, batch_reads = 4000, device = 0, min_len = 3, band = 10, rounds = 1;
     bool rna = false, n_to_t = false, help = false;
-    const char *out_path = nullptr, *kmer_path = nullptr, *read_path = nullptr;
+    const char *out_path = nullptr, *kmer_path = nullptr, *read_path = nullptr, *ref_path = nullptr, *rc_suffix = nullptr;
+    bool both_strands = false;
     int c, longindex = 0;
     optind = 1;
     while ((c = getopt_long(argc, argv, "k:m:o:h", kLongOptions, &longindex)) >= 0) {
@@ -82,6 +93,9 @@ int realign_main(int argc, char **argv) {
         else if (c == 0 && longindex == 9) ok = whole_int(optarg, 0, PG_RL_MAX_BAND, band);
         else if (c == 0 && longindex == 10) read_path = optarg;
         else if (c == 0 && longindex == 11) ok = whole_int(optarg, 1, 8, rounds);
+        else if (c == 0 && longindex == 13) ref_path = optarg;
+        else if (c == 0 && longindex == 14) both_strands = true;
+        else if (c == 0 && longindex == 15) rc_suffix = optarg;
         else { print_help(stderr); return EXIT_FAILURE; }
         if (!ok) {
             fprintf(stderr, "[realign] %s%s: '%s' is not a value it takes (-k 1..9, -m 0..64, durations 0..%u, --min_len from 1, --band 0..%u, --rounds 1..8)\n", c ? "-" : "--",
@@ -93,11 +107,21 @@ int realign_main(int argc, char **argv) {
     if (argc - optind != 3) { print_help(stderr); return EXIT_FAILURE; }
     if (min_dur > max_dur) return die("[realign] --min_dur may not exceed --max_dur");
     if (min_len > min_dur) return die("[realign] --min_len may not exceed --min_dur");
+    if (both_strands && !ref_path) return die("[realign] --both_strands applies with --ref only");
+    if (rc_suffix && !both_strands) return die("[realign] --rc_suffix applies with --both_strands only");
+    if (ref_path && n_to_t) return die("[realign] --ref cannot be combined with --n_to_t: the sequence is the reference's, there is nothing to rewrite");
+    if (!rc_suffix) rc_suffix = "_rc";
     const char *model_path = argv[optind], *slow5_path = argv[optind + 1], *sam_path = argv[optind + 2];
     if (!is_sam_or_bam(sam_path)) return die("[realign] the records come from a .bam or .sam file, not %s", sam_path);
     std::vector<uint32_t> levels;
     uint32_t k = 0; int32_t uses_u = 0;
     if (!load_level_model("realign", model_path, k_opt, levels, k, uses_u)) return EXIT_FAILURE;
+    RefRoute route; // --ref: the FASTA, the projection and the slices of every batch
+    route.both_strands = both_strands; route.rna = rna;
+    if (ref_path) {
+        std::string ferr;
+        if (!route.fai.load(ref_path, ferr)) { fprintf(stderr, "Error in loading the reference %s%s%s\n", ref_path, ferr.empty() ? "" : ": ", ferr.c_str()); return EXIT_FAILURE; }
+    }
     const uint64_t n_slots = 1ull << (2 * k);
     std::string err;
     pgh::Slow5File s5;
@@ -129,12 +153,13 @@ int realign_main(int argc, char **argv) {
     const hipStream_t xs = (hipStream_t)pg_mvops_stream(ex);
     if (pg_fit_set_stream(fit, xs) != PG_OK || pg_fit_set_stream(fit2, xs) != PG_OK || (fitm && pg_fit_set_stream(fitm, xs) != PG_OK) || pg_realign_set_stream(ra, xs) != PG_OK) { fprintf(stderr, "[realign] cannot share the expander's stream\n"); status = EXIT_FAILURE; }
 
-    PgDev<int16_t> d_sig; PgDev<uint64_t> d_sigoff;
-    std::vector<uint32_t> h_ops; std::vector<int32_t> h_qs;
+    PgDev<int16_t> d_sig; PgDev<uint64_t> d_sigoff; PgDev<uint8_t> d_seq; PgDev<uint64_t> d_seqoff;
+    std::vector<uint32_t> h_ops; std::vector<int32_t> h_qs, h_ts, h_te; std::vector<uint8_t> h_opt; std::vector<uint64_t> h_opoff;
     RealignRounds rr;
     pgh::MoveSignalBatches in(sam, s5, "realign", (size_t)batch_reads, (size_t)(PG_FIT_BATCH_SAMPLES / 2), (size_t)PG_FIT_BATCH_SAMPLES);
     const pgh::MoveRecs &rb = in.recs;
     const HipOk hip_ok{"realign", &status};
+    if (ref_path) { in.to_ref_skipped = route.skipped_counter(); in.reverse_taken = route.reverse_counter(); }
     while (!in.done() && status == EXIT_SUCCESS) {
         // ---- the records: the first one that cannot be taken ends the run behind the reads in front of it, with gmove --reform's message
         std::string bad;
@@ -146,24 +171,45 @@ int realign_main(int argc, char **argv) {
             rb.fill(mb, n, (rna ? PG_MVOPS_RNA : 0) | (n_to_t ? PG_MVOPS_N_TO_T : 0));
             pg_mvops_result mr;
             if (pg_mvops_expand(ex, &mb, &mr) != PG_OK) { fprintf(stderr, "[realign] %s\n", pg_mvops_last_error(ex)); status = EXIT_FAILURE; break; }
-            if (mr.first_refused >= 0) { // reform returns -1 on this record: the reads in front of it are the batch, and the last one
+            if (ref_path) { // the ops onto the reference and the slices of REF.fa; a record reform --to_ref ends on ends the run behind the reads in front
+                bool cut = false;
+                if (!route.project("realign", ex, rb, mr, n, bad, cut)) { status = EXIT_FAILURE; break; }
+                if (!route.slices("realign", hip_ok, (int)device, xs, rb, n) || (n && !route.to_device(hip_ok, xs, n, d_seq, d_seqoff))) { status = EXIT_FAILURE; break; }
+            } else if (mr.first_refused >= 0) { // reform returns -1 on this record: the reads in front of it are the batch, and the last one
                 n = (size_t)mr.first_refused;
                 bad = pgh::reform_error(pgh::reform_refusal(mr.status_host[n]), rb.names[n]);
             }
             uint64_t n_ops = 0; // an accepted read has as many ops as bases
             for (size_t i = 0; i < n; i++) n_ops += rb.l_seq[i];
+            if (ref_path) n_ops = route.n_ops;
             if (n_ops > 0xffffffffull) { fprintf(stderr, "[realign] a batch of more than 2^32 - 1 bases: use a smaller --batch_reads\n"); status = EXIT_FAILURE; break; }
             if (n) {
-                const pg_batch b = device_batch(mr, n, n_ops, d_sig.p, d_sigoff.p);
+                const pg_batch b = ref_path ? route.gapped_batch(n, d_sig.p, d_sigoff.p, d_seq.p, d_seqoff.p) : device_batch(mr, n, n_ops, d_sig.p, d_sigoff.p);
                 pg_fit_reads fr2;
                 if (!rr.run(fit, fitm, ra, b, rounds)) { fprintf(stderr, "[realign] %s\n", rr.err.c_str()); status = EXIT_FAILURE; break; }
                 pg_batch b2 = b; b2.op_n = rr.op_n;
                 if (pg_fit_submit(fit2, &b2, nullptr, &fr2) != PG_OK) { fprintf(stderr, "[realign] %s\n", pg_fit_last_error(fit2)); status = EXIT_FAILURE; break; }
                 h_ops.resize(n_ops); h_qs.resize(n);
                 if ((n_ops && !hip_ok(hipMemcpy(h_ops.data(), rr.op_n, n_ops * 4, hipMemcpyDeviceToHost), "hipMemcpy")) ||
-                    !hip_ok(hipMemcpy(h_qs.data(), mr.query_start, n * 4, hipMemcpyDeviceToHost), "hipMemcpy")) break;
+                    !hip_ok(hipMemcpy(h_qs.data(), b.query_start, n * 4, hipMemcpyDeviceToHost), "hipMemcpy")) break;
+                if (ref_path) { // the line reform --to_ref prints, the refined durations in its ss:Z:
+                    const pg_mvops_projection &pr = route.pr;
+                    h_ts.resize(n); h_te.resize(n); h_opt.resize(n_ops); h_opoff.resize(n + 1);
+                    if (!hip_ok(hipMemcpy(h_ts.data(), pr.target_start, n * 4, hipMemcpyDeviceToHost), "hipMemcpy") || !hip_ok(hipMemcpy(h_te.data(), pr.target_end, n * 4, hipMemcpyDeviceToHost), "hipMemcpy") ||
+                        (n_ops && !hip_ok(hipMemcpy(h_opt.data(), pr.op_t, n_ops, hipMemcpyDeviceToHost), "hipMemcpy")) ||
+                        !hip_ok(hipMemcpy(h_opoff.data(), pr.op_off, (n + 1) * 8, hipMemcpyDeviceToHost), "hipMemcpy")) break;
+                    for (size_t i = 0; i < n; i++) {
+                        const bool reverse = both_strands && (rb.flag[i] & 0x10u);
+                        const char *id = rb.names[i].c_str();
+                        fprintf(fp, "%s\t%" PRIu64 "\t%d\t%d\t%c\t%s%s\t%" PRId64 "\t%d\t%d\t%" PRIu32 "\t%" PRIu32 "\t255\tss:Z:", id, rb.ns[i], h_qs[i], pr.query_end_host[i], reverse ? '-' : '+',
+                                rb.rname[i].c_str(), reverse ? rc_suffix : "", rb.ref_len[i], h_ts[i], h_te[i], pr.n_match_host[i], pr.ref_len_host[i]);
+                        for (uint64_t e = h_opoff[i]; e < h_opoff[i + 1]; e++) fprintf(fp, "%" PRIu32 "%c", h_ops[e], ",ID"[h_opt[e] < 3 ? h_opt[e] : 0]);
+                        fputc('\n', fp);
+                        if (rf) rr.row(rf, id, i);
+                    }
+                }
                 uint64_t at = 0;
-                for (size_t i = 0; i < n; i++) {
+                for (size_t i = 0; !ref_path && i < n; i++) {
                     const uint32_t lb = rb.l_seq[i];
                     uint64_t end = (uint64_t)(int64_t)h_qs[i];
                     for (uint32_t e = 0; e < lb; e++) end += h_ops[at + e];
@@ -188,7 +234,9 @@ int realign_main(int argc, char **argv) {
                 rounds_text.c_str(), (unsigned long long)res.reads, (unsigned long long)res.fitted, (unsigned long long)rr.n_free, (unsigned long long)rr.n_moved, pooled_rms(res, n_slots).c_str(),
                 pooled_rms(res2, n_slots).c_str());
     }
+    if (ref_path) route.print_skipped("realign");
     finish_files();
+    route.release();
     release();
     return status;
 }

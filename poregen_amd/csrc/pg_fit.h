@@ -61,8 +61,10 @@ static_assert(20 + 18 < 63 && 20 + 2 * 18 < 63, "an event's sum d and sum d^2 fi
 static_assert(28 + 2 * 18 <= 64, "a batch's sum d^2 per slot fits a uint64: 2^28 (2^18 - 1)^2 < 2^64");
 static_assert(PG_FIT_PIECE % PG_FIT_STEP == 0 && PG_FIT_STEP == 64, "a step is one op per lane of a wave");
 
-enum { PG_FIT_OK = 0, PG_FIT_OUT_OF_SIGNAL = 1, PG_FIT_TOO_LONG = 2, PG_FIT_FEW_EVENTS = 3, PG_FIT_FLAT = 4, PG_FIT_NEGATIVE_SCALE = 5,
+enum { PG_FIT_OK = 0, PG_FIT_OUT_OF_SIGNAL = 1, PG_FIT_TOO_LONG = 2, PG_FIT_FEW_EVENTS = 3, PG_FIT_FLAT = 4, PG_FIT_NEGATIVE_SCALE = 5, PG_FIT_REF_LENGTH = 6,
        PG_FIT_SKIPPED = 16 }; // PG_FIT_SKIPPED + c: the caller's skip code c (the expander's status of a read reform refuses)
+enum { PG_FIT_OP_MATCH = 0, PG_FIT_OP_I = 1, PG_FIT_OP_D = 2 }; // op_t of a gapped batch
+#define PG_FIT_MAX_SLICE 0xffffffffull       // bases of a gapped read's reference slice at most: a column of a read that takes part fits 32 bits
 
 struct PgFitSums { int64_t n, sl, sll, sr, srl, srr, e; }; // 56 bytes per read
 
@@ -89,6 +91,27 @@ template <class Seq> PG_FIT_HD int32_t pg_fit_code(const Seq seq, uint32_t first
     return code;
 }
 PG_FIT_HD bool pg_fit_dur_ok(uint32_t n, uint32_t min_dur, uint32_t max_dur) { return n >= min_dur && n <= max_dur; }
+
+// ---- the gapped rule (PG_BATCH_GAPPED): ops on the signal-to-reference alignment ---------------------------------------------------------
+// op_t is 0 (match), 1 (I) or 2 (D), and seq is the read's reference slice of S bases. A match of n and an I of n take n samples, a D takes
+// none; a match takes one reference column, a D of n takes n, an I none. c_j is the column in front of op j, C the read's total; a read with
+// S != C is ref_length (behind out_of_signal) and no kernel reads its seq. Event j counts iff it is a match, ops j - m .. j - m + k - 1 all
+// exist and are all matches (a clean window: its columns are consecutive), min_dur <= n_j <= max_dur, and its k-mer -- seq[c_j - m,
+// c_j - m + k), with rna seq[S - (c_j - m) - k, S - (c_j - m)) -- lies inside the slice, has ACGT letters and a level. On a batch of only
+// matches with S = Lb this is the rule above. Bounds: a read has fewer than 2^31 ops of fewer than 2^32 columns, so C < 2^63 (a uint64 per
+// piece and per read); a read takes part only with C == S <= PG_FIT_MAX_SLICE, so inside a kernel every column fits 32 bits.
+PG_FIT_HD uint32_t pg_fit_op_samples(uint32_t t, uint32_t n) { return t == PG_FIT_OP_D ? 0u : n; }
+PG_FIT_HD uint32_t pg_fit_op_cols(uint32_t t, uint32_t n) { return t == PG_FIT_OP_MATCH ? 1u : t == PG_FIT_OP_D ? n : 0u; }
+// The k-mer of event e (a match) of a gapped read of lb ops whose column is col: false when it carries none, else its first base in seq.
+// Reads at most k bytes of op_t, all inside the read, and names no base outside [0, S).
+template <class Ops> PG_FIT_HD bool pg_fit_gap_kmer_at(const Ops op_t, uint32_t lb, uint32_t S, uint32_t k, uint32_t m, bool rna, uint32_t e, uint32_t col, uint32_t &first) {
+    if (e < m || e >= lb || lb < k || e - m > lb - k) return false;
+    for (uint32_t j = 0; j < k; j++)
+        if (op_t[e - m + j] != PG_FIT_OP_MATCH) return false;
+    if (col < m || S < k || col - m > S - k) return false;
+    first = rna ? S - (col - m) - k : col - m;
+    return true;
+}
 
 PG_FIT_HD void pg_fit_add(PgFitSums &s, int32_t r, int32_t l) {
     s.n += 1; s.sl += l; s.sll += (int64_t)l * l; s.sr += r; s.srl += (int64_t)r * l; s.srr += (int64_t)r * r;
@@ -262,4 +285,41 @@ static inline bool pg_fit_walk_host(const uint8_t *seq, uint32_t lb, const uint3
         for (uint32_t t = 0; t < op_n[e]; t++) pg_fit_add(sums, sig[pos + t], (int32_t)levels[slot]);
     }
     return true;
+}
+
+// The sample and column totals of a gapped read. false: an op code above 2.
+static inline bool pg_fit_gap_totals(const uint32_t *op_n, const uint8_t *op_t, uint32_t lb, uint64_t &samples, uint64_t &cols) {
+    samples = cols = 0;
+    for (uint32_t e = 0; e < lb; e++) {
+        if (op_t[e] > PG_FIT_OP_D) return false;
+        samples += pg_fit_op_samples(op_t[e], op_n[e]); cols += pg_fit_op_cols(op_t[e], op_n[e]);
+    }
+    return true;
+}
+// The status a gapped read has before any k-mer is read: PG_FIT_OK, PG_FIT_OUT_OF_SIGNAL or PG_FIT_REF_LENGTH
+static inline uint32_t pg_fit_gap_status(int64_t q, uint64_t samples, uint64_t n_sig, uint64_t cols, uint64_t S) {
+    if (q < 0 || (uint64_t)q > n_sig || samples > n_sig - (uint64_t)q) return PG_FIT_OUT_OF_SIGNAL;
+    return S != cols ? PG_FIT_REF_LENGTH : PG_FIT_OK;
+}
+// pg_fit_walk_host for a gapped read: seq is the slice of S bases. Returns PG_FIT_OK, PG_FIT_OUT_OF_SIGNAL or PG_FIT_REF_LENGTH, -1 for
+// an op code above 2, -2 for a slice above PG_FIT_MAX_SLICE (the library refuses such a batch).
+static inline int pg_fit_gap_walk_host(const uint8_t *seq, uint64_t S, const uint32_t *op_n, const uint8_t *op_t, uint32_t lb, int64_t q, const int16_t *sig, uint64_t n_sig,
+                                       const uint32_t *levels, uint32_t k, uint32_t m, bool rna, uint32_t min_dur, uint32_t max_dur, std::vector<PgFitEvent> &events, PgFitSums &sums) {
+    events.clear(); sums = PgFitSums{0, 0, 0, 0, 0, 0, 0};
+    uint64_t total, cols;
+    if (!pg_fit_gap_totals(op_n, op_t, lb, total, cols)) return -1;
+    if (S > PG_FIT_MAX_SLICE) return -2;
+    const uint32_t st = pg_fit_gap_status(q, total, n_sig, cols, S);
+    if (st != PG_FIT_OK) return (int)st;
+    uint64_t pos = (uint64_t)q; uint32_t col = 0;
+    for (uint32_t e = 0; e < lb; pos += pg_fit_op_samples(op_t[e], op_n[e]), col += pg_fit_op_cols(op_t[e], op_n[e]), e++) {
+        uint32_t first;
+        if (op_t[e] != PG_FIT_OP_MATCH || !pg_fit_dur_ok(op_n[e], min_dur, max_dur) || !pg_fit_gap_kmer_at(op_t, lb, (uint32_t)S, k, m, rna, e, col, first)) continue;
+        const int32_t slot = pg_fit_code(seq, first, k);
+        if (slot < 0 || !levels[slot]) continue;
+        events.push_back(PgFitEvent{pos, op_n[e], slot});
+        sums.e++;
+        for (uint32_t t = 0; t < op_n[e]; t++) pg_fit_add(sums, sig[pos + t], (int32_t)levels[slot]);
+    }
+    return PG_FIT_OK;
 }

@@ -15,6 +15,11 @@
 //   k_fit_span   per piece the sum of its ops' lengths, and a look at op_t: a batch with an op that is no match is refused. The host scans
 //                the pieces' sums (one number per 256 ops) into every piece's first sample, and refuses a read whose ops leave its samples
 //                before any kernel indexes the signal by them.
+// Gapped batches (PG_BATCH_GAPPED: I and D among the ops, seq the reference slices; the rule: pg_fit.h) run the same three kernels as
+// their <kGapped = true> instances; the all-matches instances compile to what they were. The span kernel writes a second sum per piece, its
+// reference columns; the host scans both and settles ref_length beside out_of_signal. In walk_piece lane j reads op_t, a D takes no
+// samples, a third wave scan gives every op's column (carried from step to step as pos is; a read that takes part has fewer than 2^32
+// columns), and the clean window costs at most k bytes of op_t per lane. Everything behind `counted` is the same code.
 //   k_fit_sums   pass 1: every lane keeps the six sums of its samples in registers; one wave reduction per piece, seven 64-bit integer
 //                atomics per piece into the read's sums.
 //   k_fit_resid  pass 2: a sample's residual d goes into its event's two sums with LDS atomics (the step's 64 events); behind the step
@@ -35,7 +40,7 @@
 
 static_assert(sizeof(pg_fit_sums) == 56 && sizeof(PgFitSums) == 56, "the sums come back as 56 bytes per read");
 static_assert(PG_FIT_ST_OK == PG_FIT_OK && PG_FIT_ST_OUT_OF_SIGNAL == PG_FIT_OUT_OF_SIGNAL && PG_FIT_ST_TOO_LONG == PG_FIT_TOO_LONG && PG_FIT_ST_FEW_EVENTS == PG_FIT_FEW_EVENTS &&
-              PG_FIT_ST_FLAT == PG_FIT_FLAT && PG_FIT_ST_NEGATIVE_SCALE == PG_FIT_NEGATIVE_SCALE && PG_FIT_ST_SKIPPED == PG_FIT_SKIPPED, "the header's statuses are the rule's");
+              PG_FIT_ST_FLAT == PG_FIT_FLAT && PG_FIT_ST_NEGATIVE_SCALE == PG_FIT_NEGATIVE_SCALE && PG_FIT_ST_REF_LENGTH == PG_FIT_REF_LENGTH && PG_FIT_ST_SKIPPED == PG_FIT_SKIPPED, "the header's statuses are the rule's");
 
 namespace {
 
@@ -54,6 +59,7 @@ struct FitBatch {
     const uint32_t *op_n; const uint8_t *op_t; const uint64_t *op_off;
     const uint32_t *piece_read, *piece_first; // the read of every piece; the first piece of every read (n_reads + 1)
     const uint64_t *piece_start;              // the first sample of the piece's first op, counted in its read (query_start included)
+    const uint64_t *piece_col;                // gapped batches: the reference column in front of the piece's first op
     const uint8_t *part;                      // per read: it takes part in the pass
     const uint32_t *levels;
     const double *ab;                         // pass 2: a and 1 / b of every read
@@ -76,8 +82,8 @@ __device__ __forceinline__ u64 wave_sum(u64 v) {
     return v;
 }
 
-struct PieceGeo { uint32_t r, e0, e1, lb; uint64_t o0, s0, sig0, pos; };
-__device__ __forceinline__ PieceGeo piece_geo(const FitBatch &B, uint32_t pid, bool with_start) {
+struct PieceGeo { uint32_t r, e0, e1, lb, S, col; uint64_t o0, s0, sig0, pos; }; // S, col: gapped walks only (a read that takes part has col <= S < 2^32)
+template <bool kGapped = false> __device__ __forceinline__ PieceGeo piece_geo(const FitBatch &B, uint32_t pid, bool with_start) {
     PieceGeo g;
     g.r = B.piece_read[pid];
     g.o0 = B.op_off[g.r];
@@ -86,33 +92,53 @@ __device__ __forceinline__ PieceGeo piece_geo(const FitBatch &B, uint32_t pid, b
     g.e1 = min(g.e0 + kPiece, g.lb);
     g.s0 = B.seq_off[g.r]; g.sig0 = B.sig_off[g.r];
     g.pos = with_start ? B.piece_start[pid] : 0;
+    g.S = kGapped ? (uint32_t)(B.seq_off[g.r + 1] - g.s0) : 0u;
+    g.col = kGapped && with_start ? (uint32_t)B.piece_col[pid] : 0u;
     return g;
 }
 
-__global__ __launch_bounds__(kThreads) void k_fit_span(const FitBatch B, uint64_t *__restrict__ psum, uint32_t *__restrict__ flag) {
+// flag: bit 0 an op that is no match, bit 1 an op code above 2. Gapped: pcol gets the piece's reference columns beside its samples.
+template <bool kGapped> __global__ __launch_bounds__(kThreads) void k_fit_span(const FitBatch B, uint64_t *__restrict__ psum, uint64_t *__restrict__ pcol, uint32_t *__restrict__ flag) {
     const uint32_t lane = threadIdx.x & (kWave - 1), pid = blockIdx.x * kWaves + threadIdx.x / kWave;
     if (pid >= B.n_pieces) return;                                        // (the whole wave)
     const PieceGeo g = piece_geo(B, pid, false);
-    u64 s = 0; uint32_t bad = 0;
-    for (uint32_t e = g.e0 + lane; e < g.e1; e += kWave) { s += B.op_n[g.o0 + e]; bad |= B.op_t[g.o0 + e]; }
+    u64 s = 0, c = 0; uint32_t bad = 0;
+    for (uint32_t e = g.e0 + lane; e < g.e1; e += kWave) {
+        const uint32_t n = B.op_n[g.o0 + e], t = B.op_t[g.o0 + e];
+        bad |= t > PG_FIT_OP_D ? 2u : t ? 1u : 0u;
+        if (kGapped) { s += pg_fit_op_samples(t, n); c += pg_fit_op_cols(t, n); } else s += n;
+    }
     s = wave_sum(s);
-    if (__any(bad != 0) && lane == 0) atomicOr(flag, 1u);
-    if (lane == 0) psum[pid] = s;
+    if (kGapped) c = wave_sum(c);
+    bad |= __any(bad & 1u) ? 1u : 0u; bad |= __any(bad & 2u) ? 2u : 0u;
+    if (bad && lane == 0) atomicOr(flag, bad);
+    if (lane == 0) { psum[pid] = s; if (kGapped) pcol[pid] = c; }
 }
 
 // One piece by one wave. per_sample(r, l, j): a counted sample with its event's level, j the event's lane; per_event(n, code, counted):
 // behind the samples of a step, in the lane that owns the event.
-template <bool kResid, class PerSample, class PerEvent>
+template <bool kResid, bool kGapped, class PerSample, class PerEvent>
 __device__ __forceinline__ void walk_piece(const FitBatch &B, const PieceGeo &g, WaveLds &L, uint32_t lane, PerSample per_sample, PerEvent per_event) {
     uint64_t pos = g.pos;
+    uint32_t col = g.col;                                                 // gapped: the column in front of the step's first op
     const int16_t *__restrict__ sig = B.sig + g.sig0;
     for (uint32_t es = g.e0; es < g.e1; es += kWave) {                     // (uniform: the scans need every lane)
         const uint32_t e = es + lane;
         const bool valid = e < g.e1;
         const uint32_t n = valid ? B.op_n[g.o0 + e] : 0u;
-        const uint64_t incl = wave_incl_scan_u64(n);
         uint32_t first = 0, lvl = 0; int32_t code = -1;
-        bool counted = valid && pg_fit_dur_ok(n, B.min_dur, B.max_dur) && pg_fit_kmer_at(g.lb, B.k, B.m, B.rna != 0, e, first);
+        uint64_t incl; bool counted;
+        if (kGapped) { // a D takes no samples; a third scan gives the op's column, carried from step to step as pos is
+            const uint32_t t = valid ? B.op_t[g.o0 + e] : (uint32_t)PG_FIT_OP_I, cols = pg_fit_op_cols(t, n);
+            incl = wave_incl_scan_u64(pg_fit_op_samples(t, n));
+            const uint32_t colincl = wave_incl_scan_u32(cols);
+            counted = valid && t == PG_FIT_OP_MATCH && pg_fit_dur_ok(n, B.min_dur, B.max_dur) &&
+                      pg_fit_gap_kmer_at(B.op_t + g.o0, g.lb, g.S, B.k, B.m, B.rna != 0, e, col + (colincl - cols), first);
+            col += (uint32_t)__shfl((int)colincl, kWave - 1, kWave);
+        } else {
+            incl = wave_incl_scan_u64(n);
+            counted = valid && pg_fit_dur_ok(n, B.min_dur, B.max_dur) && pg_fit_kmer_at(g.lb, B.k, B.m, B.rna != 0, e, first);
+        }
         if (counted) {
             code = pg_fit_code(B.seq + g.s0, first, B.k);
             lvl = code >= 0 ? B.levels[code] : 0u;
@@ -122,7 +148,7 @@ __device__ __forceinline__ void walk_piece(const FitBatch &B, const PieceGeo &g,
         const uint32_t cincl = wave_incl_scan_u32(cn);
         const uint32_t total = (uint32_t)__shfl((int)cincl, kWave - 1, kWave);
         L.cincl[lane] = cincl; L.lvl[lane] = lvl;
-        L.off[lane] = pos + (incl - n) - (uint64_t)(cincl - cn);          // virtual index v of this event is sample off + v of the read
+        L.off[lane] = pos + (incl - n) - (uint64_t)(cincl - cn);          // virtual index v of this event is sample off + v of the read (read by counted events only: matches)
         if (kResid) { L.evd[lane] = 0; L.evdd[lane] = 0; }
         wave_lds_sync();
         for (uint32_t v0 = lane; v0 < total; v0 += kUnroll * kWave) {      // kUnroll samples per lane and round: their searches and loads are in flight together
@@ -144,14 +170,14 @@ __device__ __forceinline__ void walk_piece(const FitBatch &B, const PieceGeo &g,
     }
 }
 
-__global__ __launch_bounds__(kThreads) void k_fit_sums(const FitBatch B, u64 *__restrict__ rsums) {
+template <bool kGapped> __global__ __launch_bounds__(kThreads) void k_fit_sums(const FitBatch B, u64 *__restrict__ rsums) {
     __shared__ WaveLds lds[kWaves];
     const uint32_t lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave, pid = blockIdx.x * kWaves + w;
     if (pid >= B.n_pieces) return;                                        // (the whole wave; this kernel has no workgroup barrier)
-    const PieceGeo g = piece_geo(B, pid, true);
+    const PieceGeo g = piece_geo<kGapped>(B, pid, true);
     if (!B.part[g.r]) return;
     PgFitSums s{0, 0, 0, 0, 0, 0, 0};
-    walk_piece<false>(B, g, lds[w], lane, [&](int32_t r, int32_t l, uint32_t) { pg_fit_add(s, r, l); }, [&](uint32_t, int32_t, bool counted) { s.e += counted ? 1 : 0; });
+    walk_piece<false, kGapped>(B, g, lds[w], lane, [&](int32_t r, int32_t l, uint32_t) { pg_fit_add(s, r, l); }, [&](uint32_t, int32_t, bool counted) { s.e += counted ? 1 : 0; });
     const u64 v[7] = {wave_sum((u64)s.n), wave_sum((u64)s.sl), wave_sum((u64)s.sll), wave_sum((u64)s.sr), wave_sum((u64)s.srl), wave_sum((u64)s.srr), wave_sum((u64)s.e)};
     if (lane < 7) { // (two's complement: the signed sums add as unsigned ones)
         const u64 mine = lane == 0 ? v[0] : lane == 1 ? v[1] : lane == 2 ? v[2] : lane == 3 ? v[3] : lane == 4 ? v[4] : lane == 5 ? v[5] : v[6];
@@ -160,7 +186,7 @@ __global__ __launch_bounds__(kThreads) void k_fit_sums(const FitBatch B, u64 *__
 }
 
 // tab: n_samples, n_events, sum d, sum d^2 of every slot, four arrays of n_slots; counters[0]: clamped samples
-template <bool kLdsTable> __global__ __launch_bounds__(kThreads) void k_fit_resid(const FitBatch B, u64 *__restrict__ tab, uint32_t n_slots, u64 *__restrict__ counters) {
+template <bool kLdsTable, bool kGapped> __global__ __launch_bounds__(kThreads) void k_fit_resid(const FitBatch B, u64 *__restrict__ tab, uint32_t n_slots, u64 *__restrict__ counters) {
     __shared__ WaveLds lds[kWaves];
     __shared__ u64 ltab[kLdsTable ? 4 * kLdsSlots : 1];
     const uint32_t lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
@@ -171,10 +197,10 @@ template <bool kLdsTable> __global__ __launch_bounds__(kThreads) void k_fit_resi
     u64 clamped = 0;
     WaveLds &L = lds[w];
     for (uint32_t pid = blockIdx.x * kWaves + w; pid < B.n_pieces; pid += gridDim.x * kWaves) { // (uniform in the wave)
-        const PieceGeo g = piece_geo(B, pid, true);
+        const PieceGeo g = piece_geo<kGapped>(B, pid, true);
         if (!B.part[g.r]) continue;
         const double a = B.ab[2ull * g.r], inv_b = B.ab[2ull * g.r + 1];
-        walk_piece<true>(B, g, L, lane,
+        walk_piece<true, kGapped>(B, g, L, lane,
             [&](int32_t r, int32_t l, uint32_t j) {
                 bool c;
                 const int32_t d = pg_fit_resid(r, a, inv_b, l, c);
@@ -219,12 +245,12 @@ struct pg_fit {
     double ms[2] = {0, 0};
     PgDev<uint32_t> d_levels, d_opn, d_pread, d_pfirst;
     PgDev<int16_t> d_sig;
-    PgDev<uint64_t> d_sigoff, d_seqoff, d_opoff, d_pstart, d_psum;
+    PgDev<uint64_t> d_sigoff, d_seqoff, d_opoff, d_pstart, d_psum, d_pcol, d_pcsum; // (d_pcol, d_pcsum: gapped batches)
     PgDev<uint8_t> d_seq, d_opt, d_part;
     PgDev<u64> d_rsums, d_tab, d_counters;
     PgDev<double> d_ab;
     PgDev<uint32_t> d_flag;
-    std::vector<uint64_t> sig_off, seq_off, op_off, psum, pstart, tab;
+    std::vector<uint64_t> sig_off, seq_off, op_off, psum, pstart, pcsum, pcol, tab;
     std::vector<int32_t> qs;
     std::vector<uint32_t> piece_read, piece_first, status;
     std::vector<uint8_t> part;
@@ -312,7 +338,9 @@ pg_status pg_fit_submit(pg_fit *h, const pg_batch *b, const uint32_t *skip, pg_f
     if (!h->k) return pg_fail(h, PG_ERR_STATE, "pg_fit_submit: no model (pg_fit_set_model)");
     if (b->struct_size != sizeof(pg_batch)) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: pg_batch.struct_size %u, this library has %zu", b->struct_size, sizeof(pg_batch));
     if (b->location != PG_LOC_HOST && b->location != PG_LOC_DEVICE) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: location must be PG_LOC_HOST or PG_LOC_DEVICE");
-    if (!(b->flags & PG_BATCH_ALL_MATCHES)) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: the batch must carry PG_BATCH_ALL_MATCHES (every op a match, as `reform` writes them)");
+    const bool gapped = (b->flags & PG_BATCH_GAPPED) != 0;
+    if (gapped && (b->flags & PG_BATCH_ALL_MATCHES)) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: a batch carries PG_BATCH_GAPPED or PG_BATCH_ALL_MATCHES, not both");
+    if (!gapped && !(b->flags & PG_BATCH_ALL_MATCHES)) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: the batch must carry PG_BATCH_ALL_MATCHES (every op a match, as `reform` writes them)");
     const uint64_t n = b->n_reads;
     if (!b->sig_off || !b->seq_off || !b->op_off || (n && !b->query_start)) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: null array");
     PG_HIP_TRY(h, hipSetDevice(h->device));
@@ -341,7 +369,10 @@ pg_status pg_fit_submit(pg_fit *h, const pg_batch *b, const uint32_t *skip, pg_f
         const bool skipped = skip && skip[r];
         if (skipped && skip[r] >= (1u << 16)) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: skip code %u of read %llu (below 2^16)", skip[r], (unsigned long long)r);
         if (lb > 0x7fffffffull) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: read %llu has %llu ops (at most 2^31 - 1)", (unsigned long long)r, (unsigned long long)lb);
-        if (!skipped && h->seq_off[r + 1] - h->seq_off[r] < lb)
+        if (gapped && h->seq_off[r + 1] - h->seq_off[r] > PG_FIT_MAX_SLICE)
+            return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: read %llu has a reference slice of %llu bases (at most 2^32 - 1)", (unsigned long long)r,
+                           (unsigned long long)(h->seq_off[r + 1] - h->seq_off[r]));
+        if (!gapped && !skipped && h->seq_off[r + 1] - h->seq_off[r] < lb)
             return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: read %llu has %llu ops and %llu bases (an accepted read has as many bases as ops)", (unsigned long long)r,
                            (unsigned long long)lb, (unsigned long long)(h->seq_off[r + 1] - h->seq_off[r]));
         h->piece_first[r] = (uint32_t)h->piece_read.size();
@@ -383,43 +414,56 @@ pg_status pg_fit_submit(pg_fit *h, const pg_batch *b, const uint32_t *skip, pg_f
         B.sig = h->d_sig.p; B.sig_off = h->d_sigoff.p; B.seq = h->d_seq.p; B.seq_off = h->d_seqoff.p; B.op_n = h->d_opn.p; B.op_t = h->d_opt.p; B.op_off = h->d_opoff.p;
     }
     FIT_ENSURE(h->d_pfirst, (n + 1) * 4); FIT_ENSURE(h->d_pread, n_pieces * 4); FIT_ENSURE(h->d_pstart, n_pieces * 8); FIT_ENSURE(h->d_psum, n_pieces * 8);
+    if (gapped) { FIT_ENSURE(h->d_pcol, n_pieces * 8); FIT_ENSURE(h->d_pcsum, n_pieces * 8); }
     FIT_ENSURE(h->d_part, n); FIT_ENSURE(h->d_rsums, n * sizeof(pg_fit_sums)); FIT_ENSURE(h->d_ab, n * 16);
 #undef FIT_ENSURE
-    B.piece_first = h->d_pfirst.p; B.piece_read = h->d_pread.p; B.piece_start = h->d_pstart.p; B.part = h->d_part.p; B.ab = h->d_ab.p;
+    B.piece_first = h->d_pfirst.p; B.piece_read = h->d_pread.p; B.piece_start = h->d_pstart.p; B.piece_col = h->d_pcol.p; B.part = h->d_part.p; B.ab = h->d_ab.p;
     const uint32_t blocks = (uint32_t)((n_pieces + kWaves - 1) / kWaves);
     (void)hipGetLastError();
 
     // ---- the spans of the pieces, and the look at op_t
-    h->psum.assign(n_pieces, 0);
+    h->psum.assign(n_pieces, 0); h->pcsum.assign(gapped ? n_pieces : 0, 0);
     if (n_pieces) {
         uint32_t flag = 0;
         PG_HIP_TRY(h, hipMemcpyAsync(h->d_pfirst.p, h->piece_first.data(), (n + 1) * 4, hipMemcpyHostToDevice, s));
         PG_HIP_TRY(h, hipMemcpyAsync(h->d_pread.p, h->piece_read.data(), n_pieces * 4, hipMemcpyHostToDevice, s));
         PG_HIP_TRY(h, hipMemsetAsync(h->d_flag.p, 0, sizeof(uint32_t), s));
-        hipLaunchKernelGGL(k_fit_span, dim3(blocks), dim3(kThreads), 0, s, B, h->d_psum.p, h->d_flag.p);
+        if (gapped) hipLaunchKernelGGL(k_fit_span<true>, dim3(blocks), dim3(kThreads), 0, s, B, h->d_psum.p, h->d_pcsum.p, h->d_flag.p);
+        else hipLaunchKernelGGL(k_fit_span<false>, dim3(blocks), dim3(kThreads), 0, s, B, h->d_psum.p, (uint64_t *)nullptr, h->d_flag.p);
         PG_HIP_TRY(h, hipGetLastError());
         PG_HIP_TRY(h, hipMemcpyAsync(h->psum.data(), h->d_psum.p, n_pieces * 8, hipMemcpyDeviceToHost, s));
+        if (gapped) PG_HIP_TRY(h, hipMemcpyAsync(h->pcsum.data(), h->d_pcsum.p, n_pieces * 8, hipMemcpyDeviceToHost, s));
         PG_HIP_TRY(h, hipMemcpyAsync(&flag, h->d_flag.p, sizeof flag, hipMemcpyDeviceToHost, s));
         PG_HIP_TRY(h, hipStreamSynchronize(s));
-        if (flag) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: the batch carries PG_BATCH_ALL_MATCHES but holds an op that is no match (an I, a D or an unknown op)");
+        if (gapped && (flag & 2u)) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: the batch carries PG_BATCH_GAPPED but holds an op code above 2 (0 match, 1 I, 2 D)");
+        if (!gapped && flag) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: the batch carries PG_BATCH_ALL_MATCHES but holds an op that is no match (an I, a D or an unknown op)");
     }
-    // ---- every piece's first sample; a read whose ops leave its samples takes no part
-    h->status.assign(n, PG_FIT_ST_OK); h->part.assign(n, 0); h->pstart.resize(n_pieces);
+    // ---- every piece's first sample (gapped: and first column); a read whose ops leave its samples takes no part, nor does a gapped read
+    // whose slice has not as many bases as its ops have columns: no kernel reads its seq
+    h->status.assign(n, PG_FIT_ST_OK); h->part.assign(n, 0); h->pstart.resize(n_pieces); h->pcol.resize(gapped ? n_pieces : 0);
     for (uint64_t r = 0; r < n; r++) {
         if (skip && skip[r]) { h->status[r] = PG_FIT_ST_SKIPPED + skip[r]; continue; }
         const uint64_t len = h->sig_off[r + 1] - h->sig_off[r];
         uint64_t at = h->qs[r] < 0 ? 0 : (uint64_t)h->qs[r];
-        for (uint32_t p = h->piece_first[r]; p < h->piece_first[r + 1]; p++) { h->pstart[p] = at; at += h->psum[p]; }
-        if (h->qs[r] < 0 || at > len) h->status[r] = PG_FIT_ST_OUT_OF_SIGNAL; else h->part[r] = 1;
+        uint64_t col = 0;
+        for (uint32_t p = h->piece_first[r]; p < h->piece_first[r + 1]; p++) {
+            h->pstart[p] = at; at += h->psum[p];
+            if (gapped) { h->pcol[p] = col; col += h->pcsum[p]; }
+        }
+        if (h->qs[r] < 0 || at > len) h->status[r] = PG_FIT_ST_OUT_OF_SIGNAL;
+        else if (gapped && col != h->seq_off[r + 1] - h->seq_off[r]) h->status[r] = PG_FIT_ST_REF_LENGTH;
+        else h->part[r] = 1;
     }
     // ---- pass 1
     h->sums.assign(n, pg_fit_sums{0, 0, 0, 0, 0, 0, 0});
     if (n_pieces) {
         PG_HIP_TRY(h, hipMemcpyAsync(h->d_pstart.p, h->pstart.data(), n_pieces * 8, hipMemcpyHostToDevice, s));
+        if (gapped) PG_HIP_TRY(h, hipMemcpyAsync(h->d_pcol.p, h->pcol.data(), n_pieces * 8, hipMemcpyHostToDevice, s));
         PG_HIP_TRY(h, hipMemcpyAsync(h->d_part.p, h->part.data(), n, hipMemcpyHostToDevice, s));
         PG_HIP_TRY(h, hipMemsetAsync(h->d_rsums.p, 0, n * sizeof(pg_fit_sums), s));
         PG_HIP_TRY(h, hipEventRecord(h->ev[0], s));
-        hipLaunchKernelGGL(k_fit_sums, dim3(blocks), dim3(kThreads), 0, s, B, h->d_rsums.p);
+        if (gapped) hipLaunchKernelGGL(k_fit_sums<true>, dim3(blocks), dim3(kThreads), 0, s, B, h->d_rsums.p);
+        else hipLaunchKernelGGL(k_fit_sums<false>, dim3(blocks), dim3(kThreads), 0, s, B, h->d_rsums.p);
         PG_HIP_TRY(h, hipGetLastError());
         PG_HIP_TRY(h, hipEventRecord(h->ev[1], s));
         PG_HIP_TRY(h, hipMemcpyAsync(h->sums.data(), h->d_rsums.p, n * sizeof(pg_fit_sums), hipMemcpyDeviceToHost, s));
@@ -450,8 +494,11 @@ pg_status pg_fit_submit(pg_fit *h, const pg_batch *b, const uint32_t *skip, pg_f
         PG_HIP_TRY(h, hipMemsetAsync(h->d_counters.p, 0, sizeof(u64), s));
         const uint32_t grid = blocks < PG_FIT_GRID ? blocks : PG_FIT_GRID;
         PG_HIP_TRY(h, hipEventRecord(h->ev[2], s));
-        if (h->k <= PG_FIT_LDS_K) hipLaunchKernelGGL(k_fit_resid<true>, dim3(grid), dim3(kThreads), 0, s, B, h->d_tab.p, (uint32_t)h->n_slots, h->d_counters.p);
-        else hipLaunchKernelGGL(k_fit_resid<false>, dim3(grid), dim3(kThreads), 0, s, B, h->d_tab.p, (uint32_t)h->n_slots, h->d_counters.p);
+        const bool lds_tab = h->k <= PG_FIT_LDS_K;
+        if (lds_tab && !gapped) hipLaunchKernelGGL((k_fit_resid<true, false>), dim3(grid), dim3(kThreads), 0, s, B, h->d_tab.p, (uint32_t)h->n_slots, h->d_counters.p);
+        else if (!gapped) hipLaunchKernelGGL((k_fit_resid<false, false>), dim3(grid), dim3(kThreads), 0, s, B, h->d_tab.p, (uint32_t)h->n_slots, h->d_counters.p);
+        else if (lds_tab) hipLaunchKernelGGL((k_fit_resid<true, true>), dim3(grid), dim3(kThreads), 0, s, B, h->d_tab.p, (uint32_t)h->n_slots, h->d_counters.p);
+        else hipLaunchKernelGGL((k_fit_resid<false, true>), dim3(grid), dim3(kThreads), 0, s, B, h->d_tab.p, (uint32_t)h->n_slots, h->d_counters.p);
         PG_HIP_TRY(h, hipGetLastError());
         PG_HIP_TRY(h, hipEventRecord(h->ev[3], s));
         PG_HIP_TRY(h, hipMemcpyAsync(h->tab.data(), h->d_tab.p, 4 * h->n_slots * sizeof(u64), hipMemcpyDeviceToHost, s));

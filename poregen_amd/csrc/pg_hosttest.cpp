@@ -615,6 +615,19 @@ extern "C" long pgt_fit_walk(const uint8_t *seq, uint32_t lb, const uint32_t *op
     memcpy(sums7, &s, sizeof s);
     return (long)ev.size();
 }
+// the same for a gapped read (seq: its slice of n_seq bases; op_t 0 match, 1 I, 2 D); -1: out_of_signal, -6: ref_length, -100: an op code
+// above 2 or a slice above 2^32 - 1 bases
+extern "C" long pgt_fit_walk_gapped(const uint8_t *seq, uint64_t n_seq, const uint32_t *op_n, const uint8_t *op_t, uint32_t lb, int64_t q, const int16_t *sig, uint64_t n_sig,
+                                    const uint32_t *levels, uint32_t k, uint32_t m, int rna, uint32_t min_dur, uint32_t max_dur, uint64_t *ev_start, uint32_t *ev_n, int32_t *ev_slot,
+                                    size_t cap, int64_t *sums7) {
+    std::vector<PgFitEvent> ev; PgFitSums s;
+    const int st = pg_fit_gap_walk_host(seq, n_seq, op_n, op_t, lb, q, sig, n_sig, levels, k, m, rna != 0, min_dur, max_dur, ev, s);
+    if (st < 0) return -100;
+    if (st != PG_FIT_OK) return -(long)st;
+    for (size_t i = 0; i < ev.size() && i < cap; i++) { ev_start[i] = ev[i].start; ev_n[i] = ev[i].n; ev_slot[i] = ev[i].slot; }
+    memcpy(sums7, &s, sizeof s);
+    return (long)ev.size();
+}
 // the status; a, b and 1 / b as they go to the device; shift, scale and rms as the per-read table prints them ("%.6f"), 64 bytes each
 extern "C" int pgt_fit_solve(const int64_t *sums7, uint32_t min_events, double dig, double off, double range, double *ab3, char *text3) {
     PgFitSums s; memcpy(&s, sums7, sizeof s);
@@ -643,6 +656,17 @@ extern "C" int pgt_realign_walk(const uint8_t *seq, uint32_t lb, const uint32_t 
                                 int rna, uint32_t min_dur, uint32_t max_dur, uint32_t band, uint32_t min_len, double a, double b, uint32_t *op_out, uint64_t *out7) {
     PgRlRead r;
     if (!pg_rl_walk_host(seq, lb, op_n, q, sig, n_sig, levels, k, m, rna != 0, min_dur, max_dur, band, min_len, 0, a, b, op_out, r)) return -1;
+    out7[0] = r.n_free; out7[1] = r.n_moved; out7[2] = r.sum_abs_shift; out7[3] = (uint64_t)r.cost_before; out7[4] = (uint64_t)(r.cost_before >> 64);
+    out7[5] = (uint64_t)r.cost_after; out7[6] = (uint64_t)(r.cost_after >> 64);
+    return 0;
+}
+// the same for a gapped read, under a phase; -1: the read has no fit (out_of_signal, ref_length, an op code above 2)
+extern "C" int pgt_realign_walk_gapped(const uint8_t *seq, uint64_t n_seq, const uint32_t *op_n, const uint8_t *op_t, uint32_t lb, int64_t q, const int16_t *sig, uint64_t n_sig,
+                                       const uint32_t *levels, uint32_t k, uint32_t m, int rna, uint32_t min_dur, uint32_t max_dur, uint32_t band, uint32_t min_len, uint32_t phase,
+                                       double a, double b, uint32_t *op_out, uint64_t *out7) {
+    static const uint8_t none = 0;
+    PgRlRead r;
+    if (!pg_rl_walk_any(seq, n_seq, lb ? op_t : &none, lb, op_n, q, sig, n_sig, levels, k, m, rna != 0, min_dur, max_dur, band, min_len, phase, a, b, op_out, r)) return -1;
     out7[0] = r.n_free; out7[1] = r.n_moved; out7[2] = r.sum_abs_shift; out7[3] = (uint64_t)r.cost_before; out7[4] = (uint64_t)(r.cost_before >> 64);
     out7[5] = (uint64_t)r.cost_after; out7[6] = (uint64_t)(r.cost_after >> 64);
     return 0;

@@ -6,6 +6,10 @@
 // (status PG_FIT_OK) under the same model, m, rna, min_dur and max_dur. Parameters: band W (0 .. PG_RL_MAX_BAND), min_len
 // (1 .. min_dur), max_dur <= PG_RL_MAX_DUR.
 //
+// A gapped read (PG_BATCH_GAPPED, pg_fit.h) is taken by the same rule: B advances by n for a match and an I and by 0 for a D, an event is
+// refinable iff the gapped fit counts it -- an I or a D never is, so both boundaries beside it are pinned -- the pinned period counts ops, and
+// the refined ops keep op_t and the op_n of every I and D.
+//
 // Boundaries. B_0 = q, B_e = q + n_0 + .. + n_{e-1}. Event e is REFINABLE iff it counts by fit's rule (pg_fit_kmer_at, pg_fit_code, a
 // level, pg_fit_dur_ok); l_e is its level. Boundary e, 0 < e < Lb, is FREE iff events e - 1 and e are both refinable and
 // e % PG_FIT_PIECE != phase (0 .. PG_FIT_PIECE - 1; 0 unless the caller asks); every other boundary is PINNED (B_0 and B_Lb too) and keeps
@@ -52,6 +56,15 @@ template <class Seq> PG_FIT_HD uint32_t pg_rl_level(const Seq seq, uint32_t lb, 
     const int32_t code = pg_fit_code(seq, first, k);
     return code < 0 ? 0u : levels[code];
 }
+// the same for a gapped read (pg_fit.h: PG_BATCH_GAPPED): op e of type t in front of column col, the slice has S bases. An I or a D is
+// never refinable, so both boundaries beside it are pinned; a D has no samples between them.
+template <class Seq, class Ops> PG_FIT_HD uint32_t pg_rl_gap_level(const Seq seq, uint32_t S, const Ops op_t, uint32_t lb, uint32_t t, uint32_t n, uint32_t e, uint32_t col,
+                                                                   const uint32_t *levels, uint32_t k, uint32_t m, bool rna, uint32_t min_dur, uint32_t max_dur) {
+    uint32_t first;
+    if (t != PG_FIT_OP_MATCH || !pg_fit_dur_ok(n, min_dur, max_dur) || !pg_fit_gap_kmer_at(op_t, lb, S, k, m, rna, e, col, first)) return 0u;
+    const int32_t code = pg_fit_code(seq, first, k);
+    return code < 0 ? 0u : levels[code];
+}
 PG_FIT_HD bool pg_rl_free(uint32_t e, uint32_t lb, uint32_t lvl_before, uint32_t lvl_at, uint32_t phase) {
     return e > 0 && e < lb && lvl_before && lvl_at && e % PG_FIT_PIECE != phase;
 }
@@ -76,20 +89,34 @@ PG_FIT_HD uint64_t pg_rl_cost(int32_t r, double a, double inv_b, uint32_t l) { b
 // ---- host only: one read walked by the rule, the recurrence over all pairs of candidates as it is stated ---------------------------------
 struct PgRlRead { uint32_t n_free = 0, n_moved = 0; uint64_t sum_abs_shift = 0; unsigned __int128 cost_before = 0, cost_after = 0; };
 
-// op_out[lb]: the refined ops. false: out_of_signal (such a read has no fit), nothing is written.
-static inline bool pg_rl_walk_host(const uint8_t *seq, uint32_t lb, const uint32_t *op_n, int64_t q, const int16_t *sig, uint64_t n_sig, const uint32_t *levels, uint32_t k, uint32_t m,
+// op_out[lb]: the refined ops. false: out_of_signal (such a read has no fit), nothing is written. op_t != null: a gapped read whose slice
+// seq has S bases (false as well for ref_length, an op code above 2 or a slice above PG_FIT_MAX_SLICE); the refined ops keep op_t and the
+// op_n of every I and D.
+static inline bool pg_rl_walk_any(const uint8_t *seq, uint64_t S, const uint8_t *op_t, uint32_t lb, const uint32_t *op_n, int64_t q, const int16_t *sig, uint64_t n_sig, const uint32_t *levels, uint32_t k, uint32_t m,
                                    bool rna, uint32_t min_dur, uint32_t max_dur, uint32_t band, uint32_t min_len, uint32_t phase, double a, double b, uint32_t *op_out,
                                    PgRlRead &out) {
     out = PgRlRead();
     uint64_t total = 0;
-    for (uint32_t e = 0; e < lb; e++) total += op_n[e];
-    if (q < 0 || (uint64_t)q > n_sig || total > n_sig - (uint64_t)q) return false;
+    if (op_t) {
+        uint64_t cols;
+        if (!pg_fit_gap_totals(op_n, op_t, lb, total, cols) || S > PG_FIT_MAX_SLICE || pg_fit_gap_status(q, total, n_sig, cols, S) != PG_FIT_OK) return false;
+    } else {
+        for (uint32_t e = 0; e < lb; e++) total += op_n[e];
+        if (q < 0 || (uint64_t)q > n_sig || total > n_sig - (uint64_t)q) return false;
+    }
     const double inv_b = 1.0 / b;
     const int64_t W = band;
     std::vector<int64_t> B(lb + 1), Bn;
     std::vector<uint32_t> lvl(lb + 1, 0u);
     B[0] = q;
-    for (uint32_t e = 0; e < lb; e++) { B[e + 1] = B[e] + op_n[e]; lvl[e] = pg_rl_level(seq, lb, op_n[e], e, levels, k, m, rna, min_dur, max_dur); }
+    uint32_t col = 0;
+    for (uint32_t e = 0; e < lb; e++) {
+        if (op_t) {
+            B[e + 1] = B[e] + pg_fit_op_samples(op_t[e], op_n[e]);
+            lvl[e] = pg_rl_gap_level(seq, (uint32_t)S, op_t, lb, op_t[e], op_n[e], e, col, levels, k, m, rna, min_dur, max_dur);
+            col += pg_fit_op_cols(op_t[e], op_n[e]);
+        } else { B[e + 1] = B[e] + op_n[e]; lvl[e] = pg_rl_level(seq, lb, op_n[e], e, levels, k, m, rna, min_dur, max_dur); }
+    }
     Bn = B;
     auto is_free = [&](uint32_t e) { return e > 0 && e < lb && pg_rl_free(e, lb, lvl[e - 1], lvl[e], phase); };
     auto cost = [&](uint32_t e, int64_t lo, int64_t hi) { unsigned __int128 s = 0; for (int64_t t = lo; t < hi; t++) s += pg_rl_cost(sig[t], a, inv_b, lvl[e]); return s; };
@@ -132,9 +159,14 @@ static inline bool pg_rl_walk_host(const uint8_t *seq, uint32_t lb, const uint32
         e0 = e1;
     }
     for (uint32_t e = 0; e < lb; e++) {
-        op_out[e] = (uint32_t)(Bn[e + 1] - Bn[e]);
+        op_out[e] = op_t && op_t[e] != PG_FIT_OP_MATCH ? op_n[e] : (uint32_t)(Bn[e + 1] - Bn[e]);
         if (is_free(e)) { out.n_free++; const int64_t s = Bn[e] - B[e]; if (s) { out.n_moved++; out.sum_abs_shift += (uint64_t)(s < 0 ? -s : s); } }
         if (lvl[e]) { out.cost_before += cost(e, B[e], B[e + 1]); out.cost_after += cost(e, Bn[e], Bn[e + 1]); }
     }
     return true;
+}
+static inline bool pg_rl_walk_host(const uint8_t *seq, uint32_t lb, const uint32_t *op_n, int64_t q, const int16_t *sig, uint64_t n_sig, const uint32_t *levels, uint32_t k, uint32_t m,
+                                   bool rna, uint32_t min_dur, uint32_t max_dur, uint32_t band, uint32_t min_len, uint32_t phase, double a, double b, uint32_t *op_out,
+                                   PgRlRead &out) {
+    return pg_rl_walk_any(seq, lb, nullptr, lb, op_n, q, sig, n_sig, levels, k, m, rna, min_dur, max_dur, band, min_len, phase, a, b, op_out, out);
 }

@@ -27,6 +27,10 @@
 //        step once and adds d^2 to either sum. Per piece two 64-bit sums; k_rl_reads adds a read's pieces in 128 bits.
 // Every number is an integer behind pg_fit_resid; nothing depends on the order of execution. No workgroup waits for another, and the four
 // waves of a workgroup never meet.
+// Gapped batches (PG_BATCH_GAPPED; the rule: pg_fit.h, pg_realign.h) run the <kGapped = true> instances: k_rl_span adds a piece's reference
+// columns, k_rl_starts scans them into every piece's first column and raises the refusal for a read whose slice does not fit them, and
+// step 1 of k_rl_align reads op_t -- a D takes no samples, a third wave scan gives the column, an I or a D has no level and so pins both
+// boundaries beside it. Step 4 writes a D's op_n back as it was. Steps 2 and 3 and the LDS layout are untouched.
 #include "../../include/pgmove.h"
 #include <hip/hip_runtime.h>
 #include "pg_realign.h"
@@ -58,7 +62,8 @@ struct RlBatch {
     const uint32_t *op_n; const uint8_t *op_t; const uint64_t *op_off;
     const uint32_t *piece_read, *piece_first; // the read of every piece; the first piece of every read (n_reads + 1)
     const uint64_t *piece_start;              // the first sample of the piece's first op, counted in its read (query_start included)
-    const uint8_t *part;                      // per read: it is refined
+    const uint64_t *piece_col;                // gapped batches: the reference column in front of the piece's first op
+    const uint8_t *part;                     // per read: it is refined
     const int32_t *qs;                        // per read: query_start
     const uint32_t *levels;
     const double *ab;                         // a and 1 / b of every read
@@ -126,34 +131,52 @@ __device__ __forceinline__ RlGeo rl_geo(const RlBatch &B, uint32_t pid) {
     return g;
 }
 
-__global__ __launch_bounds__(kThreads) void k_rl_span(const RlBatch B, uint64_t *__restrict__ psum, uint32_t *__restrict__ flag) {
+// flag[0]: bit 0 an op that is no match, bit 1 an op code above 2. Gapped: pcol gets the piece's reference columns beside its samples.
+template <bool kGapped> __global__ __launch_bounds__(kThreads) void k_rl_span(const RlBatch B, uint64_t *__restrict__ psum, uint64_t *__restrict__ pcol, uint32_t *__restrict__ flag) {
     const uint32_t lane = threadIdx.x & (kWave - 1), pid = blockIdx.x * kWaves + threadIdx.x / kWave;
     if (pid >= B.n_pieces) return;                                        // (the whole wave)
     const RlGeo g = rl_geo(B, pid);
-    u64 s = 0; uint32_t bad = 0;
-    for (uint32_t i = lane; i < g.cnt; i += kWave) { s += B.op_n[g.o0 + g.e0 + i]; bad |= B.op_t[g.o0 + g.e0 + i]; }
+    u64 s = 0, c = 0; uint32_t bad = 0;
+    for (uint32_t i = lane; i < g.cnt; i += kWave) {
+        const uint32_t n = B.op_n[g.o0 + g.e0 + i], t = B.op_t[g.o0 + g.e0 + i];
+        bad |= t > PG_FIT_OP_D ? 2u : t ? 1u : 0u;
+        if (kGapped) { s += pg_fit_op_samples(t, n); c += pg_fit_op_cols(t, n); } else s += n;
+    }
     s = wave_sum(s);
-    if (__any(bad != 0) && lane == 0) atomicOr(flag, 1u);
-    if (lane == 0) psum[pid] = s;
+    if (kGapped) c = wave_sum(c);
+    bad = (__any(bad & 1u) ? 1u : 0u) | (__any(bad & 2u) ? 2u : 0u);
+    if (bad && lane == 0) atomicOr(flag, bad);
+    if (lane == 0) { psum[pid] = s; if (kGapped) pcol[pid] = c; }
 }
 
 // One wave per read: the pieces' sums scanned into every piece's first sample, 64 pieces a step. A read that is to be refined and does not
 // lie inside its samples raises the refusal: the smallest such read's index into flag[1], which starts at UINT32_MAX. Nothing here indexes
 // the signal. A read has fewer than 2^31 ops of fewer than 2^32 samples and a query_start below 2^31: every sum stays below 2^64.
 static_assert(31 + 32 < 64, "a read's samples, summed over its ops, fit a uint64");
-__global__ __launch_bounds__(kThreads) void k_rl_starts(const RlBatch B, const uint64_t *__restrict__ psum, uint64_t *__restrict__ piece_start, uint32_t *__restrict__ flag) {
+// Gapped: the columns are scanned beside the samples (fewer than 2^31 ops of fewer than 2^32 columns: below 2^63), and flag[1] gets
+// 2 r for a read whose ops leave its samples, 2 r + 1 for one whose slice has not as many bases as its ops have columns -- the smallest
+// read, and of its two reasons the first, as fit ranks them.
+template <bool kGapped> __global__ __launch_bounds__(kThreads) void k_rl_starts(const RlBatch B, const uint64_t *__restrict__ psum, const uint64_t *__restrict__ pcsum,
+                                                                                uint64_t *__restrict__ piece_start, uint64_t *__restrict__ piece_col, uint32_t *__restrict__ flag) {
     const uint32_t lane = threadIdx.x & (kWave - 1), r = blockIdx.x * kWaves + threadIdx.x / kWave;
     if (r >= B.n_reads) return;                                           // (the whole wave)
     const uint32_t p0 = B.piece_first[r], p1 = B.piece_first[r + 1];
     const int32_t q = B.qs[r];
-    uint64_t at = q < 0 ? 0ull : (uint64_t)q;
+    uint64_t at = q < 0 ? 0ull : (uint64_t)q, col = 0;
     for (uint32_t p = p0; p < p1; p += kWave) {                           // (uniform)
         const uint32_t i = p + lane;
         const uint64_t v = i < p1 ? psum[i] : 0ull, incl = wave_incl_scan_u64(v);
         if (i < p1) piece_start[i] = at + (incl - v);
         at += __shfl(incl, kWave - 1, kWave);
+        if (kGapped) {
+            const uint64_t cv = i < p1 ? pcsum[i] : 0ull, cincl = wave_incl_scan_u64(cv);
+            if (i < p1) piece_col[i] = col + (cincl - cv);
+            col += __shfl(cincl, kWave - 1, kWave);
+        }
     }
-    if (lane == 0 && B.part[r] && (q < 0 || at > B.sig_off[r + 1] - B.sig_off[r])) atomicMin(flag + 1, r);
+    const bool out = q < 0 || at > B.sig_off[r + 1] - B.sig_off[r];
+    if (!kGapped) { if (lane == 0 && B.part[r] && out) atomicMin(flag + 1, r); }
+    else if (lane == 0 && B.part[r] && (out || col != B.seq_off[r + 1] - B.seq_off[r])) atomicMin(flag + 1, 2u * r + (out ? 0u : 1u));
 }
 
 // the first set bit of the 256 at or behind i, or 256; with `clear`, the first bit that is not set
@@ -167,7 +190,7 @@ __device__ __forceinline__ uint32_t next_bit(const RlLds &L, uint32_t i, bool cl
     return kPiece;
 }
 
-__global__ __launch_bounds__(kThreads) void k_rl_align(const RlBatch B, uint32_t *__restrict__ out_n, RlPiece *__restrict__ pstats) {
+template <bool kGapped> __global__ __launch_bounds__(kThreads) void k_rl_align(const RlBatch B, uint32_t *__restrict__ out_n, RlPiece *__restrict__ pstats) {
     __shared__ RlLds lds[kWaves];
     const uint32_t lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave, pid = blockIdx.x * kWaves + w;
     if (pid >= B.n_pieces) return;                                        // (the whole wave; this kernel has no workgroup barrier)
@@ -188,12 +211,21 @@ __global__ __launch_bounds__(kThreads) void k_rl_align(const RlBatch B, uint32_t
     uint64_t ref[kSteps];
     {
         uint64_t pos = B.piece_start[pid];
+        // gapped: a D takes no samples, and a third scan gives the op's column, carried from step to step as pos is (a read that is
+        // refined has as many columns as its slice has bases, below 2^32)
+        const uint32_t S = kGapped ? (uint32_t)(B.seq_off[g.r + 1] - g.s0) : 0u;
+        uint32_t col = kGapped ? (uint32_t)B.piece_col[pid] : 0u;
 #pragma unroll
         for (uint32_t st = 0; st < kSteps; st++) {
             const uint32_t i = st * kWave + lane;
-            const uint32_t n = i < g.cnt ? op_n[i] : 0u;
+            uint32_t n = i < g.cnt ? op_n[i] : 0u, lvl;
+            if (kGapped) {
+                const uint32_t t = i < g.cnt ? B.op_t[g.o0 + g.e0 + i] : (uint32_t)PG_FIT_OP_I, cols = pg_fit_op_cols(t, n), colincl = wave_incl_scan_u32(cols);
+                lvl = i < g.cnt ? pg_rl_gap_level(B.seq + g.s0, S, B.op_t + g.o0, g.lb, t, n, g.e0 + i, col + (colincl - cols), B.levels, B.k, B.m, B.rna != 0, B.min_dur, B.max_dur) : 0u;
+                col += (uint32_t)__shfl((int)colincl, kWave - 1, kWave);
+                n = pg_fit_op_samples(t, n);
+            } else lvl = i < g.cnt ? pg_rl_level(B.seq + g.s0, g.lb, n, g.e0 + i, B.levels, B.k, B.m, B.rna != 0, B.min_dur, B.max_dur) : 0u;
             const uint64_t incl = wave_incl_scan_u64(n);
-            const uint32_t lvl = i < g.cnt ? pg_rl_level(B.seq + g.s0, g.lb, n, g.e0 + i, B.levels, B.k, B.m, B.rna != 0, B.min_dur, B.max_dur) : 0u;
             L.pos[i] = pos + (incl - n); L.lvl[i] = lvl; L.shift[i] = 0;
             ref[st] = __ballot(lvl != 0);
             pos += __shfl(incl, kWave - 1, kWave);
@@ -260,7 +292,8 @@ __global__ __launch_bounds__(kThreads) void k_rl_align(const RlBatch B, uint32_t
         const int32_t s_lo = valid ? L.shift[i] : 0, s_hi = valid ? L.shift[i + 1] : 0;
         const uint64_t o_lo = valid ? L.pos[i] : 0, o_hi = valid ? L.pos[i + 1] : 0;
         const uint32_t lvl = valid ? L.lvl[i] : 0u;
-        if (valid) out[i] = (uint32_t)((int64_t)(o_hi - o_lo) + s_hi - s_lo);
+        if (kGapped && valid && B.op_t[g.o0 + g.e0 + i] == PG_FIT_OP_D) out[i] = op_n[i]; // (its columns; an I keeps its samples below: both boundaries are pinned)
+        else if (valid) out[i] = (uint32_t)((int64_t)(o_hi - o_lo) + s_hi - s_lo);
         moved += s_lo != 0 ? 1u : 0u; abs_shift += (u64)(s_lo < 0 ? -s_lo : s_lo);
         const int64_t n_lo = (int64_t)o_lo + s_lo, n_hi = (int64_t)o_hi + s_hi;
         // the costs: every lane walks the union of the old and the new span of ITS event, four samples in flight; neighbouring lanes
@@ -329,7 +362,7 @@ struct pg_realign {
     PgDev<uint32_t> d_levels, d_opn, d_pread, d_pfirst, d_out[2], d_flag;
     PgDev<int16_t> d_sig;
     PgDev<int32_t> d_qs;
-    PgDev<uint64_t> d_sigoff, d_seqoff, d_opoff, d_pstart, d_psum;
+    PgDev<uint64_t> d_sigoff, d_seqoff, d_opoff, d_pstart, d_psum, d_pcol, d_pcsum; // (d_pcol, d_pcsum: gapped batches)
     PgDev<uint8_t> d_seq, d_opt, d_part;
     PgDev<RlPiece> d_pstats;
     PgDev<pg_realign_read> d_reads;
@@ -428,7 +461,9 @@ pg_status pg_realign_submit(pg_realign *h, const pg_batch *b, const uint32_t *st
     if (!h->k) return pg_fail(h, PG_ERR_STATE, "pg_realign_submit: no model (pg_realign_set_model)");
     if (b->struct_size != sizeof(pg_batch)) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_submit: pg_batch.struct_size %u, this library has %zu", b->struct_size, sizeof(pg_batch));
     if (b->location != PG_LOC_HOST && b->location != PG_LOC_DEVICE) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_submit: location must be PG_LOC_HOST or PG_LOC_DEVICE");
-    if (!(b->flags & PG_BATCH_ALL_MATCHES)) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_submit: the batch must carry PG_BATCH_ALL_MATCHES (every op a match, as `reform` writes them)");
+    const bool gapped = (b->flags & PG_BATCH_GAPPED) != 0;
+    if (gapped && (b->flags & PG_BATCH_ALL_MATCHES)) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_submit: a batch carries PG_BATCH_GAPPED or PG_BATCH_ALL_MATCHES, not both");
+    if (!gapped && !(b->flags & PG_BATCH_ALL_MATCHES)) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_submit: the batch must carry PG_BATCH_ALL_MATCHES (every op a match, as `reform` writes them)");
     const uint64_t n = b->n_reads;
     if (n > 0x7fffffffull) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_submit: batch too large");
     if (!b->sig_off || !b->seq_off || !b->op_off || (n && (!b->query_start || !status || !a || !bb))) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_submit: null array");
@@ -456,7 +491,10 @@ pg_status pg_realign_submit(pg_realign *h, const pg_batch *b, const uint32_t *st
         const uint64_t lb = h->op_off[r + 1] - h->op_off[r];
         if (lb > 0x7fffffffull) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_submit: read %llu has %llu ops (at most 2^31 - 1)", (unsigned long long)r, (unsigned long long)lb);
         if (status[r] == PG_FIT_ST_OK) {
-            if (h->seq_off[r + 1] - h->seq_off[r] < lb)
+            if (gapped && h->seq_off[r + 1] - h->seq_off[r] > PG_FIT_MAX_SLICE)
+                return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_submit: read %llu has a reference slice of %llu bases (at most 2^32 - 1)", (unsigned long long)r,
+                               (unsigned long long)(h->seq_off[r + 1] - h->seq_off[r]));
+            if (!gapped && h->seq_off[r + 1] - h->seq_off[r] < lb)
                 return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_submit: read %llu has %llu ops and %llu bases (an accepted read has as many bases as ops)", (unsigned long long)r,
                                (unsigned long long)lb, (unsigned long long)(h->seq_off[r + 1] - h->seq_off[r]));
             if (!std::isfinite(a[r]) || !std::isfinite(bb[r]) || !(bb[r] > 0) || !std::isfinite(1.0 / bb[r]))
@@ -512,10 +550,11 @@ pg_status pg_realign_submit(pg_realign *h, const pg_batch *b, const uint32_t *st
         B.sig = h->d_sig.p; B.sig_off = h->d_sigoff.p; B.seq = h->d_seq.p; B.seq_off = h->d_seqoff.p; B.op_n = h->d_opn.p; B.op_t = h->d_opt.p; B.op_off = h->d_opoff.p;
     }
     RL_ENSURE(h->d_pfirst, (n + 1) * 4); RL_ENSURE(h->d_pread, n_pieces * 4); RL_ENSURE(h->d_pstart, n_pieces * 8); RL_ENSURE(h->d_psum, n_pieces * 8);
+    if (gapped) { RL_ENSURE(h->d_pcol, n_pieces * 8); RL_ENSURE(h->d_pcsum, n_pieces * 8); }
     RL_ENSURE(h->d_part, n); RL_ENSURE(h->d_ab, n * 16); RL_ENSURE(h->d_out[tgt], n_ops * 4); RL_ENSURE(h->d_pstats, n_pieces * sizeof(RlPiece));
     RL_ENSURE(h->d_reads, n * sizeof(pg_realign_read));
 #undef RL_ENSURE
-    B.piece_first = h->d_pfirst.p; B.piece_read = h->d_pread.p; B.piece_start = h->d_pstart.p; B.part = h->d_part.p; B.ab = h->d_ab.p;
+    B.piece_first = h->d_pfirst.p; B.piece_read = h->d_pread.p; B.piece_start = h->d_pstart.p; B.piece_col = h->d_pcol.p; B.part = h->d_part.p; B.ab = h->d_ab.p;
     const uint32_t blocks = (uint32_t)((n_pieces + kWaves - 1) / kWaves);
     (void)hipGetLastError();
     h->reads.assign(n, pg_realign_read{0, 0, 0, 0, 0, 0, 0});
@@ -532,20 +571,28 @@ pg_status pg_realign_submit(pg_realign *h, const pg_batch *b, const uint32_t *st
         PG_HIP_TRY(h, hipMemcpyAsync(h->d_ab.p, h->ab.data(), n * 16, hipMemcpyHostToDevice, s));
         PG_HIP_TRY(h, hipMemsetAsync(h->d_flag.p, 0, sizeof(uint32_t), s));
         PG_HIP_TRY(h, hipMemsetAsync(h->d_flag.p + 1, 0xff, sizeof(uint32_t), s));
-        hipLaunchKernelGGL(k_rl_span, dim3(blocks), dim3(kThreads), 0, s, B, h->d_psum.p, h->d_flag.p);
+        if (gapped) hipLaunchKernelGGL(k_rl_span<true>, dim3(blocks), dim3(kThreads), 0, s, B, h->d_psum.p, h->d_pcsum.p, h->d_flag.p);
+        else hipLaunchKernelGGL(k_rl_span<false>, dim3(blocks), dim3(kThreads), 0, s, B, h->d_psum.p, (uint64_t *)nullptr, h->d_flag.p);
         PG_HIP_TRY(h, hipGetLastError());
-        hipLaunchKernelGGL(k_rl_starts, dim3(read_blocks), dim3(kThreads), 0, s, B, h->d_psum.p, h->d_pstart.p, h->d_flag.p);
+        if (gapped) hipLaunchKernelGGL(k_rl_starts<true>, dim3(read_blocks), dim3(kThreads), 0, s, B, h->d_psum.p, h->d_pcsum.p, h->d_pstart.p, h->d_pcol.p, h->d_flag.p);
+        else hipLaunchKernelGGL(k_rl_starts<false>, dim3(read_blocks), dim3(kThreads), 0, s, B, h->d_psum.p, (const uint64_t *)nullptr, h->d_pstart.p, (uint64_t *)nullptr, h->d_flag.p);
         PG_HIP_TRY(h, hipGetLastError());
         PG_HIP_TRY(h, hipMemcpyAsync(flag, h->d_flag.p, sizeof flag, hipMemcpyDeviceToHost, s));
         PG_HIP_TRY(h, hipStreamSynchronize(s));
         h->busy = false;
-        if (flag[0]) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_submit: the batch carries PG_BATCH_ALL_MATCHES but holds an op that is no match (an I, a D or an unknown op)");
+        if (gapped && (flag[0] & 2u)) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_submit: the batch carries PG_BATCH_GAPPED but holds an op code above 2 (0 match, 1 I, 2 D)");
+        if (gapped && flag[1] != 0xffffffffu)
+            return pg_fail(h, PG_ERR_INVALID_ARG, (flag[1] & 1u) ? "pg_realign_submit: read %llu has the status ok, but its reference slice has not as many bases as its ops have columns (the status of another batch?)"
+                                                                 : "pg_realign_submit: read %llu has the status ok, but its ops leave its samples (the status of another batch?)",
+                           (unsigned long long)(flag[1] >> 1));
+        if (!gapped && flag[0]) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_submit: the batch carries PG_BATCH_ALL_MATCHES but holds an op that is no match (an I, a D or an unknown op)");
         if (flag[1] != 0xffffffffu)
             return pg_fail(h, PG_ERR_INVALID_ARG, "pg_realign_submit: read %llu has the status ok, but its ops leave its samples (the status of another batch?)", (unsigned long long)flag[1]);
         // ---- the alignment, and the reads' records
         h->busy = true;
         PG_HIP_TRY(h, hipEventRecord(h->ev[0], s));
-        hipLaunchKernelGGL(k_rl_align, dim3(blocks), dim3(kThreads), 0, s, B, h->d_out[tgt].p, h->d_pstats.p);
+        if (gapped) hipLaunchKernelGGL(k_rl_align<true>, dim3(blocks), dim3(kThreads), 0, s, B, h->d_out[tgt].p, h->d_pstats.p);
+        else hipLaunchKernelGGL(k_rl_align<false>, dim3(blocks), dim3(kThreads), 0, s, B, h->d_out[tgt].p, h->d_pstats.p);
         PG_HIP_TRY(h, hipGetLastError());
         PG_HIP_TRY(h, hipEventRecord(h->ev[1], s));
         hipLaunchKernelGGL(k_rl_reads, dim3(read_blocks), dim3(kThreads), 0, s, B, h->d_pstats.p, h->d_reads.p);
@@ -567,6 +614,22 @@ pg_status pg_realign_walk(const pg_realign_params *p, const uint32_t *levels, ui
         return PG_ERR_INVALID_ARG;
     PgRlRead r;
     if (!pg_rl_walk_host(seq, lb, op_n, q, sig, n_sig, levels, k, p->sig_move_offset, p->rna != 0, p->min_dur, p->max_dur, p->band, p->min_len, p->phase, a, b, op_out, r))
+        return PG_ERR_INPUT;
+    *out = pg_realign_read{r.n_free, r.n_moved, r.sum_abs_shift, (uint64_t)r.cost_before, (uint64_t)(r.cost_before >> 64), (uint64_t)r.cost_after, (uint64_t)(r.cost_after >> 64)};
+    return PG_OK;
+}
+
+pg_status pg_realign_walk_gapped(const pg_realign_params *p, const uint32_t *levels, uint32_t k, const uint8_t *seq, uint64_t n_seq, const uint32_t *op_n, const uint8_t *op_t,
+                                 uint32_t lb, int64_t q, const int16_t *sig, uint64_t n_sig, double a, double b, uint32_t *op_out, pg_realign_read *out) {
+    if (!p || !levels || !out || (lb && (!op_n || !op_t || !op_out)) || (n_seq && !seq) || (n_sig && !sig) || k < 1 || k > PG_FIT_MAX_K) return PG_ERR_INVALID_ARG;
+    if (p->struct_size != sizeof(pg_realign_params) || !pg_rl_params_ok(p->band, p->min_len, p->min_dur, p->max_dur) || p->sig_move_offset > 64 || p->phase >= PG_FIT_PIECE)
+        return PG_ERR_INVALID_ARG;
+    for (uint32_t e = 0; e < lb; e++)
+        if (op_t[e] > PG_FIT_OP_D) return PG_ERR_INVALID_ARG;
+    if (n_seq > PG_FIT_MAX_SLICE) return PG_ERR_INVALID_ARG;
+    static const uint8_t none = 0;
+    PgRlRead r;
+    if (!pg_rl_walk_any(seq, n_seq, lb ? op_t : &none, lb, op_n, q, sig, n_sig, levels, k, p->sig_move_offset, p->rna != 0, p->min_dur, p->max_dur, p->band, p->min_len, p->phase, a, b, op_out, r))
         return PG_ERR_INPUT;
     *out = pg_realign_read{r.n_free, r.n_moved, r.sum_abs_shift, (uint64_t)r.cost_before, (uint64_t)(r.cost_before >> 64), (uint64_t)r.cost_after, (uint64_t)(r.cost_after >> 64)};
     return PG_OK;

@@ -91,6 +91,7 @@ class Batch:
     n_ops: int = 0   # device batches: op_off[n_reads] when known (pg_batch.n_ops); 0 = the library reads it back (one sync per call)
     all_matches: bool = False  # the batch holds match ops only and the caller vouches for it (PG_BATCH_ALL_MATCHES, verified on the device)
     resident: bool = False     # device batch, engine on the caller's stream: nothing queued on that stream produces the arrays (PG_BATCH_RESIDENT)
+    gapped: bool = False       # ModelFit / Realigner: ops on the signal-to-reference alignment (op_t 0 match, 1 I, 2 D), seq the reference slices (PG_BATCH_GAPPED)
 
     def validate_host(self):
         for name, dt in _BATCH_FIELDS:
@@ -109,7 +110,7 @@ class Batch:
             if name == "sig":  # 16-byte slack so the tail vector of the last read stays inside the allocation
                 t = torch.cat([t, torch.zeros(8, dtype=t.dtype)])
             kw[name] = t.to(device)
-        return Batch(n_reads=self.n_reads, on_device=True, n_ops=int(self.op_off[-1]), all_matches=not bool(np.any(self.op_t)), **kw)
+        return Batch(n_reads=self.n_reads, on_device=True, n_ops=int(self.op_off[-1]), all_matches=not self.gapped and not bool(np.any(self.op_t)), gapped=self.gapped, **kw)
 
     def slice_reads(self, lo: int, hi: int) -> "Batch":
         """Host batch holding reads [lo, hi) (used to shard a PAF-ordered batch across ranks)."""
@@ -297,7 +298,7 @@ def _c_batch(b: "Batch"):
     cb.location = _abi.PG_LOC_DEVICE if b.on_device else _abi.PG_LOC_HOST
     cb.n_reads = b.n_reads
     cb.n_ops = b.n_ops if b.on_device else 0
-    cb.flags = (_abi.PG_BATCH_ALL_MATCHES if b.all_matches else 0) | (_abi.PG_BATCH_RESIDENT if (b.resident and b.on_device) else 0)
+    cb.flags = (_abi.PG_BATCH_ALL_MATCHES if b.all_matches else 0) | (_abi.PG_BATCH_RESIDENT if (b.resident and b.on_device) else 0) | (_abi.PG_BATCH_GAPPED if b.gapped else 0)
     for name, _ in _BATCH_FIELDS:
         setattr(cb, name, _ptr(getattr(b, name)))
     return cb
@@ -1931,7 +1932,7 @@ def ref_slices(contigs, contig, pos, ref_len, reverse=None, device: int = 0):
 
 # ---- fit: a k-mer model scored against signal and move tables (pg_fit_*) --------------------------------------------------------------
 
-FIT_STATUS_NAMES = {0: "ok", 1: "out_of_signal", 2: "too_long", 3: "few_events", 4: "flat", 5: "negative_scale",
+FIT_STATUS_NAMES = {0: "ok", 1: "out_of_signal", 2: "too_long", 3: "few_events", 4: "flat", 5: "negative_scale", 6: "ref_length",
                     17: "no_move_in_table", 18: "negative_tail", 19: "bases_left_over", 20: "bad_stride"}
 
 
@@ -2037,8 +2038,9 @@ class ModelFit:
         self._check(self._lib.pg_fit_set_stream(self._h, ptr))
 
     def submit(self, batch: "Batch", skip=None) -> FitReads:
-        """One batch (host or device) with all_matches set: the caller vouches that it holds match ops only, the device verifies it; a
-        batch without the flag is refused (PG_ERR_INVALID_ARG). skip: per read a code, non-zero = the read takes no part."""
+        """One batch (host or device) with all_matches set: the caller vouches that it holds match ops only, the device verifies it; or
+        with gapped set: ops on the signal-to-reference alignment (I and D among them) and seq the reads' reference slices. A batch with
+        neither flag, or with both, is refused (PG_ERR_INVALID_ARG). skip: per read a code, non-zero = the read takes no part."""
         cb = _c_batch(batch)
         sk = None if skip is None else np.ascontiguousarray(skip, dtype=np.uint32)
         out = _abi.PgFitReads()
@@ -2235,9 +2237,10 @@ def realign_rounds(levels, k: int, batch: "Batch", rounds: int, sig_move_offset:
 
 
 def realign_walk(levels, k: int, seq, ops, q: int, sig, a: float, b: float, sig_move_offset: int = 0, rna: bool = False, min_dur: int = 5, max_dur: int = 70, band: int = 10,
-                 min_len: int = 3, phase: int = 0):
+                 min_len: int = 3, phase: int = 0, op_t=None):
     """The rule for one fitted read on the host (pg_realign_walk; no GPU needed): (refined ops, n_free, n_moved, sum_abs_shift, cost_before,
-    cost_after), or None when the ops leave the samples."""
+    cost_after), or None when the ops leave the samples. op_t: the read is a gapped one (seq its reference slice; pg_realign_walk_gapped),
+    None as well when the slice has not as many bases as the ops have columns."""
     lib = _abi.load()
     p = _realign_params(sig_move_offset, rna, min_dur, max_dur, band, min_len, phase)
     lv = np.ascontiguousarray(levels, dtype=np.uint32)
@@ -2246,7 +2249,14 @@ def realign_walk(levels, k: int, seq, ops, q: int, sig, a: float, b: float, sig_
     sg = np.ascontiguousarray(sig, dtype=np.int16)
     new = np.zeros(o.size, np.uint32)
     rd = _abi.PgRealignRead()
-    st = lib.pg_realign_walk(C.byref(p), lv.ctypes.data, k, s.ctypes.data, o.size, o.ctypes.data, q, sg.ctypes.data, sg.size, a, b, new.ctypes.data, C.byref(rd))
+    if op_t is None:
+        st = lib.pg_realign_walk(C.byref(p), lv.ctypes.data, k, s.ctypes.data, o.size, o.ctypes.data, q, sg.ctypes.data, sg.size, a, b, new.ctypes.data, C.byref(rd))
+    else:
+        t = np.ascontiguousarray(op_t, dtype=np.uint8)
+        if t.size != o.size:
+            raise ValueError("op_t needs one code per op")
+        st = lib.pg_realign_walk_gapped(C.byref(p), lv.ctypes.data, k, s.ctypes.data, s.size, o.ctypes.data, t.ctypes.data, o.size, q, sg.ctypes.data, sg.size, a, b,
+                                        new.ctypes.data, C.byref(rd))
     if st == _abi.PG_ERR_INPUT:
         return None
     if st != 0:
