@@ -1,7 +1,7 @@
 # Build of the MI355X-native gmove path. `make` builds everything the tests/bench need:
 #   poregen_amd/libpgmove.so      HIP kernels + C ABI (include/pgmove.h), gfx950 only
 #   poregen_amd/_pg_hosttest.so   host-only build of the shared host/device arithmetic (CPU tests)
-#   bin/poregen                   the drop-in `poregen gmove` / `reform` / `kmer_freq` / `f1_score` / `subtool0` / `pa_stats` / `model` / `offsets` / `transform` / `fit` / `realign` / `simulate` CLI (host C++ over the C ABI)
+#   bin/poregen                   the drop-in `poregen gmove` / `reform` / `kmer_freq` / `f1_score` / `subtool0` / `pa_stats` / `model` / `offsets` / `transform` / `fit` / `realign` / `simulate` / `eventalign` CLI (host C++ over the C ABI)
 #   oracle/                       the CPU oracle (test infrastructure)
 HIPCC ?= /opt/rocm/bin/hipcc
 CXX ?= g++
@@ -13,11 +13,11 @@ CSRC = poregen_amd/csrc
 HOST = $(CSRC)/host
 # every list once: the translation units of libpgmove.so, the headers they and the host code compile (every object depends on all of them),
 # the sources of the CLI and the sources of the host test shim
-MODULES = pg_kernels pg_place pg_api pg_model pg_job pg_text pg_kfreq pg_f1 pg_pamean pg_svb pg_svbenc pg_dumptext pg_transform pg_mvops pg_refops pg_refseq pg_pool pg_evstat pg_fit pg_realign pg_sim
+MODULES = pg_kernels pg_place pg_api pg_model pg_job pg_text pg_kfreq pg_f1 pg_pamean pg_svb pg_svbenc pg_dumptext pg_transform pg_mvops pg_refops pg_refseq pg_pool pg_evstat pg_fit pg_realign pg_evalign pg_sim
 DEV_HDRS = $(wildcard $(CSRC)/*.h) include/pgmove.h
 HOST_HDRS = $(wildcard $(HOST)/*.h)
 CLI_SRCS = $(addprefix $(HOST)/,main.cpp gmove_cli.cpp reform_cli.cpp kmer_freq_cli.cpp kfreq_reads.cpp f1_cli.cpp f1_reader.cpp subtool0_cli.cpp model_cli.cpp offsets_cli.cpp fit_cli.cpp \
-           realign_cli.cpp simulate_cli.cpp transform_cli.cpp io.cpp dump.cpp moverecs.cpp)
+           realign_cli.cpp simulate_cli.cpp eventalign_cli.cpp transform_cli.cpp io.cpp dump.cpp moverecs.cpp)
 HOSTTEST_SRCS = $(CSRC)/pg_hosttest.cpp $(HOST)/io.cpp $(HOST)/dump.cpp $(HOST)/moverecs.cpp
 
 all: poregen_amd/libpgmove.so poregen_amd/_pg_hosttest.so bin/poregen oracle_build

@@ -125,6 +125,13 @@
  * pg_realign_set_model / _submit / the move table's boundaries moved within a band to where the samples fit the model's levels best
  * _kernel_ms / _walk
  *
+ * The reference's own evaluation of a finished model, scripts/eventaling.sh (f5c eventalign --kmer-model), as the project's own rule:
+ * pg_evalign_create / _destroy /   (no counterpart)
+ * _last_error / _set_stream
+ * pg_evalign_set_model / _submit / one row per event that fit counts: its place, level and spread in the model's units, the model's
+ * _copy_text / _kernel_ms / _walk  level and level_stdv for its k-mer, the standardized level; nanopolish / f5c eventalign columns
+ * / _walk_gapped / _row_text
+ *
  * The generative direction (scripts/sim.sh asks squigulator; the rule here is the project's own, fit's inverted):
  * pg_sim_create / _destroy /        (no counterpart)
  * _last_error / _set_stream / _stream
@@ -1159,6 +1166,85 @@ pg_status pg_realign_walk(const pg_realign_params *params, const uint32_t *level
 pg_status pg_realign_walk_gapped(const pg_realign_params *params, const uint32_t *levels, uint32_t kmer_size, const uint8_t *seq, uint64_t n_seq, const uint32_t *op_n,
                                  const uint8_t *op_t, uint32_t lb, int64_t query_start, const int16_t *sig, uint64_t n_sig, double a, double b, uint32_t *op_out,
                                  pg_realign_read *out);
+
+/* ---- eventalign: one row per counted event against the k-mer model ---------------------------------------------------------------------------
+ * The per-event view of what fit sums up: for every event that fit counts, of every read whose fit is PG_FIT_ST_OK, where it lies, its
+ * level and spread in the model's units, the model's level and level_stdv for its k-mer and the standardized level. Input: a batch as
+ * pg_fit_submit takes it (PG_BATCH_ALL_MATCHES or PG_BATCH_GAPPED), and per read the status, a and b that pg_fit_submit returned for this
+ * same batch under the same model, sig_move_offset, rna, min_dur and max_dur -- as pg_realign_submit takes them. The events are the
+ * basecaller's segmentation (refined by realign where the caller ran it), not f5c's; the columns are nanopolish / f5c
+ * `eventalign --scale-events --signal-index`.
+ * Per event of n raw samples r_i, with L and SD its k-mer's level and level_stdv in 1e-3 pA: u_i = 1000 r_i; m_raw the mean and s_raw the
+ * sample standard deviation (0 for n = 1) of the u_i, each rounded to the nearest unit with halves up, in integers; per read
+ * A = 1000.0 * a, G = (1.0 / b) / 1000.0; mean_u = llrint(((double)m_raw - A) * G), stdv_u = llrint((double)s_raw * G), the products cut
+ * to +-2^21 first; z_c = floor((200 (mean_u - L) + SD) / (2 SD)), hundredths of a standard deviation. Rows are ordered by (read, event)
+ * and dense; nothing depends on the device's scheduling. No CPU fallback: PG_ERR_NO_DEVICE without a GPU (pg_evalign_walk is the rule on
+ * the host, for tests). */
+typedef struct pg_evalign pg_evalign;
+enum { PG_EVALIGN_TEXT = 1u << 0,       /* the text is produced (a header line, then one line per row) */
+       PG_EVALIGN_HOST_ROWS = 1u << 1 };/* pg_evalign_out.rows_host is filled */
+typedef struct {
+    uint32_t struct_size;          /* sizeof(pg_evalign_params) */
+    uint32_t sig_move_offset;      /* -m            at most 64 */
+    uint32_t min_dur, max_dur;     /* --min_dur, --max_dur: 1 <= min_dur <= max_dur <= 4096 */
+    int32_t  rna;                  /* --rna */
+    uint32_t sample_rate;          /* --sample_rate: 0 = event_length in samples; 1 .. 10^6 = in seconds, five decimals */
+    uint32_t flags;                /* PG_EVALIGN_* */
+} pg_evalign_params;
+typedef struct {                   /* one row, 40 bytes */
+    uint32_t read, event;          /* the read's index in the batch; the op's index in its read */
+    uint64_t start;                /* the event's first sample, counted in the read's signal */
+    uint32_t n, slot, first;       /* samples; the k-mer's rank in ACGT order; its first base in the read's seq */
+    int32_t  mean_u, stdv_u, z_c;  /* 1e-3 pA, 1e-3 pA, hundredths */
+} pg_evalign_row;
+typedef struct {                   /* per read, host arrays [n_reads]; any pointer may be NULL for its default */
+    const int64_t  *ref_start;     /* forward-strand 0-based coordinate of the leftmost contig base the read's seq covers; NULL: 0 */
+    const uint8_t  *reverse;       /* non-zero: a reverse-strand read; NULL: forward */
+    const uint8_t  *contig;        /* the reads' contig strings back to back, contig_off[n_reads + 1]; NULL: empty */
+    const uint64_t *contig_off;
+    const uint8_t  *label;         /* the read_index column, label_off[n_reads + 1]; NULL: the decimal index of the read in the batch */
+    const uint64_t *label_off;
+} pg_evalign_meta;
+typedef struct {                   /* one submit; everything is owned by the handle and valid until its next submit / destroy */
+    uint32_t struct_size;          /* sizeof(pg_evalign_out), set by the caller */
+    uint32_t reserved;
+    uint64_t n_reads, n_rows;
+    const uint64_t *row_off;       /* host [n_reads + 1]: read r has the rows [row_off[r], row_off[r + 1]) */
+    const pg_evalign_row *rows;    /* DEVICE memory [n_rows] */
+    const pg_evalign_row *rows_host; /* host [n_rows] with PG_EVALIGN_HOST_ROWS, else NULL */
+    const char *text;              /* DEVICE memory [text_bytes] with PG_EVALIGN_TEXT, else NULL */
+    uint64_t text_bytes;
+} pg_evalign_out;
+pg_status pg_evalign_create(const pg_evalign_params *params, int32_t device, pg_evalign **out);
+void      pg_evalign_destroy(pg_evalign *h);
+const char *pg_evalign_last_error(const pg_evalign *h); /* h may be NULL: error of the last failed pg_evalign_create */
+/* levels as pg_fit_set_model takes them; stdvs: host uint32[4^kmer_size], level_stdv in 1e-3 pA, below 2^18. A k-mer with a level and a
+ * level_stdv of 0 refuses the model (PG_ERR_INPUT): the handle then has no model, and a submit fails with PG_ERR_INPUT until one is set. */
+pg_status pg_evalign_set_model(pg_evalign *h, const uint32_t *levels, const uint32_t *stdvs, uint32_t kmer_size);
+/* The kernels and copies of the following calls go to a caller-owned HIP stream (hipStream_t as void*); NULL restores the handle's own. */
+pg_status pg_evalign_set_stream(pg_evalign *h, void *hip_stream);
+/* One batch, synchronous. status, a, b: host arrays [n_reads] of pg_fit_reads; meta may be NULL. Refused, the handle staying usable: both
+ * batch flags or neither, an op code above 2 (an op that is no match in a PG_BATCH_ALL_MATCHES batch), a read with PG_FIT_ST_OK whose ops
+ * leave its samples or whose a, b are no fit's (PG_ERR_INVALID_ARG); more than 2^28 samples of signal (PG_ERR_UNSUPPORTED). */
+pg_status pg_evalign_submit(pg_evalign *h, const pg_batch *batch, const uint32_t *status, const double *a, const double *b, const pg_evalign_meta *meta, pg_evalign_out *out);
+/* The last submit's text into a host buffer of the caller's (cap >= text_bytes) */
+pg_status pg_evalign_copy_text(pg_evalign *h, char *dst, uint64_t cap);
+/* HIP-event time of the three stages (count, rows, text: lengths + scan + write) since create or the last call of this; ms: double[3] */
+pg_status pg_evalign_kernel_ms(pg_evalign *h, double *ms);
+/* Host only, no device needed: the rule for one fitted read. seq: its lb bases, op_n: lb ops, sig: its n_sig samples. rows_out (cap
+ * entries) gets the rows, `read` 0; *n_rows their number (also when cap is too small: PG_ERR_INVALID_ARG then). PG_ERR_INPUT: the ops
+ * leave the samples, or a k-mer with a level has a level_stdv of 0. */
+pg_status pg_evalign_walk(const pg_evalign_params *params, const uint32_t *levels, const uint32_t *stdvs, uint32_t kmer_size, const uint8_t *seq, uint32_t lb, const uint32_t *op_n,
+                          int64_t query_start, const int16_t *sig, uint64_t n_sig, double a, double b, pg_evalign_row *rows_out, uint64_t cap, uint64_t *n_rows);
+/* The same for one read of a PG_BATCH_GAPPED batch: seq is its reference slice of n_seq bases, op_t its op codes. PG_ERR_INPUT also when
+ * the slice has not as many bases as the ops have columns; PG_ERR_INVALID_ARG: an op code above 2. */
+pg_status pg_evalign_walk_gapped(const pg_evalign_params *params, const uint32_t *levels, const uint32_t *stdvs, uint32_t kmer_size, const uint8_t *seq, uint64_t n_seq,
+                                 const uint32_t *op_n, const uint8_t *op_t, uint32_t lb, int64_t query_start, const int16_t *sig, uint64_t n_sig, double a, double b,
+                                 pg_evalign_row *rows_out, uint64_t cap, uint64_t *n_rows);
+/* Host only: the line of one row as the device writes it. contig / label: the read's strings; kmer: the kmer_size letters of the read's seq
+ * at row->first; n_seq: the bases of the read's seq. Returns the bytes the line has; they are written when cap holds them. */
+uint64_t  pg_evalign_row_text(const pg_evalign_row *row, const uint8_t *contig, uint32_t contig_len, const uint8_t *label, uint32_t label_len, const uint8_t *kmer,
+                              uint32_t kmer_size, uint64_t n_seq, int64_t ref_start, int32_t reverse, uint32_t sample_rate, uint32_t level, uint32_t stdv, char *dst, uint64_t cap);
 
 /* ---- simulate: raw signal and its true alignment drawn from a k-mer model --------------------------------------------------------------------
  * The generative direction of fit's rule, the project's own (not squigulator's algorithm). Random numbers are Philox4x32-10 with the key

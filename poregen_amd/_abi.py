@@ -65,6 +65,8 @@ EXPORTS = [
     "pg_fit_parse_model", "pg_fit_residuals",
     "pg_realign_create", "pg_realign_destroy", "pg_realign_last_error", "pg_realign_set_model", "pg_realign_set_stream", "pg_realign_submit", "pg_realign_kernel_ms",
     "pg_realign_walk", "pg_realign_walk_gapped", "pg_realign_set_phase",
+    "pg_evalign_create", "pg_evalign_destroy", "pg_evalign_last_error", "pg_evalign_set_model", "pg_evalign_set_stream", "pg_evalign_submit", "pg_evalign_copy_text",
+    "pg_evalign_kernel_ms", "pg_evalign_walk", "pg_evalign_walk_gapped", "pg_evalign_row_text",
     "pg_sim_create", "pg_sim_destroy", "pg_sim_last_error", "pg_sim_set_stream", "pg_sim_stream", "pg_sim_set_model", "pg_sim_generate", "pg_sim_kernel_ms", "pg_sim_walk",
     "pg_sim_parse_model", "pg_sim_parse_dwell",
     "pg_sigenc_create", "pg_sigenc_destroy", "pg_sigenc_last_error", "pg_sigenc_set_stream", "pg_sigenc_stream", "pg_sigenc_bound", "pg_sigenc_encode", "pg_sigenc_kernel_ms",
@@ -246,6 +248,25 @@ class PgRealignRead(C.Structure):
 
 class PgRealignReads(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("n_reads", C.c_uint64), ("n_ops", C.c_uint64), ("op_n", C.c_void_p), ("reads", C.c_void_p)]
+
+
+class PgEvalignParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("sig_move_offset", C.c_uint32), ("min_dur", C.c_uint32), ("max_dur", C.c_uint32), ("rna", C.c_int32),
+                ("sample_rate", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class PgEvalignMeta(C.Structure):
+    _fields_ = [("ref_start", C.c_void_p), ("reverse", C.c_void_p), ("contig", C.c_void_p), ("contig_off", C.c_void_p), ("label", C.c_void_p), ("label_off", C.c_void_p)]
+
+
+class PgEvalignOut(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("n_reads", C.c_uint64), ("n_rows", C.c_uint64), ("row_off", C.c_void_p), ("rows", C.c_void_p),
+                ("rows_host", C.c_void_p), ("text", C.c_void_p), ("text_bytes", C.c_uint64)]
+
+
+PG_EVALIGN_TEXT, PG_EVALIGN_HOST_ROWS = 1, 2
+# pg_evalign_row as a numpy structured type (40 bytes)
+EVALIGN_ROW_DTYPE = [("read", "<u4"), ("event", "<u4"), ("start", "<u8"), ("n", "<u4"), ("slot", "<u4"), ("first", "<u4"), ("mean_u", "<i4"), ("stdv_u", "<i4"), ("z_c", "<i4")]
 
 
 class PgSimParams(C.Structure):
@@ -451,6 +472,22 @@ def load():
             lib.pg_realign_walk_gapped.restype = i32
         if hasattr(lib, "pg_realign_set_phase"):  # (a library built from the tree before the phase: --lib A/B runs at phase 0)
             lib.pg_realign_set_phase.argtypes = [vp, u32]; lib.pg_realign_set_phase.restype = i32
+    if hasattr(lib, "pg_evalign_create"):  # (as above: a library built from an older tree has no eventalign handle)
+        dbl = C.c_double
+        lib.pg_evalign_create.argtypes = [C.POINTER(PgEvalignParams), i32, C.POINTER(vp)]; lib.pg_evalign_create.restype = i32
+        lib.pg_evalign_destroy.argtypes = [vp]; lib.pg_evalign_destroy.restype = None
+        lib.pg_evalign_last_error.argtypes = [vp]; lib.pg_evalign_last_error.restype = C.c_char_p
+        lib.pg_evalign_set_model.argtypes = [vp, vp, vp, u32]; lib.pg_evalign_set_model.restype = i32
+        lib.pg_evalign_set_stream.argtypes = [vp, vp]; lib.pg_evalign_set_stream.restype = i32
+        lib.pg_evalign_submit.argtypes = [vp, C.POINTER(PgBatch), vp, vp, vp, C.POINTER(PgEvalignMeta), C.POINTER(PgEvalignOut)]; lib.pg_evalign_submit.restype = i32
+        lib.pg_evalign_copy_text.argtypes = [vp, vp, C.c_uint64]; lib.pg_evalign_copy_text.restype = i32
+        lib.pg_evalign_kernel_ms.argtypes = [vp, vp]; lib.pg_evalign_kernel_ms.restype = i32
+        lib.pg_evalign_walk.argtypes = [C.POINTER(PgEvalignParams), vp, vp, u32, vp, u32, vp, C.c_int64, vp, C.c_uint64, dbl, dbl, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        lib.pg_evalign_walk.restype = i32
+        lib.pg_evalign_walk_gapped.argtypes = [C.POINTER(PgEvalignParams), vp, vp, u32, vp, C.c_uint64, vp, vp, u32, C.c_int64, vp, C.c_uint64, dbl, dbl, vp, C.c_uint64,
+                                               C.POINTER(C.c_uint64)]
+        lib.pg_evalign_walk_gapped.restype = i32
+        lib.pg_evalign_row_text.argtypes = [vp, vp, u32, vp, u32, vp, u32, C.c_uint64, C.c_int64, i32, u32, u32, u32, vp, C.c_uint64]; lib.pg_evalign_row_text.restype = C.c_uint64
     if hasattr(lib, "pg_sim_create"):  # (as above: a library built from an older tree has no simulator)
         lib.pg_sim_create.argtypes = [C.POINTER(PgSimParams), i32, C.POINTER(vp)]; lib.pg_sim_create.restype = i32
         lib.pg_sim_destroy.argtypes = [vp]; lib.pg_sim_destroy.restype = None

@@ -1,4 +1,4 @@
-// main.cpp -- `poregen` dispatcher (src/main.c:64-103): the gmove, kmer_freq, f1_score, subtool0, pa_stats, model, offsets, fit, realign and simulate subtools (device path),
+// main.cpp -- `poregen` dispatcher (src/main.c:64-103): the gmove, kmer_freq, f1_score, subtool0, pa_stats, model, offsets, fit, realign, simulate and eventalign subtools (device path),
 // reform and transform (host-only; transform --signal runs pa_stats' device path).
 #include <cstdio>
 #include <cstring>
@@ -19,6 +19,7 @@ static int offsets_main(int, char **) { fprintf(stderr, "[poregen] this build ho
 static int fit_main(int, char **) { fprintf(stderr, "[poregen] this build holds reform only\n"); return 1; }
 static int realign_main(int, char **) { fprintf(stderr, "[poregen] this build holds reform only\n"); return 1; }
 static int simulate_main(int, char **) { fprintf(stderr, "[poregen] this build holds reform only\n"); return 1; }
+static int eventalign_main(int, char **) { fprintf(stderr, "[poregen] this build holds reform only\n"); return 1; }
 #else
 int gmove_main(int argc, char **argv);
 int kmer_freq_main(int argc, char **argv);
@@ -30,6 +31,7 @@ int offsets_main(int argc, char **argv);
 int fit_main(int argc, char **argv);
 int realign_main(int argc, char **argv);
 int simulate_main(int argc, char **argv);
+int eventalign_main(int argc, char **argv);
 #endif
 int reform_main(int argc, char **argv);
 int transform_main(int argc, char **argv);
@@ -39,7 +41,7 @@ static double cputime() { struct rusage r; getrusage(RUSAGE_SELF, &r); return r.
 static long peakrss() { struct rusage r; getrusage(RUSAGE_SELF, &r); return r.ru_maxrss * 1024; }
 
 static int usage(FILE *fp, int code) {
-    fprintf(fp, "Usage: poregen <command> [options]\n\ncommand:\n         gmove      move k-mer signal samples into k-mer buckets (MI355X implementation)\n         reform     rewrite a SAM/BAM move table as TSV or as PAF with ss:Z:\n         kmer_freq  count the k-mers of the reads in a FASTQ, BAM or SAM file\n         f1_score   compare two ss signal alignments (SAM/BAM) point by point: TP/FP/TN/FN, F1 score\n         subtool0   mean pA of every read of a SLOW5/BLOW5 file\n         pa_stats   mean and sample standard deviation of every pA value of a SLOW5/BLOW5 file\n         model      k-mer model (median, stddev, dwell) from the files of dump directories\n         offsets    which base of the k-mer decides the level: medians of the dump files pooled by the base at every position\n         transform  the final model file from a raw k-mer model: (median * stdv) + mean, stddev projected onto [2.5, 4]\n         fit        score a k-mer model against signal and move tables: per read shift and scale, per k-mer the residuals\n         realign    refine the event boundaries of the move table against a k-mer model: PAF with ss:Z:, per read and per k-mer the residuals before and after\n         simulate   draw raw signal and its true alignment from a k-mer model: SLOW5/BLOW5, PAF with ss:Z:, FASTQ, SAM with a move table\n");
+    fprintf(fp, "Usage: poregen <command> [options]\n\ncommand:\n         gmove      move k-mer signal samples into k-mer buckets (MI355X implementation)\n         reform     rewrite a SAM/BAM move table as TSV or as PAF with ss:Z:\n         kmer_freq  count the k-mers of the reads in a FASTQ, BAM or SAM file\n         f1_score   compare two ss signal alignments (SAM/BAM) point by point: TP/FP/TN/FN, F1 score\n         subtool0   mean pA of every read of a SLOW5/BLOW5 file\n         pa_stats   mean and sample standard deviation of every pA value of a SLOW5/BLOW5 file\n         model      k-mer model (median, stddev, dwell) from the files of dump directories\n         offsets    which base of the k-mer decides the level: medians of the dump files pooled by the base at every position\n         transform  the final model file from a raw k-mer model: (median * stdv) + mean, stddev projected onto [2.5, 4]\n         fit        score a k-mer model against signal and move tables: per read shift and scale, per k-mer the residuals\n         realign    refine the event boundaries of the move table against a k-mer model: PAF with ss:Z:, per read and per k-mer the residuals before and after\n         simulate   draw raw signal and its true alignment from a k-mer model: SLOW5/BLOW5, PAF with ss:Z:, FASTQ, SAM with a move table\n         eventalign one line per event against a k-mer model: position, level, spread, model level and standardized level (nanopolish / f5c eventalign columns)\n");
     return code;
 }
 
@@ -59,6 +61,7 @@ int main(int argc, char **argv) {
     else if (strcmp(argv[1], "fit") == 0) ret = fit_main(argc - 1, argv + 1);
     else if (strcmp(argv[1], "realign") == 0) ret = realign_main(argc - 1, argv + 1);
     else if (strcmp(argv[1], "simulate") == 0) ret = simulate_main(argc - 1, argv + 1);
+    else if (strcmp(argv[1], "eventalign") == 0) ret = eventalign_main(argc - 1, argv + 1);
     else if (strcmp(argv[1], "--version") == 0 || strcmp(argv[1], "-V") == 0) { fprintf(stdout, "poregen 0.1.0 (pgmove, gfx950)\n"); return 0; }
     else if (strcmp(argv[1], "--help") == 0 || strcmp(argv[1], "-h") == 0) return usage(stdout, 0);
     else { fprintf(stderr, "[poregen] Unrecognised command %s\n", argv[1]); return usage(stderr, 1); }

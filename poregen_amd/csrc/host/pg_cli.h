@@ -60,13 +60,28 @@ inline pg_batch device_batch(const pg_mvops_result &mr, size_t n, uint64_t n_ops
 }
 
 // ---- fit and realign ---------------------------------------------------------------------------------------------------------------
-// the model: parsed and refused on the host, before any device is touched. levels gets 4^PG_FIT_MAX_K entries.
-inline bool load_level_model(const char *tool, const char *path, long long k_opt, std::vector<uint32_t> &levels, uint32_t &k, int32_t &uses_u) {
+// the model: parsed and refused on the host, before any device is touched. levels gets 4^PG_FIT_MAX_K entries. stdvs (may be null): the
+// level_stdv column is kept too, in 1e-3 pA; a row without one, or a k-mer whose level_stdv rounds to 0, then refuses the model.
+inline bool load_level_model(const char *tool, const char *path, long long k_opt, std::vector<uint32_t> &levels, uint32_t &k, int32_t &uses_u, std::vector<uint32_t> *stdvs = nullptr) {
     pgh::MappedFile mf;
     if (!mf.open(path)) { fprintf(stderr, "[%s] cannot open the model %s\n", tool, path); return false; }
     levels.assign((size_t)1 << (2 * PG_FIT_MAX_K), 0);
     char perr[400];
-    if (pg_fit_parse_model(mf.data, mf.size, (uint32_t)k_opt, &k, levels.data(), levels.size(), &uses_u, perr, sizeof perr) == PG_OK) return true;
+    if (!stdvs) {
+        if (pg_fit_parse_model(mf.data, mf.size, (uint32_t)k_opt, &k, levels.data(), levels.size(), &uses_u, perr, sizeof perr) == PG_OK) return true;
+    } else {
+        stdvs->assign(levels.size(), 0);
+        if (pg_sim_parse_model(mf.data, mf.size, (uint32_t)k_opt, &k, levels.data(), stdvs->data(), levels.size(), &uses_u, perr, sizeof perr) == PG_OK) {
+            for (uint64_t s = 0; s < (1ull << (2 * k)); s++)
+                if (levels[s] && !(*stdvs)[s]) {
+                    std::string name(k, 'A');
+                    for (uint32_t j = 0; j < k; j++) name[j] = "ACGT"[(s >> (2 * (k - 1 - j))) & 3];
+                    fprintf(stderr, "[%s] the model %s is refused: the level_stdv of %s is 0 after rounding to 0.001 pA\n", tool, path, name.c_str());
+                    return false;
+                }
+            return true;
+        }
+    }
     fprintf(stderr, "[%s] the model %s is refused: %s\n", tool, path, perr);
     return false;
 }

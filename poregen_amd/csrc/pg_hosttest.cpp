@@ -679,6 +679,40 @@ extern "C" long pgt_realign_pieces(uint32_t lb, uint32_t phase, uint32_t *out, s
     return (long)np;
 }
 
+// ---- eventalign (pg_evalign.h): one event from its samples, the walk of one read, the text of a row ------------------------------------------
+#include "pg_evalign.h"
+extern "C" void pgt_evalign_levels(uint64_t *out3) { out3[0] = PG_EA_MAX_DUR; out3[1] = PG_EA_MAX_RATE; out3[2] = sizeof(PgEaRow); }
+extern "C" int pgt_evalign_params_ok(uint32_t min_dur, uint32_t max_dur, uint32_t rate) { return pg_ea_params_ok(min_dur, max_dur, rate) ? 1 : 0; }
+// one event of n samples under the fit (a, b) and the k-mer's (L, SD): out3 = mean_u, stdv_u, z_c
+extern "C" void pgt_evalign_event(const int16_t *sig, uint32_t n, double a, double b, uint32_t L, uint32_t SD, int32_t *out3) {
+    double A, G; pg_ea_read_scale(a, b, A, G);
+    int64_t s1 = 0; uint64_t s2 = 0;
+    for (uint32_t i = 0; i < n; i++) { const int64_t d = 1000ll * ((int64_t)sig[i] - (int64_t)sig[0]); s1 += d; s2 += (uint64_t)(d * d); }
+    pg_ea_event(sig[0], n, s1, s2, A, G, L, SD, out3[0], out3[1], out3[2]);
+}
+extern "C" int pgt_evalign_z(int64_t mean_u, uint32_t L, uint32_t SD) { return pg_ea_z(mean_u, L, SD); }
+// the rows of one read (op_t null: all matches), 40 bytes each, up to cap of them; returns their number, or -1 - (the walk's code)
+extern "C" long pgt_evalign_walk(const uint8_t *seq, uint64_t n_seq, const uint32_t *op_n, const uint8_t *op_t, uint32_t lb, int64_t q, const int16_t *sig, uint64_t n_sig,
+                                 const uint32_t *levels, const uint32_t *stdvs, uint32_t k, uint32_t m, int rna, uint32_t min_dur, uint32_t max_dur, double a, double b, void *rows,
+                                 size_t cap) {
+    std::vector<PgEaRow> r;
+    const int st = pg_ea_walk_host(seq, n_seq, op_n, op_t, lb, q, sig, n_sig, levels, stdvs, k, m, rna != 0, min_dur, max_dur, a, b, r);
+    if (st != PG_FIT_OK) return st < 0 ? -100 + st : -1 - st;
+    memcpy(rows, r.data(), (r.size() < cap ? r.size() : cap) * sizeof(PgEaRow));
+    return (long)r.size();
+}
+// the line of one row: returns pg_ea_row_len, *written = what pg_ea_row_write stored (dst holds at least 4096 bytes more than the strings)
+extern "C" uint32_t pgt_evalign_row_text(const void *row40, const uint8_t *contig, uint32_t contig_len, const uint8_t *label, uint32_t label_len, const uint8_t *kmer, uint32_t k,
+                                         uint32_t S, int64_t ref_start, int reverse, uint32_t rate, uint32_t L, uint32_t SD, char *dst, uint32_t *written) {
+    PgEaRow o; memcpy(&o, row40, sizeof o);
+    PgEaText t;
+    t.contig = contig; t.contig_len = contig_len; t.label = label; t.label_len = label_len; t.kmer = kmer; t.k = k; t.S = S; t.first = o.first; t.reverse = reverse ? 1 : 0;
+    t.event = o.event; t.n = o.n; t.sample_rate = rate; t.L = L; t.SD = SD; t.mean_u = o.mean_u; t.stdv_u = o.stdv_u; t.z_c = o.z_c; t.ref_start = ref_start; t.start = o.start;
+    *written = pg_ea_row_write(dst, t);
+    return pg_ea_row_len(t);
+}
+extern "C" const char *pgt_evalign_header() { return PG_EA_HEADER; }
+
 // ---- simulate (pg_sim.h): the generator, the rule for one read, the parsers, the command's read drawing and stride rounding -----------------
 #include "pg_sim.h"
 extern "C" void pgt_sim_levels(uint64_t *out6) {

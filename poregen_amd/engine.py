@@ -2264,6 +2264,187 @@ def realign_walk(levels, k: int, seq, ops, q: int, sig, a: float, b: float, sig_
     return new, rd.n_free, rd.n_moved, rd.sum_abs_shift, (rd.cost_before_hi << 64) | rd.cost_before_lo, (rd.cost_after_hi << 64) | rd.cost_after_lo
 
 
+# ---- eventalign: one row per counted event against the k-mer model (pg_evalign_*) ----------------------------------------------------------
+
+EVALIGN_HEADER = ("contig\tposition\treference_kmer\tread_index\tstrand\tevent_index\tevent_level_mean\tevent_stdv\tevent_length\tmodel_kmer\tmodel_mean\tmodel_stdv\t"
+                  "standardized_level\tstart_idx\tend_idx\n")
+
+
+@dataclass
+class EventRows:
+    """One submit: row_off (uint64[n_reads + 1]), rows (a structured numpy array: read, event, start, n, slot, first, mean_u, stdv_u, z_c;
+    ordered by (read, event)) and the text as bytes (None when the handle produces none)."""
+    row_off: np.ndarray
+    rows: np.ndarray
+    text: Optional[bytes]
+
+
+@dataclass
+class EventMeta:
+    """What the text says of every read beyond its rows: ref_start (int64), reverse (bool), contigs and labels (lists of str or bytes). Any
+    of them None: 0, forward, empty, the decimal index of the read in the batch."""
+    ref_start: object = None
+    reverse: object = None
+    contigs: object = None
+    labels: object = None
+
+
+def _evalign_params(sig_move_offset, rna, min_dur, max_dur, sample_rate, flags):
+    return _abi.PgEvalignParams(C.sizeof(_abi.PgEvalignParams), sig_move_offset, min_dur, max_dur, int(rna), sample_rate, flags)
+
+
+def _string_table(strings):
+    raw = [s.encode() if isinstance(s, str) else bytes(s) for s in strings]
+    off = np.zeros(len(raw) + 1, np.uint64)
+    if raw:
+        off[1:] = np.cumsum([len(s) for s in raw])
+    return np.frombuffer(b"".join(raw) or b"\0", np.uint8), off
+
+
+class EventAligner:
+    """The per-event table of batches laid out as MoveExpander leaves them against a k-mer model (pg_evalign_*). submit(batch, fit_reads)
+    takes the FitReads that ModelFit.submit returned for the same batch under the same model and parameters; only the reads it fitted have
+    rows. levels, stdvs: uint32[4^k] in 1e-3 pA; a k-mer with a level needs a stdv above 0 (PgError with PG_ERR_INPUT)."""
+
+    def __init__(self, levels, stdvs, k: int, sig_move_offset: int = 0, rna: bool = False, min_dur: int = 5, max_dur: int = 70, sample_rate: int = 0, text: bool = True,
+                 device: int = 0):
+        self._lib = _abi.load()
+        self.device, self._h = device, None
+        p = _evalign_params(sig_move_offset, rna, min_dur, max_dur, sample_rate, _abi.PG_EVALIGN_HOST_ROWS | (_abi.PG_EVALIGN_TEXT if text else 0))
+        h = C.c_void_p()
+        st = self._lib.pg_evalign_create(C.byref(p), device, C.byref(h))
+        if st != 0:
+            raise PgError(st, self._lib.pg_evalign_last_error(None).decode())
+        self._h = h
+        self.set_model(levels, stdvs, k)
+
+    def _check(self, st):
+        if st != 0:
+            raise PgError(st, self._lib.pg_evalign_last_error(self._h).decode())
+
+    def set_model(self, levels, stdvs, k: int):
+        lv, sd = np.ascontiguousarray(levels, dtype=np.uint32), np.ascontiguousarray(stdvs, dtype=np.uint32)
+        if lv.size != 4 ** k or sd.size != 4 ** k:
+            raise ValueError("levels and stdvs need 4^k entries")
+        self._check(self._lib.pg_evalign_set_model(self._h, lv.ctypes.data, sd.ctypes.data, k))
+        self.kmer_size = k
+
+    def set_stream(self, stream=None):
+        """Run on a caller-owned stream (a torch.cuda.Stream or a raw hipStream_t value); None: the handle's own."""
+        ptr = None if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
+        self._check(self._lib.pg_evalign_set_stream(self._h, ptr))
+
+    def submit(self, batch: "Batch", fit_reads, meta: Optional[EventMeta] = None) -> EventRows:
+        cb = _c_batch(batch)
+        st = np.ascontiguousarray(fit_reads.status, dtype=np.uint32)
+        a = np.ascontiguousarray(fit_reads.a, dtype=np.float64)
+        b = np.ascontiguousarray(fit_reads.b, dtype=np.float64)
+        n = batch.n_reads
+        if not (st.size == a.size == b.size == n):
+            raise ValueError("fit_reads is of another batch")
+        cm, keep = None, []
+        if meta is not None:
+            cm = _abi.PgEvalignMeta()
+            if meta.ref_start is not None:
+                rs = np.ascontiguousarray(meta.ref_start, dtype=np.int64); keep.append(rs); cm.ref_start = rs.ctypes.data
+            if meta.reverse is not None:
+                rv = np.ascontiguousarray(meta.reverse, dtype=np.uint8); keep.append(rv); cm.reverse = rv.ctypes.data
+            for name, strings in (("contig", meta.contigs), ("label", meta.labels)):
+                if strings is not None:
+                    data, off = _string_table(strings); keep += [data, off]
+                    setattr(cm, name, data.ctypes.data); setattr(cm, name + "_off", off.ctypes.data)
+            for arr, name in ((meta.ref_start, "ref_start"), (meta.reverse, "reverse"), (meta.contigs, "contigs"), (meta.labels, "labels")):
+                if arr is not None and len(arr) != n:
+                    raise ValueError(f"meta.{name} needs one entry per read")
+        out = _abi.PgEvalignOut()
+        out.struct_size = C.sizeof(_abi.PgEvalignOut)
+        self._check(self._lib.pg_evalign_submit(self._h, C.byref(cb), st.ctypes.data, a.ctypes.data, b.ctypes.data, None if cm is None else C.byref(cm), C.byref(out)))
+        n_rows = int(out.n_rows)
+        row_off = np.frombuffer((C.c_char * ((n + 1) * 8)).from_address(out.row_off), dtype=np.uint64).copy()
+        rows = (np.frombuffer((C.c_char * (n_rows * 40)).from_address(out.rows_host), dtype=_abi.EVALIGN_ROW_DTYPE).copy() if n_rows
+                else np.zeros(0, _abi.EVALIGN_ROW_DTYPE))
+        text = None
+        if out.text_bytes:
+            buf = C.create_string_buffer(int(out.text_bytes))
+            self._check(self._lib.pg_evalign_copy_text(self._h, buf, int(out.text_bytes)))
+            text = buf.raw
+        return EventRows(row_off=row_off, rows=rows, text=text)
+
+    def kernel_ms(self):
+        """HIP-event time of the three stages (count, rows, text) since the last call."""
+        ms = (C.c_double * 3)()
+        self._check(self._lib.pg_evalign_kernel_ms(self._h, ms))
+        return tuple(ms)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.pg_evalign_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def event_align(levels, stdvs, k: int, batch: "Batch", meta: Optional[EventMeta] = None, sig_move_offset: int = 0, rna: bool = False, min_dur: int = 5, max_dur: int = 70,
+                min_events: int = 20, sample_rate: int = 0, device: int = 0):
+    """One call: fit the batch, then its per-event table. Returns (FitReads, EventRows)."""
+    fit = ModelFit(levels, k, sig_move_offset=sig_move_offset, rna=rna, min_dur=min_dur, max_dur=max_dur, min_events=min_events, device=device)
+    try:
+        fr = fit.submit(batch)
+        with EventAligner(levels, stdvs, k, sig_move_offset=sig_move_offset, rna=rna, min_dur=min_dur, max_dur=max_dur, sample_rate=sample_rate, device=device) as ea:
+            return fr, ea.submit(batch, fr, meta)
+    finally:
+        fit.close()
+
+
+def eventalign_walk(levels, stdvs, k: int, seq, ops, q: int, sig, a: float, b: float, sig_move_offset: int = 0, rna: bool = False, min_dur: int = 5, max_dur: int = 70, op_t=None):
+    """The rule for one fitted read on the host (pg_evalign_walk; no GPU needed): its rows as a structured numpy array (`read` 0), or None
+    when the read has no fit's place (the ops leave the samples; gapped: the slice has not as many bases as the ops have columns). op_t:
+    the read is a gapped one (seq its reference slice; pg_evalign_walk_gapped)."""
+    lib = _abi.load()
+    p = _evalign_params(sig_move_offset, rna, min_dur, max_dur, 0, 0)
+    lv, sd = np.ascontiguousarray(levels, dtype=np.uint32), np.ascontiguousarray(stdvs, dtype=np.uint32)
+    s = np.frombuffer((seq.encode() if isinstance(seq, str) else bytes(seq)) or b"\0", np.uint8)
+    n_seq = len(seq)
+    o = np.ascontiguousarray(ops, dtype=np.uint32)
+    sg = np.ascontiguousarray(sig, dtype=np.int16)
+    rows = np.zeros(max(o.size, 1), _abi.EVALIGN_ROW_DTYPE)
+    nr = C.c_uint64()
+    if op_t is None:
+        st = lib.pg_evalign_walk(C.byref(p), lv.ctypes.data, sd.ctypes.data, k, s.ctypes.data, o.size, o.ctypes.data, q, sg.ctypes.data, sg.size, a, b, rows.ctypes.data, rows.size,
+                                 C.byref(nr))
+    else:
+        t = np.ascontiguousarray(op_t, dtype=np.uint8)
+        if t.size != o.size:
+            raise ValueError("op_t needs one code per op")
+        st = lib.pg_evalign_walk_gapped(C.byref(p), lv.ctypes.data, sd.ctypes.data, k, s.ctypes.data, n_seq, o.ctypes.data, t.ctypes.data, o.size, q, sg.ctypes.data, sg.size, a, b,
+                                        rows.ctypes.data, rows.size, C.byref(nr))
+    if st == _abi.PG_ERR_INPUT:
+        return None
+    if st != 0:
+        raise PgError(st, "pg_evalign_walk: bad argument")
+    return rows[:int(nr.value)].copy()
+
+
+def eventalign_row_text(row, contig, label, kmer, n_seq: int, ref_start: int, reverse: bool, sample_rate: int, level: int, stdv: int) -> bytes:
+    """The line of one row as the device writes it (pg_evalign_row_text; no GPU needed). kmer: the k letters of the read's seq at row.first."""
+    lib = _abi.load()
+    r = np.zeros(1, _abi.EVALIGN_ROW_DTYPE); r[0] = row
+    c, lb, km = [x.encode() if isinstance(x, str) else bytes(x) for x in (contig, label, kmer)]
+    buf = C.create_string_buffer(len(c) + len(lb) + 4096)
+    n = lib.pg_evalign_row_text(r.ctypes.data, c, len(c), lb, len(lb), km, len(km), n_seq, ref_start, int(reverse), sample_rate, level, stdv, buf, len(buf))
+    return buf.raw[:n]
+
+
 # ---- simulate: raw signal and its true alignment drawn from a k-mer model (pg_sim_*) --------------------------------------------------------
 
 SIM_STATUS_NAMES = {0: "ok", 1: "too_short", 2: "bad_base", 3: "no_level"}
