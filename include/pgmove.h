@@ -202,7 +202,11 @@ enum {
                                      queued on the chain's stream alone, exactly as a PG_FLAG_ONE_STREAM context queues it -- behind a
                                      complete front there is too little left to overlap (pg_kernel_stats: front_one_stream;
                                      PGMOVE_FRONT_TWO_STREAMS=1 keeps such batches on two streams: tests, A/B). Every other batch of the
-                                     context uses both streams as before. No result depends on the mode. */
+                                     context uses both streams as before. No result depends on the mode.
+                                     A batch whose statistics stand on the chain's stream behind the front's scan (this one, and the
+                                     same batch of a PG_FLAG_ONE_STREAM context) queues them in the launch of the rank emit kernel:
+                                     one launch, workgroups of two kinds that share nothing (pg_kernel_stats: emit_stats_fused;
+                                     PGMOVE_NO_EMIT_STATS=1, read per batch, keeps the two launches: tests, A/B). */
     PG_FLAG_SHORT_READS_OK = 1u << 4, /* a read with fewer than k matched bases simply has no events (move-table front-end,
                                         where that is well defined); default: PG_ERR_INPUT, because the PAF path of the
                                         reference has undefined behaviour there (src/gmove.cpp:891) */
@@ -543,7 +547,8 @@ pg_status   pg_job_kernel_stats(pg_job *job, uint32_t shard, pg_kernel_stat *out
  * the tiles behind them were not walked / did not, and were; PGMOVE_FRONT_TILES=n sets the front in tiles of 4096 ops, 0 = never),
  * stats_cut_batches / stats_cut_reads (those of the front_complete batches whose eager statistics were ordered behind the front's scan, and
  * the reads from their cut reads on, whose samples the statistics did not touch: PG_FLAG_LAZY_STATS), front_one_stream (settled batches
- * of a two-stream context that were queued on the chain's stream alone: PG_FLAG_OVERLAP), and the
+ * of a two-stream context that were queued on the chain's stream alone: PG_FLAG_OVERLAP), emit_stats_fused (settled batches whose
+ * statistics and rank emit were queued as one launch; 0 with PGMOVE_NO_EMIT_STATS=1 and for every batch that is not front first), and the
  * gathers for many kept events by the kernel queued: gather_form_wave, gather_form_evpair, gather_form_lanes4 / 8 / 16; k_sort_scatter:
  * passes of the LSD radix sort queued (more than 2^20 slots; the entry "sort_events" counts the whole sort once per batch) */
 pg_status pg_kernel_stats(pg_ctx *ctx, pg_kernel_stat *out, uint32_t cap, uint32_t *n_out);

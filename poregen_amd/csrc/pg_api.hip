@@ -50,7 +50,8 @@ struct BatchState {
     bool in_submit = false;      // counted by pg_submit: the base is the context's running counts
     bool all_matches = false;    // PG_BATCH_ALL_MATCHES (and not PG_FLAG_DEBUG_SPLIT_WALK)
     bool cut_in_scan = false;    // the sample_limit cut was applied inside the tile / region scan's launch: no k_slot_plan
-    bool stats_pending = false;  // PG_STATS_DEFERRED and not queued yet: pg_stats / pgi_stats_gathered / pg_collect queue them, pgi_skip_stats drops them
+    bool stats_pending = false;  // PG_STATS_DEFERRED, or PgStatsPlan::with_emit, and not queued yet: pg_stats / pgi_stats_gathered / pg_collect queue them, pgi_skip_stats drops them
+    bool emit_fused = false;     // pg_collect queued the statistics in the emit kernel's launch (k_emit_stats)
     bool rare_pending = false;   // the rare statistics launch is still to be issued, with the sample-offset scan of pg_collect ...
     PgRareArgs rare{};           // ... from these arguments
 };
@@ -101,7 +102,8 @@ struct pg_ctx {
     BatchState bt;          // the current batch
     // pg_kernel_stats' counters of settled batches: counted front first and the front did / did not complete every k-mer; statistics behind
     // the cut (PgStatsPlan::behind_cut) whose front completed, and the reads from their cut reads on; one-stream batches of a two-stream context
-    uint64_t front_complete = 0, front_missed = 0, stats_cut_batches = 0, stats_cut_reads = 0, front_one_stream = 0;
+    // ...; batches whose statistics and rank emit went out as one launch (PgStatsPlan::with_emit)
+    uint64_t front_complete = 0, front_missed = 0, stats_cut_batches = 0, stats_cut_reads = 0, front_one_stream = 0, emit_stats_fused = 0;
     PgEvent ev_front; // recorded behind the front's scan
     bool prev_one_stream = false; // crosses batches: the batch in FRONT of the current one was a one-stream batch (the statistics stream then waits for the chain's stream before it touches what both share)
     uint32_t gen_reads = 0; // generic reads of the last settled batch
@@ -569,11 +571,14 @@ static pg_status ensure_stats_buffers(pg_ctx *c) {
 }
 
 static pg_status fill_long(pg_ctx *c, PgLongState &LS, bool ensure);
+// what pg_collect hands to pg_launch_rank_direct_emit: launch_stats queues it with the statistics in one launch (PgStatsPlan::with_emit)
+struct EmitArgs { const uint32_t *ev_slot; uint64_t n; uint32_t n_slots; const PgSortBufs *S; const uint64_t *keep, *ev_off, *totals; const PgWalkParams *W; const PgWalkOut *O; const PgKeptOut *K; };
 // statistics of every read of the current batch: both LDS-histogram variants are queued back to back, each
 // handles the reads whose in-range code interval fits it (no host decision, no sync)
 // the batch's plan says where: on which stream, whether k_batch_init has written the records and reset the flags in front of them (on the
 // same stream, or on the stream this one was forked from, behind that kernel), and whether the rare workers ride in the next scan
-static pg_status launch_stats(pg_ctx *c) {
+// emit (pg_collect, a with_emit batch): k_read_stats' workgroups ride in the emit kernel's launch
+static pg_status launch_stats(pg_ctx *c, const EmitArgs *emit = nullptr) {
     const PgStatsPlan &P = c->bt.plan;
     hipStream_t st = pg_stats_on_second_stream(P.place) ? c->st2.h : c->st;
     const uint8_t *needed = P.place == PG_STATS_LAZY ? c->read_needed.as<uint8_t>() : nullptr; // only the reads that own a kept event
@@ -602,7 +607,14 @@ static pg_status launch_stats(pg_ctx *c) {
         const char *ov = getenv("PGMOVE_STATS_GROUP_FROM");
         group_from = ov ? (uint32_t)std::min<unsigned long long>(strtoull(ov, nullptr, 10), 0xffffffffull) : pg_stats_group_from(c->B.n_reads, c->B.n_ops, c->bt.front_tiles);
     }
-    prof_begin(c, "k_read_stats", st);
+    prof_begin(c, emit ? "k_emit_stats" : "k_read_stats", st);
+    if (emit) {
+        PG_HIP_TRY(c, pg_launch_emit_stats(st, emit->ev_slot, emit->n, emit->n_slots, *emit->S, emit->keep, emit->ev_off, emit->totals, c->B, *emit->W, *emit->O, *emit->K,
+                             c->read_plan[sl].p, c->med[sl].as<double>(), c->mad[sl].as<double>(), c->stat_status[sl].as<int32_t>(), flags, win,
+                             c->wide_list[sl].as<uint32_t>(), flags + 1, oor, range_only, c->gcal[sl].as<double>(), LS,
+                             cut ? c->errflag.as<unsigned long long>() + 5 : nullptr, c->batch_id, group_from));
+        c->bt.emit_fused = true;
+    } else
     PG_HIP_TRY(c, pg_launch_read_stats(st, c->B, c->read_plan[sl].p, c->med[sl].as<double>(), c->mad[sl].as<double>(),
                          c->stat_status[sl].as<int32_t>(), flags, win, c->wide_list[sl].as<uint32_t>(), flags + 1, oor, range_only,
                          c->gcal[sl].as<double>(), LS, cut ? c->errflag.as<unsigned long long>() + 5 : nullptr, c->batch_id, group_from));
@@ -840,7 +852,9 @@ static pg_status count_impl(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, 
     // statistics wait for the front's scan anyway, and behind a complete front little is left to overlap: the two event hand-overs, the
     // record pass's own launch and the empty rare launch cost more than the second stream hides.
     // PGMOVE_FRONT_TWO_STREAMS=1 (tests, A/B; read per batch) keeps it on two streams.
-    const PgStatsPlan P = c->bt.plan = pg_stats_plan(c->prm.flags, c->prm.scaling, FR.tiles, n, getenv("PGMOVE_FRONT_TWO_STREAMS") != nullptr);
+    // A behind_cut batch on the chain's stream leaves its statistics to pg_collect, which queues them in the emit kernel's launch
+    // (PgStatsPlan::with_emit; k_emit_stats); PGMOVE_NO_EMIT_STATS=1 (tests, A/B; read per batch) keeps the two launches.
+    const PgStatsPlan P = c->bt.plan = pg_stats_plan(c->prm.flags, c->prm.scaling, FR.tiles, n, getenv("PGMOVE_FRONT_TWO_STREAMS") != nullptr, getenv("PGMOVE_NO_EMIT_STATS") != nullptr);
     // (a two-stream batch that was counted and never collected: nothing on the chain's stream has waited for its statistics yet, and this
     // batch's k_batch_init writes the long-read table they read)
     if (P.one_stream_batch && c->stats_in_flight) PG_HIP_TRY(c, hipStreamWaitEvent(c->st, c->ev_join[c->slot ^ 1], 0));
@@ -968,8 +982,8 @@ static pg_status count_impl(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, 
     // Statistics only need the signal: in eager mode they run on the second stream, overlapping the
     // latency-bound walk/rank chain above; pg_collect joins the two streams before the gather.
     c->stats_in_flight = false;
-    c->bt.stats_pending = P.place == PG_STATS_DEFERRED;
-    if (P.place == PG_STATS_SECOND_STREAM || P.place == PG_STATS_CHAIN || P.place == PG_STATS_TAIL_FORK) {
+    c->bt.stats_pending = P.place == PG_STATS_DEFERRED || P.with_emit;
+    if (!P.with_emit && (P.place == PG_STATS_SECOND_STREAM || P.place == PG_STATS_CHAIN || P.place == PG_STATS_TAIL_FORK)) {
         // PG_FLAG_OVERLAP_TAIL: the statistics fork off HERE, behind the counting kernels, onto the second stream; the sample_limit
         // cut, the emit kernel and the offset scan of pg_collect -- small launches that keep a fraction of the chip busy -- run
         // next to the streaming kernel, and pg_collect joins the two streams in front of the gather (the only consumer of med/MAD).
@@ -1000,7 +1014,8 @@ static pg_status collect_impl(pg_ctx *c, const uint64_t *base, int32_t base_loca
 pg_status pg_count(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t counts_location) { return count_impl(c, b, counts_out, counts_location, false); }
 
 // PG_STATS_DEFERRED: the statistics pg_count left out, queued now on the chain's stream -- by whoever comes first of pg_stats,
-// pgi_stats_gathered and pg_collect (the device is set)
+// pgi_stats_gathered and pg_collect (the device is set). A with_emit batch that reaches one of the first two, or a pg_collect that does
+// not queue k_rank_emit, gets the plain k_read_stats here as well.
 static pg_status launch_pending_stats(pg_ctx *c) {
     if (!c->bt.stats_pending) return PG_OK;
     c->bt.stats_pending = false;
@@ -1046,10 +1061,12 @@ static pg_status collect_impl(pg_ctx *c, const uint64_t *base, int32_t base_loca
     if (!c->have_count) return pg_fail(c, PG_ERR_STATE, "pg_collect without a preceding pg_count");
     PG_HIP_TRY(c, hipSetDevice(c->device));
     double tmark_ = timing_on() ? wall_now() : 0.0;
-    { pg_status s2 = launch_pending_stats(c); if (s2 != PG_OK) return s2; } // PG_FLAG_DEFER_STATS and the caller did not place them with pg_stats
     const uint32_t ns = c->prm.n_slots;
     const uint64_t N = c->B.n_ops;
     const bool direct = ns <= PG_DIRECT_MAX_SLOTS;
+    // with_emit: the pending statistics go out with k_rank_emit below, in one launch (a front implies direct ranking, not dense: front_tiles_for)
+    const bool emit_stats = c->bt.stats_pending && c->bt.plan.with_emit && direct && !dense_direct(c, N);
+    if (!emit_stats) { pg_status s2 = launch_pending_stats(c); if (s2 != PG_OK) return s2; } // PG_FLAG_DEFER_STATS and the caller did not place them with pg_stats
     const uint64_t *d_base = c->running.as<uint64_t>();
     PgGathered G{}; // multi-GPU job: k_slot_plan sums the lower ranks' rows itself (and leaves the job's totals / freq.txt column)
     if (all_counts) {
@@ -1102,10 +1119,16 @@ static pg_status collect_impl(pg_ctx *c, const uint64_t *base, int32_t base_loca
     if (direct) {
         PgSortBufs S{};
         fill_sort(c, S, 0);
+        if (emit_stats) {
+            const EmitArgs EA{O.ev_slot, N, ns, &S, c->keep.as<uint64_t>(), c->ev_off.as<uint64_t>(), totals, &W, &O, &K};
+            c->bt.stats_pending = false;
+            pg_status s2 = launch_stats(c, &EA); if (s2 != PG_OK) return s2;
+        } else {
         prof_begin(c, "k_rank_emit", c->st);
         if (dense_direct(c, N)) PG_HIP_TRY(c, pg_launch_rank_emit2(c->st, O.ev_slot, N, ns, S.hist, c->keep.as<uint64_t>(), c->ev_off.as<uint64_t>(), totals, c->B, W, O, K, c->part_Bp.as<uint32_t>()));
         else PG_HIP_TRY(c, pg_launch_rank_direct_emit(c->st, O.ev_slot, N, ns, S, c->keep.as<uint64_t>(), c->ev_off.as<uint64_t>(), totals, c->B, W, O, K));
         prof_end(c, c->st);
+        }
     } else if (c->part_mode) {
         PgPartBufs P{};
         fill_part(c, P, N ? N : 1);
@@ -1218,6 +1241,7 @@ static pg_status settle_batch(pg_ctx *c) {
     const PgSettlePack pk = *c->settle_host.p;
     if (c->bt.front_tiles) { if (pk.front[0]) c->front_complete++; else c->front_missed++; } // (a batch that fails was counted front first all the same)
     if (c->bt.plan.one_stream_batch) c->front_one_stream++; // ... and was queued on the chain's stream alone in a two-stream context, complete or not
+    if (c->bt.emit_fused) c->emit_stats_fused++; // ... and its statistics rode in the emit kernel's launch
     if (c->bt.plan.behind_cut && pk.front[0]) { c->stats_cut_batches++; c->stats_cut_reads += c->B.n_reads - std::min(pk.front[1], c->B.n_reads); } // its statistics left out the reads from pk.front[1] on
     pg_status s = check_read_errors(c, pk);
     if (s != PG_OK) { c->have_batch_result = false; c->downloaded = true; return s; }
@@ -1727,6 +1751,10 @@ pg_status pg_kernel_stats(pg_ctx *c, pg_kernel_stat *out, uint32_t cap, uint32_t
         if (out && n < cap) { out[n].name = "stats_cut_reads"; out[n].launches = c->stats_cut_reads; out[n].total_ms = 0.0; } // reads from the cut read on, all those batches together
         n++;
     }
+    if (c->emit_stats_fused) { // settled batches whose statistics and rank emit were one launch (k_emit_stats)
+        if (out && n < cap) { out[n].name = "emit_stats_fused"; out[n].launches = c->emit_stats_fused; out[n].total_ms = 0.0; }
+        n++;
+    }
     if (c->front_one_stream) { // settled batches of a two-stream context that were queued on the chain's stream alone (pg_count: stream mode per batch)
         if (out && n < cap) { out[n].name = "front_one_stream"; out[n].launches = c->front_one_stream; out[n].total_ms = 0.0; }
         n++;
@@ -1754,7 +1782,7 @@ pg_status pg_kernel_stats_reset(pg_ctx *c) {
     PG_HIP_TRY(c, hipStreamSynchronize(c->st));
     if (c->st2) PG_HIP_TRY(c, hipStreamSynchronize(c->st2));
     prof_drain(c);
-    c->prof_acc.clear(); c->prof_names.clear(); c->stats_cancelled = 0; c->long_reads_split = 0; c->long_helpers_short = 0; c->front_complete = 0; c->front_missed = 0; c->stats_cut_batches = 0; c->stats_cut_reads = 0; c->front_one_stream = 0;
+    c->prof_acc.clear(); c->prof_names.clear(); c->stats_cancelled = 0; c->long_reads_split = 0; c->long_helpers_short = 0; c->front_complete = 0; c->front_missed = 0; c->stats_cut_batches = 0; c->stats_cut_reads = 0; c->front_one_stream = 0; c->emit_stats_fused = 0;
     for (uint64_t &f : c->gather_forms) f = 0;
     c->sort_scatters = 0;
     return PG_OK;

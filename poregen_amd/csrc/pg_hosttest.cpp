@@ -221,6 +221,10 @@ extern "C" void pgt_stats_plan(uint32_t ctx_flags, int32_t scaling, uint32_t fro
     const PgStatsPlan p = pg_stats_plan(ctx_flags, scaling, front_tiles, n_reads, front_two_streams != 0);
     out6[0] = p.place; out6[1] = p.behind_cut; out6[2] = p.one_stream_batch; out6[3] = p.records_in_init; out6[4] = p.flags_in_init; out6[5] = p.rare_with_scan;
 }
+// PgStatsPlan::with_emit alone, with the switch (PGMOVE_NO_EMIT_STATS) that pgt_stats_plan's signature has no room for
+extern "C" int pgt_stats_plan_with_emit(uint32_t ctx_flags, int32_t scaling, uint32_t front_tiles, uint32_t n_reads, int front_two_streams, int no_emit_stats) {
+    return pg_stats_plan(ctx_flags, scaling, front_tiles, n_reads, front_two_streams != 0, no_emit_stats != 0).with_emit ? 1 : 0;
+}
 extern "C" int pgt_stats_fork_waits(int batch_is_host, int user_stream, int batch_resident, int prev_one_stream) {
     return pg_stats_fork_waits(batch_is_host != 0, user_stream != 0, batch_resident != 0, prev_one_stream != 0) ? 1 : 0;
 }

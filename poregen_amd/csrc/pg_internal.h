@@ -415,6 +415,13 @@ hipError_t pg_launch_read_stats(hipStream_t st, const PgDevBatch &B, const void 
                                 // group_from (cut launches only): the reads from this index on are handled by group workgroups, one wave for
                                 // PG_STATS_GROUP consecutive reads (pg_stats_group_from; any value is correct, it decides speed only)
                                 const unsigned long long *cut_word = nullptr, uint32_t batch_id = 0, uint32_t group_from = 0xffffffffu);
+// pg_launch_rank_direct_emit and pg_launch_read_stats in ONE launch (k_emit_stats): workgroups of either kind, told apart by their index,
+// none of which reads what the other kind writes. For a batch whose statistics stand behind the front's scan on the chain's stream
+// (PgStatsPlan::with_emit); the arguments are those of the two launchers.
+hipError_t pg_launch_emit_stats(hipStream_t st, const uint32_t *ev_slot, uint64_t n, uint32_t n_slots, const PgSortBufs &S, const uint64_t *keep, const uint64_t *ev_off,
+                                const uint64_t *totals, const PgDevBatch &B, const PgWalkParams &W, const PgWalkOut &O, const PgKeptOut &K,
+                                const void *plan_buf, double *med, double *mad, int32_t *status, int32_t *err, int win, uint32_t *wide_list, int32_t *wide_count, uint8_t *oor,
+                                int range_only, double *gcal, const PgLongState &LS, const unsigned long long *cut_word, uint32_t batch_id, uint32_t group_from);
 uint32_t pg_stats_group_from(uint32_t n_reads, uint64_t n_ops, uint32_t front_tiles);
 // pg_finish over several batches: a batch's kept samples stay on the device until then; (k-mer, batch) segments are copied into the
 // job's k-mer-major order by one launch and leave the device once

@@ -11,6 +11,7 @@
 //                   LSD radix sort (k_rank_count / k_sort_* / k_kept_meta) beyond
 //   k_slot_plan (+ k_tile_max) or k_slot_keep, k_scan_*   the cut as a launch of its own (base from other ranks), output offsets
 //   k_read_stats (+ the rare workers riding in k_scan_chained)   pA conversion, zero-fill, exact median and MAD (lines 754-771)
+//   k_emit_stats      k_rank_emit and k_read_stats of a front-first batch as one launch: workgroups of two kinds that share nothing
 //   k_gather        window copy + normalisation of the kept events (lines 773-775, 928-944)
 // All of this is HBM/LDS-bound integer and FP64 work: there is no contraction here, so no MFMA.
 #include "pg_dev.h"
@@ -1333,13 +1334,14 @@ __device__ __forceinline__ void write_kept(const PgDevBatch &B, const PgWalkPara
 #define PG_EMIT_WAVES 16
 #define PG_EMIT_GRID 512
 #define PG_EMIT_ROWS (PG_SORT_TILE / (PG_EMIT_WAVES * WAVE))
-__global__ __launch_bounds__(PG_EMIT_WAVES * WAVE) void k_rank_emit(const uint32_t *__restrict__ keys, uint32_t n, int nbits, uint32_t n_slots, uint32_t n_tiles,
-                                                   const uint32_t *__restrict__ hist,
-                                                   const uint64_t *__restrict__ keep, const uint64_t *__restrict__ ev_off,
-                                                   const uint64_t *__restrict__ totals, PgDevBatch B, PgWalkParams W, PgWalkOut O,
-                                                   PgKeptOut K) {
-    __shared__ uint32_t wbase[PG_EMIT_WAVES][PG_RANK_MAX_DIGITS];
-    __shared__ uint32_t s_keep[PG_RANK_MAX_DIGITS], s_off[PG_RANK_MAX_DIGITS];
+// One workgroup's share of the emit grid: `bid` of `grid` workgroups (k_rank_emit: blockIdx.x of gridDim.x; k_emit_stats: the emit
+// workgroups' own numbering), the three LDS arrays the caller's. Every thread of the workgroup calls it: the barriers are the workgroup's.
+__device__ __forceinline__ void rank_emit_block(uint32_t (*wbase)[PG_RANK_MAX_DIGITS], uint32_t *s_keep, uint32_t *s_off, const uint32_t bid, const uint32_t grid,
+                                                const uint32_t *__restrict__ keys, uint32_t n, int nbits, uint32_t n_slots, uint32_t n_tiles,
+                                                const uint32_t *__restrict__ hist,
+                                                const uint64_t *__restrict__ keep, const uint64_t *__restrict__ ev_off,
+                                                const uint64_t *__restrict__ totals, const PgDevBatch B, const PgWalkParams W, const PgWalkOut O,
+                                                const PgKeptOut K) {
     static_assert(PG_RANK_MAX_DIGITS <= PG_EMIT_WAVES * WAVE, "one digit per thread");
     const uint32_t tid = threadIdx.x, w = tid >> 6;
     const int lane = lane_id();
@@ -1351,8 +1353,8 @@ __global__ __launch_bounds__(PG_EMIT_WAVES * WAVE) void k_rank_emit(const uint32
     // every started workgroup first gathers its 1024-line column of the [slot][tile] table.
     PG_PROBE_BEGIN(2);
     const int64_t last_tile = (int64_t)totals[3];
-    for (uint32_t tile = blockIdx.x; tile < n_tiles && (int64_t)tile <= last_tile; tile += gridDim.x) {
-    if (tile != blockIdx.x) __syncthreads(); // the previous tile's ranks are read out of wbase until its last wave is through
+    for (uint32_t tile = bid; tile < n_tiles && (int64_t)tile <= last_tile; tile += grid) {
+    if (tile != bid) __syncthreads(); // the previous tile's ranks are read out of wbase until its last wave is through
     PG_MARK(2, 0); // the last useful tile is known
     // phase 0: everything the ordered loop needs from global memory, all rows in flight at once. The slots of the tile's events
     // are requested in front of the "any room left?" test: a tile up to the last useful one nearly always passes it, and the
@@ -1454,8 +1456,18 @@ __global__ __launch_bounds__(PG_EMIT_WAVES * WAVE) void k_rank_emit(const uint32
         if (K.read_needed) K.read_needed[rd[row]] = 1;
     }
     PG_MARK(2, 5); // stores
-    if (tile == blockIdx.x) PG_PROBE_END(2, tile * PG_EMIT_WAVES + w);
+    if (tile == bid) PG_PROBE_END(2, tile * PG_EMIT_WAVES + w);
     } // tiles of this workgroup
+}
+
+__global__ __launch_bounds__(PG_EMIT_WAVES * WAVE) void k_rank_emit(const uint32_t *__restrict__ keys, uint32_t n, int nbits, uint32_t n_slots, uint32_t n_tiles,
+                                                   const uint32_t *__restrict__ hist,
+                                                   const uint64_t *__restrict__ keep, const uint64_t *__restrict__ ev_off,
+                                                   const uint64_t *__restrict__ totals, PgDevBatch B, PgWalkParams W, PgWalkOut O,
+                                                   PgKeptOut K) {
+    __shared__ uint32_t wbase[PG_EMIT_WAVES][PG_RANK_MAX_DIGITS];
+    __shared__ uint32_t s_keep[PG_RANK_MAX_DIGITS], s_off[PG_RANK_MAX_DIGITS];
+    rank_emit_block(wbase, s_keep, s_off, blockIdx.x, gridDim.x, keys, n, nbits, n_slots, n_tiles, hist, keep, ev_off, totals, B, W, O, K);
 }
 
 // =====================================================================================================
@@ -2478,16 +2490,14 @@ __device__ __forceinline__ void stats_read_body(uint32_t *hist, const PgDevBatch
 // a cut word: behind a complete front nearly all of those reads are skipped, and a lane each stores their NaNs; the others are computed by the
 // wave one after the other, in index order); the workgroups behind them are the HELPERS of long reads. Every other launch has r1 = n_reads
 // and no group. Both kinds of workgroup are correct for any read: r1 only decides speed (pg_stats_group_from).
-__global__ __launch_bounds__(64 * PG_STATS_WPB) __attribute__((amdgpu_waves_per_eu(PG_STATS_WAVES_PER_EU, PG_STATS_WAVES_PER_EU))) void k_read_stats(PgDevBatch B, const PgStatRec *__restrict__ rec, double *__restrict__ med,
-                                                   double *__restrict__ mad, int32_t *__restrict__ status, int32_t *__restrict__ err,
-                                                   int win, uint8_t *__restrict__ oor, int range_only, uint32_t *__restrict__ wide_list,
-                                                   int32_t *__restrict__ wide_count, uint32_t keep_cached, double *__restrict__ gcal, PgLongState LS,
-                                                   const unsigned long long *__restrict__ cut_word, uint32_t batch_id, uint32_t r1, uint32_t n_groups) {
-    __shared__ __attribute__((aligned(16))) uint32_t hist_all[PG_STATS_WPB][StatsGeom<1024>::LDS_WORDS];
-    static_assert(StatsGeom<1024>::LDS_WORDS + 1 <= PG_LONG_WORDS, "a long read's histogram in global memory");
-    static_assert(PG_STATS_WPB == 1, "the group workgroups and the helpers of long reads are found from blockIdx.x: [0, r1) reads, [r1, r1 + n_groups) groups, then helper blockIdx.x - r1 - n_groups");
-    uint32_t *hist = hist_all[0];
-    const uint32_t b = blockIdx.x;
+// One wave's share of that grid: `b` is the wave's (virtual) workgroup index, wave-uniform (blockIdx.x, or made so with readfirstlane: the
+// record and everything derived from it stay in scalar registers), `hist` the wave's own LDS histogram. No workgroup barrier anywhere in
+// here: k_read_stats is one wave per workgroup, and the sixteen waves of a statistics workgroup of k_emit_stats take an index each.
+__device__ __forceinline__ void read_stats_wave(const uint32_t b, uint32_t *hist, const PgDevBatch &B, const PgStatRec *__restrict__ rec, double *__restrict__ med,
+                                                double *__restrict__ mad, int32_t *__restrict__ status, int32_t *__restrict__ err,
+                                                int win, uint8_t *__restrict__ oor, int range_only, uint32_t *__restrict__ wide_list,
+                                                int32_t *__restrict__ wide_count, uint32_t keep_cached, double *__restrict__ gcal, const PgLongState &LS,
+                                                const unsigned long long *__restrict__ cut_word, uint32_t batch_id, uint32_t r1, uint32_t n_groups) {
     const int lane = lane_id();
     uint32_t r = b; // uniform: the record and everything derived from it stay in scalar registers
     uint32_t slice = 0, base = 0;
@@ -2542,6 +2552,73 @@ __global__ __launch_bounds__(64 * PG_STATS_WPB) __attribute__((amdgpu_waves_per_
         __builtin_amdgcn_wave_barrier();
         if (PG_STATS_SETPRIO) __builtin_amdgcn_s_setprio(0); // back to streaming
     }
+}
+
+__global__ __launch_bounds__(64 * PG_STATS_WPB) __attribute__((amdgpu_waves_per_eu(PG_STATS_WAVES_PER_EU, PG_STATS_WAVES_PER_EU))) void k_read_stats(PgDevBatch B, const PgStatRec *__restrict__ rec, double *__restrict__ med,
+                                                   double *__restrict__ mad, int32_t *__restrict__ status, int32_t *__restrict__ err,
+                                                   int win, uint8_t *__restrict__ oor, int range_only, uint32_t *__restrict__ wide_list,
+                                                   int32_t *__restrict__ wide_count, uint32_t keep_cached, double *__restrict__ gcal, PgLongState LS,
+                                                   const unsigned long long *__restrict__ cut_word, uint32_t batch_id, uint32_t r1, uint32_t n_groups) {
+    __shared__ __attribute__((aligned(16))) uint32_t hist_all[PG_STATS_WPB][StatsGeom<1024>::LDS_WORDS];
+    static_assert(StatsGeom<1024>::LDS_WORDS + 1 <= PG_LONG_WORDS, "a long read's histogram in global memory");
+    static_assert(PG_STATS_WPB == 1, "the group workgroups and the helpers of long reads are found from blockIdx.x: [0, r1) reads, [r1, r1 + n_groups) groups, then helper blockIdx.x - r1 - n_groups");
+    read_stats_wave(blockIdx.x, hist_all[0], B, rec, med, mad, status, err, win, oor, range_only, wide_list, wide_count, keep_cached, gcal, LS, cut_word, batch_id, r1, n_groups);
+}
+
+// k_rank_emit and k_read_stats of a cut batch in ONE launch (pg_api.hip: PgStatsPlan::with_emit). Behind the front's scan the two kernels
+// are independent strands of the step, and on one stream they ran one after the other; here a workgroup is either an EMIT workgroup
+// (rank_emit_block, numbered [0, E)) or a STATISTICS workgroup, whose sixteen waves take one virtual k_read_stats workgroup each
+// (read_stats_wave, indices [0, n_wgs); waves past the end leave). The kind is a function of blockIdx.x alone, so the branch is uniform
+// over the workgroup: an emit workgroup never runs statistics code behind a barrier, a statistics wave never reaches a __syncthreads.
+//   emit reads        keys, the [slot][tile] table, keep / ev_off / totals, PgWalkOut (tile_read, read records, windows), the ops
+//   emit writes       PgKeptRec records, O.err / O.status (report_error); K.read_needed is null here (lazy statistics never come here)
+//   statistics read   the statistics records, the cut word, the signal, the long-read table and counters
+//   statistics write  med / mad / gcal / status / stat_err, the wide list, the long reads' histograms and counters (agent-scope atomics
+//                     among statistics waves, as in k_read_stats)
+// No workgroup of one kind waits for, polls or reads anything a workgroup of the other kind writes: there is no atomic, flag, fence or spin
+// between the kinds, and the launch is correct under any dispatch order. What the next launch on the stream reads of either (the rare
+// workers in k_scan_chained<true>: the wide list; the gather: records and statistics) is ordered by the kernel boundary.
+// One raw LDS buffer, carved by kind: [16][1024] wave bases + keep + offsets, or sixteen histograms of StatsGeom<1024>::LDS_WORDS words.
+// Speed only, by measurement: E, the order of the kinds in the grid, the mapping of virtual indices to waves.
+#ifndef PG_FUSED_EMIT_GRID
+#define PG_FUSED_EMIT_GRID 256 // emit workgroups at most: one 1024-thread workgroup per CU, so 256 serve a miss as 512 do
+#endif
+#ifndef PG_FUSED_ORDER
+#define PG_FUSED_ORDER 0 // 0: emit workgroups first (the longer strand starts first), 1: statistics first, 2: alternating while both last
+#endif
+#ifndef PG_FUSED_STRIDED
+#define PG_FUSED_STRIDED 0 // 0: wave w of statistics workgroup s takes index 16 s + w; 1: w * n_sb + s (the computing reads spread over all of them)
+#endif
+struct PgStatsArgs { // k_read_stats' arguments behind the batch
+    const PgStatRec *rec; double *med, *mad; int32_t *status, *err; int win; uint8_t *oor; int range_only; uint32_t *wide_list; int32_t *wide_count;
+    uint32_t keep_cached; double *gcal; PgLongState LS; const unsigned long long *cut_word; uint32_t batch_id, r1, n_groups;
+    uint32_t n_wgs; // r1 + n_groups + helpers: k_read_stats' grid
+};
+__global__ __launch_bounds__(PG_EMIT_WAVES * WAVE) void k_emit_stats(uint32_t E, uint32_t n_sb, const uint32_t *__restrict__ keys, uint32_t n, int nbits, uint32_t n_slots, uint32_t n_tiles,
+                                                    const uint32_t *__restrict__ hist, const uint64_t *__restrict__ keep, const uint64_t *__restrict__ ev_off,
+                                                    const uint64_t *__restrict__ totals, PgDevBatch B, PgWalkParams W, PgWalkOut O, PgKeptOut K, PgStatsArgs A) {
+    constexpr uint32_t EMIT_WORDS = (PG_EMIT_WAVES + 2u) * PG_RANK_MAX_DIGITS, STAT_WORDS = PG_EMIT_WAVES * StatsGeom<1024>::LDS_WORDS;
+    static_assert(StatsGeom<1024>::LDS_WORDS % 4 == 0, "every wave's histogram 16-byte aligned");
+    __shared__ __attribute__((aligned(16))) uint32_t lds[EMIT_WORDS > STAT_WORDS ? EMIT_WORDS : STAT_WORDS];
+    const uint32_t bx = blockIdx.x; // gridDim.x = E + n_sb
+    bool emit; uint32_t idx;
+    if (PG_FUSED_ORDER == 0) { emit = bx < E; idx = emit ? bx : bx - E; }
+    else if (PG_FUSED_ORDER == 1) { emit = bx >= n_sb; idx = emit ? bx - n_sb : bx; }
+    else {
+        const uint32_t m = E < n_sb ? E : n_sb;
+        if (bx < 2u * m) { emit = !(bx & 1u); idx = bx >> 1; }
+        else { emit = E > n_sb; idx = bx - m; }
+    }
+    if (emit) {
+        rank_emit_block(reinterpret_cast<uint32_t (*)[PG_RANK_MAX_DIGITS]>(lds), lds + PG_EMIT_WAVES * PG_RANK_MAX_DIGITS, lds + (PG_EMIT_WAVES + 1u) * PG_RANK_MAX_DIGITS,
+                        idx, E, keys, n, nbits, n_slots, n_tiles, hist, keep, ev_off, totals, B, W, O, K);
+        return;
+    }
+    const uint32_t w = threadIdx.x >> 6;
+    const uint32_t v = (uint32_t)__builtin_amdgcn_readfirstlane((int)(PG_FUSED_STRIDED ? w * n_sb + idx : idx * PG_EMIT_WAVES + w));
+    if (v >= A.n_wgs) return;
+    read_stats_wave(v, lds + w * StatsGeom<1024>::LDS_WORDS, B, A.rec, A.med, A.mad, A.status, A.err, A.win, A.oor, A.range_only, A.wide_list, A.wide_count, A.keep_cached, A.gcal,
+                    A.LS, A.cut_word, A.batch_id, A.r1, A.n_groups);
 }
 
 // The rare reads: in-range interval wider than 1024 codes. ONE launch covers both lists (usually both are empty, and an
@@ -2985,6 +3062,25 @@ hipError_t pg_launch_read_stats(hipStream_t st, const PgDevBatch &B, const void 
     const uint32_t n_groups = (B.n_reads - r1 + PG_STATS_GROUP - 1) / PG_STATS_GROUP;
     PG_LAUNCH(k_read_stats, dim3(r1 + n_groups + (LS.tab ? LS.cap : 0u)), dim3(64 * PG_STATS_WPB), 0, st, B, plan, med, mad, status, err, win, oor, range_only, wide_list, wide_count,
               B.n_reads / PG_STATS_CACHED_FRACTION, gcal, LS, cut_word, batch_id, r1, n_groups);
+    return hipSuccess;
+}
+// pg_launch_rank_direct_emit and pg_launch_read_stats (with a cut word) as one launch: k_emit_stats
+hipError_t pg_launch_emit_stats(hipStream_t st, const uint32_t *ev_slot, uint64_t n, uint32_t n_slots, const PgSortBufs &S, const uint64_t *keep, const uint64_t *ev_off,
+                                const uint64_t *totals, const PgDevBatch &B, const PgWalkParams &W, const PgWalkOut &O, const PgKeptOut &K,
+                                const void *plan_buf, double *med, double *mad, int32_t *status, int32_t *err, int win, uint32_t *wide_list, int32_t *wide_count, uint8_t *oor,
+                                int range_only, double *gcal, const PgLongState &LS, const unsigned long long *cut_word, uint32_t batch_id, uint32_t group_from) {
+    int nbits = 1; while ((1u << nbits) < n_slots) ++nbits;
+    const uint32_t n_tiles = pg_tiles(n, true);
+    const uint32_t E = n_tiles < PG_FUSED_EMIT_GRID ? n_tiles : PG_FUSED_EMIT_GRID;
+    PgStatsArgs A{};
+    A.rec = reinterpret_cast<const PgStatRec *>(plan_buf); A.med = med; A.mad = mad; A.status = status; A.err = err; A.win = win; A.oor = oor; A.range_only = range_only;
+    A.wide_list = wide_list; A.wide_count = wide_count; A.keep_cached = B.n_reads / PG_STATS_CACHED_FRACTION; A.gcal = gcal; A.LS = LS; A.cut_word = cut_word; A.batch_id = batch_id;
+    A.r1 = cut_word ? std::min(group_from, B.n_reads) : B.n_reads; // as pg_launch_read_stats
+    A.n_groups = (B.n_reads - A.r1 + PG_STATS_GROUP - 1) / PG_STATS_GROUP;
+    A.n_wgs = B.n_reads ? A.r1 + A.n_groups + (LS.tab ? LS.cap : 0u) : 0u;
+    const uint32_t n_sb = (A.n_wgs + PG_EMIT_WAVES - 1) / PG_EMIT_WAVES;
+    if (E + n_sb == 0) return hipSuccess;
+    PG_LAUNCH(k_emit_stats, dim3(E + n_sb), dim3(PG_EMIT_WAVES * WAVE), 0, st, E, n_sb, ev_slot, (uint32_t)n, nbits, n_slots, n_tiles, (const uint32_t *)S.hist, keep, ev_off, totals, B, W, O, K, A);
     return hipSuccess;
 }
 // pg_api.hip: the first read of a cut launch that is handled by a group workgroup -- the reads that hold the front's ops if the reads are

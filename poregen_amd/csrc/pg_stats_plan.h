@@ -13,6 +13,8 @@
 //   TAIL_FORK      PG_FLAG_OVERLAP_TAIL: forked onto the second stream behind the counting kernels, beside pg_collect's small launches
 //   DEFERRED       PG_FLAG_DEFER_STATS: left to pg_stats / pgi_stats_gathered / pg_collect, on the chain's stream
 //   LAZY           PG_FLAG_LAZY_STATS: in pg_collect behind the emit kernel, for the reads that own a kept event only
+// Beside the place: a CHAIN batch behind the cut (with_emit) leaves its statistics to pg_collect, which queues them in the launch of the rank
+// emit kernel (k_emit_stats); PGMOVE_NO_EMIT_STATS keeps the two launches.
 #pragma once
 #include "../../include/pgmove.h"
 #include <cstdint>
@@ -26,13 +28,15 @@ struct PgStatsPlan {
     bool records_in_init;   // k_batch_init writes the statistics records: no k_read_plan
     bool flags_in_init;     // k_batch_init resets the slot's statistics flags, in front of the statistics in stream (or fork) order
     bool rare_with_scan;    // the rare workers ride in the launch of pg_collect's sample-offset scan, the next one on the chain's stream
+    bool with_emit;         // CHAIN and behind_cut: pg_count leaves the statistics pending, and pg_collect queues them in the emit kernel's launch (k_emit_stats)
 };
 
 static inline bool pg_stats_on_second_stream(PgStatsPlace p) { return p == PG_STATS_SECOND_STREAM || p == PG_STATS_TAIL_FORK; }
 
 // ctx_flags: the context's effective flags (pg_create has defaulted PG_FLAG_OVERLAP); front_tiles: the batch's front (0: counted in one
-// pass); front_two_streams: PGMOVE_FRONT_TWO_STREAMS is set (tests, A/B: a front-first batch keeps the second stream)
-static inline PgStatsPlan pg_stats_plan(uint32_t ctx_flags, int32_t scaling, uint32_t front_tiles, uint32_t n_reads, bool front_two_streams) {
+// pass); front_two_streams: PGMOVE_FRONT_TWO_STREAMS is set (tests, A/B: a front-first batch keeps the second stream); no_emit_stats:
+// PGMOVE_NO_EMIT_STATS is set (tests, A/B: k_read_stats and k_rank_emit stay two launches)
+static inline PgStatsPlan pg_stats_plan(uint32_t ctx_flags, int32_t scaling, uint32_t front_tiles, uint32_t n_reads, bool front_two_streams, bool no_emit_stats = false) {
     const bool skip_oor = (ctx_flags & PG_FLAG_SKIP_OUT_OF_RANGE) != 0;
     const bool lazy = !skip_oor && scaling == 1 && (ctx_flags & PG_FLAG_LAZY_STATS) != 0;
     const bool eager = skip_oor || (scaling == 1 && !lazy);
@@ -54,6 +58,9 @@ static inline PgStatsPlan pg_stats_plan(uint32_t ctx_flags, int32_t scaling, uin
     p.records_in_init = eager && !second_from_start && n_reads > 0;
     p.flags_in_init = !second_from_start;
     p.rare_with_scan = p.place == PG_STATS_CHAIN || p.place == PG_STATS_DEFERRED || p.place == PG_STATS_LAZY;
+    // a front (front_tiles != 0) means pg_submit, direct ranking, not dense, sample_limit > 0 (pg_api.hip: front_tiles_for): the emit kernel
+    // that follows is k_rank_emit, on the same stream, and nothing but the counting tail stands between the two
+    p.with_emit = p.place == PG_STATS_CHAIN && p.behind_cut && !no_emit_stats;
     return p;
 }
 
