@@ -13,7 +13,7 @@ CSRC = poregen_amd/csrc
 HOST = $(CSRC)/host
 # every list once: the translation units of libpgmove.so, the headers they and the host code compile (every object depends on all of them),
 # the sources of the CLI and the sources of the host test shim
-MODULES = pg_kernels pg_place pg_api pg_model pg_job pg_text pg_kfreq pg_f1 pg_pamean pg_svb pg_svbenc pg_dumptext pg_transform pg_mvops pg_refops pg_refseq pg_pool pg_evstat pg_fit pg_realign pg_evalign pg_sim
+MODULES = pg_kernels pg_place pg_scale pg_api pg_model pg_job pg_text pg_kfreq pg_f1 pg_pamean pg_svb pg_svbenc pg_dumptext pg_transform pg_mvops pg_refops pg_refseq pg_pool pg_evstat pg_fit pg_realign pg_evalign pg_sim
 DEV_HDRS = $(wildcard $(CSRC)/*.h) include/pgmove.h
 HOST_HDRS = $(wildcard $(HOST)/*.h)
 CLI_SRCS = $(addprefix $(HOST)/,main.cpp gmove_cli.cpp reform_cli.cpp kmer_freq_cli.cpp kfreq_reads.cpp f1_cli.cpp f1_reader.cpp subtool0_cli.cpp model_cli.cpp offsets_cli.cpp fit_cli.cpp \

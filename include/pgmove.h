@@ -118,6 +118,9 @@
  * pg_fit_parse_model               a model file as `poregen transform` writes it -> levels in 1e-3 pA
  * pg_fit_set_model / _submit /     per read sample = shift + scale * level over the basecaller's segmentation, then per k-mer how far
  * _finish / _residuals / _pass_ms  its samples lie from the level the model claims
+ * pg_fit_calibrate                 the per-read line alone, left on the device as the collector's per-read center and spread
+ *                                  (nanopolish, f5c and uncalled4 calibrate each read to the current model before they collect)
+ * pg_set_read_scaling              hands a batch's center / spread / use to a pg_params.scaling == PG_SCALING_PER_READ collector
  *
  * The reference's `realign` command (src/main.c; src/realign.cpp is a copy of reform that aligns nothing) is a handle that does align:
  * pg_realign_create / _destroy /   (no counterpart)
@@ -244,7 +247,7 @@ typedef struct {
     uint32_t max_dur;             /* --max_dur                default 70 */
     uint32_t min_dur;             /* --min_dur                default 5 */
     int32_t  kmer_pick_margin;    /* --kmer_pick_margin       default 2; must be >= 0 */
-    int32_t  scaling;             /* --scaling: 0 none, 1 med-MAD (effective default 0) */
+    int32_t  scaling;             /* --scaling: 0 none, 1 med-MAD (effective default 0), PG_SCALING_PER_READ: pg_set_read_scaling */
     int32_t  allow_rna;           /* --rna */
     double   pa_min;              /* --pa_min                 default 40.0 */
     double   pa_max;              /* --pa_max                 default 180.0 */
@@ -360,6 +363,20 @@ pg_status pg_reset(pg_ctx *ctx); /* forget all reads/events, keep parameters and
 /* count + collect with base = events accepted by earlier batches of this context */
 pg_status pg_submit(pg_ctx *ctx, const pg_batch *batch);
 
+/* pg_params.scaling == PG_SCALING_PER_READ: every batch brings a center, a spread and a use flag per read (pg_fit_calibrate computes
+ * them), and the collector stores (pA - center[r]) / spread[r] per sample: one subtraction, one division, as med-MAD's (x - median) / MAD.
+ * A sample whose pA lies outside [pa_min, pa_max] is zeroed first, as for med-MAD (gmove.cpp:756-759, 774): it is stored as
+ * (0 - center) / spread. A read with use == 0 contributes no event; it is reported as a read with an out-of-range sample is under
+ * PG_FLAG_SKIP_OUT_OF_RANGE: pg_result.read_skipped is 1, and it fails nothing. A read with use != 0 whose spread is not a finite non-zero
+ * number or whose center is not finite fails the batch with PG_ERR_INVALID_ARG; the error names the lowest such read.
+ * The arrays ([n_reads] of the NEXT pg_count / pg_submit only, host or device memory by `location`, with the lifetime of that batch's
+ * arrays; NULL only for a batch of no reads) are consumed by that call; it waits for the one word that says whether a read was refused. PG_ERR_STATE: a batch of such a
+ * context without this call in front, and this call on a context of any other scaling. pg_create refuses the scaling together with
+ * PG_FLAG_SKIP_OUT_OF_RANGE (both own the per-read skip array); pg_job_create refuses it with PG_ERR_UNSUPPORTED. No per-read statistics
+ * are computed; pg_device_view.d_med / d_mad show center and spread. */
+enum { PG_SCALING_PER_READ = 2 };
+pg_status pg_set_read_scaling(pg_ctx *ctx, const double *center, const double *spread, const uint8_t *use, int32_t location);
+
 /* Phase 1: walk/filter/rank one batch; writes the batch's accepted-event count per slot (uncapped)
  * to counts_out (uint64[n_slots]) in host or device memory. */
 pg_status pg_count(pg_ctx *ctx, const pg_batch *batch, uint64_t *counts_out, int32_t counts_location);
@@ -434,7 +451,7 @@ typedef struct {
     const uint32_t *d_ev_read;  /* read index inside the batch */
     const uint64_t *d_samp_off;
     const double   *d_samples;
-    const double   *d_med;      /* [n_reads] (scaling==1; NaN where not computed: reads without a kept event under PG_FLAG_LAZY_STATS, */
+    const double   *d_med;      /* [n_reads] (scaling==1; scaling 2: the read's center and spread; NaN where not computed: reads without a kept event under PG_FLAG_LAZY_STATS, */
     const double   *d_mad;      /* and the reads from the cut read on behind a complete front: PG_FLAG_LAZY_STATS, stats_cut_batches) */
 } pg_device_view;
 pg_status pg_last_batch_device(pg_ctx *ctx, pg_device_view *out);
@@ -1086,6 +1103,25 @@ pg_status pg_fit_set_model(pg_fit *h, const uint32_t *levels, uint32_t kmer_size
  * has ACGT letters and a level. A read with S != C (an empty slice, a contig the FASTA lacks) is PG_FIT_ST_REF_LENGTH, ranked behind
  * out_of_signal; no kernel reads its seq. Everything behind the pairing is as above. */
 pg_status pg_fit_submit(pg_fit *h, const pg_batch *batch, const uint32_t *skip, pg_fit_reads *out);
+/* A batch's reads put on the model's pA scale, for the collector (pg_set_read_scaling): pass 1 as pg_fit_submit runs it -- the same
+ * batches, flags, refusals and limits, and digitisation, offset and range ARE read -- then the solve on the device (k_fit_solve: the host's
+ * numbers bit for bit) and, per read, by this rule, each line one rounded IEEE double operation:
+ *     g      = range / digitisation
+ *     center = (a + offset) * g
+ *     spread = (b * 1000.0) * g                  (levels are in 1e-3 pA)
+ *     use    = status == PG_FIT_ST_OK  &&  center is finite  &&  spread is finite and > 0
+ * (center = spread = 0 where use is 0). A sample's pA is center + spread * (the model's level in pA) up to the fit's residual, so
+ * (pA - center) / spread is the sample on the model's pA scale. No pass 2: nothing is added to what pg_fit_finish returns. Synchronous;
+ * nothing per read comes back to the host: the arrays are DEVICE memory, owned by the handle until its next submit / calibrate / destroy.
+ * d_sums of a too_long read hold N and E only, as pg_fit_reads.sums do. */
+typedef struct {
+    uint64_t n_reads, n_ok;        /* n_ok: reads with use set */
+    const pg_fit_sums *d_sums; const uint32_t *d_status; const double *d_a, *d_b;
+    const double *d_center, *d_spread; const uint8_t *d_use;
+    uint64_t n_status[8];          /* reads per PG_FIT_ST_* 0 .. 6; [7]: reads with a skip code. n_status[0] - n_ok reads are ok and not usable */
+    double solve_ms;               /* HIP-event time of k_fit_solve and the tally behind it */
+} pg_fit_scaling;
+pg_status pg_fit_calibrate(pg_fit *h, const pg_batch *batch, const uint32_t *skip, pg_fit_scaling *out);
 /* The per-slot sums and the totals of every submit since the last finish; the handle is reset afterwards (the model stays). */
 pg_status pg_fit_finish(pg_fit *h, pg_fit_result *out);
 /* The kernels and copies of the following calls go to a caller-owned HIP stream (hipStream_t as void*); NULL restores the handle's own. */

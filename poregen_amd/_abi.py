@@ -62,7 +62,7 @@ EXPORTS = [
     "pg_mvops_create", "pg_mvops_destroy", "pg_mvops_last_error", "pg_mvops_piece", "pg_mvops_set_stream", "pg_mvops_stream", "pg_mvops_expand", "pg_mvops_project",
     "pg_mvops_project_stranded", "pg_refseq_create", "pg_refseq_destroy", "pg_refseq_last_error", "pg_refseq_set_stream", "pg_refseq_add", "pg_refseq_slice",
     "pg_fit_create", "pg_fit_destroy", "pg_fit_last_error", "pg_fit_set_model", "pg_fit_submit", "pg_fit_finish", "pg_fit_set_stream", "pg_fit_pass_ms",
-    "pg_fit_parse_model", "pg_fit_residuals",
+    "pg_fit_parse_model", "pg_fit_residuals", "pg_fit_calibrate", "pg_set_read_scaling",
     "pg_realign_create", "pg_realign_destroy", "pg_realign_last_error", "pg_realign_set_model", "pg_realign_set_stream", "pg_realign_submit", "pg_realign_kernel_ms",
     "pg_realign_walk", "pg_realign_walk_gapped", "pg_realign_set_phase",
     "pg_evalign_create", "pg_evalign_destroy", "pg_evalign_last_error", "pg_evalign_set_model", "pg_evalign_set_stream", "pg_evalign_submit", "pg_evalign_copy_text",
@@ -228,6 +228,14 @@ class PgFitParams(C.Structure):
 
 class PgFitReads(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("sums", C.c_void_p), ("status", C.c_void_p), ("a", C.c_void_p), ("b", C.c_void_p)]
+
+
+class PgFitScaling(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("n_ok", C.c_uint64), ("d_sums", C.c_void_p), ("d_status", C.c_void_p), ("d_a", C.c_void_p), ("d_b", C.c_void_p),
+                ("d_center", C.c_void_p), ("d_spread", C.c_void_p), ("d_use", C.c_void_p), ("n_status", C.c_uint64 * 8), ("solve_ms", C.c_double)]
+
+
+PG_SCALING_PER_READ = 2
 
 
 class PgFitResult(C.Structure):
@@ -452,6 +460,8 @@ def load():
         lib.pg_fit_set_model.argtypes = [vp, vp, u32]; lib.pg_fit_set_model.restype = i32
         lib.pg_fit_submit.argtypes = [vp, C.POINTER(PgBatch), vp, C.POINTER(PgFitReads)]; lib.pg_fit_submit.restype = i32
         lib.pg_fit_finish.argtypes = [vp, C.POINTER(PgFitResult)]; lib.pg_fit_finish.restype = i32
+        lib.pg_fit_calibrate.argtypes = [vp, C.POINTER(PgBatch), vp, C.POINTER(PgFitScaling)]; lib.pg_fit_calibrate.restype = i32
+        lib.pg_set_read_scaling.argtypes = [vp, vp, vp, vp, i32]; lib.pg_set_read_scaling.restype = i32
         lib.pg_fit_set_stream.argtypes = [vp, vp]; lib.pg_fit_set_stream.restype = i32
         lib.pg_fit_pass_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]; lib.pg_fit_pass_ms.restype = i32
         lib.pg_fit_parse_model.argtypes = [C.c_char_p, C.c_size_t, u32, C.POINTER(u32), vp, C.c_size_t, C.POINTER(i32), C.c_char_p, C.c_size_t]; lib.pg_fit_parse_model.restype = i32

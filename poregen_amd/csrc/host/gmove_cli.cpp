@@ -53,6 +53,7 @@ struct option long_options[] = {
     {"min_len", required_argument, 0, 0}, {"min_events", required_argument, 0, 0}, {"realign_m", required_argument, 0, 0},                // 36 .. 38
     {"realign_table", required_argument, 0, 0}, {"ref", required_argument, 0, 0},                                                        // 39, 40
     {"both_strands", no_argument, 0, 0},                                                                                                  // 41
+    {"scale_model", required_argument, 0, 0}, {"scale_min_events", required_argument, 0, 0}, {"scale_m", required_argument, 0, 0},        // 42 .. 44
     {0, 0, 0, 0}};
 
 void print_help(FILE *fp, const Opt &o) { // src/gmove.cpp:80-104
@@ -115,6 +116,12 @@ void print_help(FILE *fp, const Opt &o) { // src/gmove.cpp:80-104
     fprintf(fp, "   --min_events INT           with --realign: counted events a read needs to be fitted [20]\n");
     fprintf(fp, "   --realign_m INT            with --realign: the model's move start offset, as `poregen realign -m` [0]\n");
     fprintf(fp, "   --realign_table FILE       with --realign: the per-read table `poregen realign --read_table` writes, for the reads taken\n");
+    fprintf(fp, "   --scale_model MODEL        with --reform, one device: collect every read on the k-mer model's pA scale. Every batch is fitted to the model on\n");
+    fprintf(fp, "                              the GPU (`poregen fit`'s per-read line sample = shift + scale * level, on the ops the collector takes) and a sample\n");
+    fprintf(fp, "                              is stored as (pA - shift) / scale, so that `poregen model` over the dump directory gives level_mean in pA. A read\n");
+    fprintf(fp, "                              without a fit is left out and counted. Not with --scaling 1; --min_dur, --max_dur, --rna and --n_to_t are the fit's too\n");
+    fprintf(fp, "   --scale_min_events INT     with --scale_model: counted events a read needs to be fitted [20]\n");
+    fprintf(fp, "   --scale_m INT              with --scale_model: the model's move start offset, 0 to 64 [--realign_m, else 0]\n");
 }
 
 // The signal of a batch is hundreds of MB: a std::vector would zero every byte on resize (one thread, and the page faults
@@ -184,6 +191,8 @@ int gmove_main(int argc, char **argv) {
     bool both_strands = false;      // --both_strands: reverse-strand records are taken, the reference slices come from the device
     const char *realign_model = nullptr, *realign_table = nullptr, *realign_extra = nullptr; // realign_extra: the first option given that needs --realign
     long long realign_rounds = 1, realign_band = 10, realign_min_len = 3, realign_min_events = 20, realign_m = 0;
+    const char *scale_model = nullptr, *scale_extra = nullptr; // scale_extra: the first option given that needs --scale_model
+    long long scale_min_events = 20, scale_m = -1;             // (-1: --realign_m's value)
     int verbose = 3;
     optind = 1;
     while ((c = getopt_long(argc, argv, "k:m:s:dv:", long_options, &longindex)) >= 0) { // src/gmove.cpp:240-327
@@ -232,6 +241,14 @@ int gmove_main(int argc, char **argv) {
         else if (c == 0 && longindex == 33) realign_model = optarg;
         else if (c == 0 && longindex == 40) ref_path = optarg;
         else if (c == 0 && longindex == 41) both_strands = true;
+        else if (c == 0 && longindex == 42) scale_model = optarg;
+        else if (c == 0 && (longindex == 43 || longindex == 44)) {
+            if (!scale_extra) scale_extra = long_options[longindex].name;
+            if (!(longindex == 43 ? whole_int(optarg, 0, 0xffffffffll, scale_min_events) : whole_int(optarg, 0, 64, scale_m))) {
+                fprintf(stderr, "--%s: '%s' is not a value it takes (--scale_min_events 0 and up, --scale_m 0..64, whole numbers)\n", long_options[longindex].name, optarg);
+                print_help(stderr, opt); return EXIT_FAILURE;
+            }
+        }
         else if (c == 0 && longindex >= 34 && longindex <= 39) {
             bool ok = true;
             if (!realign_extra) realign_extra = long_options[longindex].name;
@@ -284,6 +301,20 @@ int gmove_main(int argc, char **argv) {
         // the combination with --ref stands on the model's levels alone (the sequence is the reference's): said with the refusal
         if (!model_ok && ref_path) fprintf(stderr, "--ref cannot be combined with --realign %s: a k-mer model with levels is required, as `poregen transform` writes it\n", realign_model);
         if (why || !model_ok) { print_help(fp_help, opt); return EXIT_FAILURE; }
+    }
+    // --scale_model: the same
+    std::vector<uint32_t> scale_levels; uint32_t scale_k = 0; int32_t scale_uses_u = 0;
+    {
+        const char *why = nullptr;
+        char text[200];
+        if (scale_model && !reform_mode) why = "--scale_model applies with --reform only";
+        else if (scale_extra && !scale_model) { snprintf(text, sizeof text, "--%s applies with --scale_model only", scale_extra); why = text; }
+        else if (scale_model && signal_scale == 1) why = "--scale_model cannot be combined with --scaling 1: a read is put on the model's scale or on its own med-MAD scale";
+        else if (scale_model && !devices.empty()) why = "--scale_model works on one device: it cannot be combined with --devices";
+        else if (scale_model && ((uint32_t)opt.min_dur > (uint32_t)opt.max_dur || (uint32_t)opt.max_dur > PG_FIT_MAX_DUR)) why = "--scale_model: min_dur <= max_dur <= 2^20 is required";
+        if (why) fprintf(stderr, "%s\n", why);
+        if (why || (scale_model && !load_level_model("gmove", scale_model, 0, scale_levels, scale_k, scale_uses_u))) { print_help(fp_help, opt); return EXIT_FAILURE; }
+        if (scale_m < 0) scale_m = realign_m;
     }
     if (event_model_path && devices.size() > 1) return die("--event_model works on one device: it cannot be combined with --devices of more than one device");
     if (event_model_path && devices.size() == 1) { device = devices[0]; devices.clear(); } // (one listed device: the single-device path)
@@ -363,7 +394,8 @@ int gmove_main(int argc, char **argv) {
     if (!pgh::touch_dump_files(output_dir, slot_kmers, err)) { fprintf(stderr, "%s\n", err.c_str()); return EXIT_FAILURE; } // gmove.cpp:460-473
 
     int scaling; // src/gmove.cpp:479-491
-    if (signal_scale == 0) { scaling = 0; fprintf(stderr, "scaling: %s\n", "no scale"); }
+    if (signal_scale == 0 && scale_model) { scaling = PG_SCALING_PER_READ; fprintf(stderr, "scaling: %s\n", "model scale"); }
+    else if (signal_scale == 0) { scaling = 0; fprintf(stderr, "scaling: %s\n", "no scale"); }
     else if (signal_scale == 1) { scaling = 1; fprintf(stderr, "scaling: %s\n", "medmad scale"); }
     else { print_help(fp_help, opt); return EXIT_FAILURE; }
 
@@ -687,7 +719,9 @@ int gmove_main(int argc, char **argv) {
         // array, which like the expander's lives until the slot's next batch -- behind the submit of the batch in between.
         // With --ref the ops are carried through the records' CIGARs onto the reference on the expander (pg_mvops_project), the host fetches
         // every read's slice of the FASTA, and the batch -- I and D ops among its matches -- goes to the collector's generic walk.
-        struct Slot { pg_mvops *ex = nullptr; pg_fit *fit = nullptr; pg_realign *ra = nullptr; PgDev<int16_t> sig; PgDev<uint64_t> sig_off; PgDev<double> cal;
+        // With --scale_model every slot has a fit handle of its own for the calibration (its parameters are --scale_*'s, not --realign's), on
+        // the same stream: its per-read arrays live until the slot's next batch as well.
+        struct Slot { pg_mvops *ex = nullptr; pg_fit *fit = nullptr; pg_realign *ra = nullptr; pg_fit *scale = nullptr; PgDev<int16_t> sig; PgDev<uint64_t> sig_off; PgDev<double> cal;
                       PgDev<uint8_t> seq; PgDev<uint64_t> seq_off; };
         route.both_strands = both_strands; route.rna = opt.flag_rna != 0;
         Slot slots[2];
@@ -699,10 +733,11 @@ int gmove_main(int argc, char **argv) {
         auto release = [&]() {
             for (Slot &sl : slots) {
                 if (sl.fit) pg_fit_destroy(sl.fit);
+                if (sl.scale) pg_fit_destroy(sl.scale);
                 if (sl.ra) pg_realign_destroy(sl.ra);
                 if (sl.ex) pg_mvops_destroy(sl.ex);
                 route.release();
-                sl.fit = nullptr; sl.ra = nullptr; sl.ex = nullptr; sl.sig.release(); sl.sig_off.release(); sl.cal.release(); sl.seq.release(); sl.seq_off.release();
+                sl.fit = nullptr; sl.scale = nullptr; sl.ra = nullptr; sl.ex = nullptr; sl.sig.release(); sl.sig_off.release(); sl.cal.release(); sl.seq.release(); sl.seq_off.release();
             }
         };
         RealignRounds rounds;
@@ -721,6 +756,16 @@ int gmove_main(int argc, char **argv) {
             if (pg_realign_create(&rp, on_device, &sl.ra) != PG_OK) { fprintf(stderr, "[gmove] %s\n", pg_realign_last_error(nullptr)); return false; }
             if (pg_fit_set_model(sl.fit, realign_levels.data(), realign_k) != PG_OK || pg_fit_set_stream(sl.fit, xs) != PG_OK) { fprintf(stderr, "[gmove] %s\n", pg_fit_last_error(sl.fit)); return false; }
             if (pg_realign_set_model(sl.ra, realign_levels.data(), realign_k) != PG_OK || pg_realign_set_stream(sl.ra, xs) != PG_OK) { fprintf(stderr, "[gmove] %s\n", pg_realign_last_error(sl.ra)); return false; }
+            return true;
+        };
+        // --scale_model: the slot's calibration handle, and what the batches' calibrations counted (pg_fit_scaling: nothing per read comes back)
+        uint64_t scale_reads = 0, scale_used = 0, scale_status[8] = {0, 0, 0, 0, 0, 0, 0, 0}, scale_batches = 0;
+        auto scale_handle = [&](Slot &sl, int on_device) {
+            if (sl.scale) return true;
+            pg_fit_params fp; memset(&fp, 0, sizeof fp);
+            fp.struct_size = sizeof fp; fp.sig_move_offset = (uint32_t)scale_m; fp.min_dur = (uint32_t)opt.min_dur; fp.max_dur = (uint32_t)opt.max_dur; fp.min_events = (uint32_t)scale_min_events; fp.rna = opt.flag_rna;
+            if (pg_fit_create(&fp, on_device, &sl.scale) != PG_OK) { fprintf(stderr, "[gmove] %s\n", pg_fit_last_error(nullptr)); return false; }
+            if (pg_fit_set_model(sl.scale, scale_levels.data(), scale_k) != PG_OK || pg_fit_set_stream(sl.scale, pg_mvops_stream(sl.ex)) != PG_OK) { fprintf(stderr, "[gmove] %s\n", pg_fit_last_error(sl.scale)); return false; }
             return true;
         };
         bool eof = false;
@@ -838,13 +883,24 @@ int gmove_main(int argc, char **argv) {
                     b.query_start = d_qs; b.target_start = d_ts; b.target_end = d_te; b.seq = d_seq; b.seq_off = d_seqoff;
                     b.op_n = d_opn; b.op_t = d_opt; b.op_off = d_opoff;
                     if (!ref_path) b.flags = PG_BATCH_ALL_MATCHES; // every op is a match and a read has as many ops as bases: what `reform` writes
-                    else if (realign_model) b.flags = PG_BATCH_GAPPED; // fit and realign walk the projected ops over the reference slices; the collector ignores the flag
+                    else if (realign_model || scale_model) b.flags = PG_BATCH_GAPPED; // fit and realign walk the projected ops over the reference slices; the collector ignores the flag
                     if (realign_model) { // the rounds on the device batch; the collector takes the last round's ops
                         if (!realign_handles(sl, ex_device)) { status = EXIT_FAILURE; break; }
                         if (!rounds.run(sl.fit, sl.fit, sl.ra, b, realign_rounds)) { fprintf(stderr, "[gmove] %s\n", rounds.err.c_str()); status = EXIT_FAILURE; break; }
                         b.op_n = rounds.op_n;
                         realign_reads += n;
                         if (rt) for (size_t i = 0; i < n; i++) rounds.row(rt, rb.names[i].c_str(), i);
+                    }
+                    if (scale_model) { // the fit over the ops the collector is about to take; its per-read numbers stay on the device
+                        pg_fit_scaling sc;
+                        if (!scale_handle(sl, ex_device)) { status = EXIT_FAILURE; break; }
+                        if (pg_fit_calibrate(sl.scale, &b, nullptr, &sc) != PG_OK) { fprintf(stderr, "[gmove] %s\n", pg_fit_last_error(sl.scale)); status = EXIT_FAILURE; break; }
+                        if (pg_set_read_scaling(dev.ctx, sc.d_center, sc.d_spread, sc.d_use, PG_LOC_DEVICE) != PG_OK) { fprintf(stderr, "[gmove] %s\n", dev.error()); status = EXIT_FAILURE; break; }
+                        scale_reads += sc.n_reads; scale_used += sc.n_ok; scale_batches++;
+                        for (int i = 0; i < 8; i++) scale_status[i] += sc.n_status[i];
+                        if (verbose >= 4)
+                            fprintf(stderr, "[gmove] scale_model: batch %llu reads=%llu collected=%llu solve_ms=%.3f\n", (unsigned long long)scale_batches, (unsigned long long)sc.n_reads,
+                                    (unsigned long long)sc.n_ok, sc.solve_ms);
                     }
                     if (dev.submit(&b) != PG_OK) { fprintf(stderr, "[gmove] %s\n", dev.error()); status = EXIT_FAILURE; break; }
                     t_device += secs(tf0, clk::now());
@@ -870,6 +926,11 @@ int gmove_main(int argc, char **argv) {
         release();
         if (ref_path) route.print_skipped("gmove");
         if (rt && fclose(rt) != 0 && status == EXIT_SUCCESS) { fprintf(stderr, "Error in writing %s.\n", realign_table); status = EXIT_FAILURE; }
+        if (scale_model) // the reads collected, and the reads left out by the fit's status (refused: reads the expander or the projection refuses)
+            fprintf(stderr, "[gmove] scale_model: k=%u reads=%llu collected=%llu not_usable=%llu out_of_signal=%llu too_long=%llu few_events=%llu flat=%llu negative_scale=%llu ref_length=%llu refused=%llu\n",
+                    scale_k, (unsigned long long)scale_reads, (unsigned long long)scale_used, (unsigned long long)(scale_status[0] - scale_used), (unsigned long long)scale_status[1],
+                    (unsigned long long)scale_status[2], (unsigned long long)scale_status[3], (unsigned long long)scale_status[4], (unsigned long long)scale_status[5],
+                    (unsigned long long)scale_status[6], (unsigned long long)scale_status[7]);
         if (realign_model && verbose >= 4)
             fprintf(stderr, "[gmove] realign: k=%u band=%lld rounds=%lld reads=%llu refined=%llu free=%llu moved=%llu\n", realign_k, realign_band, realign_rounds,
                     (unsigned long long)realign_reads, (unsigned long long)rounds.refined, (unsigned long long)rounds.n_free, (unsigned long long)rounds.n_moved);

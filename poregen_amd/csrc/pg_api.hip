@@ -97,6 +97,9 @@ struct pg_ctx {
     // b + 2, which zeroes entry b & 3, follows that gather on the chain's stream.
     PgDev<> long_ring; uint32_t long_seq = 0; // (long_seq crosses batches: it numbers them for the ring)
     PgDev<> meta, huge_scratch, oor;
+    // PG_SCALING_PER_READ: what pg_set_read_scaling left for the next batch (consumed by pg_count), the staged copy of host arrays, k_scale_records' word
+    const double *rs_center = nullptr, *rs_spread = nullptr; const uint8_t *rs_use = nullptr; int32_t rs_location = PG_LOC_HOST; bool rs_set = false;
+    PgDev<> rs_stage[3], rs_bad;
     PgDev<> blk_read, gen_flag, gen_list, cum, btot, tile_read; // PgWalkOut: owner index, generic-read list, block sums of op_n
     uint32_t batch_id = 0;  // serial number of the batch being counted (tags gen_flag entries and the error word); crosses batches: it counts them
     BatchState bt;          // the current batch
@@ -286,7 +289,9 @@ pg_status pg_create(const pg_params *p, pg_ctx **out) {
     if (p->kmer_size < 1 || p->kmer_size > 13) return pg_fail<pg_ctx>(nullptr, PG_ERR_INVALID_ARG, "kmer_size must be in [1,13]");
     if (p->sig_move_offset > p->kmer_size) return pg_fail<pg_ctx>(nullptr, PG_ERR_INVALID_ARG, "sig_move_offset > kmer_size indexes past the reference's arrays (gmove.cpp:892)");
     if (p->kmer_pick_margin < 0) return pg_fail<pg_ctx>(nullptr, PG_ERR_INVALID_ARG, "negative kmer_pick_margin is undefined in the reference (gmove.cpp:204-211)");
-    if (p->scaling != 0 && p->scaling != 1) return pg_fail<pg_ctx>(nullptr, PG_ERR_INVALID_ARG, "scaling must be 0 or 1");
+    if (p->scaling != 0 && p->scaling != 1 && p->scaling != PG_SCALING_PER_READ) return pg_fail<pg_ctx>(nullptr, PG_ERR_INVALID_ARG, "scaling must be 0, 1 or 2 (PG_SCALING_PER_READ)");
+    if (p->scaling == PG_SCALING_PER_READ && (p->flags & PG_FLAG_SKIP_OUT_OF_RANGE))
+        return pg_fail<pg_ctx>(nullptr, PG_ERR_INVALID_ARG, "scaling 2 (PG_SCALING_PER_READ) does not go with PG_FLAG_SKIP_OUT_OF_RANGE: both own the per-read skip array");
     if (p->n_slots < 1 || !p->table_t || !p->table_u) return pg_fail<pg_ctx>(nullptr, PG_ERR_INVALID_ARG, "n_slots/table_t/table_u missing");
     if (pg_status s = pg_select_device<pg_ctx>(p->device)) return s;
 
@@ -562,7 +567,7 @@ static pg_status check_read_errors(pg_ctx *c, const PgSettlePack &pk) {
 static pg_status ensure_stats_buffers(pg_ctx *c) {
     const uint32_t n = c->B.n_reads;
     const int sl = c->slot;
-    if (c->prm.flags & PG_FLAG_SKIP_OUT_OF_RANGE) PG_HIP_TRY(c, grow(c->oor, n + 1ull));
+    if ((c->prm.flags & PG_FLAG_SKIP_OUT_OF_RANGE) || c->prm.scaling == PG_SCALING_PER_READ) PG_HIP_TRY(c, grow(c->oor, n + 1ull));
     PG_HIP_TRY(c, grow(c->med[sl], (n + 1) * 8ull)); PG_HIP_TRY(c, grow(c->mad[sl], (n + 1) * 8ull));
     PG_HIP_TRY(c, grow(c->gcal[sl], (n + 1) * 32ull));
     PG_HIP_TRY(c, grow(c->read_plan[sl], (n + 1) * (size_t)PG_STAT_REC_BYTES)); PG_HIP_TRY(c, grow(c->wide_list[sl], (n + 1) * 4ull));
@@ -648,7 +653,7 @@ static void fill_walk(pg_ctx *c, PgWalkParams &W, PgWalkOut &O) {
     O.err = c->errflag.as<unsigned long long>(); O.layout_err = c->errflag.as<int32_t>() + 2; O.gen_count = c->errflag.as<uint32_t>() + 4;
     O.blk_read = c->blk_read.as<uint32_t>(); O.gen_flag = c->gen_flag.as<uint32_t>(); O.gen_list = c->gen_list.as<uint32_t>();
     O.cum = c->cum.as<uint32_t>(); O.btot = c->btot.as<uint32_t>(); O.batch_id = c->batch_id; O.tile_read = c->tile_read.as<uint32_t>();
-    O.oor = (c->prm.flags & PG_FLAG_SKIP_OUT_OF_RANGE) ? c->oor.as<uint8_t>() : nullptr;
+    O.oor = ((c->prm.flags & PG_FLAG_SKIP_OUT_OF_RANGE) || c->prm.scaling == PG_SCALING_PER_READ) ? c->oor.as<uint8_t>() : nullptr; // (scaling 2: the reads without a scaling)
 }
 
 // the long-read split of the statistics (PgLongState) for the batch in statistics slot c->slot; ensure = size the buffers for this batch
@@ -746,11 +751,48 @@ static pg_status ensure_unpacked(pg_ctx *c) {
     return PG_OK;
 }
 
+// PG_SCALING_PER_READ: the arrays of pg_set_read_scaling into the slot's records (k_scale_records, behind k_batch_init on the chain's
+// stream), then k_apply_oor in front of the walk, as the PG_STATS_OOR_FIRST branch queues it. Waits for the kernel's one word: a refused
+// read fails the batch before anything is walked.
+static pg_status apply_read_scaling(pg_ctx *c, const PgWalkOut &O) {
+    const uint32_t n = c->B.n_reads;
+    const int sl = c->slot;
+    pg_status se = ensure_stats_buffers(c);
+    if (se != PG_OK) return se;
+    const double *center = c->rs_center, *spread = c->rs_spread;
+    const uint8_t *use = c->rs_use;
+    if (n && (!center || !spread || !use)) return pg_fail(c, PG_ERR_INVALID_ARG, "pg_set_read_scaling gave a null array for a batch of %u reads", n);
+    if (c->rs_location == PG_LOC_HOST && n) {
+        PG_HIP_TRY(c, grow(c->rs_stage[0], n * 8ull)); PG_HIP_TRY(c, grow(c->rs_stage[1], n * 8ull)); PG_HIP_TRY(c, grow(c->rs_stage[2], n));
+        PG_HIP_TRY(c, hipMemcpyAsync(c->rs_stage[0].p, center, n * 8ull, hipMemcpyHostToDevice, c->st));
+        PG_HIP_TRY(c, hipMemcpyAsync(c->rs_stage[1].p, spread, n * 8ull, hipMemcpyHostToDevice, c->st));
+        PG_HIP_TRY(c, hipMemcpyAsync(c->rs_stage[2].p, use, n, hipMemcpyHostToDevice, c->st));
+        center = c->rs_stage[0].as<double>(); spread = c->rs_stage[1].as<double>(); use = c->rs_stage[2].as<uint8_t>();
+    }
+    PG_HIP_TRY(c, grow(c->rs_bad, 4));
+    prof_begin(c, "k_scale_records", c->st);
+    PG_HIP_TRY(c, pg_launch_scale_records(c->st, c->B, center, spread, use, c->gcal[sl].as<double>(), c->med[sl].as<double>(), c->mad[sl].as<double>(), c->oor.as<uint8_t>(),
+                                          c->stat_err[sl].as<int32_t>() + 3, c->rs_bad.as<uint32_t>()));
+    prof_end(c, c->st);
+    uint32_t bad = 0xffffffffu;
+    PG_HIP_TRY(c, hipMemcpyAsync(&bad, c->rs_bad.p, 4, hipMemcpyDeviceToHost, c->st));
+    PG_HIP_TRY(c, hipStreamSynchronize(c->st));
+    if (bad != 0xffffffffu)
+        return pg_fail(c, PG_ERR_INVALID_ARG, "read %u of the batch (global read %llu): pg_set_read_scaling marks it for use, but its spread is not a finite non-zero number or its center is not finite",
+                       bad, (unsigned long long)(c->reads_before + bad));
+    PG_HIP_TRY(c, pg_launch_apply_oor(c->st, c->B, O));
+    return PG_OK;
+}
+
 // pg_count, and the count phase of pg_submit (in_submit: the base is this context's running counts, so the sample_limit cut can ride in
 // the scan's launch and the batch can be counted front first)
 static pg_status count_impl(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, int32_t counts_location, bool in_submit) {
     if (!c || !b) return PG_ERR_INVALID_ARG;
     if (b->struct_size != sizeof(pg_batch)) return pg_fail(c, PG_ERR_INVALID_ARG, "pg_batch.struct_size mismatch");
+    if (c->prm.scaling == PG_SCALING_PER_READ) { // the arrays are this batch's alone, whatever becomes of it
+        if (!c->rs_set) return pg_fail(c, PG_ERR_STATE, "a batch of a scaling-2 (PG_SCALING_PER_READ) context needs pg_set_read_scaling in front of it");
+        c->rs_set = false;
+    }
     PG_HIP_TRY(c, hipSetDevice(c->device));
     pg_status s = download_last(c, true);
     if (s != PG_OK) return s;
@@ -878,7 +920,8 @@ static pg_status count_impl(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, 
     // fails behind this line, it costs the next two-stream batch one wait it did not need.
     c->prev_one_stream = P.one_stream_batch;
     // k_batch_init also writes the statistics record of every read: k_read_plan's work, one kernel boundary less
-    if (P.records_in_init) { pg_status se = ensure_stats_buffers(c); if (se != PG_OK) return se; }
+    // (PG_SCALING_PER_READ: fill_walk below hands the skip array to the walk, so it has to exist by now)
+    if (P.records_in_init || c->prm.scaling == PG_SCALING_PER_READ) { pg_status se = ensure_stats_buffers(c); if (se != PG_OK) return se; }
     PgWalkParams W{}; PgWalkOut O{};
     fill_walk(c, W, O);
     const bool force_generic = (c->prm.flags & PG_FLAG_DEBUG_SPLIT_WALK) != 0;
@@ -896,6 +939,9 @@ static pg_status count_impl(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, 
     if (P.place == PG_STATS_OOR_FIRST) { // statistics first: the walk needs their verdict
         pg_status s2 = launch_stats(c); if (s2 != PG_OK) return s2;
         PG_HIP_TRY(c, pg_launch_apply_oor(c->st, c->B, O));
+    }
+    if (c->prm.scaling == PG_SCALING_PER_READ) { // the caller's per-read scaling in place of statistics: its verdict, too, in front of the walk
+        pg_status s2 = apply_read_scaling(c, O); if (s2 != PG_OK) return s2;
     }
     // the generic walk over the list k_batch_init has just built; not launched when the caller vouches for a batch of matches only
     if (!c->bt.all_matches) {
@@ -1210,12 +1256,12 @@ static pg_status collect_impl(pg_ctx *c, const uint64_t *base, int32_t base_loca
     if (chunked) c->gather_forms[pg_gather_form(lanes)]++;
     if (chunked)
         PG_HIP_TRY(c, pg_launch_gather_chunks(c->st, c->B, ke_cap, totals, c->ev_rec.as<PgKeptRec>(), c->chunk_part.as<uint64_t>(), c->samp_off.as<uint64_t>(), totals + 2, c->prm.scaling,
-                                           c->prm.pa_min, c->prm.pa_max, c->samples.as<double>(), c->prm.scaling == 1 ? c->gcal[c->slot].as<double>() : nullptr, lanes,
-                                           c->prm.scaling == 1 ? c->stat_err[c->slot].as<int32_t>() : nullptr));
+                                           c->prm.pa_min, c->prm.pa_max, c->samples.as<double>(), c->prm.scaling != 0 ? c->gcal[c->slot].as<double>() : nullptr, lanes,
+                                           c->prm.scaling != 0 ? c->stat_err[c->slot].as<int32_t>() : nullptr));
     else
         PG_HIP_TRY(c, pg_launch_gather(c->st, c->B, gather_cap, totals, c->ev_rec.as<PgKeptRec>(),
                      c->samp_off.as<uint64_t>(), c->prm.scaling, c->prm.pa_min, c->prm.pa_max, c->med[c->slot].as<double>(), c->mad[c->slot].as<double>(),
-                     c->samples.as<double>(), c->prm.scaling == 1 ? c->gcal[c->slot].as<double>() : nullptr));
+                     c->samples.as<double>(), c->prm.scaling != 0 ? c->gcal[c->slot].as<double>() : nullptr));
     prof_end(c, c->st);
     // "this slot's statistics buffers have been read": for the statistics stream two batches on. With one stream nobody waits for it, and a
     // record ends the gather with 4.6 us in which the stream starts nothing (rocprofv3 kernel trace, tools/trace_gaps.py: every other
@@ -1263,6 +1309,18 @@ pg_status pg_submit(pg_ctx *c, const pg_batch *b) {
     pg_status s = count_impl(c, b, nullptr, PG_LOC_HOST, true);
     if (s != PG_OK) return s;
     return pg_collect(c, nullptr, PG_LOC_HOST);
+}
+
+pg_status pg_set_read_scaling(pg_ctx *c, const double *center, const double *spread, const uint8_t *use, int32_t location) {
+    if (!c) return PG_ERR_INVALID_ARG;
+    if (c->prm.scaling != PG_SCALING_PER_READ) return pg_fail(c, PG_ERR_STATE, "pg_set_read_scaling: the context's scaling is %d, not 2 (PG_SCALING_PER_READ)", c->prm.scaling);
+    if (location != PG_LOC_HOST && location != PG_LOC_DEVICE) return pg_fail(c, PG_ERR_INVALID_ARG, "pg_set_read_scaling: location must be PG_LOC_HOST or PG_LOC_DEVICE");
+    // (null arrays are those of an empty batch: refused by the batch's pg_count if it has reads after all)
+    if (location == PG_LOC_DEVICE)
+        for (const void *q : {(const void *)center, (const void *)spread, (const void *)use})
+            if (q && pg_ptr_kind(q, c->device) != PG_PTR_DEVICE) return pg_fail(c, PG_ERR_INVALID_ARG, "pg_set_read_scaling: PG_LOC_DEVICE arrays must be device memory of device %d", c->device);
+    c->rs_center = center; c->rs_spread = spread; c->rs_use = use; c->rs_location = location; c->rs_set = true;
+    return PG_OK;
 }
 
 pg_status pg_job_totals_device(pg_ctx *c, const uint64_t **d_total, const uint64_t **d_freq) {
@@ -1331,7 +1389,7 @@ pg_status pg_last_batch_device(pg_ctx *c, pg_device_view *v) {
     v->n_events = c->cur_n_kept; v->n_samples = c->cur_n_samples;
     v->d_keep = c->keep.as<uint64_t>(); v->d_ev_off = c->ev_off.as<uint64_t>(); v->d_ev_len = c->ev_len.as<uint32_t>();
     v->d_ev_read = c->ev_read.as<uint32_t>(); v->d_samp_off = c->samp_off.as<uint64_t>(); v->d_samples = c->samples.as<double>();
-    v->d_med = c->prm.scaling == 1 ? c->med[c->slot].as<double>() : nullptr; v->d_mad = c->prm.scaling == 1 ? c->mad[c->slot].as<double>() : nullptr;
+    v->d_med = c->prm.scaling != 0 ? c->med[c->slot].as<double>() : nullptr; v->d_mad = c->prm.scaling != 0 ? c->mad[c->slot].as<double>() : nullptr;
     return PG_OK;
 }
 

@@ -16,7 +16,8 @@
 // A read with more counted samples is reported as too_long; only its N and E are kept.
 //
 // Solve, on the host: den = N SLL - SL^2, numb = N SRL - SL SR, numa = SR SLL - SL SRL exactly; b = (double)numb / (double)den,
-// a = (double)numa / (double)den, inv_b = 1.0 / b, each conversion and division one correctly rounded IEEE operation.
+// a = (double)numa / (double)den, inv_b = 1.0 / b, each conversion and division one correctly rounded IEEE operation. On the device
+// (pg_fit_calibrate: k_fit_solve) the same numbers bit for bit from pg_fit_solve_hd, whose conversion is written out by hand.
 //
 // Pass 2, per k-mer, over the fitted reads: c = llrint(((double)r - a) * inv_b) (ties to even), d = c - l clamped to |d| <= 2^18 - 1
 // (PG_FIT_CLAMP; clamped samples are counted). |(r - a) * inv_b| >= 2^21 clamps whatever l is, so the product is cut to +-2^21 before it is
@@ -134,9 +135,77 @@ PG_FIT_HD int32_t pg_fit_resid(int32_t r, double a, double inv_b, int32_t l, boo
     return (int32_t)d;
 }
 
-// ---- host only: the solve, the text rules, the model parser, the walk of one read -----------------------------------------------------
-
 struct PgFitSolve { uint32_t status; double a, b, inv_b; };
+
+// ---- the solve for host and device (k_fit_solve, pg_fit_calibrate; the host seam pgt_fit_solve_hd) -------------------------------------
+// The same numbers as pg_fit_solve below, bit for bit, without what a device lacks: the conversion of an __int128 to a double is a
+// library call there, so it is written out. The products and sums are the compiler's 128-bit + - x on both sides.
+
+// A signed 128-bit integer to the nearest double, ties to even: the leading bit, 53 bits kept, the guard bit and the sticky bits decide,
+// and a carry out of the 53 bits goes into the exponent (the mantissa is then a power of two). Exact for |v| < 2^53.
+PG_FIT_HD double pg_fit_i128_to_double(__int128 v) {
+    const bool neg = v < 0;
+    const unsigned __int128 u = neg ? (unsigned __int128)0 - (unsigned __int128)v : (unsigned __int128)v;
+    const uint64_t hi = (uint64_t)(u >> 64), lo = (uint64_t)u;
+    if (!(hi | lo)) return 0.0;
+    const int top = hi ? 127 - __builtin_clzll(hi) : 63 - __builtin_clzll(lo); // index of the leading bit
+    uint64_t mant; // the 53 leading bits
+    int exp2 = top - 52; // the value is mant * 2^exp2
+    if (top <= 52) { mant = lo; exp2 = 0; }
+    else {
+        const int sh = top - 52; // bits dropped, 1 .. 75
+        mant = (uint64_t)(u >> sh);
+        const bool guard = (uint64_t)(u >> (sh - 1)) & 1u;
+        const bool sticky = sh > 1 && (u & ((((unsigned __int128)1) << (sh - 1)) - 1)) != 0;
+        if (guard && (sticky || (mant & 1u))) mant++;
+        if (mant >> 53) { mant >>= 1; exp2++; } // all ones rounded up: 2^53 -> 2^52 one exponent higher
+    }
+    // mant < 2^53 converts exactly; 2^exp2 is built from its bits (exp2 <= 75: a normal number), and the product is exact
+    union { uint64_t b; double d; } p2;
+    p2.b = (uint64_t)(1023 + exp2) << 52;
+    const double r = (double)(int64_t)mant * p2.d;
+    return neg ? -r : r;
+}
+
+// pg_fit_solve for host and device
+PG_FIT_HD PgFitSolve pg_fit_solve_hd(const PgFitSums &s, uint32_t min_events) {
+    PgFitSolve o{PG_FIT_OK, 0.0, 0.0, 0.0};
+    if (s.n > PG_FIT_MAX_N) { o.status = PG_FIT_TOO_LONG; return o; }
+    if (s.e < (int64_t)min_events) { o.status = PG_FIT_FEW_EVENTS; return o; }
+    const __int128 den = (__int128)s.n * s.sll - (__int128)s.sl * s.sl;
+    if (den == 0) { o.status = PG_FIT_FLAT; return o; }
+    const __int128 numb = (__int128)s.n * s.srl - (__int128)s.sl * s.sr;
+    if (numb <= 0) { o.status = PG_FIT_NEGATIVE_SCALE; return o; }
+    const __int128 numa = (__int128)s.sr * s.sll - (__int128)s.sl * s.srl;
+    const double dd = pg_fit_i128_to_double(den);
+    o.b = pg_fit_i128_to_double(numb) / dd;
+    o.a = pg_fit_i128_to_double(numa) / dd;
+    o.inv_b = 1.0 / o.b;
+    return o;
+}
+
+// ---- a read's place on the model's pA scale (gmove --reform --scale_model; pg_params.scaling == PG_SCALING_PER_READ) --------------------
+// The fit says sample = a + b * level with the level in 1e-3 pA, so a sample's pA is g (a + offset) + (1000 g b) * (level in pA), and
+//   g      = range / digitisation          (the expression PgStatRec::scale uses)
+//   center = (a + offset) * g
+//   spread = (b * 1000.0) * g
+//   use    = status == PG_FIT_OK  &&  center is finite  &&  spread is finite and > 0
+// each line one rounded IEEE double operation. The collector stores (pA - center) / spread per sample: the sample on the model's pA scale.
+// A sample whose pA lies outside [pa_min, pa_max] is zeroed FIRST, as for med-MAD (gmove.cpp:756-759, 774): it is stored as
+// (0 - center) / spread. A read with use == 0 has center = spread = 0.
+struct PgFitScale { double center, spread; uint8_t use; };
+PG_FIT_HD bool pg_fit_finite(double x) { return x - x == 0.0; } // (false for NaN and the infinities; no library call)
+PG_FIT_HD PgFitScale pg_fit_scale_rule(uint32_t status, double a, double b, double digitisation, double offset, double range) {
+    PgFitScale o{0.0, 0.0, 0};
+    if (status != PG_FIT_OK) return o;
+    const double g = range / digitisation;
+    const double center = (a + offset) * g, spread = (b * 1000.0) * g;
+    if (!pg_fit_finite(center) || !pg_fit_finite(spread) || !(spread > 0.0)) return o;
+    o.center = center; o.spread = spread; o.use = 1;
+    return o;
+}
+
+// ---- host only: the solve, the text rules, the model parser, the walk of one read -----------------------------------------------------
 
 // the statuses behind out_of_signal, tested in the order of the enum; a and b only with PG_FIT_OK
 static inline PgFitSolve pg_fit_solve(const PgFitSums &s, uint32_t min_events) {

@@ -109,6 +109,48 @@ template <bool kLdsTable, bool kGapped> __global__ __launch_bounds__(kThreads) v
     }
 }
 
+// pg_fit_calibrate: the solve of every read and the collector's numbers from it (the rule: pg_fit.h), one lane per read. status comes in
+// as the host left it behind pass 1 (ok, out_of_signal, ref_length, a skip code) and goes out final; a too_long read keeps its N and E only,
+// as on the host.
+struct FitSolveOut { uint32_t *status; double *a, *b, *center, *spread; uint8_t *use; };
+__global__ __launch_bounds__(kThreads) void k_fit_solve(uint32_t n_reads, uint32_t min_events, PgFitSums *__restrict__ sums, const double *__restrict__ dig,
+                                                        const double *__restrict__ off, const double *__restrict__ range, const FitSolveOut O) {
+    const uint32_t r = blockIdx.x * kThreads + threadIdx.x;
+    if (r >= n_reads) return;
+    uint32_t st = O.status[r];
+    double a = 0.0, b = 0.0;
+    if (st == PG_FIT_OK) {
+        const PgFitSums s = sums[r];
+        const PgFitSolve v = pg_fit_solve_hd(s, min_events);
+        st = v.status;
+        if (st == PG_FIT_TOO_LONG) sums[r] = PgFitSums{s.n, 0, 0, 0, 0, 0, s.e};
+        if (st == PG_FIT_OK) { a = v.a; b = v.b; }
+    }
+    const PgFitScale c = pg_fit_scale_rule(st, a, b, dig[r], off[r], range[r]);
+    O.status[r] = st; O.a[r] = a; O.b[r] = b; O.center[r] = c.center; O.spread[r] = c.spread; O.use[r] = c.use;
+}
+
+// what a calibration reports of its reads without bringing them back: tally[0 .. 6] reads per status, [7] reads with a skip code, [8] reads
+// with use set. One workgroup; its threads stride over the reads.
+constexpr uint32_t kTally = 9;
+__global__ __launch_bounds__(kThreads) void k_fit_tally(uint32_t n_reads, const uint32_t *__restrict__ status, const uint8_t *__restrict__ use, u64 *__restrict__ tally) {
+    __shared__ uint32_t cnt[kTally];
+    if (threadIdx.x < kTally) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    uint32_t mine[kTally] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (uint32_t r = threadIdx.x; r < n_reads; r += kThreads) {
+        const uint32_t st = status[r], slot = st < 7u ? st : 7u;
+#pragma unroll
+        for (uint32_t i = 0; i < 8; i++) mine[i] += slot == i ? 1u : 0u;
+        mine[8] += use[r] ? 1u : 0u;
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < kTally; i++)
+        if (mine[i]) atomicAdd(&cnt[i], mine[i]);
+    __syncthreads();
+    if (threadIdx.x < kTally) tally[threadIdx.x] = cnt[threadIdx.x];
+}
+
 } // namespace
 
 struct pg_fit {
@@ -116,7 +158,7 @@ struct pg_fit {
     pg_fit_params prm{};
     PgStream own;
     hipStream_t s = nullptr;
-    PgEvent ev[4];
+    PgEvent ev[4], ev_solve[2];
     uint32_t k = 0;
     uint64_t n_slots = 0;
     bool dirty = false; // a submit since the last finish
@@ -128,6 +170,11 @@ struct pg_fit {
     PgDev<u64> d_rsums, d_tab, d_counters;
     PgDev<double> d_ab;
     PgDev<uint32_t> d_flag;
+    // pg_fit_calibrate: the arrays it hands out, the staged calibration of a host batch
+    PgDev<uint32_t> d_status;
+    PgDev<double> d_a, d_b, d_center, d_spread, d_dig, d_off, d_range;
+    PgDev<uint8_t> d_use;
+    PgDev<u64> d_tally;
     std::vector<uint64_t> sig_off, seq_off, op_off, psum, pstart, pcsum, pcol, tab;
     std::vector<int32_t> qs;
     std::vector<uint32_t> piece_read, piece_first, status;
@@ -157,6 +204,7 @@ pg_status pg_fit_create(const pg_fit_params *p, int32_t device, pg_fit **out) {
     h->device = device; h->prm = *p;
     hipError_t e = hipStreamCreateWithFlags(&h->own.h, hipStreamNonBlocking);
     for (int i = 0; i < 4 && e == hipSuccess; i++) e = hipEventCreate(&h->ev[i].h);
+    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipEventCreate(&h->ev_solve[i].h);
     if (e != hipSuccess) {
         pg_fail(h, PG_ERR_HIP, "pg_fit_create: %s", hipGetErrorString(e));
         return pg_create_failed(h, PG_ERR_HIP, pg_fit_destroy);
@@ -209,18 +257,63 @@ pg_status pg_fit_set_model(pg_fit *h, const uint32_t *levels, uint32_t k) {
     return PG_OK;
 }
 
-pg_status pg_fit_submit(pg_fit *h, const pg_batch *b, const uint32_t *skip, pg_fit_reads *out) {
-    if (!h) return pg_fail<pg_fit>(nullptr, PG_ERR_INVALID_ARG, "pg_fit_submit: null handle");
-    if (!b || !out) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: null argument");
-    memset(out, 0, sizeof *out);
-    if (!h->k) return pg_fail(h, PG_ERR_STATE, "pg_fit_submit: no model (pg_fit_set_model)");
-    if (b->struct_size != sizeof(pg_batch)) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: pg_batch.struct_size %u, this library has %zu", b->struct_size, sizeof(pg_batch));
-    if (b->location != PG_LOC_HOST && b->location != PG_LOC_DEVICE) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: location must be PG_LOC_HOST or PG_LOC_DEVICE");
+} // extern "C"
+
+// The tail of pg_fit_calibrate, behind pass 1 on the handle's stream: the statuses the host has settled go up, k_fit_solve and k_fit_tally
+// run, and nine counters come back.
+static pg_status fit_solve_device(pg_fit *h, const pg_batch *b, uint64_t n, pg_fit_scaling *cal) {
+    const hipStream_t s = h->s;
+    auto room = [](size_t bytes) { return bytes + bytes / 4 + 256; };
+#define CAL_ENSURE(buf, bytes) PG_HIP_TRY(h, (buf).ensure((bytes) ? (bytes) : 1, room(bytes)))
+    CAL_ENSURE(h->d_status, n * 4); CAL_ENSURE(h->d_a, n * 8); CAL_ENSURE(h->d_b, n * 8); CAL_ENSURE(h->d_center, n * 8); CAL_ENSURE(h->d_spread, n * 8); CAL_ENSURE(h->d_use, n);
+    PG_HIP_TRY(h, h->d_tally.ensure(kTally * sizeof(u64)));
+    const double *dig = b->digitisation, *off = b->offset, *range = b->range;
+    if (n && b->location == PG_LOC_DEVICE) {
+        for (const void *q : {(const void *)dig, (const void *)off, (const void *)range})
+            if (pg_ptr_kind(q, h->device) != PG_PTR_DEVICE) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_calibrate: PG_LOC_DEVICE arrays must be device memory of device %d", h->device);
+    } else if (n) {
+        CAL_ENSURE(h->d_dig, n * 8); CAL_ENSURE(h->d_off, n * 8); CAL_ENSURE(h->d_range, n * 8);
+        PG_HIP_TRY(h, hipMemcpyAsync(h->d_dig.p, dig, n * 8, hipMemcpyHostToDevice, s));
+        PG_HIP_TRY(h, hipMemcpyAsync(h->d_off.p, off, n * 8, hipMemcpyHostToDevice, s));
+        PG_HIP_TRY(h, hipMemcpyAsync(h->d_range.p, range, n * 8, hipMemcpyHostToDevice, s));
+        dig = h->d_dig.p; off = h->d_off.p; range = h->d_range.p;
+    }
+#undef CAL_ENSURE
+    u64 tally[kTally] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (n) {
+        PG_HIP_TRY(h, hipMemcpyAsync(h->d_status.p, h->status.data(), n * 4, hipMemcpyHostToDevice, s));
+        PG_HIP_TRY(h, hipEventRecord(h->ev_solve[0], s));
+        const FitSolveOut O{h->d_status.p, h->d_a.p, h->d_b.p, h->d_center.p, h->d_spread.p, h->d_use.p};
+        hipLaunchKernelGGL(k_fit_solve, dim3((uint32_t)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, (uint32_t)n, h->prm.min_events, reinterpret_cast<PgFitSums *>(h->d_rsums.p),
+                           dig, off, range, O);
+        PG_HIP_TRY(h, hipGetLastError());
+        hipLaunchKernelGGL(k_fit_tally, dim3(1), dim3(kThreads), 0, s, (uint32_t)n, h->d_status.p, h->d_use.p, h->d_tally.p);
+        PG_HIP_TRY(h, hipGetLastError());
+        PG_HIP_TRY(h, hipEventRecord(h->ev_solve[1], s));
+        PG_HIP_TRY(h, hipMemcpyAsync(tally, h->d_tally.p, sizeof tally, hipMemcpyDeviceToHost, s));
+        PG_HIP_TRY(h, hipStreamSynchronize(s));
+        float ms = 0; PG_HIP_TRY(h, hipEventElapsedTime(&ms, h->ev_solve[0], h->ev_solve[1])); cal->solve_ms = ms;
+    }
+    cal->n_reads = n; cal->n_ok = tally[8];
+    for (uint32_t i = 0; i < 8; i++) cal->n_status[i] = tally[i];
+    cal->d_sums = reinterpret_cast<const pg_fit_sums *>(h->d_rsums.p); cal->d_status = h->d_status.p; cal->d_a = h->d_a.p; cal->d_b = h->d_b.p;
+    cal->d_center = h->d_center.p; cal->d_spread = h->d_spread.p; cal->d_use = h->d_use.p;
+    return PG_OK;
+}
+
+// pg_fit_submit (out) and pg_fit_calibrate (cal): one of the two. Both check the batch, lay out its pieces and run pass 1; the submit then
+// solves on the host and runs pass 2, the calibration leaves the sums where they are and solves on the device (k_fit_solve).
+#define FIT_FAIL(st, fmt, ...) pg_fail(h, st, "%s: " fmt, who, ##__VA_ARGS__)
+static pg_status fit_run(pg_fit *h, const pg_batch *b, const uint32_t *skip, pg_fit_reads *out, pg_fit_scaling *cal) {
+    const char *who = cal ? "pg_fit_calibrate" : "pg_fit_submit";
+    if (!h->k) return FIT_FAIL(PG_ERR_STATE, "no model (pg_fit_set_model)");
+    if (b->struct_size != sizeof(pg_batch)) return FIT_FAIL(PG_ERR_INVALID_ARG, "pg_batch.struct_size %u, this library has %zu", b->struct_size, sizeof(pg_batch));
+    if (b->location != PG_LOC_HOST && b->location != PG_LOC_DEVICE) return FIT_FAIL(PG_ERR_INVALID_ARG, "location must be PG_LOC_HOST or PG_LOC_DEVICE");
     const bool gapped = (b->flags & PG_BATCH_GAPPED) != 0;
-    if (gapped && (b->flags & PG_BATCH_ALL_MATCHES)) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: a batch carries PG_BATCH_GAPPED or PG_BATCH_ALL_MATCHES, not both");
-    if (!gapped && !(b->flags & PG_BATCH_ALL_MATCHES)) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: the batch must carry PG_BATCH_ALL_MATCHES (every op a match, as `reform` writes them)");
+    if (gapped && (b->flags & PG_BATCH_ALL_MATCHES)) return FIT_FAIL(PG_ERR_INVALID_ARG, "a batch carries PG_BATCH_GAPPED or PG_BATCH_ALL_MATCHES, not both");
+    if (!gapped && !(b->flags & PG_BATCH_ALL_MATCHES)) return FIT_FAIL(PG_ERR_INVALID_ARG, "the batch must carry PG_BATCH_ALL_MATCHES (every op a match, as `reform` writes them)");
     const uint64_t n = b->n_reads;
-    if (!b->sig_off || !b->seq_off || !b->op_off || (n && !b->query_start)) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: null array");
+    if (!b->sig_off || !b->seq_off || !b->op_off || (n && !b->query_start)) return FIT_FAIL(PG_ERR_INVALID_ARG, "null array");
     PG_HIP_TRY(h, hipSetDevice(h->device));
     const hipStream_t s = h->s;
     const bool dev = b->location == PG_LOC_DEVICE;
@@ -229,7 +322,7 @@ pg_status pg_fit_submit(pg_fit *h, const pg_batch *b, const uint32_t *skip, pg_f
     if (dev) {
         const void *must[] = {b->sig_off, b->seq_off, b->op_off, n ? (const void *)b->query_start : nullptr};
         for (const void *q : must)
-            if (q && pg_ptr_kind(q, h->device) != PG_PTR_DEVICE) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: PG_LOC_DEVICE arrays must be device memory of device %d", h->device);
+            if (q && pg_ptr_kind(q, h->device) != PG_PTR_DEVICE) return FIT_FAIL(PG_ERR_INVALID_ARG, "PG_LOC_DEVICE arrays must be device memory of device %d", h->device);
         PG_HIP_TRY(h, hipMemcpyAsync(h->sig_off.data(), b->sig_off, (n + 1) * 8, hipMemcpyDeviceToHost, s));
         PG_HIP_TRY(h, hipMemcpyAsync(h->seq_off.data(), b->seq_off, (n + 1) * 8, hipMemcpyDeviceToHost, s));
         PG_HIP_TRY(h, hipMemcpyAsync(h->op_off.data(), b->op_off, (n + 1) * 8, hipMemcpyDeviceToHost, s));
@@ -242,29 +335,29 @@ pg_status pg_fit_submit(pg_fit *h, const pg_batch *b, const uint32_t *skip, pg_f
     h->piece_first.resize(n + 1); h->piece_read.clear();
     for (uint64_t r = 0; r < n; r++) {
         if (h->sig_off[r + 1] < h->sig_off[r] || h->seq_off[r + 1] < h->seq_off[r] || h->op_off[r + 1] < h->op_off[r])
-            return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: an offset array decreases at read %llu", (unsigned long long)r);
+            return FIT_FAIL(PG_ERR_INVALID_ARG, "an offset array decreases at read %llu", (unsigned long long)r);
         const uint64_t lb = h->op_off[r + 1] - h->op_off[r];
         const bool skipped = skip && skip[r];
-        if (skipped && skip[r] >= (1u << 16)) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: skip code %u of read %llu (below 2^16)", skip[r], (unsigned long long)r);
-        if (lb > 0x7fffffffull) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: read %llu has %llu ops (at most 2^31 - 1)", (unsigned long long)r, (unsigned long long)lb);
+        if (skipped && skip[r] >= (1u << 16)) return FIT_FAIL(PG_ERR_INVALID_ARG, "skip code %u of read %llu (below 2^16)", skip[r], (unsigned long long)r);
+        if (lb > 0x7fffffffull) return FIT_FAIL(PG_ERR_INVALID_ARG, "read %llu has %llu ops (at most 2^31 - 1)", (unsigned long long)r, (unsigned long long)lb);
         if (gapped && h->seq_off[r + 1] - h->seq_off[r] > PG_FIT_MAX_SLICE)
-            return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: read %llu has a reference slice of %llu bases (at most 2^32 - 1)", (unsigned long long)r,
+            return FIT_FAIL(PG_ERR_INVALID_ARG, "read %llu has a reference slice of %llu bases (at most 2^32 - 1)", (unsigned long long)r,
                            (unsigned long long)(h->seq_off[r + 1] - h->seq_off[r]));
         if (!gapped && !skipped && h->seq_off[r + 1] - h->seq_off[r] < lb)
-            return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: read %llu has %llu ops and %llu bases (an accepted read has as many bases as ops)", (unsigned long long)r,
+            return FIT_FAIL(PG_ERR_INVALID_ARG, "read %llu has %llu ops and %llu bases (an accepted read has as many bases as ops)", (unsigned long long)r,
                            (unsigned long long)lb, (unsigned long long)(h->seq_off[r + 1] - h->seq_off[r]));
         h->piece_first[r] = (uint32_t)h->piece_read.size();
         const uint64_t np = skipped ? 0 : (lb + kPiece - 1) / kPiece;
-        if (h->piece_read.size() + np > 0x7fffffffull) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: batch too large");
+        if (h->piece_read.size() + np > 0x7fffffffull) return FIT_FAIL(PG_ERR_INVALID_ARG, "batch too large");
         h->piece_read.insert(h->piece_read.end(), np, (uint32_t)r);
     }
     h->piece_first[n] = (uint32_t)h->piece_read.size();
     const size_t n_pieces = h->piece_read.size();
     const uint64_t n_sig = h->sig_off[n], n_seq = h->seq_off[n], n_ops = h->op_off[n];
     if (n_sig - h->sig_off[0] > PG_FIT_BATCH_SAMPLES)
-        return pg_fail(h, PG_ERR_UNSUPPORTED, "pg_fit_submit: %llu samples of signal in one batch (at most 2^28: submit fewer reads at a time)", (unsigned long long)(n_sig - h->sig_off[0]));
-    if (dev && b->n_ops && b->n_ops != n_ops) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: pg_batch.n_ops is %u, op_off ends at %llu", b->n_ops, (unsigned long long)n_ops);
-    if ((n_sig && !b->sig) || (n_seq && !b->seq) || (n_ops && (!b->op_n || !b->op_t))) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: null array");
+        return FIT_FAIL(PG_ERR_UNSUPPORTED, "%llu samples of signal in one batch (at most 2^28: submit fewer reads at a time)", (unsigned long long)(n_sig - h->sig_off[0]));
+    if (dev && b->n_ops && b->n_ops != n_ops) return FIT_FAIL(PG_ERR_INVALID_ARG, "pg_batch.n_ops is %u, op_off ends at %llu", b->n_ops, (unsigned long long)n_ops);
+    if ((n_sig && !b->sig) || (n_seq && !b->seq) || (n_ops && (!b->op_n || !b->op_t))) return FIT_FAIL(PG_ERR_INVALID_ARG, "null array");
 
     FitBatch B{};
     B.n_reads = (uint32_t)n; B.n_pieces = (uint32_t)n_pieces; B.k = h->k; B.m = h->prm.sig_move_offset; B.rna = h->prm.rna ? 1 : 0; B.min_dur = h->prm.min_dur; B.max_dur = h->prm.max_dur;
@@ -275,7 +368,7 @@ pg_status pg_fit_submit(pg_fit *h, const pg_batch *b, const uint32_t *skip, pg_f
     if (dev) {
         const void *must[] = {n_sig ? (const void *)b->sig : nullptr, n_seq ? (const void *)b->seq : nullptr, n_ops ? (const void *)b->op_n : nullptr, n_ops ? (const void *)b->op_t : nullptr};
         for (const void *q : must)
-            if (q && pg_ptr_kind(q, h->device) != PG_PTR_DEVICE) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: PG_LOC_DEVICE arrays must be device memory of device %d", h->device);
+            if (q && pg_ptr_kind(q, h->device) != PG_PTR_DEVICE) return FIT_FAIL(PG_ERR_INVALID_ARG, "PG_LOC_DEVICE arrays must be device memory of device %d", h->device);
         B.sig = b->sig; B.sig_off = b->sig_off; B.seq = b->seq; B.seq_off = b->seq_off; B.op_n = b->op_n; B.op_t = b->op_t; B.op_off = b->op_off;
     } else {
         FIT_ENSURE(h->d_sig, n_sig * 2); FIT_ENSURE(h->d_seq, n_seq); FIT_ENSURE(h->d_opn, n_ops * 4); FIT_ENSURE(h->d_opt, n_ops);
@@ -313,8 +406,8 @@ pg_status pg_fit_submit(pg_fit *h, const pg_batch *b, const uint32_t *skip, pg_f
         if (gapped) PG_HIP_TRY(h, hipMemcpyAsync(h->pcsum.data(), h->d_pcsum.p, n_pieces * 8, hipMemcpyDeviceToHost, s));
         PG_HIP_TRY(h, hipMemcpyAsync(&flag, h->d_flag.p, sizeof flag, hipMemcpyDeviceToHost, s));
         PG_HIP_TRY(h, hipStreamSynchronize(s));
-        if (gapped && (flag & 2u)) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: the batch carries PG_BATCH_GAPPED but holds an op code above 2 (0 match, 1 I, 2 D)");
-        if (!gapped && flag) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: the batch carries PG_BATCH_ALL_MATCHES but holds an op that is no match (an I, a D or an unknown op)");
+        if (gapped && (flag & 2u)) return FIT_FAIL(PG_ERR_INVALID_ARG, "the batch carries PG_BATCH_GAPPED but holds an op code above 2 (0 match, 1 I, 2 D)");
+        if (!gapped && flag) return FIT_FAIL(PG_ERR_INVALID_ARG, "the batch carries PG_BATCH_ALL_MATCHES but holds an op that is no match (an I, a D or an unknown op)");
     }
     // ---- every piece's first sample (gapped: and first column); a read whose ops leave its samples takes no part, nor does a gapped read
     // whose slice has not as many bases as its ops have columns: no kernel reads its seq
@@ -344,10 +437,13 @@ pg_status pg_fit_submit(pg_fit *h, const pg_batch *b, const uint32_t *skip, pg_f
         else hipLaunchKernelGGL(k_fit_sums<false>, dim3(blocks), dim3(kThreads), 0, s, B, h->d_rsums.p);
         PG_HIP_TRY(h, hipGetLastError());
         PG_HIP_TRY(h, hipEventRecord(h->ev[1], s));
-        PG_HIP_TRY(h, hipMemcpyAsync(h->sums.data(), h->d_rsums.p, n * sizeof(pg_fit_sums), hipMemcpyDeviceToHost, s));
-        PG_HIP_TRY(h, hipStreamSynchronize(s));
-        float ms = 0; PG_HIP_TRY(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1])); h->ms[0] += ms;
-    }
+        if (!cal) {
+            PG_HIP_TRY(h, hipMemcpyAsync(h->sums.data(), h->d_rsums.p, n * sizeof(pg_fit_sums), hipMemcpyDeviceToHost, s));
+            PG_HIP_TRY(h, hipStreamSynchronize(s));
+            float ms = 0; PG_HIP_TRY(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1])); h->ms[0] += ms;
+        }
+    } else if (cal && n) PG_HIP_TRY(h, hipMemsetAsync(h->d_rsums.p, 0, n * sizeof(pg_fit_sums), s));
+    if (cal) return fit_solve_device(h, b, n, cal);
     // ---- the solve
     h->a.assign(n, 0.0); h->b.assign(n, 0.0); h->ab.assign(2 * n, 0.0);
     uint64_t fitted = 0;
@@ -392,6 +488,25 @@ pg_status pg_fit_submit(pg_fit *h, const pg_batch *b, const uint32_t *skip, pg_f
     h->reads += n; h->fitted += fitted; h->dirty = true;
     out->n_reads = n; out->sums = h->sums.data(); out->status = h->status.data(); out->a = h->a.data(); out->b = h->b.data();
     return PG_OK;
+}
+#undef FIT_FAIL
+
+extern "C" {
+
+pg_status pg_fit_submit(pg_fit *h, const pg_batch *b, const uint32_t *skip, pg_fit_reads *out) {
+    if (!h) return pg_fail<pg_fit>(nullptr, PG_ERR_INVALID_ARG, "pg_fit_submit: null handle");
+    if (!b || !out) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_submit: null argument");
+    memset(out, 0, sizeof *out);
+    return fit_run(h, b, skip, out, nullptr);
+}
+
+pg_status pg_fit_calibrate(pg_fit *h, const pg_batch *b, const uint32_t *skip, pg_fit_scaling *out) {
+    if (!h) return pg_fail<pg_fit>(nullptr, PG_ERR_INVALID_ARG, "pg_fit_calibrate: null handle");
+    if (!b || !out) return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_calibrate: null argument");
+    memset(out, 0, sizeof *out);
+    if (b->struct_size == sizeof(pg_batch) && b->n_reads && (!b->digitisation || !b->offset || !b->range))
+        return pg_fail(h, PG_ERR_INVALID_ARG, "pg_fit_calibrate: digitisation, offset and range are required");
+    return fit_run(h, b, skip, nullptr, out);
 }
 
 pg_status pg_fit_finish(pg_fit *h, pg_fit_result *out) {

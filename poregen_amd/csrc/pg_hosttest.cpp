@@ -644,6 +644,27 @@ extern "C" int pgt_fit_solve(const int64_t *sums7, uint32_t min_events, double d
     }
     return (int)v.status;
 }
+// the hand-written conversion of lo + 2^64 hi (two's complement) and, in native, the compiler's own
+extern "C" double pgt_fit_i128_to_double(uint64_t lo, uint64_t hi, double *native) {
+    const __int128 v = (__int128)(((unsigned __int128)hi << 64) | lo);
+    if (native) *native = (double)v;
+    return pg_fit_i128_to_double(v);
+}
+// pg_fit_solve_hd: the status; a, b and 1 / b; and the collector's center, spread (out5[3], out5[4]) and use by the rule of pg_fit.h
+extern "C" int pgt_fit_solve_hd(const int64_t *sums7, uint32_t min_events, double dig, double off, double range, double *out5, int *use) {
+    PgFitSums s; memcpy(&s, sums7, sizeof s);
+    const PgFitSolve v = pg_fit_solve_hd(s, min_events);
+    const PgFitScale sc = pg_fit_scale_rule(v.status, v.a, v.b, dig, off, range);
+    out5[0] = v.a; out5[1] = v.b; out5[2] = v.inv_b; out5[3] = sc.center; out5[4] = sc.spread;
+    if (use) *use = sc.use;
+    return (int)v.status;
+}
+// the rule alone, for any status, a and b
+extern "C" int pgt_fit_scale_rule(uint32_t status, double a, double b, double dig, double off, double range, double *out2) {
+    const PgFitScale sc = pg_fit_scale_rule(status, a, b, dig, off, range);
+    out2[0] = sc.center; out2[1] = sc.spread;
+    return sc.use;
+}
 extern "C" int pgt_fit_resid(int r, double a, double inv_b, int l, int *clamped) { bool c; const int32_t d = pg_fit_resid(r, a, inv_b, l, c); *clamped = c; return d; }
 // the two residual columns of a slot as the k-mer table prints them
 extern "C" void pgt_fit_resid_text(uint64_t n, int64_t sum_d, uint64_t dd_lo, uint64_t dd_hi, char *mean, char *rms, size_t cap) {

@@ -332,6 +332,11 @@ hipError_t pg_launch_events(hipStream_t st, const PgDevBatch &B, const PgWalkPar
                             uint32_t part_hi_bits, uint32_t part_lo_bits, const PgFront &F = PgFront{}, int pass = PG_PASS_WHOLE);
 // SAM/BAM front-end: reads with an out-of-range sample become skipped reads (behind the statistics, in front of the walk)
 hipError_t pg_launch_apply_oor(hipStream_t st, const PgDevBatch &B, const PgWalkOut &O);
+// PG_SCALING_PER_READ (pg_scale.hip): the caller's center / spread / use [n_reads] (device memory) into the slot's gcal records, med / mad
+// and oor; div_flag: the slot's statistics flag [3] (the dense gathers then divide with the instruction); bad: one word, the lowest read
+// whose scaling is refused, 0xffffffff for none
+hipError_t pg_launch_scale_records(hipStream_t st, const PgDevBatch &B, const double *center, const double *spread, const uint8_t *use, double *gcal, double *med, double *mad,
+                                   uint8_t *oor, int32_t *div_flag, uint32_t *bad);
 // direct ranking (n_slots <= PG_DIRECT_MAX_SLOTS): tile prefix of the per-tile per-slot counts pg_launch_events left in S.hist;
 // acc_cnt = events per slot
 hipError_t pg_launch_rank_direct_count(hipStream_t st, const uint32_t *ev_slot, uint64_t n, uint32_t n_slots, const PgSortBufs &S,

@@ -177,6 +177,8 @@ pg_status pg_job_create(const pg_params *p, const int32_t *devices, uint32_t n, 
     if (!p || !devices || !out || n == 0 || n > 64) return pg_fail<pg_job>(nullptr, PG_ERR_INVALID_ARG, "pg_job_create: params / devices / n_devices (1..64)");
     *out = nullptr;
     if (exchange > PG_JOB_EXCHANGE_RCCL) return pg_fail<pg_job>(nullptr, PG_ERR_INVALID_ARG, "pg_job_create: unknown exchange mode %u", exchange);
+    if (p->struct_size == sizeof(pg_params) && p->scaling == PG_SCALING_PER_READ)
+        return pg_fail<pg_job>(nullptr, PG_ERR_UNSUPPORTED, "pg_job_create: scaling 2 (PG_SCALING_PER_READ) is a single-device collector's; a job has no per-read scaling to hand to its ranks");
     bool distinct = true;
     for (uint32_t a = 0; a < n; ++a) for (uint32_t b = a + 1; b < n; ++b) if (devices[a] == devices[b]) distinct = false;
     bool want_rccl = exchange == PG_JOB_EXCHANGE_RCCL || (exchange == PG_JOB_EXCHANGE_AUTO && distinct);

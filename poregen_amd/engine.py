@@ -337,14 +337,33 @@ class GmoveEngine:
     def _c_batch(self, b: Batch):
         return _c_batch(b)
 
-    def submit(self, b: Batch):
-        self._keep = b
+    def _set_read_scaling(self, b: Batch, scaling):
+        """scaling: a ReadScaling (ModelFit.calibrate) or (center, spread, use), three numpy arrays or three CUDA tensors of b.n_reads
+        entries: the per-read scaling of the batch about to be counted, for an engine made with scaling=2 (pg_set_read_scaling)."""
+        if scaling is None:
+            return None
+        c, s, u = (scaling.center, scaling.spread, scaling.use) if hasattr(scaling, "center") else scaling
+        host = isinstance(c, np.ndarray) or not hasattr(c, "data_ptr")
+        if host:
+            c, s, u = np.ascontiguousarray(c, dtype=np.float64), np.ascontiguousarray(s, dtype=np.float64), np.ascontiguousarray(u, dtype=np.uint8)
+            sizes = (c.size, s.size, u.size)
+        else:
+            import torch
+            c, s, u = c.contiguous().to(torch.float64), s.contiguous().to(torch.float64), u.contiguous().to(torch.uint8)
+            sizes = (c.numel(), s.numel(), u.numel())
+        if sizes != (b.n_reads,) * 3:
+            raise ValueError("scaling needs one center, spread and use per read of the batch")
+        self._check(self._lib.pg_set_read_scaling(self._h, C.c_void_p(_ptr(c)), C.c_void_p(_ptr(s)), C.c_void_p(_ptr(u)), _abi.PG_LOC_HOST if host else _abi.PG_LOC_DEVICE))
+        return (c, s, u, scaling)
+
+    def submit(self, b: Batch, scaling=None):
+        self._keep = (b, self._set_read_scaling(b, scaling))
         self._check(self._lib.pg_submit(self._h, C.byref(self._c_batch(b))))
 
-    def count(self, b: Batch, out=None):
+    def count(self, b: Batch, out=None, scaling=None):
         """Phase 1. Returns the per-slot accepted-event counts of this batch (uncapped): a numpy uint64
         array, or fills `out` (a torch int64 CUDA tensor) in place when given."""
-        self._keep = b
+        self._keep = (b, self._set_read_scaling(b, scaling))
         if out is None:
             res = np.empty(self.n_slots, dtype=np.uint64)
             self._check(self._lib.pg_count(self._h, C.byref(self._c_batch(b)), res.ctypes.data, _abi.PG_LOC_HOST))
@@ -2006,6 +2025,31 @@ def _fit_residuals(n, sum_d, sum_dd):
     return int(m.value), int(q.value)
 
 
+class ReadScaling:
+    """What ModelFit.calibrate leaves on the device for a batch of n_reads reads: sums (int64[n, 7]), status (int32, PG_FIT_ST_*), a, b,
+    center, spread (float64) and use (uint8) as CUDA tensors; n_ok reads have use set, n_status[s] reads have status s (index 7: a skip
+    code); solve_ms is the HIP-event time of the solve."""
+
+    def __init__(self, res, device):
+        import torch
+
+        class _Alias:  # zero-copy hand-over through the CUDA array interface
+            def __init__(self, ptr, shape, typestr):
+                self.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (int(ptr or 0), False), "version": 2}
+
+        dev = torch.device("cuda", device)
+        n = self.n_reads = int(res.n_reads)
+        self.n_ok, self.n_status, self.solve_ms = int(res.n_ok), [int(v) for v in res.n_status], float(res.solve_ms)
+
+        def view(ptr, shape, typestr, dtype):
+            return torch.as_tensor(_Alias(ptr, shape, typestr), device=dev) if n else torch.empty(shape, dtype=dtype, device=dev)
+        self.sums = view(res.d_sums, (n, 7), "<i8", torch.int64)
+        self.status = view(res.d_status, (n,), "<i4", torch.int32)
+        self.a, self.b = view(res.d_a, (n,), "<f8", torch.float64), view(res.d_b, (n,), "<f8", torch.float64)
+        self.center, self.spread = view(res.d_center, (n,), "<f8", torch.float64), view(res.d_spread, (n,), "<f8", torch.float64)
+        self.use = view(res.d_use, (n,), "|u1", torch.uint8)
+
+
 class ModelFit:
     """Scores a k-mer model against batches laid out as MoveExpander leaves them (pg_fit_*): submit() fits every read, finish() returns the
     per-k-mer residual sums. levels: uint32[4^k] in 1e-3 pA, 0 for a k-mer without a level."""
@@ -2052,6 +2096,17 @@ class ModelFit:
                 return np.zeros(0, dt)
             return np.frombuffer((C.c_char * (count * np.dtype(dt).itemsize)).from_address(ptr), dtype=dt).copy()
         return FitReads(sums=arr(out.sums, 7 * n, np.int64).reshape(n, 7), status=arr(out.status, n, np.uint32), a=arr(out.a, n, np.float64), b=arr(out.b, n, np.float64))
+
+    def calibrate(self, batch: "Batch", skip=None) -> "ReadScaling":
+        """One batch as submit() takes it, put on the model's pA scale (pg_fit_calibrate): pass 1, then the solve on the device and per
+        read center = (a + offset) * g, spread = (b * 1000) * g with g = range / digitisation, use = the fit is ok and both are usable.
+        Runs no pass 2 and adds nothing to finish(). The result's tensors alias the handle's device buffers (valid until its next
+        submit / calibrate / close); GmoveEngine(scaling=2).submit(batch, scaling=...) takes it."""
+        cb = _c_batch(batch)
+        sk = None if skip is None else np.ascontiguousarray(skip, dtype=np.uint32)
+        out = _abi.PgFitScaling()
+        self._check(self._lib.pg_fit_calibrate(self._h, C.byref(cb), None if sk is None else sk.ctypes.data, C.byref(out)))
+        return ReadScaling(out, self.device)
 
     def finish(self) -> FitResult:
         r = _abi.PgFitResult()
