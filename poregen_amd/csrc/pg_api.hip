@@ -65,7 +65,8 @@ struct pg_ctx {
     PgStream st2, own_st;
     PgEvent ev_fork;
     PgEvent ev_join[2], ev_gathered[2]; // per statistics slot
-    bool slot_used[2] = {false, false}; // crosses batches: a gather has read this slot's buffers (ev_gathered is recorded)
+    bool slot_used[2] = {false, false}; // crosses batches: a gather has read this slot's buffers
+    bool slot_recorded[2] = {false, false}; // ... and ev_gathered[slot] stands behind the last such gather (that batch used the statistics stream)
     PgPinned<PgSettlePack> settle_host; // host-mapped: what settle_batch learns of a finished batch, packed by one launch (k_settle_pack)
     int slot = 0; // statistics buffers are double-buffered so that batch i+1's statistics overlap batch i's tail: flips with every batch
     bool user_stream = false, batch_is_host = false;
@@ -912,8 +913,11 @@ static pg_status count_impl(pg_ctx *c, const pg_batch *b, uint64_t *counts_out, 
             PG_HIP_TRY(c, hipEventRecord(c->ev_fork, c->st));
             PG_HIP_TRY(c, hipStreamWaitEvent(c->st2, c->ev_fork, 0));
         }
-        // ... and the buffers of this slot to be free: the gather of the batch that used them two batches ago
-        if (c->slot_used[c->slot]) PG_HIP_TRY(c, hipStreamWaitEvent(c->st2, c->ev_gathered[c->slot], 0));
+        // ... and the buffers of this slot to be free: the gather of the batch that used them two batches ago. If that was a one-stream batch,
+        // its gather recorded nothing (pg_collect), and nothing is needed: the first two-stream batch behind a one-stream batch has made the
+        // statistics stream wait for ev_fork above, which stands behind every gather queued until then, and everything this stream has
+        // been given since is behind that wait by the stream's own order.
+        if (c->slot_used[c->slot] && c->slot_recorded[c->slot]) PG_HIP_TRY(c, hipStreamWaitEvent(c->st2, c->ev_gathered[c->slot], 0));
     }
     // Not per-job state: pg_reset does not clear it, because it waits for nothing -- the one-stream batch of the job in front may still be
     // running when the next job's first batch is queued. pg_set_stream, which waits for both streams, does. Left set by a pg_count that
@@ -1265,8 +1269,10 @@ static pg_status collect_impl(pg_ctx *c, const uint64_t *base, int32_t base_loca
     prof_end(c, c->st);
     // "this slot's statistics buffers have been read": for the statistics stream two batches on. With one stream nobody waits for it, and a
     // record ends the gather with 4.6 us in which the stream starts nothing (rocprofv3 kernel trace, tools/trace_gaps.py: every other
-    // kernel-to-kernel gap of the chain is 0.0 us).
-    if (c->st2) PG_HIP_TRY(c, hipEventRecord(c->ev_gathered[c->slot], c->st));
+    // kernel-to-kernel gap of the chain is 0.0 us). The same holds for a one-stream batch of a two-stream context: the statistics stream
+    // next touches this slot in a two-stream batch, and the first of those behind a one-stream batch waits for ev_fork (pg_count).
+    c->slot_recorded[c->slot] = c->st2 && pg_stats_on_second_stream(c->bt.plan.place);
+    if (c->slot_recorded[c->slot]) PG_HIP_TRY(c, hipEventRecord(c->ev_gathered[c->slot], c->st));
     PG_TMARK("collect: buffers + kernels queued");
     if (timing_on()) { PG_HIP_TRY(c, hipStreamSynchronize(c->st)); PG_TMARK("collect: kernels done (sync)"); }
     c->slot_used[c->slot] = true;
